@@ -13,12 +13,20 @@ process, before torch is imported or the GPU touched -- relays their output and 
 code.  Started by a launcher (WORLD_SIZE set) it is one rank; WORLD_SIZE != --gpus is an error.
 The SAME gallery is sharded over the ranks (strong scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task description): metric/value/unit, `roofline`
-(dominant kernel = the 16-bit MFMA scoring kernel, HIP-event timed inside the timed region),
-`cpu_baseline` (the oracle's matching_L2 restatement timed on a bounded sample on the host) and
+Prints ONE JSON line on rank 0 (contract in the task description): metric/value/unit/ms_per_step and
+`roofline` (dominant kernel = the 16-bit MFMA scoring kernel, HIP-event timed inside the timed region).
+A plain run does nothing else: set-up, warm-up, the `--steps` timed steps, `--dump-outputs`, the line.
+
+`--full` adds what else the benchmark measures and checks, in the same process after the headline:
+the result checks of the last batch against float64, the ingest and stateless-call figures, the
+same steps with the synchronous tail (`synchronous`; the headline is then the faster of the two
+modes), `cpu_baseline` (the oracle's matching_L2 restatement timed on a bounded sample on the host),
 `scale_10m`: BASELINE configs[3] -- a synthetic 10,000,000 x 2048 gallery with a bf16 image,
-row-sharded 1 x N over the same ranks with the RCCL all-gathers of the per-shard top-K -- measured
-in the same process after the headline (10 steps).
+row-sharded 1 x N over the same ranks with the RCCL all-gathers of the per-shard top-K (10 steps) --
+and the other blocks (small batches, online, mAP, whitening, structured data, alpha-QE, multi-GPU).
+
+`--dump-outputs DIR` writes what the timed path returned for its last step (DIR/indices.npy as
+float64, DIR/scores.npy as float32); the inputs are a pure function of the arguments.
 """
 import argparse
 import json
@@ -116,7 +124,17 @@ def parse():
                          "online_concurrent, hard_data, whiten, cpu_baseline, scale_10m, map, aqe_rparis_1m, qge_small, dropin); "
                          "default: all of them.  For iterating on one block on a GPU box")
     ap.add_argument("--diagnostic", action="store_true", help="skip result checks (ablation builds; number is NOT a result)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: result checks, ingest figures, the `synchronous` block, CPU baselines "
+                         "and the secondary blocks (--scale-10m, --multi-gpu-blocks, --extra-blocks and --blocks choose among "
+                         "them).  Off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned for its last step: DIR/indices.npy (float64) and DIR/scores.npy "
+                         "(float32), [queries, topk]; above 64 MB a fixed, seeded sample of query rows (DIR/query_rows.npy)")
+    args = ap.parse_args()
+    if not args.full and (args.scale_10m == "on" or args.multi_gpu_blocks == "on" or args.blocks):
+        ap.error("--scale-10m on, --multi-gpu-blocks on and --blocks select secondary blocks: they need --full")
+    return args
 
 
 def launch_ranks(n):
@@ -579,6 +597,10 @@ def run_workload(job, n_total, nq_job, image_dtype, steps, warmup, layout, with_
         overflow = int(ov.item())
     else:
         overflow = st["overflow_batches"] + st["spec_retries"]
+    if overflow and (check or not args.diagnostic):
+        raise SystemExit("bench invalid: %d batches raised a sticky flag (buffer overflow or failed threshold)" % overflow)
+    # what the timed path returned for its last step (--dump-outputs), copied before anything else searches on `sg`
+    last_out = (idx.clone(), sc.clone()) if keep and args.dump_outputs else None
 
     # result sanity on the last batch (size-independent properties here; the oracle itself checks the full size in tests/:
     # test_gpu_full_size.py scores 8 queries against all rows in float64 on the host)
@@ -605,8 +627,6 @@ def run_workload(job, n_total, nq_job, image_dtype, steps, warmup, layout, with_
                 worst = max(worst, float(np.abs(rows @ q_last[qi] - sc_h[qi, mine]).max()))
         assert worst < 3e-7 * max(1.0, float(np.abs(sc_h).max())), \
             "returned scores differ from the float64 re-computation: %g" % worst
-        if overflow:
-            raise SystemExit("bench invalid: %d batches raised a sticky flag (buffer overflow or failed threshold)" % overflow)
         # COMPLETENESS by an independent path (no sample, no thresholds, no survivor / candidate buffers): every score of
         # this rank's shard for the same 16 queries in float64 + exact top-k of the dense rows (mi_knn_dense64_search).  The
         # job's answer restricted to my rows must be exactly the head of my dense list, and no row of my dense list that
@@ -633,7 +653,7 @@ def run_workload(job, n_total, nq_job, image_dtype, steps, warmup, layout, with_
                job_steps=job_steps,
                ingest_s=ingest_s, ingest_first_s=ingest_first_s, ingest_kernel_s=ingest_kernel_s, ingest_launch_ms=ingest_launch_ms, stateless_call_s=stateless_call_s, alloc_s=alloc_s, worst=worst,
                use_stream=use_stream, launch_ms=[float(v) for v in launch_ms], dense_check=dense_check,
-               protocol=sg._protocol, pipelined=pipelined, image_dtype=image_dtype, graph=bool(graph))
+               protocol=sg._protocol, pipelined=pipelined, image_dtype=image_dtype, graph=bool(graph), last_out=last_out)
 
     ref_i, ref_s = (idx.clone(), sc.clone()) if (also_stream and sg._protocol) else (None, None)
 
@@ -1560,6 +1580,46 @@ def multi_gpu_summary(res, ms_per_step, layout_requested):
                            "shards leave the MFMA-bound regime) and only the 10 M-row gallery (scale_10m) near 0.9"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(job, res, args):
+    """--dump-outputs DIR (every rank calls this; rank 0 writes): the job's answer to its last timed step, i.e. what a caller of
+    the searched path receives -- top-k indices [Q, k] (DIR/indices.npy, float64: exact for any row id) and scores [Q, k]
+    (DIR/scores.npy, float32, as returned).  Several ranks: each query group's slice comes from the group's shard-0 rank (every
+    rank of a group holds the same merged answer); replicas: from the rank that answered the job's last batch.  Above
+    DUMP_LIMIT_BYTES a fixed, seeded sample of query rows is written, with their row numbers in DIR/query_rows.npy."""
+    import numpy as np
+    import torch.distributed as dist
+    from isehr_amd.sharded import job_layout
+    idx, sc = (t.cpu().numpy() for t in res["last_out"])
+    world, rank = job.world, job.rank
+    if world > 1:
+        got = [None] * world
+        dist.all_gather_object(got, (idx, sc))
+        if rank != 0:
+            return
+        if args.layout == "replicas":
+            idx, sc = got[(res["job_steps"] - 1) % world]
+        else:
+            first = {}
+            for r in range(world):
+                _, _, qgroup, shard = job_layout(world, r, args.queries, args.layout)
+                if shard == 0:
+                    first[qgroup] = r
+            idx = np.concatenate([got[first[g]][0] for g in sorted(first)])
+            sc = np.concatenate([got[first[g]][1] for g in sorted(first)])
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    nq, k = idx.shape
+    keep = min(nq, DUMP_LIMIT_BYTES // max(1, k * (8 + 4)))
+    if keep < nq:
+        rows = np.sort(np.random.default_rng(args.seed).choice(nq, keep, replace=False))
+        idx, sc = idx[rows], sc[rows]
+        np.save(os.path.join(args.dump_outputs, "query_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(args.dump_outputs, "indices.npy"), idx.astype(np.float64))
+    np.save(os.path.join(args.dump_outputs, "scores.npy"), sc.astype(np.float32))
+
+
 def selftest_main(args, json_fd):
     """ISEHR_BENCH_SELFTEST=1 (tests/test_bench_cli_cpu.py, no GPU): the rank-process plumbing of main() -- process group with
     its timeout, the early headline line, a secondary block under its deadline, the exit codes -- over gloo on the CPU, with
@@ -1630,14 +1690,15 @@ def main():
     d, k = args.dim, args.topk
     default_shape = (args.workload == "roxford5k+1m" and not args.rows and args.queries == 1024 and d == 2048)
     plain = not (args.diagnostic or args.force_protocol or args.with_aqe or args.option or args.graph or args.pipeline)
-    scale_10m = args.scale_10m == "on" or (args.scale_10m == "auto" and default_shape and plain and not args.async_tail)
-    # the headline's tail mode: one GPU and batches for the tile kernel -> the deferred tail (the throughput mode); `roofline`
-    # then comes from a synchronous block of the same length on the same gallery (the undisturbed launch)
+    full = args.full
+    scale_10m = full and (args.scale_10m == "on" or (args.scale_10m == "auto" and default_shape and plain and not args.async_tail))
+    # the headline's tail mode: one GPU and batches for the tile kernel -> the deferred tail (the throughput mode); with --full
+    # `roofline` then comes from a synchronous block of the same length on the same gallery (the undisturbed launch)
     auto_tail = args.async_tail is None
     async_tail = (3 if (world == 1 and args.queries > 128 and plain) else 0) if auto_tail else args.async_tail
     args.async_tail = async_tail
     # the blocks beyond the headline that make the default one-GPU line cover every BASELINE config
-    extra_blocks = world == 1 and default_shape and plain and not args.diagnostic and args.extra_blocks != "off"
+    extra_blocks = full and world == 1 and default_shape and plain and not args.diagnostic and args.extra_blocks != "off"
     only = set(x for x in args.blocks.split(",") if x)
 
     def want(name):
@@ -1647,11 +1708,14 @@ def main():
     with emitter.deadline("headline"):
         res = run_workload(job, n_total, args.queries, args.image_dtype, args.steps, args.warmup, args.layout,
                            with_aqe=args.with_aqe, async_tail=async_tail, pipeline=args.pipeline, options=args.option,
-                           check=not args.diagnostic, warm_ingest=(n_total * d * 4 <= 16 << 30), keep=True, graph=args.graph,
-                           also_stream=(world > 1 and plain), phases=(10 if world > 1 or args.force_protocol else 0),
-                           defer_extras=world > 1)
+                           check=full and not args.diagnostic, warm_ingest=full and (n_total * d * 4 <= 16 << 30), keep=True,
+                           graph=args.graph, also_stream=(full and world > 1 and plain),
+                           phases=(10 if full and (world > 1 or args.force_protocol) else 0), defer_extras=full and world > 1)
         gal = res.pop("gal")
         q_last_pool = res.pop("q_last_pool")
+        if args.dump_outputs:
+            dump_outputs(job, res, args)
+        res.pop("last_out")
         out = None
         if rank == 0:
             elapsed, st, nq, gq, gs = res["elapsed"], res["st"], res["nq"], res["gq"], res["gs"]
@@ -1676,7 +1740,7 @@ def main():
                                            "synchronous per batch") if res["protocol"] else None,
                            "value_mode": ("pipelined: deferred tail (async_tail 3), every result joined inside the timed region; "
                                           "`synchronous` holds the same steps with the tail on the caller's stream, and "
-                                          "`roofline` is quoted on those undisturbed launches") if res["pipelined"] and auto_tail
+                                          "`roofline` is quoted on those undisturbed launches") if res["pipelined"] and auto_tail and full
                                          else ("pipelined (async_tail %d)" % async_tail if res["pipelined"] else "synchronous"),
                            "tail": ({1: "re-score + sort of batch i on the handle's own stream from the end of its phase 1: beside "
                                         "the query ingest, bootstrap AND scoring launch of batch i+1",
@@ -1691,17 +1755,19 @@ def main():
                            # ingest_s = one normalisation + layout pass over the resident raw rows in a warm process (the second
                            # ingest of this run; the first one, which also initialises the library, is ingest_first_s), and the
                            # rate of ONE call that prepares the gallery and answers one batch
-                           "ingest_s": round(res["ingest_s"], 4), "ingest_first_s": round(res["ingest_first_s"], 3),
+                           "ingest_s": round(res["ingest_s"], 4) if full else None,
+                           "ingest_first_s": round(res["ingest_first_s"], 3),
                            "ingest_kernel_s": round(res["ingest_kernel_s"], 5) if res["ingest_kernel_s"] else None,
                            "ingest_launch_ms": ([round(x, 3) for x in res["ingest_launch_ms"]] if res["ingest_launch_ms"] else None),
-                           "queries_per_s_incl_gallery_ingest_per_call_of_one_batch": nq / (ms_step * 1e-3 + res["ingest_s"]),
+                           "queries_per_s_incl_gallery_ingest_per_call_of_one_batch":
+                               nq / (ms_step * 1e-3 + res["ingest_s"]) if full else None,
                            # measured, not composed: create + one batch (first search of the handle) + destroy, wall clock
                            "stateless_call_s": round(res["stateless_call_s"], 5) if res["stateless_call_s"] else None,
                            "queries_per_s_of_one_stateless_call": (nq / res["stateless_call_s"]) if res["stateless_call_s"] else None,
                            "candidates_per_query": st["candidates"] / max(1, st["queries"]),
                            "survivors_per_query": st["survivors"] / max(1, st["queries"]),
                            "score_check": ("16 queries x top-%d re-computed in float64: max |d| %.2e; completeness: %s"
-                                           % (k, res["worst"], res["dense_check"])) if not args.diagnostic else None},
+                                           % (k, res["worst"], res["dense_check"])) if res["worst"] is not None else None},
                 "roofline": roof,
             }
         emitter.out = out
@@ -1710,7 +1776,8 @@ def main():
             out["config"]["rank_devices"] = [list(x) for x in job.rank_devices]
             out["config"]["rank_devices_distinct"] = job.devices_distinct
             out["config"]["rccl_ranks_equal_n_gpus"] = job.comm_ranks == args.gpus
-            out["blocks_after_the_headline"] = "each under a deadline; {\"error\": \"timeout\"} + a non-zero exit if one hangs"
+            if full:
+                out["blocks_after_the_headline"] = "each under a deadline; {\"error\": \"timeout\"} + a non-zero exit if one hangs"
         emitter.write(False)
 
     selftest_hang = os.environ.get("ISEHR_BENCH_TEST_HANG", "")      # "<block>:<rank>": that rank sleeps in that block (tests)
@@ -1732,9 +1799,9 @@ def main():
             out["pipelined_collectives"] = res["stream"]
         if res.get("phases"):
             out["protocol_phases_ms_max_over_ranks"] = res["phases"]
-        if world > 1:
+        if full and world > 1:
             out["multi_gpu"] = multi_gpu_summary(res, out["ms_per_step"], args.layout)
-    if world == 1 and res["pipelined"] and auto_tail:
+    if full and world == 1 and res["pipelined"] and auto_tail:
         # the same steps with the tail on the caller's stream: the undisturbed scoring launch (roofline) and what the
         # synchronous mode delivers on this box
         def sync_block():
@@ -1781,7 +1848,7 @@ def main():
             r = emitter.block("online", lambda: online_block(job, gal, args), world)
             if r is not None:
                 out["online"] = r
-    if world == 1 and not args.no_cpu_baseline and want("cpu_baseline"):
+    if full and world == 1 and not args.no_cpu_baseline and want("cpu_baseline"):
         r = emitter.block("cpu_baseline", lambda: cpu_baseline(gal, q_last_pool.cpu().numpy(), n_total, args), world)
         if r is not None:
             out["cpu_baseline"] = r
@@ -1792,7 +1859,7 @@ def main():
     torch.cuda.empty_cache()
     emitter.write(False)
 
-    multi = world > 1 and plain and (args.multi_gpu_blocks == "on" or (args.multi_gpu_blocks == "auto" and default_shape))
+    multi = full and world > 1 and plain and (args.multi_gpu_blocks == "on" or (args.multi_gpu_blocks == "auto" and default_shape))
     if multi:
         # north_star's literal partition on the benchmarked gallery: row shards only (1 x N), every rank scores all queries
         # against its rows, two all-gathers per batch -- synchronous and with the pipelined collectives, plus what every
@@ -1857,7 +1924,7 @@ def main():
         torch.cuda.empty_cache()
         emitter.write(False)
 
-    if rank == 0 and default_shape and plain and not args.diagnostic and want("map"):
+    if full and rank == 0 and default_shape and plain and not args.diagnostic and want("map"):
         # the metric's other half: mAP (E / M / H) on planted rOxford5k- / +rParis6k-sized datasets, HIP ranks vs the oracle's
         def map_blk():
             out["map"] = map_block(args, job.dev_index)

@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $o/r04j_gputests.txt 2>&1 || (tail -40 $o/r04j_gputests.txt; exit 1)
 tail -2 $o/r04j_gputests.txt
-python bench.py --steps 20 --warmup 5 > $o/r04j_bench.json 2> $o/r04j_bench.err
+python bench.py --full --steps 20 --warmup 5 > $o/r04j_bench.json 2> $o/r04j_bench.err
 python - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r04j_bench.json') if l.startswith('{')][-1])

@@ -9,11 +9,11 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 o=gpurun_out
 # 1. headline bench + its rocprofv3 kernel trace + PMC passes (separate runs, as the microarchitecture guide prescribes)
 if st 1; then
-python bench.py > $o/${tag}_bench.json 2> $o/${tag}_bench.err            # the driver's default invocation: 200 steps
+python bench.py --full > $o/${tag}_bench.json 2> $o/${tag}_bench.err     # the full record at the default 200 steps
 echo "bench done"
 # the SAME command under the profiler (minus the host-side CPU baseline): headline + the 10 M-row secondary block, whose bf16 launches
 # are other template instantiations of the kernels and get rows of their own in the statistics
-rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_trace -- python3 bench.py --no-cpu-baseline > $o/${tag}_trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_trace -- python3 bench.py --full --no-cpu-baseline > $o/${tag}_trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $o/${tag}_pmc_fetch -- python3 bench.py --scale-10m off --extra-blocks off --steps 5 --warmup 2 --no-cpu-baseline > $o/${tag}_pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $o/${tag}_pmc_write -- python3 bench.py --scale-10m off --extra-blocks off --steps 5 --warmup 2 --no-cpu-baseline > $o/${tag}_pmc_write.log 2>&1
 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $o/${tag}_pmc_l2 -- python3 bench.py --scale-10m off --extra-blocks off --steps 5 --warmup 2 --no-cpu-baseline > $o/${tag}_pmc_l2.log 2>&1
@@ -25,7 +25,7 @@ fi
 if st 2; then
 for v in "sync:--async-tail 0" "q1:--queries 1" "q70:--queries 70" "bf16:--image-dtype bf16" "aqe:--with-aqe" "aqe_rparis:--workload rparis6k+1m --with-aqe" "10m:--workload 10m --steps 10 --warmup 2"; do
   name=${v%%:*}; args=${v#*:}
-  rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_${name}_trace -- python3 bench.py --scale-10m off --extra-blocks off --no-cpu-baseline $args > $o/${tag}_${name}_bench.json 2> $o/${tag}_${name}.err || echo "$name failed"
+  rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_${name}_trace -- python3 bench.py --full --scale-10m off --extra-blocks off --no-cpu-baseline $args > $o/${tag}_${name}_bench.json 2> $o/${tag}_${name}.err || echo "$name failed"
   echo "$name done"
 done
 fi
@@ -42,7 +42,7 @@ python scripts/xcc_report.py > $o/${tag}_xcc_report.txt 2>&1 || true
 python -m pytest tests/test_gpu_diffusion.py -q -s -k reference_size > $o/${tag}_diffusion_refsize.txt 2>&1 || true
 python scripts/ladder_probe.py > $o/${tag}_ladder_probe.txt 2> /dev/null || true
 (for g in 2 4 8; do python scripts/shard_step_model.py $g 1005994 rescore_grid_x=$((96 / g)) 2> /dev/null | tail -2; done) > $o/${tag}_shard_model.txt || true
-(for f in "" "--force-protocol"; do python bench.py --scale-10m off --no-cpu-baseline --rows 125750 $f 2> /dev/null | tail -1 | cut -c1-700; done) > $o/${tag}_protocol_rccl1.txt || true
+(for f in "" "--force-protocol"; do python bench.py --full --scale-10m off --no-cpu-baseline --rows 125750 $f 2> /dev/null | tail -1 | cut -c1-700; done) > $o/${tag}_protocol_rccl1.txt || true
 bash scripts/layout_model.sh > $o/${tag}_layout_model.txt 2> /dev/null || true
 echo "scripts done"
 fi
@@ -67,8 +67,8 @@ bash scripts/rehearse_sharded.sh 2 > $o/${tag}_rehearse2.txt 2>&1 || true
 bash scripts/rehearse_sharded.sh 4 > $o/${tag}_rehearse4.txt 2>&1 || true
 bash scripts/rehearse_sharded.sh 4 --layout 1x4 --pipeline > $o/${tag}_rehearse4_rows_pipelined.txt 2>&1 || true
 # bench.py --gpus 2 started BARE (it starts its two ranks itself); ranks share the GPU over gloo; secondary block at 600 k rows
-(ISEHR_DIST_BACKEND=gloo ISEHR_SHARE_GPU=1 timeout -k 10 300 python bench.py --gpus 2 --rows 200000 --steps 6 --warmup 2 --no-cpu-baseline --multi-gpu-blocks on --scale-10m on --scale-10m-rows 600000 --scale-10m-steps 4 2> /dev/null | tail -1 | cut -c1-6000) > $o/${tag}_bare_gpus2.txt || true
-(ISEHR_DIST_BACKEND=gloo ISEHR_SHARE_GPU=1 timeout -k 10 400 python bench.py --gpus 4 --rows 400000 --steps 6 --warmup 2 --no-cpu-baseline --multi-gpu-blocks on --scale-10m on --scale-10m-rows 1200000 --scale-10m-steps 4 2> /dev/null | tail -1 | cut -c1-6000) > $o/${tag}_bare_gpus4.txt || true
+(ISEHR_DIST_BACKEND=gloo ISEHR_SHARE_GPU=1 timeout -k 10 300 python bench.py --gpus 2 --rows 200000 --steps 6 --warmup 2 --no-cpu-baseline --full --multi-gpu-blocks on --scale-10m on --scale-10m-rows 600000 --scale-10m-steps 4 2> /dev/null | tail -1 | cut -c1-6000) > $o/${tag}_bare_gpus2.txt || true
+(ISEHR_DIST_BACKEND=gloo ISEHR_SHARE_GPU=1 timeout -k 10 400 python bench.py --gpus 4 --rows 400000 --steps 6 --warmup 2 --no-cpu-baseline --full --multi-gpu-blocks on --scale-10m on --scale-10m-rows 1200000 --scale-10m-steps 4 2> /dev/null | tail -1 | cut -c1-6000) > $o/${tag}_bare_gpus4.txt || true
 (timeout -k 10 300 python bench.py --graph --no-cpu-baseline --async-tail 0 2> /dev/null | tail -1 | cut -c1-900) > $o/${tag}_graph_replay.txt || true
 fi
 # 6. same-box A/B against the library of the previous round, when a build of it was left under ab/ (git-ignored)
@@ -98,7 +98,7 @@ fi
 echo "all done"
 # 9. round 6: the whitening kernel (f64 MFMA) -- kernel statistics and, in separate passes, matrix-pipe busy cycles and fabric traffic
 if st 9; then
-W="--steps 10 --warmup 2 --scale-10m off --no-cpu-baseline --blocks whiten"
+W="--full --steps 10 --warmup 2 --scale-10m off --no-cpu-baseline --blocks whiten"
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/${tag}_whiten_trace -- python3 bench.py $W > $o/${tag}_whiten_bench.json 2> $o/${tag}_whiten.err || true
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $o/${tag}_whiten_pmc_sq -- python3 bench.py $W > $o/${tag}_whiten_pmc_sq.log 2>&1 || true
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $o/${tag}_whiten_pmc_fetch -- python3 bench.py $W > $o/${tag}_whiten_pmc_fetch.log 2>&1 || true

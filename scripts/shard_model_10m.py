@@ -8,7 +8,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def bench(*extra):
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--scale-10m", "off",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--scale-10m", "off",
                         "--image-dtype", "bf16", "--steps", "40", "--warmup", "5", *extra], capture_output=True, text=True)
     if r.returncode != 0:
         raise SystemExit(r.stderr[-2000:])

@@ -55,6 +55,50 @@ def test_one_gpu_needs_no_launcher(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse()
     assert a.gpus == 1 and a.scale_10m == "auto" and a.scale_10m_rows == 10000000
+    assert a.full is False and a.dump_outputs is None
+
+
+def test_secondary_blocks_are_asked_for_with_full(monkeypatch, capsys):
+    """A plain run is the headline alone: asking for a secondary block without --full is an error, not silently ignored."""
+    bench = _bench_module()
+    for extra in (["--scale-10m", "on"], ["--multi-gpu-blocks", "on"], ["--blocks", "whiten"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *extra])
+        try:
+            bench.parse()
+            raise AssertionError("%r without --full must be refused" % extra)
+        except SystemExit as e:
+            assert e.code == 2 and "--full" in capsys.readouterr().err
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--full", *extra])
+        assert bench.parse().full is True
+
+
+def test_dump_outputs_writes_the_last_step_as_float(tmp_path, monkeypatch):
+    """--dump-outputs on one rank: indices as float64 (exact), scores as float32, [Q, k]; above the size cap a fixed, seeded
+    sample of query rows, the same on every run, with the row numbers beside it."""
+    import types
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    rng = np.random.default_rng(0)
+    idx = torch.from_numpy(rng.integers(0, 1 << 40, size=(64, 10)))
+    sc = torch.from_numpy(rng.standard_normal((64, 10)).astype(np.float32))
+    job = types.SimpleNamespace(world=1, rank=0)
+    res = {"last_out": (idx, sc), "job_steps": 3}
+    args = types.SimpleNamespace(dump_outputs=str(tmp_path / "a"), seed=5, layout="auto", queries=64)
+    bench.dump_outputs(job, res, args)
+    gi, gs = np.load(tmp_path / "a" / "indices.npy"), np.load(tmp_path / "a" / "scores.npy")
+    assert gi.dtype == np.float64 and gs.dtype == np.float32 and gi.shape == gs.shape == (64, 10)
+    assert np.array_equal(gi.astype(np.int64), idx.numpy()) and np.array_equal(gs, sc.numpy())
+    assert not (tmp_path / "a" / "query_rows.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 16 * 10 * 12)
+    for d in ("b", "c"):
+        bench.dump_outputs(job, res, types.SimpleNamespace(**dict(vars(args), dump_outputs=str(tmp_path / d))))
+    rows = np.load(tmp_path / "b" / "query_rows.npy")
+    assert rows.shape == (16,) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "query_rows.npy"))
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b" / "indices.npy"), idx.numpy()[r].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "b" / "scores.npy"), sc.numpy()[r])
 
 
 def _selftest(extra_env, timeout=120):

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,21 +32,53 @@ def _bench(args, env_extra=None, timeout=600):
     return recs[-1]
 
 
-def test_bare_gpus_2_runs_two_ranks():
-    out = _bench(["--gpus", "2", "--rows", "200000", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"],
+def _dumped(d, n_rows, nq=1024, k=100):
+    """The arrays --dump-outputs wrote: float64 indices and float32 scores [nq, k], each row a valid top-k answer."""
+    idx, sc = np.load(os.path.join(d, "indices.npy")), np.load(os.path.join(d, "scores.npy"))
+    assert idx.dtype == np.float64 and sc.dtype == np.float32 and idx.shape == sc.shape == (nq, k)
+    assert np.array_equal(idx, np.floor(idx)) and idx.min() >= 0 and idx.max() < n_rows
+    assert all(len(set(r)) == k for r in idx.astype(np.int64)) and (np.diff(sc, axis=1) <= 0).all()
+    return idx, sc
+
+
+def test_bare_gpus_2_runs_two_ranks(tmp_path):
+    out = _bench(["--gpus", "2", "--rows", "200000", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+                  "--dump-outputs", str(tmp_path)],
                  {"ISEHR_DIST_BACKEND": "gloo", "ISEHR_SHARE_GPU": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert out["n_gpus"] == 2 and out["config"]["rccl_ranks"] == 2 and out["config"]["comm_backend"] == "gloo"
     assert out["config"]["rccl_ranks_equal_n_gpus"] is True and len(out["config"]["rank_devices"]) == 2
     assert out["config"]["rank_devices_distinct"] is False             # (rehearsal: both ranks share the box's one GPU)
     assert out["config"]["gallery_rows"] == 200000 and out["steps"] == 4 and out["value"] > 0
     assert "scale_10m" not in out                                     # --rows override: the secondary block is off
+    _dumped(tmp_path, 200000)                                         # both query groups' halves of the last batch
+
+
+def test_plain_line_is_the_headline_alone_and_dumps_what_the_checked_run_computes(tmp_path):
+    """Without --full the line is the headline and nothing else (no second timed pass, no checks, no blocks), and
+    --dump-outputs writes the last timed step's answer: the same on a second plain run and on a --full run, whose checks
+    re-compute that batch in float64 and against the dense float64 search."""
+    args = ["--rows", "150000", "--steps", "5", "--warmup", "2"]
+    a = _bench(args + ["--dump-outputs", str(tmp_path / "a")])
+    b = _bench(args + ["--dump-outputs", str(tmp_path / "b")])
+    f = _bench(args + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "f")])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert key in a, key
+    assert a["steps"] == 5 and abs(a["value"] * a["ms_per_step"] * 1e-3 - 1024) < 1e-6 * 1024
+    assert a["roofline"]["launches"] == 5 and a["config"]["score_check"] is None
+    for key in ("synchronous", "value_pipelined", "cpu_baseline", "map", "q70", "whiten", "blocks_after_the_headline"):
+        assert key not in a, key
+    assert "synchronous" in f and "mi_knn_dense64_search" in f["config"]["score_check"]
+    ia, sa = _dumped(tmp_path / "a", 150000)
+    for other in ("b", "f"):
+        io, so = _dumped(tmp_path / other, 150000)
+        assert np.array_equal(ia, io) and np.array_equal(sa, so)
 
 
 def test_bare_gpus_2_row_shards_with_secondary_block():
     """Row shards (1 x 2: the protocol with both all-gathers) and the secondary block at a reduced size (2 x 300 k rows of
     the bf16 image on the shared GPU)."""
     out = _bench(["--gpus", "2", "--rows", "200000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--layout", "1x2",
-                  "--scale-10m", "on", "--scale-10m-rows", "600000", "--scale-10m-steps", "3"],
+                  "--full", "--scale-10m", "on", "--scale-10m-rows", "600000", "--scale-10m-steps", "3"],
                  {"ISEHR_DIST_BACKEND": "gloo", "ISEHR_SHARE_GPU": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert out["n_gpus"] == 2 and out["config"]["rccl_ranks"] == 2
     assert out["config"]["collectives"] == "synchronous per batch"
@@ -55,7 +88,7 @@ def test_bare_gpus_2_row_shards_with_secondary_block():
 
 
 def test_one_gpu_line_has_the_contract_fields():
-    out = _bench(["--rows", "150000", "--steps", "5", "--warmup", "2", "--cpu-sample-rows", "8192"])
+    out = _bench(["--full", "--rows", "150000", "--steps", "5", "--warmup", "2", "--cpu-sample-rows", "8192"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in out, key
@@ -79,8 +112,8 @@ def test_default_shape_line_carries_the_secondary_blocks():
     carries `synchronous` -- the same steps with the tail on the caller's stream, whose answer must equal the pipelined one
     and on whose undisturbed launches `roofline` is quoted --, `scale_10m` (here on a smaller row count) and `map`: mAP
     (E / M / H) of the HIP ranks on the planted rOxford5k- / +rParis6k-sized datasets."""
-    out = _bench(["--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--scale-10m", "on", "--scale-10m-rows", "400000",
-                  "--scale-10m-steps", "2", "--extra-blocks", "off"])
+    out = _bench(["--full", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--scale-10m", "on",
+                  "--scale-10m-rows", "400000", "--scale-10m-steps", "2", "--extra-blocks", "off"])
     assert out["config"]["gallery_rows"] == 1005994 and out["config"]["tail"].startswith("deferred")
     # (round 6: the headline is the faster of the two tail modes of the box; both are in the line)
     assert out["config"]["value_mode"].startswith(("pipelined", "synchronous (faster than the deferred tail"))
@@ -107,7 +140,7 @@ def test_default_line_gives_every_baseline_config_a_number():
     (the diffusion branch at rOxford5k size) and `dropin`: matching_HIP(K, vecs.T, qvecs.T[, dataset]) on a HOST [2048, 1 005 994]
     float32 array -- the call src/test_rOP1m.py:155-159 makes -- stateless, stateful first / cached / from the file, with the
     prepared-gallery file written BEHIND the first call, and the float64 case of src/online.py:96."""
-    out = _bench(["--steps", "10", "--warmup", "2", "--scale-10m", "off", "--cpu-sample-rows", "8192"], timeout=900)
+    out = _bench(["--full", "--steps", "10", "--warmup", "2", "--scale-10m", "off", "--cpu-sample-rows", "8192"], timeout=900)
     for name in ("q70", "q1"):
         b = out[name]
         assert b["roofline"]["bound"] == "hbm" and 0.3 < b["roofline"]["frac"] < 1 and b["flagged_batches"] == 0
@@ -169,7 +202,7 @@ def test_bare_gpus_2_line_answers_layout_overlap_and_collective_cost():
     """what ONE hardware run at N > 1 must be able to answer.  Two ranks (sharing the test box's GPU over
     gloo), reduced sizes: the auto-layout headline, the `row_shard_1xN` block -- north_star's partition, synchronous AND with
     pipelined collectives, with the per-stage timings of the protocol -- and `scale_10m` with both as well."""
-    out = _bench(["--gpus", "2", "--rows", "200000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    out = _bench(["--gpus", "2", "--rows", "200000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full",
                   "--multi-gpu-blocks", "on", "--scale-10m", "on", "--scale-10m-rows", "600000", "--scale-10m-steps", "3"],
                  {"ISEHR_DIST_BACKEND": "gloo", "ISEHR_SHARE_GPU": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     assert out["n_gpus"] == 2 and out["config"]["rccl_ranks"] == 2
@@ -199,7 +232,7 @@ def test_a_hang_in_the_pipelined_collectives_cannot_cost_the_synchronous_headlin
                 "ISEHR_BENCH_TEST_HANG": "pipelined_collectives:1", "ISEHR_BENCH_DEADLINE_S": "25"})
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "200000", "--steps", "4",
-                        "--warmup", "2", "--no-cpu-baseline", "--layout", "1x2"], env=env, capture_output=True, text=True,
+                        "--warmup", "2", "--no-cpu-baseline", "--layout", "1x2", "--full"], env=env, capture_output=True, text=True,
                        timeout=400, cwd=ROOT)
     took = time.time() - t0
     lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
