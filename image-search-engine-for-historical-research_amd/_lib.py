@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(HERE, "libmi355_retrieval.so")
 MI_F32, MI_F64 = 0, 1
 MI_HOST, MI_DEVICE = 0, 1
 NORM_NONE, NORM_L2, NORM_L2_EPS = 0, 1, 2
+MI_ERR_CAPACITY = 7
 
 c_i64p = C.POINTER(C.c_int64)
 c_f32p = C.POINTER(C.c_float)
@@ -53,6 +54,8 @@ SIGNATURES = {
     "mi_gallery_get_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "mi_knn_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32,
                                 C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_range_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_double,
+                                  C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_knn_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "mi_knn_phase1_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -302,6 +305,33 @@ class Gallery:
             check(load().mi_knn_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
                                        idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), C.byref(secs)))
         return idx, sc, secs.value
+
+    def range_search(self, queries, min_score, max_results=None):
+        """Every row whose exact score is >= min_score (inclusive), per query ->
+        (lims int64 [Q+1], idx int64 [lims[-1]], scores float32 [lims[-1]], seconds).  The hits of query i are
+        idx/scores[lims[i]:lims[i+1]], ordered by (score desc, id asc).  The first call's capacity is `max_results`
+        (default Q * 1024); if the hits do not fit, the call is made once more with exactly lims[-1]."""
+        a, code, rs, cs = _strided(queries)
+        if a.shape[1] != self.d:
+            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        nq = a.shape[0]
+        cap = int(max_results) if max_results is not None else nq * 1024
+        lims = np.zeros(nq + 1, dtype=np.int64)
+        secs = C.c_double()
+        with self._lock:
+            lib = load()
+            for attempt in range(2):
+                idx = np.empty(cap, dtype=np.int64)
+                sc = np.empty(cap, dtype=np.float32)
+                rc = lib.mi_range_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, float(min_score), cap,
+                                         lims.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
+                                         sc.ctypes.data_as(C.c_void_p), C.byref(secs))
+                if rc != MI_ERR_CAPACITY or attempt == 1:
+                    break
+                cap = int(lims[-1])
+            check(rc)
+        total = int(lims[-1])
+        return lims, idx[:total], sc[:total], secs.value
 
     def aqe_search(self, ranks, k_qe, w, k, eps=1e-6, return_qexp=False):
         """ranks [K_in, Q] int64 (any strides) -> (idx [Q,k], scores [Q,k], qexp [Q,D] f64 | None, seconds)."""

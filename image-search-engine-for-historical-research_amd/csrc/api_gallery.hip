@@ -44,6 +44,7 @@ int mi_gallery_destroy(mi_gallery* g) {
   (void)hipFree(g->samp_scores);
   (void)hipFree(g->samp_f32);
   for (void* b : g->io_buf) (void)hipFree(b);
+  range_scratch_free(g);
   (void)hipFree(g->dif_ids);
   (void)hipFree(g->dif_vals);
   if (g->stream) (void)hipStreamDestroy(g->stream);

@@ -8,6 +8,7 @@
 //   api_entry.hip     search entry points: kNN (host / device / phases / merge), alpha-QE, dense, full-length ranking
 //   api_aux.hip       descriptor tail, whitening, k-reciprocal re-ranking, diffusion, column sums, synthetic rows
 //   api_options.hip   per-handle options, statistics, profiling, flags, diagnostics
+//   api_range.hip     exact range search: fixed-threshold chunk schedule, overflow split, dense chunks, CSR tail
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -209,6 +210,24 @@ struct mi_gallery {
   // pair per call costs more than a single-query search
   void* io_buf[3] = {nullptr, nullptr, nullptr};
   size_t io_cap[3] = {0, 0, 0};
+  // grow-only device buffers of the range search (api_range.hip), freed with the handle
+  struct RangeScratch {
+    uint32_t* rows = nullptr;              // [QB][surv_cap] rows handed to the exact re-score
+    uint32_t* rcnt = nullptr;              // [QB]
+    double* sc = nullptr;                  // [QB][surv_cap] their f64 scores
+    uint32_t lcap = 0;                     // surv_cap the three above were sized for
+    uint64_t* akey = nullptr;              // hits of the batch, chunk after chunk
+    uint32_t* arow = nullptr;
+    size_t acap = 0;
+    uint64_t* bkey[2] = {nullptr, nullptr};   // hits of the batch in CSR order (ping-pong of the merge passes)
+    uint32_t* brow[2] = {nullptr, nullptr};
+    size_t bcap = 0;
+    uint64_t* coff = nullptr;              // [chunks][QB] offset of query q's hits of chunk c in akey / arow
+    uint32_t* ccnt = nullptr;              // [chunks][QB] their number
+    size_t ccap = 0;                       // chunks
+    int64_t* lims = nullptr;               // [QB + 1]
+    unsigned long long* total = nullptr;   // hits of the current chunk
+  } range;
   // diffusion state (offline matrix rows kept on the device for the online stage)
   int32_t* dif_ids = nullptr;
   float* dif_vals = nullptr;
@@ -249,3 +268,5 @@ MI_INTERNAL int dense64_search_device(mi_gallery* g, const void* q_src, int q_dt
                                       double* out_score64_dev, hipStream_t s);
 // ---- api_gallery.hip
 MI_INTERNAL int gallery_alloc(mi_gallery* g);
+// ---- api_range.hip
+MI_INTERNAL void range_scratch_free(mi_gallery* g);

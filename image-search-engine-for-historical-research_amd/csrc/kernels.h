@@ -148,6 +148,25 @@ void launch_kth_of_gathered(const float* gathered, int32_t nshards, int64_t nq, 
 void launch_merge(const double* score64, const int64_t* idx, int32_t nshards, int64_t nq, int32_t k, int64_t shard_stride,
                   int64_t* out_idx, float* out_score, hipStream_t stream);
 
+// range_select.hip -- exact range search (api_range.hip): fixed threshold, survivor rows for rescore_kernel, rows kept at
+// f64 score >= min_score (CSR per chunk), per-query counts / offsets, order by (score desc, row asc), emit
+void launch_range_threshold(QueryState st, int32_t nq, int32_t qpad, double min_score, hipStream_t stream);
+void launch_range_chunk_begin(QueryState st, int32_t qpad, unsigned long long* total, hipStream_t stream);
+void launch_range_rows(QueryState st, int32_t nq, uint32_t* rows, uint32_t* rcnt, int dense, uint32_t row0, uint32_t nrows,
+                       hipStream_t stream);
+void launch_range_keep(const uint32_t* rows, const uint32_t* rcnt, const double* sc, uint32_t lcap, int32_t nq, double min_score,
+                       unsigned long long* total, uint64_t* off, uint32_t* cnt, uint64_t* key, uint32_t* row, uint64_t base,
+                       uint64_t cap, uint32_t* flags, hipStream_t stream);
+void launch_range_lims(const uint32_t* cnt, int32_t nchunks, int32_t ld, int32_t nq, int64_t* lims, hipStream_t stream);
+void launch_range_gather(const uint64_t* akey, const uint32_t* arow, const uint64_t* off, const uint32_t* cnt, int32_t nchunks,
+                         int32_t ld, int32_t nq, const int64_t* lims, uint64_t* key, uint32_t* row, hipStream_t stream);
+void launch_range_sort_runs(uint64_t* key, uint32_t* row, const int64_t* lims, int32_t nq, int64_t max_cnt, hipStream_t stream);
+int64_t range_run_length();
+void launch_range_merge(const uint64_t* skey, const uint32_t* srow, uint64_t* dkey, uint32_t* drow, const int64_t* lims,
+                        int32_t nq, int64_t total, int64_t w, hipStream_t stream);
+void launch_range_emit(const uint64_t* key, const uint32_t* row, int64_t total, int64_t row_offset, int64_t* out_idx,
+                       float* out_score, hipStream_t stream);
+
 // dense.hip -- exact top-k of dense score rows (global-memory radix select + LDS bitonic sort), k <= 4096
 void launch_dense_topk(const float* scores, int64_t ld, int64_t n, int32_t nq, int32_t k, int64_t row_offset,
                        int64_t* out_idx, float* out_score, hipStream_t stream);

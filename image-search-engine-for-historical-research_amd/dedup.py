@@ -1,0 +1,31 @@
+"""Near-duplicate pairs of a gallery: every pair of stored rows i < j whose exact score is >= min_score.
+
+The same print, photo or scan often enters an archive database more than once when several archives are merged
+(the reference's `src/offline.py --datasets 'A, B, ...'`); this finds those copies as a self-join of exact range searches
+(Gallery.range_search) with the gallery's own stored rows as queries.
+"""
+import numpy as np
+
+
+def near_duplicate_pairs(gallery, min_score, batch=1024):
+    """-> (i int64, j int64, score float32): all pairs i < j with exact score >= min_score (inclusive), in the order of
+    i, then of (score desc, j asc).  Stored row i is the query of its pairs: each pair is reported once, with the score of
+    the range search of row i, and self pairs drop out.  Assumes a single-shard gallery with row_offset 0 (ids are rows)."""
+    if gallery.row_offset != 0:
+        raise ValueError("near_duplicate_pairs needs a gallery with row_offset 0 (a single shard)")
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    out_i, out_j, out_s = [], [], []
+    for r0 in range(0, gallery.n, batch):
+        m = min(batch, gallery.n - r0)
+        rows = gallery.get_rows(r0, m)
+        lims, idx, sc, _ = gallery.range_search(rows, min_score)
+        qi = np.repeat(np.arange(r0, r0 + m, dtype=np.int64), np.diff(lims))
+        keep = idx > qi
+        out_i.append(qi[keep])
+        out_j.append(np.asarray(idx, dtype=np.int64)[keep])
+        out_s.append(np.asarray(sc, dtype=np.float32)[keep])
+    if not out_i:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32)
+    return np.concatenate(out_i), np.concatenate(out_j), np.concatenate(out_s)

@@ -28,5 +28,15 @@ class KNN:
         ids, sims, _ = self.gallery.search(queries, int(k))
         return sims, ids
 
+    def range_search(self, queries, thresh):
+        """-> (lims int64 [Q+1], D float32 [lims[-1]], I int64 [lims[-1]]), the return shape of faiss's `range_search`: the
+        results of query i are D/I[lims[i]:lims[i+1]].  Every row whose exact inner product with the query is >= thresh
+        (the bound is INCLUSIVE), ordered by (score desc, id asc)."""
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            queries = queries.astype(np.float32)
+        lims, ids, sims, _ = self.gallery.range_search(queries, float(thresh))
+        return lims, sims, ids
+
     def close(self):
         self.gallery.close()

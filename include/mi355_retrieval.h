@@ -37,7 +37,8 @@ enum mi_status {
   MI_ERR_NOMEM = 3,
   MI_ERR_IO = 4,
   MI_ERR_OVERFLOW = 5,    /* candidate buffers overflowed and the exact fallback was disabled */
-  MI_ERR_UNSUPPORTED = 6
+  MI_ERR_UNSUPPORTED = 6,
+  MI_ERR_CAPACITY = 7     /* mi_range_search: more results than max_results; out_lims[nq] says how many */
 };
 enum mi_dtype { MI_F32 = 0, MI_F64 = 1 };
 enum mi_memspace { MI_HOST = 0, MI_DEVICE = 1 };
@@ -94,6 +95,17 @@ int mi_gallery_get_rows(const mi_gallery* g, int64_t row0, int64_t nrows, float*
 int mi_knn_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride,
                   int64_t col_stride, int32_t k, int64_t* out_idx, float* out_score,
                   double* out_seconds);
+
+/* Exact range search: for every query, all rows whose exact score (the same float64 score mi_knn_search returns:
+ * f32 stored rows, exact f64 products, f64 accumulation, query normalised by the gallery's norm mode) is >= min_score.
+ * Results in CSR form: the hits of query i are out_idx/out_score[out_lims[i] .. out_lims[i+1]), ordered by
+ * (score desc, id asc); ids are row_offset + local row.  out_lims [nq + 1] is always written in full.  If
+ * out_lims[nq] > max_results, nothing is written to out_idx / out_score and MI_ERR_CAPACITY is returned:
+ * call again with max_results >= out_lims[nq].  out_score may be NULL; out_idx may be NULL when max_results is 0.
+ * out_seconds (may be NULL): wall time of the call.  Host input and host output, like mi_knn_search. */
+int mi_range_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
+                    double min_score, int64_t max_results, int64_t* out_lims, int64_t* out_idx, float* out_score,
+                    double* out_seconds);
 
 /* Device-resident variant: q_dev [nq][d] row-major f32 (C order), outputs are device buffers.
  * out_score64_dev (may be NULL) receives the float64 exact scores. */
