@@ -33,6 +33,15 @@ class SearchStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FilterInfo(C.Structure):
+    """mi_filter_info: what one mi_knn_search_filtered call did."""
+    _fields_ = [("allowed", C.c_int64), ("path", C.c_int32), ("kprime", C.c_int32), ("rerun_queries", C.c_int64),
+                ("cache_hit", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/mi355_retrieval.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "mi_last_error": (C.c_char_p, []),
@@ -56,6 +65,8 @@ SIGNATURES = {
                                 C.c_void_p, C.c_void_p, c_f64p]),
     "mi_range_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_double,
                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_knn_search_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(FilterInfo), c_f64p]),
     "mi_knn_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "mi_knn_phase1_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -182,6 +193,66 @@ def _base_pointer(a):
     return a.ctypes.data
 
 
+class AllowBits(np.ndarray):
+    """Packed allow words as allow_bitmap / allow_ranges return them (a uint64 ndarray).  The type is what tells packed words
+    apart from an array of ids: a plain uint64 array given as `allow` is read as ids."""
+
+
+def allow_bitmap(allow, n, row_offset=0, packed=False):
+    """The allow bitmap of mi_knn_search_filtered for a shard of n rows starting at global id row_offset: ceil(n / 64)
+    little-endian uint64 words, bit (i & 63) of word (i >> 6) allowing local row i, as an AllowBits array.  `allow` is one of
+      - a bool mask [n] over the shard's rows;
+      - an array or list of allowed GLOBAL ids (row_offset + local row; any integer dtype), each in the shard; an empty
+        one allows no row;
+      - packed words: an AllowBits array (what this function returns), or any array of ceil(n / 64) uint64 words with
+        packed=True.
+    Raises ValueError on ids outside the shard or a mask / word array of the wrong length."""
+    n = int(n)
+    nwords = (n + 63) // 64
+    if packed or isinstance(allow, AllowBits):
+        a = np.asarray(allow)
+        if a.dtype != np.uint64 or a.shape != (nwords,):
+            raise ValueError("packed bitmap of %s %s; a shard of %d rows takes %d uint64 words" % (a.dtype, a.shape, n, nwords))
+        return np.ascontiguousarray(a, dtype="<u8").view(AllowBits)
+    a = np.asarray(allow)
+    if a.size == 0 and a.dtype != np.bool_:
+        a = a.astype(np.int64)                                  # [] -> no row allowed
+    if a.dtype == np.bool_:
+        if a.shape != (n,):
+            raise ValueError("bool mask of shape %s for a shard of %d rows" % (a.shape, n))
+        mask = a
+    elif np.issubdtype(a.dtype, np.integer):
+        if a.dtype == np.uint64 and a.size and a.max() >= np.uint64(1 << 62):
+            raise ValueError("allowed ids must lie in [%d, %d)" % (row_offset, row_offset + n))
+        ids = a.reshape(-1).astype(np.int64) - int(row_offset)
+        if ids.size and (ids.min() < 0 or ids.max() >= n):
+            raise ValueError("allowed ids must lie in [%d, %d)" % (row_offset, row_offset + n))
+        mask = np.zeros(n, np.bool_)
+        mask[ids] = True
+    else:
+        raise ValueError("allow: a bool mask, an integer id array or packed AllowBits words (got %s)" % a.dtype)
+    bits = np.packbits(mask, bitorder="little")
+    buf = np.zeros(nwords * 8, np.uint8)
+    buf[:bits.size] = bits
+    return buf.view("<u8").view(AllowBits)
+
+
+def allow_ranges(ranges, n, row_offset=0):
+    """Allow bitmap of the union of half-open GLOBAL row ranges [(r0, r1), ...] -- the row range of each dataset of a gallery
+    built by concatenating several (the reference's `--datasets A,B,...`) -- for a shard of n rows at row_offset.  The part of
+    each range inside the shard is allowed; the rest is ignored.  Raises ValueError on r0 > r1 or a negative bound."""
+    n = int(n)
+    mask = np.zeros(n, np.bool_)
+    for r0, r1 in ranges:
+        r0, r1 = int(r0), int(r1)
+        if r0 < 0 or r1 < r0:
+            raise ValueError("bad row range (%d, %d)" % (r0, r1))
+        lo, hi = max(r0 - int(row_offset), 0), min(r1 - int(row_offset), n)
+        if lo < hi:
+            mask[lo:hi] = True
+    return allow_bitmap(mask, n)
+
+
 class Gallery:
     """One gallery row shard resident on one MI355X (a `mi_gallery` handle)."""
 
@@ -305,6 +376,32 @@ class Gallery:
             check(load().mi_knn_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
                                        idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), C.byref(secs)))
         return idx, sc, secs.value
+
+    def search_filtered(self, queries, k, allow=None, allow_ptr=None):
+        """Exact top-k over the rows `allow` admits (anything allow_bitmap takes: bool mask, global ids, AllowBits words) or,
+        with allow_ptr, over a device bitmap of ceil(n / 64) uint64 words -> (idx int64 [Q,k], scores float32 [Q,k], seconds,
+        info dict: allowed, path, kprime, rerun_queries, cache_hit).  Fewer than k allowed rows: trailing ids -1, scores
+        -inf.  Ties go to the lower id; every score is the one `search` gives that row."""
+        if (allow is None) == (allow_ptr is None):
+            raise ValueError("give exactly one of allow and allow_ptr")
+        a, code, rs, cs = _strided(queries)
+        if a.shape[1] != self.d:
+            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        nq = a.shape[0]
+        if allow is not None:
+            bits = allow_bitmap(allow, self.n, self.row_offset)
+            bits_p, memspace = C.c_void_p(bits.ctypes.data), MI_HOST
+        else:
+            bits, bits_p, memspace = None, C.c_void_p(int(allow_ptr)), MI_DEVICE
+        idx = np.empty((nq, k), dtype=np.int64)
+        sc = np.empty((nq, k), dtype=np.float32)
+        secs = C.c_double()
+        info = FilterInfo()
+        with self._lock:
+            check(load().mi_knn_search_filtered(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, int(k), bits_p,
+                                                memspace, idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
+                                                C.byref(info), C.byref(secs)))
+        return idx, sc, secs.value, info.as_dict()
 
     def range_search(self, queries, min_score, max_results=None):
         """Every row whose exact score is >= min_score (inclusive), per query ->

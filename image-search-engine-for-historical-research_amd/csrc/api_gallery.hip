@@ -45,6 +45,7 @@ int mi_gallery_destroy(mi_gallery* g) {
   (void)hipFree(g->samp_f32);
   for (void* b : g->io_buf) (void)hipFree(b);
   range_scratch_free(g);
+  filter_scratch_free(g);
   (void)hipFree(g->dif_ids);
   (void)hipFree(g->dif_vals);
   if (g->stream) (void)hipStreamDestroy(g->stream);
@@ -279,6 +280,7 @@ int mi_gallery_append_device(mi_gallery* g, const float* rows_dev, int64_t m, vo
   HIPC(hipGetLastError());
   g->n += m;
   g->npad = round_up(g->n, TILE);
+  filter_invalidate(g);        // the compacted sub-gallery of the filtered search was cut from the old rows
   return MI_OK;
 }
 
@@ -323,6 +325,7 @@ int mi_gallery_append(mi_gallery* g, const void* data, int64_t m, int dtype, int
   HIPC(hipStreamSynchronize(s));          // the staging buffer is freed on return
   g->n += m;
   g->npad = round_up(g->n, TILE);
+  filter_invalidate(g);        // the compacted sub-gallery of the filtered search was cut from the old rows
   return MI_OK;
 }
 
@@ -377,6 +380,7 @@ int mi_gallery_append_whitened_device(mi_gallery* g, const void* X_dev, int64_t 
   HIPC(hipStreamSynchronize(s));           // the scratch block is freed on return
   g->n += m;
   g->npad = round_up(g->n, TILE);
+  filter_invalidate(g);        // the compacted sub-gallery of the filtered search was cut from the old rows
   return MI_OK;
 }
 
@@ -419,6 +423,7 @@ int mi_gallery_set_image_dtype(mi_gallery* g, int f16) {
   g->samp_for_n = -1;          // the bootstrap sample image is rebuilt from the new image
   ws_free(g->ws);              // the query image buffers follow the element type
   ws_free(g->ws_alt);
+  filter_invalidate(g);        // the sub-gallery's image is of the old type
   return MI_OK;
 }
 

@@ -9,6 +9,7 @@
 //   api_aux.hip       descriptor tail, whitening, k-reciprocal re-ranking, diffusion, column sums, synthetic rows
 //   api_options.hip   per-handle options, statistics, profiling, flags, diagnostics
 //   api_range.hip     exact range search: fixed-threshold chunk schedule, overflow split, dense chunks, CSR tail
+//   api_filter.hip    filtered top-K: compacted sub-gallery (cached per bitmap) or over-fetch with a certificate
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -228,6 +229,34 @@ struct mi_gallery {
     int64_t* lims = nullptr;               // [QB + 1]
     unsigned long long* total = nullptr;   // hits of the current chunk
   } range;
+  // filtered top-K search (api_filter.hip): grow-only device buffers and the compacted sub-gallery, freed with the handle, never
+  // handed to the spare-buffer slots; invalidated by mi_gallery_append* and mi_gallery_set_image_dtype (filter_invalidate)
+  int filter_path = 0;                 // option "filter_path": 0 = auto, 1 = always compact, 2 = always over-fetch
+  double filter_compact_max = 0.15;    // option "filter_compact_max": auto compacts at selectivity <= this
+  int filter_cache = 1;                // option "filter_cache": keep the sub-gallery for the next call with the same bitmap
+  struct FilterScratch {
+    uint64_t* bits = nullptr;            // device copy of a host bitmap
+    size_t bits_cap = 0;                 // words
+    uint32_t* bcnt = nullptr;            // [blocks] allowed rows per compaction workgroup, then their offsets [blocks + 1]
+    uint32_t* boff = nullptr;
+    size_t blk_cap = 0;
+    uint32_t* rows = nullptr;            // allowed local rows of the sub-gallery's bitmap, ascending
+    size_t rows_cap = 0;
+    int64_t *idx = nullptr, *sidx = nullptr;   // [nq][k] answer of the call / [nq][k_eff] answer of the sub-gallery
+    float *sc = nullptr, *ssc = nullptr;
+    size_t out_cap = 0, sout_cap = 0;    // entries
+    uint32_t* ok = nullptr;              // [nq] over-fetch certificate per query
+    size_t ok_cap = 0;
+    void* qbuf = nullptr;                // queries the over-fetch could not certify, packed
+    size_t qbuf_cap = 0;                 // bytes
+    mi_gallery* sub = nullptr;           // compacted sub-gallery (shares the parent's stream)
+    int64_t sub_cap = 0;                 // rows its buffers hold
+    bool valid = false;                  // sub holds the rows `key` allows of a parent of key_n rows
+    int64_t key_n = -1;
+    std::vector<uint64_t> key;           // the bitmap it was built from (bits at or beyond key_n cleared)
+    std::vector<uint64_t> last_key;      // the bitmap of the previous call (auto compacts a bitmap it sees twice in a row)
+    int64_t last_key_n = -1;
+  } filt;
   // diffusion state (offline matrix rows kept on the device for the online stage)
   int32_t* dif_ids = nullptr;
   float* dif_vals = nullptr;
@@ -270,3 +299,7 @@ MI_INTERNAL int dense64_search_device(mi_gallery* g, const void* q_src, int q_dt
 MI_INTERNAL int gallery_alloc(mi_gallery* g);
 // ---- api_range.hip
 MI_INTERNAL void range_scratch_free(mi_gallery* g);
+// ---- api_filter.hip
+MI_INTERNAL void filter_scratch_free(mi_gallery* g);
+MI_INTERNAL void filter_release_sub(mi_gallery* g);     // frees the compacted sub-gallery (option "filter_cache" 0)
+MI_INTERNAL void filter_invalidate(mi_gallery* g);      // rows or image type of the parent changed: the sub-gallery is stale

@@ -109,6 +109,9 @@ int mi_get_option(const mi_gallery* g, const char* name, double* out_value) {
   else if (n == "async_tail") *out_value = g->async_tail;
   else if (n == "query_norm_override") *out_value = g->qnorm_override;
   else if (n == "image_dtype") *out_value = g->img_f16;
+  else if (n == "filter_path") *out_value = g->filter_path;
+  else if (n == "filter_compact_max") *out_value = g->filter_compact_max;
+  else if (n == "filter_cache") *out_value = g->filter_cache;
   else return fail(MI_ERR_INVALID, "unknown option: " + n);
   return MI_OK;
 }
@@ -161,6 +164,23 @@ int mi_set_option(mi_gallery* g, const char* name, double value) {
   else if (n == "query_norm_override") {
     REQUIRE(value >= -1 && value <= 2, "query_norm_override: -1 or an mi_norm value");
     g->qnorm_override = (int)value;
+  }
+  else if (n == "filter_path") {
+    REQUIRE(value == 0 || value == 1 || value == 2, "filter_path: 0 (auto), 1 (compact) or 2 (over-fetch)");
+    g->filter_path = (int)value;
+  }
+  else if (n == "filter_compact_max") {
+    REQUIRE(value >= 0 && value <= 1, "filter_compact_max in [0, 1]");
+    g->filter_compact_max = value;
+  }
+  else if (n == "filter_cache") {
+    REQUIRE(value == 0 || value == 1, "filter_cache: 0 or 1");
+    g->filter_cache = (int)value;
+    if (!g->filter_cache) {                    // 0 frees the sub-gallery kept by an earlier call now, and forgets the bitmaps
+      HIPC(hipSetDevice(g->device));
+      filter_release_sub(g);
+      filter_invalidate(g);
+    }
   }
   else return fail(MI_ERR_INVALID, "unknown option: " + n);
   return MI_OK;

@@ -231,6 +231,18 @@ void launch_column_sum(const void* X, int dtype, int64_t n, int32_t d, int64_t r
 void launch_aqe_finish(const double* sum, int64_t nq, int32_t d, double eps, float* out_q, double* out_q64,
                        hipStream_t stream);
 
+// filter_select.hip -- filtered top-K search (api_filter.hip): allow bitmap -> ascending allowed rows (count, one-workgroup
+// scan, compaction), the compacted sub-gallery's rows, the over-fetch selection with its certificate, the id remap
+int64_t filter_blocks(int64_t n);   // workgroups of the count / compact kernels (bcnt holds this many, boff one more)
+void launch_filter_compact(const uint64_t* bits, int64_t n, uint32_t* bcnt, uint32_t* boff, uint32_t* rows, hipStream_t stream);
+void launch_subset_gather(const float* src_f32, const void* src_img, const RowStat* src_stat, const uint32_t* rows, int64_t m,
+                          int64_t mpad, int32_t dp, float* dst_f32, void* dst_img, RowStat* dst_stat, hipStream_t stream);
+void launch_filter_overfetch(const int64_t* in_idx, const float* in_sc, int64_t nq, int32_t kp, int32_t k, const uint64_t* bits,
+                             int64_t n, int64_t row_offset, int32_t covers, int64_t* out_idx, float* out_sc, uint32_t* ok,
+                             hipStream_t stream);
+void launch_filter_remap(const int64_t* sidx, const float* ssc, int64_t nq, int32_t ke, int32_t k, const uint32_t* rows,
+                         int64_t m, int64_t row_offset, int64_t* out_idx, float* out_sc, hipStream_t stream);
+
 // synth.hip
 void launch_synth_fill(float* dst, uint64_t seed, int64_t row0, int64_t nrows, int32_t d, hipStream_t stream);
 

@@ -21,10 +21,16 @@ class KNN:
         self.N, self.D = database.shape
         self.gallery = Gallery.from_host(database, norm_mode=NORM_NONE, device=device)
 
-    def search(self, queries, k):
+    def search(self, queries, k, allow=None):
+        """-> (sims float32 [Q,k], ids int64 [Q,k]).  allow (optional, like faiss's ID selector in the search parameters):
+        restrict the search to some rows -- a bool mask [N], an array of allowed ids, or packed AllowBits words (_lib.allow_bitmap;
+        _lib.allow_ranges for row ranges).  Fewer than k allowed rows: trailing ids -1, sims -inf."""
         queries = np.asarray(queries)
         if queries.dtype != np.float32:           # src/utils/knn.py:28-29
             queries = queries.astype(np.float32)
+        if allow is not None:
+            ids, sims, _, _ = self.gallery.search_filtered(queries, int(k), allow)
+            return sims, ids
         ids, sims, _ = self.gallery.search(queries, int(k))
         return sims, ids
 

@@ -107,6 +107,31 @@ int mi_range_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t
                     double min_score, int64_t max_results, int64_t* out_lims, int64_t* out_idx, float* out_score,
                     double* out_seconds);
 
+/* Exact filtered top-K: mi_knn_search over the rows an allow bitmap admits.  allow_bits holds ceil(n / 64) words; bit
+ * (i & 63) of word (i >> 6) allows local row i of this shard, bits at or beyond n are ignored; allow_memspace is MI_HOST or
+ * MI_DEVICE (a device bitmap must be complete when the call is made).  One bitmap applies to every query of the call.
+ * The answer is exactly mi_knn_search's over the allowed rows: ids row_offset + local row, order (score desc, id asc), and each
+ * row's f32 score bit-identical to the one mi_knn_search gives that row; with every row allowed it equals mi_knn_search bit for
+ * bit.  If fewer than k rows are allowed, the trailing entries are id -1 and score -INFINITY.  1 <= k <= 2048.  Queries, strides
+ * and dtype as in mi_knn_search (host input, host output).  out_score, out_info and out_seconds may be NULL.
+ * Two exact paths, chosen per call from the selectivity s = allowed / n (options "filter_path",
+ * "filter_compact_max"): 1 = the allowed rows are copied into a sub-gallery owned by the handle and searched (kept for the next
+ * call with an equal bitmap while option "filter_cache" is 1; dropped by mi_gallery_append* and mi_gallery_set_image_dtype);
+ * 2 = the unfiltered search at depth K' = min(2048, ceil(1.25 k / s) + 32), keeping the first k allowed entries; a query that
+ * found fewer while K' did not cover the shard is answered by path 1 instead.  Like mi_range_search, the call completes a
+ * pending deferred tail first and leaves the sticky flags (mi_search_flags) as it found them. */
+typedef struct mi_filter_info {
+  int64_t allowed;        /* rows of this shard the bitmap allows */
+  int32_t path;           /* 0 = no allowed row (nothing searched), 1 = compacted sub-gallery, 2 = over-fetch */
+  int32_t kprime;         /* over-fetch depth used (0 on path 1) */
+  int64_t rerun_queries;  /* queries the over-fetch could not certify; they were answered by path 1 */
+  int32_t cache_hit;      /* path 1 reused the sub-gallery built by an earlier call */
+} mi_filter_info;
+
+int mi_knn_search_filtered(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
+                           int32_t k, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
+                           mi_filter_info* out_info, double* out_seconds);
+
 /* Device-resident variant: q_dev [nq][d] row-major f32 (C order), outputs are device buffers.
  * out_score64_dev (may be NULL) receives the float64 exact scores. */
 int mi_knn_search_device(mi_gallery* g, const float* q_dev, int64_t nq, int32_t k,
@@ -320,7 +345,7 @@ int mi_search_status(mi_gallery* g, mi_search_stats* out, int reset); /* synchro
 /* The durations (ms, launch order) of the timed scoring launches since the last mi_search_status(reset = 1): what gemm_ms is
  * the sum of.  Waits for the launches enqueued so far; writes min(count, cap) values, *out_count = launches logged. */
 int mi_profile_launch_ms(mi_gallery* g, float* out_host, int64_t cap, int64_t* out_count);
-/* Tunables (19 names; everything that was an A/B switch of a measured-and-rejected variant -- "debug", "kernel_variant",
+/* Tunables (22 names; everything that was an A/B switch of a measured-and-rejected variant -- "debug", "kernel_variant",
  * "small_tail", "stream_lookahead", "inkernel_repair_max", "ladder" = 2 -- left the product in round 5: MI_ERR_INVALID):
  * "chunk0_tiles" (rows / 256 of the bootstrap chunk and of the threshold sample; 0 = default 32), "chunk_growth",
  * "workspace_slot" (0 | 1: which of the handle's two per-batch workspaces the phase API uses -- phase 1 of batch i + 1 may
@@ -346,7 +371,14 @@ int mi_profile_launch_ms(mi_gallery* g, float* out_host, int64_t cap, int64_t* o
  * without anybody reading flags; 0 / 1 = never / always launch the repair pass),
  * "small_batch_kernel" (0 = batches of <= 128 queries use the 256 x 256-tile kernel too),
  * "query_norm_override" (-1 | mi_norm: how the _device entry points normalise their queries; MI_NORM_NONE for the
- * already normalised expanded queries of alpha-QE).
+ * already normalised expanded queries of alpha-QE),
+ * "filter_path" (mi_knn_search_filtered: 0 = auto (default), 1 = always the compacted sub-gallery, 2 = always the over-fetch;
+ * a forced over-fetch still answers the queries it cannot certify by path 1), "filter_compact_max" (auto compacts at
+ * selectivity <= this, whenever fewer than k rows are allowed, whenever the bitmap equals the one the stored sub-gallery
+ * was built from, and -- not all rows allowed -- whenever it equals the previous call's; default 0.15, the crossover of first
+ * calls at 1 and 70 queries measured in DESIGN.md 5.10), "filter_cache" (1 = keep the compacted
+ * sub-gallery for the next call with an equal bitmap (default); 0 = free it now and at the end of every call, and do not
+ * compact a bitmap only because it came twice; a kept sub-gallery holds up to 12 KB of HBM per allowed row at D = 2048).
  * mi_get_option also answers "image_dtype" (1 = fp16, 0 = bf16; read-only, see mi_gallery_set_image_dtype) and
  * "sample_rows" (rows of the threshold sample in effect). */
 int mi_set_option(mi_gallery* g, const char* name, double value);
