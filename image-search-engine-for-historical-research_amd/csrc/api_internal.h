@@ -279,7 +279,7 @@ MI_INTERNAL int phase1_batch(mi_gallery* g, const void* q_src, int q_dtype, int6
                              int32_t k, bool exact, hipStream_t s, bool fuse_cand = false, bool caller_checks_flags = false);
 MI_INTERNAL int phase2_batch(mi_gallery* g, int32_t nq, int32_t k, const float* L_dev, int64_t* out_idx, float* out_score,
                              double* out_score64, hipStream_t s, bool have_cand = false, bool resident = false,
-                             Workspace* wsp = nullptr);
+                             Workspace* wsp = nullptr, bool flag_short = false);
 MI_INTERNAL void count_flagged_batch(mi_gallery* g, uint32_t flags);
 MI_INTERNAL int check_k(const mi_gallery* g, int32_t k);
 MI_INTERNAL int search_device(mi_gallery* g, const void* q_src, int q_dtype, int64_t q_rs, int64_t q_cs, int q_norm, int64_t nq,

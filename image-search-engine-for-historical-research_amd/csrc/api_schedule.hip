@@ -441,7 +441,7 @@ int phase1_batch(mi_gallery* g, const void* q_src, int q_dtype, int64_t q_rs, in
 // ---- phase 2 for one batch: candidates within the margin of L, exact f64 re-score, sorted emit --------
 int phase2_batch(mi_gallery* g, int32_t nq, int32_t k, const float* L_dev, int64_t* out_idx, float* out_score,
                         double* out_score64, hipStream_t s, bool have_cand, bool resident,
-                        Workspace* wsp) {
+                        Workspace* wsp, bool flag_short) {
   Workspace& ws = wsp ? *wsp : g->ws;
   QueryState st = make_state(ws);
   if (!have_cand) launch_select_candidates(st, nq, L_dev, ws.cand_rows, ws.cand_cnt, ws.rcap, ws.stats2, s);
@@ -450,8 +450,10 @@ int phase2_batch(mi_gallery* g, int32_t nq, int32_t k, const float* L_dev, int64
                                         last_row);
   else launch_rescore(g->gal_f32, ws.q_f32, g->dp, nq, ws.cand_rows, ws.cand_cnt, ws.rcap, ws.cand_score, s,
                       (uint32_t)g->rescore_grid_x, last_row);
+  // flag_short: the exhaustive search (k <= N) raises FLAG_SHORT for a query left with fewer than k candidates; the phase
+  // API does not (with a global L, one shard may hold fewer than k of the top-k)
   launch_emit(ws.cand_rows, ws.cand_cnt, ws.cand_score, ws.rcap, nq, k, g->row_offset, out_idx, out_score,
-              out_score64, s);
+              out_score64, flag_short ? st.flags : nullptr, s);
   HIPC(hipGetLastError());
   return MI_OK;
 }
@@ -482,7 +484,7 @@ int flush_pending_tail(mi_gallery* g, hipStream_t s, bool beside_scoring) {
   if (e != hipSuccess) rc = fail(MI_ERR_HIP, hipGetErrorString(e));
   if (rc == MI_OK)
     rc = phase2_batch(g, p.b, p.k, ws.L, p.out_idx, p.out_score, p.out_score64, g->tail_stream, /*have_cand=*/true,
-                      /*resident=*/true, &ws);
+                      /*resident=*/true, &ws, /*flag_short=*/true);
   if (rc == MI_OK) {
     e = hipEventRecord(g->ev_tail[p.set], g->tail_stream);
     if (e != hipSuccess) rc = fail(MI_ERR_HIP, hipGetErrorString(e));
@@ -496,7 +498,9 @@ int flush_pending_tail(mi_gallery* g, hipStream_t s, bool beside_scoring) {
 }
 
 // a batch whose sticky flags were raised: a buffer overflow (or fp16 range) and a failed speculative threshold are counted apart
+// (FLAG_SHORT is counted only alone, as an overflow: next to another flag it is that flag's consequence)
 void count_flagged_batch(mi_gallery* g, uint32_t flags) {
+  if (flags & ~(uint32_t)FLAG_SHORT) flags &= ~(uint32_t)FLAG_SHORT;
   if (flags & ~(uint32_t)FLAG_SPEC_FAIL) g->stats.overflow_batches += 1;
   else g->stats.spec_retries += 1;
 }
@@ -580,7 +584,8 @@ int search_device(mi_gallery* g, const void* q_src, int q_dtype, int64_t q_rs, i
     }
     if ((rc = phase2_batch(g, b, k, g->ws.L, out_idx + q0 * k, out_score ? out_score + q0 * k : nullptr,
                            out_score64 ? out_score64 + q0 * k : nullptr, tail, /*have_cand=*/true,
-                           /*resident=*/async && g->async_tail == 1 && b > STREAM_MAX_QUERIES)) != MI_OK)
+                           /*resident=*/async && g->async_tail == 1 && b > STREAM_MAX_QUERIES, nullptr,
+                           /*flag_short=*/true)) != MI_OK)
       return rc;
     if (async) {
       HIPC(hipEventRecord(g->ev_tail[set], tail));
@@ -670,6 +675,10 @@ int search_sync(mi_gallery* g, const void* q_dev, int q_dtype, int64_t rs, int64
       if (!flags) break;
       count_flagged_batch(g, flags);
       if (exact && g->exact_fallback && k <= 4096) continue;      // -> dense f64 path
+      if (flags == FLAG_SHORT && g->exact_fallback && k <= 4096) {    // NaN scores: the f32 filter path cannot admit them
+        attempt = 1;                                              // either -> dense f64 path
+        continue;
+      }
       if (exact || !g->exact_fallback)
         return fail(MI_ERR_OVERFLOW,
                     "candidate buffers overflowed (more than survivor_cap / rescore_cap rows within the error margin "

@@ -31,7 +31,10 @@ __host__ __device__ __forceinline__ uint32_t swz_chunk(uint32_t row, uint32_t c)
   return c ^ ((0u - (row >> 2)) & 3u);
 }
 
-// float <-> order-preserving uint32 key (larger float -> larger key); NaN maps below -inf
+// float <-> order-preserving uint32 key (larger float -> larger key); NaN maps below -inf.
+// -0 maps one below +0, while the bitonic sort (dense.hip) and the emit network treat -0 == +0.  No public entry point sees
+// the difference: every scorer's chain starts at +0, so no score is -0.  Left as is because the filter thresholds share
+// these keys.
 __device__ __forceinline__ uint32_t f2key(float f) {
   uint32_t u = __float_as_uint(f);
   if (f != f) return 0u;
@@ -85,8 +88,11 @@ struct __attribute__((aligned(16))) SurvRec {
   uint32_t pad;
 };
 
-// sticky device-side flags
-enum : uint32_t { FLAG_SURV_OVERFLOW = 1u, FLAG_CAND_OVERFLOW = 2u, FLAG_REC_OVERFLOW = 4u, FLAG_RANGE = 8u, FLAG_SPEC_FAIL = 16u };
+// sticky device-side flags.  FLAG_SHORT: a query of the exhaustive search ended with fewer than k candidates (k <= N).  A failed
+// speculative threshold or an overflow does that too, and raises its own flag; FLAG_SHORT alone means NaN scores belong in
+// the top k -- no threshold admits them -- so only the dense f64 path can answer it (NaN last, by row ascending)
+enum : uint32_t { FLAG_SURV_OVERFLOW = 1u, FLAG_CAND_OVERFLOW = 2u, FLAG_REC_OVERFLOW = 4u, FLAG_RANGE = 8u, FLAG_SPEC_FAIL = 16u,
+                  FLAG_SHORT = 32u };
 
 constexpr uint32_t CNT_STRIDE = 32;   // one survivor counter per 128-byte line (atomics to one line serialise in L2)
 

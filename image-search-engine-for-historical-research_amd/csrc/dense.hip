@@ -109,7 +109,9 @@ __global__ __launch_bounds__(512) void dense_topk_kernel(const float* __restrict
       [&](uint32_t i, uint32_t& key) { key = ~i; return f2key(row[i]) == keyK; }, n, need_ties, hist, sh);
   const uint32_t idxT = ~invT;
   // 3) collect exactly k entries
-  for (uint32_t i = threadIdx.x; i < k2; i += blockDim.x) { s[i] = -INFINITY; id[i] = 0xFFFFFFFFu; }
+  // padding [k, k2): (NaN, 0xFFFFFFFF) sorts after every selected entry, selected NaN rows included (NaNs go by index
+  // ascending).  A -inf padding would sort ahead of those NaN rows and be emitted in their place.
+  for (uint32_t i = threadIdx.x; i < k2; i += blockDim.x) { s[i] = __builtin_nanf(""); id[i] = 0xFFFFFFFFu; }
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
     const float v = row[i];
@@ -232,7 +234,8 @@ __global__ __launch_bounds__(512) void dense_topk64_kernel(const double* __restr
   const uint32_t invT = block_radix_kth_largest(
       [&](uint32_t i, uint32_t& key) { key = ~i; return d2key(row[i]) == keyK; }, n, need_ties, hist, sh);
   const uint32_t idxT = ~invT;
-  for (uint32_t i = threadIdx.x; i < k2; i += blockDim.x) { s[i] = -INFINITY; id[i] = 0xFFFFFFFFu; }
+  // padding: (NaN, 0xFFFFFFFF), as in dense_topk_kernel
+  for (uint32_t i = threadIdx.x; i < k2; i += blockDim.x) { s[i] = __builtin_nan(""); id[i] = 0xFFFFFFFFu; }
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
     const double v = row[i];

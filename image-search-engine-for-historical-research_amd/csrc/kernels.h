@@ -142,7 +142,7 @@ void launch_rescore_resident(const float* gal_f32, const float* qry_f32, int32_t
                              uint32_t last_row);
 void launch_emit(const uint32_t* cand_rows, const uint32_t* cand_cnt, const double* cand_score, uint32_t rcap,
                  int32_t nq, int32_t k, int64_t row_offset, int64_t* out_idx, float* out_score,
-                 double* out_score64, hipStream_t stream);
+                 double* out_score64, uint32_t* short_flag, hipStream_t stream);
 void launch_kth_of_gathered(const float* gathered, int32_t nshards, int64_t nq, int32_t k, float* out_L,
                             hipStream_t stream);
 void launch_merge(const double* score64, const int64_t* idx, int32_t nshards, int64_t nq, int32_t k, int64_t shard_stride,

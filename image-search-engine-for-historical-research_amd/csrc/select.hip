@@ -891,7 +891,8 @@ __global__ __launch_bounds__(256) void emit_kernel(const uint32_t* __restrict__ 
                                                    const uint32_t* __restrict__ cand_cnt,
                                                    const double* __restrict__ cand_score, uint32_t rcap, int32_t k,
                                                    int64_t row_offset, int64_t* __restrict__ out_idx,
-                                                   float* __restrict__ out_score, double* __restrict__ out_score64) {
+                                                   float* __restrict__ out_score, double* __restrict__ out_score64,
+                                                   uint32_t* __restrict__ short_flag) {
   __shared__ __attribute__((aligned(16))) uint64_t tk[EMIT_TILE];
   __shared__ __attribute__((aligned(16))) uint32_t ti[EMIT_TILE];
   __shared__ uint32_t partial[256];
@@ -906,7 +907,8 @@ __global__ __launch_bounds__(256) void emit_kernel(const uint32_t* __restrict__ 
   const double s_pre = pre_ok ? qs[threadIdx.x] : 0.0;
   const uint32_t i_pre = pre_ok ? qi[threadIdx.x] : 0u;
   const uint32_t nc = min(nc_raw, rcap);
-  // slots no candidate claims (fewer than k candidates): padding
+  // slots no candidate claims (fewer than k candidates): padding, and FLAG_SHORT where the caller asks for it
+  if (short_flag && nc < (uint32_t)k && threadIdx.x == 0) atomicOr(short_flag, FLAG_SHORT);
   for (uint32_t i = nc + threadIdx.x; i < (uint32_t)k; i += blockDim.x) {
     out_idx[(uint64_t)q * k + i] = -1;
     if (out_score) out_score[(uint64_t)q * k + i] = -INFINITY;
@@ -974,9 +976,9 @@ __global__ __launch_bounds__(256) void emit_kernel(const uint32_t* __restrict__ 
 
 void launch_emit(const uint32_t* cand_rows, const uint32_t* cand_cnt, const double* cand_score, uint32_t rcap,
                  int32_t nq, int32_t k, int64_t row_offset, int64_t* out_idx, float* out_score, double* out_score64,
-                 hipStream_t stream) {
+                 uint32_t* short_flag, hipStream_t stream) {
   hipLaunchKernelGGL(emit_kernel, dim3(nq), dim3(256), 0, stream, cand_rows, cand_cnt, cand_score, rcap, k, row_offset,
-                     out_idx, out_score, out_score64);
+                     out_idx, out_score, out_score64, short_flag);
 }
 
 // ------------------------------------------------------------------------------------------------

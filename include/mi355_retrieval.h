@@ -384,7 +384,8 @@ int mi_profile_launch_ms(mi_gallery* g, float* out_host, int64_t cap, int64_t* o
 int mi_set_option(mi_gallery* g, const char* name, double value);
 int mi_get_option(const mi_gallery* g, const char* name, double* out_value);   /* same names as mi_set_option */
 /* Synchronises the handle's work, returns the sticky device flags raised by the asynchronous _device entry points since
- * the last call (0 = none; any bit = that batch must be answered again: buffer overflow or failed speculative threshold)
+ * the last call (0 = none; any bit = that batch must be answered again: buffer overflow, failed speculative threshold, or a
+ * query left with fewer than k candidates because NaN scores -- zero rows or queries under MI_NORM_L2 -- belong in its top k)
  * and clears them.  Unlike mi_search_status it leaves the statistics accumulators alone. */
 int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
 

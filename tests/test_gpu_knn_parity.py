@@ -177,6 +177,36 @@ def test_degenerate_queries(lib):
     qq[2] /= 1e30
     s = oracle.exact_scores_f64(g.astype(np.float64) * np.where(np.arange(3000) == 5, 1e30, 1.0)[:, None], qq[[0, 2, 3]])
     assert oracle.check_topk_parity(idx[[0, 2, 3]], s, 20, 1e-5) == []
+    # the zero query's ids are still k distinct rows of the gallery (not the top-k sorter's padding id)
+    z = idx[1]
+    assert len(set(z.tolist())) == 20 and z.min() >= 0 and z.max() < 3000, z
+
+
+def test_nan_rows_fill_the_tail(lib):
+    """Zero gallery rows normalise to NaN rows (ingest.hip, like the reference).  With k above the number of finite rows
+    the search returns every finite row first, in parity with the f64 scores, then NaN rows: NaN last, distinct, by row
+    ascending -- the emit order (score desc, idx asc, NaN last)."""
+    from isehr_amd._lib import Gallery, NORM_L2
+    n, d, nq, k = 1000, 64, 3, 990
+    g = synth_rows(41, 0, n, d)
+    q = synth_rows(42, 0, nq, d)
+    nan_rows = np.sort(np.random.default_rng(43).choice(n, 30, replace=False))
+    g[nan_rows] = 0.0
+    G = Gallery.from_host(g, norm_mode=NORM_L2)
+    try:
+        idx, sc, _ = G.search(q, k)
+    finally:
+        G.close()
+    with np.errstate(all="ignore"):
+        s = oracle.exact_scores_f64(g, q)
+    nf = n - len(nan_rows)
+    assert oracle.check_topk_parity(idx[:, :nf], np.where(np.isnan(s), -np.inf, s), nf, TAU) == []
+    assert not np.isnan(sc[:, :nf]).any()
+    for j in range(nq):
+        tail = idx[j, nf:]
+        assert np.isin(tail, nan_rows).all(), tail
+        assert (np.diff(tail) > 0).all(), tail
+        assert np.isnan(sc[j, nf:]).all()
 
 
 def test_unnormalised_gallery_with_large_values_uses_bf16_image(lib):
