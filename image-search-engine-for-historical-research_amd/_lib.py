@@ -537,15 +537,19 @@ class Gallery:
                                               sims.ctypes.data_as(C.c_void_p) if return_sims else None))
         return (ids, vals, sims) if return_sims else (ids, vals)
 
-    def diffusion_offline_nodes(self, n_trunc, kd, node0, node1, alpha=0.99, gamma=3, maxiter=20, tol=1e-6):
-        """The offline rows of the nodes [node0, node1) only: -> (ids int64 [N,n_trunc], vals float32 [node1-node0,n_trunc])."""
+    def diffusion_offline_nodes(self, n_trunc, kd, node0, node1, alpha=0.99, gamma=3, maxiter=20, tol=1e-6,
+                                return_sims=False):
+        """The offline rows of the nodes [node0, node1) only: -> (ids int64 [N,n_trunc], vals float32 [node1-node0,n_trunc]
+        [, knn sims float32 [N,n_trunc]])."""
         ids = np.empty((self.n, n_trunc), dtype=np.int64)
         vals = np.empty((max(0, node1 - node0), n_trunc), dtype=np.float32)
+        sims = np.empty((self.n, n_trunc), dtype=np.float32) if return_sims else None
         with self._lock:
             check(load().mi_diffusion_offline_nodes(self._h, n_trunc, kd, float(alpha), gamma, maxiter, float(tol),
                                                     int(node0), int(node1), ids.ctypes.data_as(C.c_void_p),
-                                                    vals.ctypes.data_as(C.c_void_p), None))
-        return ids, vals
+                                                    vals.ctypes.data_as(C.c_void_p),
+                                                    sims.ctypes.data_as(C.c_void_p) if return_sims else None))
+        return (ids, vals, sims) if return_sims else (ids, vals)
 
     def diffusion_set_offline(self, ids, vals):
         ids = np.ascontiguousarray(ids, dtype=np.int64)

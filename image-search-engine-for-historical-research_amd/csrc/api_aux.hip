@@ -244,6 +244,14 @@ int mi_diffusion_set_offline(mi_gallery* g, const int64_t* ids, const float* val
     if (ids[i] < 0 || ids[i] >= g->n) return fail(MI_ERR_INVALID, "offline id outside the gallery");
     ids32[i] = (int32_t)ids[i];
   }
+  // diffusion_combine_kernel adds one offline row with a plain += per column: a column listed twice in a row would race
+  std::vector<int64_t> seen((size_t)g->n, -1);
+  for (int64_t r = 0; r < g->n; ++r)
+    for (int32_t c = 0; c < n_trunc; ++c) {
+      int64_t& at = seen[(size_t)ids32[(size_t)r * n_trunc + c]];
+      if (at == r) return fail(MI_ERR_INVALID, "offline row lists a column id twice");
+      at = r;
+    }
   (void)hipFree(g->dif_ids);
   (void)hipFree(g->dif_vals);
   g->dif_ids = nullptr;

@@ -29,9 +29,11 @@ __global__ __launch_bounds__(256) void affinity_kernel(const int64_t* __restrict
     }
     float s = sims[i * ld + j];
     s = s < 0.f ? 0.f : s;
-    float v = 1.f;
-    for (int e = 0; e < gamma; ++e) v *= s;
-    aff[i * kd + j] = mutual ? v : 0.f;
+    // sims ** gamma rounded to float32 once: a float32 product chain is up to gamma - 1 ulps off, and a two-node component
+    // of the graph (L = [[1, -alpha], [-alpha, 1]]) carries one ulp of an entry into 1e-3 of its solution
+    double v = 1.0;
+    for (int e = 0; e < gamma; ++e) v *= (double)s;
+    aff[i * kd + j] = mutual ? (float)v : 0.f;
   }
 }
 

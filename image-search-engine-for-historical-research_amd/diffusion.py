@@ -20,6 +20,22 @@ from . import evaluate
 from ._lib import Gallery, NORM_NONE
 
 
+def _cached_lists(offline, n, path):
+    """A cached offline matrix as the (ids int64 [N,n_trunc], vals [N,n_trunc]) lists the device holds.  The rows of a
+    matrix this module wrote carry exactly n_trunc stored entries each (explicit zeros kept); anything else (another
+    database's cache, a matrix with its zeros eliminated) is refused instead of being reshaped into wrong rows."""
+    if getattr(offline, "shape", None) != (n, n):
+        raise ValueError("cached offline matrix %s has shape %s, the database needs (%d, %d): delete the stale cache"
+                         % (path, getattr(offline, "shape", None), n, n))
+    csr = offline.tocsr()
+    csr.sort_indices()
+    per_row = np.diff(csr.indptr)
+    if per_row[0] < 1 or (per_row != per_row[0]).any():
+        raise ValueError("cached offline matrix %s stores between %d and %d entries per row; every row must store the "
+                         "same number (n_trunc): delete the cache and recompute" % (path, per_row.min(), per_row.max()))
+    return csr.indices.reshape(n, -1).astype(np.int64), csr.data.reshape(n, -1)
+
+
 class Diffusion:
     def __init__(self, features, cache_dir=None, device=0, group=None):
         features = np.asarray(features)
@@ -48,11 +64,8 @@ class Diffusion:
             import joblib
             offline = joblib.load(path)
             print("Loading cache: {} costs {:.2f}s".format(path, time.time() - t0))
-            csr = offline.tocsr()
-            csr.sort_indices()
-            # the rows carry exactly n_trunc stored entries each (explicit zeros kept)
-            ids = csr.indices.reshape(self.N, -1).astype(np.int64)
-            self.gallery.diffusion_set_offline(ids, csr.data.reshape(self.N, -1))
+            ids, vals = _cached_lists(offline, self.N, path)
+            self.gallery.diffusion_set_offline(ids, vals)
             self.n_trunc = ids.shape[1]
             return offline
         ids, vals = self._offline(int(n_trunc), int(kd))

@@ -253,7 +253,8 @@ int mi_diffusion_offline(mi_gallery* g, int32_t n_trunc, int32_t kd, double alph
 int mi_diffusion_offline_nodes(mi_gallery* g, int32_t n_trunc, int32_t kd, double alpha, int32_t gamma,
                                int32_t maxiter, double tol, int64_t node0, int64_t node1, int64_t* out_ids,
                                float* out_vals, float* out_knn_sims);
-/* Re-installs a cached offline result (the reference caches it as offline.jbl, src/utils/diffusion.py:21-40). */
+/* Re-installs a cached offline result (the reference caches it as offline.jbl, src/utils/diffusion.py:21-40).  Every id
+ * lies in [0, N) and no row lists an id twice (MI_ERR_INVALID otherwise). */
 int mi_diffusion_set_offline(mi_gallery* g, const int64_t* ids, const float* vals, int32_t n_trunc);
 /* Online stage (src/utils/Reranking.py:238-253): top-k_query neighbours of each query, sims**gamma, weighted sum of
  * their offline rows, top-`trunc` ranks [nq][trunc] (score desc, idx asc) and scores. */

@@ -11,6 +11,7 @@ __all__ = [
     "matching_l2", "matching_fractional_dis", "fractional_distance", "ip_rank", "feature_enhancement", "qge1", "qe_weights", "l2n", "whitenapply",
     "extract_ms_tail", "knn_flat_ip", "knn_flat_ip_blas", "compute_ap2", "compute_map2", "compute_map_revisited", "compute_map_kappas", "map_custom",
     "get_affinity", "get_laplacian", "diffusion_offline", "diffusion_online", "qge_small",
+    "diffusion_cg_dense", "diffusion_solve_nodes", "diffusion_online_dense",
     "average_query_expansion", "database_augmentation", "kr_reranking", "exact_scores_f64", "exact_topk_f64", "check_topk_parity", "merge_topk",
 ]
 
@@ -263,12 +264,16 @@ def map_custom(K, matching_idx, paths_q, paths_d):
 
 
 # --------------------------------------------------------------------------- a5
-def get_affinity(sims, ids, gamma=3):
+def get_affinity(sims, ids, gamma=3, exact_power=False):
     """a5: src/utils/diffusion.py:101-116.  sims/ids [N,kd].  Negative sims are clipped to 0,
     raised to gamma; (i, ids[i,j]) is kept iff i appears in the kd-list of ids[i,j] (mutual),
-    position 0 is always dropped (:108).  CSC float32 [N,N]."""
+    position 0 is always dropped (:108).  CSC float32 [N,N].
+    numpy's float32 power is a vector routine that differs between builds and CPUs: about a fifth of its cubes are one
+    ulp off the correctly rounded float32.  exact_power=True takes the power in float64 and rounds once, which is the
+    reproducible value (and what affinity_kernel stores); the default keeps the reference's expression as written."""
     num = sims.shape[0]
-    s = np.where(sims < 0, 0, sims) ** gamma
+    s = np.where(sims < 0, 0, sims)
+    s = (s.astype(np.float64) ** gamma).astype(np.float32) if exact_power else s ** gamma
     rr, cc, vv = [], [], []
     for i in range(num):
         mutual = np.isin(ids[ids[i]], i).any(axis=1)
@@ -277,13 +282,16 @@ def get_affinity(sims, ids, gamma=3):
             rr.append(np.full(int(mutual.sum()), i, dtype=int))
             cc.append(ids[i, mutual])
             vv.append(s[i, mutual])
+    if not rr:      # a graph without a single mutual pair (kd = 1): the reference's concatenate raises; A = 0 is what it means
+        return sp.csc_matrix((num, num), dtype=np.float32)
     rr, cc, vv = map(np.concatenate, (rr, cc, vv))
     return sp.csc_matrix((vv, (rr, cc)), shape=(num, num), dtype=np.float32)
 
 
-def get_laplacian(sims, ids, alpha=0.99):
-    """a5: src/utils/diffusion.py:87-98 -- I - alpha * D^-1/2 A D^-1/2 with deg = A@1 + 1e-12."""
-    aff = get_affinity(sims, ids)
+def get_laplacian(sims, ids, alpha=0.99, gamma=3, exact_power=False):
+    """a5: src/utils/diffusion.py:87-98 -- I - alpha * D^-1/2 A D^-1/2 with deg = A@1 + 1e-12.  (The reference never
+    passes gamma on; the keyword is for the C ABI, which takes it.)"""
+    aff = get_affinity(sims, ids, gamma, exact_power)
     num = aff.shape[0]
     deg = aff @ np.ones(num) + 1e-12
     dm = sp.dia_matrix((deg ** (-0.5), [0]), shape=(num, num), dtype=np.float32)
@@ -313,6 +321,75 @@ def diffusion_offline(features, n_trunc, kd=50, return_parts=False):
     if return_parts:
         return off, sims, ids, lap, allsc
     return off
+
+
+def diffusion_cg_dense(sub, maxiter=20, tol=1e-6):
+    """The per-node solve of src/utils/diffusion.py:15-19 written out: sub x = e0 on a dense float64 [T,T] matrix by the
+    textbook CG recurrence, x0 = 0, no preconditioner, scipy's stopping rule (||r|| < tol * ||b||, ||b|| = 1, tested at the
+    top of each iteration; at most maxiter iterations; the current iterate is returned at either exit).
+    -> (x [T] float64, iterations done at exit, min over the tests of | ||r|| - tol | / tol)."""
+    sub = np.asarray(sub, dtype=np.float64)
+    t = sub.shape[0]
+    x = np.zeros(t)
+    r = np.zeros(t)
+    r[0] = 1.0
+    p = np.zeros(t)
+    rho_prev = 0.0
+    margin = np.inf
+    it = 0
+    while it < maxiter:
+        rr = float(r @ r)
+        margin = min(margin, abs(np.sqrt(rr) - tol) / tol)
+        if np.sqrt(rr) < tol:
+            break
+        p = r.copy() if it == 0 else p * (rr / rho_prev) + r
+        q = sub @ p
+        a = rr / float(p @ q)
+        x += a * p
+        r -= a * q
+        rho_prev = rr
+        it += 1
+    return x, it, margin
+
+
+def diffusion_solve_nodes(sims, ids, kd, nodes, alpha=0.99, gamma=3, maxiter=20, tol=1e-6, lap=None, exact_power=False):
+    """The truncated solves of `nodes` on a given kNN graph (sims/ids [N,T], e.g. the lists a device search returned):
+    Laplacian of the first kd columns as the reference builds it (float32 entries), per node its [T,T] sub-matrix widened
+    to float64 and diffusion_cg_dense.  -> (x [len(nodes),T] float64, iterations [len(nodes)], margins [len(nodes)], lap)."""
+    if lap is None:
+        lap = sp.csr_matrix(get_laplacian(np.array(sims[:, :kd], dtype=np.float32), ids[:, :kd], alpha, gamma, exact_power))
+    nodes = np.asarray(nodes, dtype=np.int64)
+    t = ids.shape[1]
+    xs = np.empty((len(nodes), t))
+    its = np.empty(len(nodes), dtype=np.int64)
+    margins = np.empty(len(nodes))
+    dense = lap.toarray()                                # float32 [N,N]: the diffusion sizes are a few thousand rows
+    for r, i in enumerate(nodes):
+        sub = dense[np.ix_(ids[i], ids[i])].astype(np.float64)
+        xs[r], its[r], margins[r] = diffusion_cg_dense(sub, maxiter, tol)
+    return xs, its, margins, lap
+
+
+def diffusion_online_dense(idx, sims, off_ids, off_vals, n, gamma=3):
+    """src/utils/Reranking.py:242-253 in plain float64 on given query neighbours (idx/sims [Q,kq]) and a given offline
+    result in list form (off_ids/off_vals [N,T], ids unique within a row): dense[q] = sum_j sims[q,j]**gamma *
+    row(idx[q,j]).  -> (dense [Q,n] float64, mag [Q,n] = sum_j |w_j v_j|, dsens [Q,n] = sum_j gamma |s_j|**(gamma-1) |v_j|:
+    the magnitudes a rounding bound is built from)."""
+    idx = np.asarray(idx)
+    s = np.asarray(sims, dtype=np.float64)
+    nq, kq = idx.shape
+    dense = np.zeros((nq, n))
+    mag = np.zeros((nq, n))
+    dsens = np.zeros((nq, n))
+    for q in range(nq):
+        for j in range(kq):
+            cols = off_ids[idx[q, j]]
+            v = off_vals[idx[q, j]].astype(np.float64)
+            w = s[q, j] ** gamma
+            dense[q, cols] += w * v
+            mag[q, cols] += np.abs(w * v)
+            dsens[q, cols] += gamma * np.abs(s[q, j]) ** (gamma - 1) * np.abs(v)
+    return dense, mag, dsens
 
 
 def diffusion_online(q_for_search, features, offline, k_query=3, truncation_number=2000):

@@ -84,6 +84,22 @@ def test_diffusion_online_and_qge_small():
     head = 20
     agree = np.mean([len(set(got[:head, q]) & set(ranks_dfs[:head, q])) / head for q in range(10)])
     assert agree > 0.95, agree
+    # exact: the offline rows the device computes for these features, every row against the float64 solve, and every
+    # returned score and rank against the float64 combination of those rows
+    from _diffusion_checks import check_graph, check_offline_rows, check_online
+    from isehr_amd._lib import Gallery, NORM_NONE
+    feats = np.ascontiguousarray(vecs.T)
+    q = out["qvecs_qe"].T
+    G = Gallery.from_host(feats, norm_mode=NORM_NONE)
+    try:
+        ids, vals, sims = G.diffusion_offline(trunc, 200, return_sims=True)
+        check_graph(feats, ids, sims)
+        check_offline_rows(ids, sims, vals, 200, np.arange(900), label="qge")
+        r, s = G.diffusion_online(q, 3, 3, trunc)
+        assert np.array_equal(r.T, got) and np.array_equal(s, out["scores_dfs"])
+        check_online(G, feats, ids, vals, q, 3, 3, trunc, np.ascontiguousarray(got.T), out["scores_dfs"], label="qge")
+    finally:
+        G.close()
 
 
 def test_diffusion_cache_roundtrip(tmp_path):
