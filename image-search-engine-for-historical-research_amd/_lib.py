@@ -108,6 +108,14 @@ SIGNATURES = {
     "mi_gather_weighted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
     "mi_column_sum": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
+    "mi_column_sum_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mi_scatter_workspace_bytes": (C.c_int, [C.c_int32, c_i64p]),
+    "mi_scatter_matrix_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                           C.c_void_p]),
+    "mi_scatter_matrix": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "mi_gallery_scatter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_whiten_apply": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_int32, C.c_double, C.c_int, C.c_void_p]),
     "mi_whiten_apply_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
@@ -585,6 +593,16 @@ class Gallery:
         check(load().mi_gallery_get_rows(self._h, row0, nrows, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def scatter(self, centre=None):
+        """float64 [d, d] scatter matrix sum_n (g_n - centre)(g_n - centre)^T of the stored (normalised) rows; centre None = 0."""
+        out = np.empty((self.d, self.d), dtype=np.float64)
+        c = None if centre is None else np.ascontiguousarray(np.asarray(centre, dtype=np.float64).reshape(-1))
+        if c is not None and c.shape[0] != self.d:
+            raise ValueError("centre has %d entries, the gallery dimension is %d" % (c.shape[0], self.d))
+        check(load().mi_gallery_scatter(self._h, None if c is None else c.ctypes.data_as(C.c_void_p),
+                                        out.ctypes.data_as(C.c_void_p)))
+        return out
+
     # ---- device API (raw pointers; used by bench.py and the sharded path with torch tensors)
     def search_device(self, q_ptr, nq, k, idx_ptr, score_ptr=None, score64_ptr=None, stream=None):
         check(load().mi_knn_search_device(self._h, C.c_void_p(q_ptr), nq, k, C.c_void_p(idx_ptr),
@@ -702,6 +720,52 @@ def column_sum(rows, device=0):
     check(load().mi_column_sum(C.c_void_p(_base_pointer(a)), a.shape[0], a.shape[1], code, rs, cs, device,
                                out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def column_sum_device(x_ptr, n, d, out_ptr, dtype=MI_F32, row_stride=None, col_stride=1, stream=None):
+    """Device twin of column_sum (no synchronisation): out f64 [d]."""
+    check(load().mi_column_sum_device(C.c_void_p(x_ptr), n, d, dtype, d if row_stride is None else row_stride, col_stride,
+                                      C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+
+def scatter_workspace_bytes(d):
+    """Bytes of device workspace scatter_matrix_device needs for dimension d."""
+    b = C.c_int64()
+    check(load().mi_scatter_workspace_bytes(int(d), C.byref(b)))
+    return b.value
+
+
+def scatter_matrix(rows, centre=None, pairs=None, device=0):
+    """rows [N, D] host array (any strides; f32 | f64) -> float64 [D, D]: sum_n (x_n - centre)(x_n - centre)^T, or with
+    pairs = (q, p) index arrays sum_i (x_q_i - x_p_i)(x_q_i - x_p_i)^T.  X moves in row blocks, never whole."""
+    a, code, rs, cs = _strided(rows)
+    n, d = a.shape
+    c = None if centre is None else np.ascontiguousarray(np.asarray(centre, dtype=np.float64).reshape(-1))
+    if c is not None and c.shape[0] != d:
+        raise ValueError("centre has %d entries for %d columns" % (c.shape[0], d))
+    q = p = None
+    if pairs is not None:
+        q = np.ascontiguousarray(np.asarray(pairs[0]).reshape(-1), dtype=np.int64)
+        p = np.ascontiguousarray(np.asarray(pairs[1]).reshape(-1), dtype=np.int64)
+        if q.shape != p.shape:
+            raise ValueError("pairs: %d q indices, %d p indices" % (q.size, p.size))
+    out = np.empty((d, d), dtype=np.float64)
+    check(load().mi_scatter_matrix(C.c_void_p(_base_pointer(a)), n, d, code, rs, cs,
+                                   None if c is None else c.ctypes.data_as(C.c_void_p),
+                                   None if q is None else q.ctypes.data_as(C.c_void_p),
+                                   None if p is None else p.ctypes.data_as(C.c_void_p), 0 if q is None else q.size,
+                                   int(device), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def scatter_matrix_device(x_ptr, n, d, c_out_ptr, workspace_ptr, workspace_bytes, centre_ptr=None, pair_q_ptr=None,
+                          pair_p_ptr=None, n_pairs=0, accumulate=False, dtype=MI_F32, row_stride=None, col_stride=1,
+                          stream=None):
+    """Device-resident scatter matrix (no synchronisation): c_out f64 [d, d]; workspace of scatter_workspace_bytes(d)."""
+    check(load().mi_scatter_matrix_device(C.c_void_p(x_ptr), n, d, dtype, d if row_stride is None else row_stride, col_stride,
+                                          C.c_void_p(centre_ptr), C.c_void_p(pair_q_ptr), C.c_void_p(pair_p_ptr), n_pairs,
+                                          C.c_void_p(c_out_ptr), 1 if accumulate else 0, C.c_void_p(workspace_ptr),
+                                          int(workspace_bytes), C.c_void_p(stream)))
 
 
 def whiten_apply(rows, m, P, dims, eps=1e-6, device=0):

@@ -1,6 +1,55 @@
 // Operators beside the search: descriptor tail of the extractor, whitening, k-reciprocal re-ranking, graph diffusion,
-// column sums, synthetic rows.
+// column sums, the scatter matrix of the whitening learners (host streaming ring, device, gallery), synthetic rows.
 #include "api_internal.h"
+
+namespace {
+// Two pinned blocks, two device blocks, a copy stream and a compute stream: block b + 1 is packed on the host and copied
+// while the scatter kernel of block b runs.
+struct ScatterRing {
+  void* pin[2] = {nullptr, nullptr};
+  void* dev[2] = {nullptr, nullptr};
+  hipStream_t copy = nullptr, comp = nullptr;
+  hipEvent_t copied[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
+  ~ScatterRing() {
+    for (int i = 0; i < 2; ++i) {
+      if (pin[i]) (void)hipHostFree(pin[i]);
+      if (dev[i]) (void)hipFree(dev[i]);
+      if (copied[i]) (void)hipEventDestroy(copied[i]);
+      if (done[i]) (void)hipEventDestroy(done[i]);
+    }
+    if (copy) (void)hipStreamDestroy(copy);
+    if (comp) (void)hipStreamDestroy(comp);
+  }
+};
+
+// rows [r0, r0 + m) of the strided host matrix -> `dst`; the packed block's strides come back in *prs / *pcs.  cs == 1: one
+// memcpy per row ([m][d]); rs == 1: one memcpy per column ([d][m], the device reads it with the K-contiguous path); else
+// element by element ([m][d]).
+template <typename T>
+void pack_rows(const T* X, int64_t rs, int64_t cs, int64_t r0, int64_t m, int32_t d, T* dst, int64_t* prs, int64_t* pcs) {
+  if (cs == 1) {
+    for (int64_t r = 0; r < m; ++r) memcpy(dst + r * d, X + (r0 + r) * rs, (size_t)d * sizeof(T));
+    *prs = d, *pcs = 1;
+  } else if (rs == 1) {
+    for (int32_t c = 0; c < d; ++c) memcpy(dst + (int64_t)c * m, X + (int64_t)c * cs + r0, (size_t)m * sizeof(T));
+    *prs = 1, *pcs = m;
+  } else {
+    for (int64_t r = 0; r < m; ++r)
+      for (int32_t c = 0; c < d; ++c) dst[r * d + c] = X[(r0 + r) * rs + (int64_t)c * cs];
+    *prs = d, *pcs = 1;
+  }
+}
+template <typename T>
+void pack_pairs(const T* X, int64_t rs, int64_t cs, const int64_t* q, const int64_t* p, int64_t i0, int64_t m, int32_t d, T* dst) {
+  for (int64_t i = 0; i < m; ++i)
+    for (int side = 0; side < 2; ++side) {
+      const int64_t r = side ? p[i0 + i] : q[i0 + i];
+      T* o = dst + (2 * i + side) * d;
+      if (cs == 1) memcpy(o, X + r * rs, (size_t)d * sizeof(T));
+      else for (int32_t c = 0; c < d; ++c) o[c] = X[r * rs + (int64_t)c * cs];
+    }
+}
+}  // namespace
 
 extern "C" {
 
@@ -295,6 +344,143 @@ int mi_diffusion_online(mi_gallery* g, const void* q, int64_t nq, int dtype, int
   HIPC(hipStreamSynchronize(s));
   HIPC(hipMemcpy(out_ranks, ranks_d, (size_t)nq * trunc * 8, hipMemcpyDeviceToHost));
   if (out_scores) HIPC(hipMemcpy(out_scores, sc_d, (size_t)nq * trunc * 4, hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+int mi_column_sum_device(const void* X_dev, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                         double* out_dev, void* stream) {
+  REQUIRE(X_dev && out_dev, "null pointer");
+  REQUIRE(n >= 1 && d >= 1, "bad sizes");
+  REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  REQUIRE(row_stride >= 0 && col_stride >= 0, "negative strides are not supported");
+  launch_column_sum(X_dev, dtype, n, d, row_stride, col_stride, out_dev, (hipStream_t)stream);
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+// ---- scatter matrix (csrc/scatter.hip): the reduction in front of pcawhitenlearn / whitenlearn
+int mi_scatter_workspace_bytes(int32_t d, int64_t* bytes) {
+  REQUIRE(bytes, "null pointer");
+  REQUIRE(d >= 1, "bad sizes");
+  REQUIRE(scatter_max_splits(d) >= 1, "d too large for the scatter workspace bound (512 MiB: d <= 11520)");
+  *bytes = scatter_workspace_bytes(d);
+  return MI_OK;
+}
+
+static int scatter_check(const void* X, int64_t n, int32_t d, int dtype, int64_t rs, int64_t cs, const void* pq, const void* pp,
+                         int64_t n_pairs, const void* C) {
+  REQUIRE(X && C, "null pointer");
+  REQUIRE(n >= 1 && d >= 1, "bad sizes");
+  REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  REQUIRE(rs >= 0 && cs >= 0, "negative strides are not supported");
+  REQUIRE((pq == nullptr) == (pp == nullptr), "pair_q and pair_p must be given together");
+  REQUIRE(!pq || n_pairs >= 1, "n_pairs must be >= 1 when pairs are given");
+  REQUIRE(scatter_max_splits(d) >= 1, "d too large for the scatter workspace bound (512 MiB: d <= 11520)");
+  return MI_OK;
+}
+
+int mi_scatter_matrix_device(const void* X_dev, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                             const double* centre_dev, const int64_t* pair_q_dev, const int64_t* pair_p_dev, int64_t n_pairs,
+                             double* C_dev, int accumulate, void* workspace_dev, int64_t workspace_bytes, void* stream) {
+  int rc = scatter_check(X_dev, n, d, dtype, row_stride, col_stride, pair_q_dev, pair_p_dev, n_pairs, C_dev);
+  if (rc != MI_OK) return rc;
+  REQUIRE(workspace_dev, "null workspace (mi_scatter_workspace_bytes gives its size)");
+  REQUIRE(workspace_bytes >= scatter_workspace_bytes(d), "workspace smaller than mi_scatter_workspace_bytes(d)");
+  launch_scatter(X_dev, dtype, n, d, row_stride, col_stride, centre_dev, pair_q_dev, pair_p_dev, n_pairs, C_dev, accumulate,
+                 (double*)workspace_dev, (hipStream_t)stream);
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+
+int mi_scatter_matrix(const void* X, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                      const double* centre, const int64_t* pair_q, const int64_t* pair_p, int64_t n_pairs, int device,
+                      double* C_out) {
+  int rc = scatter_check(X, n, d, dtype, row_stride, col_stride, pair_q, pair_p, n_pairs, C_out);
+  if (rc != MI_OK) return rc;
+  const bool pairs = pair_q != nullptr;
+  if (pairs)
+    for (int64_t i = 0; i < n_pairs; ++i)
+      REQUIRE(pair_q[i] >= 0 && pair_q[i] < n && pair_p[i] >= 0 && pair_p[i] < n, "pair index outside [0, n)");
+  HIPC(hipSetDevice(device));
+  const size_t esz = dtype == MI_F32 ? 4 : 8;
+  // rows per block: option "scatter_block_rows", else 64 MiB of elements (a pair is two rows)
+  int64_t brows = g_scatter_block_rows.load();
+  if (brows <= 0) brows = std::max<int64_t>(256, ((int64_t)64 << 20) / ((int64_t)d * (int64_t)esz));
+  if (pairs) brows = std::max<int64_t>(1, brows / 2);
+  const int64_t total = pairs ? n_pairs : n;
+  brows = std::min(brows, total);
+  const size_t block_bytes = (size_t)brows * (pairs ? 2 : 1) * d * esz;
+  ScatterRing ring;
+  TmpAlloc tmp;
+  const int64_t wsb = scatter_workspace_bytes(d);
+  double* ws = tmp.get<double>((size_t)wsb / 8);
+  double* cd = tmp.get<double>((size_t)d * d);
+  double* md = centre && !pairs ? tmp.get<double>((size_t)d) : nullptr;
+  int64_t* iq = pairs ? tmp.get<int64_t>((size_t)brows) : nullptr;
+  int64_t* ip = pairs ? tmp.get<int64_t>((size_t)brows) : nullptr;
+  if (!ws || !cd || (centre && !pairs && !md) || (pairs && (!iq || !ip))) return fail(MI_ERR_NOMEM, "scatter buffers");
+  HIPC(hipStreamCreateWithFlags(&ring.copy, hipStreamNonBlocking));
+  HIPC(hipStreamCreateWithFlags(&ring.comp, hipStreamNonBlocking));
+  for (int i = 0; i < 2; ++i) {
+    HIPC(hipHostMalloc(&ring.pin[i], block_bytes, hipHostMallocDefault));
+    HIPC(device_malloc(&ring.dev[i], block_bytes + 256));
+    HIPC(hipEventCreateWithFlags(&ring.copied[i], hipEventDisableTiming));
+    HIPC(hipEventCreateWithFlags(&ring.done[i], hipEventDisableTiming));
+  }
+  if (md) HIPC(hipMemcpy(md, centre, (size_t)d * 8, hipMemcpyHostToDevice));
+  if (pairs) {
+    // the packed block holds q_i in row 2 i and p_i in row 2 i + 1: one index pattern for every block
+    std::vector<int64_t> h((size_t)brows * 2);
+    for (int64_t i = 0; i < brows; ++i) h[(size_t)i] = 2 * i, h[(size_t)(brows + i)] = 2 * i + 1;
+    HIPC(hipMemcpy(iq, h.data(), (size_t)brows * 8, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(ip, h.data() + brows, (size_t)brows * 8, hipMemcpyHostToDevice));
+  }
+  int64_t b = 0;
+  for (int64_t r0 = 0; r0 < total; r0 += brows, ++b) {
+    const int slot = (int)(b & 1);
+    const int64_t m = std::min(brows, total - r0);
+    if (b >= 2) HIPC(hipEventSynchronize(ring.copied[slot]));       // the pinned block has left for the device
+    int64_t prs = d, pcs = 1;
+    if (pairs) {
+      if (dtype == MI_F32) pack_pairs((const float*)X, row_stride, col_stride, pair_q, pair_p, r0, m, d, (float*)ring.pin[slot]);
+      else pack_pairs((const double*)X, row_stride, col_stride, pair_q, pair_p, r0, m, d, (double*)ring.pin[slot]);
+    } else {
+      if (dtype == MI_F32) pack_rows((const float*)X, row_stride, col_stride, r0, m, d, (float*)ring.pin[slot], &prs, &pcs);
+      else pack_rows((const double*)X, row_stride, col_stride, r0, m, d, (double*)ring.pin[slot], &prs, &pcs);
+    }
+    if (b >= 2) HIPC(hipStreamWaitEvent(ring.copy, ring.done[slot], 0));   // the kernel of block b - 2 has read dev[slot]
+    HIPC(hipMemcpyAsync(ring.dev[slot], ring.pin[slot], (size_t)m * (pairs ? 2 : 1) * d * esz, hipMemcpyHostToDevice, ring.copy));
+    HIPC(hipEventRecord(ring.copied[slot], ring.copy));
+    HIPC(hipStreamWaitEvent(ring.comp, ring.copied[slot], 0));
+    launch_scatter(ring.dev[slot], dtype, pairs ? 2 * m : m, d, prs, pcs, md, iq, ip, m, cd, b > 0 ? 1 : 0, ws, ring.comp);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(ring.done[slot], ring.comp));
+  }
+  HIPC(hipStreamSynchronize(ring.comp));
+  HIPC(hipMemcpy(C_out, cd, (size_t)d * d * 8, hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+int mi_gallery_scatter(const mi_gallery* g, const double* centre, double* C_out) {
+  REQUIRE(g && C_out, "null pointer");
+  REQUIRE(g->n >= 1, "empty gallery");
+  REQUIRE(scatter_max_splits(g->d) >= 1, "d too large for the scatter workspace bound (512 MiB: d <= 11520)");
+  HIPC(hipSetDevice(g->device));
+  TmpAlloc tmp;
+  const int64_t wsb = scatter_workspace_bytes(g->d);
+  double* ws = tmp.get<double>((size_t)wsb / 8);
+  double* cd = tmp.get<double>((size_t)g->d * g->d);
+  double* md = centre ? tmp.get<double>((size_t)g->d) : nullptr;
+  if (!ws || !cd || (centre && !md)) return fail(MI_ERR_NOMEM, "scatter buffers");
+  // like mi_gallery_get_rows: read-only on the handle, the rows are those of the last completed append; the blocking copies
+  // below order this call against the null stream
+  if (md) HIPC(hipMemcpy(md, centre, (size_t)g->d * 8, hipMemcpyHostToDevice));
+  HIPC(hipDeviceSynchronize());
+  launch_scatter(g->gal_f32, MI_F32, g->n, g->d, g->dp, 1, md, nullptr, nullptr, 0, cd, 0, ws, nullptr);
+  HIPC(hipGetLastError());
+  HIPC(hipDeviceSynchronize());
+  HIPC(hipMemcpy(C_out, cd, (size_t)g->d * g->d * 8, hipMemcpyDeviceToHost));
   return MI_OK;
 }
 

@@ -6,7 +6,7 @@
 //   api_gallery.hip   gallery life cycle: create / append / destroy, ingest of any layout, norm bounds, image type
 //   api_file.hip      the prepared-gallery file (MI355GAL v2): save / load, parallel copies, checksums
 //   api_entry.hip     search entry points: kNN (host / device / phases / merge), alpha-QE, dense, full-length ranking
-//   api_aux.hip       descriptor tail, whitening, k-reciprocal re-ranking, diffusion, column sums, synthetic rows
+//   api_aux.hip       descriptor tail, whitening, scatter matrix, k-reciprocal re-ranking, diffusion, column sums, synthetic rows
 //   api_options.hip   per-handle options, statistics, profiling, flags, diagnostics
 //   api_range.hip     exact range search: fixed-threshold chunk schedule, overflow split, dense chunks, CSR tail
 //   api_filter.hip    filtered top-K: compacted sub-gallery (cached per bitmap) or over-fetch with a certificate
@@ -58,6 +58,7 @@ extern MI_INTERNAL std::mutex g_spare_mu;
 extern MI_INTERNAL SpareBuffers g_spare;
 extern MI_INTERNAL SpareArena g_spare_ws;
 extern MI_INTERNAL std::atomic<int> g_keep_buffers;
+extern MI_INTERNAL std::atomic<int64_t> g_scatter_block_rows;   // mi_scatter_matrix: rows per host block (0 = 64 MiB)
 constexpr size_t SPARE_MAX_BYTES = (size_t)16 << 30;
 MI_INTERNAL void spare_release_locked();
 MI_INTERNAL void spare_ws_release_locked();

@@ -212,6 +212,14 @@ int kr_rmax();
 void launch_whiten(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, const double* m,
                    const double* P, int32_t dims, double eps, double* Y, hipStream_t stream);
 
+// scatter.hip -- scatter matrix C (+)= sum (x - c)(x - c)^T (rows) or sum (x_q - x_p)(x_q - x_p)^T (pairs), f64 MFMA, upper
+// tiles + mirror, split reduction combined in a fixed order through `workspace` (scatter_workspace_bytes(d) bytes)
+int scatter_max_splits(int32_t d);            // 0: d is beyond what the 512 MiB workspace bound allows
+int64_t scatter_workspace_bytes(int32_t d);
+void launch_scatter(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, const double* centre,
+                    const int64_t* pair_q, const int64_t* pair_p, int64_t n_pairs, double* C, int accumulate,
+                    double* workspace, hipStream_t stream);
+
 // desc_tail.hip
 void launch_desc_tail(const float* feat, int32_t b, int32_t c, int32_t hw, float p, float eps, const float* W,
                       const float* bias, int32_t c_out, float* pooled, float* out, hipStream_t stream);

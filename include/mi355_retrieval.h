@@ -293,6 +293,34 @@ int mi_whiten_apply(const void* X, int64_t n, int32_t d, int dtype, int64_t row_
  * image on v_mfma_f64_16x16x4_f64 (csrc/whiten.hip); the centring is applied while X is loaded. */
 int mi_whiten_apply_device(const void* X_dev, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
                            const double* m_dev, const double* P_dev, int32_t dims, double eps, double* out_dev, void* stream);
+/* ---- learning a whitening (src/utils/whiten.py:14-48 pcawhitenlearn / whitenlearn): the scatter matrix in front of the
+ * D x D factorisation, float64 on v_mfma_f64_16x16x4_f64 (csrc/scatter.hip).
+ *   rows mode  (pair_q == pair_p == NULL):  C (+)= sum_n (x_n - centre)(x_n - centre)^T over the n rows of X
+ *   pairs mode (both given, n_pairs >= 1):  C (+)= sum_i (x_{q_i} - x_{p_i})(x_{q_i} - x_{p_i})^T; `centre` is ignored
+ * X: n images x d, strided like mi_whiten_apply (f32 | f64, promoted and centred in float64 while it is loaded); centre f64
+ * [d] or NULL (= 0); C f64 row-major [d][d], symmetric bit for bit (only tiles on or above the diagonal are multiplied, the
+ * rest is mirrored); accumulate != 0 adds onto the C already there.  The row reduction is split over workgroups and combined
+ * in a fixed order through a workspace: two calls on the same input return the same bits.  d <= 11520.
+ * mi_scatter_workspace_bytes: bytes of device workspace one call needs for dimension d (a function of d alone, at most
+ * 512 MiB; 272 MiB at d = 2048).  mi_column_sum_device: device twin of mi_column_sum (out_dev f64 [d]), for the mean. */
+int mi_scatter_workspace_bytes(int32_t d, int64_t* bytes);
+int mi_column_sum_device(const void* X_dev, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                         double* out_dev, void* stream);
+/* Device operands, enqueued on `stream` without synchronising.  Pair indices (int64, device) outside [0, n) are clamped: a
+ * bad index costs a wrong number, never an access outside X. */
+int mi_scatter_matrix_device(const void* X_dev, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                             const double* centre_dev, const int64_t* pair_q_dev, const int64_t* pair_p_dev, int64_t n_pairs,
+                             double* C_dev, int accumulate, void* workspace_dev, int64_t workspace_bytes, void* stream);
+/* Host arrays in, host matrix out; synchronous.  X is never staged whole: row blocks (global option "scatter_block_rows",
+ * default 64 MiB each) travel through two pinned buffers, the copy of block b + 1 under the kernel of block b.  In pairs
+ * mode only the rows the pairs name are moved; a pair index outside [0, n) is MI_ERR_INVALID. */
+int mi_scatter_matrix(const void* X, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                      const double* centre, const int64_t* pair_q, const int64_t* pair_p, int64_t n_pairs, int device,
+                      double* C_out);
+/* Scatter matrix of the rows a gallery stores (after its normalisation), about `centre` (host f64 [d] or NULL): PCA whitening
+ * learned from a prepared-gallery file.  Read-only on the handle, like mi_gallery_get_rows. */
+int mi_gallery_scatter(const mi_gallery* g, const double* centre, double* C_out);
+
 /* Learned whitening straight into an appendable gallery (mi_gallery_create_empty with d = dims and MI_NORM_L2_EPS, whose
  * normalisation IS whitenapply's tail `X / (norm + 1e-6)`, src/utils/whiten.py:10): m device rows are whitened in chunks of
  * 32 768 rows into one float64 scratch block and ingested from there -- the [N, dims] float64 matrix that
