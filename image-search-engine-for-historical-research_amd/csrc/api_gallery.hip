@@ -224,13 +224,19 @@ int mi_gallery_create(const void* data, int64_t n, int32_t d, int dtype, int64_t
                      : ingest_rows_any_layout(g, src, dtype, n, g->npad, row_stride, col_stride, 0, g->stream);
     if (rc != MI_OK) return cleanup(rc);
     launch_rowstat_max(g->rowstat, n, g->gstat3, g->stream);
+    // raw (un-normalised) rows: fp16 only if they sit comfortably inside its range, otherwise re-ingest as bf16.  The maxima skip
+    // rows with a non-finite norm, so a row with an element beyond fp16's range (image norm inf) is looked for on its own;
+    // the answer goes into the fourth word of the gstat3 allocation
+    const bool raw_f16 = g->img_f16 && norm_mode == MI_NORM_NONE;
+    if (raw_f16) launch_rowstat_img_overflow(g->rowstat, n, reinterpret_cast<uint32_t*>(g->gstat3 + 3), g->stream);
     e = hipStreamSynchronize(g->stream);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess || !g->img_f16 || norm_mode != MI_NORM_NONE) break;
-    // raw (un-normalised) rows: fp16 only if they sit comfortably inside its range, otherwise re-ingest as bf16
-    float gs[3] = {0, 0, 0};
-    e = hipMemcpy(gs, g->gstat3, 12, hipMemcpyDeviceToHost);
-    if (e != hipSuccess || (gs[0] <= 4.0f && std::isfinite(gs[1]))) break;
+    if (e != hipSuccess || !raw_f16) break;
+    float gs[4] = {0, 0, 0, 0};
+    e = hipMemcpy(gs, g->gstat3, 16, hipMemcpyDeviceToHost);
+    uint32_t overflow = 0;
+    memcpy(&overflow, &gs[3], 4);
+    if (e != hipSuccess || (gs[0] <= 4.0f && !overflow)) break;
     g->img_f16 = 0;
   }
   if (e != hipSuccess) return cleanup(fail(MI_ERR_HIP, std::string("ingest: ") + hipGetErrorString(e)));
@@ -254,7 +260,10 @@ int mi_gallery_create_empty(int64_t capacity, int32_t d, int norm_mode, int devi
   g->img_f16 = (norm_mode == MI_NORM_NONE) ? 0 : g_default_img_f16.load();   // raw rows of unknown range: bf16 image
   int rc = gallery_alloc(g);
   if (rc == MI_OK) {
+    // the appends write the image and the rounding norms of the appended rows only: rows n..npad of both are saved and
+    // checksummed, and the buffers may be a destroyed gallery's (spare slot) or recycled device memory
     hipError_t e = hipMemset(g->gal_img, 0, (size_t)round_up(capacity, TILE) * g->dp * 2);
+    if (e == hipSuccess) e = hipMemset(g->rowstat, 0, (size_t)round_up(capacity, TILE) * sizeof(RowStat));
     if (e == hipSuccess) e = hipMemset(g->gstat3, 0, 12);
     if (e != hipSuccess) rc = fail(MI_ERR_HIP, std::string("memset: ") + hipGetErrorString(e));
   }

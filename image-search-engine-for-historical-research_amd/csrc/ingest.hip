@@ -967,6 +967,18 @@ __global__ __launch_bounds__(256) void rowstat_max_kernel(const RowStat* __restr
   }
 }
 
+// rowstat_max_kernel skips rows with a non-finite norm, so a row whose f32 norm is finite but whose IMAGE norm is not -- a raw
+// element beyond fp16's range became inf -- is invisible in the maxima: this is what reports it
+__global__ __launch_bounds__(256) void rowstat_img_overflow_kernel(const RowStat* __restrict__ rowstat, int64_t n,
+                                                                   uint32_t* __restrict__ flag) {
+  bool hit = false;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const RowStat r = rowstat[i];
+    hit |= isfinite(r.norm_f32) && !isfinite(r.norm_img);
+  }
+  if (hit) atomicOr(flag, 1u);
+}
+
 void launch_ingest(const void* src, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, int norm_mode,
                    float* out_f32, void* out_img, int img_f16, RowStat* rowstat, int32_t dp, int64_t npad,
                    hipStream_t stream, int64_t row_base) {
@@ -1107,6 +1119,11 @@ void launch_rowstat_max(const RowStat* rowstat, int64_t n, float* out3, hipStrea
   hipLaunchKernelGGL(rowstat_max_kernel, dim3(blocks), dim3(256), 0, stream, rowstat, n, out3);
 }
 
+void launch_rowstat_img_overflow(const RowStat* rowstat, int64_t n, uint32_t* flag, hipStream_t stream) {
+  hipMemsetAsync(flag, 0, sizeof(uint32_t), stream);
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(512, (n + 255) / 256));
+  hipLaunchKernelGGL(rowstat_img_overflow_kernel, dim3(blocks), dim3(256), 0, stream, rowstat, n, flag);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Bootstrap sample image: n_s rows drawn one per stratum of N / n_s consecutive rows at a hashed offset, copied

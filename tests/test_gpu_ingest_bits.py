@@ -5,7 +5,11 @@ header) and the norm maxima of seeded galleries as the round-4 ingest kernel pro
 (scripts/make_ingest_checksums.py, run before the round-5 rewrite).  The round-5 kernels -- one wave per row for rows that are
 contiguous in memory, a one-pass panel kernel for the reference's [D, N] layout (callers hand over `vecs.T`,
 src/test_rOP1m.py:155-157, src/online.py:96,132) -- and the block / append paths must all reproduce them: same summation
-order for every norm, hence bit-identical galleries, hence identical answers by construction."""
+order for every norm, hence bit-identical galleries, hence identical answers by construction.
+
+What this module pins is STABILITY: across kernels, layouts and entry points the bits stay those of the ancestor kernel.  That
+those bits are CORRECT -- rows, image and rounding norms against a float64 reference computed from the source rows -- is pinned
+by tests/test_gpu_gallery_reference.py."""
 import importlib.util
 import json
 import os
