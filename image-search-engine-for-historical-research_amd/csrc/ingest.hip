@@ -17,15 +17,10 @@
 #include "common.h"
 #include "kernels.h"
 
-#ifndef MI_INGEST_PROBE
-#define MI_INGEST_PROBE 0      // scripts/ingestbench.hip: 1 = no rounding statistics, 2 = no f32 row store, 4 = no image store
-#endif
-// consecutive rows one workgroup of the persistent gallery ingest takes per turn (scripts/ingestbench.hip sweeps it)
-#ifndef MI_INGEST_RUN
-#define MI_INGEST_RUN 4
-#endif
-
 namespace mi {
+
+// consecutive rows one workgroup of the persistent gallery ingest takes per turn (swept 2 .. 32: profiles/r04j_ingest_run_sweep.txt)
+constexpr int INGEST_RUN = 4;
 
 // 16-bit image element: fp16 (11-bit significand: 8x smaller rounding error, same MFMA rate) or bf16 (f32 range)
 __device__ __forceinline__ uint16_t cvt_img(float v, int f16, double& back) {
@@ -147,7 +142,6 @@ __device__ __forceinline__ double xor_lane_f64(double x) {
   else if constexpr (O == 2) return dpp_mov_f64<0x4E>(x);                   // quad_perm [2, 3, 0, 1]
   else if constexpr (O == 4) return dpp_mov_f64<0x1B>(dpp_mov_f64<0x141>(x));   // row_half_mirror, quad_perm [3, 2, 1, 0]
   else if constexpr (O == 8) return dpp_mov_f64<0x141>(dpp_mov_f64<0x140>(x));  // row_mirror, row_half_mirror
-  else if constexpr ((MI_INGEST_PROBE & 256) != 0) return __shfl_xor(x, O);      // A/B: the LDS crossbar for 16 / 32
   else {
     // 16 / 32: gfx950's v_permlane16_swap / v_permlane32_swap exchange the odd rows (the upper half) of one register with the
     // even rows (the lower half) of another; fed the same value twice they return [x0 x0 x2 x2] / [x1 x1 x3 x3] (rows) resp.
@@ -248,17 +242,13 @@ __global__ __launch_bounds__(256) void ingest_query_kernel(const InT* __restrict
 #pragma unroll
     for (int j = 0; j < PT; ++j) {
       const int c = t + 256 * j;
-#if MI_INGEST_PROBE & 64
-      nxt[j] = (InT)(rr + c);
-#else
       nxt[j] = src[rr * rs + (int64_t)(c < d ? c : d - 1) * cs];     // replaced by 0 where it is USED (no wait here)
-#endif
     }
   };
   // rows of a workgroup come in runs of RUN consecutive rows (run i of workgroup b starts at (i * gridDim.x + b) * RUN): one
   // row's piece of a slice block of the image is 64 bytes, and consecutive rows of a tile are neighbours in it, so a run
   // written by ONE workgroup fills whole 256-byte stretches in ONE XCD's L2 instead of leaving half lines in eight of them
-  constexpr int64_t RUN = INIT ? 1 : MI_INGEST_RUN;
+  constexpr int64_t RUN = INIT ? 1 : INGEST_RUN;
   auto row_of = [&](int64_t it) { return ((it / RUN) * (int64_t)gridDim.x + blockIdx.x) * RUN + it % RUN; };
   request(row_of(0));
   for (int64_t it = 0;; ++it) {
@@ -283,21 +273,13 @@ __global__ __launch_bounds__(256) void ingest_query_kernel(const InT* __restrict
     for (int j = 0; j < PT; ++j)
       if (t + 256 * j < d) ss += v[j] * v[j];
     // the one-value form of block_sum3 (same adds in the same order; two thirds of its shuffles carried zeros here)
-#if !(MI_INGEST_PROBE & 32)
     wave_butterfly(ss);
     __syncthreads();
     if (lane == 0) red[0][wv] = ss;
     __syncthreads();
     ss = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-#endif
-#if MI_INGEST_PROBE & 8
-    scale = ss * 1e-3;
-    if (false)
-#endif
-    {
     const double nrm = sqrt(ss);
     scale = (norm_mode == 1) ? 1.0 / nrm : 1.0 / (nrm + 1e-6);
-    }
   }
 #pragma unroll
   for (int j = 0; j < PT; ++j)
@@ -319,26 +301,18 @@ __global__ __launch_bounds__(256) void ingest_query_kernel(const InT* __restrict
     for (int e = 0; e < 8; ++e) {
       double vb;
       pk.h[e] = cvt_img(vf[e], img_f16, vb);
-#if !(MI_INGEST_PROBE & 1)
       s_b += vb * vb;
       s_d += (vb - (double)vf[e]) * (vb - (double)vf[e]);
       s_g += (double)vf[e] * (double)vf[e];
-#endif
     }
-#if !(MI_INGEST_PROBE & 4)
     *reinterpret_cast<uint4*>(blk + (swz_chunk(r, ch) << 3)) = pk.u;
-#else
-    if (pk.u.x == 0x12345678u) *reinterpret_cast<uint4*>(blk) = pk.u;
-#endif
-    if (valid && !(MI_INGEST_PROBE & 2)) {
+    if (valid) {
       float4* o = reinterpret_cast<float4*>(out_f32 + orow * dp + c0);
       o[0] = lo;
       o[1] = hi;
     }
   }
-#if !(MI_INGEST_PROBE & 16)
   block_sum3(s_g, s_b, s_d);
-#endif
   if (t == 0) {
     RowStat rsd;
     rsd.norm_f32 = (float)(sqrt(s_g) * (1.0 + 1e-6));
@@ -410,7 +384,7 @@ __global__ __launch_bounds__(256) void ingest_query_kernel(const InT* __restrict
 //       per-wave image stores compiled in; 152 registers: three waves per SIMD (the generic instantiations take what they need).
 // PREFETCH: the wave's next row is requested into the registers of the current one as soon as those are consumed.
 // Launch-to-launch, the same launch on the same box takes 3.5-4.1 ms depending on where the driver put the three buffers (one
-// process: +-0.5 %; scripts/ingest_context_probe.py, profiles/r05o_*): compare kernels inside ONE process (scripts/ingest_ab.sh).
+// process: +-0.5 %; scripts/ingest_context_probe.py, profiles/r05o_*): compare kernels inside ONE process.
 template <typename InT, int PT, bool PREFETCH, bool FULL>
 __global__ __launch_bounds__(256, FULL ? 3 : 1) void ingest_rows_kernel(const InT* __restrict__ src, int64_t n, int32_t d, int64_t rs, int norm_mode,
                                                           float* __restrict__ out_f32, uint16_t* __restrict__ out_img,
@@ -551,7 +525,7 @@ __global__ __launch_bounds__(256, FULL ? 3 : 1) void ingest_rows_kernel(const In
           for (int ii = 0; ii < 4; ++ii) *reinterpret_cast<float4*>(buf + 4 * (lane ^ ((lane >> 4) & 1)) + 256 * ii) = y[4 * q + ii];
 #pragma unroll
           for (int ii = 0; ii < 4; ++ii)
-            if ((FULL || 4 * lane + 256 * (4 * q + ii) < dp) && !(MI_INGEST_PROBE & 2))
+            if (FULL || 4 * lane + 256 * (4 * q + ii) < dp)
               *reinterpret_cast<float4*>(orow_p + 256 * (4 * q + ii)) = y[4 * q + ii];
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
@@ -573,21 +547,15 @@ __global__ __launch_bounds__(256, FULL ? 3 : 1) void ingest_rows_kernel(const In
               for (int e = 0; e < 8; ++e) {
                 double vb;
                 pk.hh[e] = cvt_img(vf[e], F16 ? 1 : 0, vb);
-#if !(MI_INGEST_PROBE & 1)
                 s_b[k] = __builtin_fma(vb, vb, s_b[k]);
                 const double df = vb - (double)vf[e];
                 s_d[k] = __builtin_fma(df, df, s_d[k]);
                 s_g[k] = __builtin_fma((double)vf[e], (double)vf[e], s_g[k]);
-#endif
               }
               const uint32_t sl = (uint32_t)c0 / SLICE_K, ch = ((uint32_t)c0 % SLICE_K) >> 3;
-#if !(MI_INGEST_PROBE & 4)
               // (round 6) row slot wv ^ (sl & 3): the four slices a 16-lane group writes no longer share their four 16-byte slots
               if (coop) wimg[par][sl][wv ^ (sl & 3)][swz_chunk(r, ch)] = pk.u;
               else *reinterpret_cast<uint4*>(tile_base + (int64_t)sl * SLICE_ELEMS + (swz_chunk(r, ch) << 3)) = pk.u;
-#else
-              if (pk.u.x == 0x12345678u) *reinterpret_cast<uint4*>(tile_base) = pk.u;
-#endif
             }
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -603,7 +571,7 @@ __global__ __launch_bounds__(256, FULL ? 3 : 1) void ingest_rows_kernel(const In
       const float nf = (float)(sqrt(mine) * (1.0 + 1e-6));      // rounded UP a little: upper bounds after the f32 conversion
       if (lane == 0 || lane == 8 || lane == 4) reinterpret_cast<float*>(rowstat + orow)[lane == 0 ? 0 : (lane == 8 ? 1 : 2)] = nf;
     }
-    if (coop && !(MI_INGEST_PROBE & 4)) {
+    if (coop) {
       // (`run` is the same for the four waves of the workgroup: the barrier is uniform; a last run of fewer than four rows --
       // an appended block of any length -- copies its own rows only)
       __syncthreads();
@@ -690,9 +658,6 @@ __global__ __launch_bounds__(768) void ingest_cols_kernel(const InT* __restrict_
     const InT* cp = src + (int64_t)(lw * CPW + csub) * cs + first + 4 * rq;
 #pragma unroll
     for (int j = 0; j < NLD; ++j, cp += (int64_t)4 * CPW * cs) {
-#if MI_INGEST_PROBE & 16384
-      for (int e = 0; e < 4; ++e) t[j][e] = (InT)(first + j + e);
-#else
       if constexpr (sizeof(InT) == 4) {
         const f4u x = *reinterpret_cast<const f4u*>(cp);
         t[j][0] = x.x; t[j][1] = x.y; t[j][2] = x.z; t[j][3] = x.w;
@@ -700,7 +665,6 @@ __global__ __launch_bounds__(768) void ingest_cols_kernel(const InT* __restrict_
         const d2u a = *reinterpret_cast<const d2u*>(cp), c2 = *reinterpret_cast<const d2u*>(cp + 2);
         t[j][0] = a.x; t[j][1] = a.y; t[j][2] = c2.x; t[j][3] = c2.y;
       }
-#endif
     }
   };
   auto to_lds = [&](InT (*t)[4]) {
@@ -792,7 +756,7 @@ __global__ __launch_bounds__(768) void ingest_cols_kernel(const InT* __restrict_
       y.w = (float)((double)cur[i][3] * scale);
       const int wc4 = ((4 * lane + 256 * i) ^ swz) >> 2;              // 16-byte chunk of the scaled row; stored at c ^ ((c >> 4) & 1):
       *reinterpret_cast<float4*>(buf + 4 * (wc4 ^ ((wc4 >> 4) & 1))) = y;   // see ingest_rows_kernel (every lane has read its raw values)
-      if (!(MI_INGEST_PROBE & 2)) *reinterpret_cast<float4*>(orow_p + 256 * i) = y;
+      *reinterpret_cast<float4*>(orow_p + 256 * i) = y;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -830,7 +794,7 @@ __global__ __launch_bounds__(768) void ingest_cols_kernel(const InT* __restrict_
   };
   auto copy_out = [&](int64_t p, int j0) {                       // the image of run j0 + pr: 256 contiguous bytes per slice and 16 lanes
     const int64_t run_row = p * R + 4 * (j0 + pr);
-    if (!coop || run_row >= nrows || (MI_INGEST_PROBE & 4)) return;
+    if (!coop || run_row >= nrows) return;
     const int64_t orow0 = row_base + run_row;                    // a multiple of 4 (coop): one tile, one swizzle for the run
     const uint32_t r0 = (uint32_t)(orow0 % TILE);
     uint16_t* run_base = out_img + (orow0 / TILE) * NSL * (int64_t)SLICE_ELEMS + (int64_t)r0 * SLICE_K;
@@ -866,7 +830,7 @@ __global__ __launch_bounds__(768) void ingest_cols_kernel(const InT* __restrict_
     __syncthreads();                                             // A
 #pragma unroll
     for (int j0 = 0; j0 < RQ; j0 += 2) {
-      if (!(MI_INGEST_PROBE & 8192)) process_row(p, j0);
+      process_row(p, j0);
       __syncthreads();                                           // B: the image of these two runs is staged
       copy_out(p, j0);
       __syncthreads();                                           // C: the staging may be rewritten / the panel replaced
@@ -982,12 +946,12 @@ __global__ __launch_bounds__(256) void rowstat_img_overflow_kernel(const RowStat
 void launch_ingest(const void* src, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, int norm_mode,
                    float* out_f32, void* out_img, int img_f16, RowStat* rowstat, int32_t dp, int64_t npad,
                    hipStream_t stream, int64_t row_base) {
-  if (cs == 1 && dp <= 256 * QI_MAX_PER_THREAD && npad < (int64_t)1 << 31 && !(MI_INGEST_PROBE & 512)) {
+  if (cs == 1 && dp <= 256 * QI_MAX_PER_THREAD && npad < (int64_t)1 << 31) {
     // rows contiguous in memory (row-major source: device-generated galleries, appended descriptor batches, re-imaging of the
     // stored rows): one WAVE per row, one pass (round 5; the sums of the kernel below, bit for bit)
     const size_t esz = dtype == 0 ? 4 : 8;
     const int vec_ok = (d % 4 == 0) && ((rs * esz) % 16 == 0) && (((uintptr_t)src) % 16 == 0);
-    const int coop = (row_base % 4 == 0) && !(MI_INGEST_PROBE & 2048);
+    const int coop = row_base % 4 == 0;
 #define MI_GR_LAUNCH(T, PT, PF, FULL)                                                                                    \
   do {                                                                                                                  \
     /* occupancy of this instantiation: the same on every (identical) device of the node; cached in an atomic */        \
@@ -999,10 +963,8 @@ void launch_ingest(const void* src, int dtype, int64_t n, int32_t d, int64_t rs,
         occ = 2;                                                                                                        \
       occ_cache.store(occ, std::memory_order_relaxed);                                                                  \
     }                                                                                                                   \
-    if (MI_INGEST_PROBE && getenv("MI_INGEST_WG_PER_CU")) occ = atoi(getenv("MI_INGEST_WG_PER_CU"));                    \
-    if (MI_INGEST_PROBE) fprintf(stderr, "ingest (wave per row): %d workgroups per CU\n", occ);                         \
     const unsigned grid = (unsigned)std::min<int64_t>((npad + 3) / 4, (int64_t)current_device_cus() * occ);             \
-    const int xcd_walk = grid % 8 == 0 && (npad + 3) / 4 >= 8 * (int64_t)grid && !(MI_INGEST_PROBE & 32768);            \
+    const int xcd_walk = grid % 8 == 0 && (npad + 3) / 4 >= 8 * (int64_t)grid;                                       \
     hipLaunchKernelGGL((ingest_rows_kernel<T, PT, PF, FULL>), dim3(grid), dim3(256), 0, stream, (const T*)src, n, d,    \
                        rs, norm_mode, out_f32, (uint16_t*)out_img, img_f16, rowstat, dp, npad, row_base, vec_ok, coop,  \
                        xcd_walk);                                                                                       \
@@ -1019,7 +981,7 @@ void launch_ingest(const void* src, int dtype, int64_t n, int32_t d, int64_t rs,
 #undef MI_GR_LAUNCH
     return;
   }
-  if (rs == 1 && cs != 1 && d == 2048 && dp == 2048 && n >= 16 && !(MI_INGEST_PROBE & 4096)) {
+  if (rs == 1 && cs != 1 && d == 2048 && dp == 2048 && n >= 16) {
     // the reference's [D, N] layout: one pass, rows rebuilt in LDS by loader waves, consumed by the row body (ingest_cols_kernel)
     const int coop = row_base % 4 == 0;
     const unsigned grid = (unsigned)std::max<int64_t>(8, current_device_cus() / 8 * 8);      // one workgroup per CU, whole XCD labels
@@ -1055,9 +1017,7 @@ void launch_ingest(const void* src, int dtype, int64_t n, int32_t d, int64_t rs,
         occ = 4;                                                                                                        \
       occ_cache.store(occ, std::memory_order_relaxed);                                                                  \
     }                                                                                                                   \
-    if (MI_INGEST_PROBE && getenv("MI_INGEST_WG_PER_CU")) occ = atoi(getenv("MI_INGEST_WG_PER_CU"));                    \
-    if (MI_INGEST_PROBE) fprintf(stderr, "ingest: %d workgroups per CU\n", occ);                                        \
-    const unsigned grid = (unsigned)std::min<int64_t>((npad + MI_INGEST_RUN - 1) / MI_INGEST_RUN,                          \
+    const unsigned grid = (unsigned)std::min<int64_t>((npad + INGEST_RUN - 1) / INGEST_RUN,                          \
                                                       (int64_t)current_device_cus() * occ);                               \
     hipLaunchKernelGGL((ingest_query_kernel<T, false, PT>), dim3(grid), dim3(256), 0, stream, (const T*)src, n, d, rs,  \
                        cs, norm_mode, out_f32, (uint16_t*)out_img, img_f16, rowstat, dp, none, row_base);               \

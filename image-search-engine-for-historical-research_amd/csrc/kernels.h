@@ -37,11 +37,7 @@ struct ScoreArgs {
   int32_t nqt;            // query tiles (qpad / 256)
   int64_t n;              // valid gallery rows in the shard
   int32_t nq;             // valid queries
-  int32_t debug = 0;      // scripts/kbench.hip (-DMI_KBENCH builds) only: diagnostic instantiation; the product passes 0
   int32_t small_batch_kernel;   // 1: launches with <= STREAM_MAX_QUERIES queries go to stream_select.hip
-  int32_t variant = 0;          // scripts/kbench.hip (-DMI_KBENCH builds) only: A/B instantiation; the product passes 0
-  int32_t walk = 0;             // tile kernel: 0 = every XCD label walks all query tiles of its gallery range; 1 = labels 2y, 2y + 1
-                                // share a range and take half of the query tiles each (A/B, gemm_select.hip)
   SurvRec* rec;           // [grid * 8 waves][rec_cap] wave-private survivor records of this launch
   uint32_t* rec_cnt;      // [grid * 8]
   uint32_t rec_cap;
@@ -58,7 +54,8 @@ struct ScoreArgs {
                                      // written by the query ingest): small batches have 32 .. 64 bootstrap workgroups of 64
                                      // serial slices each otherwise.  The sum order is then not fixed -- the sample scores
                                      // feed the speculative (verified) threshold and the ladder level only
-  unsigned long long* dbg; // diagnostics (DBG & 8): per-wave cycle sums, [grid * 8][8]
+  unsigned long long* dbg; // tile kernel, per wave [grid * 8][8]: word 3 = records emitted, 4 = XCC id, 5 = K-slices done, 6 = shader
+                           // cycles, 7 = 10-ns ticks around the main loop (kernel_clock_mhz, the XCD shares); null: not written
   QueryState st;
 };
 // stream_select.hip: the scoring + filter launch for small query batches (HBM-bound; same records and thresholds)
@@ -114,7 +111,6 @@ void launch_init_query_state(const RowStat* qstat, const float* gstat3, int32_t 
 // mode 0: maintain (threshold <- K-th largest - margin, compact survivors)
 // mode 1: maintain + write the K largest approximate values to topvals[q][K] and L_local[q]
 // thresholds from the 2048 / 4096 / 8192-score bootstrap sample (single-launch schedule), cheaper than launch_select_maintain(mode 0)
-void set_tail_debug_phase(int phase);   // diagnostics only (scripts/tailbench.hip): selection kernels return after phase N; 0 = product
 bool sample_threshold_applies(uint32_t first_cnt, int32_t k, int32_t spec_r);
 // the r-th / (4 r)-th / lad_r-th largest of n sample scores per query read from scores[q * ld + i] (samples too large for a survivor row)
 void launch_sample_threshold_big(QueryState st, const float* scores, uint32_t ld, uint32_t n, int32_t nq, int32_t k,

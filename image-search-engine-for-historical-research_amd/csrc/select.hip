@@ -13,10 +13,6 @@
 
 namespace mi {
 
-// diagnostics (scripts/tailbench.hip): the selection kernels return after phase N of their work; 0 = run to the end (product)
-static int g_tail_debug_phase = 0;
-void set_tail_debug_phase(int phase) { g_tail_debug_phase = phase; }
-
 int ensure_dynamic_lds(const void* kernel, int bytes) {
   static std::mutex mu;
   static std::set<std::pair<const void*, int>> done;
@@ -221,7 +217,7 @@ __global__ __launch_bounds__(MAINT_THREADS) void select_maintain_kernel(QuerySta
                                                                         const uint32_t* __restrict__ cond,
                                                                         uint32_t* __restrict__ cand_rows,
                                                                         uint32_t* __restrict__ cand_cnt, uint32_t rcap,
-                                                                        int dbg_phase, RepairScan rs) {
+                                                                        RepairScan rs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   if (cond && *cond == 0) return;
   const uint32_t q = blockIdx.x;
@@ -252,7 +248,6 @@ restart:
   }
   auto rest_at = [&](uint32_t i) -> uint32_t { return f2key(entry_score(gsurv[i])); };       // keys beyond the LDS part
   auto key_at = [&](uint32_t i) -> uint32_t { return i < lds_keys ? keys[i] : rest_at(i); };
-  if (dbg_phase == 1) { if (ent[0] == 1ull && n == 0xFFFFFFFFu) st.flags[3] = 1; return; }
   if (threadIdx.x == 0) { sh[2] = 0; sh[3] = 0; }
   __syncthreads();                                  // all entries are in registers from here on
   float L = -INFINITY;
@@ -263,7 +258,6 @@ restart:
   }
   float thr_new = L - margin_q;
   float thr2 = thr_new;
-  if (dbg_phase == 2) { if (threadIdx.x == 0) l_local[q] = L; return; }
   if (MODE == 0 && spec_r > 0 && n >= (uint32_t)k) {
     // the spec_r-th and (4 spec_r)-th largest lie among the keys >= keyL (spec_r, 4 spec_r < k): gather those (k plus
     // ties, normally ~k) into the histogram scratch and rank them by counting instead of two more full radix selects
@@ -379,7 +373,6 @@ restart:
     }
   }
   __syncthreads();
-  if (dbg_phase == 3) return;
   if (MODE == 1) {
     const uint32_t have = (n >= (uint32_t)k) ? sh[3] : n;
     const float fill = (n >= (uint32_t)k) ? L : -INFINITY;
@@ -430,7 +423,7 @@ void launch_select_maintain(QueryState st, int32_t nq, int32_t k, int mode, floa
   auto go = [&](auto kern) {
     ensure_dynamic_lds((const void*)kern);                     // survivor_cap = 16384 needs 66.6 KB
     hipLaunchKernelGGL(kern, dim3(nq), dim3(MAINT_THREADS), lds, stream, st, k, topvals, l_local, stats2, spec_r, spec,
-                       repair, cond, cand_rows, cand_cnt, rcap, g_tail_debug_phase, rs);
+                       repair, cond, cand_rows, cand_cnt, rcap, rs);
   };
   const uint32_t per_thread = (st.cap + MAINT_THREADS - 1) / MAINT_THREADS;
   if (mode == 1 && repair == 3 && scan) {                      // in-kernel repair (small batches, asynchronous entry points)
@@ -491,7 +484,7 @@ constexpr int SAMP_THREADS = 512;                          // x SAMP_PER_THREAD 
                                                            // (round 6: the sample of shards beyond 160 x 8192 rows; 4-byte scores only)
 template <int SAMP_PER_THREAD>
 __global__ __launch_bounds__(SAMP_THREADS) void sample_threshold_kernel(QueryState st, int32_t k, int32_t spec_r,
-                                                                        int32_t lad_r, int32_t f32_scores, int dbg_phase,
+                                                                        int32_t lad_r, int32_t f32_scores,
                                                                         float order_slack) {
   constexpr int LDS_PER = SAMP_PER_THREAD < 16 ? SAMP_PER_THREAD : 16;
   __shared__ uint32_t keys[SAMP_THREADS * LDS_PER];           // only used by the fallback (up to 32 KiB; keys beyond: from memory)
@@ -510,7 +503,6 @@ __global__ __launch_bounds__(SAMP_THREADS) void sample_threshold_kernel(QuerySta
     kv[j] = (i < n) ? f2key(f32_scores ? reinterpret_cast<const float*>(gsurv)[i] : entry_score(gsurv[i])) : 0u;
     kmax = max(kmax, kv[j]);
   }
-  if (dbg_phase == 1) { if (kmax == 1u && n == 0xFFFFFFFFu) st.flags[3] = 1; return; }
   const uint32_t w1 = (uint32_t)spec_r, w2 = (uint32_t)min(4 * spec_r, k);   // wanted ranks, w1 <= w2 <= 256
   uint32_t* maxima = keys;                                  // 512 keys
   maxima[threadIdx.x] = kmax;
@@ -518,7 +510,6 @@ __global__ __launch_bounds__(SAMP_THREADS) void sample_threshold_kernel(QuerySta
   __syncthreads();
   const uint32_t t0 = block_kth_largest(maxima, SAMP_THREADS, w2, hist);
   __syncthreads();
-  if (dbg_phase == 2) { if (threadIdx.x == 0 && t0 == 1u) st.flags[3] = 1; return; }
 #pragma unroll
   for (int j = 0; j < SAMP_PER_THREAD; ++j)
     if (kv[j] >= t0 && kv[j] != 0u) {
@@ -627,19 +618,19 @@ void launch_sample_threshold(QueryState st, int32_t nq, int32_t k, int32_t spec_
                              int32_t lad_r, int32_t f32_scores, float order_slack) {
   if (first_cnt == SAMP_THREADS * 2u)
     hipLaunchKernelGGL(sample_threshold_kernel<2>, dim3(nq), dim3(SAMP_THREADS), 0, stream, st, k, spec_r, lad_r, f32_scores,
-                       g_tail_debug_phase, order_slack);
+                       order_slack);
   else if (first_cnt == SAMP_THREADS * 4u)
     hipLaunchKernelGGL(sample_threshold_kernel<4>, dim3(nq), dim3(SAMP_THREADS), 0, stream, st, k, spec_r, lad_r, f32_scores,
-                       g_tail_debug_phase, order_slack);
+                       order_slack);
   else if (first_cnt == SAMP_THREADS * 8u)
     hipLaunchKernelGGL(sample_threshold_kernel<8>, dim3(nq), dim3(SAMP_THREADS), 0, stream, st, k, spec_r, lad_r, f32_scores,
-                       g_tail_debug_phase, order_slack);
+                       order_slack);
   else if (first_cnt == SAMP_THREADS * 16u)
     hipLaunchKernelGGL(sample_threshold_kernel<16>, dim3(nq), dim3(SAMP_THREADS), 0, stream, st, k, spec_r, lad_r, f32_scores,
-                       g_tail_debug_phase, order_slack);
+                       order_slack);
   else
     hipLaunchKernelGGL(sample_threshold_kernel<48>, dim3(nq), dim3(SAMP_THREADS), 0, stream, st, k, spec_r, lad_r, f32_scores,
-                       g_tail_debug_phase, order_slack);
+                       order_slack);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -771,10 +762,7 @@ __global__ __launch_bounds__(256, 6) void rescore_resident_kernel(const float* _
                                                                int32_t dp, int32_t nq, const uint32_t* __restrict__ cand_rows,
                                                                const uint32_t* __restrict__ cand_cnt, uint32_t rcap,
                                                                double* __restrict__ cand_score, uint32_t sub,
-                                                               uint32_t last_row, uint32_t dbg) {
-#ifndef MI_RESIDENT_PROBE
-  dbg = 0u;                                                  // product build: the probe branches below are compiled out
-#endif
+                                                               uint32_t last_row) {
   const int lane = threadIdx.x & 63;
   const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
   const int nvec = dp >> 2;
@@ -786,21 +774,11 @@ __global__ __launch_bounds__(256, 6) void rescore_resident_kernel(const float* _
     double* outs = cand_score + (uint64_t)q * rcap;
     for (uint32_t c = part * 2; c < nc; c += 2 * sub) {
       const bool two = (c + 1 < nc);
-      uint32_t r0 = min(rows[c], last_row), r1 = min(rows[two ? c + 1 : c], last_row);
-      if (dbg & 2u) { r0 = c & 63u; r1 = (c + 1) & 63u; }                 // diagnostics: no gather (64 rows, cache-resident)
+      const uint32_t r0 = min(rows[c], last_row), r1 = min(rows[two ? c + 1 : c], last_row);
       const float4* g0 = reinterpret_cast<const float4*>(gal + (uint64_t)r0 * dp);
       const float4* g1 = reinterpret_cast<const float4*>(gal + (uint64_t)r1 * dp);
       double a0 = 0.0, a1 = 0.0;
       int v = lane;
-      if (dbg & 1u) {                                                       // diagnostics: the loads without the arithmetic
-        float f0 = 0.f, f1 = 0.f;
-        for (; v < nvec; v += 64) {
-          const float4 y0 = nt_load4(g0 + v), y1 = nt_load4(g1 + v);
-          f0 += y0.x + y0.w;
-          f1 += y1.x + y1.w;
-        }
-        a0 = f0; a1 = f1;
-      }
       // two 16-byte loads per row in flight per lane (4 KiB per wave): the launch must stay within the 80 VGPRs the tile
       // kernel leaves free on a SIMD (2 x 216 of 512), and it has a whole scoring launch to move its bytes in
       for (; v + 64 < nvec; v += 128) {
@@ -843,20 +821,11 @@ __global__ __launch_bounds__(256, 6) void rescore_resident_kernel(const float* _
 void launch_rescore_resident(const float* gal_f32, const float* qry_f32, int32_t dp, int32_t nq, const uint32_t* cand_rows,
                              const uint32_t* cand_cnt, uint32_t rcap, double* cand_score, hipStream_t stream,
                              uint32_t last_row) {
-  unsigned grid = (unsigned)current_device_cus();
-  // The probes of scripts/resident_probe.sh (1 = loads without the f64 arithmetic, 2 = arithmetic without the gather, 4 = a
-  // quarter of the CUs host the tail; results wrong by construction) exist only in a library built with -DMI_RESIDENT_PROBE:
-  // the product build has no path on which an environment variable could change the exact re-score.
-#ifdef MI_RESIDENT_PROBE
-  static const uint32_t dbg = [] { const char* e = getenv("MI_RESIDENT_DEBUG"); return e ? (uint32_t)atoi(e) : 0u; }();
-#else
-  constexpr uint32_t dbg = 0u;
-#endif
-  if (dbg & 4u) grid /= 4;
+  const unsigned grid = (unsigned)current_device_cus();
   uint32_t sub = 1;
   while ((uint64_t)nq * sub * 2 <= (uint64_t)grid * 4) sub *= 2;      // every wave of the grid gets a share
   hipLaunchKernelGGL(rescore_resident_kernel, dim3(grid), dim3(256), 0, stream, gal_f32, qry_f32, dp, nq, cand_rows,
-                     cand_cnt, rcap, cand_score, sub, last_row, dbg);
+                     cand_cnt, rcap, cand_score, sub, last_row);
 }
 
 // grid_x: workgroups (of 2 candidates) per query and sweep, 0 = default.  Workgroups beyond a query's count exit at once and

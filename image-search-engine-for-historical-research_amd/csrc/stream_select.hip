@@ -253,7 +253,7 @@ static void launch_stream_variant(const ScoreArgs& a, hipStream_t stream) {
 }
 
 bool stream_select_applies(const ScoreArgs& a) {
-  return a.small_batch_kernel && a.nqt == 1 && a.nq <= STREAM_MAX_QUERIES && a.debug == 0;
+  return a.small_batch_kernel && a.nqt == 1 && a.nq <= STREAM_MAX_QUERIES;
 }
 
 template <int NQB, bool F16>
@@ -263,7 +263,7 @@ static void launch_stream_mode(const ScoreArgs& a, bool first, hipStream_t strea
   return launch_stream_variant<NQB, F16, 0>(a, stream);
 }
 
-bool stream_bootstrap_applies(const ScoreArgs& a) { return a.small_batch_kernel && a.debug == 0; }
+bool stream_bootstrap_applies(const ScoreArgs& a) { return a.small_batch_kernel; }
 
 void launch_stream_select(const ScoreArgs& a, bool first, hipStream_t stream) {
   // bootstrap launches are one workgroup per (sample tile, group of NQB * 16 queries): with <= 512 queries the narrower

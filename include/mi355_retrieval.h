@@ -476,8 +476,8 @@ int mi_debug_xcc_shares(mi_gallery* g, float* out_w8, int32_t* out_launches);
 int mi_debug_online_clients(mi_online* o, const float* desc_dev, int32_t n_desc, int32_t threads, int32_t per_thread,
                             int64_t* out_last_idx, double* out_seconds);
 /* Diagnostics only: the per-wave words the tile kernel leaves behind, layout [workgroups * 8][8]: word 5 = K-slices done, word 6 =
- * shader cycles and word 7 = 10-ns ticks around the main loop (what kernel_clock_mhz and the XCD shares are computed from); words
- * 0-4 are written by the stamped build of scripts/kbench.hip only. */
+ * shader cycles and word 7 = 10-ns ticks around the main loop (what kernel_clock_mhz and the XCD shares are computed from); word 3 =
+ * records the wave emitted, word 4 = the XCC id it ran on; words 0-2 are not written. */
 int mi_debug_read_cycles(mi_gallery* g, uint64_t* out_host, int64_t count);
 
 /* Diagnostics only: the gallery row that sample row i of the bootstrap sample image is drawn from (shard of n rows, sample

@@ -28,7 +28,7 @@ __device__ __forceinline__ unsigned long long stamp() {
   return t;
 }
 
-template <int WAVES, int MODE, int ORDER>
+template <int WAVES, int MODE, int ISSUE>
 __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void probe(const f16x8* __restrict__ src, float* __restrict__ sink,
                                                                unsigned long long* __restrict__ clk, int iters) {
   const int tid = threadIdx.x, lane = tid & 63;
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) void probe(const f16x8* __re
     constexpr int REP = (MODE == 2) ? 2 : 1;
 #pragma unroll
     for (int rep = 0; rep < REP; ++rep) {
-      if (ORDER == 0) {
+      if (ISSUE == 0) {
 #pragma unroll
         for (int mb = 0; mb < 8; ++mb)
 #pragma unroll
@@ -159,7 +159,7 @@ __global__ void fill(uint16_t* p, size_t n, float scale) {
   }
 }
 
-template <int WAVES, int MODE, int ORDER, int SHAPE = 0>
+template <int WAVES, int MODE, int ISSUE, int SHAPE = 0>
 static void run(const char* name, const f16x8* src, float* sink, unsigned long long* clk, int iters, int grid) {
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
@@ -168,7 +168,7 @@ static void run(const char* name, const f16x8* src, float* sink, unsigned long l
   for (int r = 0; r < 4; ++r) {
     CK(hipEventRecord(e0, nullptr));
     if (SHAPE == 0)
-      hipLaunchKernelGGL((probe<WAVES, MODE, ORDER>), dim3(grid), dim3(WAVES * 64), 0, nullptr, src, sink, clk, iters);
+      hipLaunchKernelGGL((probe<WAVES, MODE, ISSUE>), dim3(grid), dim3(WAVES * 64), 0, nullptr, src, sink, clk, iters);
     else
       hipLaunchKernelGGL((probe32<WAVES, MODE>), dim3(grid), dim3(WAVES * 64), 0, nullptr, src, sink, clk, iters);
     CK(hipEventRecord(e1, nullptr));

@@ -46,20 +46,17 @@ python scripts/ladder_probe.py > $o/${tag}_ladder_probe.txt 2> /dev/null || true
 bash scripts/layout_model.sh > $o/${tag}_layout_model.txt 2> /dev/null || true
 echo "scripts done"
 fi
-# 4. kernel A/B driver and MFMA probe (C++, no torch)
+# 4. standalone driver of the scoring launches and MFMA probe (C++, no torch)
 if st 4; then
 bash scripts/kbench_build.sh > /dev/null 2>&1 || true    # the driver shares struct layouts with the library: never run a stale one
 (cd image-search-engine-for-historical-research_amd && ./build/mfma_probe > ../$o/${tag}_mfma_probe.txt 2>&1 || true)
-KB="default:0 structure1:0:1 zc:0:5 zc_inter:0:6 inter:0:7 g_nt:0:10 g_sc1:0:11 g_sc0sc1:0:12 both_nt:0:13 q_nt:0:14 g_sc0:0:16 pairs:0:20 pairs_nt:0:21 nofilter:4 nofilter_s1:4:1 nofilter_noA:36 nofilter_noB:68 noB_Bonce:16452 directB_model:49220 nodma:5 nodma_nofrag:133 filter_stamps:2048 stamps_inter:2048:6"
-(cd image-search-engine-for-historical-research_amd && timeout -k 10 400 ./build/kbench --rounds 4 --reps 5 $KB > ../$o/${tag}_kbench.txt 2>&1 || true)
-# fabric traffic and L2 hit rate per variant (round 4: which operand's DMA costs what, cache policies, paired-XCD walk)
-(timeout -k 10 400 bash scripts/kbench_pmc.sh ${tag} default:0 g_nt:0:10 g_sc1:0:11 q_nt:0:14 pairs_nt:0:21 nofilter:4 nofilter_noA:36 nofilter_noB:68 directB_model:49220 > $o/${tag}_kbench_pmc.log 2>&1 || true)
+(cd image-search-engine-for-historical-research_amd && timeout -k 10 400 ./build/kbench --rounds 4 --reps 5 1024 300 256 129 70 1 > ../$o/${tag}_kbench.txt 2>&1 || true)
 (timeout -k 10 200 python scripts/gap_probe.py 2> /dev/null | grep -v amdgpu > $o/${tag}_gap_probe.txt || true)
 (timeout -k 10 300 python scripts/first_launches.py 40 2> /dev/null | grep -v amdgpu > $o/${tag}_first_launches.txt || true)
 (timeout -k 10 900 python scripts/shard_model_10m.py > $o/${tag}_shard_model_10m.txt 2>&1 || true)
 (cd image-search-engine-for-historical-research_amd && timeout -k 10 200 ./build/tile4_probe --rounds 3 --reps 5 > ../$o/${tag}_tile4_probe.txt 2>&1 || true)
 (cd image-search-engine-for-historical-research_amd && timeout -k 10 200 ./build/tailbench --reps 50 > ../$o/${tag}_tailbench.txt 2>&1 || true)
-(cd image-search-engine-for-historical-research_amd && for t in 0.0663 0.0700 0.0760; do timeout -k 10 100 ./build/kbench --rounds 2 --reps 5 --thr $t default:0 | tail -1; done > ../$o/${tag}_kbench_thr.txt 2>&1 || true)
+(cd image-search-engine-for-historical-research_amd && for t in 0.0663 0.0700 0.0760; do timeout -k 10 100 ./build/kbench --rounds 2 --reps 5 --thr $t 1024 | tail -1; done > ../$o/${tag}_kbench_thr.txt 2>&1 || true)
 fi
 # 5. multi-rank rehearsal of bench.py (ranks share the GPU, gloo)
 if st 5; then
@@ -82,15 +79,15 @@ fi
 if st 7; then
 (for sd in 101 102 103 104; do ISEHR_SWEEP_SEED=$sd timeout -k 10 600 python -m pytest tests/test_gpu_shape_sweep.py -q 2>&1 | tail -1; done) > $o/${tag}_sweep_seeds.txt || true
 fi
-# 8. the gallery ingest kernels alone (round 5): times, probes and -- in separate passes -- the fabric read / write traffic of one launch
+# 8. the gallery ingest kernels alone (round 5): times and -- in separate passes -- the fabric read / write traffic of one launch
 # of each layout (rocprofv3 --pmc with --kernel-trace only; the program itself after --)
 if st 8; then
 P=image-search-engine-for-historical-research_amd/build
-for pr in 128 134 130 132 640; do /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -DMI_INGEST_PROBE=$pr scripts/ingestbench.hip -o $P/ingestbench$pr 2> /dev/null; done
-(for l in rows cols cols:1006016; do for pr in 128 134 130 132; do timeout -k 10 60 $P/ingestbench$pr 1005994 2048 $l 2>&1 | grep probe | tail -1; done; done; timeout -k 10 60 $P/ingestbench640 1005994 2048 rows 2>&1 | grep probe | tail -1) > $o/${tag}_ingestbench.txt 2>&1 || true
+/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 scripts/ingestbench.hip -o $P/ingestbench 2> /dev/null
+(for l in rows cols cols:1006016; do timeout -k 10 60 $P/ingestbench 1005994 2048 $l 2>&1 | grep -E '^ingest|^copy' | tail -2; done) > $o/${tag}_ingestbench.txt 2>&1 || true
 for l in rows cols; do
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $o/${tag}_ingest_${l}_fetch -- $P/ingestbench128 1005994 2048 $l > $o/${tag}_ingest_${l}_fetch.log 2>&1 || true
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $o/${tag}_ingest_${l}_write -- $P/ingestbench128 1005994 2048 $l > $o/${tag}_ingest_${l}_write.log 2>&1 || true
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $o/${tag}_ingest_${l}_fetch -- $P/ingestbench 1005994 2048 $l > $o/${tag}_ingest_${l}_fetch.log 2>&1 || true
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $o/${tag}_ingest_${l}_write -- $P/ingestbench 1005994 2048 $l > $o/${tag}_ingest_${l}_write.log 2>&1 || true
 done
 python scripts/ingest_pmc_report.py $tag > $o/${tag}_ingest_pmc.txt 2>&1 || true
 echo "ingest done"

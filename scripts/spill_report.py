@@ -14,7 +14,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "image-search-engine-for-historical-research_amd", "csrc", "gemm_select.hip")
-want = sys.argv[1] if len(sys.argv) > 1 else "gemm_tile_kernelILb0ELi0ELb1ELb0ELi3E"
+want = sys.argv[1] if len(sys.argv) > 1 else "gemm_tile_kernelILb0ELb1ELb0ELb0EE"
 
 with tempfile.TemporaryDirectory() as td:
     out = os.path.join(td, "k.s")

@@ -191,7 +191,6 @@ int main(int argc, char** argv) {
     hipLaunchKernelGGL(fill_u32, dim3(4), dim3(256), 0, 0, st.cnt, (size_t)nq, 8192u, (uint32_t)CNT_STRIDE);
     hipLaunchKernelGGL(fill_f32, dim3(4), dim3(256), 0, 0, st.thr, (size_t)nq, -INFINITY);
   };
-  for (int qv = 0; qv < nq; ++qv) {}
   {
     // scores of query q at ((float*)(surv + q * cap))[i]
     hipLaunchKernelGGL(fill_scores_f32, dim3(2048), dim3(256), 0, 0, (float*)st.surv, (size_t)nq * cap * 2, 3ull, 0.0221f);
@@ -202,14 +201,6 @@ int main(int argc, char** argv) {
       launch_sample_threshold(st, nq, k, 10, 8192u, nullptr, 3, 1);
     });
     time_train("  (the two re-arm launches alone)", reps, [&] { prep_sample(); });
-    for (int ph = 1; ph <= 2; ++ph) {
-      set_tail_debug_phase(ph);
-      time_train(ph == 1 ? "  sample_threshold up to: loads + maxima" : "  sample_threshold up to: W-th of the 512 maxima", reps, [&] {
-        prep_sample();
-        launch_sample_threshold(st, nq, k, 10, 8192u, nullptr, 3, 1);
-      });
-    }
-    set_tail_debug_phase(0);
   }
   // ---- maintain MODE 1 on ~900 survivors per query (speculative verification on, candidate lists fused)
   auto prep_maint = [&] {
@@ -225,14 +216,6 @@ int main(int argc, char** argv) {
     launch_select_maintain(st, nq, k, 1, topvals, L, stats2, 0, 1, 0, nullptr, nullptr, cand_rows, cand_cnt, rcap);
   });
   time_train("  (the four re-fill launches alone)", reps, [&] { prep_maint(); });
-  for (int ph = 1; ph <= 3; ++ph) {
-    set_tail_debug_phase(ph);
-    time_train(ph == 1 ? "  maintain up to: entries + keys loaded" : ph == 2 ? "  maintain up to: K-th largest" : "  maintain up to: compaction + topvals", reps, [&] {
-      prep_maint();
-      launch_select_maintain(st, nq, k, 1, topvals, L, stats2, 0, 1, 0, nullptr, nullptr, cand_rows, cand_cnt, rcap);
-    });
-  }
-  set_tail_debug_phase(0);
   // ---- exact re-score of 127 candidates per query (1 M-row f32 gallery) and emit
   hipLaunchKernelGGL(fill_cand, dim3(nq), dim3(256), 0, 0, cand_rows, cand_score, rcap, 127u, nrows, 5ull);
   hipLaunchKernelGGL(fill_u32, dim3(4), dim3(256), 0, 0, cand_cnt, (size_t)nq, 127u, 1u);
@@ -241,7 +224,7 @@ int main(int argc, char** argv) {
     launch_rescore(gal, qry, dp, nq, cand_rows, cand_cnt, rcap, cand_score, nullptr, 0, nrows - 1);
   });
   time_train("emit (127 candidates -> top 100)", reps, [&] {
-    launch_emit(cand_rows, cand_cnt, cand_score, rcap, nq, k, 0, out_idx, out_score, nullptr, nullptr);
+    launch_emit(cand_rows, cand_cnt, cand_score, rcap, nq, k, 0, out_idx, out_score, nullptr, nullptr, nullptr);
   });
   time_train("  emit_probe<0> loads + stores", reps, [&] { hipLaunchKernelGGL(emit_probe<0>, dim3(nq), dim3(256), 0, 0, cand_rows, cand_cnt, cand_score, rcap, k, out_idx, out_score); });
   time_train("  emit_probe<1> + LDS staging, barrier", reps, [&] { hipLaunchKernelGGL(emit_probe<1>, dim3(nq), dim3(256), 0, 0, cand_rows, cand_cnt, cand_score, rcap, k, out_idx, out_score); });
@@ -249,7 +232,7 @@ int main(int argc, char** argv) {
   time_train("  emit_probe<3> + result stores", reps, [&] { hipLaunchKernelGGL(emit_probe<3>, dim3(nq), dim3(256), 0, 0, cand_rows, cand_cnt, cand_score, rcap, k, out_idx, out_score); });
   time_train("rescore + emit", reps, [&] {
     launch_rescore(gal, qry, dp, nq, cand_rows, cand_cnt, rcap, cand_score, nullptr, 0, nrows - 1);
-    launch_emit(cand_rows, cand_cnt, cand_score, rcap, nq, k, 0, out_idx, out_score, nullptr, nullptr);
+    launch_emit(cand_rows, cand_cnt, cand_score, rcap, nq, k, 0, out_idx, out_score, nullptr, nullptr, nullptr);
   });
   (void)d;
   return 0;

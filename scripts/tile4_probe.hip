@@ -3,7 +3,7 @@
 // product's data path: the same tile-blocked fp16 images, 256 x 256 workgroup tile, XCD-aware tile order, K-slices of 32
 // moved by global_load_lds_dwordx4 into LDS rings that never drain, counted vmcnt, raw s_barrier.  No survivor filter: at
 // the end of a tile every accumulator is added into a checksum (the cost of the filter's "decide" step, roughly), so the
-// row to compare with is the product kernel WITHOUT its filter (kbench `nofilter:4`).  Diagnostics only; not part of the
+// row to compare with is the product kernel WITHOUT its filter (kbench `nofilter:4` of the trees up to the laboratory's removal, scripts/README.md).  Diagnostics only; not part of the
 // library.  Build: scripts/kbench_build.sh.  Usage: tile4_probe [--rows N] [--reps K] [--bf16]
 //
 // What differs from the product (csrc/gemm_select.hip, gemm_tile_kernel), by necessity:

@@ -94,9 +94,9 @@ def test_ragged_batches_answer_like_the_full_batch(lib, img):
 
 
 def test_laboratory_switches_are_not_in_the_product(lib):
-    """Round 5: the diagnostic / A-B instantiations of the tile kernel (stages switched off, other issue orders, DMA cache
-    policies, the paired-XCD walk, the first structure) are compiled into scripts/kbench.hip's own program only
-    (-DMI_KBENCH), which also checks that they emit the same records.  The library holds six instantiations and the options
+    """The diagnostic / A-B instantiations of the tile kernel (stages switched off, other issue orders, DMA cache policies,
+    the paired-XCD walk, the first structure) are not in the source any more: their records are under profiles/ and the
+    last commit that can re-run them is named in scripts/README.md.  The library holds eight instantiations and the options
     that selected the others -- or variants measured to lose: the one-launch small tail, the lookahead, a second ladder level,
     in-kernel repair of large batches -- are errors."""
     raw = _device_rows(lib, 41, 5000, 64)
