@@ -16,7 +16,9 @@ LIB_PATH = os.path.join(HERE, "libmi355_retrieval.so")
 MI_F32, MI_F64 = 0, 1
 MI_HOST, MI_DEVICE = 0, 1
 NORM_NONE, NORM_L2, NORM_L2_EPS = 0, 1, 2
+MI_ERR_INVALID, MI_ERR_UNSUPPORTED = 1, 6
 MI_ERR_CAPACITY = 7
+METRIC_IP, METRIC_L2 = 0, 1
 
 c_i64p = C.POINTER(C.c_int64)
 c_f32p = C.POINTER(C.c_float)
@@ -67,6 +69,14 @@ SIGNATURES = {
                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_knn_search_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(FilterInfo), c_f64p]),
+    "mi_gallery_create_l2": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                       C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "mi_knn_search_l2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FilterInfo), c_f64p]),
+    "mi_knn_search_l2_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "mi_knn_dense64_search_l2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_knn_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "mi_knn_phase1_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -301,6 +311,28 @@ class Gallery:
         check(load().mi_gallery_create_empty(capacity, d, norm_mode, device, row_offset, C.byref(h)))
         return cls(h.value)
 
+    @classmethod
+    def l2_from_host(cls, rows, device=0, row_offset=0, capacity=0, d=None):
+        """Squared-L2 gallery (mi_gallery_create_l2) of rows [N, D] float32/float64, any strides, stored as given.
+        capacity 0 = N; capacity > N leaves room for append() / append_device(); rows None (with d and capacity) = empty."""
+        h = C.c_void_p()
+        if rows is None:
+            check(load().mi_gallery_create_l2(None, 0, int(d), MI_F32, int(d), 1, MI_HOST, device, row_offset, int(capacity),
+                                              C.byref(h)))
+        else:
+            a, code, rs, cs = _strided(rows)
+            check(load().mi_gallery_create_l2(C.c_void_p(_base_pointer(a)), a.shape[0], a.shape[1], code, rs, cs, MI_HOST,
+                                              device, row_offset, int(capacity), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def l2_from_device_ptr(cls, ptr, n, d, device=0, row_offset=0, capacity=0, dtype=MI_F32, row_stride=None, col_stride=1):
+        """Device rows -> squared-L2 gallery, synchronous; the producer of `ptr` must have completed (see from_device_ptr)."""
+        h = C.c_void_p()
+        check(load().mi_gallery_create_l2(C.c_void_p(ptr), n, d, dtype, d if row_stride is None else row_stride, col_stride,
+                                          MI_DEVICE, device, row_offset, int(capacity), C.byref(h)))
+        return cls(h.value)
+
     def append_device(self, rows_ptr, m, stream=None):
         """rows_ptr: device pointer to [m, d] float32 (C order)."""
         with self._lock:
@@ -410,6 +442,48 @@ class Gallery:
                                                 memspace, idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
                                                 C.byref(info), C.byref(secs)))
         return idx, sc, secs.value, info.as_dict()
+
+    def search_l2(self, queries, k, allow=None):
+        """Exact squared-L2 top-k of a gallery built by l2_from_host -> (ids int64 [Q,k], dist float32 [Q,k], dist64 float64
+        [Q,k], info dict, seconds): distances ascending, ties to the lower id, fewer than k rows -> ids -1, distances +inf.
+        allow: anything allow_bitmap takes (bool mask, global ids, AllowBits words) restricts the search to those rows."""
+        a, code, rs, cs = _strided(queries)
+        if a.shape[1] != self.d:
+            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        nq, k = a.shape[0], int(k)
+        bits = None if allow is None else allow_bitmap(allow, self.n, self.row_offset)
+        idx = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float32)
+        dist64 = np.empty((nq, k), dtype=np.float64)
+        secs = C.c_double()
+        info = FilterInfo()
+        with self._lock:
+            check(load().mi_knn_search_l2(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
+                                          None if bits is None else C.c_void_p(bits.ctypes.data), MI_HOST,
+                                          idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
+                                          dist64.ctypes.data_as(C.c_void_p), C.byref(info), C.byref(secs)))
+        return idx, dist, dist64, info.as_dict(), secs.value
+
+    def dense64_search_l2(self, queries, k):
+        """Every direct-form float64 distance of the gallery + exact top-k (no threshold logic): the independent checker of
+        search_l2.  -> (ids int64 [Q,k], dist float32 [Q,k], dist64 float64 [Q,k], seconds)."""
+        a, code, rs, cs = _strided(queries)
+        if a.shape[1] != self.d:
+            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        nq, k = a.shape[0], int(k)
+        idx = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float32)
+        dist64 = np.empty((nq, k), dtype=np.float64)
+        secs = C.c_double()
+        with self._lock:
+            check(load().mi_knn_dense64_search_l2(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
+                                                  idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
+                                                  dist64.ctypes.data_as(C.c_void_p), C.byref(secs)))
+        return idx, dist, dist64, secs.value
+
+    def search_l2_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, dist64_ptr=None, stream=None):
+        check(load().mi_knn_search_l2_device(self._h, C.c_void_p(q_ptr), nq, k, C.c_void_p(idx_ptr), C.c_void_p(dist_ptr),
+                                             C.c_void_p(dist64_ptr), C.c_void_p(stream)))
 
     def range_search(self, queries, min_score, max_results=None):
         """Every row whose exact score is >= min_score (inclusive), per query ->

@@ -230,6 +230,7 @@ int mi_kr_rerank(const void* qvecs, int64_t nq, int64_t q_row_stride, int64_t q_
 int mi_diffusion_offline(mi_gallery* g, int32_t n_trunc, int32_t kd, double alpha, int32_t gamma, int32_t maxiter,
                          double tol, int64_t* out_ids, float* out_vals, float* out_knn_sims) {
   REQUIRE(g, "null handle");
+  REFUSE_L2(g, "mi_diffusion_offline");
   return mi_diffusion_offline_nodes(g, n_trunc, kd, alpha, gamma, maxiter, tol, 0, g->n, out_ids, out_vals, out_knn_sims);
 }
 
@@ -241,6 +242,7 @@ int mi_diffusion_offline_nodes(mi_gallery* g, int32_t n_trunc, int32_t kd, doubl
   REQUIRE(n_trunc >= 2 && (int64_t)n_trunc <= g->n && n_trunc <= 4096, "n_trunc must be in [2, min(N, 4096)]");
   REQUIRE(kd >= 1 && kd <= n_trunc, "kd must be in [1, n_trunc]");
   REQUIRE(g->n < ((int64_t)1 << 31), "too many rows");
+  REFUSE_L2(g, "mi_diffusion_offline_nodes");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   hipStream_t s = g->stream;
@@ -285,6 +287,7 @@ int mi_diffusion_offline_nodes(mi_gallery* g, int32_t n_trunc, int32_t kd, doubl
 
 int mi_diffusion_set_offline(mi_gallery* g, const int64_t* ids, const float* vals, int32_t n_trunc) {
   REQUIRE(g && ids && vals && n_trunc >= 1, "bad arguments");
+  REFUSE_L2(g, "mi_diffusion_set_offline");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   const size_t cnt = (size_t)g->n * n_trunc;
@@ -319,6 +322,7 @@ int mi_diffusion_online(mi_gallery* g, const void* q, int64_t nq, int dtype, int
   REQUIRE(g->dif_ids && g->dif_vals, "no offline diffusion result on this handle");
   REQUIRE(nq >= 1 && k_query >= 1 && (int64_t)k_query <= g->n, "bad sizes");
   REQUIRE(trunc >= 1 && (int64_t)trunc < g->n && trunc <= 4096, "trunc must be in [1, min(N-1, 4096)] (np.argpartition needs kth < N)");
+  REFUSE_L2(g, "mi_diffusion_online");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   hipStream_t s = g->stream;
@@ -465,22 +469,22 @@ int mi_scatter_matrix(const void* X, int64_t n, int32_t d, int dtype, int64_t ro
 int mi_gallery_scatter(const mi_gallery* g, const double* centre, double* C_out) {
   REQUIRE(g && C_out, "null pointer");
   REQUIRE(g->n >= 1, "empty gallery");
-  REQUIRE(scatter_max_splits(g->d) >= 1, "d too large for the scatter workspace bound (512 MiB: d <= 11520)");
+  REQUIRE(scatter_max_splits(g->ud) >= 1, "d too large for the scatter workspace bound (512 MiB: d <= 11520)");
   HIPC(hipSetDevice(g->device));
   TmpAlloc tmp;
-  const int64_t wsb = scatter_workspace_bytes(g->d);
+  const int64_t wsb = scatter_workspace_bytes(g->ud);
   double* ws = tmp.get<double>((size_t)wsb / 8);
-  double* cd = tmp.get<double>((size_t)g->d * g->d);
-  double* md = centre ? tmp.get<double>((size_t)g->d) : nullptr;
+  double* cd = tmp.get<double>((size_t)g->ud * g->ud);
+  double* md = centre ? tmp.get<double>((size_t)g->ud) : nullptr;
   if (!ws || !cd || (centre && !md)) return fail(MI_ERR_NOMEM, "scatter buffers");
   // like mi_gallery_get_rows: read-only on the handle, the rows are those of the last completed append; the blocking copies
   // below order this call against the null stream
-  if (md) HIPC(hipMemcpy(md, centre, (size_t)g->d * 8, hipMemcpyHostToDevice));
+  if (md) HIPC(hipMemcpy(md, centre, (size_t)g->ud * 8, hipMemcpyHostToDevice));
   HIPC(hipDeviceSynchronize());
-  launch_scatter(g->gal_f32, MI_F32, g->n, g->d, g->dp, 1, md, nullptr, nullptr, 0, cd, 0, ws, nullptr);
+  launch_scatter(g->gal_f32, MI_F32, g->n, g->ud, g->dp, 1, md, nullptr, nullptr, 0, cd, 0, ws, nullptr);
   HIPC(hipGetLastError());
   HIPC(hipDeviceSynchronize());
-  HIPC(hipMemcpy(C_out, cd, (size_t)g->d * g->d * 8, hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(C_out, cd, (size_t)g->ud * g->ud * 8, hipMemcpyDeviceToHost));
   return MI_OK;
 }
 

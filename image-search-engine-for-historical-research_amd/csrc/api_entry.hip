@@ -8,6 +8,7 @@ int mi_knn_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t r
   REQUIRE(g && q && out_idx, "null pointer");
   REQUIRE(nq >= 1, "no queries");
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  REFUSE_L2(g, "mi_knn_search");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   const auto t0 = std::chrono::steady_clock::now();
@@ -48,6 +49,7 @@ int mi_knn_search_device(mi_gallery* g, const float* q_dev, int64_t nq, int32_t 
                          float* out_score_dev, double* out_score64_dev, void* stream) {
   REQUIRE(g && q_dev && out_idx_dev, "null pointer");
   REQUIRE(nq >= 1, "no queries");
+  REFUSE_L2(g, "mi_knn_search_device");
   HIPC(hipSetDevice(g->device));
   return search_device(g, q_dev, MI_F32, g->d, 1, g->qnorm_override >= 0 ? g->qnorm_override : g->norm_mode, nq, k,
                        out_idx_dev, out_score_dev, out_score64_dev, g->force_exact != 0, (hipStream_t)stream,
@@ -82,6 +84,7 @@ int mi_gallery_calibrate(mi_gallery* g, int32_t launches, void* stream) {
 
 int mi_search_join(mi_gallery* g, void* stream) {
   REQUIRE(g, "null handle");
+  REFUSE_L2(g, "mi_search_join");
   HIPC(hipSetDevice(g->device));
   return join_tails(g, (hipStream_t)stream);
 }
@@ -90,6 +93,7 @@ int mi_knn_phase1_device(mi_gallery* g, const float* q_dev, int64_t nq, int32_t 
                          void* stream) {
   REQUIRE(g && q_dev && out_approx_dev, "null pointer");
   REQUIRE(nq >= 1 && nq <= QB, "phase API handles one batch of at most 1024 queries");
+  REFUSE_L2(g, "mi_knn_phase1_device (sharded search)");
   HIPC(hipSetDevice(g->device));
   REQUIRE(k >= 1, "k must be >= 1");
   // a shard may hold fewer than k rows: clamp the local k, pad the tail with -inf
@@ -129,6 +133,7 @@ int mi_knn_phase2_device(mi_gallery* g, int64_t nq, int32_t k, const float* L_de
   REQUIRE(g && L_dev && out_idx_dev, "null pointer");
   REQUIRE(nq >= 1 && nq <= QB, "phase API handles one batch of at most 1024 queries");
   REQUIRE(g->ws.qcap > 0, "phase 2 without phase 1");
+  REFUSE_L2(g, "mi_knn_phase2_device (sharded search)");
   HIPC(hipSetDevice(g->device));
   return phase2_batch(g, (int32_t)nq, k, L_dev, out_idx_dev, out_score_dev, out_score64_dev, (hipStream_t)stream);
 }
@@ -157,6 +162,7 @@ int mi_aqe_partial_device(mi_gallery* g, const int64_t* ranks_dev, int64_t rank_
                           int64_t nq, int32_t k_qe, double w, double* out_sum_dev, void* stream) {
   REQUIRE(g && ranks_dev && out_sum_dev, "null pointer");
   REQUIRE(nq >= 1 && k_qe >= 1, "bad sizes");
+  REFUSE_L2(g, "mi_aqe_partial_device");
   HIPC(hipSetDevice(g->device));
   launch_aqe_partial(g->gal_f32, g->dp, g->d, g->n, g->row_offset, ranks_dev, rank_stride_j, rank_stride_q, nq, k_qe,
                      w, nullptr, out_sum_dev, (hipStream_t)stream);
@@ -168,6 +174,7 @@ int mi_aqe_rows_device(mi_gallery* g, const int64_t* ranks_dev, int64_t rank_str
                        int32_t k_qe, float* out_rows_dev, void* stream) {
   REQUIRE(g && ranks_dev && out_rows_dev, "null pointer");
   REQUIRE(nq >= 1 && k_qe >= 1 && k_qe <= 65535, "bad sizes");
+  REFUSE_L2(g, "mi_aqe_rows_device");
   HIPC(hipSetDevice(g->device));
   launch_aqe_rows(g->gal_f32, g->dp, g->d, g->n, g->row_offset, ranks_dev, rank_stride_j, rank_stride_q, nq, k_qe,
                   out_rows_dev, (hipStream_t)stream);
@@ -197,6 +204,7 @@ int mi_aqe_search(mi_gallery* g, const int64_t* ranks, int64_t rank_stride_j, in
                   double* out_seconds) {
   REQUIRE(g && ranks && out_idx, "null pointer");
   REQUIRE(nq >= 1 && k_qe >= 1, "bad sizes");
+  REFUSE_L2(g, "mi_aqe_search");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   const auto t0 = std::chrono::steady_clock::now();
@@ -252,6 +260,7 @@ int mi_knn_dense_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int
   REQUIRE(g && q && out_idx, "null pointer");
   REQUIRE(nq >= 1, "no queries");
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  REFUSE_L2(g, "mi_knn_dense_search");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   const auto t0 = std::chrono::steady_clock::now();
@@ -278,6 +287,7 @@ extern "C" int mi_knn_dense64_search(mi_gallery* g, const void* q, int64_t nq, i
   REQUIRE(g && q && out_idx, "null pointer");
   REQUIRE(nq >= 1, "no queries");
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  REFUSE_L2(g, "mi_knn_dense64_search");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   const auto t0 = std::chrono::steady_clock::now();
@@ -368,12 +378,14 @@ static int rank_all_impl(mi_gallery* g, const void* q, int64_t nq, int dtype, in
 int mi_rank_all(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                 int query_norm, int64_t* out_idx, float* out_score, double* out_seconds) {
   REQUIRE(g, "null handle");
+  REFUSE_L2(g, "mi_rank_all");
   return rank_all_impl(g, q, nq, dtype, row_stride, col_stride, query_norm, g->n, out_idx, out_score, out_seconds);
 }
 
 int mi_rank_prefix(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                    int query_norm, int64_t keep, int64_t* out_idx, float* out_score, double* out_seconds) {
   REQUIRE(g, "null handle");
+  REFUSE_L2(g, "mi_rank_prefix");
   return rank_all_impl(g, q, nq, dtype, row_stride, col_stride, query_norm, keep, out_idx, out_score, out_seconds);
 }
 
@@ -384,6 +396,7 @@ int mi_rank_positions(mi_gallery* g, const void* q, int64_t nq, int dtype, int64
   REQUIRE(m <= rank_positions_max_listed(), "too many listed rows per query (max 2048)");
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
   REQUIRE(query_norm >= -1 && query_norm <= 2, "query_norm: -1 (as the gallery) or an mi_norm value");
+  REFUSE_L2(g, "mi_rank_positions");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   const int qn = query_norm < 0 ? g->norm_mode : query_norm;
@@ -440,6 +453,7 @@ int mi_gather_weighted(mi_gallery* g, const int64_t* ranks, int64_t rank_stride_
                        int32_t k, const double* weights, double* out_sum) {
   REQUIRE(g && ranks && weights && out_sum, "null pointer");
   REQUIRE(nq >= 1 && k >= 1, "bad sizes");
+  REFUSE_L2(g, "mi_gather_weighted");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   int64_t elems;

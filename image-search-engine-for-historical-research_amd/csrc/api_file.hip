@@ -204,6 +204,7 @@ extern "C" {
 
 int mi_gallery_save(const mi_gallery* g, const char* path) {
   REQUIRE(g && path, "null");
+  REFUSE_L2(g, "mi_gallery_save (the prepared-gallery file)");
   HIPC(hipSetDevice(g->device));
   HIPC(hipStreamSynchronize(g->stream));
   FileHeader h{};

@@ -115,7 +115,7 @@ static int sub_prepare(mi_gallery* g, const std::vector<uint64_t>& key, const ui
     if (!f.sub) {
       mi_gallery* sg = new mi_gallery();
       sg->device = g->device;
-      sg->d = g->d, sg->dp = g->dp, sg->norm_mode = g->norm_mode, sg->img_f16 = g->img_f16;
+      sg->d = sg->ud = g->d, sg->dp = g->dp, sg->norm_mode = g->norm_mode, sg->img_f16 = g->img_f16;
       sg->stream = s;
       const int64_t cap = std::max<int64_t>(allowed, std::min<int64_t>(g->n, allowed + allowed / 4));   // room to grow into
       const int64_t cap_pad = round_up(cap, TILE);
@@ -188,6 +188,15 @@ extern "C" {
 int mi_knn_search_filtered(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                            int32_t k, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
                            mi_filter_info* out_info, double* out_seconds) {
+  return filtered_search_host(g, q, nq, dtype, row_stride, col_stride, k, allow_bits, allow_memspace, out_idx, out_score, out_info,
+                              out_seconds, /*l2_caller=*/false);
+}
+
+}  // extern "C"
+
+int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                         const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
+                         mi_filter_info* out_info, double* out_seconds, bool l2_caller) {
   REQUIRE(g, "null handle");
   REQUIRE(allow_bits, "null pointer: allow_bits");
   REQUIRE(allow_memspace == MI_HOST || allow_memspace == MI_DEVICE, "allow_memspace must be MI_HOST or MI_DEVICE");
@@ -196,10 +205,12 @@ int mi_knn_search_filtered(mi_gallery* g, const void* q, int64_t nq, int dtype, 
   REQUIRE(nq == 0 || q, "null pointer: queries");
   REQUIRE(nq == 0 || out_idx, "null pointer: out_idx");
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  if (!l2_caller) REFUSE_L2(g, "mi_knn_search_filtered");
   mi_filter_info info;
   std::memset(&info, 0, sizeof info);
   if (out_info) *out_info = info;
-  std::lock_guard<std::mutex> lock(g->mu);
+  std::unique_lock<std::mutex> lock(g->mu, std::defer_lock);
+  if (!l2_caller) lock.lock();                 // (mi_knn_search_l2 holds it across the selection and its distance tail)
   HIPC(hipSetDevice(g->device));
   const auto t0 = std::chrono::steady_clock::now();
   if (nq == 0) {
@@ -355,5 +366,3 @@ int mi_knn_search_filtered(mi_gallery* g, const void* q, int64_t nq, int dtype, 
   }
   return done(MI_OK);
 }
-
-}  // extern "C"

@@ -28,7 +28,9 @@ int mi_gallery_destroy(mi_gallery* g) {
     // (every stream of the handle is drained above: nothing in flight touches these buffers any more)
     std::lock_guard<std::mutex> lock(g_spare_mu);
     const size_t total = g->buf_bytes[0] + g->buf_bytes[1] + g->buf_bytes[2];
-    if (g_keep_buffers.load() && g->gal_f32 && g->gal_img && g->rowstat && g->gstat3 && total <= SPARE_MAX_BYTES) {
+    // (the buffers of a squared-L2 gallery are freed: the spare slot only ever holds what an inner-product gallery left)
+    if (g_keep_buffers.load() && g->metric == MI_METRIC_IP && g->gal_f32 && g->gal_img && g->rowstat && g->gstat3 &&
+        total <= SPARE_MAX_BYTES) {
       spare_release_locked();
       g_spare.device = g->device;
       g_spare.f32_bytes = g->buf_bytes[0], g_spare.img_bytes = g->buf_bytes[1], g_spare.stat_bytes = g->buf_bytes[2];
@@ -46,6 +48,7 @@ int mi_gallery_destroy(mi_gallery* g) {
   for (void* b : g->io_buf) (void)hipFree(b);
   range_scratch_free(g);
   filter_scratch_free(g);
+  l2_scratch_free(g);
   (void)hipFree(g->dif_ids);
   (void)hipFree(g->dif_vals);
   if (g->stream) (void)hipStreamDestroy(g->stream);
@@ -61,8 +64,9 @@ int mi_gallery_destroy(mi_gallery* g) {
 // values are untouched, the sums are the row kernel's, so the gallery is the same bits whatever the layout.
 static int ingest_rows_any_layout(mi_gallery* g, const void* src, int dtype, int64_t m, int64_t m_pad, int64_t rs, int64_t cs,
                                   int64_t row_base, hipStream_t s) {
-  if (ingest_takes_layout(g->d, rs, cs)) {
-    launch_ingest(src, dtype, m, g->d, rs, cs, g->norm_mode, g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, m_pad, s,
+  // (a squared-L2 gallery is stored wider than its source: the one-pass kernel of the [D, N] layout does not apply to it)
+  if (ingest_takes_layout(g->ud, g->dp, rs, cs)) {
+    launch_ingest(src, dtype, m, g->ud, rs, cs, g->norm_mode, g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, m_pad, s,
                   row_base);
     HIPC(hipGetLastError());
     return MI_OK;
@@ -70,13 +74,13 @@ static int ingest_rows_any_layout(mi_gallery* g, const void* src, int dtype, int
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   const int64_t chunk = 65536;
   TmpAlloc tmp;
-  char* scratch = tmp.get<char>((size_t)std::min<int64_t>(chunk, m) * g->d * esz);
+  char* scratch = tmp.get<char>((size_t)std::min<int64_t>(chunk, m) * g->ud * esz);
   if (!scratch) return fail(MI_ERR_NOMEM, "ingest scratch block");
   for (int64_t r0 = 0; r0 < m_pad; r0 += chunk) {
     const int64_t rows = std::max<int64_t>(0, std::min<int64_t>(chunk, m - r0));
     const int64_t rows_pad = std::min<int64_t>(chunk, m_pad - r0);
-    if (rows > 0) launch_transpose_rows((const char*)src + (size_t)r0 * rs * esz, dtype, rows, g->d, rs, cs, scratch, s);
-    launch_ingest(scratch, dtype, rows, g->d, g->d, 1, g->norm_mode, g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp,
+    if (rows > 0) launch_transpose_rows((const char*)src + (size_t)r0 * rs * esz, dtype, rows, g->ud, rs, cs, scratch, s);
+    launch_ingest(scratch, dtype, rows, g->ud, g->ud, 1, g->norm_mode, g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp,
                   rows_pad, s, row_base + r0);
   }
   HIPC(hipGetLastError());
@@ -85,6 +89,7 @@ static int ingest_rows_any_layout(mi_gallery* g, const void* src, int dtype, int
 }
 
 int gallery_alloc(mi_gallery* g) {
+  if (g->ud == 0) g->ud = g->d;
   g->dp = (int32_t)round_up(g->d, BK);
   g->npad = round_up(g->n, TILE);
   if (g->cap < g->n) g->cap = g->n;
@@ -123,7 +128,7 @@ int gallery_alloc(mi_gallery* g) {
 // crosses PCIe while block i is ingested; nothing the size of the gallery is allocated besides the gallery.
 static int gallery_ingest_host_blocks(mi_gallery* g, const void* data, int dtype, int64_t n, int64_t rs, int64_t cs) {
   const size_t esz = dtype == MI_F32 ? 4 : 8;
-  const int32_t d = g->d;
+  const int32_t d = g->ud;
   const bool by_cols = rs == 1 && cs != 1;                     // [D, N] layout
   const int64_t m_blk = std::max<int64_t>(TILE, ((int64_t)32 << 20) / ((int64_t)d * (int64_t)esz) / TILE * TILE);   // ~32 MiB, whole tiles
   const size_t blk_bytes = (size_t)m_blk * d * esz;
@@ -182,7 +187,18 @@ int mi_gallery_create(const void* data, int64_t n, int32_t d, int dtype, int64_t
                       int memspace, int norm_mode, int device, int64_t row_offset, mi_gallery** out) {
   REQUIRE(data && out, "null pointer");
   REQUIRE(n >= 1 && d >= 1, "empty gallery");
-  REQUIRE(n < (int64_t)1 << 32, "a shard holds at most 2^32-1 rows");
+  return gallery_create_any(data, n, d, dtype, row_stride, col_stride, memspace, norm_mode, MI_METRIC_IP, device, row_offset, 0,
+                            out);
+}
+
+}  // extern "C"
+
+int gallery_create_any(const void* data, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace,
+                       int norm_mode, int metric, int device, int64_t row_offset, int64_t capacity, mi_gallery** out) {
+  const bool l2 = metric == MI_METRIC_L2;
+  if (capacity == 0) capacity = n;
+  REQUIRE(capacity >= n && capacity >= 1, "capacity below the number of rows (or an empty gallery without capacity)");
+  REQUIRE(capacity < (int64_t)1 << 32, "a shard holds at most 2^32-1 rows");
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
   REQUIRE(norm_mode >= 0 && norm_mode <= 2, "bad norm_mode");
   int64_t elems;
@@ -191,12 +207,31 @@ int mi_gallery_create(const void* data, int64_t n, int32_t d, int dtype, int64_t
   mi_gallery* g = new mi_gallery();
   g->device = device;
   g->n = n;
-  g->d = d;
+  g->cap = capacity;
+  g->ud = d;
+  g->d = l2 ? d + 3 : d;
+  g->metric = metric;
   g->norm_mode = norm_mode;
   g->row_offset = row_offset;
   if ((rc = gallery_alloc(g)) != MI_OK) {
     mi_gallery_destroy(g);
     return rc;
+  }
+  if (capacity > n) {
+    // appendable (mi_gallery_create_empty): the appends write the image and the rounding norms of their own rows only
+    hipError_t e = hipMemset(g->gal_img, 0, (size_t)round_up(capacity, TILE) * g->dp * 2);
+    if (e == hipSuccess) e = hipMemset(g->rowstat, 0, (size_t)round_up(capacity, TILE) * sizeof(RowStat));
+    if (e == hipSuccess) e = hipMemset(g->gstat3, 0, 12);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+      mi_gallery_destroy(g);
+      return fail(MI_ERR_HIP, std::string("memset: ") + hipGetErrorString(e));
+    }
+  }
+  if (n == 0) {
+    g->img_f16 = 0;                  // raw rows of unknown range: bf16 image
+    *out = g;
+    return MI_OK;
   }
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   void* staged = nullptr;
@@ -217,12 +252,14 @@ int mi_gallery_create(const void* data, int64_t n, int32_t d, int dtype, int64_t
     if (e != hipSuccess) return cleanup(fail(MI_ERR_HIP, std::string("H2D copy: ") + hipGetErrorString(e)));
     src = staged;
   }
-  g->img_f16 = g_default_img_f16.load();
+  // (rows appended later are of unknown range, and their bias -1/2 ||g||^2 has to fit the image type: bf16)
+  g->img_f16 = capacity > n ? 0 : g_default_img_f16.load();
   hipError_t e = hipSuccess;
   for (int pass = 0; pass < 2; ++pass) {
     rc = host_blocks ? gallery_ingest_host_blocks(g, data, dtype, n, row_stride, col_stride)
                      : ingest_rows_any_layout(g, src, dtype, n, g->npad, row_stride, col_stride, 0, g->stream);
     if (rc != MI_OK) return cleanup(rc);
+    if (l2) launch_l2_bias(g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, g->ud, 0, n, g->npad, g->stream);
     launch_rowstat_max(g->rowstat, n, g->gstat3, g->stream);
     // raw (un-normalised) rows: fp16 only if they sit comfortably inside its range, otherwise re-ingest as bf16.  The maxima skip
     // rows with a non-finite norm, so a row with an element beyond fp16's range (image norm inf) is looked for on its own;
@@ -245,6 +282,8 @@ int mi_gallery_create(const void* data, int64_t n, int32_t d, int dtype, int64_t
   return MI_OK;
 }
 
+extern "C" {
+
 int mi_gallery_create_empty(int64_t capacity, int32_t d, int norm_mode, int device, int64_t row_offset,
                             mi_gallery** out) {
   REQUIRE(out, "null pointer");
@@ -254,7 +293,7 @@ int mi_gallery_create_empty(int64_t capacity, int32_t d, int norm_mode, int devi
   g->device = device;
   g->n = 0;
   g->cap = capacity;
-  g->d = d;
+  g->d = g->ud = d;
   g->norm_mode = norm_mode;
   g->row_offset = row_offset;
   g->img_f16 = (norm_mode == MI_NORM_NONE) ? 0 : g_default_img_f16.load();   // raw rows of unknown range: bf16 image
@@ -283,8 +322,9 @@ int mi_gallery_append_device(mi_gallery* g, const float* rows_dev, int64_t m, vo
   HIPC(hipSetDevice(g->device));
   hipStream_t s = (hipStream_t)stream;
   // rows [n, n+m): normalise like the gallery, write f32 rows + 16-bit image + rounding norms at their final place
-  launch_ingest(rows_dev, MI_F32, m, g->d, g->d, 1, g->norm_mode, g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, m,
+  launch_ingest(rows_dev, MI_F32, m, g->ud, g->ud, 1, g->norm_mode, g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, m,
                 s, g->n);
+  if (g->metric == MI_METRIC_L2) launch_l2_bias(g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, g->ud, g->n, m, m, s);
   launch_rowstat_max(g->rowstat + g->n, m, g->gstat3, s, /*reset=*/false);
   HIPC(hipGetLastError());
   g->n += m;
@@ -300,7 +340,7 @@ int mi_gallery_append(mi_gallery* g, const void* data, int64_t m, int dtype, int
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
   REQUIRE(g->n + m <= g->cap, "gallery capacity exceeded");
   int64_t elems;
-  int rc = strided_extent(m, g->d, row_stride, col_stride, &elems);
+  int rc = strided_extent(m, g->ud, row_stride, col_stride, &elems);
   if (rc != MI_OK) return rc;
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
@@ -314,9 +354,9 @@ int mi_gallery_append(mi_gallery* g, const void* data, int64_t m, int dtype, int
     // vecs.T, src/test_rOP1m.py:156) is d runs of m contiguous elements: a 2-D copy packs it to [d][m] on the device and
     // the ingest kernel reads it with strides (1, m) -- no host transpose, no float64 promotion.
     if (row_stride == 1 && col_stride >= m) {
-      char* st = tmp.get<char>((size_t)g->d * m * esz);
+      char* st = tmp.get<char>((size_t)g->ud * m * esz);
       if (!st) return fail(MI_ERR_NOMEM, "append staging");
-      HIPC(hipMemcpy2D(st, (size_t)m * esz, data, (size_t)col_stride * esz, (size_t)m * esz, (size_t)g->d,
+      HIPC(hipMemcpy2D(st, (size_t)m * esz, data, (size_t)col_stride * esz, (size_t)m * esz, (size_t)g->ud,
                        hipMemcpyHostToDevice));
       src = st;
       rs = 1;
@@ -329,6 +369,7 @@ int mi_gallery_append(mi_gallery* g, const void* data, int64_t m, int dtype, int
     }
   }
   if ((rc = ingest_rows_any_layout(g, src, dtype, m, m, rs, cs, g->n, s)) != MI_OK) return rc;
+  if (g->metric == MI_METRIC_L2) launch_l2_bias(g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, g->ud, g->n, m, m, s);
   launch_rowstat_max(g->rowstat + g->n, m, g->gstat3, s, /*reset=*/false);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(s));          // the staging buffer is freed on return
@@ -342,7 +383,7 @@ int mi_gallery_info(const mi_gallery* g, int64_t* n, int32_t* d, int32_t* norm_m
                     int64_t* row_offset, int64_t* hbm_bytes) {
   REQUIRE(g, "null handle");
   if (n) *n = g->n;
-  if (d) *d = g->d;
+  if (d) *d = g->ud;
   if (norm_mode) *norm_mode = g->norm_mode;
   if (device) *device = g->device;
   if (row_offset) *row_offset = g->row_offset;
@@ -354,7 +395,7 @@ int mi_gallery_get_rows(const mi_gallery* g, int64_t row0, int64_t nrows, float*
   REQUIRE(g && out_host, "null");
   REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= g->n, "row range out of bounds");
   HIPC(hipSetDevice(g->device));
-  HIPC(hipMemcpy2D(out_host, (size_t)g->d * 4, g->gal_f32 + row0 * g->dp, (size_t)g->dp * 4, (size_t)g->d * 4,
+  HIPC(hipMemcpy2D(out_host, (size_t)g->ud * 4, g->gal_f32 + row0 * g->dp, (size_t)g->dp * 4, (size_t)g->ud * 4,
                    (size_t)nrows, hipMemcpyDeviceToHost));
   return MI_OK;
 }
@@ -362,14 +403,14 @@ int mi_gallery_get_rows(const mi_gallery* g, int64_t row0, int64_t nrows, float*
 int mi_gallery_append_whitened_device(mi_gallery* g, const void* X_dev, int64_t m, int32_t d, int dtype, int64_t row_stride,
                                       int64_t col_stride, const double* mean_dev, const double* P_dev, void* stream) {
   REQUIRE(g && X_dev && mean_dev && P_dev, "null pointer");
-  REQUIRE(m >= 1 && d >= 1 && g->d <= d, "bad sizes (the gallery's dimension is the number of rows of P that are applied)");
+  REQUIRE(m >= 1 && d >= 1 && g->ud <= d, "bad sizes (the gallery's dimension is the number of rows of P that are applied)");
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
   REQUIRE(row_stride >= 0 && col_stride >= 0, "negative strides are not supported");
   REQUIRE(g->n + m <= g->cap, "gallery capacity exceeded");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   hipStream_t s = (hipStream_t)stream;
-  const int32_t dims = g->d;
+  const int32_t dims = g->ud;
   const int64_t chunk = std::min<int64_t>(m, 32768);       // 512 MiB of float64 rows at dims = 2048: the only scratch there is
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   TmpAlloc tmp;
@@ -384,6 +425,7 @@ int mi_gallery_append_whitened_device(mi_gallery* g, const void* X_dev, int64_t 
     launch_ingest(y, MI_F64, rows, dims, dims, 1, g->norm_mode, g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, rows, s,
                   g->n + r0);
   }
+  if (g->metric == MI_METRIC_L2) launch_l2_bias(g->gal_f32, g->gal_img, g->img_f16, g->rowstat, g->dp, g->ud, g->n, m, m, s);
   launch_rowstat_max(g->rowstat + g->n, m, g->gstat3, s, /*reset=*/false);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(s));           // the scratch block is freed on return
@@ -395,6 +437,7 @@ int mi_gallery_append_whitened_device(mi_gallery* g, const void* X_dev, int64_t 
 
 int mi_gallery_norm_bounds(mi_gallery* g, float* bounds3, int raise) {
   REQUIRE(g && bounds3, "null");
+  REFUSE_L2(g, "mi_gallery_norm_bounds (sharded search)");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   HIPC(hipStreamSynchronize(g->stream));
@@ -413,6 +456,7 @@ int mi_gallery_norm_bounds(mi_gallery* g, float* bounds3, int raise) {
 
 int mi_gallery_set_image_dtype(mi_gallery* g, int f16) {
   REQUIRE(g, "null handle");
+  REFUSE_L2(g, "mi_gallery_set_image_dtype");
   f16 = f16 != 0;
   std::lock_guard<std::mutex> lock(g->mu);
   if (g->img_f16 == f16 || g->n == 0) {

@@ -10,6 +10,7 @@
 //   api_options.hip   per-handle options, statistics, profiling, flags, diagnostics
 //   api_range.hip     exact range search: fixed-threshold chunk schedule, overflow split, dense chunks, CSR tail
 //   api_filter.hip    filtered top-K: compacted sub-gallery (cached per bitmap) or over-fetch with a certificate
+//   api_l2.hip        squared-L2 metric: L2 galleries (hidden bias columns), top-K by distance (host / device), dense checker
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -143,6 +144,9 @@ struct mi_gallery {
   int64_t n = 0, npad = 0, row_offset = 0;
   int64_t cap = 0;          // allocated rows (== n unless created with mi_gallery_create_empty)
   int32_t d = 0, dp = 0, norm_mode = 0;
+  // MI_METRIC_L2: `d` counts the three hidden bias columns behind the user's `ud` columns (d == ud + 3), so the
+  // search below the entry points sees an ordinary raw gallery; what faces the caller (ingest, info, get_rows) uses `ud`
+  int32_t ud = 0, metric = 0;
   int img_f16 = 1;          // 16-bit image element type of the gallery AND of the query batches searched on it
   float* gal_f32 = nullptr;
   void* gal_img = nullptr;
@@ -258,6 +262,19 @@ struct mi_gallery {
     std::vector<uint64_t> last_key;      // the bitmap of the previous call (auto compacts a bitmap it sees twice in a row)
     int64_t last_key_n = -1;
   } filt;
+  // squared-L2 search (api_l2.hip): grow-only device buffers, freed with the handle
+  struct L2Scratch {
+    void* qraw = nullptr;                // queries of a host call as given
+    size_t qraw_cap = 0;                 // bytes
+    float* qaug = nullptr;               // [nq][dp] extended queries
+    size_t qaug_cap = 0;                 // floats
+    int64_t* ids = nullptr;              // [nq][ke] rows the selection certified
+    size_t ids_cap = 0;
+    int64_t* oidx = nullptr;             // [nq][k] results of a host call
+    float* odist = nullptr;
+    double* odist64 = nullptr;
+    size_t out_cap = 0;
+  } l2;
   // diffusion state (offline matrix rows kept on the device for the online stage)
   int32_t* dif_ids = nullptr;
   float* dif_vals = nullptr;
@@ -298,9 +315,27 @@ MI_INTERNAL int dense64_search_device(mi_gallery* g, const void* q_src, int q_dt
                                       double* out_score64_dev, hipStream_t s);
 // ---- api_gallery.hip
 MI_INTERNAL int gallery_alloc(mi_gallery* g);
+// mi_gallery_create / mi_gallery_create_l2: n rows of `data` (n == 0: none) into a gallery of `capacity` rows (0 = n)
+MI_INTERNAL int gallery_create_any(const void* data, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                                   int memspace, int norm_mode, int metric, int device, int64_t row_offset, int64_t capacity,
+                                   mi_gallery** out);
 // ---- api_range.hip
 MI_INTERNAL void range_scratch_free(mi_gallery* g);
 // ---- api_filter.hip
 MI_INTERNAL void filter_scratch_free(mi_gallery* g);
 MI_INTERNAL void filter_release_sub(mi_gallery* g);     // frees the compacted sub-gallery (option "filter_cache" 0)
 MI_INTERNAL void filter_invalidate(mi_gallery* g);      // rows or image type of the parent changed: the sub-gallery is stale
+// mi_knn_search_filtered (argument checks included); l2_caller: mi_knn_search_l2 on its own gallery, which HOLDS the handle's
+// lock (otherwise the call takes it)
+MI_INTERNAL int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
+                                     int32_t k, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
+                                     mi_filter_info* out_info, double* out_seconds, bool l2_caller);
+// ---- api_l2.hip
+MI_INTERNAL void l2_scratch_free(mi_gallery* g);
+// entry points that are not defined on a squared-L2 gallery (include/mi355_retrieval.h: mi_metric)
+#define REFUSE_L2(g, what)                                                                                          \
+  do {                                                                                                              \
+    if ((g)->metric != MI_METRIC_IP)                                                                                \
+      return fail(MI_ERR_UNSUPPORTED, what " is not available on a gallery of metric MI_METRIC_L2 (squared "         \
+                                           "Euclidean distance): use the mi_*_l2 entry points");                    \
+  } while (0)

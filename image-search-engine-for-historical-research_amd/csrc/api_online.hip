@@ -183,6 +183,8 @@ int mi_online_create(mi_gallery* g_search, mi_gallery* g_rows, int32_t k, int32_
   REQUIRE(g_search && out, "null pointer");
   REQUIRE(max_batch >= 1 && max_batch <= QB, "max_batch must be in [1, 1024]");
   REQUIRE(max_wait_us >= 0, "negative wait");
+  REFUSE_L2(g_search, "mi_online_create (the online front)");
+  if (g_rows) REFUSE_L2(g_rows, "mi_online_create (the online front)");
   int rc = check_k(g_search, k);
   if (rc != MI_OK) return rc;
   if (g_rows) {

@@ -109,6 +109,7 @@ int mi_get_option(const mi_gallery* g, const char* name, double* out_value) {
   else if (n == "async_tail") *out_value = g->async_tail;
   else if (n == "query_norm_override") *out_value = g->qnorm_override;
   else if (n == "image_dtype") *out_value = g->img_f16;
+  else if (n == "metric") *out_value = g->metric;
   else if (n == "filter_path") *out_value = g->filter_path;
   else if (n == "filter_compact_max") *out_value = g->filter_compact_max;
   else if (n == "filter_cache") *out_value = g->filter_cache;

@@ -216,6 +216,7 @@ int mi_range_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t
   REQUIRE(min_score == min_score, "min_score is NaN");
   REQUIRE(max_results >= 0, "max_results must be >= 0");
   REQUIRE(max_results == 0 || out_idx, "null pointer: out_idx");
+  REFUSE_L2(g, "mi_range_search (radius search)");
   std::lock_guard<std::mutex> lock(g->mu);
   HIPC(hipSetDevice(g->device));
   const auto t0 = std::chrono::steady_clock::now();

@@ -878,10 +878,11 @@ void launch_transpose_rows(const void* src, int dtype, int64_t m, int32_t d, int
 
 // does launch_ingest take this source as it is (one pass, canonical sums)?  Otherwise the caller copies the rows into a
 // row-major scratch block first (launch_transpose_rows) and ingests that.
-bool ingest_takes_layout(int32_t d, int64_t rs, int64_t cs) {
-  const int32_t dp = (int32_t)round_up(d, BK);
+bool ingest_takes_layout(int32_t d, int64_t rs, int64_t cs) { return ingest_takes_layout(d, (int32_t)round_up(d, BK), rs, cs); }
+// the same for rows stored wider than round_up(d, 64) (hidden columns behind the source's d: the [D, N] kernel does not apply)
+bool ingest_takes_layout(int32_t d, int32_t dp, int64_t rs, int64_t cs) {
   if (cs == 1) return true;                                      // rows contiguous: ingest_rows_kernel (dp <= 4096) / row-wise kernel
-  if (rs == 1 && d == 2048) return true;                         // the reference's layout at the reference's width: ingest_cols_kernel
+  if (rs == 1 && d == 2048 && dp == 2048) return true;           // the reference's layout at the reference's width: ingest_cols_kernel
   return dp > 256 * QI_MAX_PER_THREAD;                           // very wide rows: the row-wise kernel takes any strides
 }
 

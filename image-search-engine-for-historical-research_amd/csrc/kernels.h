@@ -8,6 +8,7 @@ namespace mi {
 // strided source -> row-major [m][d] copy of the same element type (scratch for layouts launch_ingest does not take in one pass)
 void launch_transpose_rows(const void* src, int dtype, int64_t m, int32_t d, int64_t rs, int64_t cs, void* dst, hipStream_t stream);
 bool ingest_takes_layout(int32_t d, int64_t rs, int64_t cs);
+bool ingest_takes_layout(int32_t d, int32_t dp, int64_t rs, int64_t cs);   // rows stored dp >= round_up(d, 64) wide
 void launch_ingest(const void* src, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, int norm_mode,
                    float* out_f32, void* out_img, int img_f16, RowStat* rowstat, int32_t dp, int64_t npad, hipStream_t stream,
                    int64_t row_base = 0);
@@ -248,6 +249,20 @@ void launch_filter_overfetch(const int64_t* in_idx, const float* in_sc, int64_t 
                              hipStream_t stream);
 void launch_filter_remap(const int64_t* sidx, const float* ssc, int64_t nq, int32_t ke, int32_t k, const uint32_t* rows,
                          int64_t m, int64_t row_offset, int64_t* out_idx, float* out_sc, hipStream_t stream);
+
+// l2_metric.hip -- squared-L2 metric (api_l2.hip): hidden bias columns of stored rows, query extension, direct-form f64 tail,
+// dense direct-form distances (stored negated for launch_dense_topk64) and their emit
+void launch_l2_bias(float* gal_f32, void* gal_img, int img_f16, RowStat* rowstat, int32_t dp, int32_t d, int64_t row0,
+                    int64_t nrows, int64_t nrows_pad, hipStream_t stream);
+void launch_l2_augment(const void* src, int dtype, int64_t nq, int32_t d, int64_t rs, int64_t cs, float* out, int32_t ld,
+                       hipStream_t stream);
+void launch_l2_tail(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int64_t row_offset,
+                    const int64_t* ids, int32_t ke, int32_t k, int64_t nq, int64_t* out_idx, float* out_dist, double* out_dist64,
+                    hipStream_t stream);
+void launch_l2_dense_dist(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int32_t nq, double* out,
+                          int64_t ld, hipStream_t stream);
+void launch_l2_dense_emit(const int64_t* idx, const double* neg, int64_t nq, int32_t ke, int32_t k, int64_t* out_idx,
+                          float* out_dist, double* out_dist64, hipStream_t stream);
 
 // synth.hip
 void launch_synth_fill(float* dst, uint64_t seed, int64_t row0, int64_t nrows, int32_t d, hipStream_t stream);

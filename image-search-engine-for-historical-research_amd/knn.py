@@ -5,6 +5,11 @@
 `cosine` is faiss.IndexFlatIP there: exact top-k raw inner products, descending; rows are used as
 given (the callers L2-normalise beforehand).  Here the index is a device-resident gallery
 (NORM_NONE) and the search runs through the HIP path; ties go to the lower id.
+
+    KNN(database[N,D], 'euclidean').search(queries[Q,D], k) -> (squared distances float32 [Q,k], ids int64 [Q,k])
+
+`euclidean` is faiss.IndexFlatL2: exact top-k squared L2 distances of the rows as given, ascending -- the return of
+IndexFlatL2.search -- through a squared-L2 gallery (Gallery.l2_from_host); ties go to the lower id.
 """
 import numpy as np
 
@@ -12,22 +17,32 @@ from ._lib import Gallery, NORM_NONE
 
 
 class KNN:
+    method = "cosine"
+
     def __init__(self, database, method="cosine", device=0):
-        if method != "cosine":
-            raise NotImplementedError("only 'cosine' (IndexFlatIP) is on the reference's hot path")
+        if method not in ("cosine", "euclidean"):
+            raise NotImplementedError("method must be 'cosine' (IndexFlatIP) or 'euclidean' (IndexFlatL2), got %r" % (method,))
+        self.method = method
         database = np.asarray(database)
         if database.dtype != np.float32:          # src/utils/knn.py:10-11
             database = database.astype(np.float32)
         self.N, self.D = database.shape
-        self.gallery = Gallery.from_host(database, norm_mode=NORM_NONE, device=device)
+        if method == "euclidean":
+            self.gallery = Gallery.l2_from_host(database, device=device)
+        else:
+            self.gallery = Gallery.from_host(database, norm_mode=NORM_NONE, device=device)
 
     def search(self, queries, k, allow=None):
         """-> (sims float32 [Q,k], ids int64 [Q,k]).  allow (optional, like faiss's ID selector in the search parameters):
         restrict the search to some rows -- a bool mask [N], an array of allowed ids, or packed AllowBits words (_lib.allow_bitmap;
-        _lib.allow_ranges for row ranges).  Fewer than k allowed rows: trailing ids -1, sims -inf."""
+        _lib.allow_ranges for row ranges).  Fewer than k allowed rows: trailing ids -1, sims -inf.
+        'euclidean': -> (squared distances float32 [Q,k] ascending, ids int64 [Q,k]); fewer than k rows: ids -1, distances +inf."""
         queries = np.asarray(queries)
         if queries.dtype != np.float32:           # src/utils/knn.py:28-29
             queries = queries.astype(np.float32)
+        if self.method == "euclidean":
+            ids, dist, _, _, _ = self.gallery.search_l2(queries, int(k), allow)
+            return dist, ids
         if allow is not None:
             ids, sims, _, _ = self.gallery.search_filtered(queries, int(k), allow)
             return sims, ids
@@ -37,7 +52,9 @@ class KNN:
     def range_search(self, queries, thresh):
         """-> (lims int64 [Q+1], D float32 [lims[-1]], I int64 [lims[-1]]), the return shape of faiss's `range_search`: the
         results of query i are D/I[lims[i]:lims[i+1]].  Every row whose exact inner product with the query is >= thresh
-        (the bound is INCLUSIVE), ordered by (score desc, id asc)."""
+        (the bound is INCLUSIVE), ordered by (score desc, id asc).  'cosine' only."""
+        if self.method != "cosine":
+            raise NotImplementedError("range_search is defined for 'cosine' only (a radius search in L2 is not built)")
         queries = np.asarray(queries)
         if queries.dtype != np.float32:
             queries = queries.astype(np.float32)

@@ -50,6 +50,11 @@ enum mi_norm {
                         src/utils/whiten.py:10 */
 };
 
+enum mi_metric {
+  MI_METRIC_IP = 0,  /* inner product, descending (every gallery but those of mi_gallery_create_l2) */
+  MI_METRIC_L2 = 1   /* squared Euclidean distance, ascending: faiss IndexFlatL2, KNN(..., 'euclidean'), src/utils/knn.py:33-40 */
+};
+
 const char* mi_last_error(void);
 int mi_device_count(int* count);
 
@@ -131,6 +136,40 @@ typedef struct mi_filter_info {
 int mi_knn_search_filtered(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                            int32_t k, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
                            mi_filter_info* out_info, double* out_seconds);
+
+/* ---- exact squared-L2 (Euclidean) top-K on raw descriptors: faiss IndexFlatL2 behind KNN(database, 'euclidean')
+ * (src/utils/knn.py:33-40), the metric string every reference entry point passes (src/offline.py:112, src/online.py:137,
+ * src/test_rOP1m.py:156).  On rows that are not unit length its order differs from the inner product's.  DESIGN.md 5.11.
+ * An L2 gallery (mi_get_option "metric" == MI_METRIC_L2, read-only) stores the rows as given, like MI_NORM_NONE, plus three hidden
+ * columns that never leave the library: mi_gallery_info and mi_gallery_get_rows report the caller's d.  capacity 0 means n; with
+ * capacity > n the gallery is appendable, and data == NULL with n == 0 gives an empty appendable one (appendable L2 galleries use
+ * the bf16 image).  On an L2 gallery mi_gallery_append*, mi_gallery_info, mi_gallery_get_rows, mi_gallery_destroy,
+ * mi_gallery_calibrate, mi_gallery_scatter, the options, statistics, flags and diagnostics work on the caller's d; every other
+ * entry point that takes a gallery returns MI_ERR_UNSUPPORTED (radius search, save, alpha-QE, diffusion, the online front and
+ * sharded search are not defined for this metric).  The _l2 entry points return MI_ERR_INVALID on any other gallery.  The order
+ * among non-finite distances (non-finite inputs) is unspecified. */
+int mi_gallery_create_l2(const void* data, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                         int memspace, int device, int64_t row_offset, int64_t capacity, mi_gallery** out);
+/* Host input, host output, the verified loop of mi_knn_search.  Queries are taken as given (f64 queries are rounded to f32 like
+ * every query batch).  out_idx [nq][k] int64 (row_offset + local row), out_dist64 [nq][k] (may be NULL): sum_j (q_j - g_j)^2 in
+ * the DIRECT form over the stored f32 row, f32 values promoted to float64, float64 accumulation -- a query equal to a stored row
+ * is at distance 0.0 exactly --, ascending, ties to the lower id; out_dist [nq][k] f32 (may be NULL) = (float)out_dist64.  Fewer
+ * than k rows (allowed): trailing ids -1, distances +INFINITY.  1 <= k <= 2048.  allow_bits NULL: every row; otherwise the
+ * bitmap of mi_knn_search_filtered with its two paths, its options and out_info (may be NULL; without a bitmap only `allowed`
+ * = n is filled in). */
+int mi_knn_search_l2(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                     const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_dist, double* out_dist64,
+                     mi_filter_info* out_info, double* out_seconds);
+/* Device-resident variant, enqueued on `stream` like mi_knn_search_device (q_dev [nq][d] row-major f32; out_dist_dev and
+ * out_dist64_dev may be NULL): no verified loop, a raised sticky flag (mi_search_flags) means the batch must be answered again.
+ * The call stages its extended queries and the selected rows in buffers of the handle (grown, i.e. freed and allocated again,
+ * when a larger batch comes): calls on one handle must be serialised by the caller and enqueued on ONE stream. */
+int mi_knn_search_l2_device(mi_gallery* g, const float* q_dev, int64_t nq, int32_t k, int64_t* out_idx_dev,
+                            float* out_dist_dev, double* out_dist64_dev, void* stream);
+/* The L2 twin of mi_knn_dense64_search, the independent checker: EVERY direct-form float64 distance of the gallery, no threshold
+ * logic at all, then the exact top-k by (distance asc, id asc), k <= 4096; padding as above. */
+int mi_knn_dense64_search_l2(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
+                             int32_t k, int64_t* out_idx, float* out_dist, double* out_dist64, double* out_seconds);
 
 /* Device-resident variant: q_dev [nq][d] row-major f32 (C order), outputs are device buffers.
  * out_score64_dev (may be NULL) receives the float64 exact scores. */
@@ -408,8 +447,8 @@ int mi_profile_launch_ms(mi_gallery* g, float* out_host, int64_t cap, int64_t* o
  * calls at 1 and 70 queries measured in DESIGN.md 5.10), "filter_cache" (1 = keep the compacted
  * sub-gallery for the next call with an equal bitmap (default); 0 = free it now and at the end of every call, and do not
  * compact a bitmap only because it came twice; a kept sub-gallery holds up to 12 KB of HBM per allowed row at D = 2048).
- * mi_get_option also answers "image_dtype" (1 = fp16, 0 = bf16; read-only, see mi_gallery_set_image_dtype) and
- * "sample_rows" (rows of the threshold sample in effect). */
+ * mi_get_option also answers "image_dtype" (1 = fp16, 0 = bf16; read-only, see mi_gallery_set_image_dtype),
+ * "sample_rows" (rows of the threshold sample in effect) and "metric" (an mi_metric value; read-only). */
 int mi_set_option(mi_gallery* g, const char* name, double value);
 int mi_get_option(const mi_gallery* g, const char* name, double* out_value);   /* same names as mi_set_option */
 /* Synchronises the handle's work, returns the sticky device flags raised by the asynchronous _device entry points since
