@@ -57,6 +57,7 @@ SIGNATURES = {
     "mi_desc_ms_accumulate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_int, C.c_void_p]),
     "mi_desc_ms_finish_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "mi_gallery_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "mi_gallery_remove_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64p]),
     "mi_gallery_destroy": (C.c_int, [C.c_void_p]),
     "mi_gallery_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32), c_i64p, c_i64p]),
@@ -357,6 +358,24 @@ class Gallery:
         with self._lock:
             check(load().mi_gallery_append(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST))
             self.n += a.shape[0]
+
+    def remove(self, rows):
+        """Removes rows in place (mi_gallery_remove_rows; faiss IndexFlat.remove_ids): `rows` is anything allow_bitmap takes
+        -- a bool mask [n] over the shard's rows, an array of GLOBAL ids (duplicates are fine), or packed AllowBits words.
+        The survivors keep their order and are renumbered from row_offset on.  -> kept int64 [n']: kept[j] is the old global
+        id of new row j (index a list of paths with `kept - row_offset`).  Raises ValueError, before the library is called,
+        on an id outside [row_offset, row_offset + n).  The image type stays; the cached sub-gallery of the filtered
+        search and the offline diffusion matrix are dropped.  Refused while an OnlineChain is built on the gallery."""
+        bits = allow_bitmap(rows, self.n, self.row_offset)
+        gone = np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), bitorder="little")[:self.n].astype(np.bool_)
+        kept = np.flatnonzero(~gone).astype(np.int64) + int(self.row_offset)
+        removed = C.c_int64()
+        with self._lock:
+            check(load().mi_gallery_remove_rows(self._h, C.c_void_p(bits.ctypes.data), MI_HOST, C.byref(removed)))
+            if self.n - removed.value != kept.size:
+                raise RuntimeError("mi_gallery_remove_rows removed %d rows, the bitmap names %d" % (removed.value, self.n - kept.size))
+            self.n = int(kept.size)
+        return kept
 
     @classmethod
     def from_blocks(cls, blocks, norm_mode=NORM_L2, device=0, row_offset=0, chunk_rows=131072):

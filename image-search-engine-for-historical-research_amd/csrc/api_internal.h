@@ -11,6 +11,7 @@
 //   api_range.hip     exact range search: fixed-threshold chunk schedule, overflow split, dense chunks, CSR tail
 //   api_filter.hip    filtered top-K: compacted sub-gallery (cached per bitmap) or over-fetch with a certificate
 //   api_l2.hip        squared-L2 metric: L2 galleries (hidden bias columns), top-K by distance (host / device), dense checker
+//   api_remove.hip    row removal in place: keep-list, block-ordered move through a bounded staging area, invalidations
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -60,6 +61,7 @@ extern MI_INTERNAL SpareBuffers g_spare;
 extern MI_INTERNAL SpareArena g_spare_ws;
 extern MI_INTERNAL std::atomic<int> g_keep_buffers;
 extern MI_INTERNAL std::atomic<int64_t> g_scatter_block_rows;   // mi_scatter_matrix: rows per host block (0 = 64 MiB)
+extern MI_INTERNAL std::atomic<int64_t> g_remove_block_rows;    // mi_gallery_remove_rows: rows of the staging area (0 = default)
 constexpr size_t SPARE_MAX_BYTES = (size_t)16 << 30;
 MI_INTERNAL void spare_release_locked();
 MI_INTERNAL void spare_ws_release_locked();
@@ -235,7 +237,7 @@ struct mi_gallery {
     unsigned long long* total = nullptr;   // hits of the current chunk
   } range;
   // filtered top-K search (api_filter.hip): grow-only device buffers and the compacted sub-gallery, freed with the handle, never
-  // handed to the spare-buffer slots; invalidated by mi_gallery_append* and mi_gallery_set_image_dtype (filter_invalidate)
+  // handed to the spare-buffer slots; invalidated by mi_gallery_append*, mi_gallery_set_image_dtype and mi_gallery_remove_rows (filter_invalidate)
   int filter_path = 0;                 // option "filter_path": 0 = auto, 1 = always compact, 2 = always over-fetch
   double filter_compact_max = 0.15;    // option "filter_compact_max": auto compacts at selectivity <= this
   int filter_cache = 1;                // option "filter_cache": keep the sub-gallery for the next call with the same bitmap
@@ -275,7 +277,13 @@ struct mi_gallery {
     double* odist64 = nullptr;
     size_t out_cap = 0;
   } l2;
-  // diffusion state (offline matrix rows kept on the device for the online stage)
+  // row removal (api_remove.hip): one grow-only arena -- staging area of "remove_block_rows" rows in the gallery's own layout,
+  // keep-list, bitmap, scan buffers --, freed with the handle, never handed to the spare-buffer slots
+  struct RemoveScratch {
+    void* arena = nullptr;
+    size_t bytes = 0;
+  } rm;
+  // diffusion state (offline matrix rows kept on the device for the online stage); dropped by mi_gallery_remove_rows
   int32_t* dif_ids = nullptr;
   float* dif_vals = nullptr;
   int32_t dif_T = 0;
@@ -332,6 +340,8 @@ MI_INTERNAL int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, i
                                      mi_filter_info* out_info, double* out_seconds, bool l2_caller);
 // ---- api_l2.hip
 MI_INTERNAL void l2_scratch_free(mi_gallery* g);
+// ---- api_remove.hip
+MI_INTERNAL void remove_scratch_free(mi_gallery* g);
 // entry points that are not defined on a squared-L2 gallery (include/mi355_retrieval.h: mi_metric)
 #define REFUSE_L2(g, what)                                                                                          \
   do {                                                                                                              \

@@ -26,6 +26,7 @@ SpareBuffers g_spare;
 SpareArena g_spare_ws;
 std::atomic<int> g_keep_buffers{1};
 std::atomic<int64_t> g_scatter_block_rows{0};
+std::atomic<int64_t> g_remove_block_rows{0};
 void spare_release_locked() {
   if (g_spare.device < 0) return;
   int cur = 0;
@@ -241,6 +242,10 @@ int mi_set_global_option(const char* name, double value) {
     REQUIRE(value >= 0 && value <= 1e9, "scatter_block_rows: rows per host block of mi_scatter_matrix (0 = 64 MiB blocks)");
     g_scatter_block_rows = (int64_t)value;
   }
+  else if (n == "remove_block_rows") {
+    REQUIRE(value >= 0 && value <= 1e9, "remove_block_rows: rows of the staging area of mi_gallery_remove_rows (0 = default)");
+    g_remove_block_rows = round_up((int64_t)value, TILE);
+  }
   else if (n == "release_spares") {
     // gives the spare slots back NOW and leaves the mode alone (a caller that is done with its galleries for a while --
     // nnsearch.drop_cached_galleries -- or a co-tenant that needs the memory)
@@ -259,6 +264,7 @@ int mi_get_global_option(const char* name, double* out_value) {
   else if (n == "host_ingest") *out_value = g_host_ingest.load();
   else if (n == "keep_buffers") *out_value = g_keep_buffers.load();
   else if (n == "scatter_block_rows") *out_value = (double)g_scatter_block_rows.load();
+  else if (n == "remove_block_rows") *out_value = (double)g_remove_block_rows.load();
   else if (n == "spare_bytes") {
     // device memory this process holds in the spare slots right now (gallery buffers + search workspace of destroyed handles)
     std::lock_guard<std::mutex> lock(g_spare_mu);

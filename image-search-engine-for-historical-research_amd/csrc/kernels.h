@@ -250,6 +250,16 @@ void launch_filter_overfetch(const int64_t* in_idx, const float* in_sc, int64_t 
 void launch_filter_remap(const int64_t* sidx, const float* ssc, int64_t nq, int32_t ke, int32_t k, const uint32_t* rows,
                          int64_t m, int64_t row_offset, int64_t* out_idx, float* out_sc, hipStream_t stream);
 
+// row_remove.hip -- in-place row removal (api_remove.hip): surviving rows rows[j0 .. j1) (padding rows up to j1_pad, j >= m,
+// written as zeros) gathered into a staging area of the gallery's own layout, and the staging area written back as three
+// contiguous runs (rows_f32 f32 rows, rows_pad image rows and RowStats)
+void launch_remove_gather(const float* src_f32, const void* src_img, const RowStat* src_stat, const uint32_t* rows, int64_t j0,
+                          int64_t j1_pad, int64_t m, int32_t dp, float* stg_f32, void* stg_img, RowStat* stg_stat,
+                          hipStream_t stream);
+void launch_remove_writeback(const float* stg_f32, const void* stg_img, const RowStat* stg_stat, int64_t rows_f32,
+                             int64_t rows_pad, int32_t dp, float* dst_f32, void* dst_img, RowStat* dst_stat,
+                             hipStream_t stream);
+
 // l2_metric.hip -- squared-L2 metric (api_l2.hip): hidden bias columns of stored rows, query extension, direct-form f64 tail,
 // dense direct-form distances (stored negated for launch_dense_topk64) and their emit
 void launch_l2_bias(float* gal_f32, void* gal_img, int img_f16, RowStat* rowstat, int32_t dp, int32_t d, int64_t row0,

@@ -61,5 +61,14 @@ class KNN:
         lims, ids, sims, _ = self.gallery.range_search(queries, float(thresh))
         return lims, sims, ids
 
+    def remove_ids(self, ids):
+        """faiss's IndexFlat.remove_ids, both metrics: the rows leave the index, the others keep their order and are renumbered
+        0 .. N' - 1.  ids: an array of row ids (duplicates are fine), a bool mask [N] or packed AllowBits words.  -> the number
+        of rows removed."""
+        before = self.gallery.n
+        self.gallery.remove(ids)
+        self.N = self.gallery.n
+        return before - self.N
+
     def close(self):
         self.gallery.close()

@@ -96,7 +96,9 @@ def get_gallery(train, dataset=None, ifgenerate=False, norm_mode=NORM_L2, device
     dataset=None: a fresh (uncached) gallery.  Otherwise the gallery is cached in-process under
     `dataset`, persisted to outputs/<dataset>/mi355_gallery_<norm>.bin (written behind the call, _save_behind), and rebuilt
     iff `ifgenerate` (or when its shape no longer matches `train`, which the reference leaves to the user:
-    README "delete the cache when the database changes")."""
+    README "delete the cache when the database changes").  The cache and the file are keyed by `dataset`, not by content: a
+    caller who takes rows out of the returned gallery (Gallery.remove) saves it again (Gallery.save over the file) or passes
+    `ifgenerate` with the reduced `train` the next time -- otherwise the next process loads the rows that were removed."""
     last_timing.clear()
     if dataset is None:
         t0 = time.time()

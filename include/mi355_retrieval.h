@@ -81,6 +81,24 @@ int mi_gallery_append_device(mi_gallery* g, const float* rows_dev /*[m][d] f32*/
  * with strides on the device: no host transpose, no concatenated host copy, no float64 promotion. */
 int mi_gallery_append(mi_gallery* g, const void* data, int64_t m, int dtype, int64_t row_stride, int64_t col_stride,
                       int memspace);
+/* Removes rows in place (faiss IndexFlat.remove_ids).  remove_bits has the layout of allow_bits in mi_knn_search_filtered:
+ * ceil(n / 64) words, bit (i & 63) of word (i >> 6) names LOCAL row i, bits at or beyond n are ignored; memspace is MI_HOST or
+ * MI_DEVICE (a device bitmap must be complete when the call is made).  The surviving rows keep their relative order and are
+ * renumbered 0 .. n' - 1: new row j is the j-th surviving old row.  row_offset and the capacity do not change; *out_removed (may
+ * be NULL) receives n - n'.  Afterwards every section of the prepared gallery -- stored f32 rows, 16-bit image, rounding norms,
+ * their padding rows up to the old padded size, the norm maxima, n -- holds, bit for bit, what the same ingest path would have
+ * written for the surviving source rows alone AT THE SAME IMAGE TYPE: removing the one large row of a raw bf16 gallery does not
+ * turn it into fp16 (mi_gallery_set_image_dtype is the caller's tool for that).  A bitmap with no bit set below n leaves the
+ * gallery untouched; one that names every row leaves an empty appendable gallery of the same capacity and image type.  Works
+ * on galleries of either metric and every norm mode.  Synchronous on the handle's stream; like mi_range_search it completes a
+ * pending deferred tail first (its ids are in the old numbering).  Dropped with the old numbering: the cached sub-gallery of
+ * the filtered search, the threshold samples, and the offline diffusion matrix (mi_diffusion_online then answers as on a handle
+ * that never had one).  MI_ERR_INVALID while an online handle is built on the gallery (mi_online_destroy comes first), as for
+ * mi_gallery_destroy.  Device memory beyond the gallery is bounded independently of n: a staging area of at most B rows in the gallery's
+ * layout (B * (6 * d64 + 12) bytes; global option "remove_block_rows", an upper limit), 4 bytes per surviving row and the bitmap, kept on the
+ * handle for the next call.  Shards of a sharded gallery are out of scope: the maxima the shards agreed on
+ * (mi_gallery_norm_bounds) are replaced by the shard's own.  DESIGN.md 5.12. */
+int mi_gallery_remove_rows(mi_gallery* g, const uint64_t* remove_bits, int memspace, int64_t* out_removed);
 int mi_gallery_destroy(mi_gallery* g);
 int mi_gallery_info(const mi_gallery* g, int64_t* n, int32_t* d, int32_t* norm_mode, int32_t* device,
                     int64_t* row_offset, int64_t* hbm_bytes);
@@ -121,7 +139,7 @@ int mi_range_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t
  * and dtype as in mi_knn_search (host input, host output).  out_score, out_info and out_seconds may be NULL.
  * Two exact paths, chosen per call from the selectivity s = allowed / n (options "filter_path",
  * "filter_compact_max"): 1 = the allowed rows are copied into a sub-gallery owned by the handle and searched (kept for the next
- * call with an equal bitmap while option "filter_cache" is 1; dropped by mi_gallery_append* and mi_gallery_set_image_dtype);
+ * call with an equal bitmap while option "filter_cache" is 1; dropped by mi_gallery_append*, mi_gallery_set_image_dtype, mi_gallery_remove_rows);
  * 2 = the unfiltered search at depth K' = min(2048, ceil(1.25 k / s) + 32), keeping the first k allowed entries; a query that
  * found fewer while K' did not cover the shard is answered by path 1 instead.  Like mi_range_search, the call completes a
  * pending deferred tail first and leaves the sticky flags (mi_search_flags) as it found them. */
@@ -468,12 +486,16 @@ int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
  * carved allocation of ~200 MB) in one spare slot each per process, and the next gallery of exactly the same sizes on the same
  * device takes them instead of allocating: a caller that prepares a gallery per call (create, search, destroy: a stateless
  * matching_<method>, src/utils/nnsearch.py:687-706) stops paying 1-6 ms of hipMalloc / hipFree per 12 GB and ~4 ms for the
- * workspace; 0 = free the spares now and keep nothing. */
+ * workspace; 0 = free the spares now and keep nothing.
+ * "remove_block_rows": upper limit B of the rows of the staging area mi_gallery_remove_rows moves the surviving rows through
+ * (rounded up to a multiple of 256; 0 = default, 32 768 -- a first choice, not yet taken from a measured sweep).  The call uses
+ * fewer rows when fewer move, and gives up whole tiles of 256 rows so that the allocation, as the driver rounds it, stays within
+ * B * (6 * d64 + 12) bytes + 4 bytes per surviving row + the bitmap + 1 MiB. */
 int mi_set_global_option(const char* name, double value);
 /* "release_spares" (any value) gives the spare slots back now and leaves "keep_buffers" as it is.  An allocation of the library
  * that fails with out-of-memory releases them by itself and is tried once more; a gallery of other sizes than the spare releases
- * it when the device could not hold both.  mi_get_global_option reads "image_dtype", "host_ingest", "keep_buffers" and
- * "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
+ * it when the device could not hold both.  mi_get_global_option reads "image_dtype", "host_ingest", "keep_buffers", "scatter_block_rows",
+ * "remove_block_rows" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
  * extractor's PyTorch allocator) cannot see otherwise. */
 int mi_get_global_option(const char* name, double* out_value);
 
