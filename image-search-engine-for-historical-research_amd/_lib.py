@@ -78,6 +78,18 @@ SIGNATURES = {
                                           C.c_void_p]),
     "mi_knn_dense64_search_l2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_hamming_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                    C.POINTER(C.c_void_p)]),
+    "mi_hamming_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    "mi_hamming_append_sign_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),
+    "mi_pack_sign_bits_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mi_hamming_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i64p, c_i64p, c_i64p]),
+    "mi_hamming_get_codes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "mi_hamming_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_void_p, c_f64p]),
+    "mi_hamming_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "mi_hamming_destroy": (C.c_int, [C.c_void_p]),
     "mi_knn_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "mi_knn_phase1_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -776,6 +788,149 @@ class Gallery:
         st = SearchStats()
         check(load().mi_search_status(self._h, C.byref(st), 1 if reset else 0))
         return st.as_dict()
+
+
+def pack_bits(a01):
+    """0/1 (or bool) values [*, code_len] -> packed codes uint8 [*, ceil(code_len / 8)]: bit j of a code is bit (j & 7) of byte
+    (j >> 3) (np.packbits(..., bitorder='little'), faiss's convention); a code_len that is no multiple of 8 is padded with zero
+    bits.  Raises ValueError on any value other than 0 / 1."""
+    a = np.asarray(a01)
+    if a.ndim < 1:
+        raise ValueError("expected an array [*, code_len]")
+    if a.dtype != np.bool_:
+        if not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+            raise ValueError("binary codes must be bool or numeric 0 / 1 values (got %s)" % a.dtype)
+        if a.size and not np.logical_or(a == 0, a == 1).all():
+            raise ValueError("binary codes must hold only the values 0 and 1")
+        a = a != 0
+    return np.packbits(a, axis=-1, bitorder="little")
+
+
+def unpack_bits(codes, code_len=None):
+    """Inverse of pack_bits: uint8 [*, nbytes] -> uint8 0/1 [*, code_len] (default 8 * nbytes)."""
+    bits = np.unpackbits(np.asarray(codes, np.uint8), axis=-1, bitorder="little")
+    return bits if code_len is None else bits[..., :int(code_len)]
+
+
+def pack_sign_bits_device(x_ptr, n, d, out_ptr, row_stride=None, out_row_stride=None, stream=None):
+    """Device rows x [n][d] f32 -> packed sign codes [n][d / 8] uint8 on the device (bit j = x[j] > 0), enqueued on `stream`."""
+    check(load().mi_pack_sign_bits_device(C.c_void_p(x_ptr), int(n), int(d), int(d if row_stride is None else row_stride),
+                                          C.c_void_p(out_ptr), int(d // 8 if out_row_stride is None else out_row_stride),
+                                          C.c_void_p(stream)))
+
+
+def _code_rows(codes, nbytes=None):
+    """uint8 [m, nbytes] with a whole-byte, non-negative row stride and contiguous rows (copied once otherwise)."""
+    a = np.asarray(codes)
+    if a.ndim != 2 or a.dtype != np.uint8:
+        raise ValueError("packed codes must be a uint8 array [rows, nbits / 8] (see pack_bits)")
+    if nbytes is not None and a.shape[1] != nbytes:
+        raise ValueError("codes of %d bytes, the index holds codes of %d bytes" % (a.shape[1], nbytes))
+    if a.shape[1] > 1 and a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a, max(int(a.strides[0]), a.shape[1])
+
+
+class BinaryGallery:
+    """Binary index on one MI355X (a `mi_hamming` handle): exact Hamming top-k on packed codes, ties to the lower id."""
+
+    def __init__(self, handle):
+        self._h = C.c_void_p(handle)
+        self._lock = threading.Lock()
+        n, nbits, dev, off, cap, hb = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        check(load().mi_hamming_info(self._h, n, nbits, dev, off, cap, hb))
+        self.n, self.nbits, self.device, self.row_offset, self.capacity = n.value, nbits.value, dev.value, off.value, cap.value
+
+    @classmethod
+    def from_host(cls, codes, device=0, row_offset=0, capacity=0):
+        """codes: uint8 [N, nbits / 8] (pack_bits); capacity 0 = N, larger leaves room for append()."""
+        a, stride = _code_rows(codes)
+        h = C.c_void_p()
+        check(load().mi_hamming_create(C.c_void_p(a.ctypes.data), a.shape[0], a.shape[1] * 8, stride, MI_HOST, device,
+                                       row_offset, int(capacity), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_device_ptr(cls, ptr, n, nbits, device=0, row_offset=0, capacity=0, row_stride_bytes=None):
+        """Device codes [n][nbits / 8] uint8 -> index, synchronous; the producer of `ptr` must have completed."""
+        h = C.c_void_p()
+        check(load().mi_hamming_create(C.c_void_p(ptr), int(n), int(nbits),
+                                       int(nbits) // 8 if row_stride_bytes is None else int(row_stride_bytes), MI_DEVICE, device,
+                                       row_offset, int(capacity), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def empty(cls, capacity, nbits, device=0, row_offset=0):
+        """Appendable index: `capacity` rows allocated, filled by append() / append_sign_device()."""
+        h = C.c_void_p()
+        check(load().mi_hamming_create(None, 0, int(nbits), int(nbits) // 8, MI_HOST, device, row_offset, int(capacity),
+                                       C.byref(h)))
+        return cls(h.value)
+
+    @property
+    def hbm_bytes(self):
+        hb = C.c_int64()
+        check(load().mi_hamming_info(self._h, None, None, None, None, None, hb))
+        return hb.value
+
+    def append(self, codes):
+        a, stride = _code_rows(codes, self.nbits // 8)
+        with self._lock:
+            check(load().mi_hamming_append(self._h, C.c_void_p(a.ctypes.data), a.shape[0], stride, MI_HOST))
+            self.n += a.shape[0]
+
+    def append_sign_device(self, x_ptr, m, d, row_stride=None, stream=None):
+        """m device rows [m][d] f32, d == nbits: their sign bits (x > 0) are appended on `stream`."""
+        with self._lock:
+            check(load().mi_hamming_append_sign_device(self._h, C.c_void_p(x_ptr), int(m), int(d),
+                                                       int(d if row_stride is None else row_stride), C.c_void_p(stream)))
+            self.n += int(m)
+
+    def search(self, qcodes, k, allow=None, allow_ptr=None):
+        """-> (ids int64 [Q,k], dist int32 [Q,k], seconds), ordered by (distance asc, id asc).  allow: anything allow_bitmap
+        takes (bool mask, global ids, AllowBits words); allow_ptr: a device bitmap of ceil(n / 64) uint64 words.  Fewer than k
+        admitted rows: trailing ids -1, distances INT32_MAX."""
+        a, stride = _code_rows(qcodes, self.nbits // 8)
+        nq, k = a.shape[0], int(k)
+        if allow is not None and allow_ptr is not None:
+            raise ValueError("give at most one of allow and allow_ptr")
+        bits, bits_p, memspace = None, None, MI_HOST
+        if allow is not None:
+            bits = allow_bitmap(allow, self.n, self.row_offset)
+            if bits.size == 0:
+                bits = np.zeros(1, "<u8")
+            bits_p = C.c_void_p(bits.ctypes.data)
+        elif allow_ptr is not None:
+            bits_p, memspace = C.c_void_p(int(allow_ptr)), MI_DEVICE
+        idx = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.int32)
+        secs = C.c_double()
+        with self._lock:
+            check(load().mi_hamming_search(self._h, C.c_void_p(a.ctypes.data), nq, stride, k, bits_p, memspace,
+                                           idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p), C.byref(secs)))
+        return idx, dist, secs.value
+
+    def search_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, allow_ptr=None, stream=None):
+        check(load().mi_hamming_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(allow_ptr),
+                                              C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def get_codes(self, row0=0, nrows=None):
+        nrows = self.n - row0 if nrows is None else int(nrows)
+        out = np.empty((nrows, self.nbits // 8), dtype=np.uint8)
+        with self._lock:
+            check(load().mi_hamming_get_codes(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            check(load().mi_hamming_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def kth_of_gathered_device(gathered_ptr, nshards, nq, k, out_ptr, stream=None):

@@ -1,0 +1,281 @@
+// Binary index of the C ABI: exact Hamming top-K on packed binary codes (mi_hamming; kernels in csrc/hamming.hip).
+// The reference's matching_Greedyhash (src/utils/nnsearch.py:1001-1013), faiss IndexBinaryFlat.  A handle of its own: codes in
+// transposed 64-row blocks, a uint16 distance matrix of at most "hamming_matrix_bytes" (queries go through it in chunks), grow-only
+// staging for queries, bitmap and host results.  Integer and exact: no certificate, no flag, no fallback.
+#include "api_internal.h"
+
+struct mi_hamming {
+  int device = 0;
+  int64_t n = 0, cap = 0, row_offset = 0;
+  int32_t nbits = 0, nb = 0, W32 = 0, wq = 0;      // bits, bytes, 32-bit words of a code; words of a stored query
+  uint32_t* codes = nullptr;                       // [ceil(cap / 64)][W32][64]
+  size_t codes_bytes = 0;
+  hipStream_t stream = nullptr;
+  uint8_t* qraw = nullptr;                         // query bytes of a host call, packed [nq][nb]
+  size_t qraw_cap = 0;
+  uint32_t* qw = nullptr;                          // [nq][wq]
+  size_t qw_cap = 0;
+  uint16_t* mat = nullptr;                         // distance matrix [queries of a chunk][round_up(n, 64)]
+  size_t mat_cap = 0;
+  uint64_t* bits = nullptr;                        // device copy of a host bitmap
+  size_t bits_cap = 0;
+  int64_t* oidx = nullptr;                         // results of a host call
+  int32_t* odist = nullptr;
+  size_t oidx_cap = 0, odist_cap = 0;
+  std::mutex mu;
+};
+
+template <typename T>
+static int hm_grow(T** p, size_t* cap, size_t count) {
+  if (*p && *cap >= count) return MI_OK;
+  (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = count + count / 4 + 64;
+  HIPC(device_malloc((void**)p, want * sizeof(T)));
+  *cap = want;
+  return MI_OK;
+}
+
+static int64_t hm_scratch_bytes(const mi_hamming* h) {
+  return (int64_t)(h->qraw_cap + h->qw_cap * 4 + h->mat_cap * 2 + h->bits_cap * 8 + h->oidx_cap * 8 + h->odist_cap * 4);
+}
+
+// m host rows of nb bytes at `stride` -> packed device rows, on stream s
+static int hm_copy_rows(uint8_t* dst, const uint8_t* src, int64_t stride, int32_t nb, int64_t m, hipStream_t s) {
+  if (stride == nb || m == 1) HIPC(hipMemcpyAsync(dst, src, (size_t)m * nb, hipMemcpyHostToDevice, s));
+  else HIPC(hipMemcpy2DAsync(dst, (size_t)nb, src, (size_t)stride, (size_t)nb, (size_t)m, hipMemcpyHostToDevice, s));
+  return MI_OK;
+}
+
+// m packed-or-strided rows of code bytes (host or device) -> rows n .. n + m of the index, synchronous on the handle's stream.
+// Host rows pass through a staging buffer of at most 64 MiB at a time.
+static int hm_ingest(mi_hamming* h, const void* codes, int64_t m, int64_t stride, int memspace) {
+  hipStream_t s = h->stream;
+  if (memspace == MI_DEVICE) {
+    launch_hamming_ingest((const uint8_t*)codes, stride, h->nbits, h->n, m, h->codes, s);
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));
+    return MI_OK;
+  }
+  const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / h->nb);
+  int rc;
+  TmpAlloc tmp;
+  uint8_t* stage = tmp.get<uint8_t>((size_t)std::min(step, m) * h->nb);
+  if (!stage) return fail(MI_ERR_NOMEM, "staging buffer of the code ingest");
+  for (int64_t r = 0; r < m; r += step) {
+    const int64_t mm = std::min(step, m - r);
+    if ((rc = hm_copy_rows(stage, (const uint8_t*)codes + r * stride, stride, h->nb, mm, s)) != MI_OK) return rc;
+    launch_hamming_ingest(stage, h->nb, h->nbits, h->n + r, mm, h->codes, s);
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));                 // the staging buffer is reused by the next block
+  }
+  return MI_OK;
+}
+
+// the search proper on stream s: queries are words in h->qw, results go to device buffers
+static int hm_search_core(mi_hamming* h, int64_t nq, int32_t k, const uint64_t* allow_dev, int64_t* out_idx_dev,
+                          int32_t* out_dist_dev, hipStream_t s) {
+  const int64_t npad = round_up(h->n, 64);
+  const int64_t budget = g_hamming_matrix_bytes.load();
+  const int64_t qc = npad == 0 ? nq : std::max<int64_t>(1, std::min<int64_t>(nq, budget / (npad * 2)));
+  int rc;
+  if ((rc = hm_grow(&h->mat, &h->mat_cap, (size_t)std::max<int64_t>(qc * npad, 64))) != MI_OK) return rc;
+  for (int64_t q0 = 0; q0 < nq; q0 += qc) {
+    const int32_t b = (int32_t)std::min<int64_t>(qc, nq - q0);
+    launch_hamming_dist(h->codes, h->nbits, h->n, h->qw + q0 * h->wq, b, allow_dev, h->mat, s);
+    launch_hamming_select(h->mat, h->n, h->nbits, b, k, h->row_offset, out_idx_dev + q0 * k,
+                          out_dist_dev ? out_dist_dev + q0 * k : nullptr, s);
+  }
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+extern "C" {
+
+int mi_hamming_create(const void* codes, int64_t n, int32_t nbits, int64_t row_stride_bytes, int memspace, int device,
+                      int64_t row_offset, int64_t capacity, mi_hamming** out) {
+  REQUIRE(out, "null pointer: out");
+  REQUIRE(n >= 0, "negative number of rows");
+  REQUIRE(nbits >= 8 && nbits <= 4096 && nbits % 8 == 0, "nbits must be a multiple of 8 in [8, 4096]");
+  REQUIRE(capacity >= 0, "negative capacity");
+  REQUIRE(capacity == 0 || capacity >= n, "capacity below the number of rows");
+  REQUIRE(codes || n == 0, "null pointer: codes");
+  REQUIRE(n >= 1 || capacity >= 1, "an empty index needs a capacity");
+  REQUIRE(n == 0 || row_stride_bytes >= nbits / 8, "row_stride_bytes below nbits / 8");
+  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
+  if (capacity == 0) capacity = n;
+  REQUIRE(capacity < (int64_t)1 << 32, "an index holds at most 2^32-1 rows");
+  HIPC(hipSetDevice(device));
+  mi_hamming* h = new mi_hamming();
+  h->device = device;
+  h->cap = capacity;
+  h->row_offset = row_offset;
+  h->nbits = nbits;
+  h->nb = nbits / 8;
+  h->W32 = (nbits + 31) / 32;
+  h->wq = hamming_query_words(h->W32);
+  h->codes_bytes = (size_t)((capacity + 63) / 64) * h->W32 * 64 * 4;
+  auto cleanup = [&](int code) {
+    mi_hamming_destroy(h);
+    return code;
+  };
+  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = device_malloc((void**)&h->codes, h->codes_bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(h->codes, 0, h->codes_bytes, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess)
+    return cleanup(fail(e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, std::string("binary index: ") + hipGetErrorString(e)));
+  if (n > 0) {
+    const int rc = hm_ingest(h, codes, n, row_stride_bytes, memspace);
+    if (rc != MI_OK) return cleanup(rc);
+    h->n = n;
+  }
+  *out = h;
+  return MI_OK;
+}
+
+int mi_hamming_append(mi_hamming* h, const void* codes, int64_t m, int64_t row_stride_bytes, int memspace) {
+  REQUIRE(h, "null handle");
+  REQUIRE(m >= 0, "negative number of rows");
+  REQUIRE(codes || m == 0, "null pointer: codes");
+  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
+  REQUIRE(m == 0 || row_stride_bytes >= h->nb, "row_stride_bytes below nbits / 8");
+  std::lock_guard<std::mutex> lock(h->mu);
+  REQUIRE(h->n + m <= h->cap, "index capacity exceeded");
+  if (m == 0) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  const int rc = hm_ingest(h, codes, m, row_stride_bytes, memspace);
+  if (rc != MI_OK) return rc;
+  h->n += m;
+  return MI_OK;
+}
+
+int mi_hamming_append_sign_device(mi_hamming* h, const float* x_dev, int64_t m, int32_t d, int64_t row_stride, void* stream) {
+  REQUIRE(h, "null handle");
+  REQUIRE(m >= 0, "negative number of rows");
+  REQUIRE(x_dev || m == 0, "null pointer: x_dev");
+  REQUIRE(d == h->nbits, "d must equal the index's nbits");
+  REQUIRE(m == 0 || row_stride >= d, "row_stride below d");
+  REQUIRE(h->n + m <= h->cap, "index capacity exceeded");
+  if (m == 0) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  launch_hamming_sign(x_dev, m, d, row_stride, nullptr, 0, h->codes, h->n, (hipStream_t)stream);
+  HIPC(hipGetLastError());
+  h->n += m;
+  return MI_OK;
+}
+
+int mi_pack_sign_bits_device(const float* x_dev, int64_t n, int32_t d, int64_t row_stride, uint8_t* out_dev,
+                             int64_t out_row_stride_bytes, void* stream) {
+  REQUIRE(n >= 0, "negative number of rows");
+  REQUIRE(d >= 8 && d % 8 == 0, "d must be a positive multiple of 8");
+  REQUIRE(n == 0 || (x_dev && out_dev), "null pointer");
+  REQUIRE(n == 0 || (row_stride >= d && out_row_stride_bytes >= d / 8), "row stride below the row length");
+  if (n == 0) return MI_OK;
+  launch_hamming_sign(x_dev, n, d, row_stride, out_dev, out_row_stride_bytes, nullptr, 0, (hipStream_t)stream);
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+int mi_hamming_info(const mi_hamming* h, int64_t* n, int32_t* nbits, int32_t* device, int64_t* row_offset, int64_t* capacity,
+                    int64_t* hbm_bytes) {
+  REQUIRE(h, "null handle");
+  if (n) *n = h->n;
+  if (nbits) *nbits = h->nbits;
+  if (device) *device = h->device;
+  if (row_offset) *row_offset = h->row_offset;
+  if (capacity) *capacity = h->cap;
+  if (hbm_bytes) *hbm_bytes = (int64_t)h->codes_bytes + hm_scratch_bytes(h);
+  return MI_OK;
+}
+
+int mi_hamming_get_codes(mi_hamming* h, int64_t row0, int64_t nrows, uint8_t* out_host) {
+  REQUIRE(h, "null handle");
+  REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= h->n, "row range outside the index");
+  REQUIRE(out_host || nrows == 0, "null pointer: out_host");
+  if (nrows == 0) return MI_OK;
+  std::lock_guard<std::mutex> lock(h->mu);
+  HIPC(hipSetDevice(h->device));
+  HIPC(hipStreamSynchronize(h->stream));
+  const int64_t blk_words = (int64_t)h->W32 * 64;
+  const int64_t step = 4096;                       // blocks per copy
+  std::vector<uint32_t> buf;
+  for (int64_t b0 = row0 / 64; b0 * 64 < row0 + nrows; b0 += step) {
+    const int64_t b1 = std::min(b0 + step, (row0 + nrows + 63) / 64);
+    buf.resize((size_t)((b1 - b0) * blk_words));
+    HIPC(hipMemcpy(buf.data(), h->codes + b0 * blk_words, buf.size() * 4, hipMemcpyDeviceToHost));
+    for (int64_t r = std::max(row0, b0 * 64); r < std::min(row0 + nrows, b1 * 64); ++r) {
+      const uint32_t* src = buf.data() + ((r >> 6) - b0) * blk_words + (r & 63);
+      uint8_t* dst = out_host + (r - row0) * h->nb;
+      for (int32_t j = 0; j < h->nb; ++j) dst[j] = (uint8_t)(src[(int64_t)(j >> 2) * 64] >> (8 * (j & 3)));
+    }
+  }
+  return MI_OK;
+}
+
+int mi_hamming_search(mi_hamming* h, const void* q_codes, int64_t nq, int64_t q_row_stride_bytes, int32_t k,
+                      const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, int32_t* out_dist, double* out_seconds) {
+  REQUIRE(h, "null handle");
+  REQUIRE(k >= 1 && k <= 2048, "k must be in [1, 2048]");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  REQUIRE(nq == 0 || q_codes, "null pointer: queries");
+  REQUIRE(nq == 0 || out_idx, "null pointer: out_idx");
+  REQUIRE(!allow_bits || allow_memspace == MI_HOST || allow_memspace == MI_DEVICE, "allow_memspace must be MI_HOST or MI_DEVICE");
+  if (out_seconds) *out_seconds = 0.0;
+  if (nq == 0) return MI_OK;
+  REQUIRE(q_row_stride_bytes >= h->nb, "q_row_stride_bytes below nbits / 8");
+  std::lock_guard<std::mutex> lock(h->mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  int rc;
+  const size_t cnt = (size_t)nq * k;
+  if ((rc = hm_grow(&h->qraw, &h->qraw_cap, (size_t)nq * h->nb)) != MI_OK) return rc;
+  if ((rc = hm_grow(&h->qw, &h->qw_cap, (size_t)nq * h->wq)) != MI_OK) return rc;
+  if ((rc = hm_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
+  if (out_dist && (rc = hm_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
+  const uint64_t* allow_dev = allow_bits;
+  if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
+    const size_t words = (size_t)((h->n + 63) / 64);
+    if ((rc = hm_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
+    HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
+    allow_dev = h->bits;
+  }
+  if ((rc = hm_copy_rows(h->qraw, (const uint8_t*)q_codes, q_row_stride_bytes, h->nb, nq, s)) != MI_OK) return rc;
+  launch_hamming_query_words(h->qraw, h->nb, h->nbits, nq, h->qw, s);
+  if ((rc = hm_search_core(h, nq, k, allow_dev, h->oidx, out_dist ? h->odist : nullptr, s)) != MI_OK) return rc;
+  HIPC(hipMemcpyAsync(out_idx, h->oidx, cnt * 8, hipMemcpyDeviceToHost, s));
+  if (out_dist) HIPC(hipMemcpyAsync(out_dist, h->odist, cnt * 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return MI_OK;
+}
+
+int mi_hamming_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, int32_t k, const uint64_t* allow_bits_dev,
+                             int64_t* out_idx_dev, int32_t* out_dist_dev, void* stream) {
+  REQUIRE(h, "null handle");
+  REQUIRE(k >= 1 && k <= 2048, "k must be in [1, 2048]");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  REQUIRE(nq == 0 || (q_dev && out_idx_dev), "null pointer");
+  if (nq == 0) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = hm_grow(&h->qw, &h->qw_cap, (size_t)nq * h->wq)) != MI_OK) return rc;
+  launch_hamming_query_words(q_dev, h->nb, h->nbits, nq, h->qw, s);
+  return hm_search_core(h, nq, k, allow_bits_dev, out_idx_dev, out_dist_dev, s);
+}
+
+int mi_hamming_destroy(mi_hamming* h) {
+  if (!h) return MI_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (void* p : {(void*)h->codes, (void*)h->qraw, (void*)h->qw, (void*)h->mat, (void*)h->bits, (void*)h->oidx, (void*)h->odist})
+    (void)hipFree(p);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+  return MI_OK;
+}
+
+}  // extern "C"

@@ -27,6 +27,10 @@ SpareArena g_spare_ws;
 std::atomic<int> g_keep_buffers{1};
 std::atomic<int64_t> g_scatter_block_rows{0};
 std::atomic<int64_t> g_remove_block_rows{0};
+// mi_set_global_option("hamming_matrix_bytes", ...): upper limit of the uint16 distance matrix of a binary index (api_hamming.hip);
+// a batch goes through it in chunks of queries, one query at the least
+constexpr int64_t HAMMING_MATRIX_DEFAULT = (int64_t)2 << 30;
+std::atomic<int64_t> g_hamming_matrix_bytes{HAMMING_MATRIX_DEFAULT};
 void spare_release_locked() {
   if (g_spare.device < 0) return;
   int cur = 0;
@@ -246,6 +250,10 @@ int mi_set_global_option(const char* name, double value) {
     REQUIRE(value >= 0 && value <= 1e9, "remove_block_rows: rows of the staging area of mi_gallery_remove_rows (0 = default)");
     g_remove_block_rows = round_up((int64_t)value, TILE);
   }
+  else if (n == "hamming_matrix_bytes") {
+    REQUIRE(value >= 0 && value <= 1e13, "hamming_matrix_bytes: bytes of the distance matrix of a binary index (0 = default, 2 GiB)");
+    g_hamming_matrix_bytes = value == 0 ? HAMMING_MATRIX_DEFAULT : (int64_t)value;
+  }
   else if (n == "release_spares") {
     // gives the spare slots back NOW and leaves the mode alone (a caller that is done with its galleries for a while --
     // nnsearch.drop_cached_galleries -- or a co-tenant that needs the memory)
@@ -265,6 +273,7 @@ int mi_get_global_option(const char* name, double* out_value) {
   else if (n == "keep_buffers") *out_value = g_keep_buffers.load();
   else if (n == "scatter_block_rows") *out_value = (double)g_scatter_block_rows.load();
   else if (n == "remove_block_rows") *out_value = (double)g_remove_block_rows.load();
+  else if (n == "hamming_matrix_bytes") *out_value = (double)g_hamming_matrix_bytes.load();
   else if (n == "spare_bytes") {
     // device memory this process holds in the spare slots right now (gallery buffers + search workspace of destroyed handles)
     std::lock_guard<std::mutex> lock(g_spare_mu);

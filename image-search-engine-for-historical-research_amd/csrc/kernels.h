@@ -274,6 +274,21 @@ void launch_l2_dense_dist(const float* gal_f32, const float* qry, int32_t dp, in
 void launch_l2_dense_emit(const int64_t* idx, const double* neg, int64_t nq, int32_t ke, int32_t k, int64_t* out_idx,
                           float* out_dist, double* out_dist64, hipStream_t stream);
 
+// hamming.hip -- exact Hamming top-K on packed binary codes (api_hamming.hip): gallery blocks of 64 rows with transposed words
+// codes[block][w < ceil(nbits / 32)][64], queries as row-major words [nq][hamming_query_words(W32)], uint16 distance matrix
+// [nq][round_up(n, 64)] (0xFFFF = row not admitted), counting selection by (distance asc, id asc)
+int32_t hamming_query_words(int32_t W32);       // words per stored query: the register tile of the distance kernel
+void launch_hamming_ingest(const uint8_t* src, int64_t stride, int32_t nbits, int64_t row0, int64_t m, uint32_t* codes,
+                           hipStream_t stream);
+void launch_hamming_query_words(const uint8_t* src, int64_t stride, int32_t nbits, int64_t nq, uint32_t* out, hipStream_t stream);
+void launch_hamming_dist(const uint32_t* codes, int32_t nbits, int64_t n, const uint32_t* qw, int32_t nq, const uint64_t* allow,
+                         uint16_t* dist, hipStream_t stream);
+void launch_hamming_select(const uint16_t* dist, int64_t n, int32_t nbits, int32_t nq, int32_t k, int64_t row_offset,
+                           int64_t* out_idx, int32_t* out_dist, hipStream_t stream);
+// out_bytes != NULL: rows of d / 8 bytes at out_rs; else the words of rows row0 .. row0 + n of a gallery of d-bit codes
+void launch_hamming_sign(const float* x, int64_t n, int32_t d, int64_t rs, uint8_t* out_bytes, int64_t out_rs, uint32_t* codes,
+                         int64_t row0, hipStream_t stream);
+
 // synth.hip
 void launch_synth_fill(float* dst, uint64_t seed, int64_t row0, int64_t nrows, int32_t d, hipStream_t stream);
 

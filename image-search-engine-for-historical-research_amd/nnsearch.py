@@ -228,6 +228,38 @@ def matching_L2_hip(K, embedded_features_train, embedded_features_test):
     return matching_HIP(K, embedded_features_train, embedded_features_test)
 
 
+def matching_Greedyhash_hip(K, hash_codes_train, hash_codes_test):
+    """Same signature and return shape as matching_Greedyhash (src/utils/nnsearch.py:1001-1013): exact Hamming top-K of 0/1 hash
+    codes [N, code_len] / [Q, code_len] (any integer or bool dtype) -> (idx int64 [Q, K], time_per_query).  The reference
+    sorts `(query ^ train).sum(axis=1)` with an unstable argsort; here rows at equal distance come by ascending index.
+    code_len is padded to a multiple of 8 with zero columns on both sides, which changes no distance.  K > N raises, as the
+    reference's `idx[row, :] = ...` assignment does.  The timer spans what the reference's spans: everything the call does
+    (packing, index build and search), device-synchronised."""
+    t1 = time.time()
+    train, test = np.asarray(hash_codes_train), np.asarray(hash_codes_test)
+    if train.ndim != 2 or test.ndim != 2 or train.shape[1] != test.shape[1]:
+        raise ValueError("expected hash codes [N, code_len] and [Q, code_len], got %s and %s" % (train.shape, test.shape))
+    for name, a in (("hash_codes_train", train), ("hash_codes_test", test)):
+        if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("%s: binary codes must be an integer or bool array of 0 / 1 values (got %s)" % (name, a.dtype))
+    K = int(K)
+    num_train, num_test = train.shape[0], test.shape[0]
+    if K > num_train or K < 1:
+        raise ValueError("K = %d, the database holds %d codes" % (K, num_train))
+    if K > TOPK_PATH_MAX_K:
+        raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
+    g = _lib.BinaryGallery.from_host(_lib.pack_bits(train))        # (pack_bits raises ValueError on anything but 0 / 1)
+    try:
+        idx, _, _ = g.search(_lib.pack_bits(test), K)
+    finally:
+        g.close()
+    return idx, (time.time() - t1) / num_test
+
+
+# the matchers of this build by the name the reference's entry points dispatch on (--matching_method, src/offline.py:107-118)
+MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip}
+
+
 def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test):
     """Same signature and return shape as matching_fractional_dis (src/utils/nnsearch.py:709-731).  The reference calls
     its fractional distance with p = 2 (:721), which orders the gallery exactly like matching_L2, and slices the QUERY

@@ -189,6 +189,52 @@ int mi_knn_search_l2_device(mi_gallery* g, const float* q_dev, int64_t nq, int32
 int mi_knn_dense64_search_l2(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                              int32_t k, int64_t* out_idx, float* out_dist, double* out_dist64, double* out_seconds);
 
+/* ---- binary index: exact Hamming top-K on packed binary codes.  The reference's matching_Greedyhash(K, hash_codes_train,
+ * hash_codes_test) (src/utils/nnsearch.py:1001-1013: XOR against every gallery code, sum, argsort, first K) and faiss
+ * IndexBinaryFlat (what IndexLSH, src/utils/nnsearch.py:734-745, searches with internally).  DESIGN.md 5.13.
+ * A code is nbits bits, nbits a multiple of 8 in [8, 4096], passed as nbits / 8 bytes per row: bit j is bit (j & 7) of byte
+ * (j >> 3) -- np.packbits(..., bitorder='little'), faiss's convention.  A 2048-bit code takes 256 bytes of HBM.  The handle is
+ * a type of its own, ONE row shard on ONE device like mi_gallery; none of the mi_gallery entry points takes it.  The answer is
+ * integer and fully determined: ids row_offset + local row ordered by (distance asc, id asc), ties at the K-th distance to the
+ * lowest ids, however many rows share it -- no certificate, no flag, no fallback path.  Out of scope for binary indexes: row
+ * removal, radius search, save / load, sharding.
+ * mi_hamming_create: n rows of `codes` (row i at codes + i * row_stride_bytes; MI_HOST or MI_DEVICE, device rows complete when
+ * the call is made) into an index of `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty
+ * appendable index.  Synchronous. */
+typedef struct mi_hamming mi_hamming; /* opaque */
+int mi_hamming_create(const void* codes, int64_t n, int32_t nbits, int64_t row_stride_bytes, int memspace, int device,
+                      int64_t row_offset, int64_t capacity, mi_hamming** out);
+/* m more rows, synchronous.  Beyond the capacity: MI_ERR_INVALID like mi_gallery_append, and the index stays as it was. */
+int mi_hamming_append(mi_hamming* h, const void* codes, int64_t m, int64_t row_stride_bytes, int memspace);
+/* Sign bits of m device rows x_dev [m][d] f32 (row i at x_dev + i * row_stride floats), d == nbits, appended without leaving
+ * the device: bit j = x[j] > 0 (NaN and +-0 give 0) -- GreedyHash's code layer is sign().  Enqueued on `stream`, no
+ * synchronisation: later calls on the handle go to the same stream (or follow its completion). */
+int mi_hamming_append_sign_device(mi_hamming* h, const float* x_dev, int64_t m, int32_t d, int64_t row_stride, void* stream);
+/* The same packing stand-alone (queries): n rows of d floats (d a multiple of 8) -> n rows of d / 8 bytes at
+ * out_row_stride_bytes.  Enqueued on `stream`. */
+int mi_pack_sign_bits_device(const float* x_dev, int64_t n, int32_t d, int64_t row_stride, uint8_t* out_dev,
+                             int64_t out_row_stride_bytes, void* stream);
+/* Any out pointer may be NULL.  hbm_bytes: codes plus the grow-only search buffers the handle holds right now. */
+int mi_hamming_info(const mi_hamming* h, int64_t* n, int32_t* nbits, int32_t* device, int64_t* row_offset, int64_t* capacity,
+                    int64_t* hbm_bytes);
+/* Rows [row0, row0 + nrows) as the caller gave them, nbits / 8 bytes each, to a host buffer. */
+int mi_hamming_get_codes(mi_hamming* h, int64_t row0, int64_t nrows, uint8_t* out_host);
+/* Host in, host out, synchronous.  q_codes: nq rows of nbits / 8 bytes at q_row_stride_bytes.  1 <= k <= 2048.  out_idx [nq][k]
+ * int64, out_dist [nq][k] int32 (may be NULL).  allow_bits NULL: every row; otherwise the bitmap of mi_knn_search_filtered
+ * (ceil(n / 64) words, bit (i & 63) of word (i >> 6) admits local row i; MI_HOST or MI_DEVICE), one bitmap for every query.
+ * Fewer than k admitted rows: trailing ids -1, distances INT32_MAX.  nq == 0 is MI_OK.  out_seconds (may be NULL): wall time
+ * of the call.  The queries of a call pass through a uint16 distance matrix [queries][n rounded up to 64] owned by the handle,
+ * in chunks that keep it within the global option "hamming_matrix_bytes" (default 2 GiB; one query at the least). */
+int mi_hamming_search(mi_hamming* h, const void* q_codes, int64_t nq, int64_t q_row_stride_bytes, int32_t k,
+                      const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, int32_t* out_dist, double* out_seconds);
+/* Device-resident variant, enqueued on `stream` without synchronising: q_dev packed [nq][nbits / 8], allow_bits_dev (may be
+ * NULL) and the outputs are device buffers (out_dist_dev may be NULL).  The answer is complete when the stream reaches it;
+ * there is no flag to read.  The call uses buffers of the handle (grown, i.e. freed and allocated again, when a larger batch
+ * comes): calls on one handle must be serialised by the caller and enqueued on ONE stream. */
+int mi_hamming_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, int32_t k, const uint64_t* allow_bits_dev,
+                             int64_t* out_idx_dev, int32_t* out_dist_dev, void* stream);
+int mi_hamming_destroy(mi_hamming* h); /* NULL is MI_OK */
+
 /* Device-resident variant: q_dev [nq][d] row-major f32 (C order), outputs are device buffers.
  * out_score64_dev (may be NULL) receives the float64 exact scores. */
 int mi_knn_search_device(mi_gallery* g, const float* q_dev, int64_t nq, int32_t k,
@@ -490,12 +536,13 @@ int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
  * "remove_block_rows": upper limit B of the rows of the staging area mi_gallery_remove_rows moves the surviving rows through
  * (rounded up to a multiple of 256; 0 = default, 32 768 -- a first choice, not yet taken from a measured sweep).  The call uses
  * fewer rows when fewer move, and gives up whole tiles of 256 rows so that the allocation, as the driver rounds it, stays within
- * B * (6 * d64 + 12) bytes + 4 bytes per surviving row + the bitmap + 1 MiB. */
+ * B * (6 * d64 + 12) bytes + 4 bytes per surviving row + the bitmap + 1 MiB.
+ * "hamming_matrix_bytes": upper limit of the distance matrix of a binary index (mi_hamming_search*; 0 = default, 2 GiB). */
 int mi_set_global_option(const char* name, double value);
 /* "release_spares" (any value) gives the spare slots back now and leaves "keep_buffers" as it is.  An allocation of the library
  * that fails with out-of-memory releases them by itself and is tried once more; a gallery of other sizes than the spare releases
  * it when the device could not hold both.  mi_get_global_option reads "image_dtype", "host_ingest", "keep_buffers", "scatter_block_rows",
- * "remove_block_rows" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
+ * "remove_block_rows", "hamming_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
  * extractor's PyTorch allocator) cannot see otherwise. */
 int mi_get_global_option(const char* name, double* out_value);
 
