@@ -90,6 +90,20 @@ SIGNATURES = {
     "mi_hamming_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "mi_hamming_destroy": (C.c_int, [C.c_void_p]),
+    "mi_pq_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                               C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "mi_pq_append_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    "mi_pq_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "mi_pq_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
+    "mi_pq_dtable": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p]),
+    "mi_pq_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int,
+                               C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_pq_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_pq_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                             C.POINTER(C.c_int32), c_i64p, c_i64p, c_i64p]),
+    "mi_pq_get_codes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "mi_pq_get_codebooks": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_pq_destroy": (C.c_int, [C.c_void_p]),
     "mi_knn_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "mi_knn_phase1_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -925,6 +939,197 @@ class BinaryGallery:
         if self._h is not None and self._h.value:
             check(load().mi_hamming_destroy(self._h))
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+PQ_MAX_BOOKS, PQ_MAX_WORDS, PQ_MAX_DIM = 64, 256, 4096
+
+
+def pq_codebooks(codebooks):
+    """float32 [M, Ks, L] C-contiguous codebooks (nanopq's pq.codewords, faiss's ProductQuantizer.centroids), checked against
+    what a PQ index takes: 1 <= M <= 64, 2 <= Ks <= 256, M * L <= 4096, finite.  Raises ValueError."""
+    cb = np.ascontiguousarray(codebooks, dtype=np.float32)
+    if cb.ndim != 3:
+        raise ValueError("codebooks must be [M, Ks, L] (got shape %s)" % (cb.shape,))
+    m, ks, L = cb.shape
+    if not 1 <= m <= PQ_MAX_BOOKS:
+        raise ValueError("M = %d books, a PQ index takes 1 .. %d" % (m, PQ_MAX_BOOKS))
+    if not 2 <= ks <= PQ_MAX_WORDS:
+        raise ValueError("Ks = %d codewords per book, a PQ index takes 2 .. %d (one byte per book)" % (ks, PQ_MAX_WORDS))
+    if L < 1 or m * L > PQ_MAX_DIM:
+        raise ValueError("d = M * L = %d, a PQ index takes 1 .. %d" % (m * L, PQ_MAX_DIM))
+    if not np.isfinite(cb).all():
+        raise ValueError("codebooks must be finite")
+    return cb
+
+
+def pq_code_rows(codes, m, ks):
+    """uint8 [rows, m] code rows from any integer array with values in [0, ks) (row stride kept when the array is uint8 with
+    contiguous rows).  Raises ValueError on another dtype, shape or a value outside [0, ks)."""
+    a = np.asarray(codes)
+    if a.ndim != 2 or a.shape[1] != m:
+        raise ValueError("codes must be [rows, M = %d] (got shape %s)" % (m, a.shape))
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("codes must be an integer array of codeword indices (got %s)" % a.dtype)
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= ks):
+        raise ValueError("codes must lie in [0, Ks = %d)" % ks)
+    if a.dtype != np.uint8:
+        a = a.astype(np.uint8)
+    if a.shape[1] > 1 and a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a, max(int(a.strides[0]), a.shape[1])
+
+
+class PQIndex:
+    """PQ index on one MI355X (a `mi_pq` handle): exact ADC top-k on product-quantized codes by (distance asc, id asc)."""
+
+    def __init__(self, handle):
+        self._h = C.c_void_p(handle)
+        self._lock = threading.Lock()
+        n, cap, off, hb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        d, m, ks, dev = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(load().mi_pq_info(self._h, n, d, m, ks, dev, off, cap, hb))
+        self.n, self.d, self.m, self.ks, self.device = n.value, d.value, m.value, ks.value, dev.value
+        self.row_offset, self.capacity = off.value, cap.value
+
+    @classmethod
+    def _create(cls, cb, ptr, n, stride, memspace, device, row_offset, capacity):
+        m, ks, L = cb.shape
+        h = C.c_void_p()
+        check(load().mi_pq_create(C.c_void_p(cb.ctypes.data), m * L, m, ks, C.c_void_p(ptr), int(n), int(stride), memspace, device,
+                                  int(row_offset), int(capacity), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_codes(cls, codebooks, codes, device=0, row_offset=0, capacity=0):
+        """codebooks [M, Ks, L] float32, codes integer [N, M] with values in [0, Ks); capacity 0 = N, larger leaves room for
+        append_codes() / add()."""
+        cb = pq_codebooks(codebooks)
+        a, stride = pq_code_rows(codes, cb.shape[0], cb.shape[1])
+        if capacity and capacity < a.shape[0]:
+            raise ValueError("capacity %d below the %d rows given" % (capacity, a.shape[0]))
+        return cls._create(cb, a.ctypes.data, a.shape[0], stride, MI_HOST, device, row_offset, capacity)
+
+    @classmethod
+    def from_device_ptr(cls, codebooks, ptr, n, device=0, row_offset=0, capacity=0, row_stride_bytes=None):
+        """Device codes [n][M] uint8 -> index, synchronous; the producer of `ptr` must have completed."""
+        cb = pq_codebooks(codebooks)
+        return cls._create(cb, ptr, n, cb.shape[0] if row_stride_bytes is None else row_stride_bytes, MI_DEVICE, device, row_offset,
+                           capacity)
+
+    @classmethod
+    def empty(cls, codebooks, capacity, device=0, row_offset=0):
+        """Appendable index: `capacity` rows allocated, filled by append_codes() / add()."""
+        cb = pq_codebooks(codebooks)
+        if int(capacity) < 1:
+            raise ValueError("an empty index needs a capacity")
+        return cls._create(cb, None, 0, cb.shape[0], MI_HOST, device, row_offset, capacity)
+
+    @property
+    def hbm_bytes(self):
+        hb = C.c_int64()
+        check(load().mi_pq_info(self._h, None, None, None, None, None, None, None, hb))
+        return hb.value
+
+    @property
+    def codebooks(self):
+        out = np.empty((self.m, self.ks, self.d // self.m), dtype=np.float32)
+        check(load().mi_pq_get_codebooks(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def _rows(self, x):
+        a, code, rs, cs = _strided(x)
+        if a.shape[1] != self.d:
+            raise ValueError("rows of %d columns, the index takes %d" % (a.shape[1], self.d))
+        return a, code, rs, cs
+
+    def append_codes(self, codes):
+        a, stride = pq_code_rows(codes, self.m, self.ks)
+        with self._lock:
+            check(load().mi_pq_append_codes(self._h, C.c_void_p(a.ctypes.data), a.shape[0], stride, MI_HOST))
+            self.n += a.shape[0]
+
+    def add(self, x):
+        """Encodes rows [rows, d] float32/float64 (any strides) on the device and appends their codes."""
+        a, code, rs, cs = self._rows(x)
+        with self._lock:
+            check(load().mi_pq_add(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST))
+            self.n += a.shape[0]
+
+    def add_device(self, x_ptr, rows, dtype=MI_F32, row_stride=None, col_stride=1):
+        with self._lock:
+            check(load().mi_pq_add(self._h, C.c_void_p(x_ptr), int(rows), dtype, self.d if row_stride is None else int(row_stride),
+                                   int(col_stride), MI_DEVICE))
+            self.n += int(rows)
+
+    def encode(self, x):
+        """-> codes uint8 [rows, M]: per book the codeword nearest in float64, ties to the lower index.  The index is unchanged."""
+        a, code, rs, cs = self._rows(x)
+        out = np.empty((a.shape[0], self.m), dtype=np.uint8)
+        with self._lock:
+            check(load().mi_pq_encode(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST,
+                                      out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def dtable(self, q):
+        """-> float32 [Q, M, Ks]: squared distances of the queries' sub-vectors to every codeword (nanopq's dtable)."""
+        a, code, rs, cs = self._rows(q)
+        out = np.empty((a.shape[0], self.m, self.ks), dtype=np.float32)
+        with self._lock:
+            check(load().mi_pq_dtable(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def search(self, q, k, allow=None, allow_ptr=None):
+        """-> (ids int64 [Q,k], dist float32 [Q,k], seconds), ordered by (distance asc, id asc).  allow: anything allow_bitmap
+        takes (bool mask, global ids, AllowBits words); allow_ptr: a device bitmap of ceil(n / 64) uint64 words.  Fewer than k
+        admitted rows: trailing ids -1, distances +inf."""
+        a, code, rs, cs = self._rows(q)
+        nq, k = a.shape[0], int(k)
+        if allow is not None and allow_ptr is not None:
+            raise ValueError("give at most one of allow and allow_ptr")
+        bits, bits_p, memspace = None, None, MI_HOST
+        if allow is not None:
+            bits = allow_bitmap(allow, self.n, self.row_offset)
+            if bits.size == 0:
+                bits = np.zeros(1, "<u8")
+            bits_p = C.c_void_p(bits.ctypes.data)
+        elif allow_ptr is not None:
+            bits_p, memspace = C.c_void_p(int(allow_ptr)), MI_DEVICE
+        idx = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float32)
+        secs = C.c_double()
+        with self._lock:
+            check(load().mi_pq_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, bits_p, memspace,
+                                      idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p), C.byref(secs)))
+        return idx, dist, secs.value
+
+    def search_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, allow_ptr=None, stream=None):
+        """q_ptr: packed float32 [nq][d] on the device; enqueued on `stream`, no synchronisation."""
+        check(load().mi_pq_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(allow_ptr), C.c_void_p(idx_ptr),
+                                         C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def get_codes(self, row0=0, nrows=None):
+        nrows = self.n - row0 if nrows is None else int(nrows)
+        out = np.empty((nrows, self.m), dtype=np.uint8)
+        with self._lock:
+            check(load().mi_pq_get_codes(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            check(load().mi_pq_destroy(self._h))
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

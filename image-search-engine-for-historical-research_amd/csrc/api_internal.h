@@ -13,6 +13,7 @@
 //   api_l2.hip        squared-L2 metric: L2 galleries (hidden bias columns), top-K by distance (host / device), dense checker
 //   api_remove.hip    row removal in place: keep-list, block-ordered move through a bounded staging area, invalidations
 //   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix
+//   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -64,6 +65,7 @@ extern MI_INTERNAL std::atomic<int> g_keep_buffers;
 extern MI_INTERNAL std::atomic<int64_t> g_scatter_block_rows;   // mi_scatter_matrix: rows per host block (0 = 64 MiB)
 extern MI_INTERNAL std::atomic<int64_t> g_remove_block_rows;    // mi_gallery_remove_rows: rows of the staging area (0 = default)
 extern MI_INTERNAL std::atomic<int64_t> g_hamming_matrix_bytes; // mi_hamming_search*: bytes of the distance matrix (default 2 GiB)
+extern MI_INTERNAL std::atomic<int64_t> g_pq_matrix_bytes;      // mi_pq_search*: bytes of the distance matrix (default 2 GiB)
 constexpr size_t SPARE_MAX_BYTES = (size_t)16 << 30;
 MI_INTERNAL void spare_release_locked();
 MI_INTERNAL void spare_ws_release_locked();

@@ -31,6 +31,10 @@ std::atomic<int64_t> g_remove_block_rows{0};
 // a batch goes through it in chunks of queries, one query at the least
 constexpr int64_t HAMMING_MATRIX_DEFAULT = (int64_t)2 << 30;
 std::atomic<int64_t> g_hamming_matrix_bytes{HAMMING_MATRIX_DEFAULT};
+// mi_set_global_option("pq_matrix_bytes", ...): the same limit for the float32 distance matrix of a PQ index (api_pq.hip); a batch
+// goes through it in chunks of whole query tiles, four queries at the least
+constexpr int64_t PQ_MATRIX_DEFAULT = (int64_t)2 << 30;
+std::atomic<int64_t> g_pq_matrix_bytes{PQ_MATRIX_DEFAULT};
 void spare_release_locked() {
   if (g_spare.device < 0) return;
   int cur = 0;
@@ -254,6 +258,10 @@ int mi_set_global_option(const char* name, double value) {
     REQUIRE(value >= 0 && value <= 1e13, "hamming_matrix_bytes: bytes of the distance matrix of a binary index (0 = default, 2 GiB)");
     g_hamming_matrix_bytes = value == 0 ? HAMMING_MATRIX_DEFAULT : (int64_t)value;
   }
+  else if (n == "pq_matrix_bytes") {
+    REQUIRE(value >= 0 && value <= 1e13, "pq_matrix_bytes: bytes of the distance matrix of a PQ index (0 = default, 2 GiB)");
+    g_pq_matrix_bytes = value == 0 ? PQ_MATRIX_DEFAULT : (int64_t)value;
+  }
   else if (n == "release_spares") {
     // gives the spare slots back NOW and leaves the mode alone (a caller that is done with its galleries for a while --
     // nnsearch.drop_cached_galleries -- or a co-tenant that needs the memory)
@@ -274,6 +282,7 @@ int mi_get_global_option(const char* name, double* out_value) {
   else if (n == "scatter_block_rows") *out_value = (double)g_scatter_block_rows.load();
   else if (n == "remove_block_rows") *out_value = (double)g_remove_block_rows.load();
   else if (n == "hamming_matrix_bytes") *out_value = (double)g_hamming_matrix_bytes.load();
+  else if (n == "pq_matrix_bytes") *out_value = (double)g_pq_matrix_bytes.load();
   else if (n == "spare_bytes") {
     // device memory this process holds in the spare slots right now (gallery buffers + search workspace of destroyed handles)
     std::lock_guard<std::mutex> lock(g_spare_mu);

@@ -289,6 +289,22 @@ void launch_hamming_select(const uint16_t* dist, int64_t n, int32_t nbits, int32
 void launch_hamming_sign(const float* x, int64_t n, int32_t d, int64_t rs, uint8_t* out_bytes, int64_t out_rs, uint32_t* codes,
                          int64_t row0, hipStream_t stream);
 
+// pq.hip -- exact ADC top-K on product-quantized codes (api_pq.hip): codebooks [M][Ks][L] f32, gallery blocks of 64 rows with the
+// code bytes four books to a dword and the dwords transposed, codes[block][w < ceil(M / 4)][64]; distance tables [nq][M][Ks] f32;
+// a float32 matrix [nq][round_up(n, 64)] of NEGATED distances (NaN = row not admitted) for launch_dense_topk
+void launch_pq_check(const uint8_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream);
+void launch_pq_ingest(const uint8_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream);
+void launch_pq_table(const void* x, int dtype, int64_t rs, int64_t cs, int64_t nq, const float* cb, int32_t M, int32_t Ks, int32_t L,
+                     float* tab, hipStream_t stream);
+// packed code bytes out [n][M]
+void launch_pq_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* cb, int32_t M, int32_t Ks, int32_t L,
+                      uint8_t* out, hipStream_t stream);
+int32_t pq_query_tile(int32_t M, int32_t Ks, int64_t nq);      // queries per workgroup of the scan (1, 2 or 4): the LDS budget
+void launch_pq_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, const float* tab, int32_t nq, int32_t qt,
+                    const uint64_t* allow, float* mat, hipStream_t stream);
+void launch_pq_emit(const int64_t* tidx, const float* tneg, int64_t nq, int32_t ke, int32_t k, int64_t row_offset, int64_t* out_idx,
+                    float* out_dist, hipStream_t stream);
+
 // synth.hip
 void launch_synth_fill(float* dst, uint64_t seed, int64_t row0, int64_t nrows, int32_t d, hipStream_t stream);
 

@@ -1,0 +1,331 @@
+// Exact ADC top-K on product-quantized codes (api_pq.hip): the reference's matching_PQ_Net
+// (src/utils/nnsearch.py:905-946), nanopq's dtable(query).adist(codes), faiss IndexPQ.search.
+//
+// M books of Ks <= 256 codewords of L floats (codebooks [M][Ks][L] f32), a code is M bytes.  Gallery layout: blocks of 64 rows,
+// four books to a dword, dwords transposed: codes[block][w][lane], w < MQ = ceil(M / 4), byte (m & 3) of dword (m >> 2) is the
+// row's code in book m; the bytes of the books M .. 4 MQ - 1 are zero.  Lane l of a wave owns row 64 * block + l, one book-quad
+// of the 64 rows is one coalesced 256-byte read.
+//
+//   pq_sqdist         THE arithmetic: sum_j (double(x_j) - double(c_j))^2 in float64, ascending j, a separate multiply and add
+//                     per term (no contraction).  The table rounds it once to float32, the encoder takes its argmin
+//   pq_table_kernel   T[q][m][c] = (float)pq_sqdist(x[q][m L ..], C[m][c]), thread = (q, m, c)
+//   pq_encode_kernel  code[i][m] = argmin_c pq_sqdist(x[i][m L ..], C[m][c]), ties to the lower c.  A workgroup takes 64 rows of
+//                     one book; row and codeword slices pass through LDS as float64, 8 accumulators per thread
+//   pq_scan_kernel    the hot path: a workgroup loads the tables of a tile of QT queries into LDS interleaved query-fastest,
+//                     T[m][c][QT], and walks a slab of row blocks; per (row, book) ONE LDS read of 4 QT bytes at the
+//                     data-dependent address (m Ks + code) returns the entry of every query of the tile.  dist = T[0][code_0] +
+//                     T[1][code_1] + ... in float32, ascending book order.  The NEGATED distance goes to a matrix
+//                     [queries][npad]; rows not admitted (beyond n, or cleared in the allow bitmap) get NaN, which
+//                     launch_dense_topk (dense.hip) orders below every number, -inf included
+//   pq_emit_kernel    its (-distance desc, id asc) lists -> (distance asc, id asc) outputs, -1 / +inf where the list ran out of
+//                     admitted rows
+#include <algorithm>
+
+#include "kernels.h"
+
+namespace mi {
+
+// ---- the one place the squared distance of a sub-vector is computed.  fp contraction is off: hipcc would otherwise fuse d * d + acc
+template <typename FX, typename FC>
+__device__ __forceinline__ double pq_sqdist(FX x, FC c, int32_t L) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+  for (int32_t j = 0; j < L; ++j) {
+    const double d = x(j) - c(j);
+    const double p = d * d;
+    acc = acc + p;
+  }
+  return acc;
+}
+
+// one more term of the same chain (the encoder walks j in slices)
+__device__ __forceinline__ double pq_sqdist_step(double acc, double x, double c) {
+#pragma clang fp contract(off)
+  const double d = x - c;
+  const double p = d * d;
+  return acc + p;
+}
+
+// ---- code bytes >= ks raise the flag (device-resident codes; host codes are checked on the host)
+__global__ __launch_bounds__(256) void pq_check_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t M, int32_t ks, int64_t m,
+                                                      uint32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= m * M) return;
+  const int64_t r = i / M;
+  const int32_t b = (int32_t)(i % M);
+  if ((int32_t)src[r * stride + b] >= ks) *flag = 1u;
+}
+
+// ---- code bytes [m][stride] -> dwords of rows row0 .. row0 + m of the transposed layout (thread = (dword, row), rows fastest)
+__global__ __launch_bounds__(256) void pq_ingest_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t M, int32_t MQ, int64_t row0,
+                                                       int64_t m, uint32_t* __restrict__ codes) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= m * MQ) return;
+  const int64_t r = i % m;
+  const int32_t w = (int32_t)(i / m);
+  const uint8_t* p = src + r * stride;
+  uint32_t v = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+    if (4 * w + b < M) v |= (uint32_t)p[4 * w + b] << (8 * b);
+  const int64_t row = row0 + r;
+  codes[((row >> 6) * MQ + w) * 64 + (row & 63)] = v;
+}
+
+// ---- table
+template <typename InT>
+__global__ __launch_bounds__(256) void pq_table_kernel(const InT* __restrict__ x, int64_t rs, int64_t cs, int64_t nq,
+                                                      const float* __restrict__ cb, int32_t M, int32_t Ks, int32_t L,
+                                                      float* __restrict__ tab) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nq * M * Ks) return;
+  const int32_t c = (int32_t)(i % Ks);
+  const int32_t m = (int32_t)((i / Ks) % M);
+  const int64_t q = i / ((int64_t)Ks * M);
+  const InT* xr = x + q * rs + (int64_t)m * L * cs;
+  const float* cw = cb + ((int64_t)m * Ks + c) * L;
+  tab[i] = (float)pq_sqdist([&](int32_t j) { return (double)xr[(int64_t)j * cs]; }, [&](int32_t j) { return (double)cw[j]; }, L);
+}
+
+// ---- encoder.  Workgroup = 64 rows x one book; thread t: row t & 63, codeword group t >> 6 (one wave each).  The codewords
+// pass in tiles of PE_CT = 32 (8 per thread), the columns in slices of PE_JT = 64; xs[j][row] and cs[c][j] are float64 in LDS
+// (xs: consecutive lanes, consecutive addresses; cs: one address per wave, a broadcast).
+constexpr int PE_ROWS = 64, PE_CT = 32, PE_JT = 64, PE_PER = PE_CT / 4;
+
+template <typename InT>
+__global__ __launch_bounds__(256) void pq_encode_kernel(const InT* __restrict__ x, int64_t rs, int64_t cs, int64_t n,
+                                                       const float* __restrict__ cb, int32_t M, int32_t Ks, int32_t L,
+                                                       uint8_t* __restrict__ out) {
+  __shared__ double xs[PE_JT][PE_ROWS];
+  __shared__ double cw[PE_CT][PE_JT + 1];
+  __shared__ double bd[4][PE_ROWS];
+  __shared__ int32_t bc[4][PE_ROWS];
+  const int tid = threadIdx.x, r = tid & 63, cg = tid >> 6;
+  const int64_t row0 = (int64_t)blockIdx.x * PE_ROWS;
+  const int32_t m = (int32_t)blockIdx.y;
+  double best = __builtin_inf();
+  int32_t best_c = 0;
+  for (int32_t c0 = 0; c0 < Ks; c0 += PE_CT) {
+    double acc[PE_PER];
+#pragma unroll
+    for (int e = 0; e < PE_PER; ++e) acc[e] = 0.0;
+    for (int32_t j0 = 0; j0 < L; j0 += PE_JT) {
+      const int32_t jn = min(PE_JT, L - j0);
+      __syncthreads();
+      for (int i = tid; i < PE_ROWS * PE_JT; i += 256) {          // consecutive threads, consecutive columns of one row
+        const int j = i % PE_JT, rr = i / PE_JT;
+        const int64_t row = row0 + rr;
+        xs[j][rr] = (j < jn && row < n) ? (double)x[row * rs + ((int64_t)m * L + j0 + j) * cs] : 0.0;
+      }
+      for (int i = tid; i < PE_CT * PE_JT; i += 256) {
+        const int j = i % PE_JT, cc = i / PE_JT;
+        cw[cc][j] = (j < jn && c0 + cc < Ks) ? (double)cb[((int64_t)m * Ks + c0 + cc) * L + j0 + j] : 0.0;
+      }
+      __syncthreads();
+      for (int32_t j = 0; j < jn; ++j) {
+        const double xv = xs[j][r];
+#pragma unroll
+        for (int e = 0; e < PE_PER; ++e) acc[e] = pq_sqdist_step(acc[e], xv, cw[cg * PE_PER + e][j]);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < PE_PER; ++e) {
+      const int32_t c = c0 + cg * PE_PER + e;
+      if (c < Ks && acc[e] < best) {                              // ascending c, strict: ties stay with the lower c
+        best = acc[e];
+        best_c = c;
+      }
+    }
+  }
+  bd[cg][r] = best;
+  bc[cg][r] = best_c;
+  __syncthreads();
+  if (tid < PE_ROWS && row0 + tid < n) {
+    double b = bd[0][tid];
+    int32_t c = bc[0][tid];
+#pragma unroll
+    for (int g = 1; g < 4; ++g) {
+      const double v = bd[g][tid];
+      const int32_t vc = bc[g][tid];
+      if (v < b || (v == b && vc < c)) {
+        b = v;
+        c = vc;
+      }
+    }
+    out[(row0 + tid) * M + m] = (uint8_t)c;
+  }
+}
+
+// ---- scan
+constexpr int PS_THREADS = 512, PS_WAVES = PS_THREADS / 64;
+constexpr int PS_LDS_BUDGET = 128 * 1024;
+
+template <int QT> struct PqVec;
+template <> struct PqVec<1> { using type = float; };
+template <> struct PqVec<2> { using type = float2; };
+template <> struct PqVec<4> { using type = float4; };
+
+template <int QT>
+__device__ __forceinline__ void pq_acc(float (&acc)[QT], const typename PqVec<QT>::type v);
+template <> __device__ __forceinline__ void pq_acc<1>(float (&acc)[1], const float v) { acc[0] = acc[0] + v; }
+template <> __device__ __forceinline__ void pq_acc<2>(float (&acc)[2], const float2 v) {
+  acc[0] = acc[0] + v.x;
+  acc[1] = acc[1] + v.y;
+}
+template <> __device__ __forceinline__ void pq_acc<4>(float (&acc)[4], const float4 v) {
+  acc[0] = acc[0] + v.x;
+  acc[1] = acc[1] + v.y;
+  acc[2] = acc[2] + v.z;
+  acc[3] = acc[3] + v.w;
+}
+
+// grid = (query tiles, slabs).  tab: [nq][M][Ks] f32.  The LDS image holds 4 MQ books: the entries of the books M .. 4 MQ - 1
+// are +0.0 and the code bytes of those books are 0, so a whole dword of codes is walked without a branch and the extra adds
+// change nothing (the running sum is never -0.0: it starts at +0.0 and takes non-negative terms).
+template <int QT>
+__global__ __launch_bounds__(PS_THREADS) void pq_scan_kernel(const uint32_t* __restrict__ codes, int32_t M, int32_t MQ, int32_t Ks,
+                                                            int64_t nblk, int64_t blk_per, int64_t n, const float* __restrict__ tab,
+                                                            int32_t nq, const uint64_t* __restrict__ allow, float* __restrict__ mat,
+                                                            int64_t npad) {
+  extern __shared__ __attribute__((aligned(16))) char pq_smem[];
+  using Vec = typename PqVec<QT>::type;
+  float* tl = reinterpret_cast<float*>(pq_smem);
+  const int32_t q0 = (int32_t)blockIdx.x * QT;
+  const int32_t ent = 4 * MQ * Ks, real = M * Ks;
+  for (int32_t i = threadIdx.x; i < ent * QT; i += PS_THREADS) {     // consecutive threads, consecutive entries of one query
+    const int32_t t = i / ent, e = i - t * ent;
+    tl[e * QT + t] = (e < real && q0 + t < nq) ? tab[((int64_t)(q0 + t) * M) * Ks + e] : 0.0f;
+  }
+  __syncthreads();
+  const Vec* tv = reinterpret_cast<const Vec*>(pq_smem);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t b0 = (int64_t)blockIdx.y * blk_per, b1 = min(nblk, b0 + blk_per);
+  for (int64_t b = b0 + wave; b < b1; b += PS_WAVES) {               // wave-uniform
+    const uint32_t* src = codes + b * MQ * 64 + lane;
+    float acc[QT];
+#pragma unroll
+    for (int t = 0; t < QT; ++t) acc[t] = 0.0f;
+#pragma unroll 4
+    for (int32_t w = 0; w < MQ; ++w) {
+      const uint32_t g = src[(int64_t)w * 64];
+      const int32_t base = 4 * w * Ks;
+      pq_acc<QT>(acc, tv[base + (int32_t)(g & 255u)]);
+      pq_acc<QT>(acc, tv[base + Ks + (int32_t)((g >> 8) & 255u)]);
+      pq_acc<QT>(acc, tv[base + 2 * Ks + (int32_t)((g >> 16) & 255u)]);
+      pq_acc<QT>(acc, tv[base + 3 * Ks + (int32_t)(g >> 24)]);
+    }
+    const int64_t row = b * 64 + lane;
+    bool ok = row < n;
+    if (allow) ok = ok && ((allow[b] >> lane) & 1ull);
+#pragma unroll
+    for (int t = 0; t < QT; ++t)
+      if (q0 + t < nq) mat[(int64_t)(q0 + t) * npad + row] = ok ? -acc[t] : __builtin_nanf("");
+  }
+}
+
+// ---- emit: lists of launch_dense_topk over the negated matrix -> the caller's outputs
+__global__ __launch_bounds__(256) void pq_emit_kernel(const int64_t* __restrict__ tidx, const float* __restrict__ tneg, int64_t nq,
+                                                     int32_t ke, int32_t k, int64_t row_offset, int64_t* __restrict__ out_idx,
+                                                     float* __restrict__ out_dist) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nq * k) return;
+  const int64_t q = i / k;
+  const int32_t j = (int32_t)(i % k);
+  int64_t id = -1;
+  float dist = __builtin_inff();
+  if (j < ke) {
+    const float s = tneg[q * ke + j];
+    if (s == s) {
+      id = row_offset + tidx[q * ke + j];
+      dist = -s;
+    }
+  }
+  out_idx[i] = id;
+  if (out_dist) out_dist[i] = dist;
+}
+
+// ---- launchers
+constexpr int64_t PQ_STEP = (int64_t)1 << 22;                 // rows per launch of the element-wise kernels: grids stay below 2^31
+
+void launch_pq_check(const uint8_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream) {
+  for (int64_t r = 0; r < m; r += PQ_STEP) {
+    const int64_t mm = std::min(PQ_STEP, m - r);
+    pq_check_kernel<<<dim3((unsigned)((mm * M + 255) / 256)), 256, 0, stream>>>(src + r * stride, stride, M, ks, mm, flag);
+  }
+}
+
+void launch_pq_ingest(const uint8_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream) {
+  const int32_t MQ = (M + 3) / 4;
+  for (int64_t r = 0; r < m; r += PQ_STEP) {
+    const int64_t mm = std::min(PQ_STEP, m - r);
+    pq_ingest_kernel<<<dim3((unsigned)((mm * MQ + 255) / 256)), 256, 0, stream>>>(src + r * stride, stride, M, MQ, row0 + r, mm, codes);
+  }
+}
+
+void launch_pq_table(const void* x, int dtype, int64_t rs, int64_t cs, int64_t nq, const float* cb, int32_t M, int32_t Ks, int32_t L,
+                     float* tab, hipStream_t stream) {
+  const int64_t per = (int64_t)M * Ks;
+  const int64_t step = std::max<int64_t>(1, ((int64_t)1 << 30) / per);       // queries per launch
+  for (int64_t q = 0; q < nq; q += step) {
+    const int64_t b = std::min(step, nq - q);
+    const dim3 grid((unsigned)((b * per + 255) / 256));
+    if (dtype == 0)
+      pq_table_kernel<float><<<grid, 256, 0, stream>>>((const float*)x + q * rs, rs, cs, b, cb, M, Ks, L, tab + q * per);
+    else
+      pq_table_kernel<double><<<grid, 256, 0, stream>>>((const double*)x + q * rs, rs, cs, b, cb, M, Ks, L, tab + q * per);
+  }
+}
+
+void launch_pq_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* cb, int32_t M, int32_t Ks, int32_t L,
+                      uint8_t* out, hipStream_t stream) {
+  for (int64_t r = 0; r < n; r += PQ_STEP) {
+    const int64_t mm = std::min(PQ_STEP, n - r);
+    const dim3 grid((unsigned)((mm + PE_ROWS - 1) / PE_ROWS), (unsigned)M);
+    if (dtype == 0)
+      pq_encode_kernel<float><<<grid, 256, 0, stream>>>((const float*)x + r * rs, rs, cs, mm, cb, M, Ks, L, out + r * M);
+    else
+      pq_encode_kernel<double><<<grid, 256, 0, stream>>>((const double*)x + r * rs, rs, cs, mm, cb, M, Ks, L, out + r * M);
+  }
+}
+
+int32_t pq_query_tile(int32_t M, int32_t Ks, int64_t nq) {
+  const int64_t one = (int64_t)4 * ((M + 3) / 4) * Ks * 4;    // bytes of one query's LDS image
+  if (nq >= 3 && 4 * one <= PS_LDS_BUDGET) return 4;
+  if (nq >= 2 && 2 * one <= PS_LDS_BUDGET) return 2;
+  return 1;
+}
+
+template <int QT>
+static void scan_launch(hipStream_t s, const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, const float* tab, int32_t nq,
+                        const uint64_t* allow, float* mat) {
+  const int32_t MQ = (M + 3) / 4;
+  const int64_t nblk = (n + 63) / 64, npad = nblk * 64;
+  const int lds = 4 * MQ * Ks * 4 * QT;
+  ensure_dynamic_lds((const void*)pq_scan_kernel<QT>);
+  // slabs: enough workgroups to fill the device (256 CUs, one or two workgroups each), but no slab below PS_WAVES blocks
+  const int64_t tiles = (nq + QT - 1) / QT;
+  int64_t slabs = std::min<int64_t>({(1024 + tiles - 1) / tiles, (nblk + PS_WAVES - 1) / PS_WAVES, 65535});
+  slabs = std::max<int64_t>(slabs, 1);
+  const int64_t blk_per = (nblk + slabs - 1) / slabs;
+  slabs = (nblk + blk_per - 1) / blk_per;
+  pq_scan_kernel<QT><<<dim3((unsigned)tiles, (unsigned)slabs), PS_THREADS, lds, s>>>(codes, M, MQ, Ks, nblk, blk_per, n, tab, nq, allow,
+                                                                                    mat, npad);
+}
+
+void launch_pq_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, const float* tab, int32_t nq, int32_t qt,
+                    const uint64_t* allow, float* mat, hipStream_t stream) {
+  if (n <= 0 || nq <= 0) return;
+  switch (qt) {
+    case 4: scan_launch<4>(stream, codes, M, Ks, n, tab, nq, allow, mat); break;
+    case 2: scan_launch<2>(stream, codes, M, Ks, n, tab, nq, allow, mat); break;
+    default: scan_launch<1>(stream, codes, M, Ks, n, tab, nq, allow, mat); break;
+  }
+}
+
+void launch_pq_emit(const int64_t* tidx, const float* tneg, int64_t nq, int32_t ke, int32_t k, int64_t row_offset, int64_t* out_idx,
+                    float* out_dist, hipStream_t stream) {
+  if (nq <= 0) return;
+  pq_emit_kernel<<<dim3((unsigned)((nq * k + 255) / 256)), 256, 0, stream>>>(tidx, tneg, nq, ke, k, row_offset, out_idx, out_dist);
+}
+
+}  // namespace mi

@@ -256,6 +256,43 @@ def matching_Greedyhash_hip(K, hash_codes_train, hash_codes_test):
     return idx, (time.time() - t1) / num_test
 
 
+def matching_PQ_Net_hip(K, Codewords, Query, N_books, CW_idx):
+    """Same signature and return shape as matching_PQ_Net (src/utils/nnsearch.py:905-946): asymmetric-distance top-K of queries
+    [Q, dim] against N_books-byte PQ codes CW_idx [N, N_books] under Codewords [N_words, dim] (book j is the column block
+    j * L .. (j + 1) * L, L = dim / N_books) -> (idx int64 [Q, K], time_per_query).  The reference sorts float32 sums of a
+    float32 table with an unstable argsort; here a table entry is the float64 sum of squares rounded once to float32, a
+    distance is the float32 sum of a row's entries in book order, and rows at equal distance come by ascending index
+    (include/mi355_retrieval.h, PQ index).  N_words <= 256 (one byte per book), dim % N_books == 0, 1 <= K <= min(N, 2048);
+    CW_idx must be an integer array with values in [0, N_words).  Bad input raises ValueError before the device is touched.  It
+    is no (K, train, test) matcher and therefore not in MATCHING_METHODS.  The timer spans what the reference's spans:
+    everything the call does (index build, tables and search), device-synchronised."""
+    t1 = time.time()
+    cw, q, codes = np.asarray(Codewords), np.asarray(Query), np.asarray(CW_idx)
+    if cw.ndim != 2 or q.ndim != 2 or codes.ndim != 2 or q.shape[1] != cw.shape[1]:
+        raise ValueError("expected Codewords [N_words, dim], Query [Q, dim] and CW_idx [N, N_books], got %s, %s and %s"
+                         % (cw.shape, q.shape, codes.shape))
+    N_books, K = int(N_books), int(K)
+    n_words, dim = cw.shape
+    if N_books < 1 or dim % N_books:
+        raise ValueError("dim = %d is no multiple of N_books = %d" % (dim, N_books))
+    if codes.shape[1] != N_books:
+        raise ValueError("CW_idx has %d columns, N_books = %d" % (codes.shape[1], N_books))
+    if n_words > _lib.PQ_MAX_WORDS:
+        raise ValueError("N_words = %d, a code byte holds at most %d codewords per book" % (n_words, _lib.PQ_MAX_WORDS))
+    num_train, num_test = codes.shape[0], q.shape[0]
+    if K < 1 or K > num_train:
+        raise ValueError("K = %d, the database holds %d codes" % (K, num_train))
+    if K > TOPK_PATH_MAX_K:
+        raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
+    if not (np.issubdtype(q.dtype, np.floating) and np.isfinite(q).all()):
+        raise ValueError("Query must be a finite floating-point array")
+    # [N_words, N_books * L] -> [N_books, N_words, L]
+    books = cw.reshape(n_words, N_books, dim // N_books).transpose(1, 0, 2)
+    with _lib.PQIndex.from_codes(books, codes) as g:              # (raises ValueError on non-integer or out-of-range codes)
+        idx, _, _ = g.search(q, K)
+    return idx, (time.time() - t1) / max(num_test, 1)
+
+
 # the matchers of this build by the name the reference's entry points dispatch on (--matching_method, src/offline.py:107-118)
 MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip}
 

@@ -235,6 +235,57 @@ int mi_hamming_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, in
                              int64_t* out_idx_dev, int32_t* out_dist_dev, void* stream);
 int mi_hamming_destroy(mi_hamming* h); /* NULL is MI_OK */
 
+/* ---- PQ index: exact ADC top-K on product-quantized codes.  The reference's matching_PQ_Net(K, Codewords, Query, N_books,
+ * CW_idx) (src/utils/nnsearch.py:905-946), nanopq's pq.dtable(query).adist(codes), faiss IndexPQ.search.  DESIGN.md 5.14.
+ * m books (1 <= m <= 64) of ks codewords (2 <= ks <= 256) of L = d / m floats, d <= 4096; a code is m bytes, byte j the
+ * codeword of book j.  Codebooks are float32 [m][ks][L] in C order (nanopq's pq.codewords, faiss's ProductQuantizer.centroids)
+ * and must be finite.  Given codebooks and codes the search is exhaustive and its answer is fully determined:
+ *   table     T[q][j][c] = (float) sum_{i < L} (double(x[q][j L + i]) - double(C[j][c][i]))^2, the sum in float64 in ascending i,
+ *             a separate multiply and add per term (nothing fused), rounded once to float32
+ *   distance  dist[q][r] = T[q][0][code[r][0]] + T[q][1][code[r][1]] + ... in float32, added in ascending book order
+ *   order     (distance asc, id asc), ids row_offset + local row; +inf (a table entry beyond float32) is an ordinary value
+ *   encoding  code[r][j] = argmin_c of the float64 sum above (before the rounding), ties to the lower c
+ * No certificate, no flag, no fallback path.  The handle is a type of its own, ONE row shard on ONE device; none of the mi_gallery
+ * entry points takes it.  Out of scope: learning codebooks, ks > 256, row removal, save / load, sharding, IVF, re-ranking.
+ * mi_pq_create: n rows of `codes` (row i at codes + i * row_stride_bytes; MI_HOST or MI_DEVICE, device rows complete when the
+ * call is made) into an index of `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty appendable
+ * index.  A code byte >= ks is MI_ERR_INVALID (host codes are checked before a device is touched).  Synchronous. */
+typedef struct mi_pq mi_pq; /* opaque */
+int mi_pq_create(const float* codebooks_host, int32_t d, int32_t m, int32_t ks, const void* codes, int64_t n,
+                 int64_t row_stride_bytes, int memspace, int device, int64_t row_offset, int64_t capacity, mi_pq** out);
+/* rows more codes, synchronous.  Beyond the capacity, or a code byte >= ks: MI_ERR_INVALID, and the index stays as it was. */
+int mi_pq_append_codes(mi_pq* h, const void* codes, int64_t rows, int64_t row_stride_bytes, int memspace);
+/* Encodes rows x [rows][d] (MI_F32 or MI_F64; element (i, j) at x + i * row_stride + j * col_stride elements; MI_HOST or
+ * MI_DEVICE) on the device and appends the codes.  Synchronous; the same capacity rule. */
+int mi_pq_add(mi_pq* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace);
+/* The same encoding stand-alone: out_codes_host [rows][m] bytes; the index is unchanged. */
+int mi_pq_encode(mi_pq* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace,
+                 uint8_t* out_codes_host);
+/* nanopq's dtable: the tables of nq host queries, out_table_host [nq][m][ks] float32.  Non-finite queries: MI_ERR_INVALID. */
+int mi_pq_dtable(mi_pq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, float* out_table_host);
+/* Host in, host out, synchronous.  Queries as for mi_knn_search_l2 (any strides); non-finite queries are MI_ERR_INVALID.
+ * 1 <= k <= 2048.  out_idx [nq][k] int64, out_dist [nq][k] float32 (may be NULL).  allow_bits NULL: every row; otherwise the
+ * bitmap of mi_hamming_search, one for every query.  Fewer than k admitted rows: trailing ids -1, distances +inf.  nq == 0 is
+ * MI_OK.  out_seconds (may be NULL): wall time of the call.  The queries of a call pass through a float32 matrix [queries][n
+ * rounded up to 64] owned by the handle, in chunks that keep it within the global option "pq_matrix_bytes" (default 2 GiB; four
+ * queries at the least); the answer does not depend on the chunking. */
+int mi_pq_search(mi_pq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                 const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_dist, double* out_seconds);
+/* Device-resident variant, enqueued on `stream` without synchronising: q_dev packed [nq][d] float32, allow_bits_dev (may be
+ * NULL) and the outputs are device buffers (out_dist_dev may be NULL).  A non-finite query leaves the order of ITS answer
+ * unspecified (nothing is read or written out of bounds).  Buffers of the handle are used and grown as for
+ * mi_hamming_search_device: calls on one handle must be serialised by the caller and enqueued on ONE stream. */
+int mi_pq_search_device(mi_pq* h, const float* q_dev, int64_t nq, int32_t k, const uint64_t* allow_bits_dev, int64_t* out_idx_dev,
+                        float* out_dist_dev, void* stream);
+/* Any out pointer may be NULL.  hbm_bytes: codes, codebooks and the grow-only buffers the handle holds right now. */
+int mi_pq_info(const mi_pq* h, int64_t* n, int32_t* d, int32_t* m, int32_t* ks, int32_t* device, int64_t* row_offset,
+               int64_t* capacity, int64_t* hbm_bytes);
+/* Rows [row0, row0 + nrows) as given or encoded, m bytes each, to a host buffer. */
+int mi_pq_get_codes(mi_pq* h, int64_t row0, int64_t nrows, uint8_t* out_host);
+/* The codebooks as given, [m][ks][L] float32. */
+int mi_pq_get_codebooks(const mi_pq* h, float* out_host);
+int mi_pq_destroy(mi_pq* h); /* NULL is MI_OK */
+
 /* Device-resident variant: q_dev [nq][d] row-major f32 (C order), outputs are device buffers.
  * out_score64_dev (may be NULL) receives the float64 exact scores. */
 int mi_knn_search_device(mi_gallery* g, const float* q_dev, int64_t nq, int32_t k,
@@ -537,12 +588,13 @@ int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
  * (rounded up to a multiple of 256; 0 = default, 32 768 -- a first choice, not yet taken from a measured sweep).  The call uses
  * fewer rows when fewer move, and gives up whole tiles of 256 rows so that the allocation, as the driver rounds it, stays within
  * B * (6 * d64 + 12) bytes + 4 bytes per surviving row + the bitmap + 1 MiB.
- * "hamming_matrix_bytes": upper limit of the distance matrix of a binary index (mi_hamming_search*; 0 = default, 2 GiB). */
+ * "hamming_matrix_bytes": upper limit of the distance matrix of a binary index (mi_hamming_search*; 0 = default, 2 GiB).
+ * "pq_matrix_bytes": upper limit of the distance matrix of a PQ index (mi_pq_search*; 0 = default, 2 GiB). */
 int mi_set_global_option(const char* name, double value);
 /* "release_spares" (any value) gives the spare slots back now and leaves "keep_buffers" as it is.  An allocation of the library
  * that fails with out-of-memory releases them by itself and is tried once more; a gallery of other sizes than the spare releases
  * it when the device could not hold both.  mi_get_global_option reads "image_dtype", "host_ingest", "keep_buffers", "scatter_block_rows",
- * "remove_block_rows", "hamming_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
+ * "remove_block_rows", "hamming_matrix_bytes", "pq_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
  * extractor's PyTorch allocator) cannot see otherwise. */
 int mi_get_global_option(const char* name, double* out_value);
 

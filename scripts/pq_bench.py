@@ -1,0 +1,169 @@
+#!/usr/bin/env python3
+"""Timing of the PQ index (mi_pq_search_device, mi_pq_add) on one MI355X -> profiles/pq_bench.json.
+
+K = 100, M = 16 books of Ks = 256 codewords, d = 2048 (L = 128); N = 1 005 994 and 10^7 codes generated on the device; 1, 70 and
+1024 Gaussian queries.  Per case: warm-up steps, then `--steps` timed steps between two HIP events (one search_device call each),
+median and spread, beside the roofs the step is compared with:
+
+  lookups   nq * N * M table lookups; one LDS read of 4 QT bytes serves the QT queries of a tile, and a random-address read runs
+            at 32 lanes per clock and CU before bank conflicts (ds_read_b32 / b64; ds_read_b128: 16 lanes), i.e.
+            256 CUs x 2.4 GHz x (32 | 16) x QT lookups / s
+  matrix    the float32 matrix [nq][N] is written once by the scan and read by the selection (11 passes of launch_dense_topk:
+            4 + 4 radix passes, 2 counts, 1 collect), against 8 TB/s -- the selection's passes mostly hit the 4 MB row in L2
+
+The encode case times mi_pq_add of `--encode-rows` device rows (N x Ks x d float64 term-steps of 3 instructions against the
+vector f64 rate 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz / 2).  The "greedyhash-sized" case is the shape of
+scripts/hamming_bench.py (1 005 994 rows of d = 2048, 70 queries) for a side-by-side of queries/s.
+
+Every case runs in a child process of its own under `timeout`; the driver stops at the first case that fails."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "profiles", "pq_bench.json")
+
+CLOCK, CUS = 2.4e9, 256
+HBM_ROOF = 8e12                            # bytes / s
+F64_VALU = CUS * 4 * 16 * CLOCK / 2        # float64 vector instructions / s (half rate)
+M, KS, D, K = 16, 256, 2048, 100
+SELECT_PASSES = 11
+
+
+def device_index(_lib, torch, n):
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    books = torch.randn((M, KS, D // M), dtype=torch.float32, device=dev, generator=gen).cpu().numpy()
+    codes = torch.randint(0, KS, (n, M), dtype=torch.uint8, device=dev, generator=gen)
+    torch.cuda.synchronize()
+    idx = _lib.PQIndex.from_device_ptr(books, codes.data_ptr(), n)
+    del codes
+    torch.cuda.empty_cache()
+    return idx, gen
+
+
+def search_case(_lib, torch, n, nq, steps, warmup):
+    dev = torch.device("cuda", 0)
+    idx, gen = device_index(_lib, torch, n)
+    q = torch.randn((nq, D), dtype=torch.float32, device=dev, generator=gen)
+    out_i = torch.empty((nq, K), dtype=torch.int64, device=dev)
+    out_d = torch.empty((nq, K), dtype=torch.float32, device=dev)
+    s = torch.cuda.current_stream().cuda_stream
+    for _ in range(warmup):
+        idx.search_device(q.data_ptr(), nq, K, out_i.data_ptr(), out_d.data_ptr(), stream=s)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        idx.search_device(q.data_ptr(), nq, K, out_i.data_ptr(), out_d.data_ptr(), stream=s)
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    ms = np.array(ms)
+    qt = 1 if nq == 1 else (2 if nq == 2 else 4)
+    lanes = 16 if qt == 4 else 32
+    npad = (n + 63) // 64 * 64
+    lookups = float(nq) * n * M
+    lds_floor = lookups / qt / (CUS * CLOCK * lanes)
+    mat_bytes = float(nq) * npad * 4 * (1 + SELECT_PASSES)
+    med = float(np.median(ms))
+    rec = {"case": "search", "n": n, "m": M, "ks": KS, "d": D, "queries": nq, "k": K, "steps": steps, "warmup": warmup,
+           "ms_per_batch_median": med, "ms_per_batch_min": float(ms.min()), "ms_per_batch_max": float(ms.max()),
+           "queries_per_s": nq / (med * 1e-3), "query_tile": qt, "lookups": lookups, "lds_floor_ms": lds_floor * 1e3,
+           "matrix_bytes": mat_bytes, "matrix_hbm_floor_ms": mat_bytes / HBM_ROOF * 1e3,
+           "step_over_floor": med / (max(lds_floor, mat_bytes / HBM_ROOF) * 1e3), "hbm_bytes_index": idx.hbm_bytes,
+           "note": "step = one mi_pq_search_device call (table, scan, selection and emit per chunk of queries)"}
+    idx.close()
+    return rec
+
+
+def encode_case(_lib, torch, rows, steps):
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(99)
+    books = torch.randn((M, KS, D // M), dtype=torch.float32, device=dev, generator=gen).cpu().numpy()
+    x = torch.randn((rows, D), dtype=torch.float32, device=dev, generator=gen)
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps + 1):                                          # the first call allocates: not timed
+        with _lib.PQIndex.empty(books, rows) as idx:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            idx.add_device(x.data_ptr(), rows)
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+    ms = np.array(ms[1:])
+    steps64 = float(rows) * KS * D
+    med = float(np.median(ms))
+    return {"case": "encode", "rows": rows, "m": M, "ks": KS, "d": D, "steps": steps, "ms_median": med, "ms_min": float(ms.min()),
+            "rows_per_s": rows / (med * 1e-3), "f64_term_steps": steps64, "f64_valu_floor_ms": 3 * steps64 / F64_VALU * 1e3,
+            "over_floor": med / (3 * steps64 / F64_VALU * 1e3),
+            "note": "mi_pq_add of device rows (synchronous call between two events on the default stream)"}
+
+
+def run_child(args):
+    import torch
+    import isehr_amd  # noqa: F401
+    from isehr_amd import _lib
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: this benchmark measures the device and has no other path")
+    kind, *rest = args.child.split(":")
+    if kind == "search":
+        rec = search_case(_lib, torch, int(rest[0]), int(rest[1]), args.steps, args.warmup)
+    else:
+        rec = encode_case(_lib, torch, int(rest[0]), max(1, args.steps // 4))
+    rec["device"] = torch.cuda.get_device_name(0)
+    print("PQBENCH " + json.dumps(rec), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="1m,10m,encode", help="comma list of: 1m / 10m (1 005 994 / 10^7 codes at 1, 70 and 1024 "
+                                                              "queries), 1m-<Q> / 10m-<Q> (one batch size), encode")
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--encode-rows", type=int, default=1005994)
+    ap.add_argument("--case-timeout", type=int, default=240, help="seconds each child process may take")
+    ap.add_argument("--out", default=OUT)
+    ap.add_argument("--child", default="", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return run_child(args)
+    sizes = {"1m": 1005994, "10m": 10 ** 7}
+    children = []
+    for c in args.cases.split(","):
+        if c in sizes:
+            children += ["search:%d:%d" % (sizes[c], nq) for nq in (1, 70, 1024)]
+        elif "-" in c and c.split("-")[0] in sizes:
+            children.append("search:%d:%d" % (sizes[c.split("-")[0]], int(c.split("-")[1])))
+        elif c == "encode":
+            children.append("encode:%d" % args.encode_rows)
+        else:
+            raise SystemExit("unknown case " + c)
+    results = []
+    for child in children:
+        cmd = ["timeout", "-k", "10", str(args.case_timeout), sys.executable, os.path.abspath(__file__), "--child", child,
+               "--steps", str(args.steps), "--warmup", str(args.warmup)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("PQBENCH ")]
+        if r.returncode != 0 or not line:
+            print(r.stdout[-2000:], r.stderr[-4000:], file=sys.stderr)
+            raise SystemExit("case %s ended with status %d: nothing more is started" % (child, r.returncode))
+        results.append(json.loads(line[0][len("PQBENCH "):]))
+        print(json.dumps(results[-1]), flush=True)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    json.dump({"lds_roof": "256 CUs x 2.4 GHz x (32 | 16 at ds_read_b128) lanes per clock, before bank conflicts",
+               "hbm_roof_bytes_per_s": HBM_ROOF, "f64_valu_instructions_per_s": F64_VALU, "cases": results},
+              open(args.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
