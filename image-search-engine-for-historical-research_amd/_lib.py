@@ -104,6 +104,9 @@ SIGNATURES = {
     "mi_pq_get_codes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "mi_pq_get_codebooks": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi_pq_destroy": (C.c_int, [C.c_void_p]),
+    "mi_pq_train": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.c_int32, C.c_int32,
+                              C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_pq_train_timing": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mi_knn_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "mi_knn_phase1_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -985,6 +988,103 @@ def pq_code_rows(codes, m, ks):
     return a, max(int(a.strides[0]), a.shape[1])
 
 
+def _pq_train_shape(n, d, M, Ks, iters):
+    """The limits of mi_pq_train, answered with ValueError before the library is loaded.  -> L"""
+    n, d, M, Ks, iters = int(n), int(d), int(M), int(Ks), int(iters)
+    if not 1 <= M <= PQ_MAX_BOOKS:
+        raise ValueError("M = %d books, a PQ index takes 1 .. %d" % (M, PQ_MAX_BOOKS))
+    if not 2 <= Ks <= PQ_MAX_WORDS:
+        raise ValueError("Ks = %d codewords per book, a PQ index takes 2 .. %d (one byte per book)" % (Ks, PQ_MAX_WORDS))
+    if not 1 <= d <= PQ_MAX_DIM:
+        raise ValueError("d = %d, a PQ index takes 1 .. %d" % (d, PQ_MAX_DIM))
+    if d % M:
+        raise ValueError("d = %d is no multiple of M = %d" % (d, M))
+    if n < Ks:
+        raise ValueError("n = %d training rows, Ks = %d codewords need at least as many" % (n, Ks))
+    if iters < 1:
+        raise ValueError("iters = %d, training takes at least one iteration" % iters)
+    return d // M
+
+
+def _pq_train_init(init, M, Ks, L):
+    cb = pq_codebooks(init)
+    if cb.shape != (M, Ks, L):
+        raise ValueError("init of shape %s, the training takes [M, Ks, L] = %s" % (cb.shape, (M, Ks, L)))
+    return cb
+
+
+def _pq_train_call(ptr, n, d, code, rs, cs, memspace, M, Ks, iters, cb0, device):
+    L = d // M
+    out = np.empty((M, Ks, L), dtype=np.float32)
+    moved = np.zeros(iters, dtype=np.int64)
+    check(load().mi_pq_train(C.c_void_p(ptr), int(n), int(d), code, int(rs), int(cs), memspace, M, Ks, iters,
+                             None if cb0 is None else C.c_void_p(cb0.ctypes.data), device, out.ctypes.data_as(C.c_void_p),
+                             moved.ctypes.data_as(C.c_void_p), None))
+    return out, moved
+
+
+def pq_train(x, M, Ks, iters=20, init=None, init_rows=None, seed=None, device=0):
+    """Learns PQ codebooks on the device (mi_pq_train): Lloyd's k-means iteration per book, as a deterministic function of its
+    inputs.  x [n, d] float32/float64 (any strides), n >= Ks -> (codebooks float32 [M, Ks, L], moved int64 [iters]).
+    The initial codebooks are ONE of
+      init       a codebook array [M, Ks, L] (a result passed back in resumes the run bit for bit);
+      init_rows  an integer array [M, Ks] of row indices: codeword c of book j starts as book j's slice of row init_rows[j, c],
+                 gathered on the host;
+      seed       init_rows drawn as RandomState(seed).choice(n, Ks, replace=False), once per book in book order from one
+                 RandomState;
+    or, with none of them, the library's default: the rows floor(c * n / Ks).  More than one given is a ValueError.
+    moved[t] counts the (row, book) pairs whose codeword changed in iteration t (moved[0] = n * M); training stops at the first
+    zero and the remaining entries stay zero.  Arithmetic: float64 argmin assignment with ties to the lower codeword, member sums
+    in float64 in ascending row order, one divide, centroids rounded to float32 after every iteration; a codeword without members
+    keeps its value -- scipy.cluster.vq.kmeans2(minit="matrix"), the routine nanopq.PQ.fit runs per book.  It does NOT reproduce
+    nanopq's or faiss's random draw of initial points, nor their float32 arithmetic.  Bad arguments and non-finite rows raise
+    ValueError before the device is touched."""
+    a, code, rs, cs = _strided(x)
+    n, d = a.shape
+    M, Ks, iters = int(M), int(Ks), int(iters)
+    L = _pq_train_shape(n, d, M, Ks, iters)
+    if (init is not None) + (init_rows is not None) + (seed is not None) > 1:
+        raise ValueError("give at most one of init, init_rows and seed")
+    if not np.isfinite(a).all():
+        raise ValueError("training rows must be finite")
+    cb0 = None
+    if init is not None:
+        cb0 = _pq_train_init(init, M, Ks, L)
+    elif seed is not None:
+        rng = np.random.RandomState(seed)
+        init_rows = np.stack([rng.choice(n, Ks, replace=False) for _ in range(M)])
+    if init_rows is not None:
+        rows = np.asarray(init_rows)
+        if rows.shape != (M, Ks) or rows.dtype == np.bool_ or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("init_rows must be an integer array [M, Ks] = %s (got %s %s)" % ((M, Ks), rows.dtype, rows.shape))
+        if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= n):
+            raise ValueError("init_rows must lie in [0, n = %d)" % n)
+        cb0 = np.ascontiguousarray(np.stack([a[rows[j], j * L:(j + 1) * L] for j in range(M)]), dtype=np.float32)
+    return _pq_train_call(_base_pointer(a), n, d, code, rs, cs, MI_HOST, M, Ks, iters, cb0, device)
+
+
+def pq_train_device(x_ptr, n, d, M, Ks, iters, init=None, dtype=MI_F32, row_stride=None, col_stride=1, device=0):
+    """pq_train on device-resident rows (used where they lie; their producer must have completed): element (r, i) at
+    x_ptr + (r * row_stride + i * col_stride) elements of `dtype`, row_stride None = d.  init: codebooks [M, Ks, L] or None (the
+    rows floor(c * n / Ks)).  Non-finite rows leave the codebooks of the books they touch unspecified."""
+    M, Ks, iters = int(M), int(Ks), int(iters)
+    L = _pq_train_shape(n, d, M, Ks, iters)
+    cb0 = None if init is None else _pq_train_init(init, M, Ks, L)
+    return _pq_train_call(int(x_ptr), n, d, dtype, d if row_stride is None else row_stride, col_stride, MI_DEVICE, M, Ks, iters, cb0,
+                          device)
+
+
+def pq_train_timing():
+    """-> (assign_ms float32 [iterations that ran], update_ms float32 [updates that ran]): device times of this thread's last
+    pq_train / pq_train_device call."""
+    na, nu = C.c_int32(), C.c_int32()
+    check(load().mi_pq_train_timing(0, None, None, C.byref(na), C.byref(nu)))
+    cap = max(na.value, nu.value, 1)
+    a, u = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
+    check(load().mi_pq_train_timing(cap, a.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p), None, None))
+    return a[:na.value], u[:nu.value]
+
+
 class PQIndex:
     """PQ index on one MI355X (a `mi_pq` handle): exact ADC top-k on product-quantized codes by (distance asc, id asc)."""
 
@@ -1029,6 +1129,19 @@ class PQIndex:
         if int(capacity) < 1:
             raise ValueError("an empty index needs a capacity")
         return cls._create(cb, None, 0, cb.shape[0], MI_HOST, device, row_offset, capacity)
+
+    @classmethod
+    def fit(cls, x, M, Ks, iters=20, seed=42, capacity=0, device=0, row_offset=0):
+        """Learns the codebooks on x [n, d] (pq_train with `seed`; seed=None: the library's default initial rows), creates the
+        index and adds x.  The move counts of the training are in `.train_moved`."""
+        cb, moved = pq_train(x, M, Ks, iters=iters, seed=seed, device=device)
+        n = np.shape(x)[0]
+        if capacity and capacity < n:
+            raise ValueError("capacity %d below the %d rows given" % (capacity, n))
+        idx = cls.empty(cb, capacity or n, device=device, row_offset=row_offset)
+        idx.train_moved = moved
+        idx.add(x)
+        return idx
 
     @property
     def hbm_bytes(self):

@@ -14,6 +14,7 @@
 //   api_remove.hip    row removal in place: keep-list, block-ordered move through a bounded staging area, invalidations
 //   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix
 //   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
+//   api_pq_train.hip  learning PQ codebooks (mi_pq_train): deterministic Lloyd iterations on device-resident rows
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -346,6 +347,14 @@ MI_INTERNAL int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, i
 MI_INTERNAL void l2_scratch_free(mi_gallery* g);
 // ---- api_remove.hip
 MI_INTERNAL void remove_scratch_free(mi_gallery* g);
+// ---- api_pq.hip, api_pq_train.hip: host rows (any strides, in elements) hold no NaN and no infinity
+template <typename T>
+static bool pq_all_finite(const T* x, int64_t rows, int32_t d, int64_t rs, int64_t cs) {
+  for (int64_t r = 0; r < rows; ++r)
+    for (int32_t c = 0; c < d; ++c)
+      if (!std::isfinite(x[r * rs + (int64_t)c * cs])) return false;
+  return true;
+}
 // entry points that are not defined on a squared-L2 gallery (include/mi355_retrieval.h: mi_metric)
 #define REFUSE_L2(g, what)                                                                                          \
   do {                                                                                                              \

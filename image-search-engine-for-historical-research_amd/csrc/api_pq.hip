@@ -59,14 +59,6 @@ static bool pq_codes_below(const uint8_t* codes, int64_t rows, int64_t stride, i
   return true;
 }
 
-template <typename T>
-static bool pq_all_finite(const T* x, int64_t rows, int32_t d, int64_t rs, int64_t cs) {
-  for (int64_t r = 0; r < rows; ++r)
-    for (int32_t c = 0; c < d; ++c)
-      if (!std::isfinite(x[r * rs + (int64_t)c * cs])) return false;
-  return true;
-}
-
 // `rows` host rows of d elements from row r0 on -> h->xraw, packed [rows][d] in their own type, on the handle's stream.  Rows that
 // are not contiguous are packed on the host first, in `pack` (the copy has completed on return in that case)
 static int pq_stage_rows(mi_pq* h, const void* x, int64_t r0, int64_t rows, int dtype, int64_t rs, int64_t cs, std::vector<char>& pack) {

@@ -305,6 +305,16 @@ void launch_pq_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, con
 void launch_pq_emit(const int64_t* tidx, const float* tneg, int64_t nq, int32_t ke, int32_t k, int64_t row_offset, int64_t* out_idx,
                     float* out_dist, hipStream_t stream);
 
+// pq_train.hip -- learning PQ codebooks (api_pq_train.hip): Lloyd's iteration around launch_pq_encode.  cb [M][Ks][L] f32 is updated
+// in place (a codeword without members keeps its value); codes [n][M] bytes, cols [M][n] bytes (one contiguous column per book)
+void launch_pq_init_rows(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, int32_t M, int32_t Ks, int32_t L, float* cb,
+                         hipStream_t stream);
+void launch_pq_code_columns(const uint8_t* codes, int32_t M, int64_t n, uint8_t* cols, hipStream_t stream);
+// adds the number of differing bytes to *count; a and b 16-byte aligned
+void launch_pq_moved(const uint8_t* a, const uint8_t* b, int64_t bytes, unsigned long long* count, hipStream_t stream);
+void launch_pq_update(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const uint8_t* cols, int32_t M, int32_t Ks, int32_t L,
+                      float* cb, hipStream_t stream);
+
 // synth.hip
 void launch_synth_fill(float* dst, uint64_t seed, int64_t row0, int64_t nrows, int32_t d, hipStream_t stream);
 

@@ -293,8 +293,96 @@ def matching_PQ_Net_hip(K, Codewords, Query, N_books, CW_idx):
     return idx, (time.time() - t1) / max(num_test, 1)
 
 
+def _l2_rows_f32(a, name):
+    """The reference's normalisation (src/utils/nnsearch.py:832-835, 866-873): rows divided by their Euclidean norm in the
+    array's own precision, then cast to float32."""
+    a = np.asarray(a)
+    if a.ndim != 2 or not np.issubdtype(a.dtype, np.floating):
+        raise ValueError("%s must be a 2-D floating-point array (got %s %s)" % (name, a.dtype, a.shape))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = (a / np.expand_dims(np.linalg.norm(a, axis=1), axis=1)).astype(np.float32)
+    if not np.isfinite(out).all():
+        raise ValueError("%s: rows must be finite and non-zero" % name)
+    return out
+
+
+def _pq_words(n_bits_perbook):
+    n_bits = int(n_bits_perbook)
+    if n_bits < 1 or (1 << n_bits) > _lib.PQ_MAX_WORDS:
+        raise ValueError("n_bits_perbook = %d: a code byte holds Ks <= %d codewords per book (1 .. 8 bits)" % (n_bits, _lib.PQ_MAX_WORDS))
+    return 1 << n_bits
+
+
+def _pq_books_path(dataset, n_books, n_words):
+    return os.path.join(os.path.dirname(_gallery_path(dataset)), "mi355_pq_M%d_Ks%d.npz" % (n_books, n_words))
+
+
+def Nano_PQ_hip(embedded_features, N_books, N_words):
+    """Same signature and return shape as Nano_PQ (src/utils/nnsearch.py:828-845): rows L2-normalised and cast to float32,
+    codebooks learned on them (20 iterations, seed 42: _lib.pq_train), rows encoded -> (codes uint8 [N, N_books], Codewords
+    [N_words, dim] in the reference's layout -- book j is the column block j * L .. (j + 1) * L -- and the reconstruction
+    float32 [N, dim], codebooks[j, code[:, j]] gathered on the host).  The iteration is the one nanopq runs
+    (scipy.cluster.vq.kmeans2, minit="matrix") in float64 with float32 centroids; nanopq's random draw of the initial rows
+    is not reproduced, so the codebooks differ from nanopq's the way two seeds differ."""
+    x = _l2_rows_f32(embedded_features, "embedded_features")
+    N_books, N_words = int(N_books), int(N_words)
+    with _lib.PQIndex.fit(x, N_books, N_words, iters=20, seed=42) as g:
+        books, codes = g.codebooks, g.get_codes()
+    recon = np.concatenate([books[j][codes[:, j]] for j in range(N_books)], axis=1)
+    codewords = np.ascontiguousarray(books.transpose(1, 0, 2)).reshape(N_words, -1)
+    return codes, codewords, recon
+
+
+def matching_Nano_PQ_hip(K, embedded_features_train, embedded_features_test, dataset=None, N_books=16, n_bits_perbook=8,
+                         ifgenerate=True):
+    """Same signature and return shape as matching_Nano_PQ (src/utils/nnsearch.py:847-901), `--matching_method PQ`: both sides
+    L2-normalised and cast to float32 as the reference does (:866-873), codebooks of N_books books of 2^n_bits_perbook
+    codewords learned on the database rows (20 iterations, seed 42), rows encoded, exact ADC top-K
+    -> (idx int64 [Q, K], time_per_query).  n_bits_perbook <= 8 (Ks <= 256, one byte per book; the reference's entry points pass
+    13, which this build does not take), 1 <= K <= min(N, 2048).  With a `dataset` the codebooks persist as
+    outputs/<dataset>/mi355_pq_M<M>_Ks<Ks>.npz (written to a temporary name and renamed): learned and written iff `ifgenerate`,
+    otherwise loaded -- a missing file raises FileNotFoundError, as the reference's open() does; dataset=None writes nothing
+    (and needs ifgenerate).  The timer spans what the reference's spans (:892-900): the search only, device-synchronised.
+    Learning is deterministic (see _lib.pq_train) but does not reproduce nanopq's random draw of initial rows.  Bad input raises
+    ValueError before the device is touched."""
+    N_books, K = int(N_books), int(K)
+    n_words = _pq_words(n_bits_perbook)
+    train = _l2_rows_f32(embedded_features_train, "embedded_features_train")
+    test = _l2_rows_f32(embedded_features_test, "embedded_features_test")
+    if train.shape[1] != test.shape[1]:
+        raise ValueError("expected rows [N, dim] and queries [Q, dim], got %s and %s" % (train.shape, test.shape))
+    num_train, num_test = train.shape[0], test.shape[0]
+    if K < 1 or K > num_train:
+        raise ValueError("K = %d, the database holds %d rows" % (K, num_train))
+    if K > TOPK_PATH_MAX_K:
+        raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
+    L = _lib._pq_train_shape(num_train, train.shape[1], N_books, n_words, 20)
+    if dataset is None and not ifgenerate:
+        raise ValueError("ifgenerate=False loads the codebooks of a dataset: give one")
+    if ifgenerate:
+        books, _ = _lib.pq_train(train, N_books, n_words, iters=20, seed=42)
+        if dataset is not None:
+            path = _pq_books_path(dataset, N_books, n_words)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            tmp = "%s.tmp.%d.%s.npz" % (path, os.getpid(), uuid.uuid4().hex[:12])
+            with _path_lock(path):
+                np.savez(tmp, codebooks=books)
+                os.replace(tmp, path)
+    else:
+        with np.load(_pq_books_path(dataset, N_books, n_words)) as z:        # (FileNotFoundError when it was never generated)
+            books = z["codebooks"]
+        if books.shape != (N_books, n_words, L):
+            raise ValueError("stored codebooks of shape %s, this call takes %s" % (books.shape, (N_books, n_words, L)))
+    with _lib.PQIndex.empty(books, num_train) as g:
+        g.add(train)
+        t1 = time.time()
+        idx, _, _ = g.search(test, K)                  # (synchronous: the results are on the host when it returns)
+        t2 = time.time()
+    return idx, (t2 - t1) / max(num_test, 1)
+
+
 # the matchers of this build by the name the reference's entry points dispatch on (--matching_method, src/offline.py:107-118)
-MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip}
+MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip, "PQ": matching_Nano_PQ_hip}
 
 
 def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test):

@@ -246,7 +246,8 @@ int mi_hamming_destroy(mi_hamming* h); /* NULL is MI_OK */
  *   order     (distance asc, id asc), ids row_offset + local row; +inf (a table entry beyond float32) is an ordinary value
  *   encoding  code[r][j] = argmin_c of the float64 sum above (before the rounding), ties to the lower c
  * No certificate, no flag, no fallback path.  The handle is a type of its own, ONE row shard on ONE device; none of the mi_gallery
- * entry points takes it.  Out of scope: learning codebooks, ks > 256, row removal, save / load, sharding, IVF, re-ranking.
+ * entry points takes it.  Codebooks are learned by mi_pq_train (below).  Out of scope: ks > 256, row removal, save / load,
+ * sharding, IVF, re-ranking.
  * mi_pq_create: n rows of `codes` (row i at codes + i * row_stride_bytes; MI_HOST or MI_DEVICE, device rows complete when the
  * call is made) into an index of `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty appendable
  * index.  A code byte >= ks is MI_ERR_INVALID (host codes are checked before a device is touched).  Synchronous. */
@@ -285,6 +286,36 @@ int mi_pq_get_codes(mi_pq* h, int64_t row0, int64_t nrows, uint8_t* out_host);
 /* The codebooks as given, [m][ks][L] float32. */
 int mi_pq_get_codebooks(const mi_pq* h, float* out_host);
 int mi_pq_destroy(mi_pq* h); /* NULL is MI_OK */
+/* Learning the codebooks: Lloyd's k-means iteration per book from given initial centroids, as a deterministic function of its
+ * inputs -- scipy.cluster.vq.kmeans2(minit="matrix"), the routine nanopq's PQ.fit runs, made reproducible on the device.  DESIGN.md
+ * 5.14b.  Training rows x [n][d] (MI_F32 or MI_F64; element (r, i) at x + r * row_stride + i * col_stride elements; MI_HOST or
+ * MI_DEVICE), m books of ks codewords of L = d / m floats with the limits of mi_pq_create, n >= ks, iters >= 1.  C_0 is
+ * init_codebooks_host ([m][ks][L] float32, finite; passing a result back in RESUMES a run) or, when NULL, codeword c of every book
+ * is the book's slice of row floor(c * n / ks), rounded to float32.  For t = 0 .. iters - 1:
+ *   assign   code_t[r][j] = what mi_pq_encode returns for row r under C_t (float64 argmin, ties to the lower codeword)
+ *   moved    moved[t] = number of (r, j) with code_t[r][j] != code_{t-1}[r][j]; moved[0] = n * m.  t > 0 and moved[t] == 0:
+ *            training stops, the result is C_t and moved[t + 1 ..] = 0 (exact: the same members give the same sums)
+ *   update   for every (j, c) with members: S[i] = sum of double(x[r][j L + i]) over the members r in ASCENDING r, from +0.0, each
+ *            an IEEE float64 add; C_{t+1}[j][c][i] = (float)(S[i] / (double)count), one IEEE float64 divide, rounded once to
+ *            float32.  A codeword without members keeps its value (kmeans2's rule, hence nanopq's)
+ * out_codebooks_host [m][ks][L] receives C_iters, out_moved [iters] (may be NULL) the move counts, out_seconds (may be NULL) the
+ * wall time of the call.  Centroids are rounded to float32 after EVERY iteration, so every step can be checked through
+ * mi_pq_encode, and iters = a followed by iters = b from the result equals iters = a + b bit for bit; two calls on the same input
+ * return the same bytes.  Not a goal: nanopq's or faiss's random draw of initial points, or their float32 arithmetic.
+ * Synchronous, on a stream of its own, no handle and no state left behind.  Host rows are uploaded ONCE, packed [n][d] in their own
+ * type (n * d * 4 or 8 bytes of device memory: 8.2 GB at 1 005 994 x 2048 float32), and all iterations run from that copy; device
+ * rows are used where they lie and must be complete when the call is made.  Besides: 3 * n * m bytes of codes and the codebooks;
+ * one 8-byte read-back per iteration decides the early stop.  Every argument check -- the limits, n >= ks, iters >= 1, NULL
+ * pointers, a non-finite initial codebook, non-finite HOST rows -- answers MI_ERR_INVALID before a device is touched.  Non-finite
+ * DEVICE rows leave the codebooks of the books they touch unspecified (nothing is read or written out of bounds).  An allocation
+ * that fails: MI_ERR_NOMEM, everything freed. */
+int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t m,
+                int32_t ks, int32_t iters, const float* init_codebooks_host, int device, float* out_codebooks_host,
+                int64_t* out_moved, double* out_seconds);
+/* Device times (HIP events, milliseconds) of the calling thread's last mi_pq_train: the assignment (encode and move count) of
+ * every iteration that ran and the update of every iteration that had one; at most `capacity` values each are written, the
+ * numbers that ran go to out_assignments / out_updates (may be NULL). */
+int mi_pq_train_timing(int32_t capacity, float* out_assign_ms, float* out_update_ms, int32_t* out_assignments, int32_t* out_updates);
 
 /* Device-resident variant: q_dev [nq][d] row-major f32 (C order), outputs are device buffers.
  * out_score64_dev (may be NULL) receives the float64 exact scores. */

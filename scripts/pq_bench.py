@@ -15,6 +15,12 @@ The encode case times mi_pq_add of `--encode-rows` device rows (N x Ks x d float
 vector f64 rate 256 CUs x 4 SIMDs x 16 lanes x 2.4 GHz / 2).  The "greedyhash-sized" case is the shape of
 scripts/hamming_bench.py (1 005 994 rows of d = 2048, 70 queries) for a side-by-side of queries/s.
 
+The train case (`--cases train`, written to profiles/pq_train_bench.json) times mi_pq_train on 1 005 994 x 2048 float32 rows
+generated on the device, M = 16, Ks = 256, 20 iterations from the default initial rows: the library's HIP events around the
+assignment and the update of every iteration (mi_pq_train_timing), the move counts, the whole call; then the host variant
+on a prefix of the same rows (`--train-host-rows`) for the upload, and scipy.cluster.vq.kmeans2 on one book of a 100 000-row
+subsample for scale -- one thread, one book.
+
 Every case runs in a child process of its own under `timeout`; the driver stops at the first case that fails."""
 import argparse
 import json
@@ -27,6 +33,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "profiles", "pq_bench.json")
+TRAIN_OUT = os.path.join(ROOT, "profiles", "pq_train_bench.json")
 
 CLOCK, CUS = 2.4e9, 256
 HBM_ROOF = 8e12                            # bytes / s
@@ -109,6 +116,59 @@ def encode_case(_lib, torch, rows, steps):
             "note": "mi_pq_add of device rows (synchronous call between two events on the default stream)"}
 
 
+def train_case(_lib, torch, rows, iters, host_rows):
+    import time
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)
+    L = D // M
+    # clustered rows: 256 centres per book and noise, so that the iteration has something to find
+    cent = torch.randn((M, KS, L), dtype=torch.float32, device=dev, generator=gen)
+    lab = torch.randint(0, KS, (rows, M), device=dev, generator=gen)
+    x = torch.empty((rows, D), dtype=torch.float32, device=dev)
+    for j in range(M):
+        x[:, j * L:(j + 1) * L] = cent[j][lab[:, j]]
+    del lab
+    step = 1 << 17
+    for r in range(0, rows, step):
+        x[r:r + step] += 0.5 * torch.randn((min(step, rows - r), D), dtype=torch.float32, device=dev, generator=gen)
+    torch.cuda.synchronize()
+    _lib.pq_train_device(x.data_ptr(), 4096, D, M, KS, 1)               # the first call loads the code objects: not timed
+    t0 = time.time()
+    books, moved = _lib.pq_train_device(x.data_ptr(), rows, D, M, KS, iters)
+    call_s = time.time() - t0
+    assign, update = _lib.pq_train_timing()
+    rec = {"case": "train", "rows": rows, "m": M, "ks": KS, "d": D, "iters": iters, "init": "default rows floor(c n / ks)",
+           "call_seconds": call_s, "moved": moved.tolist(), "assign_ms": [float(v) for v in assign], "update_ms": [float(v) for v in update],
+           "assign_ms_median": float(np.median(assign)), "update_ms_median": float(np.median(update)),
+           "update_hbm_floor_ms": float(rows) * D * 4 / HBM_ROOF * 1e3,
+           "assign_f64_valu_floor_ms": [2 * float(rows) * KS * D / F64_VALU * 1e3, 3 * float(rows) * KS * D / F64_VALU * 1e3],
+           "note": "device rows; assignment = pq_encode_kernel + the move count, update = code columns + pq_update_kernel, both "
+                   "between HIP events of the library (mi_pq_train_timing)"}
+    if host_rows > 0:
+        hx = x[:host_rows].cpu().numpy()
+        t0 = time.time()
+        _lib.pq_train(hx, M, KS, iters=1)
+        host_s = time.time() - t0
+        t0 = time.time()
+        _lib.pq_train_device(x.data_ptr(), host_rows, D, M, KS, 1)
+        dev_s = time.time() - t0
+        rec["host_variant"] = {"rows": host_rows, "bytes": host_rows * D * 4, "iters": 1, "host_call_seconds": host_s,
+                               "device_call_seconds": dev_s, "upload_and_checks_seconds": host_s - dev_s,
+                               "note": "pageable host rows; the difference holds the finite check on the host and the one upload"}
+    try:
+        from scipy.cluster.vq import kmeans2
+        sub = x[:100000, :L].double().cpu().numpy()
+        c0 = sub[(np.arange(KS) * sub.shape[0]) // KS]
+        t0 = time.time()
+        kmeans2(sub, c0, iter=iters, minit="matrix")
+        rec["scipy_kmeans2"] = {"rows": int(sub.shape[0]), "books": 1, "iters": iters, "seconds": time.time() - t0,
+                                "note": "one thread, ONE book of a 100 000-row subsample on the host of the GPU"}
+    except ImportError:
+        rec["scipy_kmeans2"] = None
+    return rec
+
+
 def run_child(args):
     import torch
     import isehr_amd  # noqa: F401
@@ -118,6 +178,8 @@ def run_child(args):
     kind, *rest = args.child.split(":")
     if kind == "search":
         rec = search_case(_lib, torch, int(rest[0]), int(rest[1]), args.steps, args.warmup)
+    elif kind == "train":
+        rec = train_case(_lib, torch, int(rest[0]), args.train_iters, min(args.train_host_rows, int(rest[0])))
     else:
         rec = encode_case(_lib, torch, int(rest[0]), max(1, args.steps // 4))
     rec["device"] = torch.cuda.get_device_name(0)
@@ -127,10 +189,14 @@ def run_child(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="1m,10m,encode", help="comma list of: 1m / 10m (1 005 994 / 10^7 codes at 1, 70 and 1024 "
-                                                              "queries), 1m-<Q> / 10m-<Q> (one batch size), encode")
+                                                              "queries), 1m-<Q> / 10m-<Q> (one batch size), encode, train")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--encode-rows", type=int, default=1005994)
+    ap.add_argument("--train-rows", type=int, default=1005994)
+    ap.add_argument("--train-iters", type=int, default=20)
+    ap.add_argument("--train-host-rows", type=int, default=250000, help="rows of the host variant (0 = skip it)")
+    ap.add_argument("--train-out", default=TRAIN_OUT)
     ap.add_argument("--case-timeout", type=int, default=240, help="seconds each child process may take")
     ap.add_argument("--out", default=OUT)
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
@@ -146,12 +212,15 @@ def main():
             children.append("search:%d:%d" % (sizes[c.split("-")[0]], int(c.split("-")[1])))
         elif c == "encode":
             children.append("encode:%d" % args.encode_rows)
+        elif c == "train":
+            children.append("train:%d" % args.train_rows)
         else:
             raise SystemExit("unknown case " + c)
     results = []
     for child in children:
         cmd = ["timeout", "-k", "10", str(args.case_timeout), sys.executable, os.path.abspath(__file__), "--child", child,
-               "--steps", str(args.steps), "--warmup", str(args.warmup)]
+               "--steps", str(args.steps), "--warmup", str(args.warmup), "--train-iters", str(args.train_iters),
+               "--train-host-rows", str(args.train_host_rows)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("PQBENCH ")]
         if r.returncode != 0 or not line:
@@ -159,6 +228,14 @@ def main():
             raise SystemExit("case %s ended with status %d: nothing more is started" % (child, r.returncode))
         results.append(json.loads(line[0][len("PQBENCH "):]))
         print(json.dumps(results[-1]), flush=True)
+    trained = [r for r in results if r["case"] == "train"]
+    results = [r for r in results if r["case"] != "train"]
+    if trained:
+        os.makedirs(os.path.dirname(args.train_out), exist_ok=True)
+        json.dump({"hbm_roof_bytes_per_s": HBM_ROOF, "f64_valu_instructions_per_s": F64_VALU, "cases": trained},
+                  open(args.train_out, "w"), indent=1)
+    if not results:
+        return
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     json.dump({"lds_roof": "256 CUs x 2.4 GHz x (32 | 16 at ds_read_b128) lanes per clock, before bank conflicts",
                "hbm_roof_bytes_per_s": HBM_ROOF, "f64_valu_instructions_per_s": F64_VALU, "cases": results},
