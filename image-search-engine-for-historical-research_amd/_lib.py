@@ -107,6 +107,20 @@ SIGNATURES = {
     "mi_pq_train": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_pq_train_timing": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mi_ivfpq_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                  C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "mi_ivfpq_append_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    "mi_ivfpq_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "mi_ivfpq_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
+    "mi_ivfpq_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_ivfpq_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "mi_ivfpq_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i64p, c_i64p, c_i64p]),
+    "mi_ivfpq_list_sizes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_ivfpq_get_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mi_ivfpq_destroy": (C.c_int, [C.c_void_p]),
     "mi_knn_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
     "mi_knn_phase1_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -1236,6 +1250,237 @@ class PQIndex:
     def close(self):
         if self._h is not None and self._h.value:
             check(load().mi_pq_destroy(self._h))
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+IVF_MAX_LISTS = 256
+
+
+def ivf_coarse(coarse, d):
+    """float32 [nlist, d] C-contiguous coarse centroids, checked against what an IVF-PQ index takes: 2 <= nlist <= 256, finite.
+    Raises ValueError."""
+    g = np.ascontiguousarray(coarse, dtype=np.float32)
+    if g.ndim == 3 and g.shape[0] == 1:              # what pq_train(x, 1, nlist) returns
+        g = g[0]
+    if g.ndim != 2:
+        raise ValueError("coarse centroids must be [nlist, d] (got shape %s)" % (g.shape,))
+    if not 2 <= g.shape[0] <= IVF_MAX_LISTS:
+        raise ValueError("nlist = %d lists, an IVF-PQ index takes 2 .. %d (one byte per row)" % (g.shape[0], IVF_MAX_LISTS))
+    if g.shape[1] != d:
+        raise ValueError("coarse centroids of %d columns, the codebooks span d = %d" % (g.shape[1], d))
+    if not np.isfinite(g).all():
+        raise ValueError("coarse centroids must be finite")
+    return g
+
+
+def ivf_list_ids(lists, rows, nlist):
+    """uint8 [rows] C-contiguous list ids from any integer array with values in [0, nlist).  Raises ValueError."""
+    a = np.asarray(lists)
+    if a.ndim != 1 or a.shape[0] != rows:
+        raise ValueError("list ids must be [rows = %d] (got shape %s)" % (rows, a.shape))
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("list ids must be an integer array (got %s)" % a.dtype)
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= nlist):
+        raise ValueError("list ids must lie in [0, nlist = %d)" % nlist)
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+class IVFPQIndex:
+    """IVF index over PQ codes on one MI355X (a `mi_ivfpq` handle): the exact ADC top-k of PQIndex.search over the rows whose
+    list is one of a query's probed lists, by (distance asc, id asc)."""
+
+    def __init__(self, handle):
+        self._h = C.c_void_p(handle)
+        self._lock = threading.Lock()
+        self._info()
+
+    def _info(self):
+        n, cap, off, hb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        d, m, ks, nlist, dev = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(load().mi_ivfpq_info(self._h, n, d, m, ks, nlist, dev, off, cap, hb))
+        self.n, self.d, self.m, self.ks, self.nlist, self.device = n.value, d.value, m.value, ks.value, nlist.value, dev.value
+        self.row_offset, self.capacity = off.value, cap.value
+        return hb.value
+
+    @classmethod
+    def _create(cls, g, cb, codes_ptr, lists_ptr, n, stride, memspace, device, row_offset, capacity):
+        m, ks, L = cb.shape
+        h = C.c_void_p()
+        check(load().mi_ivfpq_create(C.c_void_p(g.ctypes.data), g.shape[0], C.c_void_p(cb.ctypes.data), m * L, m, ks, C.c_void_p(codes_ptr),
+                                     C.c_void_p(lists_ptr), int(n), int(stride), memspace, device, int(row_offset), int(capacity),
+                                     C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_codes(cls, coarse, codebooks, codes, lists, device=0, row_offset=0, capacity=0):
+        """coarse [nlist, d] float32, codebooks [M, Ks, L] float32, codes integer [N, M] in [0, Ks), lists integer [N] in
+        [0, nlist); capacity 0 = N, larger leaves room for append_codes() / add()."""
+        cb = pq_codebooks(codebooks)
+        g = ivf_coarse(coarse, cb.shape[0] * cb.shape[2])
+        a, stride = pq_code_rows(codes, cb.shape[0], cb.shape[1])
+        li = ivf_list_ids(lists, a.shape[0], g.shape[0])
+        if capacity and capacity < a.shape[0]:
+            raise ValueError("capacity %d below the %d rows given" % (capacity, a.shape[0]))
+        return cls._create(g, cb, a.ctypes.data, li.ctypes.data, a.shape[0], stride, MI_HOST, device, row_offset, capacity)
+
+    @classmethod
+    def from_device_ptr(cls, coarse, codebooks, codes_ptr, lists_ptr, n, device=0, row_offset=0, capacity=0, row_stride_bytes=None):
+        """Device codes [n][M] uint8 and list ids [n] uint8 -> index, synchronous; their producer must have completed."""
+        cb = pq_codebooks(codebooks)
+        g = ivf_coarse(coarse, cb.shape[0] * cb.shape[2])
+        return cls._create(g, cb, codes_ptr, lists_ptr, n, cb.shape[0] if row_stride_bytes is None else row_stride_bytes, MI_DEVICE,
+                           device, row_offset, capacity)
+
+    @classmethod
+    def empty(cls, coarse, codebooks, capacity, device=0, row_offset=0):
+        """Appendable index: `capacity` rows allocated, filled by append_codes() / add()."""
+        cb = pq_codebooks(codebooks)
+        g = ivf_coarse(coarse, cb.shape[0] * cb.shape[2])
+        if int(capacity) < 1:
+            raise ValueError("an empty index needs a capacity")
+        return cls._create(g, cb, None, None, 0, cb.shape[0], MI_HOST, device, row_offset, capacity)
+
+    @classmethod
+    def fit(cls, x, nlist, M, Ks, iters=20, seed=42, capacity=0, device=0, row_offset=0):
+        """Learns the coarse centroids (pq_train with ONE book of nlist codewords) and the codebooks (pq_train) on x [n, d], both
+        with `seed`, creates the index and adds x.  The move counts are in `.coarse_moved` and `.train_moved`."""
+        nlist = int(nlist)
+        if not 2 <= nlist <= IVF_MAX_LISTS:
+            raise ValueError("nlist = %d lists, an IVF-PQ index takes 2 .. %d (one byte per row)" % (nlist, IVF_MAX_LISTS))
+        n = np.shape(x)[0]
+        if capacity and capacity < n:
+            raise ValueError("capacity %d below the %d rows given" % (capacity, n))
+        g, gmoved = pq_train(x, 1, nlist, iters=iters, seed=seed, device=device)
+        cb, moved = pq_train(x, M, Ks, iters=iters, seed=seed, device=device)
+        idx = cls.empty(g[0], cb, capacity or n, device=device, row_offset=row_offset)
+        idx.coarse_moved, idx.train_moved = gmoved, moved
+        idx.add(x)
+        return idx
+
+    @property
+    def hbm_bytes(self):
+        hb = C.c_int64()
+        check(load().mi_ivfpq_info(self._h, None, None, None, None, None, None, None, None, hb))
+        return hb.value
+
+    def _rows(self, x):
+        a, code, rs, cs = _strided(x)
+        if a.shape[1] != self.d:
+            raise ValueError("rows of %d columns, the index takes %d" % (a.shape[1], self.d))
+        return a, code, rs, cs
+
+    def _nprobe(self, nprobe):
+        nprobe = int(nprobe)
+        if not 1 <= nprobe <= self.nlist:
+            raise ValueError("nprobe = %d, the index has nlist = %d lists (1 .. nlist)" % (nprobe, self.nlist))
+        return nprobe
+
+    def append_codes(self, codes, lists):
+        a, stride = pq_code_rows(codes, self.m, self.ks)
+        li = ivf_list_ids(lists, a.shape[0], self.nlist)
+        with self._lock:
+            check(load().mi_ivfpq_append_codes(self._h, C.c_void_p(a.ctypes.data), C.c_void_p(li.ctypes.data), a.shape[0], stride, MI_HOST))
+            self.n += a.shape[0]
+
+    def append_codes_device(self, codes_ptr, lists_ptr, rows, row_stride_bytes=None):
+        with self._lock:
+            check(load().mi_ivfpq_append_codes(self._h, C.c_void_p(codes_ptr), C.c_void_p(lists_ptr), int(rows),
+                                               self.m if row_stride_bytes is None else int(row_stride_bytes), MI_DEVICE))
+            self.n += int(rows)
+
+    def add(self, x):
+        """Assigns rows [rows, d] float32/float64 (any strides) to their lists, encodes them on the device and appends."""
+        a, code, rs, cs = self._rows(x)
+        with self._lock:
+            check(load().mi_ivfpq_add(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST))
+            self.n += a.shape[0]
+
+    def add_device(self, x_ptr, rows, dtype=MI_F32, row_stride=None, col_stride=1):
+        with self._lock:
+            check(load().mi_ivfpq_add(self._h, C.c_void_p(x_ptr), int(rows), dtype, self.d if row_stride is None else int(row_stride),
+                                      int(col_stride), MI_DEVICE))
+            self.n += int(rows)
+
+    def probe(self, q, nprobe=1):
+        """-> int32 [Q, nprobe]: per query the nprobe lists nearest in float64, nearest first, ties to the lower list."""
+        a, code, rs, cs = self._rows(q)
+        nprobe = self._nprobe(nprobe)
+        out = np.empty((a.shape[0], nprobe), dtype=np.int32)
+        with self._lock:
+            check(load().mi_ivfpq_probe(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, nprobe,
+                                        out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def search(self, q, k, nprobe=1, probes=None, allow=None, allow_ptr=None):
+        """-> (ids int64 [Q,k], dist float32 [Q,k], seconds), ordered by (distance asc, id asc), over the rows of the probed
+        lists.  probes: integer [Q, P] of list ids, -1 = no list, repeats ignored (then nprobe is P); None: the library probes the
+        nprobe nearest lists.  allow / allow_ptr as for PQIndex.search.  Fewer than k such rows: trailing ids -1, distances +inf."""
+        a, code, rs, cs = self._rows(q)
+        nq, k = a.shape[0], int(k)
+        if allow is not None and allow_ptr is not None:
+            raise ValueError("give at most one of allow and allow_ptr")
+        pr, pr_p = None, None
+        if probes is not None:
+            pr = np.asarray(probes)
+            if pr.ndim != 2 or pr.shape[0] != nq or pr.dtype == np.bool_ or not np.issubdtype(pr.dtype, np.integer):
+                raise ValueError("probes must be an integer array [Q = %d, P] (got %s %s)" % (nq, pr.dtype, pr.shape))
+            if pr.size and (int(pr.min()) < -1 or int(pr.max()) >= self.nlist):
+                raise ValueError("probes must be -1 or lie in [0, nlist = %d)" % self.nlist)
+            nprobe = pr.shape[1]
+            pr = np.ascontiguousarray(pr, dtype=np.int32)
+            pr_p = C.c_void_p(pr.ctypes.data)
+        nprobe = self._nprobe(nprobe)
+        bits, bits_p, memspace = None, None, MI_HOST
+        if allow is not None:
+            bits = allow_bitmap(allow, self.n, self.row_offset)
+            if bits.size == 0:
+                bits = np.zeros(1, "<u8")
+            bits_p = C.c_void_p(bits.ctypes.data)
+        elif allow_ptr is not None:
+            bits_p, memspace = C.c_void_p(int(allow_ptr)), MI_DEVICE
+        idx = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float32)
+        secs = C.c_double()
+        with self._lock:
+            check(load().mi_ivfpq_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, nprobe, pr_p, bits_p, memspace,
+                                         idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p), C.byref(secs)))
+        return idx, dist, secs.value
+
+    def search_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, nprobe=1, probes_ptr=None, allow_ptr=None, stream=None):
+        """q_ptr: packed float32 [nq][d] on the device; probes_ptr: None or int32 [nq][nprobe] on the device (entries outside
+        [0, nlist) count as -1); enqueued on `stream`, no synchronisation."""
+        check(load().mi_ivfpq_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), int(nprobe), C.c_void_p(probes_ptr),
+                                            C.c_void_p(allow_ptr), C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def list_sizes(self):
+        out = np.empty(self.nlist, dtype=np.int64)
+        check(load().mi_ivfpq_list_sizes(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def get_rows(self, row0=0, nrows=None):
+        """-> (codes uint8 [nrows, M], lists uint8 [nrows]) of the rows row0 .. row0 + nrows in the order they were given."""
+        nrows = self.n - row0 if nrows is None else int(nrows)
+        codes = np.empty((nrows, self.m), dtype=np.uint8)
+        lists = np.empty(nrows, dtype=np.uint8)
+        with self._lock:
+            check(load().mi_ivfpq_get_rows(self._h, int(row0), nrows, codes.ctypes.data_as(C.c_void_p), lists.ctypes.data_as(C.c_void_p)))
+        return codes, lists
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            check(load().mi_ivfpq_destroy(self._h))
             self._h = None
 
     def __enter__(self):

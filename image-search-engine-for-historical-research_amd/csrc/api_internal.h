@@ -15,6 +15,7 @@
 //   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix
 //   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
 //   api_pq_train.hip  learning PQ codebooks (mi_pq_train): deterministic Lloyd iterations on device-resident rows
+//   api_ivfpq.hip     IVF index over PQ codes (mi_ivfpq): coarse lists as chains of 64-slot blocks, exact ADC top-K over the probed lists
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -66,7 +67,7 @@ extern MI_INTERNAL std::atomic<int> g_keep_buffers;
 extern MI_INTERNAL std::atomic<int64_t> g_scatter_block_rows;   // mi_scatter_matrix: rows per host block (0 = 64 MiB)
 extern MI_INTERNAL std::atomic<int64_t> g_remove_block_rows;    // mi_gallery_remove_rows: rows of the staging area (0 = default)
 extern MI_INTERNAL std::atomic<int64_t> g_hamming_matrix_bytes; // mi_hamming_search*: bytes of the distance matrix (default 2 GiB)
-extern MI_INTERNAL std::atomic<int64_t> g_pq_matrix_bytes;      // mi_pq_search*: bytes of the distance matrix (default 2 GiB)
+extern MI_INTERNAL std::atomic<int64_t> g_pq_matrix_bytes;      // mi_pq_search*: bytes of the distance matrix (default 2 GiB); mi_ivfpq_search*: of the partial lists
 constexpr size_t SPARE_MAX_BYTES = (size_t)16 << 30;
 MI_INTERNAL void spare_release_locked();
 MI_INTERNAL void spare_ws_release_locked();
@@ -347,7 +348,7 @@ MI_INTERNAL int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, i
 MI_INTERNAL void l2_scratch_free(mi_gallery* g);
 // ---- api_remove.hip
 MI_INTERNAL void remove_scratch_free(mi_gallery* g);
-// ---- api_pq.hip, api_pq_train.hip: host rows (any strides, in elements) hold no NaN and no infinity
+// ---- api_pq.hip, api_pq_train.hip, api_ivfpq.hip: host rows (any strides, in elements) hold no NaN and no infinity
 template <typename T>
 static bool pq_all_finite(const T* x, int64_t rows, int32_t d, int64_t rs, int64_t cs) {
   for (int64_t r = 0; r < rows; ++r)

@@ -1,0 +1,560 @@
+// IVF index over PQ codes of the C ABI (mi_ivfpq; kernels in csrc/ivfpq.hip): the reference's
+// matching_PQ_Net_bucket (src/utils/nnsearch.py:949-998), faiss IndexIVFPQ with by_residual = false.  A handle of its own: coarse
+// centroids, codebooks, a pool of 64-slot blocks chained into lists, and grow-only staging.  The HOST decides where a row goes
+// (the next free slot of its list; a new block from the pool when the tail is full) and keeps, per list, its block numbers and,
+// per row, its slot and list; after every create / append / add it uploads the flattened block table and list_off.  The answer
+// is a function of the inputs alone: the exact ADC top-K of mi_pq_search over the rows whose list is probed.
+#include "api_internal.h"
+
+struct mi_ivfpq {
+  int device = 0;
+  int64_t n = 0, cap = 0, row_offset = 0;
+  int32_t d = 0, m = 0, ks = 0, L = 0, MQ = 0, nlist = 0;
+  std::vector<float> cb_host, coarse_host;         // [m][ks][L], [nlist][d]
+  float *cb = nullptr, *coarse = nullptr;
+  int64_t pool_blocks = 0, pool_used = 0;          // ceil(cap / 64) + nlist: every list may end in a partly filled block
+  uint32_t* codes = nullptr;                       // [pool_blocks][MQ][64]
+  uint32_t* rowid = nullptr;                       // [pool_blocks][64]
+  uint32_t* blk_table = nullptr;                   // [pool_blocks]: the blocks of list 0, of list 1, ...
+  int32_t* list_off = nullptr;                     // [nlist + 1] into blk_table, followed by
+  uint32_t* list_rows = nullptr;                   // [nlist] rows per list (the same allocation)
+  std::vector<std::vector<uint32_t>> blocks;       // per list
+  std::vector<int64_t> list_size;                  // rows per list
+  std::vector<int64_t> slot_of_row;                // pblock * 64 + lane
+  std::vector<uint8_t> list_of_row;
+  uint32_t* flag = nullptr;
+  hipStream_t stream = nullptr;
+  char* xraw = nullptr;                            // rows / queries of a host call, packed [rows][d] in their own type
+  uint8_t *cbytes = nullptr, *lbytes = nullptr;    // packed code bytes [rows][m] and list ids [rows] on their way in
+  int64_t* slots = nullptr;
+  float* tab = nullptr;                            // [queries of a chunk][m][ks]
+  int32_t *praw = nullptr, *pnorm = nullptr, *pref = nullptr, *pex = nullptr;   // probes: chosen, normalised, prefix; a host call's own
+  uint64_t* part = nullptr;                        // [queries of a chunk][slabs][k]
+  uint64_t* bits = nullptr;
+  int64_t* oidx = nullptr;
+  float* odist = nullptr;
+  size_t xraw_cap = 0, cbytes_cap = 0, lbytes_cap = 0, slots_cap = 0, tab_cap = 0, praw_cap = 0, pnorm_cap = 0, pref_cap = 0, pex_cap = 0,
+         part_cap = 0, bits_cap = 0, oidx_cap = 0, odist_cap = 0;
+  std::mutex mu;
+};
+
+template <typename T>
+static int ivf_grow(T** p, size_t* cap, size_t count) {
+  if (*p && *cap >= count) return MI_OK;
+  (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = count + count / 4 + 64;
+  HIPC(device_malloc((void**)p, want * sizeof(T)));
+  *cap = want;
+  return MI_OK;
+}
+
+static int64_t ivf_scratch_bytes(const mi_ivfpq* h) {
+  return (int64_t)(h->xraw_cap + h->cbytes_cap + h->lbytes_cap + h->slots_cap * 8 + h->tab_cap * 4 +
+                   (h->praw_cap + h->pnorm_cap + h->pref_cap + h->pex_cap) * 4 + h->part_cap * 8 + h->bits_cap * 8 + h->oidx_cap * 8 +
+                   h->odist_cap * 4);
+}
+
+static bool ivf_bytes_below(const uint8_t* p, int64_t rows, int64_t stride, int32_t m, int32_t limit) {
+  if (limit >= 256) return true;
+  for (int64_t r = 0; r < rows; ++r)
+    for (int32_t b = 0; b < m; ++b)
+      if (p[r * stride + b] >= limit) return false;
+  return true;
+}
+
+// `rows` host rows of d elements from row r0 on -> h->xraw, packed [rows][d] in their own type (api_pq.hip's pq_stage_rows)
+static int ivf_stage_rows(mi_ivfpq* h, const void* x, int64_t r0, int64_t rows, int dtype, int64_t rs, int64_t cs, std::vector<char>& pack) {
+  const size_t esz = dtype == MI_F32 ? 4 : 8;
+  const size_t bytes = (size_t)rows * h->d * esz;
+  int rc;
+  if ((rc = ivf_grow(&h->xraw, &h->xraw_cap, bytes)) != MI_OK) return rc;
+  const char* src = (const char*)x + (size_t)r0 * rs * esz;
+  if (!(cs == 1 && (rs == h->d || rows == 1))) {
+    pack.resize(bytes);
+    for (int64_t r = 0; r < rows; ++r)
+      for (int32_t c = 0; c < h->d; ++c)
+        std::memcpy(pack.data() + ((size_t)r * h->d + c) * esz, src + ((size_t)r * rs + (size_t)c * cs) * esz, esz);
+    src = pack.data();
+  }
+  HIPC(hipMemcpyAsync(h->xraw, src, bytes, hipMemcpyHostToDevice, h->stream));
+  if (src == pack.data()) HIPC(hipStreamSynchronize(h->stream));
+  return MI_OK;
+}
+
+// ---- host bookkeeping.  A failed call puts the lists back: rows it already scattered sit in slots beyond their list's fill,
+// which the scan does not admit and the next append overwrites
+struct IvfMark {
+  int64_t n, pool_used;
+  std::vector<int64_t> list_size;
+};
+
+static IvfMark ivf_mark(const mi_ivfpq* h) { return {h->n, h->pool_used, h->list_size}; }
+
+static void ivf_rollback(mi_ivfpq* h, const IvfMark& mk) {
+  h->pool_used = mk.pool_used;
+  h->list_size = mk.list_size;
+  for (int32_t l = 0; l < h->nlist; ++l) h->blocks[l].resize((size_t)((mk.list_size[l] + 63) / 64));
+  h->slot_of_row.resize((size_t)mk.n);
+  h->list_of_row.resize((size_t)mk.n);
+}
+
+// the slots of `rows` more rows with the given lists, in row order
+static void ivf_place(mi_ivfpq* h, const uint8_t* lists, int64_t rows, int64_t* slots) {
+  for (int64_t r = 0; r < rows; ++r) {
+    const int32_t l = lists[r];
+    const int64_t fill = h->list_size[l]++;
+    if ((fill & 63) == 0) h->blocks[l].push_back((uint32_t)h->pool_used++);
+    slots[r] = (int64_t)h->blocks[l].back() * 64 + (fill & 63);
+    h->slot_of_row.push_back(slots[r]);
+    h->list_of_row.push_back((uint8_t)l);
+  }
+}
+
+// block table, list_off and list_rows -> device, synchronous
+static int ivf_publish(mi_ivfpq* h) {
+  std::vector<uint32_t> flat;
+  std::vector<int32_t> off(2 * (size_t)h->nlist + 1, 0);
+  flat.reserve((size_t)h->pool_used);
+  for (int32_t l = 0; l < h->nlist; ++l) {
+    flat.insert(flat.end(), h->blocks[l].begin(), h->blocks[l].end());
+    off[l + 1] = (int32_t)flat.size();
+    off[h->nlist + 1 + l] = (int32_t)(uint32_t)h->list_size[l];
+  }
+  if (!flat.empty()) HIPC(hipMemcpyAsync(h->blk_table, flat.data(), flat.size() * 4, hipMemcpyHostToDevice, h->stream));
+  HIPC(hipMemcpyAsync(h->list_off, off.data(), off.size() * 4, hipMemcpyHostToDevice, h->stream));
+  HIPC(hipStreamSynchronize(h->stream));
+  return MI_OK;
+}
+
+// code bytes of `rows` rows at src (device, row stride `stride`) whose lists are lists_host -> the index, behind the rows that
+// are there (h->n does not move).  Synchronous.
+static int ivf_scatter_rows(mi_ivfpq* h, const uint8_t* src_dev, int64_t stride, const uint8_t* lists_host, int64_t row0, int64_t rows,
+                            std::vector<int64_t>& slots) {
+  int rc;
+  slots.resize((size_t)rows);
+  ivf_place(h, lists_host, rows, slots.data());
+  if ((rc = ivf_grow(&h->slots, &h->slots_cap, (size_t)rows)) != MI_OK) return rc;
+  HIPC(hipMemcpyAsync(h->slots, slots.data(), (size_t)rows * 8, hipMemcpyHostToDevice, h->stream));
+  launch_ivf_scatter(src_dev, stride, h->m, h->slots, row0, rows, h->codes, h->rowid, h->stream);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(h->stream));
+  return MI_OK;
+}
+
+// rows of code bytes with their list ids (host: checked by the caller; device: checked here, before anything is ingested)
+static int ivf_ingest(mi_ivfpq* h, const void* codes, const uint8_t* list_ids, int64_t rows, int64_t stride, int memspace) {
+  hipStream_t s = h->stream;
+  int rc;
+  std::vector<uint8_t> lists_back;
+  if (memspace == MI_DEVICE) {
+    uint32_t f = 0;
+    if (h->ks < 256) launch_pq_check((const uint8_t*)codes, stride, h->m, h->ks, rows, h->flag, s);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(&f, h->flag, 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    uint32_t f2 = 0;
+    if (f == 0 && h->nlist < 256) {
+      launch_ivf_check(list_ids, h->nlist, rows, h->flag, s);
+      HIPC(hipGetLastError());
+      HIPC(hipMemcpyAsync(&f2, h->flag, 4, hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+    }
+    if (f || f2) {
+      HIPC(hipMemsetAsync(h->flag, 0, 4, s));
+      HIPC(hipStreamSynchronize(s));
+      return fail(MI_ERR_INVALID, f ? "a code byte is >= ks" : "a list id is >= nlist");
+    }
+    lists_back.resize((size_t)rows);
+    HIPC(hipMemcpy(lists_back.data(), list_ids, (size_t)rows, hipMemcpyDeviceToHost));
+    list_ids = lists_back.data();
+  }
+  const IvfMark mk = ivf_mark(h);
+  const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / h->m);
+  std::vector<int64_t> slots;
+  rc = MI_OK;
+  if (memspace == MI_HOST) rc = ivf_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m);
+  for (int64_t r = 0; r < rows && rc == MI_OK; r += step) {
+    const int64_t mm = std::min(step, rows - r);
+    const uint8_t* src = (const uint8_t*)codes + r * stride;
+    auto upload = [&]() -> int {
+      if (stride == h->m || mm == 1) HIPC(hipMemcpyAsync(h->cbytes, src, (size_t)mm * h->m, hipMemcpyHostToDevice, s));
+      else HIPC(hipMemcpy2DAsync(h->cbytes, (size_t)h->m, src, (size_t)stride, (size_t)h->m, (size_t)mm, hipMemcpyHostToDevice, s));
+      return MI_OK;
+    };
+    if (memspace == MI_HOST) {
+      if ((rc = upload()) != MI_OK) break;
+      rc = ivf_scatter_rows(h, h->cbytes, h->m, list_ids + r, h->n + r, mm, slots);
+    } else {
+      rc = ivf_scatter_rows(h, src, stride, list_ids + r, h->n + r, mm, slots);
+    }
+  }
+  if (rc == MI_OK) rc = ivf_publish(h);
+  if (rc != MI_OK) {
+    ivf_rollback(h, mk);
+    return rc;
+  }
+  h->n += rows;
+  return MI_OK;
+}
+
+// the `nprobe` largest lists' blocks, in slabs of 64: what the grid of the scan has to cover for ANY choice of probes
+static int64_t ivf_slab_bound(const mi_ivfpq* h, int32_t nprobe) {
+  std::vector<int64_t> c((size_t)h->nlist);
+  for (int32_t l = 0; l < h->nlist; ++l) c[l] = (int64_t)h->blocks[l].size();
+  std::partial_sort(c.begin(), c.begin() + nprobe, c.end(), std::greater<int64_t>());
+  int64_t tot = 0;
+  for (int32_t i = 0; i < nprobe; ++i) tot += c[i];
+  return (tot + 63) / 64;
+}
+
+// the search proper on stream s: queries on the device (any strides), probes_dev NULL or [nq][nprobe], results to device buffers
+static int ivf_search_core(mi_ivfpq* h, const void* q_dev, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k, int32_t nprobe,
+                           const int32_t* probes_dev, const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s) {
+  const size_t esz = dtype == MI_F32 ? 4 : 8;
+  const int64_t nslab = ivf_slab_bound(h, nprobe);
+  const int64_t per = (int64_t)h->m * h->ks;
+  // queries per pass: the partial lists within the budget, the tables within 256 MiB, the grid's y below 65536; one at the least
+  const int64_t budget = g_pq_matrix_bytes.load();
+  int64_t qc = std::min<int64_t>({nq, 65535, budget / std::max<int64_t>(1, nslab * k * 8), ((int64_t)256 << 20) / (per * 4)});
+  qc = std::max<int64_t>(1, qc);
+  int rc;
+  if ((rc = ivf_grow(&h->tab, &h->tab_cap, (size_t)(qc * per))) != MI_OK) return rc;
+  if ((rc = ivf_grow(&h->praw, &h->praw_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
+  if ((rc = ivf_grow(&h->pnorm, &h->pnorm_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
+  if ((rc = ivf_grow(&h->pref, &h->pref_cap, (size_t)(qc * (nprobe + 1)))) != MI_OK) return rc;
+  if ((rc = ivf_grow(&h->part, &h->part_cap, (size_t)(qc * nslab * k))) != MI_OK) return rc;
+  for (int64_t q0 = 0; q0 < nq; q0 += qc) {
+    const int32_t b = (int32_t)std::min<int64_t>(qc, nq - q0);
+    const char* qp = (const char*)q_dev + (size_t)q0 * rs * esz;
+    const int32_t* in = probes_dev ? probes_dev + q0 * nprobe : h->praw;
+    if (!probes_dev) launch_ivf_probe(qp, dtype, rs, cs, b, h->coarse, h->nlist, h->d, nprobe, h->praw, s);
+    launch_ivf_prefix(in, b, h->nlist, nprobe, h->list_off, h->pnorm, h->pref, s);
+    launch_pq_table(qp, dtype, rs, cs, b, h->cb, h->m, h->ks, h->L, h->tab, s);
+    launch_ivf_scan_select(h->codes, h->rowid, h->blk_table, h->list_off, h->m, h->ks, h->tab, h->pnorm, h->pref, nprobe, b, h->list_rows,
+                           allow_dev, k, (int32_t)nslab, h->part, s);
+    launch_ivf_merge(h->part, h->pref, nprobe, b, k, (int32_t)nslab, h->row_offset, out_idx_dev + q0 * k,
+                     out_dist_dev ? out_dist_dev + q0 * k : nullptr, s);
+  }
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+static int ivf_check_host_queries(const mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t rs, int64_t cs) {
+  REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  REQUIRE(rs >= 0 && cs >= 0, "negative strides are not supported");
+  const bool finite = dtype == MI_F32 ? pq_all_finite((const float*)q, nq, h->d, rs, cs) : pq_all_finite((const double*)q, nq, h->d, rs, cs);
+  REQUIRE(finite, "queries must be finite");
+  return MI_OK;
+}
+
+#define REQUIRE_ROWS(x, rows, dtype, rs, cs, memspace)                                                       \
+  REQUIRE((rows) >= 0, "negative number of rows");                                                           \
+  REQUIRE((x) || (rows) == 0, "null pointer: rows");                                                         \
+  REQUIRE((dtype) == MI_F32 || (dtype) == MI_F64, "dtype must be MI_F32 or MI_F64");                         \
+  REQUIRE((rs) >= 0 && (cs) >= 0, "negative strides are not supported");                                     \
+  REQUIRE((memspace) == MI_HOST || (memspace) == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE")
+
+extern "C" {
+
+int mi_ivfpq_create(const float* coarse_host, int32_t nlist, const float* codebooks_host, int32_t d, int32_t m, int32_t ks, const void* codes,
+                    const uint8_t* list_ids, int64_t n, int64_t row_stride_bytes, int memspace, int device, int64_t row_offset,
+                    int64_t capacity, mi_ivfpq** out) {
+  REQUIRE(out, "null pointer: out");
+  REQUIRE(coarse_host, "null pointer: coarse_host");
+  REQUIRE(codebooks_host, "null pointer: codebooks_host");
+  REQUIRE(nlist >= 2 && nlist <= 256, "nlist (lists) must be in [2, 256]");
+  REQUIRE(m >= 1 && m <= 64, "m (books) must be in [1, 64]");
+  REQUIRE(ks >= 2 && ks <= 256, "ks (codewords per book) must be in [2, 256]");
+  REQUIRE(d >= 1 && d <= 4096, "d must be in [1, 4096]");
+  REQUIRE(d % m == 0, "d must be a multiple of m");
+  REQUIRE(n >= 0, "negative number of rows");
+  REQUIRE(capacity >= 0, "negative capacity");
+  REQUIRE(capacity == 0 || capacity >= n, "capacity below the number of rows");
+  REQUIRE(codes || n == 0, "null pointer: codes");
+  REQUIRE(list_ids || n == 0, "null pointer: list_ids");
+  REQUIRE(n >= 1 || capacity >= 1, "an empty index needs a capacity");
+  REQUIRE(n == 0 || row_stride_bytes >= m, "row_stride_bytes below m");
+  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
+  if (capacity == 0) capacity = n;
+  REQUIRE(capacity < ((int64_t)1 << 32) - 1, "an index holds fewer than 2^32 - 1 rows");
+  const size_t cb_count = (size_t)ks * d, co_count = (size_t)nlist * d;
+  for (size_t i = 0; i < co_count; ++i) REQUIRE(std::isfinite(coarse_host[i]), "coarse centroids must be finite");
+  for (size_t i = 0; i < cb_count; ++i) REQUIRE(std::isfinite(codebooks_host[i]), "codebooks must be finite");
+  REQUIRE(memspace != MI_HOST || ivf_bytes_below((const uint8_t*)codes, n, row_stride_bytes, m, ks), "a code byte is >= ks");
+  REQUIRE(memspace != MI_HOST || ivf_bytes_below(list_ids, n, 1, 1, nlist), "a list id is >= nlist");
+  HIPC(hipSetDevice(device));
+  mi_ivfpq* h = new mi_ivfpq();
+  h->device = device;
+  h->cap = capacity;
+  h->row_offset = row_offset;
+  h->d = d;
+  h->m = m;
+  h->ks = ks;
+  h->L = d / m;
+  h->MQ = (m + 3) / 4;
+  h->nlist = nlist;
+  h->cb_host.assign(codebooks_host, codebooks_host + cb_count);
+  h->coarse_host.assign(coarse_host, coarse_host + co_count);
+  h->blocks.resize((size_t)nlist);
+  h->list_size.assign((size_t)nlist, 0);
+  h->pool_blocks = (capacity + 63) / 64 + nlist;
+  const size_t codes_bytes = (size_t)h->pool_blocks * h->MQ * 64 * 4, id_bytes = (size_t)h->pool_blocks * 64 * 4;
+  auto cleanup = [&](int code) {
+    mi_ivfpq_destroy(h);
+    return code;
+  };
+  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) e = device_malloc((void**)&h->codes, codes_bytes);
+  if (e == hipSuccess) e = device_malloc((void**)&h->rowid, id_bytes);
+  if (e == hipSuccess) e = device_malloc((void**)&h->blk_table, (size_t)h->pool_blocks * 4);
+  if (e == hipSuccess) e = device_malloc((void**)&h->list_off, (2 * (size_t)nlist + 1) * 4);
+  if (e == hipSuccess) e = device_malloc((void**)&h->cb, cb_count * 4);
+  if (e == hipSuccess) e = device_malloc((void**)&h->coarse, co_count * 4);
+  if (e == hipSuccess) e = device_malloc((void**)&h->flag, 256);
+  if (e == hipSuccess) e = hipMemsetAsync(h->codes, 0, codes_bytes, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->rowid, 0xFF, id_bytes, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->blk_table, 0, (size_t)h->pool_blocks * 4, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->list_off, 0, (2 * (size_t)nlist + 1) * 4, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->flag, 0, 256, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->cb, h->cb_host.data(), cb_count * 4, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h->coarse, h->coarse_host.data(), co_count * 4, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  h->list_rows = (uint32_t*)(h->list_off + nlist + 1);
+  if (e != hipSuccess)
+    return cleanup(fail(e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, std::string("IVF-PQ index: ") + hipGetErrorString(e)));
+  if (n > 0) {
+    const int rc = ivf_ingest(h, codes, list_ids, n, row_stride_bytes, memspace);
+    if (rc != MI_OK) return cleanup(rc);
+  }
+  *out = h;
+  return MI_OK;
+}
+
+int mi_ivfpq_append_codes(mi_ivfpq* h, const void* codes, const uint8_t* list_ids, int64_t rows, int64_t row_stride_bytes, int memspace) {
+  REQUIRE(h, "null handle");
+  REQUIRE(rows >= 0, "negative number of rows");
+  REQUIRE(codes || rows == 0, "null pointer: codes");
+  REQUIRE(list_ids || rows == 0, "null pointer: list_ids");
+  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
+  REQUIRE(rows == 0 || row_stride_bytes >= h->m, "row_stride_bytes below m");
+  std::lock_guard<std::mutex> lock(h->mu);
+  REQUIRE(h->n + rows <= h->cap, "index capacity exceeded");
+  if (rows == 0) return MI_OK;
+  REQUIRE(memspace != MI_HOST || ivf_bytes_below((const uint8_t*)codes, rows, row_stride_bytes, h->m, h->ks), "a code byte is >= ks");
+  REQUIRE(memspace != MI_HOST || ivf_bytes_below(list_ids, rows, 1, 1, h->nlist), "a list id is >= nlist");
+  HIPC(hipSetDevice(h->device));
+  return ivf_ingest(h, codes, list_ids, rows, row_stride_bytes, memspace);
+}
+
+int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace) {
+  REQUIRE(h, "null handle");
+  REQUIRE_ROWS(x, rows, dtype, row_stride, col_stride, memspace);
+  std::lock_guard<std::mutex> lock(h->mu);
+  REQUIRE(h->n + rows <= h->cap, "index capacity exceeded");
+  if (rows == 0) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  const size_t esz = dtype == MI_F32 ? 4 : 8;
+  const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * (int64_t)esz));
+  hipStream_t s = h->stream;
+  const IvfMark mk = ivf_mark(h);
+  std::vector<char> pack;
+  std::vector<uint8_t> lists;
+  std::vector<int64_t> slots;
+  // a block of rows: its codes (the encoder on the codebooks) and its lists (the encoder on ONE book, the coarse centroids)
+  auto block = [&](int64_t r, int64_t mm) -> int {
+    int rc;
+    const void* xp = (const char*)x + (size_t)r * row_stride * esz;
+    int64_t rs = row_stride, cs = col_stride;
+    if (memspace == MI_HOST) {
+      if ((rc = ivf_stage_rows(h, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+      xp = h->xraw;
+      rs = h->d;
+      cs = 1;
+    }
+    launch_pq_encode(xp, dtype, rs, cs, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
+    launch_pq_encode(xp, dtype, rs, cs, mm, h->coarse, 1, h->nlist, h->d, h->lbytes, s);
+    HIPC(hipGetLastError());
+    lists.resize((size_t)mm);
+    HIPC(hipMemcpyAsync(lists.data(), h->lbytes, (size_t)mm, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    return ivf_scatter_rows(h, h->cbytes, h->m, lists.data(), mk.n + r, mm, slots);
+  };
+  int rc = ivf_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m);
+  if (rc == MI_OK) rc = ivf_grow(&h->lbytes, &h->lbytes_cap, (size_t)std::min(step, rows));
+  for (int64_t r = 0; r < rows && rc == MI_OK; r += step) rc = block(r, std::min(step, rows - r));
+  if (rc == MI_OK) rc = ivf_publish(h);
+  if (rc != MI_OK) {
+    ivf_rollback(h, mk);
+    return rc;
+  }
+  h->n = mk.n + rows;
+  return MI_OK;
+}
+
+int mi_ivfpq_probe(mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t nprobe,
+                   int32_t* out_lists_host) {
+  REQUIRE(h, "null handle");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  REQUIRE(nprobe >= 1 && nprobe <= 256, "nprobe must be in [1, nlist]");
+  REQUIRE(nq == 0 || (q && out_lists_host), "null pointer");
+  REQUIRE(nprobe <= h->nlist, "nprobe must be in [1, nlist]");
+  if (nq == 0) return MI_OK;
+  int rc;
+  if ((rc = ivf_check_host_queries(h, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
+  std::lock_guard<std::mutex> lock(h->mu);
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t esz = dtype == MI_F32 ? 4 : 8;
+  const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)h->d * (int64_t)esz));
+  if ((rc = ivf_grow(&h->praw, &h->praw_cap, (size_t)(std::min(step, nq) * nprobe))) != MI_OK) return rc;
+  std::vector<char> pack;
+  for (int64_t q0 = 0; q0 < nq; q0 += step) {
+    const int64_t b = std::min(step, nq - q0);
+    if ((rc = ivf_stage_rows(h, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+    launch_ivf_probe(h->xraw, dtype, h->d, 1, b, h->coarse, h->nlist, h->d, nprobe, h->praw, s);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(out_lists_host + q0 * nprobe, h->praw, (size_t)(b * nprobe) * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+  }
+  return MI_OK;
+}
+
+int mi_ivfpq_search(mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k, int32_t nprobe,
+                    const int32_t* probes_host, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_dist,
+                    double* out_seconds) {
+  REQUIRE(h, "null handle");
+  REQUIRE(k >= 1 && k <= 2048, "k must be in [1, 2048]");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  REQUIRE(nprobe >= 1 && nprobe <= 256, "nprobe must be in [1, nlist]");
+  REQUIRE(nq == 0 || q, "null pointer: queries");
+  REQUIRE(nq == 0 || out_idx, "null pointer: out_idx");
+  REQUIRE(!allow_bits || allow_memspace == MI_HOST || allow_memspace == MI_DEVICE, "allow_memspace must be MI_HOST or MI_DEVICE");
+  if (out_seconds) *out_seconds = 0.0;
+  // the entries are compared with the one-byte limit first and with the handle's nlist after it: no check before this line reads
+  // the handle
+  if (probes_host)
+    for (int64_t i = 0; i < nq * nprobe; ++i)
+      REQUIRE(probes_host[i] >= -1 && probes_host[i] < 256, "a probe entry is neither -1 nor in [0, nlist)");
+  REQUIRE(nprobe <= h->nlist, "nprobe must be in [1, nlist]");
+  if (nq == 0) return MI_OK;
+  if (probes_host)
+    for (int64_t i = 0; i < nq * nprobe; ++i) REQUIRE(probes_host[i] < h->nlist, "a probe entry is neither -1 nor in [0, nlist)");
+  int rc;
+  if ((rc = ivf_check_host_queries(h, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
+  std::lock_guard<std::mutex> lock(h->mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const size_t cnt = (size_t)nq * k;
+  if ((rc = ivf_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
+  if (out_dist && (rc = ivf_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
+  const uint64_t* allow_dev = allow_bits;
+  if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
+    const size_t words = (size_t)((h->n + 63) / 64);
+    if ((rc = ivf_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
+    HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
+    allow_dev = h->bits;
+  }
+  if (probes_host) {
+    if ((rc = ivf_grow(&h->pex, &h->pex_cap, (size_t)(nq * nprobe))) != MI_OK) return rc;
+    HIPC(hipMemcpyAsync(h->pex, probes_host, (size_t)(nq * nprobe) * 4, hipMemcpyHostToDevice, s));
+  }
+  std::vector<char> pack;
+  if ((rc = ivf_stage_rows(h, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+  if ((rc = ivf_search_core(h, h->xraw, dtype, h->d, 1, nq, k, nprobe, probes_host ? h->pex : nullptr, allow_dev, h->oidx,
+                            out_dist ? h->odist : nullptr, s)) != MI_OK)
+    return rc;
+  HIPC(hipMemcpyAsync(out_idx, h->oidx, cnt * 8, hipMemcpyDeviceToHost, s));
+  if (out_dist) HIPC(hipMemcpyAsync(out_dist, h->odist, cnt * 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return MI_OK;
+}
+
+int mi_ivfpq_search_device(mi_ivfpq* h, const float* q_dev, int64_t nq, int32_t k, int32_t nprobe, const int32_t* probes_dev,
+                           const uint64_t* allow_bits_dev, int64_t* out_idx_dev, float* out_dist_dev, void* stream) {
+  REQUIRE(h, "null handle");
+  REQUIRE(k >= 1 && k <= 2048, "k must be in [1, 2048]");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  REQUIRE(nprobe >= 1 && nprobe <= 256, "nprobe must be in [1, nlist]");
+  REQUIRE(nq == 0 || (q_dev && out_idx_dev), "null pointer");
+  REQUIRE(nprobe <= h->nlist, "nprobe must be in [1, nlist]");
+  if (nq == 0) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  return ivf_search_core(h, q_dev, MI_F32, h->d, 1, nq, k, nprobe, probes_dev, allow_bits_dev, out_idx_dev, out_dist_dev, (hipStream_t)stream);
+}
+
+int mi_ivfpq_info(const mi_ivfpq* h, int64_t* n, int32_t* d, int32_t* m, int32_t* ks, int32_t* nlist, int32_t* device, int64_t* row_offset,
+                  int64_t* capacity, int64_t* hbm_bytes) {
+  REQUIRE(h, "null handle");
+  if (n) *n = h->n;
+  if (d) *d = h->d;
+  if (m) *m = h->m;
+  if (ks) *ks = h->ks;
+  if (nlist) *nlist = h->nlist;
+  if (device) *device = h->device;
+  if (row_offset) *row_offset = h->row_offset;
+  if (capacity) *capacity = h->cap;
+  if (hbm_bytes)
+    *hbm_bytes = h->pool_blocks * ((int64_t)h->MQ * 256 + 256 + 4) + (2 * (int64_t)h->nlist + 1) * 4 +
+                 (int64_t)(h->cb_host.size() + h->coarse_host.size()) * 4 + 256 + ivf_scratch_bytes(h);
+  return MI_OK;
+}
+
+int mi_ivfpq_list_sizes(const mi_ivfpq* h, int64_t* out) {
+  REQUIRE(h, "null handle");
+  REQUIRE(out, "null pointer: out");
+  for (int32_t l = 0; l < h->nlist; ++l) out[l] = h->list_size[l];
+  return MI_OK;
+}
+
+int mi_ivfpq_get_rows(mi_ivfpq* h, int64_t row0, int64_t nrows, uint8_t* out_codes_host, uint8_t* out_lists_host) {
+  REQUIRE(h, "null handle");
+  REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= h->n, "row range outside the index");
+  if (nrows == 0) return MI_OK;
+  std::lock_guard<std::mutex> lock(h->mu);
+  if (out_lists_host) std::memcpy(out_lists_host, h->list_of_row.data() + row0, (size_t)nrows);
+  if (!out_codes_host) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  HIPC(hipStreamSynchronize(h->stream));
+  // only the blocks the rows touch are read back: the rows in ascending order of their slot, every run of consecutive block
+  // numbers (at most 65536 blocks) in one copy
+  const int64_t blk_words = (int64_t)h->MQ * 64;
+  std::vector<std::pair<int64_t, int64_t>> by_slot((size_t)nrows);      // (slot, row)
+  for (int64_t r = 0; r < nrows; ++r) by_slot[(size_t)r] = {h->slot_of_row[(size_t)(row0 + r)], r};
+  std::sort(by_slot.begin(), by_slot.end());
+  std::vector<uint32_t> buf;
+  for (size_t t0 = 0; t0 < by_slot.size();) {
+    const int64_t b0 = by_slot[t0].first >> 6;
+    int64_t b1 = b0 + 1;
+    size_t t1 = t0 + 1;
+    while (t1 < by_slot.size() && (by_slot[t1].first >> 6) <= b1 && (by_slot[t1].first >> 6) - b0 < 65536) b1 = (by_slot[t1++].first >> 6) + 1;
+    buf.resize((size_t)((b1 - b0) * blk_words));
+    HIPC(hipMemcpy(buf.data(), h->codes + b0 * blk_words, buf.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t t = t0; t < t1; ++t) {
+      const int64_t slot = by_slot[t].first;
+      const uint32_t* src = buf.data() + ((slot >> 6) - b0) * blk_words + (slot & 63);
+      uint8_t* dst = out_codes_host + by_slot[t].second * h->m;
+      for (int32_t j = 0; j < h->m; ++j) dst[j] = (uint8_t)(src[(int64_t)(j >> 2) * 64] >> (8 * (j & 3)));
+    }
+    t0 = t1;
+  }
+  return MI_OK;
+}
+
+int mi_ivfpq_destroy(mi_ivfpq* h) {
+  if (!h) return MI_OK;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  for (void* p : {(void*)h->codes, (void*)h->rowid, (void*)h->blk_table, (void*)h->list_off, (void*)h->cb, (void*)h->coarse, (void*)h->flag,
+                  (void*)h->xraw, (void*)h->cbytes, (void*)h->lbytes, (void*)h->slots, (void*)h->tab, (void*)h->praw, (void*)h->pnorm,
+                  (void*)h->pref, (void*)h->pex, (void*)h->part, (void*)h->bits, (void*)h->oidx, (void*)h->odist})
+    (void)hipFree(p);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+  return MI_OK;
+}
+
+}  // extern "C"

@@ -315,6 +315,27 @@ void launch_pq_moved(const uint8_t* a, const uint8_t* b, int64_t bytes, unsigned
 void launch_pq_update(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const uint8_t* cols, int32_t M, int32_t Ks, int32_t L,
                       float* cb, hipStream_t stream);
 
+// ivfpq.hip -- inverted-file search over PQ codes (api_ivfpq.hip).  Blocks of 64 slots from one pool: codes [pblock][MQ][64] in
+// the PQ index's transposed form, rowid [pblock][64] the local row of a slot; list l is the chain of blocks
+// blk_table[list_off[l] .. list_off[l + 1]), of whose slots the first list_rows[l] are filled.  probes [nq][nprobe] int32 (-1 = no list), pref [nq][nprobe + 1] the prefix of block
+// counts over a query's probes; part [nq][nslab][k] sorted keys float_bits(dist) << 32 | local row (all ones = none)
+void launch_ivf_probe(const void* x, int dtype, int64_t rs, int64_t cs, int64_t nq, const float* G, int32_t nlist, int32_t d,
+                      int32_t nprobe, int32_t* out, hipStream_t stream);
+// entries outside [0, nlist) and repeats of an earlier entry -> -1 (norm is a buffer of its own), then the prefix
+void launch_ivf_prefix(const int32_t* in, int64_t nq, int32_t nlist, int32_t nprobe, const int32_t* list_off, int32_t* norm,
+                       int32_t* pref, hipStream_t stream);
+void launch_ivf_check(const uint8_t* ids, int32_t nlist, int64_t m, uint32_t* flag, hipStream_t stream);
+// code bytes [m][stride] of the rows row0 .. row0 + m -> the slots slot[r] = pblock * 64 + lane
+void launch_ivf_scatter(const uint8_t* src, int64_t stride, int32_t M, const int64_t* slot, int64_t row0, int64_t m, uint32_t* codes,
+                        uint32_t* rowid, hipStream_t stream);
+// grid (nslab, nq): nq <= 65535; a slab is 64 virtual blocks of a query; slabs beyond a query's own count write nothing; a slot
+// is admitted when it lies below its list's fill list_rows[l] and the allow bitmap, if any, has its row's bit
+void launch_ivf_scan_select(const uint32_t* codes, const uint32_t* rowid, const uint32_t* blk_table, const int32_t* list_off, int32_t M,
+                            int32_t Ks, const float* tab, const int32_t* probes, const int32_t* pref, int32_t nprobe, int32_t nq,
+                            const uint32_t* list_rows, const uint64_t* allow, int32_t k, int32_t nslab, uint64_t* part, hipStream_t stream);
+void launch_ivf_merge(const uint64_t* part, const int32_t* pref, int32_t nprobe, int64_t nq, int32_t k, int32_t nslab, int64_t row_offset,
+                      int64_t* out_idx, float* out_dist, hipStream_t stream);
+
 // synth.hip
 void launch_synth_fill(float* dst, uint64_t seed, int64_t row0, int64_t nrows, int32_t d, hipStream_t stream);
 

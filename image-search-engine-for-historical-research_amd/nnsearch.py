@@ -293,6 +293,62 @@ def matching_PQ_Net_hip(K, Codewords, Query, N_books, CW_idx):
     return idx, (time.time() - t1) / max(num_test, 1)
 
 
+def matching_PQ_Net_bucket_hip(K, Codewords, Query, N_books, CW_idx, Gallery_features, n_clusters=10, nprobe=1):
+    """Same signature and return shape as matching_PQ_Net_bucket (src/utils/nnsearch.py:949-998), plus n_clusters (the reference
+    fixes 10) and nprobe (the reference's 1): k-means buckets over Gallery_features [N, dim]; a query is answered by the ADC top-K
+    of matching_PQ_Net_hip over the rows of the nprobe buckets nearest to it -> (idx int64 [Q, K], time_per_query).  Both of the
+    reference's TODOs are closed by construction: a query whose buckets hold fewer than K rows gets trailing ids -1, and nprobe
+    selects several buckets.
+    The CLUSTERS differ from the reference's, on purpose and unpinned: the reference runs sklearn's KMeans(n_clusters,
+    random_state=0) -- k-means++ seeding from sklearn's random stream, float32 / Elkan arithmetic, several restarts -- while the
+    coarse centroids here are _lib.pq_train(Gallery_features, 1, n_clusters, seed=0): Lloyd's iteration from rows drawn by
+    RandomState(0), float64 assignment.  Which local optimum k-means reaches is a matter of initialisation, and no answer below
+    depends on it being sklearn's.  What IS exact is the search given the buckets: a row's bucket is the float64 argmin over the
+    centroids (ties to the lower bucket: the 1-book encode), a query's buckets are the nprobe smallest by (float64 distance, id),
+    and the answer is the top-K by (distance asc, id asc) of matching_PQ_Net_hip's distances over those rows
+    (include/mi355_retrieval.h, IVF index over PQ codes).  Limits as for matching_PQ_Net_hip, 2 <= n_clusters <= 256 and
+    N >= n_clusters; bad input raises ValueError before the device is touched.  It is no (K, train, test) matcher and therefore
+    not in MATCHING_METHODS.  The timer spans what the reference's spans: the bucket of every query, tables and search,
+    device-synchronised; clustering and index build lie before it, as the reference's KMeans.fit does."""
+    cw, q, codes, gal = np.asarray(Codewords), np.asarray(Query), np.asarray(CW_idx), np.asarray(Gallery_features)
+    if cw.ndim != 2 or q.ndim != 2 or codes.ndim != 2 or gal.ndim != 2 or q.shape[1] != cw.shape[1] or gal.shape[1] != cw.shape[1]:
+        raise ValueError("expected Codewords [N_words, dim], Query [Q, dim], CW_idx [N, N_books] and Gallery_features [N, dim], got "
+                         "%s, %s, %s and %s" % (cw.shape, q.shape, codes.shape, gal.shape))
+    N_books, K, n_clusters, nprobe = int(N_books), int(K), int(n_clusters), int(nprobe)
+    n_words, dim = cw.shape
+    if N_books < 1 or dim % N_books:
+        raise ValueError("dim = %d is no multiple of N_books = %d" % (dim, N_books))
+    if codes.shape[1] != N_books:
+        raise ValueError("CW_idx has %d columns, N_books = %d" % (codes.shape[1], N_books))
+    if n_words > _lib.PQ_MAX_WORDS:
+        raise ValueError("N_words = %d, a code byte holds at most %d codewords per book" % (n_words, _lib.PQ_MAX_WORDS))
+    num_train, num_test = codes.shape[0], q.shape[0]
+    if gal.shape[0] != num_train:
+        raise ValueError("Gallery_features has %d rows, CW_idx %d" % (gal.shape[0], num_train))
+    if not 2 <= n_clusters <= _lib.IVF_MAX_LISTS:
+        raise ValueError("n_clusters = %d, a list id is one byte (2 .. %d)" % (n_clusters, _lib.IVF_MAX_LISTS))
+    if not 1 <= nprobe <= n_clusters:
+        raise ValueError("nprobe = %d of n_clusters = %d" % (nprobe, n_clusters))
+    if K < 1 or K > num_train:
+        raise ValueError("K = %d, the database holds %d codes" % (K, num_train))
+    if K > TOPK_PATH_MAX_K:
+        raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
+    if not (np.issubdtype(q.dtype, np.floating) and np.isfinite(q).all()):
+        raise ValueError("Query must be a finite floating-point array")
+    if not (np.issubdtype(gal.dtype, np.floating) and np.isfinite(gal).all()):
+        raise ValueError("Gallery_features must be a finite floating-point array")
+    books = cw.reshape(n_words, N_books, dim // N_books).transpose(1, 0, 2)
+    code_rows, _ = _lib.pq_code_rows(codes, N_books, n_words)      # (raises ValueError on non-integer or out-of-range codes)
+    coarse, _ = _lib.pq_train(gal, 1, n_clusters, seed=0)
+    with _lib.PQIndex.empty(coarse, 1) as one_book:
+        labels = one_book.encode(gal)[:, 0]
+    with _lib.IVFPQIndex.from_codes(coarse[0], books, code_rows, labels) as g:
+        t1 = time.time()
+        idx, _, _ = g.search(q, K, nprobe=nprobe)
+        t2 = time.time()
+    return idx, (t2 - t1) / max(num_test, 1)
+
+
 def _l2_rows_f32(a, name):
     """The reference's normalisation (src/utils/nnsearch.py:832-835, 866-873): rows divided by their Euclidean norm in the
     array's own precision, then cast to float32."""

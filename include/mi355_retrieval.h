@@ -246,8 +246,8 @@ int mi_hamming_destroy(mi_hamming* h); /* NULL is MI_OK */
  *   order     (distance asc, id asc), ids row_offset + local row; +inf (a table entry beyond float32) is an ordinary value
  *   encoding  code[r][j] = argmin_c of the float64 sum above (before the rounding), ties to the lower c
  * No certificate, no flag, no fallback path.  The handle is a type of its own, ONE row shard on ONE device; none of the mi_gallery
- * entry points takes it.  Codebooks are learned by mi_pq_train (below).  Out of scope: ks > 256, row removal, save / load,
- * sharding, IVF, re-ranking.
+ * entry points takes it.  Codebooks are learned by mi_pq_train (below); mi_ivfpq (further below) searches such codes by inverted
+ * lists.  Out of scope: ks > 256, row removal, save / load, sharding, re-ranking.
  * mi_pq_create: n rows of `codes` (row i at codes + i * row_stride_bytes; MI_HOST or MI_DEVICE, device rows complete when the
  * call is made) into an index of `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty appendable
  * index.  A code byte >= ks is MI_ERR_INVALID (host codes are checked before a device is touched).  Synchronous. */
@@ -316,6 +316,66 @@ int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stri
  * every iteration that ran and the update of every iteration that had one; at most `capacity` values each are written, the
  * numbers that ran go to out_assignments / out_updates (may be NULL). */
 int mi_pq_train_timing(int32_t capacity, float* out_assign_ms, float* out_update_ms, int32_t* out_assignments, int32_t* out_updates);
+
+/* ---- IVF index over PQ codes: exact ADC top-K over the rows of the probed lists.  The reference's matching_PQ_Net_bucket(K,
+ * Codewords, Query, N_books, CW_idx, Gallery_features, n_clusters) (src/utils/nnsearch.py:949-998), faiss IndexIVFPQ with
+ * by_residual = false.  DESIGN.md 5.14c.  nlist lists (2 <= nlist <= 256: a list id is one byte, like a code) with coarse centroids
+ * G[nlist][d] float32, finite; codebooks, m, ks and d exactly as for mi_pq_create; fewer than 2^32 - 1 local rows.  The codes are
+ * NOT residual codes: they are what mi_pq_encode gives the whole vector, so a query's table does not depend on the list and the
+ * distance of (query, row) has the bits it has in mi_pq_search.  Given coarse centroids, codebooks, codes and the list of every
+ * row the answer is fully determined:
+ *   list      of a row the library assigns (mi_ivfpq_add): what mi_pq_encode returns on a 1-book index whose codebook is G -- the
+ *             argmin over l of the float64 sum_i (double(x[i]) - double(G[l][i]))^2 (ascending i, nothing fused), ties to the lower l
+ *   probes    of a query the library chooses: the nprobe lists smallest by (that float64 sum, l), in that order; 1 <= nprobe <=
+ *             nlist.  Explicit probes (int32 [nq][nprobe]) replace the choice: the probe set of a query is the set of its distinct
+ *             entries in [0, nlist); -1 is "no list", an entry equal to an earlier one of the same query is ignored; any other
+ *             entry is MI_ERR_INVALID on the host path (before a device is touched) and counts as -1 on the device path
+ *   answer    top-k by (distance asc, id asc) over the rows whose list is in the probe set and whose bit is set in the allow
+ *             bitmap, if one is given; table, distance and the meaning of +inf are those of mi_pq_search, ids row_offset + local
+ *             row; fewer than k such rows: trailing ids -1, distances +inf
+ * With nprobe == nlist ids and distance bits equal mi_pq_search on the same codes.  The answer does not depend on the order in
+ * which rows were appended, on how a batch is chunked or on how lists are cut into slabs.  No certificate, no flag, no fallback
+ * path.  The handle is a type of its own, ONE row shard on ONE device; no mi_gallery or mi_pq entry point takes it.  Out of scope:
+ * residual encoding, nlist > 256, grouping queries by list, row removal, save / load, sharding, re-ranking.
+ * mi_ivfpq_create: n rows of `codes` (as for mi_pq_create) with list_ids uint8 [n] in the same memspace, into an index of
+ * `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty appendable index.  A code byte >= ks or a
+ * list id >= nlist is MI_ERR_INVALID: host data is checked on the host before a device is touched, device data by a flag kernel
+ * whose flag is read before anything is ingested.  Synchronous.  An allocation that fails frees everything. */
+typedef struct mi_ivfpq mi_ivfpq; /* opaque */
+int mi_ivfpq_create(const float* coarse_host, int32_t nlist, const float* codebooks_host, int32_t d, int32_t m, int32_t ks,
+                    const void* codes, const uint8_t* list_ids, int64_t n, int64_t row_stride_bytes, int memspace, int device,
+                    int64_t row_offset, int64_t capacity, mi_ivfpq** out);
+/* rows more codes with their lists, synchronous.  Beyond the capacity, a code byte >= ks or a list id >= nlist: MI_ERR_INVALID,
+ * and the index stays as it was. */
+int mi_ivfpq_append_codes(mi_ivfpq* h, const void* codes, const uint8_t* list_ids, int64_t rows, int64_t row_stride_bytes,
+                          int memspace);
+/* Assigns rows x [rows][d] (as for mi_pq_add) to their lists, encodes them and appends.  Synchronous; the same capacity rule. */
+int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace);
+/* The probes the library chooses for nq host queries: out_lists_host [nq][nprobe] int32.  Non-finite queries: MI_ERR_INVALID. */
+int mi_ivfpq_probe(mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t nprobe,
+                   int32_t* out_lists_host);
+/* Host in, host out, synchronous.  Queries, k, allow_bits, outputs and out_seconds as for mi_pq_search; non-finite queries are
+ * MI_ERR_INVALID; nq == 0 is MI_OK.  probes_host NULL: the library chooses nprobe lists per query; otherwise int32 [nq][nprobe]
+ * as above.  The queries of a call pass in chunks that keep the partial lists ([queries][slabs of 4096 candidates][k] 8-byte
+ * keys) within the global option "pq_matrix_bytes" (one query at the least); the answer does not depend on the chunking. */
+int mi_ivfpq_search(mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                    int32_t nprobe, const int32_t* probes_host, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx,
+                    float* out_dist, double* out_seconds);
+/* Device-resident variant, enqueued on `stream` without synchronising: q_dev packed [nq][d] float32; probes_dev (may be NULL)
+ * int32 [nq][nprobe], allow_bits_dev (may be NULL) and the outputs are device buffers (out_dist_dev may be NULL).  A non-finite
+ * query leaves ITS answer unspecified (nothing is read or written out of bounds).  Buffers of the handle are used and grown as
+ * for mi_pq_search_device: calls on one handle must be serialised by the caller and enqueued on ONE stream. */
+int mi_ivfpq_search_device(mi_ivfpq* h, const float* q_dev, int64_t nq, int32_t k, int32_t nprobe, const int32_t* probes_dev,
+                           const uint64_t* allow_bits_dev, int64_t* out_idx_dev, float* out_dist_dev, void* stream);
+/* Any out pointer may be NULL.  hbm_bytes: the block pool, tables, centroids and the grow-only buffers the handle holds now. */
+int mi_ivfpq_info(const mi_ivfpq* h, int64_t* n, int32_t* d, int32_t* m, int32_t* ks, int32_t* nlist, int32_t* device,
+                  int64_t* row_offset, int64_t* capacity, int64_t* hbm_bytes);
+/* Rows per list: out [nlist] int64. */
+int mi_ivfpq_list_sizes(const mi_ivfpq* h, int64_t* out);
+/* Rows [row0, row0 + nrows) by ORIGINAL row order: out_codes_host [nrows][m] bytes, out_lists_host [nrows] bytes; either may be
+ * NULL.  Only the blocks these rows lie in are read back from the device. */
+int mi_ivfpq_get_rows(mi_ivfpq* h, int64_t row0, int64_t nrows, uint8_t* out_codes_host, uint8_t* out_lists_host);
+int mi_ivfpq_destroy(mi_ivfpq* h); /* NULL is MI_OK */
 
 /* Device-resident variant: q_dev [nq][d] row-major f32 (C order), outputs are device buffers.
  * out_score64_dev (may be NULL) receives the float64 exact scores. */
@@ -620,7 +680,8 @@ int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
  * fewer rows when fewer move, and gives up whole tiles of 256 rows so that the allocation, as the driver rounds it, stays within
  * B * (6 * d64 + 12) bytes + 4 bytes per surviving row + the bitmap + 1 MiB.
  * "hamming_matrix_bytes": upper limit of the distance matrix of a binary index (mi_hamming_search*; 0 = default, 2 GiB).
- * "pq_matrix_bytes": upper limit of the distance matrix of a PQ index (mi_pq_search*; 0 = default, 2 GiB). */
+ * "pq_matrix_bytes": upper limit of the distance matrix of a PQ index (mi_pq_search*; 0 = default, 2 GiB) and of the partial
+ * lists of an IVF-PQ index (mi_ivfpq_search*). */
 int mi_set_global_option(const char* name, double value);
 /* "release_spares" (any value) gives the spare slots back now and leaves "keep_buffers" as it is.  An allocation of the library
  * that fails with out-of-memory releases them by itself and is tried once more; a gallery of other sizes than the spare releases

@@ -21,6 +21,11 @@ assignment and the update of every iteration (mi_pq_train_timing), the move coun
 on a prefix of the same rows (`--train-host-rows`) for the upload, and scipy.cluster.vq.kmeans2 on one book of a 100 000-row
 subsample for scale -- one thread, one book.
 
+The ivf cases (`--cases ivf`, written to profiles/ivfpq_bench.json) time mi_ivfpq_search_device on 1 005 994 codes in nlist = 256
+lists whose sizes lie within 2x of each other, nq in {1, 70, 1024} x nprobe in {1, 8, 32, 256}, and in the SAME process the step
+of mi_pq_search_device on the same codes -- the exhaustive step every ratio is taken against -- beside the mean candidates per
+query.  The first child checks one case against PQIndex.search with the equivalent allow bitmap before anything is timed.
+
 Every case runs in a child process of its own under `timeout`; the driver stops at the first case that fails."""
 import argparse
 import json
@@ -34,6 +39,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "profiles", "pq_bench.json")
 TRAIN_OUT = os.path.join(ROOT, "profiles", "pq_train_bench.json")
+IVF_OUT = os.path.join(ROOT, "profiles", "ivfpq_bench.json")
+IVF_N, IVF_LISTS = 1005994, 256
 
 CLOCK, CUS = 2.4e9, 256
 HBM_ROOF = 8e12                            # bytes / s
@@ -116,6 +123,68 @@ def encode_case(_lib, torch, rows, steps):
             "note": "mi_pq_add of device rows (synchronous call between two events on the default stream)"}
 
 
+def timed_steps(torch, call, steps, warmup):
+    for _ in range(warmup):
+        call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return np.array(ms)
+
+
+def ivf_case(_lib, torch, nq, nprobe, steps, warmup, check):
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    n, nlist = IVF_N, IVF_LISTS
+    books = torch.randn((M, KS, D // M), dtype=torch.float32, device=dev, generator=gen).cpu().numpy()
+    coarse = torch.randn((nlist, D), dtype=torch.float32, device=dev, generator=gen).cpu().numpy()
+    codes = torch.randint(0, KS, (n, M), dtype=torch.uint8, device=dev, generator=gen)
+    # list sizes within 2x of each other: weights uniform in [1, 1.6), a row draws its list by weight.  The expected sizes span
+    # at most 1.6x, and a list of some 3 000 rows strays from its expectation by about 2 % (one standard deviation)
+    w = 1.0 + 0.6 * torch.rand(nlist, device=dev, generator=gen)
+    lists = torch.multinomial(w, n, replacement=True, generator=gen).to(torch.uint8)
+    q = torch.randn((nq, D), dtype=torch.float32, device=dev, generator=gen)
+    torch.cuda.synchronize()
+    flat = _lib.PQIndex.from_device_ptr(books, codes.data_ptr(), n)
+    ivf = _lib.IVFPQIndex.from_device_ptr(coarse, books, codes.data_ptr(), lists.data_ptr(), n)
+    sizes = ivf.list_sizes()
+    assert sizes.max() < 2 * sizes.min(), (sizes.min(), sizes.max())
+    probes = ivf.probe(q.cpu().numpy(), nprobe)
+    if check:                                                           # before anything is timed
+        qs = q[:min(nq, 4)].cpu().numpy()
+        host_lists = lists.cpu().numpy()
+        for i in range(qs.shape[0]):
+            a = ivf.search(qs[i:i + 1], K, nprobe=nprobe)[:2]
+            b = flat.search(qs[i:i + 1], K, allow=np.isin(host_lists, probes[i]))[:2]
+            if not (np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))):
+                raise SystemExit("ivf answer differs from PQIndex.search under the equivalent allow bitmap: nothing is timed")
+    out_i = torch.empty((nq, K), dtype=torch.int64, device=dev)
+    out_d = torch.empty((nq, K), dtype=torch.float32, device=dev)
+    s = torch.cuda.current_stream().cuda_stream
+    ms = timed_steps(torch, lambda: ivf.search_device(q.data_ptr(), nq, K, out_i.data_ptr(), out_d.data_ptr(), nprobe=nprobe, stream=s),
+                     steps, warmup)
+    ex = timed_steps(torch, lambda: flat.search_device(q.data_ptr(), nq, K, out_i.data_ptr(), out_d.data_ptr(), stream=s), steps, warmup)
+    med, exmed = float(np.median(ms)), float(np.median(ex))
+    rec = {"case": "ivf", "n": n, "m": M, "ks": KS, "d": D, "nlist": nlist, "list_rows_min": int(sizes.min()),
+           "list_rows_max": int(sizes.max()), "queries": nq, "nprobe": nprobe, "k": K, "steps": steps, "warmup": warmup,
+           "candidates_per_query_mean": float(sizes[probes].sum(1).mean()), "checked_against_pq_search": bool(check),
+           "ms_per_batch_median": med, "ms_per_batch_min": float(ms.min()), "ms_per_batch_max": float(ms.max()),
+           "exhaustive_ms_median": exmed, "exhaustive_ms_min": float(ex.min()), "exhaustive_ms_max": float(ex.max()),
+           "exhaustive_over_ivf": exmed / med, "queries_per_s": nq / (med * 1e-3), "hbm_bytes_index": ivf.hbm_bytes,
+           "note": "step = one mi_ivfpq_search_device call (probe, prefix, table, scan + select, merge per chunk of queries); "
+                   "exhaustive = one mi_pq_search_device call on the same codes in the same process"}
+    ivf.close()
+    flat.close()
+    return rec
+
+
 def train_case(_lib, torch, rows, iters, host_rows):
     import time
     dev = torch.device("cuda", 0)
@@ -178,6 +247,8 @@ def run_child(args):
     kind, *rest = args.child.split(":")
     if kind == "search":
         rec = search_case(_lib, torch, int(rest[0]), int(rest[1]), args.steps, args.warmup)
+    elif kind == "ivf":
+        rec = ivf_case(_lib, torch, int(rest[0]), int(rest[1]), args.steps, args.warmup, rest[2] == "1")
     elif kind == "train":
         rec = train_case(_lib, torch, int(rest[0]), args.train_iters, min(args.train_host_rows, int(rest[0])))
     else:
@@ -189,7 +260,8 @@ def run_child(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="1m,10m,encode", help="comma list of: 1m / 10m (1 005 994 / 10^7 codes at 1, 70 and 1024 "
-                                                              "queries), 1m-<Q> / 10m-<Q> (one batch size), encode, train")
+                                                              "queries), 1m-<Q> / 10m-<Q> (one batch size), encode, train, ivf, "
+                                                              "ivf-<Q>-<nprobe>")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--encode-rows", type=int, default=1005994)
@@ -197,6 +269,7 @@ def main():
     ap.add_argument("--train-iters", type=int, default=20)
     ap.add_argument("--train-host-rows", type=int, default=250000, help="rows of the host variant (0 = skip it)")
     ap.add_argument("--train-out", default=TRAIN_OUT)
+    ap.add_argument("--ivf-out", default=IVF_OUT)
     ap.add_argument("--case-timeout", type=int, default=240, help="seconds each child process may take")
     ap.add_argument("--out", default=OUT)
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
@@ -214,6 +287,12 @@ def main():
             children.append("encode:%d" % args.encode_rows)
         elif c == "train":
             children.append("train:%d" % args.train_rows)
+        elif c == "ivf":
+            # the first ivf child of a run checks its case against PQIndex.search before anything is timed
+            children += ["ivf:%d:%d:%d" % (nq, nprobe, not any(ch.startswith("ivf:") for ch in children) and (nq, nprobe) == (1, 1))
+                         for nq in (1, 70, 1024) for nprobe in (1, 8, 32, 256)]
+        elif c.startswith("ivf-"):
+            children.append("ivf:%d:%d:1" % tuple(int(v) for v in c.split("-")[1:3]))
         else:
             raise SystemExit("unknown case " + c)
     results = []
@@ -229,7 +308,11 @@ def main():
         results.append(json.loads(line[0][len("PQBENCH "):]))
         print(json.dumps(results[-1]), flush=True)
     trained = [r for r in results if r["case"] == "train"]
-    results = [r for r in results if r["case"] != "train"]
+    inverted = [r for r in results if r["case"] == "ivf"]
+    results = [r for r in results if r["case"] not in ("train", "ivf")]
+    if inverted:
+        os.makedirs(os.path.dirname(args.ivf_out), exist_ok=True)
+        json.dump({"cases": inverted}, open(args.ivf_out, "w"), indent=1)
     if trained:
         os.makedirs(os.path.dirname(args.train_out), exist_ok=True)
         json.dump({"hbm_roof_bytes_per_s": HBM_ROOF, "f64_valu_instructions_per_s": F64_VALU, "cases": trained},
