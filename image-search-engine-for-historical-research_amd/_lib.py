@@ -109,6 +109,13 @@ SIGNATURES = {
     "mi_pq_train_timing": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mi_ivfpq_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "mi_ivfpq_create_residual": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
+    "mi_ivfpq_is_residual": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "mi_ivfpq_residual_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_int]),
+    "mi_ivfpq_search_stages_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "mi_ivfpq_append_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
     "mi_ivfpq_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int]),
     "mi_ivfpq_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
@@ -1299,12 +1306,25 @@ def ivf_list_ids(lists, rows, nlist):
 
 class IVFPQIndex:
     """IVF index over PQ codes on one MI355X (a `mi_ivfpq` handle): the exact ADC top-k of PQIndex.search over the rows whose
-    list is one of a query's probed lists, by (distance asc, id asc)."""
+    list is one of a query's probed lists, by (distance asc, id asc).  by_residual=True at creation gives faiss's IndexIVFPQ
+    default: a code quantizes double(x) - double(coarse[list]) and a query has one float64-summed table per probed list; the kind
+    is fixed for the life of the index.
+    Beyond the C handle, and kept on purpose: every index made by from_codes / from_device_ptr / empty / fit (either kind)
+    carries `.coarse` [nlist, d] and `.codebooks` [M, Ks, L], float32 copies of the arrays it was created with -- the handle has no
+    getter for them, and knn.ANN's callers and the tests need them to restate an answer; and `train()` is the training half of
+    fit() as a classmethod of its own, which knn.ANN uses to train on a sample and add all rows."""
 
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
         self._lock = threading.Lock()
         self._info()
+        kind = C.c_int32()
+        check(load().mi_ivfpq_is_residual(self._h, C.byref(kind)))
+        self._residual = bool(kind.value)
+
+    @property
+    def by_residual(self):
+        return self._residual
 
     def _info(self):
         n, cap, off, hb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
@@ -1315,56 +1335,90 @@ class IVFPQIndex:
         return hb.value
 
     @classmethod
-    def _create(cls, g, cb, codes_ptr, lists_ptr, n, stride, memspace, device, row_offset, capacity):
+    def _create(cls, g, cb, codes_ptr, lists_ptr, n, stride, memspace, device, row_offset, capacity, by_residual=False):
         m, ks, L = cb.shape
         h = C.c_void_p()
-        check(load().mi_ivfpq_create(C.c_void_p(g.ctypes.data), g.shape[0], C.c_void_p(cb.ctypes.data), m * L, m, ks, C.c_void_p(codes_ptr),
-                                     C.c_void_p(lists_ptr), int(n), int(stride), memspace, device, int(row_offset), int(capacity),
-                                     C.byref(h)))
-        return cls(h.value)
+        create = load().mi_ivfpq_create_residual if by_residual else load().mi_ivfpq_create
+        check(create(C.c_void_p(g.ctypes.data), g.shape[0], C.c_void_p(cb.ctypes.data), m * L, m, ks, C.c_void_p(codes_ptr),
+                     C.c_void_p(lists_ptr), int(n), int(stride), memspace, device, int(row_offset), int(capacity), C.byref(h)))
+        idx = cls(h.value)
+        idx.coarse, idx.codebooks = g.copy(), cb.copy()
+        return idx
 
     @classmethod
-    def from_codes(cls, coarse, codebooks, codes, lists, device=0, row_offset=0, capacity=0):
+    def from_codes(cls, coarse, codebooks, codes, lists, device=0, row_offset=0, capacity=0, by_residual=False):
         """coarse [nlist, d] float32, codebooks [M, Ks, L] float32, codes integer [N, M] in [0, Ks), lists integer [N] in
-        [0, nlist); capacity 0 = N, larger leaves room for append_codes() / add()."""
+        [0, nlist); capacity 0 = N, larger leaves room for append_codes() / add().  by_residual=True: the codes are residual codes."""
         cb = pq_codebooks(codebooks)
         g = ivf_coarse(coarse, cb.shape[0] * cb.shape[2])
         a, stride = pq_code_rows(codes, cb.shape[0], cb.shape[1])
         li = ivf_list_ids(lists, a.shape[0], g.shape[0])
         if capacity and capacity < a.shape[0]:
             raise ValueError("capacity %d below the %d rows given" % (capacity, a.shape[0]))
-        return cls._create(g, cb, a.ctypes.data, li.ctypes.data, a.shape[0], stride, MI_HOST, device, row_offset, capacity)
+        return cls._create(g, cb, a.ctypes.data, li.ctypes.data, a.shape[0], stride, MI_HOST, device, row_offset, capacity, by_residual)
 
     @classmethod
-    def from_device_ptr(cls, coarse, codebooks, codes_ptr, lists_ptr, n, device=0, row_offset=0, capacity=0, row_stride_bytes=None):
+    def from_device_ptr(cls, coarse, codebooks, codes_ptr, lists_ptr, n, device=0, row_offset=0, capacity=0, row_stride_bytes=None,
+                        by_residual=False):
         """Device codes [n][M] uint8 and list ids [n] uint8 -> index, synchronous; their producer must have completed."""
         cb = pq_codebooks(codebooks)
         g = ivf_coarse(coarse, cb.shape[0] * cb.shape[2])
         return cls._create(g, cb, codes_ptr, lists_ptr, n, cb.shape[0] if row_stride_bytes is None else row_stride_bytes, MI_DEVICE,
-                           device, row_offset, capacity)
+                           device, row_offset, capacity, by_residual)
 
     @classmethod
-    def empty(cls, coarse, codebooks, capacity, device=0, row_offset=0):
+    def empty(cls, coarse, codebooks, capacity, device=0, row_offset=0, by_residual=False):
         """Appendable index: `capacity` rows allocated, filled by append_codes() / add()."""
         cb = pq_codebooks(codebooks)
         g = ivf_coarse(coarse, cb.shape[0] * cb.shape[2])
         if int(capacity) < 1:
             raise ValueError("an empty index needs a capacity")
-        return cls._create(g, cb, None, None, 0, cb.shape[0], MI_HOST, device, row_offset, capacity)
+        return cls._create(g, cb, None, None, 0, cb.shape[0], MI_HOST, device, row_offset, capacity, by_residual)
 
     @classmethod
-    def fit(cls, x, nlist, M, Ks, iters=20, seed=42, capacity=0, device=0, row_offset=0):
+    def train(cls, x, nlist, M, Ks, iters=20, seed=42, device=0, by_residual=False):
+        """The training of fit() without the index: -> (coarse float32 [nlist, d], codebooks float32 [M, Ks, L], coarse_moved,
+        train_moved).  The coarse centroids are pq_train with ONE book of nlist codewords.  by_residual=False: the codebooks are
+        pq_train on x.  by_residual=True: the rows are assigned to their lists, the float32 residual rows
+        float32(double(x) - double(coarse[list])) are formed on the device and pq_train_device runs on them, with the seed rule
+        of pq_train (initial rows drawn by RandomState(seed), taken from the residual rows; seed=None: the library's default)."""
+        nlist = int(nlist)
+        if not 2 <= nlist <= IVF_MAX_LISTS:
+            raise ValueError("nlist = %d lists, an IVF-PQ index takes 2 .. %d (one byte per row)" % (nlist, IVF_MAX_LISTS))
+        if by_residual:                                  # the limits of the second training, before the first touches the device
+            n, d = np.shape(x)
+            M, Ks, iters = int(M), int(Ks), int(iters)
+            L = _pq_train_shape(n, d, M, Ks, iters)
+        g, gmoved = pq_train(x, 1, nlist, iters=iters, seed=seed, device=device)
+        if not by_residual:
+            cb, moved = pq_train(x, M, Ks, iters=iters, seed=seed, device=device)
+            return g[0], cb, gmoved, moved
+        import torch
+        res = torch.empty((n, d), dtype=torch.float32, device="cuda:%d" % device)
+        with cls.empty(g[0], np.zeros((M, Ks, L), np.float32), 1, device=device) as tmp:      # the centroids are all it is used for
+            tmp.residual_rows_device(x, res.data_ptr())
+        cb0 = None
+        if seed is not None:
+            rng = np.random.RandomState(seed)
+            rows = np.stack([rng.choice(n, Ks, replace=False) for _ in range(M)])
+            picked = res[torch.as_tensor(rows.reshape(-1), device=res.device)].cpu().numpy().reshape(M, Ks, d)
+            cb0 = np.ascontiguousarray(np.stack([picked[j, :, j * L:(j + 1) * L] for j in range(M)]), dtype=np.float32)
+        cb, moved = pq_train_device(res.data_ptr(), n, d, M, Ks, iters, init=cb0, device=device)
+        return g[0], cb, gmoved, moved
+
+    @classmethod
+    def fit(cls, x, nlist, M, Ks, iters=20, seed=42, capacity=0, device=0, row_offset=0, by_residual=False):
         """Learns the coarse centroids (pq_train with ONE book of nlist codewords) and the codebooks (pq_train) on x [n, d], both
-        with `seed`, creates the index and adds x.  The move counts are in `.coarse_moved` and `.train_moved`."""
+        with `seed`, creates the index and adds x.  by_residual=True: the codebooks are learned on the residual rows (train()) and
+        the index is a residual index.  The move counts are in `.coarse_moved` and `.train_moved`."""
         nlist = int(nlist)
         if not 2 <= nlist <= IVF_MAX_LISTS:
             raise ValueError("nlist = %d lists, an IVF-PQ index takes 2 .. %d (one byte per row)" % (nlist, IVF_MAX_LISTS))
         n = np.shape(x)[0]
         if capacity and capacity < n:
             raise ValueError("capacity %d below the %d rows given" % (capacity, n))
-        g, gmoved = pq_train(x, 1, nlist, iters=iters, seed=seed, device=device)
-        cb, moved = pq_train(x, M, Ks, iters=iters, seed=seed, device=device)
-        idx = cls.empty(g[0], cb, capacity or n, device=device, row_offset=row_offset)
+        g, cb, gmoved, moved = cls.train(x, nlist, M, Ks, iters=iters, seed=seed, device=device, by_residual=by_residual)
+        idx = cls.empty(g, cb, capacity or n, device=device, row_offset=row_offset, by_residual=by_residual)
         idx.coarse_moved, idx.train_moved = gmoved, moved
         idx.add(x)
         return idx
@@ -1412,6 +1466,29 @@ class IVFPQIndex:
             check(load().mi_ivfpq_add(self._h, C.c_void_p(x_ptr), int(rows), dtype, self.d if row_stride is None else int(row_stride),
                                       int(col_stride), MI_DEVICE))
             self.n += int(rows)
+
+    def _lists(self, lists, rows):
+        return None if lists is None else ivf_list_ids(lists, rows, self.nlist)
+
+    def residual_rows(self, x, lists=None):
+        """-> float32 [rows, d]: float32(double(x) - double(coarse[l])), one rounding, computed on the device; l is lists[row]
+        (integer [rows] in [0, nlist)) or, with lists None, the list the index assigns.  Either kind of index; it is unchanged."""
+        a, code, rs, cs = self._rows(x)
+        li = self._lists(lists, a.shape[0])
+        out = np.empty((a.shape[0], self.d), dtype=np.float32)
+        with self._lock:
+            check(load().mi_ivfpq_residual_rows(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST,
+                                                None if li is None else C.c_void_p(li.ctypes.data), out.ctypes.data_as(C.c_void_p),
+                                                MI_HOST))
+        return out
+
+    def residual_rows_device(self, x, out_ptr, lists=None):
+        """residual_rows of host rows into a device buffer float32 [rows][d] at out_ptr; synchronous."""
+        a, code, rs, cs = self._rows(x)
+        li = self._lists(lists, a.shape[0])
+        with self._lock:
+            check(load().mi_ivfpq_residual_rows(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST,
+                                                None if li is None else C.c_void_p(li.ctypes.data), C.c_void_p(int(out_ptr)), MI_DEVICE))
 
     def probe(self, q, nprobe=1):
         """-> int32 [Q, nprobe]: per query the nprobe lists nearest in float64, nearest first, ties to the lower list."""
@@ -1463,6 +1540,14 @@ class IVFPQIndex:
         [0, nlist) count as -1); enqueued on `stream`, no synchronisation."""
         check(load().mi_ivfpq_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), int(nprobe), C.c_void_p(probes_ptr),
                                             C.c_void_p(allow_ptr), C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def search_stages_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, nprobe=1, stream=None):
+        """search_device with the library's probes, measured: -> (table_ms, scan_ms), HIP-event times of the table kernel and of the
+        scan-and-select summed over the chunks of the batch.  Synchronous; for benchmarks."""
+        t, u = C.c_float(), C.c_float()
+        check(load().mi_ivfpq_search_stages_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), int(nprobe), C.c_void_p(idx_ptr),
+                                                   C.c_void_p(dist_ptr), C.c_void_p(stream), C.byref(t), C.byref(u)))
+        return t.value, u.value
 
     def list_sizes(self):
         out = np.empty(self.nlist, dtype=np.int64)

@@ -4,12 +4,16 @@
 // (the next free slot of its list; a new block from the pool when the tail is full) and keeps, per list, its block numbers and,
 // per row, its slot and list; after every create / append / add it uploads the flattened block table and list_off.  The answer
 // is a function of the inputs alone: the exact ADC top-K of mi_pq_search over the rows whose list is probed.
+// A RESIDUAL index (mi_ivfpq_create_residual; kernels in csrc/ivfpq_residual.hip) is faiss's by_residual = true: the
+// same handle, lists and blocks, but a code quantizes double(x) - double(G[list]) and a query has one table per probed list.  The
+// kind is fixed at creation; `tab` then holds [queries of a chunk][nprobe][m][ks].
 #include "api_internal.h"
 
 struct mi_ivfpq {
   int device = 0;
   int64_t n = 0, cap = 0, row_offset = 0;
   int32_t d = 0, m = 0, ks = 0, L = 0, MQ = 0, nlist = 0;
+  bool residual = false;                           // codes quantize the residual against the row's list
   std::vector<float> cb_host, coarse_host;         // [m][ks][L], [nlist][d]
   float *cb = nullptr, *coarse = nullptr;
   int64_t pool_blocks = 0, pool_used = 0;          // ceil(cap / 64) + nlist: every list may end in a partly filled block
@@ -27,7 +31,7 @@ struct mi_ivfpq {
   char* xraw = nullptr;                            // rows / queries of a host call, packed [rows][d] in their own type
   uint8_t *cbytes = nullptr, *lbytes = nullptr;    // packed code bytes [rows][m] and list ids [rows] on their way in
   int64_t* slots = nullptr;
-  float* tab = nullptr;                            // [queries of a chunk][m][ks]
+  float* tab = nullptr;                            // [queries of a chunk][m][ks]; residual: [queries of a chunk][nprobe][m][ks]
   int32_t *praw = nullptr, *pnorm = nullptr, *pref = nullptr, *pex = nullptr;   // probes: chosen, normalised, prefix; a host call's own
   uint64_t* part = nullptr;                        // [queries of a chunk][slabs][k]
   uint64_t* bits = nullptr;
@@ -211,29 +215,65 @@ static int64_t ivf_slab_bound(const mi_ivfpq* h, int32_t nprobe) {
 
 // the search proper on stream s: queries on the device (any strides), probes_dev NULL or [nq][nprobe], results to device buffers
 static int ivf_search_core(mi_ivfpq* h, const void* q_dev, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k, int32_t nprobe,
-                           const int32_t* probes_dev, const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s) {
+                           const int32_t* probes_dev, const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s,
+                           float* stage_ms = nullptr) {
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   const int64_t nslab = ivf_slab_bound(h, nprobe);
   const int64_t per = (int64_t)h->m * h->ks;
-  // queries per pass: the partial lists within the budget, the tables within 256 MiB, the grid's y below 65536; one at the least
+  // queries per pass: the partial lists within the budget, the tables within 256 MiB, the grid's y below 65536; one at the least.
+  // A residual index has nprobe tables per query and keeps tables + partial lists within the budget
   const int64_t budget = g_pq_matrix_bytes.load();
-  int64_t qc = std::min<int64_t>({nq, 65535, budget / std::max<int64_t>(1, nslab * k * 8), ((int64_t)256 << 20) / (per * 4)});
+  const int64_t tabs = h->residual ? per * nprobe : per;
+  int64_t qc = h->residual ? std::min<int64_t>({nq, 65535, budget / (nslab * k * 8 + tabs * 4)})
+                           : std::min<int64_t>({nq, 65535, budget / std::max<int64_t>(1, nslab * k * 8), ((int64_t)256 << 20) / (per * 4)});
   qc = std::max<int64_t>(1, qc);
   int rc;
-  if ((rc = ivf_grow(&h->tab, &h->tab_cap, (size_t)(qc * per))) != MI_OK) return rc;
+  if ((rc = ivf_grow(&h->tab, &h->tab_cap, (size_t)(qc * tabs))) != MI_OK) return rc;
   if ((rc = ivf_grow(&h->praw, &h->praw_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
   if ((rc = ivf_grow(&h->pnorm, &h->pnorm_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
   if ((rc = ivf_grow(&h->pref, &h->pref_cap, (size_t)(qc * (nprobe + 1)))) != MI_OK) return rc;
   if ((rc = ivf_grow(&h->part, &h->part_cap, (size_t)(qc * nslab * k))) != MI_OK) return rc;
+  // stage_ms (mi_ivfpq_search_stages_device): HIP events around the table and the scan of every chunk, read after each chunk
+  // the guard destroys them on every way out of this function
+  struct StageEvents {
+    hipEvent_t e[3] = {nullptr, nullptr, nullptr};
+    ~StageEvents() {
+      for (hipEvent_t x : e)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } guard;
+  hipEvent_t* ev = guard.e;
+  if (stage_ms) {
+    stage_ms[0] = stage_ms[1] = 0.0f;
+    for (int i = 0; i < 3; ++i) HIPC(hipEventCreate(&ev[i]));
+  }
   for (int64_t q0 = 0; q0 < nq; q0 += qc) {
     const int32_t b = (int32_t)std::min<int64_t>(qc, nq - q0);
     const char* qp = (const char*)q_dev + (size_t)q0 * rs * esz;
     const int32_t* in = probes_dev ? probes_dev + q0 * nprobe : h->praw;
     if (!probes_dev) launch_ivf_probe(qp, dtype, rs, cs, b, h->coarse, h->nlist, h->d, nprobe, h->praw, s);
     launch_ivf_prefix(in, b, h->nlist, nprobe, h->list_off, h->pnorm, h->pref, s);
-    launch_pq_table(qp, dtype, rs, cs, b, h->cb, h->m, h->ks, h->L, h->tab, s);
-    launch_ivf_scan_select(h->codes, h->rowid, h->blk_table, h->list_off, h->m, h->ks, h->tab, h->pnorm, h->pref, nprobe, b, h->list_rows,
-                           allow_dev, k, (int32_t)nslab, h->part, s);
+    if (stage_ms) HIPC(hipEventRecord(ev[0], s));
+    if (h->residual) {
+      launch_ivfr_table(qp, dtype, rs, cs, b, h->coarse, h->d, h->cb, h->m, h->ks, h->L, h->pnorm, nprobe, h->tab, s);
+      if (stage_ms) HIPC(hipEventRecord(ev[1], s));
+      launch_ivfr_scan_select(h->codes, h->rowid, h->blk_table, h->list_off, h->m, h->ks, h->tab, h->pnorm, h->pref, nprobe, b, h->list_rows,
+                              allow_dev, k, (int32_t)nslab, h->part, s);
+    } else {
+      launch_pq_table(qp, dtype, rs, cs, b, h->cb, h->m, h->ks, h->L, h->tab, s);
+      if (stage_ms) HIPC(hipEventRecord(ev[1], s));
+      launch_ivf_scan_select(h->codes, h->rowid, h->blk_table, h->list_off, h->m, h->ks, h->tab, h->pnorm, h->pref, nprobe, b, h->list_rows,
+                             allow_dev, k, (int32_t)nslab, h->part, s);
+    }
+    if (stage_ms) {
+      float t = 0.0f, u = 0.0f;
+      HIPC(hipEventRecord(ev[2], s));
+      HIPC(hipEventSynchronize(ev[2]));
+      HIPC(hipEventElapsedTime(&t, ev[0], ev[1]));
+      HIPC(hipEventElapsedTime(&u, ev[1], ev[2]));
+      stage_ms[0] += t;
+      stage_ms[1] += u;
+    }
     launch_ivf_merge(h->part, h->pref, nprobe, b, k, (int32_t)nslab, h->row_offset, out_idx_dev + q0 * k,
                      out_dist_dev ? out_dist_dev + q0 * k : nullptr, s);
   }
@@ -256,11 +296,10 @@ static int ivf_check_host_queries(const mi_ivfpq* h, const void* q, int64_t nq, 
   REQUIRE((rs) >= 0 && (cs) >= 0, "negative strides are not supported");                                     \
   REQUIRE((memspace) == MI_HOST || (memspace) == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE")
 
-extern "C" {
-
-int mi_ivfpq_create(const float* coarse_host, int32_t nlist, const float* codebooks_host, int32_t d, int32_t m, int32_t ks, const void* codes,
-                    const uint8_t* list_ids, int64_t n, int64_t row_stride_bytes, int memspace, int device, int64_t row_offset,
-                    int64_t capacity, mi_ivfpq** out) {
+// mi_ivfpq_create and mi_ivfpq_create_residual: one body, the kind is the only difference
+static int ivf_create(bool residual, const float* coarse_host, int32_t nlist, const float* codebooks_host, int32_t d, int32_t m, int32_t ks,
+                      const void* codes, const uint8_t* list_ids, int64_t n, int64_t row_stride_bytes, int memspace, int device,
+                      int64_t row_offset, int64_t capacity, mi_ivfpq** out) {
   REQUIRE(out, "null pointer: out");
   REQUIRE(coarse_host, "null pointer: coarse_host");
   REQUIRE(codebooks_host, "null pointer: codebooks_host");
@@ -295,6 +334,7 @@ int mi_ivfpq_create(const float* coarse_host, int32_t nlist, const float* codebo
   h->L = d / m;
   h->MQ = (m + 3) / 4;
   h->nlist = nlist;
+  h->residual = residual;
   h->cb_host.assign(codebooks_host, codebooks_host + cb_count);
   h->coarse_host.assign(coarse_host, coarse_host + co_count);
   h->blocks.resize((size_t)nlist);
@@ -332,6 +372,29 @@ int mi_ivfpq_create(const float* coarse_host, int32_t nlist, const float* codebo
   return MI_OK;
 }
 
+extern "C" {
+
+int mi_ivfpq_create(const float* coarse_host, int32_t nlist, const float* codebooks_host, int32_t d, int32_t m, int32_t ks, const void* codes,
+                    const uint8_t* list_ids, int64_t n, int64_t row_stride_bytes, int memspace, int device, int64_t row_offset,
+                    int64_t capacity, mi_ivfpq** out) {
+  return ivf_create(false, coarse_host, nlist, codebooks_host, d, m, ks, codes, list_ids, n, row_stride_bytes, memspace, device, row_offset,
+                    capacity, out);
+}
+
+int mi_ivfpq_create_residual(const float* coarse_host, int32_t nlist, const float* codebooks_host, int32_t d, int32_t m, int32_t ks,
+                             const void* codes, const uint8_t* list_ids, int64_t n, int64_t row_stride_bytes, int memspace, int device,
+                             int64_t row_offset, int64_t capacity, mi_ivfpq** out) {
+  return ivf_create(true, coarse_host, nlist, codebooks_host, d, m, ks, codes, list_ids, n, row_stride_bytes, memspace, device, row_offset,
+                    capacity, out);
+}
+
+int mi_ivfpq_is_residual(const mi_ivfpq* h, int32_t* out) {
+  REQUIRE(h, "null handle");
+  REQUIRE(out, "null pointer: out");
+  *out = h->residual ? 1 : 0;
+  return MI_OK;
+}
+
 int mi_ivfpq_append_codes(mi_ivfpq* h, const void* codes, const uint8_t* list_ids, int64_t rows, int64_t row_stride_bytes, int memspace) {
   REQUIRE(h, "null handle");
   REQUIRE(rows >= 0, "negative number of rows");
@@ -362,7 +425,8 @@ int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t ro
   std::vector<char> pack;
   std::vector<uint8_t> lists;
   std::vector<int64_t> slots;
-  // a block of rows: its codes (the encoder on the codebooks) and its lists (the encoder on ONE book, the coarse centroids)
+  // a block of rows: its codes (the encoder on the codebooks) and its lists (the encoder on ONE book, the coarse centroids); on a
+  // residual index the lists come first and the codes are those of the residual against them
   auto block = [&](int64_t r, int64_t mm) -> int {
     int rc;
     const void* xp = (const char*)x + (size_t)r * row_stride * esz;
@@ -373,8 +437,9 @@ int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t ro
       rs = h->d;
       cs = 1;
     }
-    launch_pq_encode(xp, dtype, rs, cs, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
+    if (!h->residual) launch_pq_encode(xp, dtype, rs, cs, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
     launch_pq_encode(xp, dtype, rs, cs, mm, h->coarse, 1, h->nlist, h->d, h->lbytes, s);
+    if (h->residual) launch_ivfr_encode(xp, dtype, rs, cs, mm, h->coarse, h->d, h->lbytes, h->cb, h->m, h->ks, h->L, h->cbytes, s);
     HIPC(hipGetLastError());
     lists.resize((size_t)mm);
     HIPC(hipMemcpyAsync(lists.data(), h->lbytes, (size_t)mm, hipMemcpyDeviceToHost, s));
@@ -390,6 +455,59 @@ int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t ro
     return rc;
   }
   h->n = mk.n + rows;
+  return MI_OK;
+}
+
+int mi_ivfpq_residual_rows(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace,
+                           const uint8_t* list_ids, float* out, int out_memspace) {
+  REQUIRE(h, "null handle");
+  REQUIRE_ROWS(x, rows, dtype, row_stride, col_stride, memspace);
+  REQUIRE(out || rows == 0, "null pointer: out");
+  REQUIRE(out_memspace == MI_HOST || out_memspace == MI_DEVICE, "out_memspace must be MI_HOST or MI_DEVICE");
+  if (rows == 0) return MI_OK;
+  REQUIRE(!list_ids || memspace != MI_HOST || ivf_bytes_below(list_ids, rows, 1, 1, h->nlist), "a list id is >= nlist");
+  std::lock_guard<std::mutex> lock(h->mu);
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  if (list_ids && memspace == MI_DEVICE && h->nlist < 256) {
+    uint32_t f = 0;
+    launch_ivf_check(list_ids, h->nlist, rows, h->flag, s);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(&f, h->flag, 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    if (f) {
+      HIPC(hipMemsetAsync(h->flag, 0, 4, s));
+      HIPC(hipStreamSynchronize(s));
+      return fail(MI_ERR_INVALID, "a list id is >= nlist");
+    }
+  }
+  const size_t esz = dtype == MI_F32 ? 4 : 8;
+  const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * 8));
+  const int64_t most = std::min(step, rows);
+  int rc;
+  if ((rc = ivf_grow(&h->lbytes, &h->lbytes_cap, (size_t)most)) != MI_OK) return rc;
+  if (out_memspace == MI_HOST && (rc = ivf_grow(&h->odist, &h->odist_cap, (size_t)(most * h->d))) != MI_OK) return rc;
+  std::vector<char> pack;
+  for (int64_t r = 0; r < rows; r += step) {
+    const int64_t mm = std::min(step, rows - r);
+    const void* xp = (const char*)x + (size_t)r * row_stride * esz;
+    int64_t rs = row_stride, cs = col_stride;
+    if (memspace == MI_HOST) {
+      if ((rc = ivf_stage_rows(h, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+      xp = h->xraw;
+      rs = h->d;
+      cs = 1;
+    }
+    const uint8_t* lp = h->lbytes;
+    if (!list_ids) launch_pq_encode(xp, dtype, rs, cs, mm, h->coarse, 1, h->nlist, h->d, h->lbytes, s);
+    else if (memspace == MI_HOST) HIPC(hipMemcpyAsync(h->lbytes, list_ids + r, (size_t)mm, hipMemcpyHostToDevice, s));
+    else lp = list_ids + r;
+    float* dst = out_memspace == MI_DEVICE ? out + r * h->d : h->odist;
+    launch_ivfr_rows(xp, dtype, rs, cs, mm, h->coarse, h->d, lp, dst, s);
+    HIPC(hipGetLastError());
+    if (out_memspace == MI_HOST) HIPC(hipMemcpyAsync(out + r * h->d, h->odist, (size_t)(mm * h->d) * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+  }
   return MI_OK;
 }
 
@@ -484,6 +602,27 @@ int mi_ivfpq_search_device(mi_ivfpq* h, const float* q_dev, int64_t nq, int32_t 
   if (nq == 0) return MI_OK;
   HIPC(hipSetDevice(h->device));
   return ivf_search_core(h, q_dev, MI_F32, h->d, 1, nq, k, nprobe, probes_dev, allow_bits_dev, out_idx_dev, out_dist_dev, (hipStream_t)stream);
+}
+
+int mi_ivfpq_search_stages_device(mi_ivfpq* h, const float* q_dev, int64_t nq, int32_t k, int32_t nprobe, int64_t* out_idx_dev,
+                                  float* out_dist_dev, void* stream, float* out_table_ms, float* out_scan_ms) {
+  REQUIRE(h, "null handle");
+  REQUIRE(k >= 1 && k <= 2048, "k must be in [1, 2048]");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  REQUIRE(nprobe >= 1 && nprobe <= 256, "nprobe must be in [1, nlist]");
+  REQUIRE(nq == 0 || (q_dev && out_idx_dev), "null pointer");
+  REQUIRE(out_table_ms && out_scan_ms, "null pointer: out_table_ms / out_scan_ms");
+  REQUIRE(nprobe <= h->nlist, "nprobe must be in [1, nlist]");
+  float ms[2] = {0.0f, 0.0f};
+  *out_table_ms = *out_scan_ms = 0.0f;
+  if (nq == 0) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  const int rc = ivf_search_core(h, q_dev, MI_F32, h->d, 1, nq, k, nprobe, nullptr, nullptr, out_idx_dev, out_dist_dev, (hipStream_t)stream, ms);
+  if (rc != MI_OK) return rc;
+  HIPC(hipStreamSynchronize((hipStream_t)stream));
+  *out_table_ms = ms[0];
+  *out_scan_ms = ms[1];
+  return MI_OK;
 }
 
 int mi_ivfpq_info(const mi_ivfpq* h, int64_t* n, int32_t* d, int32_t* m, int32_t* ks, int32_t* nlist, int32_t* device, int64_t* row_offset,

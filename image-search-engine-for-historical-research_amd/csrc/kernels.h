@@ -336,6 +336,22 @@ void launch_ivf_scan_select(const uint32_t* codes, const uint32_t* rowid, const 
 void launch_ivf_merge(const uint64_t* part, const int32_t* pref, int32_t nprobe, int64_t nq, int32_t k, int32_t nslab, int64_t row_offset,
                       int64_t* out_idx, float* out_dist, hipStream_t stream);
 
+// ivfpq_residual.hip -- residual codes on the same layout (api_ivfpq.hip): a code quantizes double(x) - double(G[list]), a query has
+// one table per probe slot.  probes: the NORMALISED probes of launch_ivf_prefix; tab [nq][nprobe][M][Ks] f32, the tables of -1 slots
+// are neither written nor read.  Prefix and merge are ivfpq.hip's
+void launch_ivfr_table(const void* x, int dtype, int64_t rs, int64_t cs, int32_t nq, const float* G, int32_t d, const float* cb, int32_t M,
+                       int32_t Ks, int32_t L, const int32_t* probes, int32_t nprobe, float* tab, hipStream_t stream);
+// the grid, the slabs and the partial lists of launch_ivf_scan_select
+void launch_ivfr_scan_select(const uint32_t* codes, const uint32_t* rowid, const uint32_t* blk_table, const int32_t* list_off, int32_t M,
+                             int32_t Ks, const float* tab, const int32_t* probes, const int32_t* pref, int32_t nprobe, int32_t nq,
+                             const uint32_t* list_rows, const uint64_t* allow, int32_t k, int32_t nslab, uint64_t* part, hipStream_t stream);
+// lists [n] bytes (device), every one < nlist; packed code bytes out [n][M]
+void launch_ivfr_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* G, int32_t d, const uint8_t* lists,
+                        const float* cb, int32_t M, int32_t Ks, int32_t L, uint8_t* out, hipStream_t stream);
+// out [n][d] packed f32 = float(double(x) - double(G[list]))
+void launch_ivfr_rows(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* G, int32_t d, const uint8_t* lists, float* out,
+                      hipStream_t stream);
+
 // synth.hip
 void launch_synth_fill(float* dst, uint64_t seed, int64_t row0, int64_t nrows, int32_t d, hipStream_t stream);
 

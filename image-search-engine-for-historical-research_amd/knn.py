@@ -16,10 +16,16 @@ IndexFlatL2.search -- through a squared-L2 gallery (Gallery.l2_from_host); ties 
 `hamming` is faiss.IndexBinaryFlat: exact top-k Hamming distances of packed binary codes (_lib.pack_bits: bit j of a code is
 bit j & 7 of byte j >> 3), ascending -- the return of IndexBinaryFlat.search -- through a binary index (_lib.BinaryGallery);
 ties go to the lower id.  Removal, radius search, save / load and sharding are not built for binary indexes.
+
+    ANN(database[N,D], 'euclidean', M=64, nbits=8, nlist=256, nprobe=64).search(queries[Q,D], k)
+        -> (squared ADC distances float32 [Q,k] ascending, ids int64 [Q,k])
+
+the counterpart of the reference's approximate wrapper (src/utils/knn.py:43-53, faiss.IndexIVFPQ with its defaults, so
+by_residual = true) on a residual _lib.IVFPQIndex.
 """
 import numpy as np
 
-from ._lib import BinaryGallery, Gallery, NORM_NONE
+from ._lib import BinaryGallery, Gallery, IVFPQIndex, IVF_MAX_LISTS, NORM_NONE, PQ_MAX_BOOKS
 
 
 class KNN:
@@ -90,3 +96,70 @@ class KNN:
 
     def close(self):
         self.gallery.close()
+
+
+def _unit_rows(a):
+    a = np.asarray(a, dtype=np.float32)
+    norm = np.sqrt((a.astype(np.float64) ** 2).sum(1, keepdims=True))
+    return (a / np.maximum(norm, np.finfo(np.float64).tiny)).astype(np.float32)
+
+
+class ANN:
+    """The reference's ANN (src/utils/knn.py:43-53: faiss.IndexIVFPQ(quantizer, D, nlist, M, nbits), trained on a fifth of the
+    rows, nprobe set after the add) on a residual IVFPQIndex.
+
+    LIMITS: the index takes M <= 64 books, nlist <= 256 lists and nbits == 8 only; anything else raises ValueError.  The
+    reference's own defaults, M = 128 and nlist = 316, lie OUTSIDE these limits, which is why the defaults here are M = 64 and
+    nlist = 256.  D must be a multiple of M and N // 5 >= max(256, nlist).
+
+    It trains on the N // 5 rows RandomState(seed).permutation(N)[:N // 5] (IVFPQIndex.train(by_residual=True) with `seed`), then
+    adds all rows.  The clusters and codebooks are this library's deterministic k-means, NOT faiss's, on purpose: nothing pins them
+    to faiss.  What is exact is the search given them: the residual contract of the index, top-k by (distance asc, id asc).
+    'cosine' L2-normalises the database and the queries first, so that the squared distance orders like the inner product; the
+    values returned are still squared distances, ascending.  Diffusion does not use this class: the exact search is faster
+    there."""
+
+    def __init__(self, database, method="euclidean", M=64, nbits=8, nlist=256, nprobe=64, seed=0, device=0):
+        if method not in ("cosine", "euclidean"):
+            raise NotImplementedError("method must be 'cosine' or 'euclidean', got %r" % (method,))
+        M, nbits, nlist, nprobe = int(M), int(nbits), int(nlist), int(nprobe)
+        if not 1 <= M <= PQ_MAX_BOOKS:
+            raise ValueError("M = %d books, the IVF-PQ index takes 1 .. %d (the reference's default of 128 is outside)" % (M, PQ_MAX_BOOKS))
+        if nbits != 8:
+            raise ValueError("nbits = %d, the IVF-PQ index takes nbits = 8 only (one byte per book)" % nbits)
+        if not 2 <= nlist <= IVF_MAX_LISTS:
+            raise ValueError("nlist = %d lists, the IVF-PQ index takes 2 .. %d (the reference's default of 316 is outside)"
+                             % (nlist, IVF_MAX_LISTS))
+        if not 1 <= nprobe <= nlist:
+            raise ValueError("nprobe = %d, the index has nlist = %d lists (1 .. nlist)" % (nprobe, nlist))
+        database = np.asarray(database)
+        if database.ndim != 2:
+            raise ValueError("database must be [N, D]")
+        if database.dtype != np.float32:          # src/utils/knn.py:10-11
+            database = database.astype(np.float32)
+        self.method, self.nprobe = method, nprobe
+        self.N, self.D = database.shape
+        if self.D % M:
+            raise ValueError("D = %d is no multiple of M = %d" % (self.D, M))
+        if self.N // 5 < max(1 << nbits, nlist):
+            raise ValueError("N // 5 = %d training rows, %d codewords and %d lists need at least as many" % (self.N // 5, 1 << nbits, nlist))
+        if method == "cosine":
+            database = _unit_rows(database)
+        samples = database[np.random.RandomState(seed).permutation(self.N)[:self.N // 5]]
+        g, cb, _, _ = IVFPQIndex.train(samples, nlist, M, 1 << nbits, seed=seed, device=device, by_residual=True)
+        self.index = IVFPQIndex.empty(g, cb, self.N, device=device, by_residual=True)
+        self.index.add(database)
+
+    def search(self, queries, k):
+        """-> (squared distances float32 [Q,k] ascending, ids int64 [Q,k]); fewer than k rows in the probed lists: ids -1,
+        distances +inf."""
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            queries = queries.astype(np.float32)
+        if self.method == "cosine":
+            queries = _unit_rows(queries)
+        ids, dist, _ = self.index.search(queries, int(k), nprobe=self.nprobe)
+        return dist, ids
+
+    def close(self):
+        self.index.close()

@@ -336,7 +336,8 @@ int mi_pq_train_timing(int32_t capacity, float* out_assign_ms, float* out_update
  * With nprobe == nlist ids and distance bits equal mi_pq_search on the same codes.  The answer does not depend on the order in
  * which rows were appended, on how a batch is chunked or on how lists are cut into slabs.  No certificate, no flag, no fallback
  * path.  The handle is a type of its own, ONE row shard on ONE device; no mi_gallery or mi_pq entry point takes it.  Out of scope:
- * residual encoding, nlist > 256, grouping queries by list, row removal, save / load, sharding, re-ranking.
+ * nlist > 256, grouping queries by list, row removal, save / load, sharding, re-ranking.  Residual codes: mi_ivfpq_create_residual
+ * (below).
  * mi_ivfpq_create: n rows of `codes` (as for mi_pq_create) with list_ids uint8 [n] in the same memspace, into an index of
  * `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty appendable index.  A code byte >= ks or a
  * list id >= nlist is MI_ERR_INVALID: host data is checked on the host before a device is touched, device data by a flag kernel
@@ -376,6 +377,40 @@ int mi_ivfpq_list_sizes(const mi_ivfpq* h, int64_t* out);
  * NULL.  Only the blocks these rows lie in are read back from the device. */
 int mi_ivfpq_get_rows(mi_ivfpq* h, int64_t row0, int64_t nrows, uint8_t* out_codes_host, uint8_t* out_lists_host);
 int mi_ivfpq_destroy(mi_ivfpq* h); /* NULL is MI_OK */
+
+/* ---- Residual IVF-PQ index: faiss IndexIVFPQ with by_residual = true (its default), the reference's ANN (src/utils/knn.py:43-53).
+ * DESIGN.md 5.14d.  The same handle, limits, lists, probes and entry points; an index is residual or not for its whole life.  A
+ * row's code quantizes its residual against the centroid of its list, and the arithmetic is the specification:
+ *   residual  of a vector x (float32 or float64) against list l: r[j] = double(x[j]) - double(G[l][j]), ONE float64 subtraction per
+ *             component, never rounded to float32 on the search or the encode path
+ *   table     T[q][l][b][c] = float32(sum_j (r[b L + j] - double(C[b][c][j]))^2) for every probed list l of query q: ascending j, a
+ *             separate float64 subtract, multiply and add per term (nothing fused), rounded once
+ *   distance  of (query q, row i of list l): the float32 sum of T[q][l][b][code_i[b]] in ascending book order from +0.0f
+ *   encoding  mi_ivfpq_add assigns the list as on any index; code byte b is then the argmin over c of that float64 sum taken of the
+ *             row's own residual, ties to the lower c.  mi_ivfpq_append_codes and the codes given at creation ARE residual codes
+ *             and are stored as given
+ *   answer    as above: top-k by (distance asc, id asc) over the rows whose list is in the probe set and whose allow bit is set;
+ *             independent of the order of appends, of the chunking of a batch and of how lists are cut into slabs
+ * With every centroid zero the answer equals, bit for bit, that of a non-residual index over the same codes and lists.  The queries
+ * of a call pass in chunks that keep the tables ([queries][nprobe][m][ks] float32) AND the partial lists within "pq_matrix_bytes"
+ * (one query at the least).  mi_ivfpq_probe, _list_sizes, _get_rows, _info and _destroy do not depend on the kind.
+ * mi_ivfpq_create_residual: the parameters, checks and error order of mi_ivfpq_create. */
+int mi_ivfpq_create_residual(const float* coarse_host, int32_t nlist, const float* codebooks_host, int32_t d, int32_t m, int32_t ks,
+                             const void* codes, const uint8_t* list_ids, int64_t n, int64_t row_stride_bytes, int memspace,
+                             int device, int64_t row_offset, int64_t capacity, mi_ivfpq** out);
+/* *out = 1 on a residual index, 0 otherwise. */
+int mi_ivfpq_is_residual(const mi_ivfpq* h, int32_t* out);
+/* out [rows][d] packed float32 = float32(double(x) - double(G[l])), one rounding: what codebook training consumes.  x as for
+ * mi_ivfpq_add; l is list_ids[row] (uint8 [rows] in x's memspace; an id >= nlist is MI_ERR_INVALID) or, with list_ids NULL, the
+ * list the library assigns.  out is a host or a device buffer (out_memspace).  Either kind of index; the index is unchanged.
+ * Synchronous. */
+int mi_ivfpq_residual_rows(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace,
+                           const uint8_t* list_ids, float* out, int out_memspace);
+/* A measuring variant of mi_ivfpq_search_device (library probes, no bitmap; either kind of index): the same launches and the same
+ * answer, with HIP events around the table kernel and around the scan-and-select of every chunk of queries; the sums over the
+ * chunks, in milliseconds, go to *out_table_ms and *out_scan_ms.  It waits for every chunk: for benchmarks, not for serving. */
+int mi_ivfpq_search_stages_device(mi_ivfpq* h, const float* q_dev, int64_t nq, int32_t k, int32_t nprobe, int64_t* out_idx_dev,
+                                  float* out_dist_dev, void* stream, float* out_table_ms, float* out_scan_ms);
 
 /* Device-resident variant: q_dev [nq][d] row-major f32 (C order), outputs are device buffers.
  * out_score64_dev (may be NULL) receives the float64 exact scores. */

@@ -26,6 +26,12 @@ lists whose sizes lie within 2x of each other, nq in {1, 70, 1024} x nprobe in {
 of mi_pq_search_device on the same codes -- the exhaustive step every ratio is taken against -- beside the mean candidates per
 query.  The first child checks one case against PQIndex.search with the equivalent allow bitmap before anything is timed.
 
+The ivf_residual cases (`--cases ivf_residual`, written to profiles/ivfpq_residual_bench.json) run the shapes of the ivf cases on
+a RESIDUAL index over the same codes and lists (mi_ivfpq_create_residual): the step of mi_ivfpq_search_device, in the SAME process
+the step of the non-residual index, and the table kernel and the scan-and-select apart (HIP events of
+mi_ivfpq_search_stages_device), with the table kernel's share of the float64 vector rate: 3 instructions per (table entry, column).
+The first child checks, before anything is timed, that a residual index with zero centroids answers bit for bit as the plain one.
+
 Every case runs in a child process of its own under `timeout`; the driver stops at the first case that fails."""
 import argparse
 import json
@@ -40,6 +46,7 @@ sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "profiles", "pq_bench.json")
 TRAIN_OUT = os.path.join(ROOT, "profiles", "pq_train_bench.json")
 IVF_OUT = os.path.join(ROOT, "profiles", "ivfpq_bench.json")
+IVF_RES_OUT = os.path.join(ROOT, "profiles", "ivfpq_residual_bench.json")
 IVF_N, IVF_LISTS = 1005994, 256
 
 CLOCK, CUS = 2.4e9, 256
@@ -185,6 +192,67 @@ def ivf_case(_lib, torch, nq, nprobe, steps, warmup, check):
     return rec
 
 
+def ivf_residual_case(_lib, torch, nq, nprobe, steps, warmup, check):
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)
+    n, nlist = IVF_N, IVF_LISTS
+    books = torch.randn((M, KS, D // M), dtype=torch.float32, device=dev, generator=gen).cpu().numpy()
+    coarse = torch.randn((nlist, D), dtype=torch.float32, device=dev, generator=gen).cpu().numpy()
+    codes = torch.randint(0, KS, (n, M), dtype=torch.uint8, device=dev, generator=gen)
+    w = 1.0 + 0.6 * torch.rand(nlist, device=dev, generator=gen)          # the lists of ivf_case
+    lists = torch.multinomial(w, n, replacement=True, generator=gen).to(torch.uint8)
+    q = torch.randn((nq, D), dtype=torch.float32, device=dev, generator=gen)
+    torch.cuda.synchronize()
+    plain = _lib.IVFPQIndex.from_device_ptr(coarse, books, codes.data_ptr(), lists.data_ptr(), n)
+    res = _lib.IVFPQIndex.from_device_ptr(coarse, books, codes.data_ptr(), lists.data_ptr(), n, by_residual=True)
+    sizes = res.list_sizes()
+    probes = res.probe(q.cpu().numpy(), nprobe)
+    if check:                                                           # before anything is timed
+        # with every centroid zero a residual index answers, bit for bit, as a plain one over the same codes and lists: the
+        # probes of the real centroids, given explicitly to both
+        zero = np.zeros_like(coarse)
+        qs = q[:min(nq, 4)].cpu().numpy()
+        with _lib.IVFPQIndex.from_device_ptr(zero, books, codes.data_ptr(), lists.data_ptr(), n, by_residual=True) as rz, \
+                _lib.IVFPQIndex.from_device_ptr(zero, books, codes.data_ptr(), lists.data_ptr(), n) as pz:
+            a = rz.search(qs, K, probes=probes[:qs.shape[0]])[:2]
+            b = pz.search(qs, K, probes=probes[:qs.shape[0]])[:2]
+        if not (np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)) and (a[0] >= 0).all()):
+            raise SystemExit("the residual index with zero centroids differs from the plain index: nothing is timed")
+    out_i, out_d = (torch.empty((nq, K), dtype=torch.int64, device=dev), torch.empty((nq, K), dtype=torch.float32, device=dev))
+    pout_i, pout_d = torch.empty_like(out_i), torch.empty_like(out_d)    # the plain index writes into buffers of its own
+    s = torch.cuda.current_stream().cuda_stream
+    ms = timed_steps(torch, lambda: res.search_device(q.data_ptr(), nq, K, out_i.data_ptr(), out_d.data_ptr(), nprobe=nprobe, stream=s),
+                     steps, warmup)
+    pl = timed_steps(torch, lambda: plain.search_device(q.data_ptr(), nq, K, pout_i.data_ptr(), pout_d.data_ptr(), nprobe=nprobe, stream=s),
+                     steps, warmup)
+    ref_i, ref_d, pref_i, pref_d = out_i.clone(), out_d.clone(), pout_i.clone(), pout_d.clone()
+    stages = np.array([res.search_stages_device(q.data_ptr(), nq, K, out_i.data_ptr(), out_d.data_ptr(), nprobe=nprobe, stream=s)
+                       for _ in range(steps)])
+    pstages = np.array([plain.search_stages_device(q.data_ptr(), nq, K, pout_i.data_ptr(), pout_d.data_ptr(), nprobe=nprobe, stream=s)
+                        for _ in range(steps)])
+    torch.cuda.synchronize()
+    if not (torch.equal(ref_i, out_i) and torch.equal(ref_d.view(torch.int32), out_d.view(torch.int32)) and
+            torch.equal(pref_i, pout_i) and torch.equal(pref_d.view(torch.int32), pout_d.view(torch.int32))):
+        raise SystemExit("the measured variant answers differently from mi_ivfpq_search_device")
+    med, plmed = float(np.median(ms)), float(np.median(pl))
+    table_ms, scan_ms = (float(v) for v in np.median(stages, axis=0))
+    f64_instructions = 3.0 * nq * nprobe * KS * D
+    rec = {"case": "ivf_residual", "n": n, "m": M, "ks": KS, "d": D, "nlist": nlist, "queries": nq, "nprobe": nprobe, "k": K,
+           "steps": steps, "warmup": warmup, "checked_against_plain_index_at_zero_centroids": bool(check), "candidates_per_query_mean": float(sizes[probes].sum(1).mean()),
+           "ms_per_batch_median": med, "ms_per_batch_min": float(ms.min()), "ms_per_batch_max": float(ms.max()),
+           "plain_ms_median": plmed, "plain_ms_min": float(pl.min()), "plain_ms_max": float(pl.max()), "residual_over_plain": med / plmed,
+           "table_ms_median": table_ms, "scan_ms_median": scan_ms, "plain_table_ms_median": float(np.median(pstages[:, 0])),
+           "plain_scan_ms_median": float(np.median(pstages[:, 1])), "table_f64_instructions": f64_instructions,
+           "table_fraction_of_f64_vector_rate": f64_instructions / (table_ms * 1e-3) / F64_VALU,
+           "queries_per_s": nq / (med * 1e-3), "hbm_bytes_index": res.hbm_bytes,
+           "note": "step = one mi_ivfpq_search_device call on the residual index; plain = the non-residual index over the same codes "
+                   "and lists in the same process; table / scan = HIP events of mi_ivfpq_search_stages_device, summed over the chunks"}
+    res.close()
+    plain.close()
+    return rec
+
+
 def train_case(_lib, torch, rows, iters, host_rows):
     import time
     dev = torch.device("cuda", 0)
@@ -249,6 +317,8 @@ def run_child(args):
         rec = search_case(_lib, torch, int(rest[0]), int(rest[1]), args.steps, args.warmup)
     elif kind == "ivf":
         rec = ivf_case(_lib, torch, int(rest[0]), int(rest[1]), args.steps, args.warmup, rest[2] == "1")
+    elif kind == "ivfres":
+        rec = ivf_residual_case(_lib, torch, int(rest[0]), int(rest[1]), args.steps, args.warmup, rest[2] == "1")
     elif kind == "train":
         rec = train_case(_lib, torch, int(rest[0]), args.train_iters, min(args.train_host_rows, int(rest[0])))
     else:
@@ -261,7 +331,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="1m,10m,encode", help="comma list of: 1m / 10m (1 005 994 / 10^7 codes at 1, 70 and 1024 "
                                                               "queries), 1m-<Q> / 10m-<Q> (one batch size), encode, train, ivf, "
-                                                              "ivf-<Q>-<nprobe>")
+                                                              "ivf-<Q>-<nprobe>, ivf_residual, ivf_residual-<Q>-<nprobe>")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--encode-rows", type=int, default=1005994)
@@ -270,6 +340,7 @@ def main():
     ap.add_argument("--train-host-rows", type=int, default=250000, help="rows of the host variant (0 = skip it)")
     ap.add_argument("--train-out", default=TRAIN_OUT)
     ap.add_argument("--ivf-out", default=IVF_OUT)
+    ap.add_argument("--ivf-residual-out", default=IVF_RES_OUT)
     ap.add_argument("--case-timeout", type=int, default=240, help="seconds each child process may take")
     ap.add_argument("--out", default=OUT)
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
@@ -291,6 +362,11 @@ def main():
             # the first ivf child of a run checks its case against PQIndex.search before anything is timed
             children += ["ivf:%d:%d:%d" % (nq, nprobe, not any(ch.startswith("ivf:") for ch in children) and (nq, nprobe) == (1, 1))
                          for nq in (1, 70, 1024) for nprobe in (1, 8, 32, 256)]
+        elif c == "ivf_residual":
+            # the first child checks the residual index against the plain one at zero centroids before anything is timed
+            children += ["ivfres:%d:%d:%d" % (nq, nprobe, (nq, nprobe) == (1, 1)) for nq in (1, 70, 1024) for nprobe in (1, 8, 32, 256)]
+        elif c.startswith("ivf_residual-"):
+            children.append("ivfres:%d:%d:1" % tuple(int(v) for v in c.split("-")[1:3]))
         elif c.startswith("ivf-"):
             children.append("ivf:%d:%d:1" % tuple(int(v) for v in c.split("-")[1:3]))
         else:
@@ -309,7 +385,11 @@ def main():
         print(json.dumps(results[-1]), flush=True)
     trained = [r for r in results if r["case"] == "train"]
     inverted = [r for r in results if r["case"] == "ivf"]
-    results = [r for r in results if r["case"] not in ("train", "ivf")]
+    residual = [r for r in results if r["case"] == "ivf_residual"]
+    results = [r for r in results if r["case"] not in ("train", "ivf", "ivf_residual")]
+    if residual:
+        os.makedirs(os.path.dirname(args.ivf_residual_out), exist_ok=True)
+        json.dump({"f64_valu_instructions_per_s": F64_VALU, "cases": residual}, open(args.ivf_residual_out, "w"), indent=1)
     if inverted:
         os.makedirs(os.path.dirname(args.ivf_out), exist_ok=True)
         json.dump({"cases": inverted}, open(args.ivf_out, "w"), indent=1)
