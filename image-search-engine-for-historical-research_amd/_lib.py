@@ -103,6 +103,7 @@ SIGNATURES = {
                              C.POINTER(C.c_int32), c_i64p, c_i64p, c_i64p]),
     "mi_pq_get_codes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "mi_pq_get_codebooks": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_pq_remove_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64p]),
     "mi_pq_destroy": (C.c_int, [C.c_void_p]),
     "mi_pq_train": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_f64p]),
@@ -127,6 +128,7 @@ SIGNATURES = {
                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i64p, c_i64p, c_i64p]),
     "mi_ivfpq_list_sizes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi_ivfpq_get_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mi_ivfpq_remove_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64p]),
     "mi_ivfpq_destroy": (C.c_int, [C.c_void_p]),
     "mi_knn_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p]),
@@ -1106,6 +1108,22 @@ def pq_train_timing():
     return a[:na.value], u[:nu.value]
 
 
+def _remove_rows(index, name, rows):
+    """Gallery.remove for a PQIndex / IVFPQIndex: the bitmap of `rows`, the call `name` of the library, `kept`, index.n."""
+    bits = allow_bitmap(rows, index.n, index.row_offset)
+    gone = np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), bitorder="little")[:index.n].astype(np.bool_)
+    kept = np.flatnonzero(~gone).astype(np.int64) + int(index.row_offset)
+    if bits.size == 0:
+        bits = np.zeros(1, "<u8")                               # an empty index: the library wants a pointer all the same
+    removed = C.c_int64()
+    with index._lock:
+        check(getattr(load(), name)(index._h, C.c_void_p(bits.ctypes.data), MI_HOST, C.byref(removed)))
+        if index.n - removed.value != kept.size:
+            raise RuntimeError("%s removed %d rows, the bitmap names %d" % (name, removed.value, index.n - kept.size))
+        index.n = int(kept.size)
+    return kept
+
+
 class PQIndex:
     """PQ index on one MI355X (a `mi_pq` handle): exact ADC top-k on product-quantized codes by (distance asc, id asc)."""
 
@@ -1246,6 +1264,14 @@ class PQIndex:
         """q_ptr: packed float32 [nq][d] on the device; enqueued on `stream`, no synchronisation."""
         check(load().mi_pq_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(allow_ptr), C.c_void_p(idx_ptr),
                                          C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def remove(self, rows):
+        """Removes rows in place (mi_pq_remove_rows; faiss IndexPQ.remove_ids): `rows` is anything allow_bitmap takes -- a bool
+        mask [n] over the shard's rows, an array of GLOBAL ids (duplicates are fine), or packed AllowBits words.  The survivors
+        keep their order and their code bytes and are renumbered from row_offset on; the capacity stays.  -> kept int64 [n']:
+        kept[j] is the old global id of new row j.  Raises ValueError, before the library is called, on an id outside
+        [row_offset, row_offset + n)."""
+        return _remove_rows(self, "mi_pq_remove_rows", rows)
 
     def get_codes(self, row0=0, nrows=None):
         nrows = self.n - row0 if nrows is None else int(nrows)
@@ -1553,6 +1579,12 @@ class IVFPQIndex:
         out = np.empty(self.nlist, dtype=np.int64)
         check(load().mi_ivfpq_list_sizes(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def remove(self, rows):
+        """Removes rows in place (mi_ivfpq_remove_rows; faiss IndexIVFPQ.remove_ids), either kind of index: arguments, return
+        value and errors of PQIndex.remove.  A survivor stays in its list; the blocks the lists no longer reach are reused by
+        later appends."""
+        return _remove_rows(self, "mi_ivfpq_remove_rows", rows)
 
     def get_rows(self, row0=0, nrows=None):
         """-> (codes uint8 [nrows, M], lists uint8 [nrows]) of the rows row0 .. row0 + nrows in the order they were given."""

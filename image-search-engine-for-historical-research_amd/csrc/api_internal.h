@@ -16,6 +16,7 @@
 //   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
 //   api_pq_train.hip  learning PQ codebooks (mi_pq_train): deterministic Lloyd iterations on device-resident rows
 //   api_ivfpq.hip     IVF index over PQ codes (mi_ivfpq): coarse lists as chains of 64-slot blocks, exact ADC top-K over the probed lists
+//                     (row removal of both PQ handles: mi_pq_remove_rows in api_pq.hip, mi_ivfpq_remove_rows here; kernels in pq_remove.hip)
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -66,6 +67,7 @@ extern MI_INTERNAL SpareArena g_spare_ws;
 extern MI_INTERNAL std::atomic<int> g_keep_buffers;
 extern MI_INTERNAL std::atomic<int64_t> g_scatter_block_rows;   // mi_scatter_matrix: rows per host block (0 = 64 MiB)
 extern MI_INTERNAL std::atomic<int64_t> g_remove_block_rows;    // mi_gallery_remove_rows: rows of the staging area (0 = default)
+extern MI_INTERNAL std::atomic<int64_t> g_pq_remove_block_rows; // mi_pq_remove_rows: rows of the staging area (default 2 097 152)
 extern MI_INTERNAL std::atomic<int64_t> g_hamming_matrix_bytes; // mi_hamming_search*: bytes of the distance matrix (default 2 GiB)
 extern MI_INTERNAL std::atomic<int64_t> g_pq_matrix_bytes;      // mi_pq_search*: bytes of the distance matrix (default 2 GiB); mi_ivfpq_search*: of the partial lists
 constexpr size_t SPARE_MAX_BYTES = (size_t)16 << 30;
@@ -85,6 +87,17 @@ MI_INTERNAL const char* last_error_message();
   do {                     \
     if (!(cond)) return fail(MI_ERR_INVALID, msg); \
   } while (0)
+
+
+// The host half of a row removal on a PQ or an IVF-PQ index (mi_pq_remove_rows, mi_ivfpq_remove_rows; defined in api_pq.hip): the
+// caller's bitmap of the rows that leave (host or device, ceil(n / 64) words, bits at or beyond n ignored) -> the bitmap of the
+// rows that STAY and the exclusive count of its bits per word, which is what the kernels of pq_remove.hip renumber by
+struct RemovePlan {
+  std::vector<uint64_t> keep;      // [ceil(n / 64)], bits at or beyond n clear
+  std::vector<uint32_t> prefix;    // [ceil(n / 64) + 1], prefix.back() = n' = n - removed
+  int64_t removed = 0, first = -1; // rows that leave; the lowest of them
+};
+MI_INTERNAL int remove_plan(const uint64_t* remove_bits, int memspace, int64_t n, RemovePlan* plan);
 
 
 constexpr int QB = 1024;  // queries per batch (workspace size)

@@ -17,6 +17,7 @@ struct mi_ivfpq {
   std::vector<float> cb_host, coarse_host;         // [m][ks][L], [nlist][d]
   float *cb = nullptr, *coarse = nullptr;
   int64_t pool_blocks = 0, pool_used = 0;          // ceil(cap / 64) + nlist: every list may end in a partly filled block
+  std::vector<uint32_t> free_blocks;               // blocks below pool_used that a removal emptied: taken first, last in first out
   uint32_t* codes = nullptr;                       // [pool_blocks][MQ][64]
   uint32_t* rowid = nullptr;                       // [pool_blocks][64]
   uint32_t* blk_table = nullptr;                   // [pool_blocks]: the blocks of list 0, of list 1, ...
@@ -35,8 +36,10 @@ struct mi_ivfpq {
   int32_t *praw = nullptr, *pnorm = nullptr, *pref = nullptr, *pex = nullptr;   // probes: chosen, normalised, prefix; a host call's own
   uint64_t* part = nullptr;                        // [queries of a chunk][slabs][k]
   uint64_t* bits = nullptr;
+  uint32_t* rmpref = nullptr;                      // mi_ivfpq_remove_rows: prefix counts per bitmap word
   int64_t* oidx = nullptr;
   float* odist = nullptr;
+  size_t rmpref_cap = 0;
   size_t xraw_cap = 0, cbytes_cap = 0, lbytes_cap = 0, slots_cap = 0, tab_cap = 0, praw_cap = 0, pnorm_cap = 0, pref_cap = 0, pex_cap = 0,
          part_cap = 0, bits_cap = 0, oidx_cap = 0, odist_cap = 0;
   std::mutex mu;
@@ -57,7 +60,7 @@ static int ivf_grow(T** p, size_t* cap, size_t count) {
 static int64_t ivf_scratch_bytes(const mi_ivfpq* h) {
   return (int64_t)(h->xraw_cap + h->cbytes_cap + h->lbytes_cap + h->slots_cap * 8 + h->tab_cap * 4 +
                    (h->praw_cap + h->pnorm_cap + h->pref_cap + h->pex_cap) * 4 + h->part_cap * 8 + h->bits_cap * 8 + h->oidx_cap * 8 +
-                   h->odist_cap * 4);
+                   h->odist_cap * 4 + h->rmpref_cap * 4);
 }
 
 static bool ivf_bytes_below(const uint8_t* p, int64_t rows, int64_t stride, int32_t m, int32_t limit) {
@@ -92,24 +95,33 @@ static int ivf_stage_rows(mi_ivfpq* h, const void* x, int64_t r0, int64_t rows, 
 struct IvfMark {
   int64_t n, pool_used;
   std::vector<int64_t> list_size;
+  std::vector<uint32_t> free_blocks;
 };
 
-static IvfMark ivf_mark(const mi_ivfpq* h) { return {h->n, h->pool_used, h->list_size}; }
+static IvfMark ivf_mark(const mi_ivfpq* h) { return {h->n, h->pool_used, h->list_size, h->free_blocks}; }
 
+// the blocks the failed call took, from the free list or from the end of the pool, go back where they came from: the chains are
+// cut to the marked fills below, so none of them is in a chain any more
 static void ivf_rollback(mi_ivfpq* h, const IvfMark& mk) {
   h->pool_used = mk.pool_used;
+  h->free_blocks = mk.free_blocks;
   h->list_size = mk.list_size;
   for (int32_t l = 0; l < h->nlist; ++l) h->blocks[l].resize((size_t)((mk.list_size[l] + 63) / 64));
   h->slot_of_row.resize((size_t)mk.n);
   h->list_of_row.resize((size_t)mk.n);
 }
 
-// the slots of `rows` more rows with the given lists, in row order
+// the slots of `rows` more rows with the given lists, in row order.  A new block is one a removal emptied, if there is one, else
+// the next of the pool: the pool grows only while every block below pool_used is in a chain, and the chains hold
+// sum ceil(list_size / 64) <= n / 64 + nlist blocks, so pool_used stays within pool_blocks after any removals and appends
 static void ivf_place(mi_ivfpq* h, const uint8_t* lists, int64_t rows, int64_t* slots) {
   for (int64_t r = 0; r < rows; ++r) {
     const int32_t l = lists[r];
     const int64_t fill = h->list_size[l]++;
-    if ((fill & 63) == 0) h->blocks[l].push_back((uint32_t)h->pool_used++);
+    if ((fill & 63) == 0) {
+      if (h->free_blocks.empty()) h->blocks[l].push_back((uint32_t)h->pool_used++);
+      else h->blocks[l].push_back(h->free_blocks.back()), h->free_blocks.pop_back();
+    }
     slots[r] = (int64_t)h->blocks[l].back() * 64 + (fill & 63);
     h->slot_of_row.push_back(slots[r]);
     h->list_of_row.push_back((uint8_t)l);
@@ -139,6 +151,8 @@ static int ivf_scatter_rows(mi_ivfpq* h, const uint8_t* src_dev, int64_t stride,
   int rc;
   slots.resize((size_t)rows);
   ivf_place(h, lists_host, rows, slots.data());
+  // cannot happen while ivf_place's bound holds; a slot beyond the pool must never reach the scatter
+  REQUIRE(h->pool_used <= h->pool_blocks, "internal: the block pool is exhausted");
   if ((rc = ivf_grow(&h->slots, &h->slots_cap, (size_t)rows)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(h->slots, slots.data(), (size_t)rows * 8, hipMemcpyHostToDevice, h->stream));
   launch_ivf_scatter(src_dev, stride, h->m, h->slots, row0, rows, h->codes, h->rowid, h->stream);
@@ -683,13 +697,68 @@ int mi_ivfpq_get_rows(mi_ivfpq* h, int64_t row0, int64_t nrows, uint8_t* out_cod
   return MI_OK;
 }
 
+// Row removal in place (faiss IndexIVFPQ.remove_ids), either kind of index: every chain is compacted where it
+// lies by one workgroup (pq_remove.hip), a survivor stays in its list and keeps its code bytes, its row id becomes its new local
+// row.  The host then rebuilds its mirror the way the device moved the rows -- ascending row id, one counter per list, which is
+// the order of a chain because appends fill a chain in row order and the renumbering is monotone -- hands the blocks the chains
+// no longer reach to the free list, and publishes the tables.  Device memory beyond the index: the bitmap and 4 bytes per
+// bitmap word, grow-only on the handle, allocated before anything moves.
+int mi_ivfpq_remove_rows(mi_ivfpq* h, const uint64_t* remove_bits, int memspace, int64_t* out_removed) {
+  REQUIRE(h, "null handle");
+  REQUIRE(remove_bits, "null pointer: remove_bits");
+  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
+  if (out_removed) *out_removed = 0;
+  std::lock_guard<std::mutex> lock(h->mu);
+  const int64_t n = h->n;
+  if (n == 0) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  HIPC(hipStreamSynchronize(s));
+  RemovePlan plan;
+  int rc;
+  if ((rc = remove_plan(remove_bits, memspace, n, &plan)) != MI_OK) return rc;
+  if (plan.removed == 0) return MI_OK;                        // nothing changes
+  const int64_t m = n - plan.removed;                         // n'
+  const int64_t nwords = (n + 63) / 64;
+  if ((rc = ivf_grow(&h->bits, &h->bits_cap, (size_t)nwords)) != MI_OK) return rc;
+  if ((rc = ivf_grow(&h->rmpref, &h->rmpref_cap, (size_t)nwords + 1)) != MI_OK) return rc;
+  HIPC(hipMemcpyAsync(h->bits, plan.keep.data(), (size_t)nwords * 8, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(h->rmpref, plan.prefix.data(), ((size_t)nwords + 1) * 4, hipMemcpyHostToDevice, s));
+  // the tables on the device are those of the last publish: the chains and fills before the removal
+  launch_ivf_remove(h->codes, h->rowid, h->blk_table, h->list_off, h->list_rows, h->nlist, h->m, h->bits, h->rmpref, s);
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(s));
+  std::vector<int64_t> fill((size_t)h->nlist, 0);
+  int64_t j = 0;
+  for (int64_t r = 0; r < n; ++r) {
+    if (!((plan.keep[(size_t)(r >> 6)] >> (r & 63)) & 1ull)) continue;
+    const int32_t l = h->list_of_row[(size_t)r];
+    const int64_t c = fill[l]++;
+    h->slot_of_row[(size_t)j] = (int64_t)h->blocks[l][(size_t)(c >> 6)] * 64 + (c & 63);
+    h->list_of_row[(size_t)j] = (uint8_t)l;
+    ++j;
+  }
+  h->slot_of_row.resize((size_t)m);
+  h->list_of_row.resize((size_t)m);
+  for (int32_t l = 0; l < h->nlist; ++l) {
+    const size_t nb = (size_t)((fill[l] + 63) / 64);
+    h->free_blocks.insert(h->free_blocks.end(), h->blocks[l].begin() + nb, h->blocks[l].end());
+    h->blocks[l].resize(nb);
+  }
+  h->list_size = fill;
+  h->n = m;
+  if ((rc = ivf_publish(h)) != MI_OK) return rc;
+  if (out_removed) *out_removed = plan.removed;
+  return MI_OK;
+}
+
 int mi_ivfpq_destroy(mi_ivfpq* h) {
   if (!h) return MI_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->codes, (void*)h->rowid, (void*)h->blk_table, (void*)h->list_off, (void*)h->cb, (void*)h->coarse, (void*)h->flag,
                   (void*)h->xraw, (void*)h->cbytes, (void*)h->lbytes, (void*)h->slots, (void*)h->tab, (void*)h->praw, (void*)h->pnorm,
-                  (void*)h->pref, (void*)h->pex, (void*)h->part, (void*)h->bits, (void*)h->oidx, (void*)h->odist})
+                  (void*)h->pref, (void*)h->pex, (void*)h->part, (void*)h->bits, (void*)h->rmpref, (void*)h->oidx, (void*)h->odist})
     (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

@@ -31,6 +31,8 @@ struct mi_pq {
   int64_t* oidx = nullptr;                         // results of a host call
   float* odist = nullptr;
   size_t oidx_cap = 0, odist_cap = 0;
+  uint32_t *rmpref = nullptr, *rmstage = nullptr;  // mi_pq_remove_rows: prefix counts per bitmap word; staging blocks [..][MQ][64]
+  size_t rmpref_cap = 0, rmstage_cap = 0;
   std::mutex mu;
 };
 
@@ -48,7 +50,7 @@ static int pq_grow(T** p, size_t* cap, size_t count) {
 
 static int64_t pq_scratch_bytes(const mi_pq* h) {
   return (int64_t)(h->xraw_cap + h->cbytes_cap + h->tab_cap * 4 + h->mat_cap * 4 + h->tidx_cap * 8 + h->tneg_cap * 4 + h->bits_cap * 8 +
-                   h->oidx_cap * 8 + h->odist_cap * 4);
+                   h->oidx_cap * 8 + h->odist_cap * 4 + h->rmpref_cap * 4 + h->rmstage_cap * 4);
 }
 
 static bool pq_codes_below(const uint8_t* codes, int64_t rows, int64_t stride, int32_t m, int32_t ks) {
@@ -170,6 +172,28 @@ static int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, in
     launch_pq_emit(h->tidx, h->tneg, b, ke, k, h->row_offset, out_idx_dev + q0 * k, out_dist_dev ? out_dist_dev + q0 * k : nullptr, s);
   }
   HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+int remove_plan(const uint64_t* remove_bits, int memspace, int64_t n, RemovePlan* plan) {
+  const int64_t nwords = (n + 63) / 64;
+  plan->keep.resize((size_t)nwords);
+  plan->prefix.resize((size_t)nwords + 1);
+  plan->removed = 0, plan->first = -1;
+  if (memspace == MI_HOST) std::memcpy(plan->keep.data(), remove_bits, (size_t)nwords * 8);
+  else HIPC(hipMemcpy(plan->keep.data(), remove_bits, (size_t)nwords * 8, hipMemcpyDeviceToHost));
+  const uint64_t tail = n % 64 ? (1ull << (n % 64)) - 1ull : ~0ull;
+  int64_t kept = 0;
+  for (int64_t w = 0; w < nwords; ++w) {
+    const uint64_t in = w == nwords - 1 ? tail : ~0ull;
+    const uint64_t v = plan->keep[(size_t)w] & in;
+    if (v && plan->first < 0) plan->first = w * 64 + __builtin_ctzll(v);
+    plan->removed += __builtin_popcountll(v);
+    plan->keep[(size_t)w] = ~v & in;
+    plan->prefix[(size_t)w] = (uint32_t)kept;
+    kept += __builtin_popcountll(~v & in);
+  }
+  plan->prefix[(size_t)nwords] = (uint32_t)kept;
   return MI_OK;
 }
 
@@ -415,12 +439,63 @@ int mi_pq_get_codebooks(const mi_pq* h, float* out_host) {
   return MI_OK;
 }
 
+// Row removal in place (faiss IndexPQ.remove_ids): `codes` compacted stably through a staging area of at most B
+// rows (global option "pq_remove_block_rows").  The rows pass in chunks of B source rows, ascending, from the block of the first
+// row that leaves: a chunk's survivors are gathered into the staging area at their new positions, then written to the index.
+// A survivor never moves up, so a chunk's destination [d0, d0 + count) ends at or before the chunk's own last source row: what it
+// overwrites are rows this chunk or an earlier one has read, the chunks behind it are unread sources, and the rows below d0
+// are final.  Device memory beyond the index: the staging area, the bitmap and 4 bytes per bitmap word, all grow-only on the
+// handle and all allocated before anything moves.
+int mi_pq_remove_rows(mi_pq* h, const uint64_t* remove_bits, int memspace, int64_t* out_removed) {
+  REQUIRE(h, "null handle");
+  REQUIRE(remove_bits, "null pointer: remove_bits");
+  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
+  if (out_removed) *out_removed = 0;
+  std::lock_guard<std::mutex> lock(h->mu);
+  const int64_t n = h->n;
+  if (n == 0) return MI_OK;
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  HIPC(hipStreamSynchronize(s));
+  RemovePlan plan;
+  int rc;
+  if ((rc = remove_plan(remove_bits, memspace, n, &plan)) != MI_OK) return rc;
+  if (plan.removed == 0) return MI_OK;                        // nothing changes
+  const int64_t m = n - plan.removed;                         // n'
+  // m == first: only trailing rows leave, no survivor lies behind a row that leaves, nothing moves
+  if (m > plan.first) {
+    const int64_t nwords = (n + 63) / 64;
+    const int64_t blk_words = (int64_t)h->MQ * 64;
+    const int64_t start = plan.first / 64;                    // the blocks before the first row that leaves stay as they are
+    const int64_t B = std::min<int64_t>(g_pq_remove_block_rows.load(), (nwords - start) * 64) / 64;   // source blocks per chunk
+    if ((rc = pq_grow(&h->bits, &h->bits_cap, (size_t)nwords)) != MI_OK) return rc;
+    if ((rc = pq_grow(&h->rmpref, &h->rmpref_cap, (size_t)nwords + 1)) != MI_OK) return rc;
+    // a chunk's first survivor may sit in any lane of its destination block: one block more than the chunk's rows fill
+    if ((rc = pq_grow(&h->rmstage, &h->rmstage_cap, (size_t)((B + 1) * blk_words))) != MI_OK) return rc;
+    HIPC(hipMemcpyAsync(h->bits, plan.keep.data(), (size_t)nwords * 8, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(h->rmpref, plan.prefix.data(), ((size_t)nwords + 1) * 4, hipMemcpyHostToDevice, s));
+    for (int64_t b0 = start; b0 < nwords; b0 += B) {
+      const int64_t b1 = std::min(b0 + B, nwords);
+      const int64_t d0 = plan.prefix[(size_t)b0], count = (int64_t)plan.prefix[(size_t)b1] - d0;
+      if (count == 0) continue;
+      const int64_t lo = d0 % 64;
+      launch_pq_remove_gather(h->codes, h->m, h->bits, h->rmpref, b0, b1, d0 / 64, h->rmstage, s);
+      launch_pq_remove_writeback(h->rmstage, h->m, d0 / 64, lo, lo + count, h->codes, s);
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));
+  }
+  h->n = m;
+  if (out_removed) *out_removed = plan.removed;
+  return MI_OK;
+}
+
 int mi_pq_destroy(mi_pq* h) {
   if (!h) return MI_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   for (void* p : {(void*)h->codes, (void*)h->cb, (void*)h->flag, (void*)h->xraw, (void*)h->cbytes, (void*)h->tab, (void*)h->mat,
-                  (void*)h->tidx, (void*)h->tneg, (void*)h->bits, (void*)h->oidx, (void*)h->odist})
+                  (void*)h->tidx, (void*)h->tneg, (void*)h->bits, (void*)h->oidx, (void*)h->odist, (void*)h->rmpref, (void*)h->rmstage})
     (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

@@ -35,6 +35,11 @@ std::atomic<int64_t> g_hamming_matrix_bytes{HAMMING_MATRIX_DEFAULT};
 // goes through it in chunks of whole query tiles, four queries at the least
 constexpr int64_t PQ_MATRIX_DEFAULT = (int64_t)2 << 30;
 std::atomic<int64_t> g_pq_matrix_bytes{PQ_MATRIX_DEFAULT};
+// mi_set_global_option("pq_remove_block_rows", ...): upper limit B of the rows mi_pq_remove_rows moves through its staging area at a
+// time (api_pq.hip; a multiple of 64).  2 097 152 rows are 32 MiB of staging at M = 16 and 128 MiB at M = 64, and 16 M rows pass
+// in 8 chunks of two launches; a first choice, no sweep yet
+constexpr int64_t PQ_REMOVE_BLOCK_ROWS_DEFAULT = (int64_t)1 << 21;
+std::atomic<int64_t> g_pq_remove_block_rows{PQ_REMOVE_BLOCK_ROWS_DEFAULT};
 void spare_release_locked() {
   if (g_spare.device < 0) return;
   int cur = 0;
@@ -254,6 +259,11 @@ int mi_set_global_option(const char* name, double value) {
     REQUIRE(value >= 0 && value <= 1e9, "remove_block_rows: rows of the staging area of mi_gallery_remove_rows (0 = default)");
     g_remove_block_rows = round_up((int64_t)value, TILE);
   }
+  else if (n == "pq_remove_block_rows") {
+    REQUIRE(value == 0 || (value >= 64 && value <= 4e9),
+            "pq_remove_block_rows: rows of the staging area of mi_pq_remove_rows, at least 64 (0 = default, 2 097 152)");
+    g_pq_remove_block_rows = value == 0 ? PQ_REMOVE_BLOCK_ROWS_DEFAULT : round_up((int64_t)value, (int64_t)64);
+  }
   else if (n == "hamming_matrix_bytes") {
     REQUIRE(value >= 0 && value <= 1e13, "hamming_matrix_bytes: bytes of the distance matrix of a binary index (0 = default, 2 GiB)");
     g_hamming_matrix_bytes = value == 0 ? HAMMING_MATRIX_DEFAULT : (int64_t)value;
@@ -281,6 +291,7 @@ int mi_get_global_option(const char* name, double* out_value) {
   else if (n == "keep_buffers") *out_value = g_keep_buffers.load();
   else if (n == "scatter_block_rows") *out_value = (double)g_scatter_block_rows.load();
   else if (n == "remove_block_rows") *out_value = (double)g_remove_block_rows.load();
+  else if (n == "pq_remove_block_rows") *out_value = (double)g_pq_remove_block_rows.load();
   else if (n == "hamming_matrix_bytes") *out_value = (double)g_hamming_matrix_bytes.load();
   else if (n == "pq_matrix_bytes") *out_value = (double)g_pq_matrix_bytes.load();
   else if (n == "spare_bytes") {

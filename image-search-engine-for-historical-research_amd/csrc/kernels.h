@@ -352,6 +352,19 @@ void launch_ivfr_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_
 void launch_ivfr_rows(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* G, int32_t d, const uint8_t* lists, float* out,
                       hipStream_t stream);
 
+// pq_remove.hip -- in-place row removal of the PQ and the IVF-PQ index (api_pq.hip, api_ivfpq.hip).  keep [ceil(n / 64)]: the bitmap
+// of the rows that stay (bits at or beyond n clear); prefix [ceil(n / 64) + 1]: the exclusive count of keep bits per word.
+// Flat index, one chunk of source blocks [blk0, blk1): its survivors -> the staging area, whose block 0 stands for block dst_blk0
+// of the index (the block of the chunk's first survivor); then the staging positions [lo, hi) -> the index
+void launch_pq_remove_gather(const uint32_t* codes, int32_t M, const uint64_t* keep, const uint32_t* prefix, int64_t blk0, int64_t blk1,
+                             int64_t dst_blk0, uint32_t* stg, hipStream_t stream);
+void launch_pq_remove_writeback(const uint32_t* stg, int32_t M, int64_t dst_blk0, int64_t lo, int64_t hi, uint32_t* codes,
+                                hipStream_t stream);
+// IVF index: every chain compacted in place by one workgroup (blk_table, list_off, list_rows: the tables BEFORE the removal),
+// row ids rewritten to the new numbering
+void launch_ivf_remove(uint32_t* codes, uint32_t* rowid, const uint32_t* blk_table, const int32_t* list_off, const uint32_t* list_rows,
+                       int32_t nlist, int32_t M, const uint64_t* keep, const uint32_t* prefix, hipStream_t stream);
+
 // synth.hip
 void launch_synth_fill(float* dst, uint64_t seed, int64_t row0, int64_t nrows, int32_t d, hipStream_t stream);
 

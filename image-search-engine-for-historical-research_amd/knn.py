@@ -161,5 +161,14 @@ class ANN:
         ids, dist, _ = self.index.search(queries, int(k), nprobe=self.nprobe)
         return dist, ids
 
+    def remove_ids(self, ids):
+        """faiss's IndexIVFPQ.remove_ids: the rows leave the index, the others keep their order, codes and lists and are renumbered
+        0 .. N' - 1.  ids: an array of row ids (duplicates are fine), a bool mask [N] or packed AllowBits words.  -> the number of
+        rows removed."""
+        before = self.index.n
+        self.index.remove(ids)
+        self.N = self.index.n
+        return before - self.N
+
     def close(self):
         self.index.close()

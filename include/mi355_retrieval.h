@@ -247,7 +247,7 @@ int mi_hamming_destroy(mi_hamming* h); /* NULL is MI_OK */
  *   encoding  code[r][j] = argmin_c of the float64 sum above (before the rounding), ties to the lower c
  * No certificate, no flag, no fallback path.  The handle is a type of its own, ONE row shard on ONE device; none of the mi_gallery
  * entry points takes it.  Codebooks are learned by mi_pq_train (below); mi_ivfpq (further below) searches such codes by inverted
- * lists.  Out of scope: ks > 256, row removal, save / load, sharding, re-ranking.
+ * lists.  Rows leave through mi_pq_remove_rows (below).  Out of scope: ks > 256, save / load, sharding, re-ranking.
  * mi_pq_create: n rows of `codes` (row i at codes + i * row_stride_bytes; MI_HOST or MI_DEVICE, device rows complete when the
  * call is made) into an index of `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty appendable
  * index.  A code byte >= ks is MI_ERR_INVALID (host codes are checked before a device is touched).  Synchronous. */
@@ -285,6 +285,19 @@ int mi_pq_info(const mi_pq* h, int64_t* n, int32_t* d, int32_t* m, int32_t* ks, 
 int mi_pq_get_codes(mi_pq* h, int64_t row0, int64_t nrows, uint8_t* out_host);
 /* The codebooks as given, [m][ks][L] float32. */
 int mi_pq_get_codebooks(const mi_pq* h, float* out_host);
+/* Removes rows in place (faiss IndexPQ.remove_ids); DESIGN.md 5.14e.  The arguments are those of mi_gallery_remove_rows:
+ * remove_bits is a bitmap of ceil(n / 64) words over the index's LOCAL rows (bit i & 63 of word i >> 6 names row i), a host or a
+ * device buffer (memspace); bits at or beyond n are ignored; out_removed (may be NULL) receives the number of rows that left.  The
+ * survivors keep their relative order and are renumbered 0 .. n' - 1, so ids become row_offset + new local row.  Code bytes are
+ * moved, never re-encoded, and the capacity stays: afterwards the index cannot be told apart, through any entry point, from a
+ * fresh one of the same capacity, codebooks and row_offset to which the survivors' codes were appended in order (mi_pq_info's
+ * hbm_bytes excepted: it counts the grow-only scratch) -- searches return the same ids and the same distance bits, and later
+ * appends go behind row n' - 1.  Removing every row leaves a valid empty index.  A bitmap that names no row, or n == 0, is MI_OK and
+ * touches nothing.  A NULL handle, a NULL bitmap or a bad memspace is MI_ERR_INVALID before anything else.  Synchronous, under the
+ * handle's mutex, on the handle's stream.  Device memory beyond the index: a staging area of B rows of codes (global option
+ * "pq_remove_block_rows"), the bitmap and 4 bytes per bitmap word, kept on the handle and allocated before anything moves, so an
+ * allocation that fails (MI_ERR_NOMEM) leaves the index as it was. */
+int mi_pq_remove_rows(mi_pq* h, const uint64_t* remove_bits, int memspace, int64_t* out_removed);
 int mi_pq_destroy(mi_pq* h); /* NULL is MI_OK */
 /* Learning the codebooks: Lloyd's k-means iteration per book from given initial centroids, as a deterministic function of its
  * inputs -- scipy.cluster.vq.kmeans2(minit="matrix"), the routine nanopq's PQ.fit runs, made reproducible on the device.  DESIGN.md
@@ -335,9 +348,9 @@ int mi_pq_train_timing(int32_t capacity, float* out_assign_ms, float* out_update
  *             row; fewer than k such rows: trailing ids -1, distances +inf
  * With nprobe == nlist ids and distance bits equal mi_pq_search on the same codes.  The answer does not depend on the order in
  * which rows were appended, on how a batch is chunked or on how lists are cut into slabs.  No certificate, no flag, no fallback
- * path.  The handle is a type of its own, ONE row shard on ONE device; no mi_gallery or mi_pq entry point takes it.  Out of scope:
- * nlist > 256, grouping queries by list, row removal, save / load, sharding, re-ranking.  Residual codes: mi_ivfpq_create_residual
- * (below).
+ * path.  The handle is a type of its own, ONE row shard on ONE device; no mi_gallery or mi_pq entry point takes it.  Rows leave
+ * through mi_ivfpq_remove_rows (below).  Out of scope: nlist > 256, grouping queries by list, save / load, sharding, re-ranking.
+ * Residual codes: mi_ivfpq_create_residual (below).
  * mi_ivfpq_create: n rows of `codes` (as for mi_pq_create) with list_ids uint8 [n] in the same memspace, into an index of
  * `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty appendable index.  A code byte >= ks or a
  * list id >= nlist is MI_ERR_INVALID: host data is checked on the host before a device is touched, device data by a flag kernel
@@ -376,6 +389,15 @@ int mi_ivfpq_list_sizes(const mi_ivfpq* h, int64_t* out);
 /* Rows [row0, row0 + nrows) by ORIGINAL row order: out_codes_host [nrows][m] bytes, out_lists_host [nrows] bytes; either may be
  * NULL.  Only the blocks these rows lie in are read back from the device. */
 int mi_ivfpq_get_rows(mi_ivfpq* h, int64_t row0, int64_t nrows, uint8_t* out_codes_host, uint8_t* out_lists_host);
+/* Removes rows in place (faiss IndexIVFPQ.remove_ids), on either kind of index; DESIGN.md 5.14e.  Arguments, renumbering and error
+ * answers are those of mi_pq_remove_rows.  A survivor keeps its code bytes and its list; every list is compacted where it lies and
+ * the blocks it no longer reaches are reused by later appends, so n' + rows added later <= capacity works as on a fresh index.
+ * Afterwards the index cannot be told apart, through any entry point (mi_ivfpq_info's n, mi_ivfpq_get_rows, mi_ivfpq_list_sizes,
+ * the searches with library or explicit probes and with a bitmap in the NEW numbering, later appends), from a fresh one of the
+ * same capacity, centroids, codebooks, kind and row_offset to which the survivors' codes and lists were appended in order;
+ * hbm_bytes may include the scratch.  Device memory beyond the index: the bitmap and 4 bytes per bitmap word, allocated before
+ * anything moves. */
+int mi_ivfpq_remove_rows(mi_ivfpq* h, const uint64_t* remove_bits, int memspace, int64_t* out_removed);
 int mi_ivfpq_destroy(mi_ivfpq* h); /* NULL is MI_OK */
 
 /* ---- Residual IVF-PQ index: faiss IndexIVFPQ with by_residual = true (its default), the reference's ANN (src/utils/knn.py:43-53).
@@ -714,6 +736,9 @@ int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
  * (rounded up to a multiple of 256; 0 = default, 32 768 -- a first choice, not yet taken from a measured sweep).  The call uses
  * fewer rows when fewer move, and gives up whole tiles of 256 rows so that the allocation, as the driver rounds it, stays within
  * B * (6 * d64 + 12) bytes + 4 bytes per surviving row + the bitmap + 1 MiB.
+ * "pq_remove_block_rows": upper limit B of the rows mi_pq_remove_rows moves through its staging area at a time (B * 4 * ceil(m / 4)
+ * bytes; at least 64, rounded up to a multiple of 64; 0 = default, 2 097 152 -- a first choice, not taken from a sweep; a value
+ * in (0, 64) or below 0 is MI_ERR_INVALID).  The result does not depend on it.  mi_ivfpq_remove_rows has no staging area.
  * "hamming_matrix_bytes": upper limit of the distance matrix of a binary index (mi_hamming_search*; 0 = default, 2 GiB).
  * "pq_matrix_bytes": upper limit of the distance matrix of a PQ index (mi_pq_search*; 0 = default, 2 GiB) and of the partial
  * lists of an IVF-PQ index (mi_ivfpq_search*). */
@@ -721,7 +746,7 @@ int mi_set_global_option(const char* name, double value);
 /* "release_spares" (any value) gives the spare slots back now and leaves "keep_buffers" as it is.  An allocation of the library
  * that fails with out-of-memory releases them by itself and is tried once more; a gallery of other sizes than the spare releases
  * it when the device could not hold both.  mi_get_global_option reads "image_dtype", "host_ingest", "keep_buffers", "scatter_block_rows",
- * "remove_block_rows", "hamming_matrix_bytes", "pq_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
+ * "remove_block_rows", "pq_remove_block_rows", "hamming_matrix_bytes", "pq_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
  * extractor's PyTorch allocator) cannot see otherwise. */
 int mi_get_global_option(const char* name, double* out_value);
 
