@@ -7,6 +7,7 @@ or `__graft_entry__.build()`.
 import ctypes as C
 import os
 import threading
+import time
 
 import numpy as np
 
@@ -90,6 +91,12 @@ SIGNATURES = {
     "mi_hamming_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "mi_hamming_destroy": (C.c_int, [C.c_void_p]),
+    "mi_lsh_encode_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p, C.c_int64, C.c_void_p]),
+    "mi_lsh_encode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
+                                C.c_void_p]),
+    "mi_hamming_append_lsh_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
     "mi_pq_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "mi_pq_append_codes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
@@ -926,6 +933,15 @@ class BinaryGallery:
                                                        int(d if row_stride is None else row_stride), C.c_void_p(stream)))
             self.n += int(m)
 
+    def append_lsh_device(self, x_ptr, m, d, r_ptr, thr_ptr=None, dtype=MI_F32, row_stride=None, col_stride=1, stream=None):
+        """m device rows of d elements: the LSH codes of their projections (x . R[j] >= t[j]; R float64 [nbits][d] and t float64
+        [nbits] or None on the device) are appended on `stream` (mi_hamming_append_lsh_device)."""
+        with self._lock:
+            check(load().mi_hamming_append_lsh_device(self._h, C.c_void_p(x_ptr), int(m), int(d), dtype,
+                                                      int(d if row_stride is None else row_stride), int(col_stride),
+                                                      C.c_void_p(r_ptr), C.c_void_p(thr_ptr), C.c_void_p(stream)))
+            self.n += int(m)
+
     def search(self, qcodes, k, allow=None, allow_ptr=None):
         """-> (ids int64 [Q,k], dist int32 [Q,k], seconds), ordered by (distance asc, id asc).  allow: anything allow_bitmap
         takes (bool mask, global ids, AllowBits words); allow_ptr: a device bitmap of ceil(n / 64) uint64 words.  Fewer than k
@@ -965,6 +981,219 @@ class BinaryGallery:
         if self._h is not None and self._h.value:
             check(load().mi_hamming_destroy(self._h))
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+LSH_MAX_BITS, LSH_MAX_DIM = 4096, 4096
+
+
+def _lsh_shape(d, nbits):
+    d, nbits = int(d), int(nbits)
+    if nbits < 8 or nbits > LSH_MAX_BITS or nbits % 8:
+        raise ValueError("n_bits = %d: an LSH code is a multiple of 8 bits in [8, %d]" % (nbits, LSH_MAX_BITS))
+    if not 1 <= d <= LSH_MAX_DIM:
+        raise ValueError("d = %d: LSH rows have 1 .. %d columns" % (d, LSH_MAX_DIM))
+    return d, nbits
+
+
+def lsh_rotation(d, nbits, seed=5):
+    """-> float64 [nbits, d]: the projection directions of an LSH index.  Q of the QR factorisation of an m x m standard normal
+    matrix drawn by RandomState(seed), m = max(d, nbits), cut to its first nbits rows and d columns: orthonormal rows when
+    nbits <= d.  This is the construction of faiss's RandomRotationMatrix, which IndexLSH(d, nbits) initialises with the same
+    seed 5 -- but not faiss's random stream (its own generator, float32), so the directions differ from faiss's the way two
+    seeds differ.  Deterministic: two calls return equal bits."""
+    d, nbits = _lsh_shape(d, nbits)
+    m = max(d, nbits)
+    q, _ = np.linalg.qr(np.random.RandomState(seed).standard_normal((m, m)))
+    return np.ascontiguousarray(q[:nbits, :d], dtype=np.float64)
+
+
+def _lsh_operands(d, R, thresholds):
+    """R float64 [nbits, d] C-contiguous and the thresholds float64 [nbits] (or None) of rows of d columns."""
+    R = np.ascontiguousarray(R, dtype=np.float64)
+    if R.ndim != 2 or R.shape[1] != int(d):
+        raise ValueError("R must be [nbits, d = %d] (got %s)" % (d, R.shape))
+    _lsh_shape(d, R.shape[0])
+    t = None
+    if thresholds is not None:
+        t = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if t.shape != (R.shape[0],):
+            raise ValueError("thresholds must be [nbits = %d] (got %s)" % (R.shape[0], t.shape))
+    return R, t
+
+
+def lsh_encode(x, R, thresholds=None, device=0):
+    """Rows x [n, d] float32/float64 (any strides) -> LSH codes uint8 [n, nbits / 8]: bit j = (x . R[j] >= thresholds[j]), the
+    sum in float64, thresholds None = 0 (mi_lsh_encode; faiss IndexLSH's sa_encode without trained thresholds).  Host in, host
+    out; the rows pass through the device in blocks."""
+    a, code, rs, cs = _strided(x)
+    R, t = _lsh_operands(a.shape[1], R, thresholds)
+    out = np.empty((a.shape[0], R.shape[0] // 8), dtype=np.uint8)
+    check(load().mi_lsh_encode(C.c_void_p(_base_pointer(a)), a.shape[0], a.shape[1], code, rs, cs, C.c_void_p(R.ctypes.data),
+                               None if t is None else C.c_void_p(t.ctypes.data), R.shape[0], device,
+                               out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def lsh_encode_device(x_ptr, n, d, r_ptr, nbits, out_ptr, thr_ptr=None, dtype=MI_F32, row_stride=None, col_stride=1,
+                      out_row_stride=None, stream=None):
+    """Device rows [n][d] -> LSH codes [n][nbits / 8] uint8 on the device, enqueued on `stream` (mi_lsh_encode_device)."""
+    check(load().mi_lsh_encode_device(C.c_void_p(x_ptr), int(n), int(d), dtype, int(d if row_stride is None else row_stride),
+                                      int(col_stride), C.c_void_p(r_ptr), C.c_void_p(thr_ptr), int(nbits), C.c_void_p(out_ptr),
+                                      int(nbits // 8 if out_row_stride is None else out_row_stride), C.c_void_p(stream)))
+
+
+class LSHIndex:
+    """LSH index on one MI355X, faiss IndexLSH(d, nbits) without trained thresholds: a BinaryGallery of the codes
+    bit j = (x . R[j] >= thresholds[j]) plus R float64 [nbits, d] and the thresholds on the device.  Rows are encoded straight
+    into the gallery's code storage; a search encodes its queries on the device and runs the exact Hamming top-k there, by
+    (distance asc, id asc)."""
+
+    def __init__(self, gallery, R, thresholds=None):
+        import torch
+        R, t = _lsh_operands(np.shape(R)[1], R, thresholds)
+        if R.shape[0] != gallery.nbits:
+            raise ValueError("R has %d rows, the gallery holds codes of %d bits" % (R.shape[0], gallery.nbits))
+        self.gallery, self.R, self.thresholds = gallery, R, t
+        self.nbits, self.d = R.shape
+        self.device = gallery.device
+        self._tdev = "cuda:%d" % gallery.device
+        self._R = torch.from_numpy(R).to(self._tdev)
+        self._thr = None if t is None else torch.from_numpy(t).to(self._tdev)
+
+    @classmethod
+    def empty(cls, d, nbits, capacity, R=None, thresholds=None, seed=5, device=0, row_offset=0):
+        """Appendable index of `capacity` rows.  R None: lsh_rotation(d, nbits, seed)."""
+        if R is None:
+            if nbits is None:
+                raise ValueError("give nbits or R")
+            R = lsh_rotation(d, nbits, seed)
+        R, t = _lsh_operands(d, R, thresholds)
+        if nbits is not None and int(nbits) != R.shape[0]:
+            raise ValueError("nbits = %d, R has %d rows" % (nbits, R.shape[0]))
+        if int(capacity) < 1:
+            raise ValueError("an empty index needs a capacity")
+        return cls(BinaryGallery.empty(int(capacity), R.shape[0], device=device, row_offset=row_offset), R, t)
+
+    @classmethod
+    def from_host(cls, x, nbits=None, R=None, thresholds=None, seed=5, device=0, capacity=0):
+        """Index of the rows x [N, d] float32/float64; capacity 0 = N, larger leaves room for add()."""
+        a, _, _, _ = _strided(x)
+        if capacity and capacity < a.shape[0]:
+            raise ValueError("capacity %d below the %d rows given" % (capacity, a.shape[0]))
+        idx = cls.empty(a.shape[1], nbits, capacity or a.shape[0], R=R, thresholds=thresholds, seed=seed, device=device)
+        idx.add(a)
+        return idx
+
+    @property
+    def n(self):
+        return self.gallery.n
+
+    @property
+    def capacity(self):
+        return self.gallery.capacity
+
+    @property
+    def hbm_bytes(self):
+        return self.gallery.hbm_bytes + self.R.nbytes + (0 if self.thresholds is None else self.thresholds.nbytes)
+
+    def _rows(self, x):
+        a, code, _, _ = _strided(x)
+        if a.shape[1] != self.d:
+            raise ValueError("rows of %d columns, the index takes %d" % (a.shape[1], self.d))
+        return a, code
+
+    def _stream(self):
+        import torch
+        return torch.cuda.current_stream(self._tdev).cuda_stream
+
+    def _thr_ptr(self):
+        return None if self._thr is None else self._thr.data_ptr()
+
+    def _blocks(self, a):
+        """Host rows -> (first row, packed device rows) in blocks of at most 64 MiB."""
+        import torch
+        step = max(128, (64 << 20) // (self.d * a.dtype.itemsize))
+        for r in range(0, a.shape[0], step):
+            yield r, torch.from_numpy(np.ascontiguousarray(a[r:r + step])).to(self._tdev)
+
+    def add(self, x):
+        """Encodes host rows [rows, d] float32/float64 (any strides) on the device and appends their codes; synchronous."""
+        import torch
+        a, code = self._rows(x)
+        if self.gallery.n + a.shape[0] > self.gallery.capacity:
+            raise ValueError("%d rows more than the capacity %d holds (%d are in)" % (a.shape[0], self.gallery.capacity, self.gallery.n))
+        for _, blk in self._blocks(a):
+            self.gallery.append_lsh_device(blk.data_ptr(), blk.shape[0], self.d, self._R.data_ptr(), self._thr_ptr(), dtype=code,
+                                           stream=self._stream())
+        torch.cuda.current_stream(self._tdev).synchronize()
+
+    def add_device(self, x_ptr, rows, dtype=MI_F32, row_stride=None, col_stride=1, stream=None):
+        """Device rows, enqueued on `stream` without synchronising (mi_hamming_append_lsh_device)."""
+        self.gallery.append_lsh_device(x_ptr, rows, self.d, self._R.data_ptr(), self._thr_ptr(), dtype=dtype, row_stride=row_stride,
+                                       col_stride=col_stride, stream=stream)
+
+    def encode(self, q):
+        """-> codes uint8 [rows, nbits / 8] of host rows, computed on the device.  The index is unchanged."""
+        import torch
+        a, code = self._rows(q)
+        out = np.empty((a.shape[0], self.nbits // 8), dtype=np.uint8)
+        for r, blk in self._blocks(a):
+            codes = torch.empty((blk.shape[0], self.nbits // 8), dtype=torch.uint8, device=self._tdev)
+            lsh_encode_device(blk.data_ptr(), blk.shape[0], self.d, self._R.data_ptr(), self.nbits, codes.data_ptr(),
+                              thr_ptr=self._thr_ptr(), dtype=code, stream=self._stream())
+            out[r:r + blk.shape[0]] = codes.cpu().numpy()
+        return out
+
+    def search(self, q, k, allow=None):
+        """-> (ids int64 [Q,k], dist int32 [Q,k], seconds), ordered by (Hamming distance asc, id asc).  The queries are encoded on
+        the device and searched there (mi_lsh_encode_device, mi_hamming_search_device): only the queries, the allow bitmap and
+        the answer cross the host link.  allow: anything allow_bitmap takes.  Fewer than k admitted rows: trailing ids -1,
+        distances INT32_MAX.  seconds: wall time of upload, encoding, search and download, device-synchronised."""
+        import torch
+        a, code = self._rows(q)
+        nq, k = a.shape[0], int(k)
+        if not 1 <= k <= 2048:
+            raise ValueError("k must be in [1, 2048]")
+        bits = None
+        if allow is not None:
+            bits = np.asarray(allow_bitmap(allow, self.gallery.n, self.gallery.row_offset))
+            if bits.size == 0:
+                bits = np.zeros(1, "<u8")
+        if nq == 0:
+            return np.empty((0, k), np.int64), np.empty((0, k), np.int32), 0.0
+        t0 = time.perf_counter()
+        stream = self._stream()
+        xq = torch.from_numpy(np.ascontiguousarray(a)).to(self._tdev)
+        bits_dev = None if bits is None else torch.from_numpy(bits.view(np.int64)).to(self._tdev)
+        qcodes = torch.empty((nq, self.nbits // 8), dtype=torch.uint8, device=self._tdev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=self._tdev)
+        dist = torch.empty((nq, k), dtype=torch.int32, device=self._tdev)
+        lsh_encode_device(xq.data_ptr(), nq, self.d, self._R.data_ptr(), self.nbits, qcodes.data_ptr(), thr_ptr=self._thr_ptr(),
+                          dtype=code, stream=stream)
+        self.gallery.search_device(qcodes.data_ptr(), nq, k, idx.data_ptr(), dist_ptr=dist.data_ptr(),
+                                   allow_ptr=None if bits_dev is None else bits_dev.data_ptr(), stream=stream)
+        ids, dd = idx.cpu().numpy(), dist.cpu().numpy()              # (synchronises with the stream the work is on)
+        return ids, dd, time.perf_counter() - t0
+
+    def get_codes(self, row0=0, nrows=None):
+        return self.gallery.get_codes(row0, nrows)
+
+    def close(self):
+        if self.gallery is not None:
+            self.gallery.close()
+            self.gallery = self._R = self._thr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

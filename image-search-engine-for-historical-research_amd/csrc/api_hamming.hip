@@ -4,26 +4,7 @@
 // staging for queries, bitmap and host results.  Integer and exact: no certificate, no flag, no fallback.
 #include "api_internal.h"
 
-struct mi_hamming {
-  int device = 0;
-  int64_t n = 0, cap = 0, row_offset = 0;
-  int32_t nbits = 0, nb = 0, W32 = 0, wq = 0;      // bits, bytes, 32-bit words of a code; words of a stored query
-  uint32_t* codes = nullptr;                       // [ceil(cap / 64)][W32][64]
-  size_t codes_bytes = 0;
-  hipStream_t stream = nullptr;
-  uint8_t* qraw = nullptr;                         // query bytes of a host call, packed [nq][nb]
-  size_t qraw_cap = 0;
-  uint32_t* qw = nullptr;                          // [nq][wq]
-  size_t qw_cap = 0;
-  uint16_t* mat = nullptr;                         // distance matrix [queries of a chunk][round_up(n, 64)]
-  size_t mat_cap = 0;
-  uint64_t* bits = nullptr;                        // device copy of a host bitmap
-  size_t bits_cap = 0;
-  int64_t* oidx = nullptr;                         // results of a host call
-  int32_t* odist = nullptr;
-  size_t oidx_cap = 0, odist_cap = 0;
-  std::mutex mu;
-};
+// (struct mi_hamming: api_internal.h -- api_lsh.hip appends to its code storage)
 
 template <typename T>
 static int hm_grow(T** p, size_t* cap, size_t count) {

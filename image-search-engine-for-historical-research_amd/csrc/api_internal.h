@@ -17,6 +17,7 @@
 //   api_pq_train.hip  learning PQ codebooks (mi_pq_train): deterministic Lloyd iterations on device-resident rows
 //   api_ivfpq.hip     IVF index over PQ codes (mi_ivfpq): coarse lists as chains of 64-slot blocks, exact ADC top-K over the probed lists
 //                     (row removal of both PQ handles: mi_pq_remove_rows in api_pq.hip, mi_ivfpq_remove_rows here; kernels in pq_remove.hip)
+//   api_lsh.hip       LSH codes (mi_lsh_encode*, mi_hamming_append_lsh_device): f64 projection to sign bits, fused (lsh.hip)
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -308,6 +309,28 @@ struct mi_gallery {
   int32_t dif_T = 0;
   std::mutex mu;
   std::atomic<int> online_users{0};   // mi_online handles built on this gallery: it cannot be destroyed under them
+};
+
+// the binary index (api_hamming.hip; api_lsh.hip encodes rows straight into `codes`)
+struct mi_hamming {
+  int device = 0;
+  int64_t n = 0, cap = 0, row_offset = 0;
+  int32_t nbits = 0, nb = 0, W32 = 0, wq = 0;      // bits, bytes, 32-bit words of a code; words of a stored query
+  uint32_t* codes = nullptr;                       // [ceil(cap / 64)][W32][64]
+  size_t codes_bytes = 0;
+  hipStream_t stream = nullptr;
+  uint8_t* qraw = nullptr;                         // query bytes of a host call, packed [nq][nb]
+  size_t qraw_cap = 0;
+  uint32_t* qw = nullptr;                          // [nq][wq]
+  size_t qw_cap = 0;
+  uint16_t* mat = nullptr;                         // distance matrix [queries of a chunk][round_up(n, 64)]
+  size_t mat_cap = 0;
+  uint64_t* bits = nullptr;                        // device copy of a host bitmap
+  size_t bits_cap = 0;
+  int64_t* oidx = nullptr;                         // results of a host call
+  int32_t* odist = nullptr;
+  size_t oidx_cap = 0, odist_cap = 0;
+  std::mutex mu;
 };
 
 // ---- api_state.hip

@@ -289,6 +289,12 @@ void launch_hamming_select(const uint16_t* dist, int64_t n, int32_t nbits, int32
 void launch_hamming_sign(const float* x, int64_t n, int32_t d, int64_t rs, uint8_t* out_bytes, int64_t out_rs, uint32_t* codes,
                          int64_t row0, hipStream_t stream);
 
+// lsh.hip -- LSH codes (api_lsh.hip): bit j of row i = (sum_k double(x[i][k]) R[j][k] >= thr[j]) (thr NULL: 0), f64 MFMA with the
+// comparison and the packing in the epilogue.  out != NULL: rows of nbits / 8 bytes at out_rs; else the words of rows dst_row0 ..
+// dst_row0 + n of a binary gallery of nbits-bit codes (hamming.hip's layout)
+void launch_lsh_encode(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, const double* R, const double* thr,
+                       int32_t nbits, uint8_t* out, int64_t out_rs, uint32_t* codes, int64_t dst_row0, hipStream_t stream);
+
 // pq.hip -- exact ADC top-K on product-quantized codes (api_pq.hip): codebooks [M][Ks][L] f32, gallery blocks of 64 rows with the
 // code bytes four books to a dword and the dwords transposed, codes[block][w < ceil(M / 4)][64]; distance tables [nq][M][Ks] f32;
 // a float32 matrix [nq][round_up(n, 64)] of NEGATED distances (NaN = row not admitted) for launch_dense_topk

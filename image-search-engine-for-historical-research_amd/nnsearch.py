@@ -256,6 +256,36 @@ def matching_Greedyhash_hip(K, hash_codes_train, hash_codes_test):
     return idx, (time.time() - t1) / num_test
 
 
+def matching_LSH_hip(K, embedded_features_train, embedded_features_test, n_bits, seed=5):
+    """Same signature and return shape as matching_LSH_faiss (src/utils/nnsearch.py:734-745), plus the seed faiss fixes at 5:
+    faiss.IndexLSH(feature_len, n_bits) over the database rows, searched with the queries -> (idx int64 [Q, K],
+    time_per_query).  A row's code is bit j = (x . R[j] >= 0), the sums in float64, R = _lib.lsh_rotation(dim, n_bits, seed) --
+    faiss's construction of the random rotation, not faiss's random stream, so the codes differ from faiss's the way two seeds
+    differ; the answer given the codes is the exact Hamming top-K, rows at equal distance by ascending index.  The rows are used
+    as given (faiss does not normalise here).  n_bits a multiple of 8 in [8, 4096], dim <= 4096, 1 <= K <= min(N, 2048); bad
+    input raises ValueError before the device is touched.  No reference entry point dispatches to LSH, so it is not in
+    MATCHING_METHODS.  The timer spans what the reference's spans: the search only -- upload and encoding of the queries
+    included --, device-synchronised; the index build lies before it."""
+    train, test = np.asarray(embedded_features_train), np.asarray(embedded_features_test)
+    if train.ndim != 2 or test.ndim != 2 or train.shape[1] != test.shape[1]:
+        raise ValueError("expected rows [N, dim] and queries [Q, dim], got %s and %s" % (train.shape, test.shape))
+    for name, a in (("embedded_features_train", train), ("embedded_features_test", test)):
+        if not np.issubdtype(a.dtype, np.floating):
+            raise ValueError("%s must be a floating-point array (got %s)" % (name, a.dtype))
+    K = int(K)
+    dim, n_bits = _lib._lsh_shape(train.shape[1], n_bits)        # (raises ValueError on n_bits or dim outside the limits)
+    num_train, num_test = train.shape[0], test.shape[0]
+    if K < 1 or K > num_train:
+        raise ValueError("K = %d, the database holds %d rows" % (K, num_train))
+    if K > TOPK_PATH_MAX_K:
+        raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
+    with _lib.LSHIndex.from_host(train, R=_lib.lsh_rotation(dim, n_bits, seed)) as g:
+        t1 = time.time()
+        idx, _, _ = g.search(test, K)                  # (synchronous: the results are on the host when it returns)
+        t2 = time.time()
+    return idx, (t2 - t1) / max(num_test, 1)
+
+
 def matching_PQ_Net_hip(K, Codewords, Query, N_books, CW_idx):
     """Same signature and return shape as matching_PQ_Net (src/utils/nnsearch.py:905-946): asymmetric-distance top-K of queries
     [Q, dim] against N_books-byte PQ codes CW_idx [N, N_books] under Codewords [N_words, dim] (book j is the column block

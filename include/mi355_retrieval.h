@@ -235,6 +235,34 @@ int mi_hamming_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, in
                              int64_t* out_idx_dev, int32_t* out_dist_dev, void* stream);
 int mi_hamming_destroy(mi_hamming* h); /* NULL is MI_OK */
 
+/* ---- LSH codes: float descriptors -> packed sign codes of their projections, the first half of faiss IndexLSH(d, nbits)
+ * (matching_LSH_faiss, src/utils/nnsearch.py:734-745); the second half is the Hamming search above.  DESIGN.md 5.13b.
+ *   bit j of row i  =  ( sum_k double(x[i][k]) * R[j][k]  >=  t[j] ),       t == NULL: every threshold 0
+ * with `>=`, faiss's fvecs2bitvecs rule -- not the `> 0` of mi_pack_sign_bits_device: a sum exactly at its threshold gives 1,
+ * -0.0 >= 0 gives 1, a NaN sum gives 0.  Bit j is bit (j & 7) of byte (j >> 3), as for every binary code here.
+ * X: n rows of d elements, MI_F32 or MI_F64, element (i, k) at X + i * row_stride + k * col_stride (in elements; the reference's
+ * [D, N] matrix is row_stride 1, col_stride N).  R: float64 [nbits][d] row-major (any directions; faiss uses the first nbits rows
+ * of a random rotation, _lib.lsh_rotation).  t: float64 [nbits].  nbits a multiple of 8 in [8, 4096], 1 <= d <= 4096, n >= 0
+ * (n == 0 is MI_OK).  out: nbits / 8 bytes per row at out_row_stride_bytes >= nbits / 8; bytes of a row beyond nbits / 8 are
+ * not touched.
+ * The sum is float64 on the f64 matrix pipe, x promoted to double (exact), k ascending across the steps of 4 of the matrix
+ * instruction: its error is at most (d + 2) 2^-53 sum_k |x[i][k] R[j][k]|, so a bit depends on the order of summation only when
+ * the projection lies within that distance of its threshold; sums that are exact in any order (small integers) are compared
+ * exactly.  The float64 products are never stored: the kernel writes the codes alone.
+ * mi_lsh_encode_device: every operand on the device; enqueued on `stream`, no synchronisation. */
+int mi_lsh_encode_device(const void* X_dev, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
+                         const double* R_dev, const double* thr_dev, int32_t nbits, uint8_t* out_dev, int64_t out_row_stride_bytes,
+                         void* stream);
+/* Host operands, host result [n][nbits / 8] packed, synchronous.  The rows pass through the device in blocks of at most 64 MiB,
+ * so host and device memory stay bounded whatever n is; the codes do not depend on the blocks. */
+int mi_lsh_encode(const void* X, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, const double* R,
+                  const double* thr, int32_t nbits, int device, uint8_t* out);
+/* The codes of m device rows appended to a binary index without leaving the device and without an intermediate buffer; nbits is
+ * the handle's.  Stream contract of mi_hamming_append_sign_device: enqueued on `stream`, no synchronisation, later calls on the
+ * handle go to the same stream (or follow its completion).  Beyond the capacity: MI_ERR_INVALID, and the index stays as it was. */
+int mi_hamming_append_lsh_device(mi_hamming* h, const void* X_dev, int64_t m, int32_t d, int dtype, int64_t row_stride,
+                                 int64_t col_stride, const double* R_dev, const double* thr_dev, void* stream);
+
 /* ---- PQ index: exact ADC top-K on product-quantized codes.  The reference's matching_PQ_Net(K, Codewords, Query, N_books,
  * CW_idx) (src/utils/nnsearch.py:905-946), nanopq's pq.dtable(query).adist(codes), faiss IndexPQ.search.  DESIGN.md 5.14.
  * m books (1 <= m <= 64) of ks codewords (2 <= ks <= 256) of L = d / m floats, d <= 4096; a code is m bytes, byte j the
