@@ -79,6 +79,12 @@ SIGNATURES = {
                                           C.c_void_p]),
     "mi_knn_dense64_search_l2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_refine_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "mi_refine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
+                            C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_debug_l2_tail_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "mi_hamming_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                     C.POINTER(C.c_void_p)]),
     "mi_hamming_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
@@ -563,6 +569,38 @@ class Gallery:
         check(load().mi_knn_search_l2_device(self._h, C.c_void_p(q_ptr), nq, k, C.c_void_p(idx_ptr), C.c_void_p(dist_ptr),
                                              C.c_void_p(dist64_ptr), C.c_void_p(stream)))
 
+    def refine(self, queries, cand, k):
+        """Exact re-ranking of a shortlist on this gallery's stored rows (mi_refine; faiss IndexRefineFlat): cand integer [Q, kc]
+        of GLOBAL ids from any index over the same rows, any order, repeats allowed, ids outside the shard (-1 ...) = padding ->
+        (ids int64 [Q,k], val float32 [Q,k], val64 float64 [Q,k], seconds): the best k distinct candidates by (value, id asc).
+        An L2 gallery gives direct-form squared distances ascending (the bits of search_l2), any other gallery inner products
+        against the stored row descending, the query used as given.  Fewer than k distinct candidates: ids -1, values +inf /
+        -inf.  1 <= kc <= 8192, 1 <= k <= kc."""
+        a, code, rs, cs = _strided(queries)
+        if a.shape[1] != self.d:
+            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        c = np.asarray(cand)
+        if c.ndim != 2 or c.shape[0] != a.shape[0] or c.dtype == np.bool_ or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError("cand must be an integer array [Q = %d, kc] (got %s %s)" % (a.shape[0], c.dtype, c.shape))
+        c = np.ascontiguousarray(c, dtype=np.int64)
+        nq, kc, k = a.shape[0], c.shape[1], int(k)
+        idx = np.empty((nq, k), dtype=np.int64)
+        val = np.empty((nq, k), dtype=np.float32)
+        val64 = np.empty((nq, k), dtype=np.float64)
+        secs = C.c_double()
+        with self._lock:
+            check(load().mi_refine(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, C.c_void_p(c.ctypes.data), kc, kc, k,
+                                   idx.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p),
+                                   val64.ctypes.data_as(C.c_void_p), C.byref(secs)))
+        return idx, val, val64, secs.value
+
+    def refine_device(self, q_ptr, nq, cand_ptr, kc, k, idx_ptr, val_ptr=None, val64_ptr=None, stream=None, cand_stride=None):
+        """mi_refine_device: q_ptr packed float32 [nq][d], cand_ptr int64 [nq][cand_stride or kc] on the device; enqueued on
+        `stream`, no synchronisation."""
+        check(load().mi_refine_device(self._h, C.c_void_p(q_ptr), int(nq), C.c_void_p(cand_ptr), int(kc),
+                                      int(kc if cand_stride is None else cand_stride), int(k), C.c_void_p(idx_ptr),
+                                      C.c_void_p(val_ptr), C.c_void_p(val64_ptr), C.c_void_p(stream)))
+
     def range_search(self, queries, min_score, max_results=None):
         """Every row whose exact score is >= min_score (inclusive), per query ->
         (lims int64 [Q+1], idx int64 [lims[-1]], scores float32 [lims[-1]], seconds).  The hits of query i are
@@ -878,6 +916,54 @@ def _code_rows(codes, nbytes=None):
     return a, max(int(a.strides[0]), a.shape[1])
 
 
+REFINE_MAX_KC = 8192
+
+
+def refine_kc(k, k_factor, n):
+    """Length of the shortlist an index search hands to Gallery.refine_device: min(k * k_factor, n, 8192), never below k."""
+    k, f = int(k), int(k_factor)
+    if f < 1:
+        raise ValueError("k_factor = %d: the shortlist is k * k_factor ids, k_factor >= 1" % f)
+    return max(k, min(k * f, int(n), REFINE_MAX_KC))
+
+
+def _search_refined(rows, q, k, kc, allow_bits, search_device, device):
+    """The refine= path of the index searches: q float32 [Q, d] host rows; search_device(q_dev, nq, kc, cand_ptr, allow_ptr,
+    stream) enqueues the index's own device search for kc ids per query; rows.refine_device follows on the same stream, and only
+    the final k ids and exact values come back -> (ids int64 [Q,k], val float32 [Q,k], seconds)."""
+    import torch
+    if not isinstance(rows, Gallery):
+        raise ValueError("refine must be a Gallery that holds the raw rows (got %s)" % type(rows).__name__)
+    a = np.ascontiguousarray(q, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != rows.d:
+        raise ValueError("refine: queries of %s columns, the rows gallery holds %d" % (a.shape[1:], rows.d))
+    if rows.device != device:
+        raise ValueError("refine: the rows gallery is on device %d, the index on device %d" % (rows.device, device))
+    nq, k = a.shape[0], int(k)
+    if nq == 0:
+        return np.empty((0, k), np.int64), np.empty((0, k), np.float32), 0.0
+    tdev = "cuda:%d" % device
+    t0 = time.perf_counter()
+    stream = torch.cuda.current_stream(tdev).cuda_stream
+    xq = torch.from_numpy(a).to(tdev)
+    bits_dev = None if allow_bits is None else torch.from_numpy(np.ascontiguousarray(allow_bits).view(np.int64)).to(tdev)
+    cand = torch.empty((nq, kc), dtype=torch.int64, device=tdev)
+    idx = torch.empty((nq, k), dtype=torch.int64, device=tdev)
+    val = torch.empty((nq, k), dtype=torch.float32, device=tdev)
+    search_device(xq, nq, kc, cand.data_ptr(), None if bits_dev is None else bits_dev.data_ptr(), stream)
+    with rows._lock:
+        rows.refine_device(xq.data_ptr(), nq, cand.data_ptr(), kc, k, idx.data_ptr(), val_ptr=val.data_ptr(), stream=stream)
+        ids, vv = idx.cpu().numpy(), val.cpu().numpy()           # (synchronises with the stream the work is on)
+    return ids, vv, time.perf_counter() - t0
+
+
+def _allow_words(allow, n, row_offset):
+    if allow is None:
+        return None
+    bits = np.asarray(allow_bitmap(allow, n, row_offset))
+    return bits if bits.size else np.zeros(1, "<u8")
+
+
 class BinaryGallery:
     """Binary index on one MI355X (a `mi_hamming` handle): exact Hamming top-k on packed codes, ties to the lower id."""
 
@@ -942,14 +1028,31 @@ class BinaryGallery:
                                                       C.c_void_p(r_ptr), C.c_void_p(thr_ptr), C.c_void_p(stream)))
             self.n += int(m)
 
-    def search(self, qcodes, k, allow=None, allow_ptr=None):
+    def search(self, qcodes, k, allow=None, allow_ptr=None, refine=None, k_factor=1, refine_queries=None):
         """-> (ids int64 [Q,k], dist int32 [Q,k], seconds), ordered by (distance asc, id asc).  allow: anything allow_bitmap
         takes (bool mask, global ids, AllowBits words); allow_ptr: a device bitmap of ceil(n / 64) uint64 words.  Fewer than k
-        admitted rows: trailing ids -1, distances INT32_MAX."""
+        admitted rows: trailing ids -1, distances INT32_MAX.
+        refine=<Gallery of the raw rows> with refine_queries [Q, d] (the raw queries behind qcodes): the Hamming search takes
+        refine_kc(k, k_factor, n) ids on the device, the gallery re-ranks them there (Gallery.refine) and the distances returned
+        are its exact float32 values."""
         a, stride = _code_rows(qcodes, self.nbits // 8)
         nq, k = a.shape[0], int(k)
         if allow is not None and allow_ptr is not None:
             raise ValueError("give at most one of allow and allow_ptr")
+        if refine is not None:
+            import torch
+            if refine_queries is None or np.shape(refine_queries)[0] != nq:
+                raise ValueError("refine: give refine_queries [Q = %d, d], the raw queries behind the codes" % nq)
+            if allow_ptr is not None:
+                raise ValueError("refine takes allow, not allow_ptr")
+            packed = np.ascontiguousarray(a)
+
+            def dev(xq, m, kc, cand_ptr, bits_ptr, stream):
+                qc = torch.from_numpy(packed).to(xq.device)
+                with self._lock:
+                    self.search_device(qc.data_ptr(), m, kc, cand_ptr, allow_ptr=bits_ptr, stream=stream)
+            return _search_refined(refine, refine_queries, k, refine_kc(k, k_factor, self.n),
+                                   _allow_words(allow, self.n, self.row_offset), dev, self.device)
         bits, bits_p, memspace = None, None, MI_HOST
         if allow is not None:
             bits = allow_bitmap(allow, self.n, self.row_offset)
@@ -1150,8 +1253,10 @@ class LSHIndex:
             out[r:r + blk.shape[0]] = codes.cpu().numpy()
         return out
 
-    def search(self, q, k, allow=None):
-        """-> (ids int64 [Q,k], dist int32 [Q,k], seconds), ordered by (Hamming distance asc, id asc).  The queries are encoded on
+    def search(self, q, k, allow=None, refine=None, k_factor=1):
+        """refine=<Gallery of the raw rows>: the Hamming search takes refine_kc(k, k_factor, n) ids, the gallery re-ranks them on
+        the device (Gallery.refine) and the distances returned are its exact float32 values.  Otherwise:
+        -> (ids int64 [Q,k], dist int32 [Q,k], seconds), ordered by (Hamming distance asc, id asc).  The queries are encoded on
         the device and searched there (mi_lsh_encode_device, mi_hamming_search_device): only the queries, the allow bitmap and
         the answer cross the host link.  allow: anything allow_bitmap takes.  Fewer than k admitted rows: trailing ids -1,
         distances INT32_MAX.  seconds: wall time of upload, encoding, search and download, device-synchronised."""
@@ -1165,6 +1270,15 @@ class LSHIndex:
             bits = np.asarray(allow_bitmap(allow, self.gallery.n, self.gallery.row_offset))
             if bits.size == 0:
                 bits = np.zeros(1, "<u8")
+        if refine is not None:
+            a32 = np.ascontiguousarray(a, dtype=np.float32)
+
+            def dev(xq, m, kc, cand_ptr, bits_ptr, stream):
+                qcodes = torch.empty((m, self.nbits // 8), dtype=torch.uint8, device=self._tdev)
+                lsh_encode_device(xq.data_ptr(), m, self.d, self._R.data_ptr(), self.nbits, qcodes.data_ptr(), thr_ptr=self._thr_ptr(),
+                                  dtype=MI_F32, stream=stream)
+                self.gallery.search_device(qcodes.data_ptr(), m, kc, cand_ptr, allow_ptr=bits_ptr, stream=stream)
+            return _search_refined(refine, a32, k, refine_kc(k, k_factor, self.gallery.n), bits, dev, self.device)
         if nq == 0:
             return np.empty((0, k), np.int64), np.empty((0, k), np.int32), 0.0
         t0 = time.perf_counter()
@@ -1465,14 +1579,25 @@ class PQIndex:
             check(load().mi_pq_dtable(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def search(self, q, k, allow=None, allow_ptr=None):
+    def search(self, q, k, allow=None, allow_ptr=None, refine=None, k_factor=1):
         """-> (ids int64 [Q,k], dist float32 [Q,k], seconds), ordered by (distance asc, id asc).  allow: anything allow_bitmap
         takes (bool mask, global ids, AllowBits words); allow_ptr: a device bitmap of ceil(n / 64) uint64 words.  Fewer than k
-        admitted rows: trailing ids -1, distances +inf."""
+        admitted rows: trailing ids -1, distances +inf.
+        refine=<Gallery of the raw rows>: the ADC search takes refine_kc(k, k_factor, n) ids on the device, the gallery re-ranks
+        them there (Gallery.refine; queries rounded to float32) and the distances returned are its exact float32 values."""
         a, code, rs, cs = self._rows(q)
         nq, k = a.shape[0], int(k)
         if allow is not None and allow_ptr is not None:
             raise ValueError("give at most one of allow and allow_ptr")
+        if refine is not None:
+            if allow_ptr is not None:
+                raise ValueError("refine takes allow, not allow_ptr")
+
+            def dev(xq, m, kc, cand_ptr, bits_ptr, stream):
+                with self._lock:
+                    self.search_device(xq.data_ptr(), m, kc, cand_ptr, allow_ptr=bits_ptr, stream=stream)
+            return _search_refined(refine, a, k, refine_kc(k, k_factor, self.n), _allow_words(allow, self.n, self.row_offset), dev,
+                                   self.device)
         bits, bits_p, memspace = None, None, MI_HOST
         if allow is not None:
             bits = allow_bitmap(allow, self.n, self.row_offset)
@@ -1755,10 +1880,12 @@ class IVFPQIndex:
                                         out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def search(self, q, k, nprobe=1, probes=None, allow=None, allow_ptr=None):
+    def search(self, q, k, nprobe=1, probes=None, allow=None, allow_ptr=None, refine=None, k_factor=1):
         """-> (ids int64 [Q,k], dist float32 [Q,k], seconds), ordered by (distance asc, id asc), over the rows of the probed
         lists.  probes: integer [Q, P] of list ids, -1 = no list, repeats ignored (then nprobe is P); None: the library probes the
-        nprobe nearest lists.  allow / allow_ptr as for PQIndex.search.  Fewer than k such rows: trailing ids -1, distances +inf."""
+        nprobe nearest lists.  allow / allow_ptr as for PQIndex.search.  Fewer than k such rows: trailing ids -1, distances +inf.
+        refine=<Gallery of the raw rows>: the search takes refine_kc(k, k_factor, n) ids on the device, the gallery re-ranks them
+        there (Gallery.refine; queries rounded to float32) and the distances returned are its exact float32 values."""
         a, code, rs, cs = self._rows(q)
         nq, k = a.shape[0], int(k)
         if allow is not None and allow_ptr is not None:
@@ -1774,6 +1901,18 @@ class IVFPQIndex:
             pr = np.ascontiguousarray(pr, dtype=np.int32)
             pr_p = C.c_void_p(pr.ctypes.data)
         nprobe = self._nprobe(nprobe)
+        if refine is not None:
+            import torch
+            if allow_ptr is not None:
+                raise ValueError("refine takes allow, not allow_ptr")
+
+            def dev(xq, m, kc, cand_ptr, bits_ptr, stream):
+                pr_dev = None if pr is None else torch.from_numpy(pr).to(xq.device)
+                with self._lock:
+                    self.search_device(xq.data_ptr(), m, kc, cand_ptr, nprobe=nprobe, probes_ptr=None if pr_dev is None else pr_dev.data_ptr(),
+                                       allow_ptr=bits_ptr, stream=stream)
+            return _search_refined(refine, a, k, refine_kc(k, k_factor, self.n), _allow_words(allow, self.n, self.row_offset), dev,
+                                   self.device)
         bits, bits_p, memspace = None, None, MI_HOST
         if allow is not None:
             bits = allow_bitmap(allow, self.n, self.row_offset)

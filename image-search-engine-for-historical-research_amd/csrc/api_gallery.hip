@@ -49,6 +49,7 @@ int mi_gallery_destroy(mi_gallery* g) {
   range_scratch_free(g);
   filter_scratch_free(g);
   l2_scratch_free(g);
+  refine_scratch_free(g);
   remove_scratch_free(g);
   (void)hipFree(g->dif_ids);
   (void)hipFree(g->dif_vals);

@@ -11,6 +11,7 @@
 //   api_range.hip     exact range search: fixed-threshold chunk schedule, overflow split, dense chunks, CSR tail
 //   api_filter.hip    filtered top-K: compacted sub-gallery (cached per bitmap) or over-fetch with a certificate
 //   api_l2.hip        squared-L2 metric: L2 galleries (hidden bias columns), top-K by distance (host / device), dense checker
+//   api_refine.hip    exact re-ranking of index shortlists on the stored rows (mi_refine*): gather launch + per-query sort
 //   api_remove.hip    row removal in place: keep-list, block-ordered move through a bounded staging area, invalidations
 //   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix
 //   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
@@ -297,6 +298,21 @@ struct mi_gallery {
     double* odist64 = nullptr;
     size_t out_cap = 0;
   } l2;
+  // re-ranking of shortlists (api_refine.hip): grow-only device buffers, freed with the handle
+  struct RefineScratch {
+    void* qraw = nullptr;                // queries of a host call as given
+    size_t qraw_cap = 0;                 // bytes
+    float* qpad = nullptr;               // [nq][dp] queries with 16-byte aligned rows
+    size_t qpad_cap = 0;                 // floats
+    double* val = nullptr;               // [nq][kc] f64 value of every candidate
+    size_t val_cap = 0;
+    int64_t* cand = nullptr;             // [nq][kc] candidates of a host call
+    size_t cand_cap = 0;
+    int64_t* oidx = nullptr;             // [nq][k] results of a host call
+    float* oval = nullptr;
+    double* oval64 = nullptr;
+    size_t out_cap = 0;
+  } refine;
   // row removal (api_remove.hip): one grow-only arena -- staging area of "remove_block_rows" rows in the gallery's own layout,
   // keep-list, bitmap, scan buffers --, freed with the handle, never handed to the spare-buffer slots
   struct RemoveScratch {
@@ -382,6 +398,8 @@ MI_INTERNAL int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, i
                                      mi_filter_info* out_info, double* out_seconds, bool l2_caller);
 // ---- api_l2.hip
 MI_INTERNAL void l2_scratch_free(mi_gallery* g);
+// ---- api_refine.hip
+MI_INTERNAL void refine_scratch_free(mi_gallery* g);
 // ---- api_remove.hip
 MI_INTERNAL void remove_scratch_free(mi_gallery* g);
 // ---- api_pq.hip, api_pq_train.hip, api_ivfpq.hip: host rows (any strides, in elements) hold no NaN and no infinity

@@ -274,6 +274,15 @@ void launch_l2_dense_dist(const float* gal_f32, const float* qry, int32_t dp, in
 void launch_l2_dense_emit(const int64_t* idx, const double* neg, int64_t nq, int32_t ke, int32_t k, int64_t* out_idx,
                           float* out_dist, double* out_dist64, hipStream_t stream);
 
+// refine.hip -- exact re-ranking of index shortlists on the stored f32 rows (api_refine.hip; wave arithmetic in l2_wave.h): the
+// f64 value of every candidate into val [nq][kc] (one wave per row, grid over (slab, query)), then one workgroup per query sorts
+// (value, id), drops repeated ids and writes k rows.  l2 != 0: direct-form distances ascending, else inner products descending.
+// qry [nq][dp] with 16-byte aligned rows; kc <= REFINE_MAX_KC; the LDS tier is chosen by kc <= REFINE_SMALL_KC.
+constexpr int REFINE_SMALL_KC = 2048, REFINE_MAX_KC = 8192;
+void launch_refine(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int64_t row_offset, int l2,
+                   const int64_t* cand, int32_t kc, int64_t cand_stride, int32_t k, int64_t nq, double* val, int64_t* out_idx,
+                   float* out_val, double* out_val64, hipStream_t stream);
+
 // hamming.hip -- exact Hamming top-K on packed binary codes (api_hamming.hip): gallery blocks of 64 rows with transposed words
 // codes[block][w < ceil(nbits / 32)][64], queries as row-major words [nq][hamming_query_words(W32)], uint16 distance matrix
 // [nq][round_up(n, 64)] (0xFFFF = row not admitted), counting selection by (distance asc, id asc)

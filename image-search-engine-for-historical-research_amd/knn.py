@@ -119,10 +119,14 @@ class ANN:
     values returned are still squared distances, ascending.  Diffusion does not use this class: the exact search is faster
     there."""
 
-    def __init__(self, database, method="euclidean", M=64, nbits=8, nlist=256, nprobe=64, seed=0, device=0):
+    def __init__(self, database, method="euclidean", M=64, nbits=8, nlist=256, nprobe=64, seed=0, device=0, refine_k_factor=0):
         if method not in ("cosine", "euclidean"):
             raise NotImplementedError("method must be 'cosine' or 'euclidean', got %r" % (method,))
         M, nbits, nlist, nprobe = int(M), int(nbits), int(nlist), int(nprobe)
+        self.refine_k_factor = int(refine_k_factor)
+        if self.refine_k_factor < 0:
+            raise ValueError("refine_k_factor = %d: 0 = no refinement, f >= 1 = re-rank k * f ids" % self.refine_k_factor)
+        self.rows = None
         if not 1 <= M <= PQ_MAX_BOOKS:
             raise ValueError("M = %d books, the IVF-PQ index takes 1 .. %d (the reference's default of 128 is outside)" % (M, PQ_MAX_BOOKS))
         if nbits != 8:
@@ -149,15 +153,22 @@ class ANN:
         g, cb, _, _ = IVFPQIndex.train(samples, nlist, M, 1 << nbits, seed=seed, device=device, by_residual=True)
         self.index = IVFPQIndex.empty(g, cb, self.N, device=device, by_residual=True)
         self.index.add(database)
+        if self.refine_k_factor > 0:
+            # faiss IndexRefineFlat over the IVF-PQ index: the rows themselves (unit rows for 'cosine') beside the codes
+            self.rows = Gallery.l2_from_host(database, device=device)
 
     def search(self, queries, k):
         """-> (squared distances float32 [Q,k] ascending, ids int64 [Q,k]); fewer than k rows in the probed lists: ids -1,
-        distances +inf."""
+        distances +inf.  With refine_k_factor = f > 0 the index returns min(k * f, N, 8192) ids per query and the k best of them
+        by their EXACT squared distance to the stored rows come back, with those distances (Gallery.refine)."""
         queries = np.asarray(queries)
         if queries.dtype != np.float32:
             queries = queries.astype(np.float32)
         if self.method == "cosine":
             queries = _unit_rows(queries)
+        if getattr(self, "rows", None) is not None:
+            ids, dist, _ = self.index.search(queries, int(k), nprobe=self.nprobe, refine=self.rows, k_factor=self.refine_k_factor)
+            return dist, ids
         ids, dist, _ = self.index.search(queries, int(k), nprobe=self.nprobe)
         return dist, ids
 
@@ -166,9 +177,16 @@ class ANN:
         0 .. N' - 1.  ids: an array of row ids (duplicates are fine), a bool mask [N] or packed AllowBits words.  -> the number of
         rows removed."""
         before = self.index.n
+        if getattr(self, "rows", None) is not None:
+            from ._lib import allow_bitmap
+            ids = allow_bitmap(ids, self.index.n, 0)             # one bitmap for both: the index and the rows stay aligned
+            self.rows.remove(ids)
         self.index.remove(ids)
         self.N = self.index.n
         return before - self.N
 
     def close(self):
         self.index.close()
+        if getattr(self, "rows", None) is not None:
+            self.rows.close()
+            self.rows = None

@@ -256,7 +256,7 @@ def matching_Greedyhash_hip(K, hash_codes_train, hash_codes_test):
     return idx, (time.time() - t1) / num_test
 
 
-def matching_LSH_hip(K, embedded_features_train, embedded_features_test, n_bits, seed=5):
+def matching_LSH_hip(K, embedded_features_train, embedded_features_test, n_bits, seed=5, refine_rows=None, k_factor=10):
     """Same signature and return shape as matching_LSH_faiss (src/utils/nnsearch.py:734-745), plus the seed faiss fixes at 5:
     faiss.IndexLSH(feature_len, n_bits) over the database rows, searched with the queries -> (idx int64 [Q, K],
     time_per_query).  A row's code is bit j = (x . R[j] >= 0), the sums in float64, R = _lib.lsh_rotation(dim, n_bits, seed) --
@@ -265,7 +265,10 @@ def matching_LSH_hip(K, embedded_features_train, embedded_features_test, n_bits,
     as given (faiss does not normalise here).  n_bits a multiple of 8 in [8, 4096], dim <= 4096, 1 <= K <= min(N, 2048); bad
     input raises ValueError before the device is touched.  No reference entry point dispatches to LSH, so it is not in
     MATCHING_METHODS.  The timer spans what the reference's spans: the search only -- upload and encoding of the queries
-    included --, device-synchronised; the index build lies before it."""
+    included --, device-synchronised; the index build lies before it.
+    refine_rows: the raw features [N, D] (usually embedded_features_train itself) -> faiss IndexRefineFlat on top: the Hamming
+    search hands min(K * k_factor, N, 8192) ids to an exact squared-L2 re-ranking against those rows on the device
+    (_lib.Gallery.refine), and the K best of them come back."""
     train, test = np.asarray(embedded_features_train), np.asarray(embedded_features_test)
     if train.ndim != 2 or test.ndim != 2 or train.shape[1] != test.shape[1]:
         raise ValueError("expected rows [N, dim] and queries [Q, dim], got %s and %s" % (train.shape, test.shape))
@@ -279,11 +282,29 @@ def matching_LSH_hip(K, embedded_features_train, embedded_features_test, n_bits,
         raise ValueError("K = %d, the database holds %d rows" % (K, num_train))
     if K > TOPK_PATH_MAX_K:
         raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
-    with _lib.LSHIndex.from_host(train, R=_lib.lsh_rotation(dim, n_bits, seed)) as g:
-        t1 = time.time()
-        idx, _, _ = g.search(test, K)                  # (synchronous: the results are on the host when it returns)
-        t2 = time.time()
+    rows = _refine_gallery(refine_rows, num_train, dim)
+    try:
+        with _lib.LSHIndex.from_host(train, R=_lib.lsh_rotation(dim, n_bits, seed)) as g:
+            t1 = time.time()
+            if rows is None:
+                idx, _, _ = g.search(test, K)              # (synchronous: the results are on the host when it returns)
+            else:
+                idx, _, _ = g.search(test, K, refine=rows, k_factor=k_factor)
+            t2 = time.time()
+    finally:
+        if rows is not None:
+            rows.close()
     return idx, (t2 - t1) / max(num_test, 1)
+
+
+def _refine_gallery(refine_rows, n, dim):
+    """The squared-L2 gallery of the raw features a matcher re-ranks its shortlist on, or None."""
+    if refine_rows is None:
+        return None
+    r = np.asarray(refine_rows)
+    if r.ndim != 2 or r.shape != (n, dim) or not np.issubdtype(r.dtype, np.floating):
+        raise ValueError("refine_rows must be the raw floating-point features [N = %d, D = %d] (got %s %s)" % (n, dim, r.dtype, r.shape))
+    return _lib.Gallery.l2_from_host(r)
 
 
 def matching_PQ_Net_hip(K, Codewords, Query, N_books, CW_idx):
@@ -323,7 +344,8 @@ def matching_PQ_Net_hip(K, Codewords, Query, N_books, CW_idx):
     return idx, (time.time() - t1) / max(num_test, 1)
 
 
-def matching_PQ_Net_bucket_hip(K, Codewords, Query, N_books, CW_idx, Gallery_features, n_clusters=10, nprobe=1):
+def matching_PQ_Net_bucket_hip(K, Codewords, Query, N_books, CW_idx, Gallery_features, n_clusters=10, nprobe=1, refine_rows=None,
+                               k_factor=10):
     """Same signature and return shape as matching_PQ_Net_bucket (src/utils/nnsearch.py:949-998), plus n_clusters (the reference
     fixes 10) and nprobe (the reference's 1): k-means buckets over Gallery_features [N, dim]; a query is answered by the ADC top-K
     of matching_PQ_Net_hip over the rows of the nprobe buckets nearest to it -> (idx int64 [Q, K], time_per_query).  Both of the
@@ -339,7 +361,9 @@ def matching_PQ_Net_bucket_hip(K, Codewords, Query, N_books, CW_idx, Gallery_fea
     (include/mi355_retrieval.h, IVF index over PQ codes).  Limits as for matching_PQ_Net_hip, 2 <= n_clusters <= 256 and
     N >= n_clusters; bad input raises ValueError before the device is touched.  It is no (K, train, test) matcher and therefore
     not in MATCHING_METHODS.  The timer spans what the reference's spans: the bucket of every query, tables and search,
-    device-synchronised; clustering and index build lie before it, as the reference's KMeans.fit does."""
+    device-synchronised; clustering and index build lie before it, as the reference's KMeans.fit does.
+    refine_rows: the raw features [N, dim] -> faiss IndexRefineFlat on top: the search hands min(K * k_factor, N, 8192) ids to an
+    exact squared-L2 re-ranking against those rows on the device (_lib.Gallery.refine), and the K best of them come back."""
     cw, q, codes, gal = np.asarray(Codewords), np.asarray(Query), np.asarray(CW_idx), np.asarray(Gallery_features)
     if cw.ndim != 2 or q.ndim != 2 or codes.ndim != 2 or gal.ndim != 2 or q.shape[1] != cw.shape[1] or gal.shape[1] != cw.shape[1]:
         raise ValueError("expected Codewords [N_words, dim], Query [Q, dim], CW_idx [N, N_books] and Gallery_features [N, dim], got "
@@ -372,10 +396,18 @@ def matching_PQ_Net_bucket_hip(K, Codewords, Query, N_books, CW_idx, Gallery_fea
     coarse, _ = _lib.pq_train(gal, 1, n_clusters, seed=0)
     with _lib.PQIndex.empty(coarse, 1) as one_book:
         labels = one_book.encode(gal)[:, 0]
-    with _lib.IVFPQIndex.from_codes(coarse[0], books, code_rows, labels) as g:
-        t1 = time.time()
-        idx, _, _ = g.search(q, K, nprobe=nprobe)
-        t2 = time.time()
+    rows = _refine_gallery(refine_rows, num_train, dim)
+    try:
+        with _lib.IVFPQIndex.from_codes(coarse[0], books, code_rows, labels) as g:
+            t1 = time.time()
+            if rows is None:
+                idx, _, _ = g.search(q, K, nprobe=nprobe)
+            else:
+                idx, _, _ = g.search(q, K, nprobe=nprobe, refine=rows, k_factor=k_factor)
+            t2 = time.time()
+    finally:
+        if rows is not None:
+            rows.close()
     return idx, (t2 - t1) / max(num_test, 1)
 
 

@@ -189,6 +189,34 @@ int mi_knn_search_l2_device(mi_gallery* g, const float* q_dev, int64_t nq, int32
 int mi_knn_dense64_search_l2(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                              int32_t k, int64_t* out_idx, float* out_dist, double* out_dist64, double* out_seconds);
 
+/* ---- exact re-ranking of an index's shortlist on the raw rows: faiss IndexRefineFlat, and the last step of the reference's
+ * matching_ANNOY (exact distances over a candidate union).  DESIGN.md 5.15.  `rows` is the gallery that holds the raw rows, ONE
+ * shard on one device; the candidates are what a PQ, IVF-PQ, binary or LSH index returned for the same rows: per query kc ids,
+ * int64, global (row_offset + local row of `rows`), in any order, repeats allowed.  An id that is negative or outside
+ * [row_offset, row_offset + n) is padding.  The answer per query is the best k DISTINCT candidates:
+ *   L2 gallery (mi_gallery_create_l2): sum_j (q_j - g_j)^2 in the direct form over the caller's d columns -- the arithmetic and
+ *     the bits of mi_knn_search_l2 --, ascending;
+ *   any other gallery: sum_j q_j g_j against the STORED f32 row (the normalised row under MI_NORM_L2), f32 promoted to float64,
+ *     float64 FMA accumulation, descending.  The query is used as given: normalise it yourself if the value matters; its scale
+ *     does not change the order.
+ * Order (value, id ascending); a repeated id counts once; fewer than k distinct candidates: trailing ids -1, values +INFINITY
+ * (L2) or -INFINITY.  out_val (f32, may be NULL) = (float)out_val64 (may be NULL).  1 <= kc <= 8192, 1 <= k <= kc,
+ * cand_stride >= kc (elements between the candidate rows of consecutive queries); nq == 0 is MI_OK and writes nothing.
+ * mi_refine_device: q_dev [nq][d] packed f32; enqueued on `stream`, no synchronisation.  It stages the queries and the values of
+ * the candidates in buffers of the handle (grown when a larger call comes): calls on one handle must be serialised by the caller
+ * and enqueued on ONE stream.  Not built: refine over a sharded gallery, and an allow bitmap (the index that produced the
+ * shortlist has applied its own). */
+int mi_refine_device(mi_gallery* rows, const float* q_dev, int64_t nq, const int64_t* cand_dev, int32_t kc, int64_t cand_stride,
+                     int32_t k, int64_t* out_idx_dev, float* out_val_dev, double* out_val64_dev, void* stream);
+/* Host form: queries of any strides and dtype as in mi_knn_search_l2 (f64 rounded to f32), candidates [nq][cand_stride] in host
+ * memory; synchronous. */
+int mi_refine(mi_gallery* rows, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, const int64_t* cand,
+              int32_t kc, int64_t cand_stride, int32_t k, int64_t* out_idx, float* out_val, double* out_val64, double* out_seconds);
+/* Measurement only (scripts/refine_timing.py): the one-workgroup-per-query tail of mi_knn_search_l2 fed ke <= k <= 2048 ids per
+ * query, [nq][ke] packed, on an L2 gallery; enqueued on `stream`. */
+int mi_debug_l2_tail_device(mi_gallery* g, const float* q_dev, int64_t nq, const int64_t* ids_dev, int32_t ke, int32_t k,
+                            int64_t* out_idx_dev, double* out_dist64_dev, void* stream);
+
 /* ---- binary index: exact Hamming top-K on packed binary codes.  The reference's matching_Greedyhash(K, hash_codes_train,
  * hash_codes_test) (src/utils/nnsearch.py:1001-1013: XOR against every gallery code, sum, argsort, first K) and faiss
  * IndexBinaryFlat (what IndexLSH, src/utils/nnsearch.py:734-745, searches with internally).  DESIGN.md 5.13.
