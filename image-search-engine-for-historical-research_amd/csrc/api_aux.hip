@@ -59,7 +59,7 @@ int mi_desc_tail_device(const float* feat_dev, int32_t b, int32_t c, int32_t hw,
   REQUIRE(feat_dev && out_dev, "null pointer");
   REQUIRE(b >= 1 && c >= 1 && hw >= 1, "bad sizes");
   REQUIRE(!whiten_w_dev || (scratch_dev && c_out >= 1), "whitening needs a [b][c] scratch buffer and c_out");
-  REQUIRE(!whiten_w_dev || (size_t)8 * c * 4 <= 160 * 1024 - 1024, "c too large for the whitening kernel");
+  REQUIRE(!whiten_w_dev || c <= DESC_TAIL_MAX_C, "c too large for the whitening kernel (at most 4968)");
   launch_desc_tail(feat_dev, b, c, hw, p, eps, whiten_w_dev, whiten_b_dev, c_out, scratch_dev, out_dev,
                    (hipStream_t)stream);
   HIPC(hipGetLastError());

@@ -100,6 +100,9 @@ void launch_desc_tail(const float* feat, int32_t b, int32_t c, int32_t hw, float
                      pool_dst);
   hipLaunchKernelGGL(l2n_rows_kernel, dim3(b), dim3(256), 0, stream, pool_dst, c, 1e-6f);
   if (W) {
+    // 8 rows of c floats pass 64 KiB at c > 2048: opted in on the current device, which is the device of the caller's
+    // stream (the *_device entry points launch on the caller's stream without a hipSetDevice of their own)
+    ensure_dynamic_lds((const void*)linear_rows_kernel, 8 * DESC_TAIL_MAX_C * 4);
     for (int b0 = 0; b0 < b; b0 += 8) {
       const int nb = b - b0 < 8 ? b - b0 : 8;
       hipLaunchKernelGGL(linear_rows_kernel, dim3((c_out + 3) / 4), dim3(256), (size_t)nb * c * 4, stream,

@@ -220,6 +220,9 @@ void launch_scatter(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, 
                     double* workspace, hipStream_t stream);
 
 // desc_tail.hip
+// widest input of the whitening layer: linear_rows_kernel stages 8 rows of c floats in dynamic LDS, 8 * 4968 * 4 = 158 976
+// bytes of the CU's 163 840; launch_desc_tail opts the kernel in for exactly this, mi_desc_tail_device refuses more
+constexpr int32_t DESC_TAIL_MAX_C = 4968;
 void launch_desc_tail(const float* feat, int32_t b, int32_t c, int32_t hw, float p, float eps, const float* W,
                       const float* bias, int32_t c_out, float* pooled, float* out, hipStream_t stream);
 void launch_ms_accumulate(float* acc, const float* desc, int64_t count, float msp, int first, hipStream_t stream);

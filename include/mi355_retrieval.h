@@ -622,7 +622,8 @@ int mi_diffusion_online(mi_gallery* g, const void* q, int64_t nq, int dtype, int
 
 /* ---- descriptor tail of the extractor (src/networks/imageretrievalnet.py:183-187, 464-479; src/layers/functional.py:
  * 20-22, 129-130): GeM pooling of the last feature map feat[b][c][hw] (p, eps), L2N (eps 1e-6), optional whitening
- * Linear(c -> c_out, bias) + L2N (scratch_dev: [b][c] floats), into out_dev [b][c_out or c].  Multi-scale: accumulate
+ * Linear(c -> c_out, bias) + L2N (scratch_dev: [b][c] floats; c <= 4968 with whitening, the layer keeps 8 rows of c floats in
+ * LDS), into out_dev [b][c_out or c].  The stream belongs to the current device.  Multi-scale: accumulate
  * desc^msp per scale (first != 0 overwrites), then finish = (acc / nscales)^(1/msp) / ||.||. */
 int mi_desc_tail_device(const float* feat_dev, int32_t b, int32_t c, int32_t hw, float p, float eps,
                         const float* whiten_w_dev, const float* whiten_b_dev, int32_t c_out, float* scratch_dev,
