@@ -172,8 +172,9 @@ int mi_kr_rerank(const void* qvecs, int64_t nq, int64_t q_row_stride, int64_t q_
   int32_t* Rcnt = tmp.get<int32_t>((size_t)all);
   float* V = tmp.get<float>((size_t)all * kr_rmax());
   float* dmax = tmp.get<float>((size_t)all);
-  uint16_t* Vqe = tmp.get<uint16_t>((size_t)all * all);
-  uint16_t* VqeT = tmp.get<uint16_t>((size_t)all * all);
+  const size_t vqe_bytes = (size_t)all * all * (k2 != 1 ? 2 : 4);      // float16; float32 at k2 == 1 (V itself, :580)
+  char* Vqe = tmp.get<char>(vqe_bytes);
+  char* VqeT = tmp.get<char>(vqe_bytes);
   uint32_t* flags = tmp.get<uint32_t>(4);
   float* negf = tmp.get<float>((size_t)nq * n);
   uint32_t* ka = tmp.get<uint32_t>((size_t)nq * n);
@@ -211,7 +212,7 @@ int mi_kr_rerank(const void* qvecs, int64_t nq, int64_t q_row_stride, int64_t q_
   launch_kr_sets(rank, ld, (int)all, k1, R, Rcnt, flags, s);
   launch_kr_weights(S, (int)all, R, Rcnt, V, dmax, s);
   launch_kr_expand(rank, ld, k2, (int)all, R, Rcnt, V, Vqe, VqeT, s);
-  launch_kr_final(Vqe, VqeT, S, dmax, (int)all, (int)nq, (float)(1.0 - lambda_value), (float)lambda_value, negf, flags, s);
+  launch_kr_final(Vqe, VqeT, k2 == 1, S, dmax, (int)all, (int)nq, (float)(1.0 - lambda_value), (float)lambda_value, negf, flags, s);
   // np.argsort(final_dist, axis=1) (:618): ascending distance = descending -distance, ties to the lower index
   launch_rank_all(negf, n, n, (int32_t)nq, ka, ia, kb, ib, 0, oi, os, s);
   HIPC(hipGetLastError());

@@ -203,8 +203,8 @@ void launch_kr_weights(const float* S, int all, const int32_t* R, const int32_t*
                        hipStream_t stream);
 void launch_kr_expand(const int64_t* rank, int ld, int k2, int all, const int32_t* R, const int32_t* Rcnt, const float* V,
                       void* Vqe, void* VqeT, hipStream_t stream);
-void launch_kr_final(const void* Vqe, const void* VqeT, const float* S, const float* dmax, int all, int nq, float w_jac,
-                     float w_org, float* neg_final, uint32_t* flags, hipStream_t stream);
+void launch_kr_final(const void* Vqe, const void* VqeT, bool f32, const float* S, const float* dmax, int all, int nq,
+                     float w_jac, float w_org, float* neg_final, uint32_t* flags, hipStream_t stream);
 int kr_rmax();
 
 // whiten.hip

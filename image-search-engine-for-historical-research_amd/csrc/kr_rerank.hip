@@ -9,7 +9,8 @@
 //                      than 2/3 of their elements with it (:565-575); sorted, unique (np.unique)
 //   kr_weights_kernel  V[i, R[i]] = softmax(-dist(i, .) / max_j dist(i, j)), dist = 2 - 2 a.b (:514-525)
 //   kr_expand_kernel   V_qe[i] = mean of the rows of the k2 nearest, rounded to float16 (:585-589), stored twice
-//                      (row-major and transposed: the Jaccard pass reads columns)
+//                      (row-major and transposed: the Jaccard pass reads columns).  k2 == 1: the reference skips this step
+//                      (`if k2 != 1:`, :580) and V stays what it is, row i itself in float32, so V_qe is stored as float32
 //   kr_final_kernel    jaccard[i, j] = 1 - m / (2 - m), m = sum_c min(V_qe[i, c], V_qe[j, c]) over the non-zero columns c
 //                      of query i in ascending order, float32 accumulation (:602-609); final = (1 - lambda) jaccard +
 //                      lambda dist / colmax (:611-613) for the gallery columns
@@ -122,18 +123,27 @@ __global__ __launch_bounds__(256) void kr_weights_kernel(const float* __restrict
   if (t == 0) dmax_out[i] = dmax;
 }
 
+// storage of V_qe: __half (k2 != 1) or float (k2 == 1)
+__device__ __forceinline__ void kr_store(__half* p, float v) { *p = __float2half_rn(v); }
+__device__ __forceinline__ void kr_store(float* p, float v) { *p = v; }
+__device__ __forceinline__ float kr_load(__half h) { return __half2float(h); }    // exact
+__device__ __forceinline__ float kr_load(float f) { return f; }
+
 // V_qe[i, :] = float16(mean of V[rank[i, 0..k2), :]): the k2 sparse rows are added in the reference's order, column by
-// column in float32 (np.mean over axis 0 of a [k2, all] float32 array), divided by k2, rounded to float16
+// column in float32 (np.mean over axis 0 of a [k2, all] float32 array), divided by k2, rounded to float16.
+// T = float (k2 == 1): V_qe[i, :] = V[i, :] as it is -- row i, not rank[i, 0], which is another image where i has exact
+// duplicates with lower indices
+template <typename T>
 __global__ __launch_bounds__(256) void kr_expand_kernel(const int64_t* __restrict__ rank, int ld, int k2, int all,
                                                         const int32_t* __restrict__ R, const int32_t* __restrict__ Rcnt,
-                                                        const float* __restrict__ V, __half* __restrict__ Vqe,
-                                                        __half* __restrict__ VqeT) {
+                                                        const float* __restrict__ V, T* __restrict__ Vqe,
+                                                        T* __restrict__ VqeT) {
   extern __shared__ float acc[];                   // [all]
   const int i = blockIdx.x, t = threadIdx.x;
   for (int c = t; c < all; c += 256) acc[c] = 0.f;
   __syncthreads();
   for (int nb = 0; nb < k2; ++nb) {
-    const int j = (int)rank[(int64_t)i * ld + nb];
+    const int j = k2 != 1 ? (int)rank[(int64_t)i * ld + nb] : i;
     const int n = Rcnt[j];
     if (t < n) {
       const int c = R[(int64_t)j * KR_RMAX + t];
@@ -143,30 +153,33 @@ __global__ __launch_bounds__(256) void kr_expand_kernel(const int64_t* __restric
   }
   const float k2f = (float)k2;
   for (int c = t; c < all; c += 256) {
-    const __half h = __float2half_rn(k2 != 1 ? __fdiv_rn(acc[c], k2f) : acc[c]);
-    Vqe[(int64_t)i * all + c] = h;
-    VqeT[(int64_t)c * all + i] = h;
+    const float v = k2 != 1 ? __fdiv_rn(acc[c], k2f) : acc[c];
+    kr_store(Vqe + (int64_t)i * all + c, v);
+    kr_store(VqeT + (int64_t)c * all + i, v);
   }
 }
 
 // one workgroup per (256 columns j, query i): the non-zero columns of V_qe[i] in ascending order (LDS), then per j the
 // float32 sum of min(V_qe[i, c], V_qe[j, c]), the Jaccard distance, the normalised original distance and the mix
-__global__ __launch_bounds__(256) void kr_final_kernel(const __half* __restrict__ Vqe, const __half* __restrict__ VqeT,
+template <typename T>
+__global__ __launch_bounds__(256) void kr_final_kernel(const T* __restrict__ Vqe, const T* __restrict__ VqeT,
                                                        const float* __restrict__ S, const float* __restrict__ dmax, int all,
                                                        int nq, float w_jac, float w_org, float* __restrict__ neg_final,
                                                        uint32_t* __restrict__ flags) {
   __shared__ uint32_t nz_col[KR_NZMAX];
-  __shared__ __half nz_val[KR_NZMAX];
+  __shared__ T nz_val[KR_NZMAX];
   __shared__ int wave_cnt[4];
   __shared__ int total;
   const int i = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const __half* rowi = Vqe + (int64_t)i * all;
+  const T* rowi = Vqe + (int64_t)i * all;
   if (t == 0) total = 0;
   __syncthreads();
   for (int c0 = 0; c0 < all; c0 += 256) {
     const int c = c0 + t;
-    const __half v = c < all ? rowi[c] : __float2half(0.f);
-    const bool nzf = c < all && __half2float(v) != 0.f;
+    T v;
+    kr_store(&v, 0.f);
+    if (c < all) v = rowi[c];
+    const bool nzf = kr_load(v) != 0.f;
     const unsigned long long m = __ballot(nzf);
     if (lane == 0) wave_cnt[wv] = __popcll(m);
     __syncthreads();
@@ -188,8 +201,8 @@ __global__ __launch_bounds__(256) void kr_final_kernel(const __half* __restrict_
   if (j >= all || j < nq) return;                  // only the gallery columns are kept (final_dist[:Q, Q:], :617)
   float tm = 0.f;
   for (int e = 0; e < nnz; ++e) {
-    const __half vj = VqeT[(int64_t)nz_col[e] * all + j];
-    if (__half2float(vj) != 0.f) tm = __fadd_rn(tm, __half2float(__hlt(nz_val[e], vj) ? nz_val[e] : vj));
+    const float vi = kr_load(nz_val[e]), vj = kr_load(VqeT[(int64_t)nz_col[e] * all + j]);
+    if (vj != 0.f) tm = __fadd_rn(tm, vi < vj ? vi : vj);
   }
   const float jac = __fsub_rn(1.0f, __fdiv_rn(tm, __fsub_rn(2.0f, tm)));
   const float org = __fdiv_rn(__fsub_rn(2.0f, __fmul_rn(2.0f, S[(int64_t)j * all + i])), dmax[i]);
@@ -222,14 +235,25 @@ void launch_kr_weights(const float* S, int all, const int32_t* R, const int32_t*
 }
 void launch_kr_expand(const int64_t* rank, int ld, int k2, int all, const int32_t* R, const int32_t* Rcnt, const float* V,
                       void* Vqe, void* VqeT, hipStream_t stream) {
-  ensure_dynamic_lds((const void*)kr_expand_kernel);
-  hipLaunchKernelGGL(kr_expand_kernel, dim3(all), dim3(256), (size_t)all * 4, stream, rank, ld, k2, all, R, Rcnt, V,
-                     (__half*)Vqe, (__half*)VqeT);
+  if (k2 != 1) {
+    ensure_dynamic_lds((const void*)kr_expand_kernel<__half>);
+    hipLaunchKernelGGL(kr_expand_kernel<__half>, dim3(all), dim3(256), (size_t)all * 4, stream, rank, ld, k2, all, R, Rcnt, V,
+                       (__half*)Vqe, (__half*)VqeT);
+  } else {
+    ensure_dynamic_lds((const void*)kr_expand_kernel<float>);
+    hipLaunchKernelGGL(kr_expand_kernel<float>, dim3(all), dim3(256), (size_t)all * 4, stream, rank, ld, k2, all, R, Rcnt, V,
+                       (float*)Vqe, (float*)VqeT);
+  }
 }
-void launch_kr_final(const void* Vqe, const void* VqeT, const float* S, const float* dmax, int all, int nq, float w_jac,
-                     float w_org, float* neg_final, uint32_t* flags, hipStream_t stream) {
-  hipLaunchKernelGGL(kr_final_kernel, dim3((all + 255) / 256, nq), dim3(256), 0, stream, (const __half*)Vqe,
-                     (const __half*)VqeT, S, dmax, all, nq, w_jac, w_org, neg_final, flags);
+void launch_kr_final(const void* Vqe, const void* VqeT, bool f32, const float* S, const float* dmax, int all, int nq,
+                     float w_jac, float w_org, float* neg_final, uint32_t* flags, hipStream_t stream) {
+  const dim3 grid((all + 255) / 256, nq);
+  if (!f32)
+    hipLaunchKernelGGL(kr_final_kernel<__half>, grid, dim3(256), 0, stream, (const __half*)Vqe, (const __half*)VqeT, S, dmax,
+                       all, nq, w_jac, w_org, neg_final, flags);
+  else
+    hipLaunchKernelGGL(kr_final_kernel<float>, grid, dim3(256), 0, stream, (const float*)Vqe, (const float*)VqeT, S, dmax,
+                       all, nq, w_jac, w_org, neg_final, flags);
 }
 int kr_rmax() { return KR_RMAX; }
 

@@ -53,6 +53,7 @@ def test_kr_rerank_vs_oracle_larger_case():
     plain = np.argsort(-(qv.T @ vecs), axis=1, kind="stable")
     assert (got[:, :50] != plain[:, :50]).mean() > 0.05
     # other constants than the reference's
-    got2 = kr_reranking_hip(qv, vecs, k1=10, k2=1, lambda_value=0.5)
+    got2, dist2 = kr_reranking_hip(qv, vecs, k1=10, k2=1, lambda_value=0.5, return_dist=True)
     ref2, final2 = oracle.kr_reranking(qv, vecs, k1=10, k2=1, lambda_value=0.5, return_dist=True)
+    assert np.abs(np.take_along_axis(final2, got2, 1) - dist2).max() < 2e-6      # k2 = 1: V stays float32 (:580)
     assert _same_up_to_near_ties(got2, ref2, final2, 2e-6)
