@@ -96,6 +96,12 @@ SIGNATURES = {
                                     C.c_void_p, c_f64p]),
     "mi_hamming_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "mi_hamming_range_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int, C.c_int64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_hamming_range_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_hamming_self_range": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        c_f64p]),
     "mi_hamming_destroy": (C.c_int, [C.c_void_p]),
     "mi_lsh_encode_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_int64, C.c_void_p]),
@@ -1073,6 +1079,63 @@ class BinaryGallery:
         check(load().mi_hamming_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(allow_ptr),
                                               C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), C.c_void_p(stream)))
 
+    def _range_call(self, call, nq, max_results):
+        """The capacity protocol of Gallery.range_search: `call(cap, lims, idx, dist, secs)` -> rc, once more with exactly
+        lims[-1] when the first capacity (max_results, default Q * 1024) was too small."""
+        cap = int(max_results) if max_results is not None else nq * 1024
+        lims = np.zeros(nq + 1, dtype=np.int64)
+        secs = C.c_double()
+        with self._lock:
+            for attempt in range(2):
+                idx = np.empty(cap, dtype=np.int64)
+                dist = np.empty(cap, dtype=np.int32)
+                rc = call(cap, lims.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
+                          C.byref(secs))
+                if rc != MI_ERR_CAPACITY or attempt == 1:
+                    break
+                cap = int(lims[-1])
+            check(rc)
+        total = int(lims[-1])
+        return lims, idx[:total], dist[:total], secs.value
+
+    def range_search(self, qcodes, radius, allow=None, max_results=None, allow_ptr=None):
+        """Every admitted row within `radius` bits (inclusive) of each query ->
+        (lims int64 [Q+1], ids int64 [lims[-1]], dist int32 [lims[-1]], seconds).  The hits of query i are
+        ids/dist[lims[i]:lims[i+1]], ordered by (distance asc, id asc); a query has 0 .. n of them.  allow / allow_ptr as in
+        search().  The first call's capacity is `max_results` (default Q * 1024); if the hits do not fit, the call is made once
+        more with exactly lims[-1]."""
+        a, stride = _code_rows(qcodes, self.nbits // 8)
+        if allow is not None and allow_ptr is not None:
+            raise ValueError("give at most one of allow and allow_ptr")
+        bits, bits_p, memspace = None, None, MI_HOST
+        if allow is not None:
+            bits = _allow_words(allow, self.n, self.row_offset)
+            bits_p = C.c_void_p(bits.ctypes.data)
+        elif allow_ptr is not None:
+            bits_p, memspace = C.c_void_p(int(allow_ptr)), MI_DEVICE
+        lib = load()
+        return self._range_call(
+            lambda cap, lims, idx, dist, secs: lib.mi_hamming_range_search(
+                self._h, C.c_void_p(a.ctypes.data), a.shape[0], stride, int(radius), bits_p, memspace, cap, lims, idx, dist, secs),
+            a.shape[0], max_results)
+
+    def range_search_device(self, q_ptr, nq, radius, max_results, lims_ptr, idx_ptr, dist_ptr=None, allow_ptr=None, stream=None):
+        """Enqueued on `stream` without synchronising (mi_hamming_range_search_device): lims [nq + 1] int64, ids / dist
+        [max_results] on the device.  When lims[nq] > max_results nothing is written to ids / dist: read lims[nq]."""
+        check(load().mi_hamming_range_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(radius), C.c_void_p(allow_ptr),
+                                                    int(max_results), C.c_void_p(lims_ptr), C.c_void_p(idx_ptr),
+                                                    C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def self_range(self, row0, nrows, radius, max_results=None):
+        """Stored rows [row0, row0 + nrows) as queries against the rows above each of them -> (lims int64 [nrows+1], ids, dist,
+        seconds): the hits of row row0 + i are the rows j > row0 + i within `radius` bits, by (distance asc, j asc)
+        (mi_hamming_self_range).  Capacity as in range_search."""
+        lib = load()
+        return self._range_call(
+            lambda cap, lims, idx, dist, secs: lib.mi_hamming_self_range(self._h, int(row0), int(nrows), int(radius), cap, lims,
+                                                                         idx, dist, secs),
+            int(nrows), max_results)
+
     def get_codes(self, row0=0, nrows=None):
         nrows = self.n - row0 if nrows is None else int(nrows)
         out = np.empty((nrows, self.nbits // 8), dtype=np.uint8)
@@ -1294,6 +1357,42 @@ class LSHIndex:
                                    allow_ptr=None if bits_dev is None else bits_dev.data_ptr(), stream=stream)
         ids, dd = idx.cpu().numpy(), dist.cpu().numpy()              # (synchronises with the stream the work is on)
         return ids, dd, time.perf_counter() - t0
+
+    def range_search(self, q, radius, allow=None, max_results=None):
+        """-> (lims int64 [Q+1], ids int64, dist int32, seconds): every admitted row whose code is within `radius` bits
+        (inclusive) of the query's, per query by (distance asc, id asc).  The queries are encoded on the device and searched there
+        (mi_lsh_encode_device, mi_hamming_range_search_device).  The first capacity is `max_results` (default Q * 1024); if the
+        hits do not fit, the search runs once more with exactly lims[-1]."""
+        import torch
+        a, code = self._rows(q)
+        nq = a.shape[0]
+        if int(radius) < 0:
+            raise ValueError("radius must be >= 0")
+        if nq == 0:
+            return np.zeros(1, np.int64), np.empty(0, np.int64), np.empty(0, np.int32), 0.0
+        bits = _allow_words(allow, self.gallery.n, self.gallery.row_offset)
+        t0 = time.perf_counter()
+        stream = self._stream()
+        xq = torch.from_numpy(np.ascontiguousarray(a)).to(self._tdev)
+        bits_dev = None if bits is None else torch.from_numpy(bits.view(np.int64)).to(self._tdev)
+        qcodes = torch.empty((nq, self.nbits // 8), dtype=torch.uint8, device=self._tdev)
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=self._tdev)
+        lsh_encode_device(xq.data_ptr(), nq, self.d, self._R.data_ptr(), self.nbits, qcodes.data_ptr(), thr_ptr=self._thr_ptr(),
+                          dtype=code, stream=stream)
+        cap = int(max_results) if max_results is not None else nq * 1024
+        for attempt in range(2):
+            idx = torch.empty(max(cap, 1), dtype=torch.int64, device=self._tdev)
+            dist = torch.empty(max(cap, 1), dtype=torch.int32, device=self._tdev)
+            with self.gallery._lock:
+                self.gallery.range_search_device(qcodes.data_ptr(), nq, radius, cap, lims.data_ptr(), idx.data_ptr(),
+                                                 dist_ptr=dist.data_ptr(),
+                                                 allow_ptr=None if bits_dev is None else bits_dev.data_ptr(), stream=stream)
+            lims_h = lims.cpu().numpy()                                  # (synchronises with the stream the work is on)
+            total = int(lims_h[-1])
+            if total <= cap:
+                break
+            cap = total
+        return lims_h, idx[:total].cpu().numpy(), dist[:total].cpu().numpy(), time.perf_counter() - t0
 
     def get_codes(self, row0=0, nrows=None):
         return self.gallery.get_codes(row0, nrows)

@@ -2,6 +2,8 @@
 // The reference's matching_Greedyhash (src/utils/nnsearch.py:1001-1013), faiss IndexBinaryFlat.  A handle of its own: codes in
 // transposed 64-row blocks, a uint16 distance matrix of at most "hamming_matrix_bytes" (queries go through it in chunks), grow-only
 // staging for queries, bitmap and host results.  Integer and exact: no certificate, no flag, no fallback.
+// Radius search and self-join (mi_hamming_range_search*, mi_hamming_self_range; kernels in csrc/hamming_range.hip):
+// no matrix, one 64-bit ballot per (block, query) in a workspace of at most "hamming_range_bytes", counted first, filled second.
 #include "api_internal.h"
 
 // (struct mi_hamming: api_internal.h -- api_lsh.hip appends to its code storage)
@@ -19,7 +21,8 @@ static int hm_grow(T** p, size_t* cap, size_t count) {
 }
 
 static int64_t hm_scratch_bytes(const mi_hamming* h) {
-  return (int64_t)(h->qraw_cap + h->qw_cap * 4 + h->mat_cap * 2 + h->bits_cap * 8 + h->oidx_cap * 8 + h->odist_cap * 4);
+  return (int64_t)(h->qraw_cap + h->qw_cap * 4 + h->mat_cap * 2 + h->bits_cap * 8 + h->oidx_cap * 8 + h->odist_cap * 4 +
+                   h->rmask_cap * 8 + h->roffs_cap * 2 + h->rseg_cap * 4 + h->rstage_cap * 8 + h->rlims_cap * 8);
 }
 
 // m host rows of nb bytes at `stride` -> packed device rows, on stream s
@@ -69,6 +72,118 @@ static int hm_search_core(mi_hamming* h, int64_t nq, int32_t k, const uint64_t* 
                           out_dist_dev ? out_dist_dev + q0 * k : nullptr, s);
   }
   HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+// ---- radius search: what one call is about, and how its queries go through the workspace
+struct HrCall {
+  const uint32_t* qw = nullptr;      // query words [nq][wq] on the device; NULL: the self-join, query i is stored row row0 + i
+  int64_t row0 = 0;
+  int64_t nq = 0;
+  uint32_t radius = 0;
+  const uint64_t* allow = nullptr;
+};
+struct HrPlan {
+  int64_t qc = 0;                    // queries per chunk, a multiple of 64: the row length of the workspace
+  int64_t nchunks = 0;
+};
+
+// the workspace for chunks of a call whose first chunk scans the blocks from b0 on (later chunks of a self-join scan fewer):
+// 8 + 2 bytes per (block, query), 4 per (segment of 64 blocks, query), within "hamming_range_bytes", 64 queries at the least
+static int hr_prepare(mi_hamming* h, int64_t nq, int64_t b0, HrPlan* p) {
+  const int64_t nbl = std::max<int64_t>(1, (h->n + 63) / 64 - b0), nseg = (nbl + 63) / 64;
+  int64_t qc = g_hamming_range_bytes.load() / (nbl * 10 + nseg * 4) / 64 * 64;
+  qc = std::max<int64_t>(64, std::min<int64_t>({qc, (int64_t)1 << 20, round_up(nq, 64)}));
+  p->qc = qc;
+  p->nchunks = (nq + qc - 1) / qc;
+  int rc;
+  if ((rc = hm_grow(&h->rmask, &h->rmask_cap, (size_t)(nbl * qc))) != MI_OK) return rc;
+  if ((rc = hm_grow(&h->roffs, &h->roffs_cap, (size_t)(nbl * qc))) != MI_OK) return rc;
+  return hm_grow(&h->rseg, &h->rseg_cap, (size_t)(nseg * qc));
+}
+
+static HammingRangeArgs hr_args(const mi_hamming* h, const HrCall& c, const HrPlan& p, int64_t q0) {
+  HammingRangeArgs a;
+  a.codes = h->codes;
+  a.nbits = h->nbits;
+  a.n = h->n;
+  a.self = c.qw == nullptr;
+  a.b0 = a.self ? (c.row0 + q0 + 1) >> 6 : 0;      // the block of the first row above the chunk's first query
+  a.qsrc = a.self ? h->codes : c.qw + q0 * h->wq;
+  a.qrow0 = c.row0 + q0;
+  a.nq = (int32_t)std::min<int64_t>(p.qc, c.nq - q0);
+  a.allow = c.allow;
+  a.radius = c.radius;
+  a.early = g_hamming_range_early_exit.load();
+  a.masks = h->rmask;
+  a.offs = h->roffs;
+  a.seg = h->rseg;
+  a.qstride = p.qc;
+  return a;
+}
+
+// pass 1 on stream s: the hit count of every query, then the CSR offsets lims_dev [nq + 1]
+static int hr_count(mi_hamming* h, const HrCall& c, const HrPlan& p, int64_t* lims_dev, hipStream_t s) {
+  for (int64_t q0 = 0; q0 < c.nq; q0 += p.qc) {
+    const HammingRangeArgs a = hr_args(h, c, p, q0);
+    if ((h->n + 63) / 64 <= a.b0) {                   // nothing to scan: an empty index, or a self-join chunk at the last rows
+      HIPC(hipMemsetAsync(lims_dev + 1 + q0, 0, (size_t)a.nq * 8, s));
+      continue;
+    }
+    launch_hamming_range_scan(a, s);
+    launch_hamming_range_offsets(a, lims_dev + 1 + q0, s);
+  }
+  launch_hamming_range_lims(lims_dev, c.nq, s);
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+// pass 2 on stream s: the hits, ordered, into out_idx_dev / out_dist_dev -- unless lims_dev[nq] > max_results, which the kernels
+// see for themselves.  h->rstage holds the hits of any one chunk.  A call of one chunk still has its ballots from pass 1
+static int hr_fill(mi_hamming* h, const HrCall& c, const HrPlan& p, const int64_t* lims_dev, int64_t max_results,
+                   int64_t* out_idx_dev, int32_t* out_dist_dev, hipStream_t s) {
+  for (int64_t q0 = 0; q0 < c.nq; q0 += p.qc) {
+    HammingRangeArgs a = hr_args(h, c, p, q0);
+    if ((h->n + 63) / 64 <= a.b0) continue;
+    if (p.nchunks > 1) {
+      launch_hamming_range_scan(a, s);
+      launch_hamming_range_offsets(a, nullptr, s);
+    }
+    a.lims = lims_dev + q0;
+    a.total = lims_dev + c.nq;
+    a.max_results = max_results;
+    a.stage = h->rstage;
+    launch_hamming_range_fill(a, s);
+    launch_hamming_range_order(a, h->row_offset, out_idx_dev, out_dist_dev, s);
+  }
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+// host output of a radius search or a self-join whose queries (and bitmap) are on the device already
+static int hr_host(mi_hamming* h, const HrCall& c, int64_t max_results, int64_t* out_lims, int64_t* out_idx, int32_t* out_dist) {
+  hipStream_t s = h->stream;
+  HrPlan p;
+  int rc;
+  if ((rc = hr_prepare(h, c.nq, c.qw ? 0 : (c.row0 + 1) >> 6, &p)) != MI_OK) return rc;
+  if ((rc = hm_grow(&h->rlims, &h->rlims_cap, (size_t)c.nq + 1)) != MI_OK) return rc;
+  if ((rc = hr_count(h, c, p, h->rlims, s)) != MI_OK) return rc;
+  HIPC(hipMemcpyAsync(out_lims, h->rlims, ((size_t)c.nq + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  const int64_t total = out_lims[c.nq];
+  if (total > max_results)
+    return fail(MI_ERR_CAPACITY, "radius search: " + std::to_string(total) + " results > max_results " +
+                                     std::to_string(max_results) + "; call again with max_results >= out_lims[nq]");
+  if (total == 0) return MI_OK;
+  int64_t most = 0;                                   // hits of the fullest chunk
+  for (int64_t q0 = 0; q0 < c.nq; q0 += p.qc) most = std::max(most, out_lims[std::min(q0 + p.qc, c.nq)] - out_lims[q0]);
+  if ((rc = hm_grow(&h->rstage, &h->rstage_cap, (size_t)most)) != MI_OK) return rc;
+  if ((rc = hm_grow(&h->oidx, &h->oidx_cap, (size_t)total)) != MI_OK) return rc;
+  if (out_dist && (rc = hm_grow(&h->odist, &h->odist_cap, (size_t)total)) != MI_OK) return rc;
+  if ((rc = hr_fill(h, c, p, h->rlims, total, h->oidx, out_dist ? h->odist : nullptr, s)) != MI_OK) return rc;
+  HIPC(hipMemcpyAsync(out_idx, h->oidx, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+  if (out_dist) HIPC(hipMemcpyAsync(out_dist, h->odist, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
   return MI_OK;
 }
 
@@ -248,11 +363,110 @@ int mi_hamming_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, in
   return hm_search_core(h, nq, k, allow_bits_dev, out_idx_dev, out_dist_dev, s);
 }
 
+int mi_hamming_range_search(mi_hamming* h, const void* q_codes, int64_t nq, int64_t q_row_stride_bytes, int32_t radius,
+                            const uint64_t* allow_bits, int allow_memspace, int64_t max_results, int64_t* out_lims,
+                            int64_t* out_idx, int32_t* out_dist, double* out_seconds) {
+  REQUIRE(h, "null handle");
+  REQUIRE(radius >= 0, "radius must be >= 0");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  REQUIRE(out_lims, "null pointer: out_lims");
+  REQUIRE(nq == 0 || q_codes, "null pointer: queries");
+  REQUIRE(max_results >= 0, "max_results must be >= 0");
+  REQUIRE(max_results == 0 || out_idx, "null pointer: out_idx");
+  REQUIRE(!allow_bits || allow_memspace == MI_HOST || allow_memspace == MI_DEVICE, "allow_memspace must be MI_HOST or MI_DEVICE");
+  if (out_seconds) *out_seconds = 0.0;
+  out_lims[0] = 0;
+  if (nq == 0) return MI_OK;
+  REQUIRE(q_row_stride_bytes >= h->nb, "q_row_stride_bytes below nbits / 8");
+  std::lock_guard<std::mutex> lock(h->mu);
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  int rc;
+  if ((rc = hm_grow(&h->qraw, &h->qraw_cap, (size_t)nq * h->nb)) != MI_OK) return rc;
+  if ((rc = hm_grow(&h->qw, &h->qw_cap, (size_t)nq * h->wq)) != MI_OK) return rc;
+  HrCall c;
+  c.allow = allow_bits;
+  if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
+    const size_t words = (size_t)((h->n + 63) / 64);
+    if ((rc = hm_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
+    HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
+    c.allow = h->bits;
+  }
+  if ((rc = hm_copy_rows(h->qraw, (const uint8_t*)q_codes, q_row_stride_bytes, h->nb, nq, s)) != MI_OK) return rc;
+  launch_hamming_query_words(h->qraw, h->nb, h->nbits, nq, h->qw, s);
+  c.qw = h->qw;
+  c.nq = nq;
+  c.radius = (uint32_t)radius;
+  rc = hr_host(h, c, max_results, out_lims, out_idx, out_dist);
+  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
+int mi_hamming_range_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, int32_t radius, const uint64_t* allow_bits_dev,
+                                   int64_t max_results, int64_t* out_lims_dev, int64_t* out_idx_dev, int32_t* out_dist_dev,
+                                   void* stream) {
+  REQUIRE(h, "null handle");
+  REQUIRE(radius >= 0, "radius must be >= 0");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  REQUIRE(out_lims_dev, "null pointer: out_lims_dev");
+  REQUIRE(nq == 0 || q_dev, "null pointer: queries");
+  REQUIRE(max_results >= 0, "max_results must be >= 0");
+  REQUIRE(max_results == 0 || out_idx_dev, "null pointer: out_idx_dev");
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = (hipStream_t)stream;
+  if (nq == 0) {
+    HIPC(hipMemsetAsync(out_lims_dev, 0, 8, s));
+    return MI_OK;
+  }
+  int rc;
+  HrPlan p;
+  if ((rc = hm_grow(&h->qw, &h->qw_cap, (size_t)nq * h->wq)) != MI_OK) return rc;
+  if ((rc = hr_prepare(h, nq, 0, &p)) != MI_OK) return rc;
+  // the hits of one chunk: at most the caller's capacity (beyond it nothing is written), at most every row for every query
+  const int64_t stage = std::min<int64_t>(max_results, std::min(p.qc, nq) * h->n);
+  if (stage > 0 && (rc = hm_grow(&h->rstage, &h->rstage_cap, (size_t)stage)) != MI_OK) return rc;
+  launch_hamming_query_words(q_dev, h->nb, h->nbits, nq, h->qw, s);
+  HrCall c;
+  c.qw = h->qw;
+  c.nq = nq;
+  c.radius = (uint32_t)radius;
+  c.allow = allow_bits_dev;
+  if ((rc = hr_count(h, c, p, out_lims_dev, s)) != MI_OK) return rc;
+  if (stage == 0) return MI_OK;
+  return hr_fill(h, c, p, out_lims_dev, max_results, out_idx_dev, out_dist_dev, s);
+}
+
+int mi_hamming_self_range(mi_hamming* h, int64_t row0, int64_t nrows, int32_t radius, int64_t max_results, int64_t* out_lims,
+                          int64_t* out_idx, int32_t* out_dist, double* out_seconds) {
+  REQUIRE(h, "null handle");
+  REQUIRE(radius >= 0, "radius must be >= 0");
+  REQUIRE(out_lims, "null pointer: out_lims");
+  REQUIRE(max_results >= 0, "max_results must be >= 0");
+  REQUIRE(max_results == 0 || out_idx, "null pointer: out_idx");
+  REQUIRE(row0 >= 0 && nrows >= 0, "row range outside the index");
+  std::lock_guard<std::mutex> lock(h->mu);
+  REQUIRE(row0 <= h->n && nrows <= h->n - row0, "row range outside the index");
+  if (out_seconds) *out_seconds = 0.0;
+  out_lims[0] = 0;
+  if (nrows == 0) return MI_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPC(hipSetDevice(h->device));
+  HrCall c;
+  c.row0 = row0;
+  c.nq = nrows;
+  c.radius = (uint32_t)radius;
+  const int rc = hr_host(h, c, max_results, out_lims, out_idx, out_dist);
+  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return rc;
+}
+
 int mi_hamming_destroy(mi_hamming* h) {
   if (!h) return MI_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->codes, (void*)h->qraw, (void*)h->qw, (void*)h->mat, (void*)h->bits, (void*)h->oidx, (void*)h->odist})
+  for (void* p : {(void*)h->codes, (void*)h->qraw, (void*)h->qw, (void*)h->mat, (void*)h->bits, (void*)h->oidx, (void*)h->odist,
+                  (void*)h->rmask, (void*)h->roffs, (void*)h->rseg, (void*)h->rstage, (void*)h->rlims})
     (void)hipFree(p);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;

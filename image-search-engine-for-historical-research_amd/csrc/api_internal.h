@@ -13,7 +13,8 @@
 //   api_l2.hip        squared-L2 metric: L2 galleries (hidden bias columns), top-K by distance (host / device), dense checker
 //   api_refine.hip    exact re-ranking of index shortlists on the stored rows (mi_refine*): gather launch + per-query sort
 //   api_remove.hip    row removal in place: keep-list, block-ordered move through a bounded staging area, invalidations
-//   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix
+//   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix;
+//                     radius search and self-join through one ballot per (block, query)
 //   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
 //   api_pq_train.hip  learning PQ codebooks (mi_pq_train): deterministic Lloyd iterations on device-resident rows
 //   api_ivfpq.hip     IVF index over PQ codes (mi_ivfpq): coarse lists as chains of 64-slot blocks, exact ADC top-K over the probed lists
@@ -71,6 +72,8 @@ extern MI_INTERNAL std::atomic<int64_t> g_scatter_block_rows;   // mi_scatter_ma
 extern MI_INTERNAL std::atomic<int64_t> g_remove_block_rows;    // mi_gallery_remove_rows: rows of the staging area (0 = default)
 extern MI_INTERNAL std::atomic<int64_t> g_pq_remove_block_rows; // mi_pq_remove_rows: rows of the staging area (default 2 097 152)
 extern MI_INTERNAL std::atomic<int64_t> g_hamming_matrix_bytes; // mi_hamming_search*: bytes of the distance matrix (default 2 GiB)
+extern MI_INTERNAL std::atomic<int64_t> g_hamming_range_bytes;  // mi_hamming_range_search* / self_range: bytes of the (block, query) workspace (default 1 GiB)
+extern MI_INTERNAL std::atomic<int> g_hamming_range_early_exit; // ... drop a (block, query) whose partial sums are all above the radius (default 1)
 extern MI_INTERNAL std::atomic<int64_t> g_pq_matrix_bytes;      // mi_pq_search*: bytes of the distance matrix (default 2 GiB); mi_ivfpq_search*: of the partial lists
 constexpr size_t SPARE_MAX_BYTES = (size_t)16 << 30;
 MI_INTERNAL void spare_release_locked();
@@ -346,6 +349,14 @@ struct mi_hamming {
   int64_t* oidx = nullptr;                         // results of a host call
   int32_t* odist = nullptr;
   size_t oidx_cap = 0, odist_cap = 0;
+  // radius search (hamming_range.hip): ballots, prefixes and segment sums of one chunk of queries, the chunk's hits in id order,
+  // CSR offsets of a host call
+  unsigned long long* rmask = nullptr;
+  uint16_t* roffs = nullptr;
+  uint32_t* rseg = nullptr;
+  unsigned long long* rstage = nullptr;
+  int64_t* rlims = nullptr;
+  size_t rmask_cap = 0, roffs_cap = 0, rseg_cap = 0, rstage_cap = 0, rlims_cap = 0;
   std::mutex mu;
 };
 

@@ -31,6 +31,12 @@ std::atomic<int64_t> g_remove_block_rows{0};
 // a batch goes through it in chunks of queries, one query at the least
 constexpr int64_t HAMMING_MATRIX_DEFAULT = (int64_t)2 << 30;
 std::atomic<int64_t> g_hamming_matrix_bytes{HAMMING_MATRIX_DEFAULT};
+// mi_set_global_option("hamming_range_bytes", ...): upper limit of the (block, query) workspace of a radius search on a binary index
+// (10 bytes per block and query; api_hamming.hip): a batch goes through it in chunks of 64 queries at the least.
+// "hamming_range_early_exit": 1 = the scan drops a (block, query) once all 64 partial sums are above the radius
+constexpr int64_t HAMMING_RANGE_DEFAULT = (int64_t)1 << 30;
+std::atomic<int64_t> g_hamming_range_bytes{HAMMING_RANGE_DEFAULT};
+std::atomic<int> g_hamming_range_early_exit{1};
 // mi_set_global_option("pq_matrix_bytes", ...): the same limit for the float32 distance matrix of a PQ index (api_pq.hip); a batch
 // goes through it in chunks of whole query tiles, four queries at the least
 constexpr int64_t PQ_MATRIX_DEFAULT = (int64_t)2 << 30;
@@ -268,6 +274,14 @@ int mi_set_global_option(const char* name, double value) {
     REQUIRE(value >= 0 && value <= 1e13, "hamming_matrix_bytes: bytes of the distance matrix of a binary index (0 = default, 2 GiB)");
     g_hamming_matrix_bytes = value == 0 ? HAMMING_MATRIX_DEFAULT : (int64_t)value;
   }
+  else if (n == "hamming_range_bytes") {
+    REQUIRE(value >= 0 && value <= 1e13, "hamming_range_bytes: bytes of the workspace of a radius search on a binary index (0 = default, 1 GiB)");
+    g_hamming_range_bytes = value == 0 ? HAMMING_RANGE_DEFAULT : (int64_t)value;
+  }
+  else if (n == "hamming_range_early_exit") {
+    REQUIRE(value == 0 || value == 1, "hamming_range_early_exit: 0 or 1");
+    g_hamming_range_early_exit = (int)value;
+  }
   else if (n == "pq_matrix_bytes") {
     REQUIRE(value >= 0 && value <= 1e13, "pq_matrix_bytes: bytes of the distance matrix of a PQ index (0 = default, 2 GiB)");
     g_pq_matrix_bytes = value == 0 ? PQ_MATRIX_DEFAULT : (int64_t)value;
@@ -293,6 +307,8 @@ int mi_get_global_option(const char* name, double* out_value) {
   else if (n == "remove_block_rows") *out_value = (double)g_remove_block_rows.load();
   else if (n == "pq_remove_block_rows") *out_value = (double)g_pq_remove_block_rows.load();
   else if (n == "hamming_matrix_bytes") *out_value = (double)g_hamming_matrix_bytes.load();
+  else if (n == "hamming_range_bytes") *out_value = (double)g_hamming_range_bytes.load();
+  else if (n == "hamming_range_early_exit") *out_value = g_hamming_range_early_exit.load();
   else if (n == "pq_matrix_bytes") *out_value = (double)g_pq_matrix_bytes.load();
   else if (n == "spare_bytes") {
     // device memory this process holds in the spare slots right now (gallery buffers + search workspace of destroyed handles)

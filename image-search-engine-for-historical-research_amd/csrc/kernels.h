@@ -301,6 +301,38 @@ void launch_hamming_select(const uint16_t* dist, int64_t n, int32_t nbits, int32
 void launch_hamming_sign(const float* x, int64_t n, int32_t d, int64_t rs, uint8_t* out_bytes, int64_t out_rs, uint32_t* codes,
                          int64_t row0, hipStream_t stream);
 
+// hamming_range.hip -- radius search and self-join on the same layout (api_hamming.hip): one 64-bit ballot per (block, query),
+// prefix sums of their popcounts as output positions, a stable counting placement per query.  One chunk of queries at a time:
+// masks / offs are [blocks scanned][qstride], seg is [ceil(blocks / 64)][qstride], qstride a multiple of 64 >= nq
+struct HammingRangeArgs {
+  const uint32_t* codes = nullptr;       // the index: [ceil(n / 64)][W32][64]
+  int32_t nbits = 0;
+  int64_t n = 0;
+  int64_t b0 = 0;                        // first block scanned (self-join: the blocks below hold no row above a query)
+  const uint32_t* qsrc = nullptr;        // query words [nq][hamming_query_words(W32)]; self: codes
+  int64_t qrow0 = 0;                     // self: the stored row that is query 0 of the chunk
+  bool self = false;
+  int32_t nq = 0;                        // queries of the chunk
+  const uint64_t* allow = nullptr;
+  uint32_t radius = 0;
+  int32_t early = 0;                     // drop a (block, query) once every partial sum is above the radius
+  unsigned long long* masks = nullptr;
+  uint16_t* offs = nullptr;
+  uint32_t* seg = nullptr;
+  int64_t qstride = 0;
+  const int64_t* lims = nullptr;         // fill / order: CSR offsets of the chunk's queries [nq + 1]
+  const int64_t* total = nullptr;        // fill / order: the call's total; above max_results nothing is written
+  int64_t max_results = 0;
+  unsigned long long* stage = nullptr;   // the chunk's hits in id order: distance << 32 | local row
+};
+void launch_hamming_range_scan(const HammingRangeArgs& a, hipStream_t stream);
+// per-query prefix over the blocks; lims1 != NULL: hit count of query q of the chunk -> lims1[q]
+void launch_hamming_range_offsets(const HammingRangeArgs& a, int64_t* lims1, hipStream_t stream);
+void launch_hamming_range_lims(int64_t* lims, int64_t nq, hipStream_t stream);   // counts in lims[1 ..] -> offsets, in place
+void launch_hamming_range_fill(const HammingRangeArgs& a, hipStream_t stream);
+void launch_hamming_range_order(const HammingRangeArgs& a, int64_t row_offset, int64_t* out_idx, int32_t* out_dist,
+                                hipStream_t stream);
+
 // lsh.hip -- LSH codes (api_lsh.hip): bit j of row i = (sum_k double(x[i][k]) R[j][k] >= thr[j]) (thr NULL: 0), f64 MFMA with the
 // comparison and the packing in the epilogue.  out != NULL: rows of nbits / 8 bytes at out_rs; else the words of rows dst_row0 ..
 // dst_row0 + n of a binary gallery of nbits-bit codes (hamming.hip's layout)

@@ -38,7 +38,8 @@ enum mi_status {
   MI_ERR_IO = 4,
   MI_ERR_OVERFLOW = 5,    /* candidate buffers overflowed and the exact fallback was disabled */
   MI_ERR_UNSUPPORTED = 6,
-  MI_ERR_CAPACITY = 7     /* mi_range_search: more results than max_results; out_lims[nq] says how many */
+  MI_ERR_CAPACITY = 7     /* mi_range_search, mi_hamming_range_search, mi_hamming_self_range: more results than max_results;
+                             out_lims[nq] says how many */
 };
 enum mi_dtype { MI_F32 = 0, MI_F64 = 1 };
 enum mi_memspace { MI_HOST = 0, MI_DEVICE = 1 };
@@ -225,7 +226,7 @@ int mi_debug_l2_tail_device(mi_gallery* g, const float* q_dev, int64_t nq, const
  * a type of its own, ONE row shard on ONE device like mi_gallery; none of the mi_gallery entry points takes it.  The answer is
  * integer and fully determined: ids row_offset + local row ordered by (distance asc, id asc), ties at the K-th distance to the
  * lowest ids, however many rows share it -- no certificate, no flag, no fallback path.  Out of scope for binary indexes: row
- * removal, radius search, save / load, sharding.
+ * removal, save / load, sharding.
  * mi_hamming_create: n rows of `codes` (row i at codes + i * row_stride_bytes; MI_HOST or MI_DEVICE, device rows complete when
  * the call is made) into an index of `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty
  * appendable index.  Synchronous. */
@@ -261,6 +262,35 @@ int mi_hamming_search(mi_hamming* h, const void* q_codes, int64_t nq, int64_t q_
  * comes): calls on one handle must be serialised by the caller and enqueued on ONE stream. */
 int mi_hamming_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, int32_t k, const uint64_t* allow_bits_dev,
                              int64_t* out_idx_dev, int32_t* out_dist_dev, void* stream);
+/* Radius search: for every query, EVERY admitted row with Hamming distance <= radius -- inclusive, like the >= of
+ * mi_range_search (faiss's binary range_search is believed to take distance < radius: its radius would be this one plus one).
+ * 0 <= radius; a radius >= nbits returns every admitted row; a negative one is MI_ERR_INVALID.  Results in CSR form: the hits of
+ * query i are out_idx/out_dist[out_lims[i] .. out_lims[i+1]), ordered by (distance asc, id asc), ids row_offset + local row; a
+ * query has anywhere from 0 to n hits.  out_lims [nq + 1] is always written in full.  If out_lims[nq] > max_results, nothing is
+ * written to out_idx / out_dist and MI_ERR_CAPACITY is returned: call again with max_results >= out_lims[nq].  out_dist may be
+ * NULL; out_idx may be NULL when max_results is 0.  nq == 0 is MI_OK.  Queries, bitmap and out_seconds as in mi_hamming_search.
+ * Integer and fully determined: positions are prefix sums, not the order in which the device ran.  There is no distance matrix:
+ * a (block of 64 rows, query) pair leaves one 64-bit word in a workspace of at most the global option "hamming_range_bytes"
+ * (10 bytes per pair; default 1 GiB), which the queries pass through in chunks of 64 at the least, plus 8 bytes per hit of one
+ * chunk.  A call of more than one chunk scans the index three times instead of once. */
+int mi_hamming_range_search(mi_hamming* h, const void* q_codes, int64_t nq, int64_t q_row_stride_bytes, int32_t radius,
+                            const uint64_t* allow_bits, int allow_memspace, int64_t max_results, int64_t* out_lims,
+                            int64_t* out_idx, int32_t* out_dist, double* out_seconds);
+/* Device-resident variant, enqueued on `stream` without synchronising: q_dev packed [nq][nbits / 8], allow_bits_dev (may be NULL),
+ * out_lims_dev [nq + 1], out_idx_dev / out_dist_dev [max_results] are device buffers.  The capacity is decided on the device:
+ * when out_lims_dev[nq] > max_results nothing is written to out_idx_dev / out_dist_dev and the call still returns MI_OK -- the
+ * caller reads out_lims_dev[nq] once the stream has reached it.  The staging of the hits is sized by max_results (at most
+ * n hits per query of a chunk).  Buffers and stream contract of mi_hamming_search_device: one stream, calls serialised by the
+ * caller. */
+int mi_hamming_range_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, int32_t radius,
+                                   const uint64_t* allow_bits_dev, int64_t max_results, int64_t* out_lims_dev,
+                                   int64_t* out_idx_dev, int32_t* out_dist_dev, void* stream);
+/* Self-join of stored rows: query i is row row0 + i, 0 <= i < nrows, read on the device from the index itself; only the rows
+ * j > row0 + i are reported (each near pair once, no self pairs), and the blocks of rows at or below row0 are not scanned.
+ * No bitmap.  Output and capacity protocol of mi_hamming_range_search.  row0 or nrows outside [0, n] (or row0 + nrows > n) is
+ * MI_ERR_INVALID; nrows == 0 is MI_OK. */
+int mi_hamming_self_range(mi_hamming* h, int64_t row0, int64_t nrows, int32_t radius, int64_t max_results, int64_t* out_lims,
+                          int64_t* out_idx, int32_t* out_dist, double* out_seconds);
 int mi_hamming_destroy(mi_hamming* h); /* NULL is MI_OK */
 
 /* ---- LSH codes: float descriptors -> packed sign codes of their projections, the first half of faiss IndexLSH(d, nbits)
@@ -797,13 +827,17 @@ int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
  * bytes; at least 64, rounded up to a multiple of 64; 0 = default, 2 097 152 -- a first choice, not taken from a sweep; a value
  * in (0, 64) or below 0 is MI_ERR_INVALID).  The result does not depend on it.  mi_ivfpq_remove_rows has no staging area.
  * "hamming_matrix_bytes": upper limit of the distance matrix of a binary index (mi_hamming_search*; 0 = default, 2 GiB).
+ * "hamming_range_bytes": upper limit of the (block, query) workspace of a radius search on a binary index
+ * (mi_hamming_range_search*, mi_hamming_self_range; 0 = default, 1 GiB; 64 queries at the least).  The result does not depend on it.
+ * "hamming_range_early_exit": 1 (default) = the radius scan drops a (block, query) pair as soon as the partial distances of all
+ * 64 rows exceed the radius; 0 = every pair is scanned to the last word.  The result does not depend on it.
  * "pq_matrix_bytes": upper limit of the distance matrix of a PQ index (mi_pq_search*; 0 = default, 2 GiB) and of the partial
  * lists of an IVF-PQ index (mi_ivfpq_search*). */
 int mi_set_global_option(const char* name, double value);
 /* "release_spares" (any value) gives the spare slots back now and leaves "keep_buffers" as it is.  An allocation of the library
  * that fails with out-of-memory releases them by itself and is tried once more; a gallery of other sizes than the spare releases
  * it when the device could not hold both.  mi_get_global_option reads "image_dtype", "host_ingest", "keep_buffers", "scatter_block_rows",
- * "remove_block_rows", "pq_remove_block_rows", "hamming_matrix_bytes", "pq_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
+ * "remove_block_rows", "pq_remove_block_rows", "hamming_matrix_bytes", "hamming_range_bytes", "hamming_range_early_exit", "pq_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
  * extractor's PyTorch allocator) cannot see otherwise. */
 int mi_get_global_option(const char* name, double* out_value);
 
