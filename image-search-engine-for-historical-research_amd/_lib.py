@@ -85,6 +85,16 @@ SIGNATURES = {
                             C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_debug_l2_tail_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "mi_graph_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mi_graph_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mi_graph_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mi_graph_get_neighbors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "mi_graph_get_entries": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_graph_destroy": (C.c_int, [C.c_void_p]),
+    "mi_graph_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_graph_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
     "mi_hamming_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                     C.POINTER(C.c_void_p)]),
     "mi_hamming_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
@@ -923,6 +933,147 @@ def _code_rows(codes, nbytes=None):
 
 
 REFINE_MAX_KC = 8192
+
+
+GRAPH_MAX_EF, GRAPH_MAX_R, GRAPH_MAX_ENTRIES = 2048, 64, 64
+
+
+def _graph_search_shape(k, ef):
+    """(k, ef) of a graph search, ef defaulting to max(k, 64); raises ValueError outside 1 <= k <= ef <= 2048."""
+    k = int(k)
+    ef = max(k, 64) if ef is None else int(ef)
+    if ef < 1 or ef > GRAPH_MAX_EF:
+        raise ValueError("ef = %d: ef must be in [1, %d]" % (ef, GRAPH_MAX_EF))
+    if k < 1 or k > ef:
+        raise ValueError("k = %d: k must be in [1, ef = %d]" % (k, ef))
+    return k, ef
+
+
+def _graph_build_shape(n, R, n_entry):
+    """Raises ValueError unless R is even in [2, 64], 1 <= n_entry <= 64 and n >= 2 (mi_graph_build)."""
+    R, n_entry = int(R), int(n_entry)
+    if R < 2 or R > GRAPH_MAX_R or R % 2:
+        raise ValueError("R = %d: R must be even and in [2, %d]" % (R, GRAPH_MAX_R))
+    if n_entry < 1 or n_entry > GRAPH_MAX_ENTRIES:
+        raise ValueError("n_entry = %d: the number of entry rows must be in [1, %d]" % (n_entry, GRAPH_MAX_ENTRIES))
+    if int(n) < 2:
+        raise ValueError("a graph is built over at least two rows (the gallery holds %d)" % n)
+    return R, n_entry
+
+
+def _graph_table(n, table, entries):
+    """(table int32 [n, R] C-contiguous, entries int32 [ne]) of GraphIndex.from_neighbors; raises ValueError on a table of another
+    shape, R or ne outside [1, 64], an entry outside [0, n) or a table value below -1 or >= n."""
+    t, e = np.asarray(table), np.asarray(entries)
+    for name, a in (("table", t), ("entries", e)):
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("%s must be an integer array (got %s)" % (name, a.dtype))
+    if t.ndim != 2 or t.shape[0] != int(n) or not 1 <= t.shape[1] <= GRAPH_MAX_R:
+        raise ValueError("table of shape %s; a gallery of %d rows takes [%d, R] with R in [1, %d]" % (t.shape, n, n, GRAPH_MAX_R))
+    if e.ndim != 1 or not 1 <= e.shape[0] <= GRAPH_MAX_ENTRIES:
+        raise ValueError("entries of shape %s; give 1 .. %d entry rows" % (e.shape, GRAPH_MAX_ENTRIES))
+    if e.min() < 0 or e.max() >= n:
+        raise ValueError("entry rows must lie in [0, %d)" % n)
+    if t.size and (t.min() < -1 or t.max() >= n):
+        raise ValueError("table values must be -1 (padding) or lie in [0, %d)" % n)
+    return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(e, dtype=np.int32)
+
+
+class GraphIndex:
+    """A neighbour graph over the rows of a Gallery (a `mi_graph` handle): best-first search from a set of entry
+    rows, the role of the reference's HNSW matchers.  Which rows the graph reaches is approximate; the answer given graph, entry
+    rows, stored rows and query is exact: values are Gallery.refine's (direct-form float64 squared distances on an L2 gallery,
+    float64 inner products against the stored row on any other), the order is (value best first, id ascending).  The gallery
+    must outlive the index; after gallery.append* / gallery.remove a search raises (build a new graph)."""
+
+    def __init__(self, handle, gallery):
+        self._h = C.c_void_p(handle)
+        self._lock = threading.Lock()
+        self.gallery = gallery
+        n, R, ne = C.c_int64(), C.c_int32(), C.c_int32()
+        check(load().mi_graph_info(self._h, n, R, ne))
+        self.n, self.R, self.n_entry = n.value, R.value, ne.value
+
+    @classmethod
+    def build(cls, gallery, R=32, n_entry=16):
+        """mi_graph_build: per row its R / 2 nearest rows, up to R / 2 reverse edges, then further nearest rows up to R entries;
+        min(n_entry, n) evenly spaced entry rows.  Deterministic; runs on the device."""
+        R, n_entry = _graph_build_shape(gallery.n, R, n_entry)
+        h = C.c_void_p()
+        with gallery._lock:
+            check(load().mi_graph_build(gallery._h, R, n_entry, C.byref(h)))
+        return cls(h.value, gallery)
+
+    @classmethod
+    def from_neighbors(cls, gallery, table, entries):
+        """mi_graph_create: table integer [n, R] of LOCAL rows (-1 = padding; self-loops and repeats are legal), entries integer
+        [ne] local rows.  Bad input raises ValueError before the device is touched."""
+        t, e = _graph_table(gallery.n, table, entries)
+        h = C.c_void_p()
+        with gallery._lock:
+            check(load().mi_graph_create(gallery._h, C.c_void_p(t.ctypes.data), t.shape[1], MI_HOST, C.c_void_p(e.ctypes.data),
+                                         e.shape[0], C.byref(h)))
+        return cls(h.value, gallery)
+
+    @property
+    def neighbors(self):
+        """The table, int32 [n, R]."""
+        out = np.empty((self.n, self.R), np.int32)
+        with self._lock:
+            check(load().mi_graph_get_neighbors(self._h, 0, self.n, C.c_void_p(out.ctypes.data)))
+        return out
+
+    @property
+    def entries(self):
+        """The entry rows, int32 [n_entry]."""
+        out = np.empty(self.n_entry, np.int32)
+        with self._lock:
+            check(load().mi_graph_get_entries(self._h, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def search(self, q, k, ef=None, return_visited=False, return_values64=False):
+        """-> (ids int64 [Q, k], values float32 [Q, k], seconds); ef (the size of the candidate list W) defaults to max(k, 64),
+        1 <= k <= ef <= 2048.  Fewer than k rows reached: ids -1, values +inf (L2) / -inf.  return_values64: the float64 values
+        in place of their float32 cast; return_visited: int32 [Q], the rows evaluated per query, appended to the tuple."""
+        k, ef = _graph_search_shape(k, ef)
+        a, code, rs, cs = _strided(q)
+        if a.shape[1] != self.gallery.d:
+            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.gallery.d))
+        nq = a.shape[0]
+        idx = np.empty((nq, k), dtype=np.int64)
+        val = np.empty((nq, k), dtype=np.float32)
+        val64 = np.empty((nq, k), dtype=np.float64)
+        vis = np.empty(nq, dtype=np.int32)
+        secs = C.c_double()
+        with self._lock:
+            check(load().mi_graph_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, ef, C.c_void_p(idx.ctypes.data),
+                                         C.c_void_p(val.ctypes.data), C.c_void_p(val64.ctypes.data), C.c_void_p(vis.ctypes.data),
+                                         C.byref(secs)))
+        out = (idx, val64 if return_values64 else val, secs.value)
+        return out + (vis,) if return_visited else out
+
+    def search_device(self, q_ptr, nq, k, idx_ptr, ef=None, val_ptr=None, val64_ptr=None, visited_ptr=None, stream=None):
+        """mi_graph_search_device: q_ptr packed float32 [nq][d] on the device; enqueued on `stream`, no synchronisation."""
+        k, ef = _graph_search_shape(k, ef)
+        check(load().mi_graph_search_device(self._h, C.c_void_p(q_ptr), int(nq), k, ef, C.c_void_p(idx_ptr), C.c_void_p(val_ptr),
+                                            C.c_void_p(val64_ptr), C.c_void_p(visited_ptr), C.c_void_p(stream)))
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            check(load().mi_graph_destroy(self._h))
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def refine_kc(k, k_factor, n):

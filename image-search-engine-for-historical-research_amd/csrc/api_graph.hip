@@ -1,0 +1,309 @@
+// Graph index over the stored rows of a gallery (mi_graph*; the role of the reference's HNSW matchers).  DESIGN.md 5.16.
+// The handle holds a neighbour table int32 [n][R] and up to 64 entry rows on the device, plus the workspace of its searches;
+// the rows, their metric and the stream of the host entry points are the gallery's.  Kernels: graph_search.hip (one workgroup
+// per query, best-first traversal), graph_build.hip (table from exact nearest-neighbour lists); the lists themselves come from
+// the verified search of the gallery (search_sync) followed by launch_refine, which puts them in the graph's own order.
+#include "api_internal.h"
+
+struct mi_graph {
+  mi_gallery* rows = nullptr;
+  int64_t n = 0;                       // rows of the gallery when the table was made: a search refuses any other number
+  int32_t R = 0, ne = 0;
+  int32_t* adj = nullptr;              // [n][R], -1 = padding
+  int32_t* entries = nullptr;          // [ne]
+  // grow-only workspace of the searches
+  void* qraw = nullptr;                // queries of a host call as given
+  size_t qraw_cap = 0;                 // bytes
+  float* qpad = nullptr;               // [nq][dp]
+  size_t qpad_cap = 0;
+  uint32_t* vis = nullptr;             // [queries of a chunk][ceil(n / 32)] visited bitmaps
+  size_t vis_cap = 0;                  // words
+  int64_t* oidx = nullptr;             // results of a host call
+  float* oval = nullptr;
+  double* oval64 = nullptr;
+  int32_t* ovis = nullptr;
+  size_t oidx_cap = 0, oval_cap = 0, oval64_cap = 0, ovis_cap = 0;
+  std::mutex mu;
+};
+
+// bytes of visited bitmaps one launch may use: a batch whose bitmaps need more is searched in chunks of queries
+constexpr size_t GRAPH_VIS_BYTES = (size_t)256 << 20;
+constexpr int64_t GRAPH_BUILD_BATCH = 8192;      // rows per exact search of mi_graph_build
+
+template <typename T>
+static int graph_grow(T** p, size_t* cap, size_t count) {
+  if (*p && *cap >= count) return MI_OK;
+  (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = count + count / 4 + 64;
+  HIPC(device_malloc((void**)p, want * sizeof(T)));
+  *cap = want;
+  return MI_OK;
+}
+
+static void graph_free(mi_graph* gr) {
+  for (void* p : {(void*)gr->adj, (void*)gr->entries, gr->qraw, (void*)gr->qpad, (void*)gr->vis, (void*)gr->oidx, (void*)gr->oval,
+                  (void*)gr->oval64, (void*)gr->ovis})
+    (void)hipFree(p);
+  delete gr;
+}
+
+// what both search forms check before the handle is read
+static int graph_search_check(const mi_graph* gr, int64_t nq, int32_t k, int32_t ef) {
+  REQUIRE(gr, "null handle");
+  REQUIRE(ef >= 1 && ef <= GRAPH_MAX_EF, "ef must be in [1, 2048]");
+  REQUIRE(k >= 1 && k <= ef, "k must be in [1, ef]");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  return MI_OK;
+}
+
+static int graph_fresh(const mi_graph* gr) {
+  REQUIRE(gr->rows->n == gr->n, "the gallery has been appended to or had rows removed since the graph was made: build a new graph");
+  return MI_OK;
+}
+
+// queries [nq][dp] in gr->qpad (from `src`, device memory, any strides), then one launch per chunk of queries on `s`
+static int graph_enqueue(mi_graph* gr, const void* src, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k, int32_t ef,
+                         int64_t* out_idx, float* out_val, double* out_val64, int32_t* out_visited, hipStream_t s) {
+  mi_gallery* g = gr->rows;
+  int rc;
+  if ((rc = graph_grow(&gr->qpad, &gr->qpad_cap, (size_t)nq * g->dp)) != MI_OK) return rc;
+  const int64_t words = (gr->n + 31) / 32;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(GRAPH_VIS_BYTES / 4) / words));
+  if ((rc = graph_grow(&gr->vis, &gr->vis_cap, (size_t)chunk * words)) != MI_OK) return rc;
+  launch_l2_augment(src, dtype, nq, g->ud, rs, cs, gr->qpad, g->dp, s);
+  for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+    const int64_t b = std::min<int64_t>(chunk, nq - q0);
+    HIPC(hipMemsetAsync(gr->vis, 0, (size_t)b * words * 4, s));
+    launch_graph_search(g->gal_f32, gr->qpad + (size_t)q0 * g->dp, g->dp, g->ud, gr->n, g->row_offset,
+                        g->metric == MI_METRIC_L2 ? 1 : 0, gr->adj, gr->R, gr->entries, gr->ne, k, ef, b, gr->vis, words,
+                        out_idx + q0 * k, out_val ? out_val + q0 * k : nullptr, out_val64 ? out_val64 + q0 * k : nullptr,
+                        out_visited ? out_visited + q0 : nullptr, s);
+  }
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
+// a handle over `rows` with room for the table and the entries (neither filled)
+static int graph_alloc(mi_gallery* rows, int32_t R, int32_t ne, mi_graph** out) {
+  mi_graph* gr = new mi_graph();
+  gr->rows = rows;
+  gr->n = rows->n;
+  gr->R = R;
+  gr->ne = ne;
+  hipError_t e = device_malloc((void**)&gr->adj, (size_t)gr->n * R * 4);
+  if (e == hipSuccess) e = device_malloc((void**)&gr->entries, (size_t)ne * 4);
+  if (e != hipSuccess) {
+    graph_free(gr);
+    return fail(e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, std::string("graph table: ") + hipGetErrorString(e));
+  }
+  *out = gr;
+  return MI_OK;
+}
+
+extern "C" {
+
+int mi_graph_create(mi_gallery* rows, const int32_t* neighbors, int32_t R, int neighbors_memspace, const int32_t* entries,
+                    int32_t ne, mi_graph** out) {
+  REQUIRE(rows, "null handle");
+  REQUIRE(neighbors, "null pointer: neighbors");
+  REQUIRE(entries, "null pointer: entries");
+  REQUIRE(out, "null pointer: out");
+  REQUIRE(R >= 1 && R <= GRAPH_MAX_R, "R must be in [1, 64]");
+  REQUIRE(ne >= 1 && ne <= GRAPH_MAX_ENTRIES, "ne must be in [1, 64]");
+  REQUIRE(neighbors_memspace == MI_HOST || neighbors_memspace == MI_DEVICE, "neighbors_memspace must be MI_HOST or MI_DEVICE");
+  for (int32_t i = 0; i < ne; ++i) REQUIRE(entries[i] >= 0, "entry rows must lie in [0, n)");
+  std::lock_guard<std::mutex> lock(rows->mu);
+  const int64_t n = rows->n;
+  REQUIRE(n >= 1, "the gallery holds no rows");
+  REQUIRE(n <= 0x7fffffff, "a graph takes at most 2^31 - 1 rows");
+  for (int32_t i = 0; i < ne; ++i) REQUIRE(entries[i] < n, "entry rows must lie in [0, n)");
+  HIPC(hipSetDevice(rows->device));
+  const size_t cnt = (size_t)n * R;
+  std::vector<int32_t> staged;
+  const int32_t* tab = neighbors;
+  if (neighbors_memspace == MI_DEVICE) {
+    staged.resize(cnt);
+    HIPC(hipMemcpy(staged.data(), neighbors, cnt * 4, hipMemcpyDeviceToHost));
+    tab = staged.data();
+  }
+  for (size_t i = 0; i < cnt; ++i) REQUIRE(tab[i] >= -1 && tab[i] < n, "table values must be -1 (padding) or lie in [0, n)");
+  mi_graph* gr = nullptr;
+  int rc = graph_alloc(rows, R, ne, &gr);
+  if (rc != MI_OK) return rc;
+  hipError_t e = hipMemcpy(gr->adj, tab, cnt * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(gr->entries, entries, (size_t)ne * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    graph_free(gr);
+    return fail(MI_ERR_HIP, std::string("graph table copy: ") + hipGetErrorString(e));
+  }
+  *out = gr;
+  return MI_OK;
+}
+
+int mi_graph_build(mi_gallery* rows, int32_t R, int32_t ne, mi_graph** out) {
+  REQUIRE(rows, "null handle");
+  REQUIRE(out, "null pointer: out");
+  REQUIRE(R >= 2 && R <= GRAPH_MAX_R && R % 2 == 0, "R must be even and in [2, 64]");
+  REQUIRE(ne >= 1 && ne <= GRAPH_MAX_ENTRIES, "ne must be in [1, 64]");
+  mi_gallery* g = rows;
+  std::lock_guard<std::mutex> lock(g->mu);
+  const int64_t n = g->n;
+  REQUIRE(n >= 2, "a graph is built over at least two rows");
+  REQUIRE(n <= 0x7fffffff, "a graph takes at most 2^31 - 1 rows");
+  HIPC(hipSetDevice(g->device));
+  hipStream_t s = g->stream;
+  const bool l2 = g->metric == MI_METRIC_L2;
+  const int32_t ks = (int32_t)std::min<int64_t>(R + 1, n);
+  const int32_t nent = (int32_t)std::min<int64_t>(ne, n);
+  int rc;
+  if ((rc = join_tails(g, s)) != MI_OK) return rc;
+  mi_graph* gr = nullptr;
+  if ((rc = graph_alloc(g, R, nent, &gr)) != MI_OK) return rc;
+  auto bail = [&](int code) {
+    (void)hipStreamSynchronize(s);
+    graph_free(gr);
+    return code;
+  };
+  TmpAlloc tmp;                                   // (freed on return; every path out of here has synchronised `s`)
+  const int64_t bmax = std::min<int64_t>(GRAPH_BUILD_BATCH, n);
+  int32_t* F = tmp.get<int32_t>((size_t)n * R);
+  int32_t* B = tmp.get<int32_t>((size_t)n * R);
+  uint32_t* cnt = tmp.get<uint32_t>((size_t)n * 2);               // counts, then fill cursors
+  unsigned long long* off = tmp.get<unsigned long long>((size_t)n + 1);
+  int64_t* ids = tmp.get<int64_t>((size_t)bmax * ks);
+  int64_t* ord = tmp.get<int64_t>((size_t)bmax * ks);
+  double* val = tmp.get<double>((size_t)bmax * ks);
+  float* qaug = l2 ? tmp.get<float>((size_t)bmax * g->dp) : nullptr;
+  if (!F || !B || !cnt || !off || !ids || !ord || !val || (l2 && !qaug)) return bail(fail(MI_ERR_NOMEM, "graph build workspace"));
+  // forward lists: the exact search of every stored row against the gallery, through the verified loop (a raised flag is answered
+  // again inside search_sync), then the values and the order of mi_refine over what it returned
+  for (int64_t r0 = 0; r0 < n; r0 += bmax) {
+    const int64_t b = std::min<int64_t>(bmax, n - r0);
+    const float* src = g->gal_f32 + (size_t)r0 * g->dp;
+    if (l2) {
+      // (an L2 gallery is searched with three 1.0 columns behind the caller's: api_l2.hip)
+      launch_l2_augment(src, MI_F32, b, g->ud, g->dp, 1, qaug, g->dp, s);
+      rc = search_sync(g, qaug, MI_F32, g->dp, 1, MI_NORM_NONE, b, ks, ids, nullptr, nullptr);
+    } else {
+      rc = search_sync(g, src, MI_F32, g->dp, 1, MI_NORM_NONE, b, ks, ids, nullptr, nullptr);
+    }
+    if (rc != MI_OK) return bail(rc);
+    launch_refine(g->gal_f32, src, g->dp, g->ud, n, g->row_offset, l2 ? 1 : 0, ids, ks, ks, ks, b, val, ord, nullptr, nullptr, s);
+    launch_graph_forward(ord, ks, r0, b, g->row_offset, n, R, F, s);
+    hipError_t e = hipStreamSynchronize(s);        // (ids / ord / val are reused by the next batch's search)
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("graph build: ") + hipGetErrorString(e)));
+  }
+  hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n * 2 * 4, s);
+  if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("graph build: ") + hipGetErrorString(e)));
+  launch_graph_rev_count(F, n, R, cnt, off, s);
+  unsigned long long total = 0;
+  e = hipMemcpyAsync(&total, off + n, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("graph build: ") + hipGetErrorString(e)));
+  unsigned long long* edges = tmp.get<unsigned long long>((size_t)std::max<unsigned long long>(total, 1));
+  if (!edges) return bail(fail(MI_ERR_NOMEM, "graph build: reverse edges"));
+  launch_graph_table(F, n, R, off, cnt + n, edges, B, gr->adj, s);
+  std::vector<int32_t> ent((size_t)nent);
+  for (int32_t t = 0; t < nent; ++t) ent[t] = (int32_t)(((__int128)t * n) / nent);
+  e = hipMemcpyAsync(gr->entries, ent.data(), (size_t)nent * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("graph build: ") + hipGetErrorString(e)));
+  *out = gr;
+  return MI_OK;
+}
+
+int mi_graph_info(const mi_graph* gr, int64_t* n, int32_t* R, int32_t* ne) {
+  REQUIRE(gr, "null handle");
+  if (n) *n = gr->n;
+  if (R) *R = gr->R;
+  if (ne) *ne = gr->ne;
+  return MI_OK;
+}
+
+int mi_graph_get_neighbors(mi_graph* gr, int64_t row0, int64_t nrows, int32_t* out_host) {
+  REQUIRE(gr, "null handle");
+  REQUIRE(nrows >= 0 && row0 >= 0, "negative row range");
+  REQUIRE(nrows == 0 || out_host, "null pointer: out");
+  REQUIRE(row0 + nrows <= gr->n, "row range beyond the table");
+  if (nrows == 0) return MI_OK;
+  std::lock_guard<std::mutex> lock(gr->mu);
+  HIPC(hipSetDevice(gr->rows->device));
+  HIPC(hipMemcpy(out_host, gr->adj + (size_t)row0 * gr->R, (size_t)nrows * gr->R * 4, hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+int mi_graph_get_entries(mi_graph* gr, int32_t* out_host) {
+  REQUIRE(gr, "null handle");
+  REQUIRE(out_host, "null pointer: out");
+  std::lock_guard<std::mutex> lock(gr->mu);
+  HIPC(hipSetDevice(gr->rows->device));
+  HIPC(hipMemcpy(out_host, gr->entries, (size_t)gr->ne * 4, hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+int mi_graph_destroy(mi_graph* gr) {
+  if (!gr) return MI_OK;
+  (void)hipSetDevice(gr->rows->device);
+  (void)hipDeviceSynchronize();
+  graph_free(gr);
+  return MI_OK;
+}
+
+int mi_graph_search_device(mi_graph* gr, const float* q_dev, int64_t nq, int32_t k, int32_t ef, int64_t* out_idx_dev,
+                           float* out_val_dev, double* out_val64_dev, int32_t* out_visited_dev, void* stream) {
+  int rc = graph_search_check(gr, nq, k, ef);
+  if (rc != MI_OK) return rc;
+  REQUIRE(nq == 0 || q_dev, "null pointer: queries");
+  REQUIRE(nq == 0 || out_idx_dev, "null pointer: out_idx");
+  if (nq == 0) return MI_OK;
+  if ((rc = graph_fresh(gr)) != MI_OK) return rc;
+  HIPC(hipSetDevice(gr->rows->device));
+  return graph_enqueue(gr, q_dev, MI_F32, gr->rows->ud, 1, nq, k, ef, out_idx_dev, out_val_dev, out_val64_dev, out_visited_dev,
+                       (hipStream_t)stream);
+}
+
+int mi_graph_search(mi_graph* gr, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                    int32_t ef, int64_t* out_idx, float* out_val, double* out_val64, int32_t* out_visited, double* out_seconds) {
+  int rc = graph_search_check(gr, nq, k, ef);
+  if (rc != MI_OK) return rc;
+  REQUIRE(nq == 0 || q, "null pointer: queries");
+  REQUIRE(nq == 0 || out_idx, "null pointer: out_idx");
+  REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  if (out_seconds) *out_seconds = 0.0;
+  if (nq == 0) return MI_OK;
+  std::lock_guard<std::mutex> lock(gr->mu);
+  mi_gallery* g = gr->rows;
+  std::lock_guard<std::mutex> lock_rows(g->mu);
+  if ((rc = graph_fresh(gr)) != MI_OK) return rc;
+  const auto t0 = std::chrono::steady_clock::now();
+  HIPC(hipSetDevice(g->device));
+  hipStream_t s = g->stream;
+  int64_t elems;
+  if ((rc = strided_extent(nq, g->ud, row_stride, col_stride, &elems)) != MI_OK) return rc;
+  const size_t esz = dtype == MI_F32 ? 4 : 8;
+  char* raw = (char*)gr->qraw;
+  rc = graph_grow(&raw, &gr->qraw_cap, (size_t)elems * esz);
+  gr->qraw = raw;
+  if (rc != MI_OK) return rc;
+  const size_t cnt = (size_t)nq * k;
+  if ((rc = graph_grow(&gr->oidx, &gr->oidx_cap, cnt)) != MI_OK || (rc = graph_grow(&gr->oval, &gr->oval_cap, cnt)) != MI_OK ||
+      (rc = graph_grow(&gr->oval64, &gr->oval64_cap, cnt)) != MI_OK || (rc = graph_grow(&gr->ovis, &gr->ovis_cap, (size_t)nq)) != MI_OK)
+    return rc;
+  HIPC(hipMemcpyAsync(gr->qraw, q, (size_t)elems * esz, hipMemcpyHostToDevice, s));
+  if ((rc = graph_enqueue(gr, gr->qraw, dtype, row_stride, col_stride, nq, k, ef, gr->oidx, gr->oval, gr->oval64, gr->ovis, s)) !=
+      MI_OK)
+    return rc;
+  HIPC(hipMemcpyAsync(out_idx, gr->oidx, cnt * 8, hipMemcpyDeviceToHost, s));
+  if (out_val) HIPC(hipMemcpyAsync(out_val, gr->oval, cnt * 4, hipMemcpyDeviceToHost, s));
+  if (out_val64) HIPC(hipMemcpyAsync(out_val64, gr->oval64, cnt * 8, hipMemcpyDeviceToHost, s));
+  if (out_visited) HIPC(hipMemcpyAsync(out_visited, gr->ovis, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  return MI_OK;
+}
+
+}  // extern "C"

@@ -20,6 +20,8 @@
 //   api_ivfpq.hip     IVF index over PQ codes (mi_ivfpq): coarse lists as chains of 64-slot blocks, exact ADC top-K over the probed lists
 //                     (row removal of both PQ handles: mi_pq_remove_rows in api_pq.hip, mi_ivfpq_remove_rows here; kernels in pq_remove.hip)
 //   api_lsh.hip       LSH codes (mi_lsh_encode*, mi_hamming_append_lsh_device): f64 projection to sign bits, fused (lsh.hip)
+//   api_graph.hip     graph index (mi_graph): neighbour table over a gallery's rows, best-first search (graph_search.hip), table
+//                     from exact nearest-neighbour lists (graph_build.hip)
 #pragma once
 #include "../../include/mi355_retrieval.h"
 

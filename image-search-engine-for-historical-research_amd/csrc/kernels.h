@@ -286,6 +286,24 @@ void launch_refine(const float* gal_f32, const float* qry, int32_t dp, int32_t d
                    const int64_t* cand, int32_t kc, int64_t cand_stride, int32_t k, int64_t nq, double* val, int64_t* out_idx,
                    float* out_val, double* out_val64, hipStream_t stream);
 
+// graph_search.hip -- best-first search of a neighbour graph on the stored f32 rows (api_graph.hip; values by l2_wave.h): one
+// workgroup per query, W (the best ef rows, sorted) in LDS, an exact visited bitmap of vis_words 32-bit words per query in `vis`
+// ([nq][vis_words], all zero when the launch starts).  adj [n][R] int32 (-1 = padding), entries [ne <= 64], 1 <= k <= ef <=
+// GRAPH_MAX_EF, R <= GRAPH_MAX_R.  out_val, out_val64, out_visited may be NULL.
+constexpr int GRAPH_MAX_EF = 2048, GRAPH_MAX_R = 64, GRAPH_MAX_ENTRIES = 64;
+void launch_graph_search(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int64_t row_offset, int l2,
+                         const int32_t* adj, int32_t R, const int32_t* entries, int32_t ne, int32_t k, int32_t ef, int64_t nq,
+                         uint32_t* vis, int64_t vis_words, int64_t* out_idx, float* out_val, double* out_val64,
+                         int32_t* out_visited, hipStream_t stream);
+// graph_build.hip -- the table of mi_graph_build from exact nearest-neighbour lists: forward lists F [n][R] out of a batch of
+// search answers, reverse-edge counts and their 64-bit exclusive prefix off [n + 1], then fill / select / compose (cnt and fill
+// [n] zeroed by the caller, edges [off[n]], B [n][R] scratch)
+void launch_graph_forward(const int64_t* ids, int32_t ks, int64_t row0, int64_t b, int64_t row_offset, int64_t n, int32_t R,
+                          int32_t* F, hipStream_t stream);
+void launch_graph_rev_count(const int32_t* F, int64_t n, int32_t R, uint32_t* cnt, unsigned long long* off, hipStream_t stream);
+void launch_graph_table(const int32_t* F, int64_t n, int32_t R, const unsigned long long* off, uint32_t* fill,
+                        unsigned long long* edges, int32_t* B, int32_t* adj, hipStream_t stream);
+
 // hamming.hip -- exact Hamming top-K on packed binary codes (api_hamming.hip): gallery blocks of 64 rows with transposed words
 // codes[block][w < ceil(nbits / 32)][64], queries as row-major words [nq][hamming_query_words(W32)], uint16 distance matrix
 // [nq][round_up(n, 64)] (0xFFFF = row not admitted), counting selection by (distance asc, id asc)

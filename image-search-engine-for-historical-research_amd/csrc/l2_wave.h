@@ -1,5 +1,5 @@
-// The wave-level arithmetic of the squared-L2 metric, shared by the tail of the flat search (l2_metric.hip) and the re-ranking
-// of shortlists (refine.hip): both give a (query, row) pair the same bits.  DESIGN.md 5.11, 5.15.
+// The wave-level arithmetic of the squared-L2 metric, shared by the tail of the flat search (l2_metric.hip), the re-ranking
+// of shortlists (refine.hip) and the graph search (graph_search.hip): all give a (query, row) pair the same bits.  DESIGN.md 5.11, 5.15.
 #pragma once
 #include "common.h"
 
@@ -23,6 +23,20 @@ __device__ __forceinline__ double l2_direct_wave(const float* __restrict__ q, co
     if (c + 1 < d) acc = __builtin_fma(d1, d1, acc);
     if (c + 2 < d) acc = __builtin_fma(d2, d2, acc);
     if (c + 3 < d) acc = __builtin_fma(d3, d3, acc);
+  }
+  return l2_wave_sum(acc);
+}
+
+// sum_j q_j g_j over d columns by one wave: l2_direct_wave's walk with the product in place of the squared difference (products of
+// f32 values are exact in f64, so every FMA rounds once, as rescore_kernel's sum does: select.hip)
+__device__ __forceinline__ double refine_dot_wave(const float* __restrict__ q, const float* __restrict__ g, int32_t d, int lane) {
+  double acc = 0.0;
+  for (int32_t c = 4 * lane; c < d; c += 256) {
+    const float4 a = *reinterpret_cast<const float4*>(q + c), b = *reinterpret_cast<const float4*>(g + c);
+    acc = __builtin_fma((double)a.x, (double)b.x, acc);
+    if (c + 1 < d) acc = __builtin_fma((double)a.y, (double)b.y, acc);
+    if (c + 2 < d) acc = __builtin_fma((double)a.z, (double)b.z, acc);
+    if (c + 3 < d) acc = __builtin_fma((double)a.w, (double)b.w, acc);
   }
   return l2_wave_sum(acc);
 }

@@ -17,20 +17,6 @@ namespace mi {
 
 constexpr int REFINE_SLAB = 8;          // candidates per gather workgroup (4 waves, two rows each)
 
-// sum_j q_j g_j over d columns by one wave: l2_direct_wave's walk with the product in place of the squared difference (products of
-// f32 values are exact in f64, so every FMA rounds once, as rescore_kernel's sum does: select.hip)
-__device__ __forceinline__ double refine_dot_wave(const float* __restrict__ q, const float* __restrict__ g, int32_t d, int lane) {
-  double acc = 0.0;
-  for (int32_t c = 4 * lane; c < d; c += 256) {
-    const float4 a = *reinterpret_cast<const float4*>(q + c), b = *reinterpret_cast<const float4*>(g + c);
-    acc = __builtin_fma((double)a.x, (double)b.x, acc);
-    if (c + 1 < d) acc = __builtin_fma((double)a.y, (double)b.y, acc);
-    if (c + 2 < d) acc = __builtin_fma((double)a.z, (double)b.z, acc);
-    if (c + 3 < d) acc = __builtin_fma((double)a.w, (double)b.w, acc);
-  }
-  return l2_wave_sum(acc);
-}
-
 // qry [nq][dp] (16-byte aligned rows, d columns used), cand [nq][cand_stride], val [nq][kc].  A padding candidate gets no value
 // here: the sort kernel decides padding from the id again and never reads its slot.
 template <bool L2>

@@ -499,8 +499,76 @@ def matching_Nano_PQ_hip(K, embedded_features_train, embedded_features_test, dat
     return idx, (t2 - t1) / max(num_test, 1)
 
 
+def _graph_path(dataset, R):
+    return os.path.join(os.path.dirname(_gallery_path(dataset)), "mi355_graph_R%d.npz" % R)
+
+
+def matching_HNSW_hip(K, embedded_features_train, embedded_features_test, dataset=None, m=4, ef=8, ifgenerate=True):
+    """Same signature and return shape as matching_HNSW (src/utils/nnsearch.py:487-538), `--matching_method HNSW`: a neighbour
+    graph over the database rows under squared Euclidean distance, searched best-first with a candidate list of K rows (the
+    reference searches with ef=K, :531; its `ef` argument is efConstruction, which this build has no use for and ignores)
+    -> (idx int64 [Q, K], time_per_query).  THE GRAPH IS THIS LIBRARY'S, not the reference's: _lib.GraphIndex.build with
+    R = 2 * m neighbours per row (faiss's and the reference's bottom-layer degree m0) -- each row's m nearest rows, up to m
+    reverse edges and further nearest rows, from the exact search, with 16 evenly spaced entry rows -- not an insertion-order HNSW
+    with layers, and nothing pins it to that graph.  What is exact is the search GIVEN the graph: float64
+    direct-form distances, ties to the lower index.  Where fewer than K rows are reached the tail is filled with the lowest
+    indices not in the answer, as :532-534 does.  With a `dataset` the table and the entry rows persist as
+    outputs/<dataset>/mi355_graph_R<R>.npz (written to a temporary name and renamed): built and written iff `ifgenerate`,
+    otherwise loaded -- a missing file raises FileNotFoundError, as the reference's open() does; dataset=None writes nothing (and
+    needs ifgenerate).  1 <= m <= 32, 1 <= K <= min(N, 2048), N >= 2.  The timer spans what the reference's spans (:528-536):
+    the search only, device-synchronised.  Bad input raises ValueError before the device is touched."""
+    train, test = np.asarray(embedded_features_train), np.asarray(embedded_features_test)
+    if train.ndim != 2 or test.ndim != 2 or train.shape[1] != test.shape[1]:
+        raise ValueError("expected rows [N, dim] and queries [Q, dim], got %s and %s" % (train.shape, test.shape))
+    for name, a in (("embedded_features_train", train), ("embedded_features_test", test)):
+        if not np.issubdtype(a.dtype, np.floating):
+            raise ValueError("%s must be a floating-point array (got %s)" % (name, a.dtype))
+    K, m = int(K), int(m)
+    if m < 1 or 2 * m > _lib.GRAPH_MAX_R:
+        raise ValueError("m = %d: the graph holds R = 2 * m <= %d neighbours per row" % (m, _lib.GRAPH_MAX_R))
+    R = 2 * m
+    num_train, num_test = train.shape[0], test.shape[0]
+    if K < 1 or K > num_train:
+        raise ValueError("K = %d, the database holds %d rows" % (K, num_train))
+    if K > TOPK_PATH_MAX_K:
+        raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
+    _lib._graph_build_shape(num_train, R, 16)
+    if dataset is None and not ifgenerate:
+        raise ValueError("ifgenerate=False loads the graph of a dataset: give one")
+    if not ifgenerate:
+        with np.load(_graph_path(dataset, R)) as z:                 # (FileNotFoundError when it was never generated)
+            table, entries = _lib._graph_table(num_train, z["neighbors"], z["entries"])
+        if table.shape[1] != R:
+            raise ValueError("stored table of shape %s, this call takes [%d, %d]" % (table.shape, num_train, R))
+    rows = Gallery.l2_from_host(train)
+    try:
+        if ifgenerate:
+            g = _lib.GraphIndex.build(rows, R=R, n_entry=16)
+        else:
+            g = _lib.GraphIndex.from_neighbors(rows, table, entries)
+        with g:
+            if ifgenerate and dataset is not None:
+                path = _graph_path(dataset, R)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                tmp = "%s.tmp.%d.%s.npz" % (path, os.getpid(), uuid.uuid4().hex[:12])
+                with _path_lock(path):
+                    np.savez(tmp, neighbors=g.neighbors, entries=g.entries)
+                    os.replace(tmp, path)
+            t1 = time.time()
+            idx, _, _ = g.search(test, K, ef=K)            # (synchronous: the results are on the host when it returns)
+            t2 = time.time()
+    finally:
+        rows.close()
+    for row in np.flatnonzero((idx < 0).any(axis=1)):
+        got = idx[row][idx[row] >= 0]
+        miss = np.flatnonzero(~np.isin(np.arange(num_train), got))
+        idx[row] = np.concatenate((got, miss))[:K]
+    return idx, (t2 - t1) / max(num_test, 1)
+
+
 # the matchers of this build by the name the reference's entry points dispatch on (--matching_method, src/offline.py:107-118)
-MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip, "PQ": matching_Nano_PQ_hip}
+MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip, "PQ": matching_Nano_PQ_hip,
+                    "HNSW": matching_HNSW_hip}
 
 
 def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test):

@@ -218,6 +218,56 @@ int mi_refine(mi_gallery* rows, const void* q, int64_t nq, int dtype, int64_t ro
 int mi_debug_l2_tail_device(mi_gallery* g, const float* q_dev, int64_t nq, const int64_t* ids_dev, int32_t ke, int32_t k,
                             int64_t* out_idx_dev, double* out_dist64_dev, void* stream);
 
+/* ---- graph index: best-first search of a neighbour graph over the rows of a gallery, the role of the reference's HNSW matchers
+ * (matching_HNSW and its kin, src/utils/nnsearch.py:59-538).  DESIGN.md 5.16.  What is approximate is WHICH rows the graph
+ * reaches; everything else is an exact, deterministic function of graph, entry rows, stored rows and query.
+ * A handle sits over ONE gallery `rows` (one shard on one device, squared-L2 or inner product, as for mi_refine), which must
+ * outlive it.  It holds a neighbour table int32 [n][R] of LOCAL rows, -1 being padding anywhere in a row, and ne entry rows.
+ * The VALUE of a row for a query is mi_refine's: on an L2 gallery the direct-form float64 squared distance (the bits of
+ * mi_knn_search_l2), smaller is better; on any other gallery the float64 inner product against the stored row, larger is better.
+ * The ORDER is (value best first, id ascending).  Per query, with 1 <= k <= ef <= 2048:
+ *   start   the distinct entry rows are visited and evaluated; W is the best ef of them in the order; none is expanded;
+ *   step    the first row of W (in the order) that is not yet expanded is marked expanded; of its R table entries the -1s, ids
+ *           outside [0, n), repeats within the row and rows already visited are dropped, the rest are marked visited and
+ *           evaluated; W becomes the best ef of W plus the new rows.  A row pushed out of W is never expanded and stays visited;
+ *   stop    when every row of W is expanded (and after n expansions at the latest, whatever the table holds);
+ *   answer  the first k rows of W: ids row_offset + local row (int64), values float64 (out_val64, may be NULL) with their f32
+ *           cast (out_val, may be NULL); fewer than k rows in W: trailing ids -1, values +INFINITY (L2) or -INFINITY.
+ *           out_visited (int32 [nq], may be NULL): the number of rows evaluated, entries included.
+ * Without ties among values this is the reference's HNSW._search_graph (:321-350) on its bottom layer; with ties the order above
+ * decides, not the accidents of Python's heaps.  The visited set is exact (a bitmap of n bits per query).
+ * mi_graph_create takes a caller's table (a pickled HNSW bottom layer, a ring, ...): neighbors [n][R] packed int32 in host or
+ * device memory, n the gallery's rows, 1 <= R <= 64; entries int32 [ne] in host memory, 1 <= ne <= 64.  An entry outside [0, n) or
+ * a table value below -1 or >= n is MI_ERR_INVALID; self-loops and repeats are legal (the visited rule disposes of them).
+ * mi_graph_build makes the table on the device, R even in [2, 64], 1 <= ne <= 64, n >= 2, the same bytes on every call:
+ *   F(i)  the min(R, n - 1) nearest other rows of row i in the order, by the exact search of the gallery on its own stored rows
+ *         with k = min(R + 1, n) (verified loop), i dropped from the answer -- or the last row where i is absent, which more than
+ *         R identical rows can cause;
+ *   B(i)  with h = R / 2, the rows j such that i is among the first h of F(j), ordered by (position of i in F(j), j);
+ *   N(i)  F(i)[:h], then the first h rows of B(i) not yet present, then the rows of F(i)[h:] not yet present, R at most, -1 behind;
+ *   entries  row floor(t * n / ne') for t = 0 .. ne' - 1, ne' = min(ne, n).
+ * The handle records the gallery's n: after mi_gallery_append* or mi_gallery_remove_rows a search returns MI_ERR_INVALID and
+ * reads no stale table.  Not built: updating a graph in place, HNSW's upper layers and insertion-order construction, an allow
+ * bitmap, sharding. */
+typedef struct mi_graph mi_graph; /* opaque */
+int mi_graph_create(mi_gallery* rows, const int32_t* neighbors, int32_t R, int neighbors_memspace, const int32_t* entries,
+                    int32_t ne, mi_graph** out);
+int mi_graph_build(mi_gallery* rows, int32_t R, int32_t ne, mi_graph** out);
+/* n, R, ne (any may be NULL); the table rows [row0, row0 + nrows) and the ne entries into host memory */
+int mi_graph_info(const mi_graph* gr, int64_t* n, int32_t* R, int32_t* ne);
+int mi_graph_get_neighbors(mi_graph* gr, int64_t row0, int64_t nrows, int32_t* out_host);
+int mi_graph_get_entries(mi_graph* gr, int32_t* out_host);
+int mi_graph_destroy(mi_graph* gr);
+/* Host form: queries of any strides and dtype as in mi_knn_search_l2 (f64 rounded to f32), used as given; synchronous, on the
+ * gallery's stream.  nq == 0 is MI_OK and writes nothing. */
+int mi_graph_search(mi_graph* gr, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                    int32_t ef, int64_t* out_idx, float* out_val, double* out_val64, int32_t* out_visited, double* out_seconds);
+/* q_dev [nq][d] packed f32; enqueued on `stream`, no synchronisation.  It stages the queries and the visited bitmaps in buffers
+ * of the handle (grown when a larger call comes; a batch whose bitmaps would exceed 256 MiB runs in chunks of queries): calls on
+ * one handle must be serialised by the caller and enqueued on ONE stream. */
+int mi_graph_search_device(mi_graph* gr, const float* q_dev, int64_t nq, int32_t k, int32_t ef, int64_t* out_idx_dev,
+                           float* out_val_dev, double* out_val64_dev, int32_t* out_visited_dev, void* stream);
+
 /* ---- binary index: exact Hamming top-K on packed binary codes.  The reference's matching_Greedyhash(K, hash_codes_train,
  * hash_codes_test) (src/utils/nnsearch.py:1001-1013: XOR against every gallery code, sum, argsort, first K) and faiss
  * IndexBinaryFlat (what IndexLSH, src/utils/nnsearch.py:734-745, searches with internally).  DESIGN.md 5.13.
