@@ -65,18 +65,6 @@ void filter_release_sub(mi_gallery* g) {
   f.valid = false;
 }
 
-// grow-only device buffers (contents are not kept)
-template <typename T>
-static int grow(T** p, size_t* cap, size_t count) {
-  if (*p && *cap >= count) return MI_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = count + count / 4 + 64;
-  HIPC(device_malloc((void**)p, want * sizeof(T)));
-  *cap = want;
-  return MI_OK;
-}
 template <typename A, typename B>
 static int grow2(A** a, B** b, size_t* cap, size_t count) {
   if (*a && *b && *cap >= count) return MI_OK;
@@ -85,7 +73,7 @@ static int grow2(A** a, B** b, size_t* cap, size_t count) {
   (void)hipFree(*b);
   *a = nullptr, *b = nullptr, *cap = 0;
   int rc;
-  if ((rc = grow(a, &ca, count)) != MI_OK || (rc = grow(b, &cb, count)) != MI_OK) return rc;
+  if ((rc = device_grow(a, &ca, count)) != MI_OK || (rc = device_grow(b, &cb, count)) != MI_OK) return rc;
   *cap = std::min(ca, cb);
   return MI_OK;
 }
@@ -136,7 +124,7 @@ static int sub_prepare(mi_gallery* g, const std::vector<uint64_t>& key, const ui
     mi_gallery* sg = f.sub;
     const int64_t nblk = filter_blocks(g->n);
     int rc;
-    if ((rc = grow(&f.rows, &f.rows_cap, (size_t)allowed)) != MI_OK) return rc;
+    if ((rc = device_grow(&f.rows, &f.rows_cap, (size_t)allowed)) != MI_OK) return rc;
     if ((rc = grow2(&f.bcnt, &f.boff, &f.blk_cap, (size_t)nblk + 1)) != MI_OK) return rc;
     const int64_t mpad = round_up(allowed, TILE);
     launch_filter_compact(bits_dev, g->n, f.bcnt, f.boff, f.rows, s);
@@ -299,7 +287,7 @@ int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, in
   const uint64_t* bits_dev = allow_memspace == MI_DEVICE ? allow_bits : nullptr;
   auto upload_bits = [&]() -> int {
     if (bits_dev) return MI_OK;
-    int r = grow(&f.bits, &f.bits_cap, (size_t)nwords);
+    int r = device_grow(&f.bits, &f.bits_cap, (size_t)nwords);
     if (r != MI_OK) return r;
     HIPC(hipMemcpy(f.bits, key.data(), (size_t)nwords * 8, hipMemcpyHostToDevice));
     bits_dev = f.bits;
@@ -324,7 +312,7 @@ int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, in
   float* tsc = (float*)stage(2, (size_t)nq * kp * 4);
   if (!tidx || !tsc) return done(fail(MI_ERR_NOMEM, "staging buffers of mi_knn_search_filtered"));
   if ((rc = grow2(&f.idx, &f.sc, &f.out_cap, (size_t)nq * k)) != MI_OK) return done(rc);
-  if ((rc = grow(&f.ok, &f.ok_cap, (size_t)nq)) != MI_OK) return done(rc);
+  if ((rc = device_grow(&f.ok, &f.ok_cap, (size_t)nq)) != MI_OK) return done(rc);
   if ((rc = search_sync(g, qd, dtype, row_stride, col_stride, g->norm_mode, nq, kp, tidx, tsc, nullptr)) != MI_OK)
     return done(rc);
   launch_filter_overfetch(tidx, tsc, nq, kp, k, bits_dev, g->n, g->row_offset, covers, f.idx, f.sc, f.ok, s);
@@ -351,7 +339,7 @@ int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, in
     else
       for (int32_t c = 0; c < d; ++c) std::memcpy(dst + (size_t)c * esz, src + (size_t)c * col_stride * esz, esz);
   }
-  if ((rc = grow(reinterpret_cast<char**>(&f.qbuf), &f.qbuf_cap, packed.size())) != MI_OK) return done(rc);
+  if ((rc = device_grow(reinterpret_cast<char**>(&f.qbuf), &f.qbuf_cap, packed.size())) != MI_OK) return done(rc);
   if (hipMemcpy(f.qbuf, packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess)
     return done(fail(MI_ERR_HIP, "H2D copy of the re-run queries failed"));
   std::vector<int64_t> ridx((size_t)m * k);

@@ -30,18 +30,6 @@ struct mi_graph {
 constexpr size_t GRAPH_VIS_BYTES = (size_t)256 << 20;
 constexpr int64_t GRAPH_BUILD_BATCH = 8192;      // rows per exact search of mi_graph_build
 
-template <typename T>
-static int graph_grow(T** p, size_t* cap, size_t count) {
-  if (*p && *cap >= count) return MI_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = count + count / 4 + 64;
-  HIPC(device_malloc((void**)p, want * sizeof(T)));
-  *cap = want;
-  return MI_OK;
-}
-
 static void graph_free(mi_graph* gr) {
   for (void* p : {(void*)gr->adj, (void*)gr->entries, gr->qraw, (void*)gr->qpad, (void*)gr->vis, (void*)gr->oidx, (void*)gr->oval,
                   (void*)gr->oval64, (void*)gr->ovis})
@@ -68,10 +56,10 @@ static int graph_enqueue(mi_graph* gr, const void* src, int dtype, int64_t rs, i
                          int64_t* out_idx, float* out_val, double* out_val64, int32_t* out_visited, hipStream_t s) {
   mi_gallery* g = gr->rows;
   int rc;
-  if ((rc = graph_grow(&gr->qpad, &gr->qpad_cap, (size_t)nq * g->dp)) != MI_OK) return rc;
+  if ((rc = device_grow(&gr->qpad, &gr->qpad_cap, (size_t)nq * g->dp)) != MI_OK) return rc;
   const int64_t words = (gr->n + 31) / 32;
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(GRAPH_VIS_BYTES / 4) / words));
-  if ((rc = graph_grow(&gr->vis, &gr->vis_cap, (size_t)chunk * words)) != MI_OK) return rc;
+  if ((rc = device_grow(&gr->vis, &gr->vis_cap, (size_t)chunk * words)) != MI_OK) return rc;
   launch_l2_augment(src, dtype, nq, g->ud, rs, cs, gr->qpad, g->dp, s);
   for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
     const int64_t b = std::min<int64_t>(chunk, nq - q0);
@@ -286,12 +274,12 @@ int mi_graph_search(mi_graph* gr, const void* q, int64_t nq, int dtype, int64_t 
   if ((rc = strided_extent(nq, g->ud, row_stride, col_stride, &elems)) != MI_OK) return rc;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   char* raw = (char*)gr->qraw;
-  rc = graph_grow(&raw, &gr->qraw_cap, (size_t)elems * esz);
+  rc = device_grow(&raw, &gr->qraw_cap, (size_t)elems * esz);
   gr->qraw = raw;
   if (rc != MI_OK) return rc;
   const size_t cnt = (size_t)nq * k;
-  if ((rc = graph_grow(&gr->oidx, &gr->oidx_cap, cnt)) != MI_OK || (rc = graph_grow(&gr->oval, &gr->oval_cap, cnt)) != MI_OK ||
-      (rc = graph_grow(&gr->oval64, &gr->oval64_cap, cnt)) != MI_OK || (rc = graph_grow(&gr->ovis, &gr->ovis_cap, (size_t)nq)) != MI_OK)
+  if ((rc = device_grow(&gr->oidx, &gr->oidx_cap, cnt)) != MI_OK || (rc = device_grow(&gr->oval, &gr->oval_cap, cnt)) != MI_OK ||
+      (rc = device_grow(&gr->oval64, &gr->oval64_cap, cnt)) != MI_OK || (rc = device_grow(&gr->ovis, &gr->ovis_cap, (size_t)nq)) != MI_OK)
     return rc;
   HIPC(hipMemcpyAsync(gr->qraw, q, (size_t)elems * esz, hipMemcpyHostToDevice, s));
   if ((rc = graph_enqueue(gr, gr->qraw, dtype, row_stride, col_stride, nq, k, ef, gr->oidx, gr->oval, gr->oval64, gr->ovis, s)) !=

@@ -22,6 +22,7 @@
 //   api_lsh.hip       LSH codes (mi_lsh_encode*, mi_hamming_append_lsh_device): f64 projection to sign bits, fused (lsh.hip)
 //   api_graph.hip     graph index (mi_graph): neighbour table over a gallery's rows, best-first search (graph_search.hip), table
 //                     from exact nearest-neighbour lists (graph_build.hip)
+// Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index family)
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -415,7 +416,22 @@ MI_INTERNAL void l2_scratch_free(mi_gallery* g);
 MI_INTERNAL void refine_scratch_free(mi_gallery* g);
 // ---- api_remove.hip
 MI_INTERNAL void remove_scratch_free(mi_gallery* g);
-// ---- api_pq.hip, api_pq_train.hip, api_ivfpq.hip: host rows (any strides, in elements) hold no NaN and no infinity
+// ---- helpers of the index handles (static: every translation unit has its own, nothing is exported)
+// a grow-only device buffer of `count` elements (contents are not kept): a quarter of spare, so that a slowly growing request does
+// not reallocate every call
+static inline size_t grow_capacity(size_t count) { return count + count / 4 + 64; }
+template <typename T>
+static int device_grow(T** p, size_t* cap, size_t count) {
+  if (*p && *cap >= count) return MI_OK;
+  (void)hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = grow_capacity(count);
+  HIPC(device_malloc((void**)p, want * sizeof(T)));
+  *cap = want;
+  return MI_OK;
+}
+// api_pq.hip, api_pq_train.hip, api_ivfpq.hip: host rows (any strides, in elements) hold no NaN and no infinity
 template <typename T>
 static bool pq_all_finite(const T* x, int64_t rows, int32_t d, int64_t rs, int64_t cs) {
   for (int64_t r = 0; r < rows; ++r)
@@ -423,6 +439,49 @@ static bool pq_all_finite(const T* x, int64_t rows, int32_t d, int64_t rs, int64
       if (!std::isfinite(x[r * rs + (int64_t)c * cs])) return false;
   return true;
 }
+// api_pq.hip, api_ivfpq.hip: the checks the host query entry points share
+static inline int check_host_queries(int32_t d, const void* q, int64_t nq, int dtype, int64_t rs, int64_t cs) {
+  REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
+  REQUIRE(rs >= 0 && cs >= 0, "negative strides are not supported");
+  const bool finite = dtype == MI_F32 ? pq_all_finite((const float*)q, nq, d, rs, cs) : pq_all_finite((const double*)q, nq, d, rs, cs);
+  REQUIRE(finite, "queries must be finite");
+  return MI_OK;
+}
+// the first m bytes of every row (code bytes, list ids) are below `limit`
+static inline bool codes_below(const uint8_t* p, int64_t rows, int64_t stride, int32_t m, int32_t limit) {
+  if (limit >= 256) return true;
+  for (int64_t r = 0; r < rows; ++r)
+    for (int32_t b = 0; b < m; ++b)
+      if (p[r * stride + b] >= limit) return false;
+  return true;
+}
+// `rows` host rows of d elements from row r0 on -> *xraw (grown to fit), packed [rows][d] in their own type, on `stream`.  Rows that
+// are not contiguous are packed on the host first, in `pack` (the copy has completed on return in that case)
+static inline int stage_host_rows(char** xraw, size_t* cap, int32_t d, hipStream_t stream, const void* x, int64_t r0, int64_t rows,
+                                  int dtype, int64_t rs, int64_t cs, std::vector<char>& pack) {
+  const size_t esz = dtype == MI_F32 ? 4 : 8;
+  const size_t bytes = (size_t)rows * d * esz;
+  int rc;
+  if ((rc = device_grow(xraw, cap, bytes)) != MI_OK) return rc;
+  const char* src = (const char*)x + (size_t)r0 * rs * esz;
+  if (!(cs == 1 && (rs == d || rows == 1))) {
+    pack.resize(bytes);
+    for (int64_t r = 0; r < rows; ++r)
+      for (int32_t c = 0; c < d; ++c)
+        std::memcpy(pack.data() + ((size_t)r * d + c) * esz, src + ((size_t)r * rs + (size_t)c * cs) * esz, esz);
+    src = pack.data();
+  }
+  HIPC(hipMemcpyAsync(*xraw, src, bytes, hipMemcpyHostToDevice, stream));
+  if (src == pack.data()) HIPC(hipStreamSynchronize(stream));
+  return MI_OK;
+}
+// rows handed to an index: the argument checks of mi_pq_add / mi_pq_encode and their mi_ivfpq counterparts
+#define REQUIRE_ROWS(x, rows, dtype, rs, cs, memspace)                                                       \
+  REQUIRE((rows) >= 0, "negative number of rows");                                                           \
+  REQUIRE((x) || (rows) == 0, "null pointer: rows");                                                         \
+  REQUIRE((dtype) == MI_F32 || (dtype) == MI_F64, "dtype must be MI_F32 or MI_F64");                         \
+  REQUIRE((rs) >= 0 && (cs) >= 0, "negative strides are not supported");                                     \
+  REQUIRE((memspace) == MI_HOST || (memspace) == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE")
 // entry points that are not defined on a squared-L2 gallery (include/mi355_retrieval.h: mi_metric)
 #define REFUSE_L2(g, what)                                                                                          \
   do {                                                                                                              \

@@ -45,49 +45,10 @@ struct mi_ivfpq {
   std::mutex mu;
 };
 
-template <typename T>
-static int ivf_grow(T** p, size_t* cap, size_t count) {
-  if (*p && *cap >= count) return MI_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = count + count / 4 + 64;
-  HIPC(device_malloc((void**)p, want * sizeof(T)));
-  *cap = want;
-  return MI_OK;
-}
-
 static int64_t ivf_scratch_bytes(const mi_ivfpq* h) {
   return (int64_t)(h->xraw_cap + h->cbytes_cap + h->lbytes_cap + h->slots_cap * 8 + h->tab_cap * 4 +
                    (h->praw_cap + h->pnorm_cap + h->pref_cap + h->pex_cap) * 4 + h->part_cap * 8 + h->bits_cap * 8 + h->oidx_cap * 8 +
                    h->odist_cap * 4 + h->rmpref_cap * 4);
-}
-
-static bool ivf_bytes_below(const uint8_t* p, int64_t rows, int64_t stride, int32_t m, int32_t limit) {
-  if (limit >= 256) return true;
-  for (int64_t r = 0; r < rows; ++r)
-    for (int32_t b = 0; b < m; ++b)
-      if (p[r * stride + b] >= limit) return false;
-  return true;
-}
-
-// `rows` host rows of d elements from row r0 on -> h->xraw, packed [rows][d] in their own type (api_pq.hip's pq_stage_rows)
-static int ivf_stage_rows(mi_ivfpq* h, const void* x, int64_t r0, int64_t rows, int dtype, int64_t rs, int64_t cs, std::vector<char>& pack) {
-  const size_t esz = dtype == MI_F32 ? 4 : 8;
-  const size_t bytes = (size_t)rows * h->d * esz;
-  int rc;
-  if ((rc = ivf_grow(&h->xraw, &h->xraw_cap, bytes)) != MI_OK) return rc;
-  const char* src = (const char*)x + (size_t)r0 * rs * esz;
-  if (!(cs == 1 && (rs == h->d || rows == 1))) {
-    pack.resize(bytes);
-    for (int64_t r = 0; r < rows; ++r)
-      for (int32_t c = 0; c < h->d; ++c)
-        std::memcpy(pack.data() + ((size_t)r * h->d + c) * esz, src + ((size_t)r * rs + (size_t)c * cs) * esz, esz);
-    src = pack.data();
-  }
-  HIPC(hipMemcpyAsync(h->xraw, src, bytes, hipMemcpyHostToDevice, h->stream));
-  if (src == pack.data()) HIPC(hipStreamSynchronize(h->stream));
-  return MI_OK;
 }
 
 // ---- host bookkeeping.  A failed call puts the lists back: rows it already scattered sit in slots beyond their list's fill,
@@ -153,7 +114,7 @@ static int ivf_scatter_rows(mi_ivfpq* h, const uint8_t* src_dev, int64_t stride,
   ivf_place(h, lists_host, rows, slots.data());
   // cannot happen while ivf_place's bound holds; a slot beyond the pool must never reach the scatter
   REQUIRE(h->pool_used <= h->pool_blocks, "internal: the block pool is exhausted");
-  if ((rc = ivf_grow(&h->slots, &h->slots_cap, (size_t)rows)) != MI_OK) return rc;
+  if ((rc = device_grow(&h->slots, &h->slots_cap, (size_t)rows)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(h->slots, slots.data(), (size_t)rows * 8, hipMemcpyHostToDevice, h->stream));
   launch_ivf_scatter(src_dev, stride, h->m, h->slots, row0, rows, h->codes, h->rowid, h->stream);
   HIPC(hipGetLastError());
@@ -192,7 +153,7 @@ static int ivf_ingest(mi_ivfpq* h, const void* codes, const uint8_t* list_ids, i
   const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / h->m);
   std::vector<int64_t> slots;
   rc = MI_OK;
-  if (memspace == MI_HOST) rc = ivf_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m);
+  if (memspace == MI_HOST) rc = device_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m);
   for (int64_t r = 0; r < rows && rc == MI_OK; r += step) {
     const int64_t mm = std::min(step, rows - r);
     const uint8_t* src = (const uint8_t*)codes + r * stride;
@@ -242,11 +203,11 @@ static int ivf_search_core(mi_ivfpq* h, const void* q_dev, int dtype, int64_t rs
                            : std::min<int64_t>({nq, 65535, budget / std::max<int64_t>(1, nslab * k * 8), ((int64_t)256 << 20) / (per * 4)});
   qc = std::max<int64_t>(1, qc);
   int rc;
-  if ((rc = ivf_grow(&h->tab, &h->tab_cap, (size_t)(qc * tabs))) != MI_OK) return rc;
-  if ((rc = ivf_grow(&h->praw, &h->praw_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
-  if ((rc = ivf_grow(&h->pnorm, &h->pnorm_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
-  if ((rc = ivf_grow(&h->pref, &h->pref_cap, (size_t)(qc * (nprobe + 1)))) != MI_OK) return rc;
-  if ((rc = ivf_grow(&h->part, &h->part_cap, (size_t)(qc * nslab * k))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->tab, &h->tab_cap, (size_t)(qc * tabs))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->praw, &h->praw_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->pnorm, &h->pnorm_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->pref, &h->pref_cap, (size_t)(qc * (nprobe + 1)))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->part, &h->part_cap, (size_t)(qc * nslab * k))) != MI_OK) return rc;
   // stage_ms (mi_ivfpq_search_stages_device): HIP events around the table and the scan of every chunk, read after each chunk
   // the guard destroys them on every way out of this function
   struct StageEvents {
@@ -295,21 +256,6 @@ static int ivf_search_core(mi_ivfpq* h, const void* q_dev, int dtype, int64_t rs
   return MI_OK;
 }
 
-static int ivf_check_host_queries(const mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t rs, int64_t cs) {
-  REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
-  REQUIRE(rs >= 0 && cs >= 0, "negative strides are not supported");
-  const bool finite = dtype == MI_F32 ? pq_all_finite((const float*)q, nq, h->d, rs, cs) : pq_all_finite((const double*)q, nq, h->d, rs, cs);
-  REQUIRE(finite, "queries must be finite");
-  return MI_OK;
-}
-
-#define REQUIRE_ROWS(x, rows, dtype, rs, cs, memspace)                                                       \
-  REQUIRE((rows) >= 0, "negative number of rows");                                                           \
-  REQUIRE((x) || (rows) == 0, "null pointer: rows");                                                         \
-  REQUIRE((dtype) == MI_F32 || (dtype) == MI_F64, "dtype must be MI_F32 or MI_F64");                         \
-  REQUIRE((rs) >= 0 && (cs) >= 0, "negative strides are not supported");                                     \
-  REQUIRE((memspace) == MI_HOST || (memspace) == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE")
-
 // mi_ivfpq_create and mi_ivfpq_create_residual: one body, the kind is the only difference
 static int ivf_create(bool residual, const float* coarse_host, int32_t nlist, const float* codebooks_host, int32_t d, int32_t m, int32_t ks,
                       const void* codes, const uint8_t* list_ids, int64_t n, int64_t row_stride_bytes, int memspace, int device,
@@ -335,8 +281,8 @@ static int ivf_create(bool residual, const float* coarse_host, int32_t nlist, co
   const size_t cb_count = (size_t)ks * d, co_count = (size_t)nlist * d;
   for (size_t i = 0; i < co_count; ++i) REQUIRE(std::isfinite(coarse_host[i]), "coarse centroids must be finite");
   for (size_t i = 0; i < cb_count; ++i) REQUIRE(std::isfinite(codebooks_host[i]), "codebooks must be finite");
-  REQUIRE(memspace != MI_HOST || ivf_bytes_below((const uint8_t*)codes, n, row_stride_bytes, m, ks), "a code byte is >= ks");
-  REQUIRE(memspace != MI_HOST || ivf_bytes_below(list_ids, n, 1, 1, nlist), "a list id is >= nlist");
+  REQUIRE(memspace != MI_HOST || codes_below((const uint8_t*)codes, n, row_stride_bytes, m, ks), "a code byte is >= ks");
+  REQUIRE(memspace != MI_HOST || codes_below(list_ids, n, 1, 1, nlist), "a list id is >= nlist");
   HIPC(hipSetDevice(device));
   mi_ivfpq* h = new mi_ivfpq();
   h->device = device;
@@ -419,8 +365,8 @@ int mi_ivfpq_append_codes(mi_ivfpq* h, const void* codes, const uint8_t* list_id
   std::lock_guard<std::mutex> lock(h->mu);
   REQUIRE(h->n + rows <= h->cap, "index capacity exceeded");
   if (rows == 0) return MI_OK;
-  REQUIRE(memspace != MI_HOST || ivf_bytes_below((const uint8_t*)codes, rows, row_stride_bytes, h->m, h->ks), "a code byte is >= ks");
-  REQUIRE(memspace != MI_HOST || ivf_bytes_below(list_ids, rows, 1, 1, h->nlist), "a list id is >= nlist");
+  REQUIRE(memspace != MI_HOST || codes_below((const uint8_t*)codes, rows, row_stride_bytes, h->m, h->ks), "a code byte is >= ks");
+  REQUIRE(memspace != MI_HOST || codes_below(list_ids, rows, 1, 1, h->nlist), "a list id is >= nlist");
   HIPC(hipSetDevice(h->device));
   return ivf_ingest(h, codes, list_ids, rows, row_stride_bytes, memspace);
 }
@@ -446,7 +392,7 @@ int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t ro
     const void* xp = (const char*)x + (size_t)r * row_stride * esz;
     int64_t rs = row_stride, cs = col_stride;
     if (memspace == MI_HOST) {
-      if ((rc = ivf_stage_rows(h, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+      if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
       xp = h->xraw;
       rs = h->d;
       cs = 1;
@@ -460,8 +406,8 @@ int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t ro
     HIPC(hipStreamSynchronize(s));
     return ivf_scatter_rows(h, h->cbytes, h->m, lists.data(), mk.n + r, mm, slots);
   };
-  int rc = ivf_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m);
-  if (rc == MI_OK) rc = ivf_grow(&h->lbytes, &h->lbytes_cap, (size_t)std::min(step, rows));
+  int rc = device_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m);
+  if (rc == MI_OK) rc = device_grow(&h->lbytes, &h->lbytes_cap, (size_t)std::min(step, rows));
   for (int64_t r = 0; r < rows && rc == MI_OK; r += step) rc = block(r, std::min(step, rows - r));
   if (rc == MI_OK) rc = ivf_publish(h);
   if (rc != MI_OK) {
@@ -479,7 +425,7 @@ int mi_ivfpq_residual_rows(mi_ivfpq* h, const void* x, int64_t rows, int dtype, 
   REQUIRE(out || rows == 0, "null pointer: out");
   REQUIRE(out_memspace == MI_HOST || out_memspace == MI_DEVICE, "out_memspace must be MI_HOST or MI_DEVICE");
   if (rows == 0) return MI_OK;
-  REQUIRE(!list_ids || memspace != MI_HOST || ivf_bytes_below(list_ids, rows, 1, 1, h->nlist), "a list id is >= nlist");
+  REQUIRE(!list_ids || memspace != MI_HOST || codes_below(list_ids, rows, 1, 1, h->nlist), "a list id is >= nlist");
   std::lock_guard<std::mutex> lock(h->mu);
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
@@ -499,15 +445,15 @@ int mi_ivfpq_residual_rows(mi_ivfpq* h, const void* x, int64_t rows, int dtype, 
   const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * 8));
   const int64_t most = std::min(step, rows);
   int rc;
-  if ((rc = ivf_grow(&h->lbytes, &h->lbytes_cap, (size_t)most)) != MI_OK) return rc;
-  if (out_memspace == MI_HOST && (rc = ivf_grow(&h->odist, &h->odist_cap, (size_t)(most * h->d))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->lbytes, &h->lbytes_cap, (size_t)most)) != MI_OK) return rc;
+  if (out_memspace == MI_HOST && (rc = device_grow(&h->odist, &h->odist_cap, (size_t)(most * h->d))) != MI_OK) return rc;
   std::vector<char> pack;
   for (int64_t r = 0; r < rows; r += step) {
     const int64_t mm = std::min(step, rows - r);
     const void* xp = (const char*)x + (size_t)r * row_stride * esz;
     int64_t rs = row_stride, cs = col_stride;
     if (memspace == MI_HOST) {
-      if ((rc = ivf_stage_rows(h, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+      if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
       xp = h->xraw;
       rs = h->d;
       cs = 1;
@@ -534,17 +480,17 @@ int mi_ivfpq_probe(mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t ro
   REQUIRE(nprobe <= h->nlist, "nprobe must be in [1, nlist]");
   if (nq == 0) return MI_OK;
   int rc;
-  if ((rc = ivf_check_host_queries(h, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
+  if ((rc = check_host_queries(h->d, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
   std::lock_guard<std::mutex> lock(h->mu);
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)h->d * (int64_t)esz));
-  if ((rc = ivf_grow(&h->praw, &h->praw_cap, (size_t)(std::min(step, nq) * nprobe))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->praw, &h->praw_cap, (size_t)(std::min(step, nq) * nprobe))) != MI_OK) return rc;
   std::vector<char> pack;
   for (int64_t q0 = 0; q0 < nq; q0 += step) {
     const int64_t b = std::min(step, nq - q0);
-    if ((rc = ivf_stage_rows(h, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+    if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
     launch_ivf_probe(h->xraw, dtype, h->d, 1, b, h->coarse, h->nlist, h->d, nprobe, h->praw, s);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(out_lists_host + q0 * nprobe, h->praw, (size_t)(b * nprobe) * 4, hipMemcpyDeviceToHost, s));
@@ -574,27 +520,27 @@ int mi_ivfpq_search(mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t r
   if (probes_host)
     for (int64_t i = 0; i < nq * nprobe; ++i) REQUIRE(probes_host[i] < h->nlist, "a probe entry is neither -1 nor in [0, nlist)");
   int rc;
-  if ((rc = ivf_check_host_queries(h, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
+  if ((rc = check_host_queries(h->d, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
   std::lock_guard<std::mutex> lock(h->mu);
   const auto t0 = std::chrono::steady_clock::now();
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t cnt = (size_t)nq * k;
-  if ((rc = ivf_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
-  if (out_dist && (rc = ivf_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
+  if ((rc = device_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
+  if (out_dist && (rc = device_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
   const uint64_t* allow_dev = allow_bits;
   if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
     const size_t words = (size_t)((h->n + 63) / 64);
-    if ((rc = ivf_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
+    if ((rc = device_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
     HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
     allow_dev = h->bits;
   }
   if (probes_host) {
-    if ((rc = ivf_grow(&h->pex, &h->pex_cap, (size_t)(nq * nprobe))) != MI_OK) return rc;
+    if ((rc = device_grow(&h->pex, &h->pex_cap, (size_t)(nq * nprobe))) != MI_OK) return rc;
     HIPC(hipMemcpyAsync(h->pex, probes_host, (size_t)(nq * nprobe) * 4, hipMemcpyHostToDevice, s));
   }
   std::vector<char> pack;
-  if ((rc = ivf_stage_rows(h, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+  if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
   if ((rc = ivf_search_core(h, h->xraw, dtype, h->d, 1, nq, k, nprobe, probes_host ? h->pex : nullptr, allow_dev, h->oidx,
                             out_dist ? h->odist : nullptr, s)) != MI_OK)
     return rc;
@@ -720,8 +666,8 @@ int mi_ivfpq_remove_rows(mi_ivfpq* h, const uint64_t* remove_bits, int memspace,
   if (plan.removed == 0) return MI_OK;                        // nothing changes
   const int64_t m = n - plan.removed;                         // n'
   const int64_t nwords = (n + 63) / 64;
-  if ((rc = ivf_grow(&h->bits, &h->bits_cap, (size_t)nwords)) != MI_OK) return rc;
-  if ((rc = ivf_grow(&h->rmpref, &h->rmpref_cap, (size_t)nwords + 1)) != MI_OK) return rc;
+  if ((rc = device_grow(&h->bits, &h->bits_cap, (size_t)nwords)) != MI_OK) return rc;
+  if ((rc = device_grow(&h->rmpref, &h->rmpref_cap, (size_t)nwords + 1)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(h->bits, plan.keep.data(), (size_t)nwords * 8, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(h->rmpref, plan.prefix.data(), ((size_t)nwords + 1) * 4, hipMemcpyHostToDevice, s));
   // the tables on the device are those of the last publish: the chains and fills before the removal

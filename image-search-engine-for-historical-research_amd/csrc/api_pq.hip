@@ -36,49 +36,9 @@ struct mi_pq {
   std::mutex mu;
 };
 
-template <typename T>
-static int pq_grow(T** p, size_t* cap, size_t count) {
-  if (*p && *cap >= count) return MI_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = count + count / 4 + 64;
-  HIPC(device_malloc((void**)p, want * sizeof(T)));
-  *cap = want;
-  return MI_OK;
-}
-
 static int64_t pq_scratch_bytes(const mi_pq* h) {
   return (int64_t)(h->xraw_cap + h->cbytes_cap + h->tab_cap * 4 + h->mat_cap * 4 + h->tidx_cap * 8 + h->tneg_cap * 4 + h->bits_cap * 8 +
                    h->oidx_cap * 8 + h->odist_cap * 4 + h->rmpref_cap * 4 + h->rmstage_cap * 4);
-}
-
-static bool pq_codes_below(const uint8_t* codes, int64_t rows, int64_t stride, int32_t m, int32_t ks) {
-  if (ks >= 256) return true;
-  for (int64_t r = 0; r < rows; ++r)
-    for (int32_t b = 0; b < m; ++b)
-      if (codes[r * stride + b] >= ks) return false;
-  return true;
-}
-
-// `rows` host rows of d elements from row r0 on -> h->xraw, packed [rows][d] in their own type, on the handle's stream.  Rows that
-// are not contiguous are packed on the host first, in `pack` (the copy has completed on return in that case)
-static int pq_stage_rows(mi_pq* h, const void* x, int64_t r0, int64_t rows, int dtype, int64_t rs, int64_t cs, std::vector<char>& pack) {
-  const size_t esz = dtype == MI_F32 ? 4 : 8;
-  const size_t bytes = (size_t)rows * h->d * esz;
-  int rc;
-  if ((rc = pq_grow(&h->xraw, &h->xraw_cap, bytes)) != MI_OK) return rc;
-  const char* src = (const char*)x + (size_t)r0 * rs * esz;
-  if (!(cs == 1 && (rs == h->d || rows == 1))) {
-    pack.resize(bytes);
-    for (int64_t r = 0; r < rows; ++r)
-      for (int32_t c = 0; c < h->d; ++c)
-        std::memcpy(pack.data() + ((size_t)r * h->d + c) * esz, src + ((size_t)r * rs + (size_t)c * cs) * esz, esz);
-    src = pack.data();
-  }
-  HIPC(hipMemcpyAsync(h->xraw, src, bytes, hipMemcpyHostToDevice, h->stream));
-  if (src == pack.data()) HIPC(hipStreamSynchronize(h->stream));
-  return MI_OK;
 }
 
 // rows of code bytes (host: checked by the caller; device: checked here) -> rows n .. n + rows of the index, synchronous on the
@@ -105,7 +65,7 @@ static int pq_ingest(mi_pq* h, const void* codes, int64_t rows, int64_t stride, 
   }
   const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / h->m);
   int rc;
-  if ((rc = pq_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
+  if ((rc = device_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
   for (int64_t r = 0; r < rows; r += step) {
     const int64_t mm = std::min(step, rows - r);
     const uint8_t* src = (const uint8_t*)codes + r * stride;
@@ -126,12 +86,12 @@ static int pq_encode_blocks(mi_pq* h, const void* x, int64_t rows, int dtype, in
   const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * (int64_t)esz));
   hipStream_t s = h->stream;
   int rc;
-  if ((rc = pq_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
+  if ((rc = device_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
   std::vector<char> pack;
   for (int64_t r = 0; r < rows; r += step) {
     const int64_t mm = std::min(step, rows - r);
     if (memspace == MI_HOST) {
-      if ((rc = pq_stage_rows(h, x, r, mm, dtype, rs, cs, pack)) != MI_OK) return rc;
+      if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, x, r, mm, dtype, rs, cs, pack)) != MI_OK) return rc;
       launch_pq_encode(h->xraw, dtype, h->d, 1, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
     } else {
       launch_pq_encode((const char*)x + (size_t)r * rs * esz, dtype, rs, cs, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
@@ -160,10 +120,10 @@ static int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, in
   const int32_t ke = (int32_t)std::min<int64_t>(k, npad);
   const int64_t per = (int64_t)h->m * h->ks;
   int rc;
-  if ((rc = pq_grow(&h->tab, &h->tab_cap, (size_t)(qc * per))) != MI_OK) return rc;
-  if ((rc = pq_grow(&h->mat, &h->mat_cap, (size_t)(qc * npad))) != MI_OK) return rc;
-  if ((rc = pq_grow(&h->tidx, &h->tidx_cap, (size_t)(qc * ke))) != MI_OK) return rc;
-  if ((rc = pq_grow(&h->tneg, &h->tneg_cap, (size_t)(qc * ke))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->tab, &h->tab_cap, (size_t)(qc * per))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->mat, &h->mat_cap, (size_t)(qc * npad))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->tidx, &h->tidx_cap, (size_t)(qc * ke))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->tneg, &h->tneg_cap, (size_t)(qc * ke))) != MI_OK) return rc;
   for (int64_t q0 = 0; q0 < nq; q0 += qc) {
     const int32_t b = (int32_t)std::min<int64_t>(qc, nq - q0);
     launch_pq_table((const char*)q_dev + (size_t)q0 * rs * esz, dtype, rs, cs, b, h->cb, h->m, h->ks, h->L, h->tab, s);
@@ -197,13 +157,6 @@ int remove_plan(const uint64_t* remove_bits, int memspace, int64_t n, RemovePlan
   return MI_OK;
 }
 
-#define REQUIRE_ROWS(x, rows, dtype, rs, cs, memspace)                                                       \
-  REQUIRE((rows) >= 0, "negative number of rows");                                                           \
-  REQUIRE((x) || (rows) == 0, "null pointer: rows");                                                         \
-  REQUIRE((dtype) == MI_F32 || (dtype) == MI_F64, "dtype must be MI_F32 or MI_F64");                         \
-  REQUIRE((rs) >= 0 && (cs) >= 0, "negative strides are not supported");                                     \
-  REQUIRE((memspace) == MI_HOST || (memspace) == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE")
-
 extern "C" {
 
 int mi_pq_create(const float* codebooks_host, int32_t d, int32_t m, int32_t ks, const void* codes, int64_t n, int64_t row_stride_bytes,
@@ -225,7 +178,7 @@ int mi_pq_create(const float* codebooks_host, int32_t d, int32_t m, int32_t ks, 
   REQUIRE(capacity < ((int64_t)1 << 32) - 64, "an index holds fewer than 2^32 - 64 rows");
   const size_t cb_count = (size_t)ks * d;
   for (size_t i = 0; i < cb_count; ++i) REQUIRE(std::isfinite(codebooks_host[i]), "codebooks must be finite");
-  REQUIRE(memspace != MI_HOST || pq_codes_below((const uint8_t*)codes, n, row_stride_bytes, m, ks), "a code byte is >= ks");
+  REQUIRE(memspace != MI_HOST || codes_below((const uint8_t*)codes, n, row_stride_bytes, m, ks), "a code byte is >= ks");
   HIPC(hipSetDevice(device));
   mi_pq* h = new mi_pq();
   h->device = device;
@@ -270,7 +223,7 @@ int mi_pq_append_codes(mi_pq* h, const void* codes, int64_t rows, int64_t row_st
   std::lock_guard<std::mutex> lock(h->mu);
   REQUIRE(h->n + rows <= h->cap, "index capacity exceeded");
   if (rows == 0) return MI_OK;
-  REQUIRE(memspace != MI_HOST || pq_codes_below((const uint8_t*)codes, rows, row_stride_bytes, h->m, h->ks), "a code byte is >= ks");
+  REQUIRE(memspace != MI_HOST || codes_below((const uint8_t*)codes, rows, row_stride_bytes, h->m, h->ks), "a code byte is >= ks");
   HIPC(hipSetDevice(h->device));
   const int rc = pq_ingest(h, codes, rows, row_stride_bytes, memspace);
   if (rc != MI_OK) return rc;
@@ -313,32 +266,23 @@ int mi_pq_encode(mi_pq* h, const void* x, int64_t rows, int dtype, int64_t row_s
   });
 }
 
-// the checks the two host query entry points share
-static int pq_check_host_queries(const mi_pq* h, const void* q, int64_t nq, int dtype, int64_t rs, int64_t cs) {
-  REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
-  REQUIRE(rs >= 0 && cs >= 0, "negative strides are not supported");
-  const bool finite = dtype == MI_F32 ? pq_all_finite((const float*)q, nq, h->d, rs, cs) : pq_all_finite((const double*)q, nq, h->d, rs, cs);
-  REQUIRE(finite, "queries must be finite");
-  return MI_OK;
-}
-
 int mi_pq_dtable(mi_pq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, float* out_table_host) {
   REQUIRE(h, "null handle");
   REQUIRE(nq >= 0, "nq must be >= 0");
   REQUIRE(nq == 0 || (q && out_table_host), "null pointer");
   if (nq == 0) return MI_OK;
   int rc;
-  if ((rc = pq_check_host_queries(h, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
+  if ((rc = check_host_queries(h->d, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
   std::lock_guard<std::mutex> lock(h->mu);
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const int64_t per = (int64_t)h->m * h->ks;
   const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / (per * 4));
-  if ((rc = pq_grow(&h->tab, &h->tab_cap, (size_t)(std::min(step, nq) * per))) != MI_OK) return rc;
+  if ((rc = device_grow(&h->tab, &h->tab_cap, (size_t)(std::min(step, nq) * per))) != MI_OK) return rc;
   std::vector<char> pack;
   for (int64_t q0 = 0; q0 < nq; q0 += step) {
     const int64_t b = std::min(step, nq - q0);
-    if ((rc = pq_stage_rows(h, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+    if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
     launch_pq_table(h->xraw, dtype, h->d, 1, b, h->cb, h->m, h->ks, h->L, h->tab, s);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(out_table_host + q0 * per, h->tab, (size_t)(b * per) * 4, hipMemcpyDeviceToHost, s));
@@ -358,23 +302,23 @@ int mi_pq_search(mi_pq* h, const void* q, int64_t nq, int dtype, int64_t row_str
   if (out_seconds) *out_seconds = 0.0;
   if (nq == 0) return MI_OK;
   int rc;
-  if ((rc = pq_check_host_queries(h, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
+  if ((rc = check_host_queries(h->d, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
   std::lock_guard<std::mutex> lock(h->mu);
   const auto t0 = std::chrono::steady_clock::now();
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t cnt = (size_t)nq * k;
-  if ((rc = pq_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
-  if (out_dist && (rc = pq_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
+  if ((rc = device_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
+  if (out_dist && (rc = device_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
   const uint64_t* allow_dev = allow_bits;
   if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
     const size_t words = (size_t)((h->n + 63) / 64);
-    if ((rc = pq_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
+    if ((rc = device_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
     HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
     allow_dev = h->bits;
   }
   std::vector<char> pack;
-  if ((rc = pq_stage_rows(h, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+  if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
   if ((rc = pq_search_core(h, h->xraw, dtype, h->d, 1, nq, k, allow_dev, h->oidx, out_dist ? h->odist : nullptr, s)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(out_idx, h->oidx, cnt * 8, hipMemcpyDeviceToHost, s));
   if (out_dist) HIPC(hipMemcpyAsync(out_dist, h->odist, cnt * 4, hipMemcpyDeviceToHost, s));
@@ -468,10 +412,10 @@ int mi_pq_remove_rows(mi_pq* h, const uint64_t* remove_bits, int memspace, int64
     const int64_t blk_words = (int64_t)h->MQ * 64;
     const int64_t start = plan.first / 64;                    // the blocks before the first row that leaves stay as they are
     const int64_t B = std::min<int64_t>(g_pq_remove_block_rows.load(), (nwords - start) * 64) / 64;   // source blocks per chunk
-    if ((rc = pq_grow(&h->bits, &h->bits_cap, (size_t)nwords)) != MI_OK) return rc;
-    if ((rc = pq_grow(&h->rmpref, &h->rmpref_cap, (size_t)nwords + 1)) != MI_OK) return rc;
+    if ((rc = device_grow(&h->bits, &h->bits_cap, (size_t)nwords)) != MI_OK) return rc;
+    if ((rc = device_grow(&h->rmpref, &h->rmpref_cap, (size_t)nwords + 1)) != MI_OK) return rc;
     // a chunk's first survivor may sit in any lane of its destination block: one block more than the chunk's rows fill
-    if ((rc = pq_grow(&h->rmstage, &h->rmstage_cap, (size_t)((B + 1) * blk_words))) != MI_OK) return rc;
+    if ((rc = device_grow(&h->rmstage, &h->rmstage_cap, (size_t)((B + 1) * blk_words))) != MI_OK) return rc;
     HIPC(hipMemcpyAsync(h->bits, plan.keep.data(), (size_t)nwords * 8, hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(h->rmpref, plan.prefix.data(), ((size_t)nwords + 1) * 4, hipMemcpyHostToDevice, s));
     for (int64_t b0 = start; b0 < nwords; b0 += B) {

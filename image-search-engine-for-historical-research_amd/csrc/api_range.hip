@@ -34,7 +34,7 @@ static int regrow(T** p, size_t want, size_t keep) {
 template <typename A, typename B>
 static int grow_pair(A** a, B** b, size_t* cap, size_t count, size_t keep = 0) {
   if (*cap >= count && *a && *b) return MI_OK;
-  const size_t want = count + count / 4 + 64;
+  const size_t want = grow_capacity(count);
   int rc;
   if ((rc = regrow(a, want, keep)) != MI_OK || (rc = regrow(b, want, keep)) != MI_OK) {
     *cap = 0;

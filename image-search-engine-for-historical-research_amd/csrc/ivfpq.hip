@@ -7,18 +7,17 @@
 // a chain of blocks: blk_table[list_off[l] .. list_off[l + 1]) are its block numbers, in no particular order in the pool (appends
 // interleave the blocks of different lists); its first list_rows[l] slots, counted along the chain, are filled.
 //
-//   ivf_sqdist_step         one term of pq.hip's pq_sqdist chain, restated here because pq.hip keeps it to its own translation
-//                           unit: double subtract, multiply, add, nothing fused.  The probe is the ONLY user
-//   ivf_probe_kernel        workgroup = query, thread = list: float64 distance to every coarse centroid, rank of a list = number
+// The squared-distance chain, the ADC row sum, the code dword, the slab of 4096 keys and its sort are pq_device.h's, shared with
+// pq.hip and ivfpq_residual.hip.
+//
+//   ivf_probe_kernel        workgroup = query, thread = list: float64 distance (pq_sqdist_step) to every coarse centroid, rank of a list = number
 //                           of lists with a smaller (value, id), lists of rank < nprobe written at their rank
 //   ivf_prefix_kernel       workgroup = query: normalises a probe row (entries outside [0, nlist) and repeats of an earlier
 //                           entry become -1) and writes the prefix of block counts over it: the query's virtual block sequence
 //   ivf_scatter_kernel      code bytes and row ids -> the slots the host computed
 //   ivf_check_kernel        list ids >= nlist raise the flag (device-resident list ids)
 //   ivf_scan_select_kernel  the hot path.  Grid = (slab of 64 virtual blocks, query), 512 threads.  ONE query's table in LDS,
-//                           T[m][c]; every wave walks 8 blocks as pq_scan_kernel does (same adds, same book order, zero entries
-//                           for the books beyond M); key = float_bits(dist) << 32 | local row (distances are >= +0.0, so the
-//                           bit pattern is monotone and +inf an ordinary value; keys are distinct, there is no tie class);
+//                           T[m][c]; every wave walks 8 blocks as pq_scan_kernel does (pq_adc_row); key = pq_key(dist, local row);
 //                           slots beyond a list's fill and rows the allow bitmap clears get the all-ones sentinel; the 4096 keys are
 //                           bitonic-sorted in LDS and the first k written to part[query][slab][k]
 //   ivf_merge_kernel        workgroup = query: the sorted partial lists of its slabs -> the k smallest keys in order (keeps the
@@ -26,42 +25,13 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "pq_device.h"
 
 namespace mi {
 
-constexpr uint64_t IVF_SENTINEL = ~0ull;
 constexpr int IVF_THREADS = 512, IVF_WAVES = IVF_THREADS / 64;
-constexpr int IVF_SLAB_BLOCKS = 64, IVF_SLAB_KEYS = IVF_SLAB_BLOCKS * 64;      // 4096 candidates of a workgroup
 constexpr int IVF_MAX_LISTS = 256;
 constexpr int IVF_PJ = 32;                                                     // columns of a probe slice
-
-__device__ __forceinline__ double ivf_sqdist_step(double acc, double x, double c) {
-#pragma clang fp contract(off)
-  const double d = x - c;
-  const double p = d * d;
-  return acc + p;
-}
-
-// ascending bitonic sort of 4096 keys in LDS by NT threads; ends with a barrier
-template <int NT>
-__device__ __forceinline__ void ivf_sort4096(uint64_t* keys, int tid) {
-  for (int k = 2; k <= IVF_SLAB_KEYS; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-      for (int t = tid; t < IVF_SLAB_KEYS / 2; t += NT) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int p = i | j;
-        const uint64_t a = keys[i], b = keys[p];
-        const bool up = (i & k) == 0;
-        if ((a > b) == up) {
-          keys[i] = b;
-          keys[p] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
 
 // ---- probe.  gs[l][j] holds a slice of IVF_PJ columns of every centroid (row padded to an odd stride: lane l reads bank
 // (33 l + j) % 64, no conflict), xs[j] the query's slice in float64 (one address per wave, a broadcast)
@@ -86,7 +56,7 @@ __global__ __launch_bounds__(IVF_MAX_LISTS) void ivf_probe_kernel(const InT* __r
     if (tid < IVF_PJ) xs[tid] = tid < jn ? (double)xr[(int64_t)(j0 + tid) * cs] : 0.0;
     __syncthreads();
     if (tid < nlist)
-      for (int32_t j = 0; j < jn; ++j) acc = ivf_sqdist_step(acc, xs[j], (double)gs[tid][j]);
+      for (int32_t j = 0; j < jn; ++j) acc = pq_sqdist_step(acc, xs[j], (double)gs[tid][j]);
   }
   dist[tid] = acc;
   if (tid < nprobe) out[q * nprobe + tid] = -1;           // a non-finite query may leave ranks unused: those stay "no list"
@@ -150,11 +120,7 @@ __global__ __launch_bounds__(256) void ivf_scatter_kernel(const uint8_t* __restr
   if (i >= m * MQ) return;
   const int64_t r = i % m;
   const int32_t w = (int32_t)(i / m);
-  const uint8_t* p = src + r * stride;
-  uint32_t v = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b)
-    if (4 * w + b < M) v |= (uint32_t)p[4 * w + b] << (8 * b);
+  const uint32_t v = pq_pack_dword(src + r * stride, w, M);
   const int64_t s = slot[r];
   codes[((s >> 6) * MQ + w) * 64 + (s & 63)] = v;
   if (w == 0) rowid[s] = (uint32_t)(row0 + r);
@@ -176,22 +142,20 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_select_kernel(const uint
   const int32_t total = qpref[nprobe];                                 // virtual blocks of this query
   // the merge reads only the slabs below the query's count, so nothing is written here.  The condition is uniform over the
   // workgroup and stands before every barrier: it must stay both
-  if ((int64_t)slab * IVF_SLAB_BLOCKS >= total) return;
+  if ((int64_t)slab * PQ_SLAB_BLOCKS >= total) return;
   uint64_t* keys = reinterpret_cast<uint64_t*>(ivf_smem);
-  float* tl = reinterpret_cast<float*>(ivf_smem + IVF_SLAB_KEYS * 8);
+  float* tl = reinterpret_cast<float*>(ivf_smem + PQ_SLAB_KEYS * 8);
   const int32_t ent = 4 * MQ * Ks, real = M * Ks;
   int32_t* lpref = reinterpret_cast<int32_t*>(tl + ent);
   int32_t* lprobe = lpref + nprobe + 1;
   const int tid = threadIdx.x;
-  const float* qt = tab + q * real;
-  for (int32_t i = tid; i < ent; i += IVF_THREADS) tl[i] = i < real ? qt[i] : 0.0f;
-  for (int32_t i = tid; i <= nprobe; i += IVF_THREADS) lpref[i] = qpref[i];
-  for (int32_t i = tid; i < nprobe; i += IVF_THREADS) lprobe[i] = probes[q * nprobe + i];
+  pq_slab_load_table<IVF_THREADS>(tl, tab + q * real, ent, real, tid);
+  pq_slab_load_probes<IVF_THREADS>(lpref, lprobe, qpref, probes + q * nprobe, nprobe, tid);
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
-  for (int32_t vb = wave; vb < IVF_SLAB_BLOCKS; vb += IVF_WAVES) {      // wave-uniform
-    const int32_t v = slab * IVF_SLAB_BLOCKS + vb;
-    uint64_t key = IVF_SENTINEL;
+  for (int32_t vb = wave; vb < PQ_SLAB_BLOCKS; vb += IVF_WAVES) {      // wave-uniform
+    const int32_t v = slab * PQ_SLAB_BLOCKS + vb;
+    uint64_t key = PQ_SENTINEL;
     if (v < total) {
       // the probe whose range [pref[i], pref[i + 1]) holds v: the last i with pref[i] <= v (empty probes have empty ranges)
       int32_t lo = 0, hi = nprobe - 1;
@@ -204,27 +168,13 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_select_kernel(const uint
       const int64_t b = blk_table[list_off[l] + (v - lpref[lo])];
       const bool filled = (uint32_t)(v - lpref[lo]) * 64u + (uint32_t)lane < list_rows[l];   // the tail block is partly filled
       const uint32_t row = rowid[b * 64 + lane];
-      const uint32_t* src = codes + b * MQ * 64 + lane;
-      float acc = 0.0f;
-#pragma unroll 4
-      for (int32_t w = 0; w < MQ; ++w) {
-        const uint32_t g = src[(int64_t)w * 64];
-        const int32_t base = 4 * w * Ks;
-        acc = acc + tl[base + (int32_t)(g & 255u)];
-        acc = acc + tl[base + Ks + (int32_t)((g >> 8) & 255u)];
-        acc = acc + tl[base + 2 * Ks + (int32_t)((g >> 16) & 255u)];
-        acc = acc + tl[base + 3 * Ks + (int32_t)(g >> 24)];
-      }
-      bool ok = filled;
-      if (ok && allow) ok = (allow[row >> 6] >> (row & 63u)) & 1ull;
-      if (ok) key = ((uint64_t)__float_as_uint(acc) << 32) | row;
+      const float dist = pq_adc_row<1>(tl, codes + b * MQ * 64 + lane, MQ, Ks).v[0];
+      if (pq_admit(filled, allow, row)) key = pq_key(dist, row);
     }
     keys[vb * 64 + lane] = key;
   }
   __syncthreads();
-  ivf_sort4096<IVF_THREADS>(keys, tid);
-  uint64_t* out = part + ((int64_t)q * nslab + slab) * k;
-  for (int32_t i = tid; i < k; i += IVF_THREADS) out[i] = keys[i];
+  pq_slab_select<IVF_THREADS>(keys, part + ((int64_t)q * nslab + slab) * k, k, tid);
 }
 
 // ---- merge: LDS keys [4096]; [0, 2048) is the best so far (sorted after every pass), [2048, 4096) takes the next 2048 keys of
@@ -232,26 +182,26 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_select_kernel(const uint
 __global__ __launch_bounds__(IVF_THREADS) void ivf_merge_kernel(const uint64_t* __restrict__ part, const int32_t* __restrict__ pref,
                                                                int32_t nprobe, int32_t k, int32_t nslab, int64_t row_offset,
                                                                int64_t* __restrict__ out_idx, float* __restrict__ out_dist) {
-  __shared__ uint64_t keys[IVF_SLAB_KEYS];
+  __shared__ uint64_t keys[PQ_SLAB_KEYS];
   const int64_t q = blockIdx.x;
   const int tid = threadIdx.x;
   const int32_t total = pref[q * (nprobe + 1) + nprobe];
-  const int32_t slabs = min(nslab, (total + IVF_SLAB_BLOCKS - 1) / IVF_SLAB_BLOCKS);
+  const int32_t slabs = min(nslab, (total + PQ_SLAB_BLOCKS - 1) / PQ_SLAB_BLOCKS);
   const int64_t count = (int64_t)slabs * k;
   const uint64_t* src = part + (int64_t)q * nslab * k;
-  constexpr int HALF = IVF_SLAB_KEYS / 2;
-  for (int i = tid; i < HALF; i += IVF_THREADS) keys[i] = IVF_SENTINEL;
+  constexpr int HALF = PQ_SLAB_KEYS / 2;
+  for (int i = tid; i < HALF; i += IVF_THREADS) keys[i] = PQ_SENTINEL;
   for (int64_t c0 = 0; c0 < count; c0 += HALF) {
-    for (int i = tid; i < HALF; i += IVF_THREADS) keys[HALF + i] = c0 + i < count ? src[c0 + i] : IVF_SENTINEL;
+    for (int i = tid; i < HALF; i += IVF_THREADS) keys[HALF + i] = c0 + i < count ? src[c0 + i] : PQ_SENTINEL;
     __syncthreads();
-    ivf_sort4096<IVF_THREADS>(keys, tid);
+    pq_sort4096<IVF_THREADS>(keys, tid);
   }
   __syncthreads();
   for (int32_t i = tid; i < k; i += IVF_THREADS) {
     const uint64_t key = keys[i];
-    const bool none = key == IVF_SENTINEL;
-    out_idx[q * k + i] = none ? -1 : row_offset + (int64_t)(uint32_t)key;
-    if (out_dist) out_dist[q * k + i] = none ? __builtin_inff() : __uint_as_float((uint32_t)(key >> 32));
+    const bool none = key == PQ_SENTINEL;
+    out_idx[q * k + i] = none ? -1 : row_offset + (int64_t)pq_key_row(key);
+    if (out_dist) out_dist[q * k + i] = none ? __builtin_inff() : pq_key_dist(key);
   }
 }
 
@@ -291,7 +241,7 @@ void launch_ivf_scan_select(const uint32_t* codes, const uint32_t* rowid, const 
                             const uint32_t* list_rows, const uint64_t* allow, int32_t k, int32_t nslab, uint64_t* part, hipStream_t stream) {
   if (nq <= 0 || nslab <= 0) return;
   const int32_t MQ = (M + 3) / 4;
-  const int lds = IVF_SLAB_KEYS * 8 + 4 * MQ * Ks * 4 + (2 * nprobe + 1) * 4;
+  const int lds = PQ_SLAB_KEYS * 8 + 4 * MQ * Ks * 4 + (2 * nprobe + 1) * 4;
   ensure_dynamic_lds((const void*)ivf_scan_select_kernel);
   ivf_scan_select_kernel<<<dim3((unsigned)nslab, (unsigned)nq), IVF_THREADS, lds, stream>>>(codes, rowid, blk_table, list_off, M, MQ, Ks, tab,
                                                                                             probes, pref, nprobe, list_rows, allow, k, nslab, part);

@@ -3,8 +3,9 @@
 // one distance table per PROBED LIST: T[q][p][m][c] = float32(sum_j (r_j - double(C[m][c][j]))^2) with r the query's residual
 // against the list of probe slot p.  Layout, lists, probes, keys and the merge are those of ivfpq.hip, whose kernels stay as they are.
 //
-//   ivfr_sqdist_step       one term of the chain of pq.hip / ivfpq.hip, restated for this translation unit: double subtract, multiply,
-//                          add, nothing fused
+// The squared-distance chain, the ADC row sum, the encoder's tile constants, the slab of 4096 keys and its sort are pq_device.h's, shared with
+// pq.hip and ivfpq.hip.
+//
 //   ivfr_table_kernel      grid = (groups of IVFR_RP probe slots, query), thread = codeword.  Per (book, slice of IVFR_PJ columns) the
 //                          codebook slice passes through LDS as float32 (row padded to an odd stride, as ivf_probe_kernel's
 //                          centroids) and the residual slices of the group's slots as float64, xs[j][slot]: a thread converts its
@@ -20,22 +21,14 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "pq_device.h"
 
 namespace mi {
 
-constexpr uint64_t IVFR_SENTINEL = ~0ull;
 constexpr int IVFR_THREADS = 512, IVFR_WAVES = IVFR_THREADS / 64;
-constexpr int IVFR_SLAB_BLOCKS = 64, IVFR_SLAB_KEYS = IVFR_SLAB_BLOCKS * 64;   // ivfpq.hip's slab: the merge is shared
 constexpr int IVFR_TT = 256;                                                   // threads of the table kernel = codewords of a book
 constexpr int IVFR_PJ = 32;                                                    // columns of a slice
 constexpr int IVFR_RP = 4;                                                     // probe slots of a workgroup
-
-__device__ __forceinline__ double ivfr_sqdist_step(double acc, double x, double c) {
-#pragma clang fp contract(off)
-  const double d = x - c;
-  const double p = d * d;
-  return acc + p;
-}
 
 // ---- table.  probes: the NORMALISED probes [nq][nprobe] (-1 = no list).  tab [nq][nprobe][M][Ks]
 template <typename InT>
@@ -85,33 +78,13 @@ __global__ __launch_bounds__(IVFR_TT) void ivfr_table_kernel(const InT* __restri
         for (int32_t j = 0; j < jn; ++j) {
           const double c = (double)cw[tid][j];
 #pragma unroll
-          for (int r = 0; r < IVFR_RP; ++r) acc[r] = ivfr_sqdist_step(acc[r], xs[j][r], c);
+          for (int r = 0; r < IVFR_RP; ++r) acc[r] = pq_sqdist_step(acc[r], xs[j][r], c);
         }
     }
     if (tid < Ks) {
 #pragma unroll
       for (int r = 0; r < IVFR_RP; ++r)
         if (lst[r] >= 0) tab[(((int64_t)q * nprobe + p0 + r) * M + m) * Ks + tid] = (float)acc[r];
-    }
-  }
-}
-
-// ascending bitonic sort of 4096 keys in LDS (ivfpq.hip's ivf_sort4096); ends with a barrier
-__device__ __forceinline__ void ivfr_sort4096(uint64_t* keys, int tid) {
-  for (int k = 2; k <= IVFR_SLAB_KEYS; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-      for (int t = tid; t < IVFR_SLAB_KEYS / 2; t += IVFR_THREADS) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int p = i | j;
-        const uint64_t a = keys[i], b = keys[p];
-        const bool up = (i & k) == 0;
-        if ((a > b) == up) {
-          keys[i] = b;
-          keys[p] = a;
-        }
-      }
-      __syncthreads();
     }
   }
 }
@@ -132,27 +105,25 @@ __global__ __launch_bounds__(IVFR_THREADS) void ivfr_scan_select_kernel(const ui
   const int32_t total = qpref[nprobe];                                 // virtual blocks of this query
   // the merge reads only the slabs below the query's count, so nothing is written here.  The condition is uniform over the
   // workgroup and stands before every barrier: it must stay both
-  if ((int64_t)slab * IVFR_SLAB_BLOCKS >= total) return;
+  if ((int64_t)slab * PQ_SLAB_BLOCKS >= total) return;
   uint64_t* keys = reinterpret_cast<uint64_t*>(ivfr_smem);
-  float* tl = reinterpret_cast<float*>(ivfr_smem + IVFR_SLAB_KEYS * 8);
+  float* tl = reinterpret_cast<float*>(ivfr_smem + PQ_SLAB_KEYS * 8);
   const int32_t ent = 4 * MQ * Ks, real = M * Ks;
   int32_t* lpref = reinterpret_cast<int32_t*>(tl + ent);
   int32_t* lprobe = lpref + nprobe + 1;
   const int tid = threadIdx.x;
-  for (int32_t i = tid; i < IVFR_SLAB_KEYS; i += IVFR_THREADS) keys[i] = IVFR_SENTINEL;   // the slots no probe's range covers
-  for (int32_t i = tid; i <= nprobe; i += IVFR_THREADS) lpref[i] = qpref[i];
-  for (int32_t i = tid; i < nprobe; i += IVFR_THREADS) lprobe[i] = probes[q * nprobe + i];
+  for (int32_t i = tid; i < PQ_SLAB_KEYS; i += IVFR_THREADS) keys[i] = PQ_SENTINEL;   // the slots no probe's range covers
+  pq_slab_load_probes<IVFR_THREADS>(lpref, lprobe, qpref, probes + q * nprobe, nprobe, tid);
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
-  const int32_t v0 = slab * IVFR_SLAB_BLOCKS, v1 = min(total, v0 + IVFR_SLAB_BLOCKS);
+  const int32_t v0 = slab * PQ_SLAB_BLOCKS, v1 = min(total, v0 + PQ_SLAB_BLOCKS);
   // every value that steers this loop is read from LDS behind the barrier above or is a kernel argument: the trip count and the
   // branch around the body are the same for all 512 threads, and both barriers of the body are met by all of them
   for (int32_t p = 0; p < nprobe; ++p) {
     const int32_t a = max(v0, lpref[p]), b = min(v1, lpref[p + 1]);    // this slot's virtual blocks inside the slab
     if (a >= b) continue;                                              // an empty range (a -1 slot, an empty list) or another slab
     __syncthreads();                                                   // the waves have finished with the previous table
-    const float* qt = tab + ((int64_t)q * nprobe + p) * real;
-    for (int32_t i = tid; i < ent; i += IVFR_THREADS) tl[i] = i < real ? qt[i] : 0.0f;
+    pq_slab_load_table<IVFR_THREADS>(tl, tab + ((int64_t)q * nprobe + p) * real, ent, real, tid);
     __syncthreads();
     const int32_t l = lprobe[p];                                       // >= 0: its range is not empty
     const int32_t first = lpref[p];
@@ -160,75 +131,60 @@ __global__ __launch_bounds__(IVFR_THREADS) void ivfr_scan_select_kernel(const ui
       const int64_t blk = blk_table[list_off[l] + (v - first)];
       const bool filled = (uint32_t)(v - first) * 64u + (uint32_t)lane < list_rows[l];    // the tail block is partly filled
       const uint32_t row = rowid[blk * 64 + lane];
-      const uint32_t* src = codes + blk * MQ * 64 + lane;
-      float acc = 0.0f;
-#pragma unroll 4
-      for (int32_t w = 0; w < MQ; ++w) {
-        const uint32_t g = src[(int64_t)w * 64];
-        const int32_t base = 4 * w * Ks;
-        acc = acc + tl[base + (int32_t)(g & 255u)];
-        acc = acc + tl[base + Ks + (int32_t)((g >> 8) & 255u)];
-        acc = acc + tl[base + 2 * Ks + (int32_t)((g >> 16) & 255u)];
-        acc = acc + tl[base + 3 * Ks + (int32_t)(g >> 24)];
-      }
-      bool ok = filled;
-      if (ok && allow) ok = (allow[row >> 6] >> (row & 63u)) & 1ull;
-      if (ok) keys[(v - v0) * 64 + lane] = ((uint64_t)__float_as_uint(acc) << 32) | row;
+      const float dist = pq_adc_row<1>(tl, codes + blk * MQ * 64 + lane, MQ, Ks).v[0];
+      if (pq_admit(filled, allow, row)) keys[(v - v0) * 64 + lane] = pq_key(dist, row);
     }
   }
   __syncthreads();
-  ivfr_sort4096(keys, tid);
-  uint64_t* out = part + ((int64_t)q * nslab + slab) * k;
-  for (int32_t i = tid; i < k; i += IVFR_THREADS) out[i] = keys[i];
+  pq_slab_select<IVFR_THREADS>(keys, part + ((int64_t)q * nslab + slab) * k, k, tid);
 }
 
 // ---- encoder: pq_encode_kernel's tiling (64 rows x one book, 4 codeword groups of 8 accumulators), the row slice replaced by
-// the residual against the row's list
-constexpr int RE_ROWS = 64, RE_CT = 32, RE_JT = 64, RE_PER = RE_CT / 4;
-
+// the residual against the row's list.  Kept as a kernel of its own beside pq_encode_kernel: a shared body did not reproduce the
+// device code of either (profiles/pq_helpers_isa.txt); the step of the sum and the PE_* tile constants are pq_device.h's
 template <typename InT>
 __global__ __launch_bounds__(256) void ivfr_encode_kernel(const InT* __restrict__ x, int64_t rs, int64_t cs, int64_t n,
                                                          const float* __restrict__ G, int32_t d, const uint8_t* __restrict__ lists,
                                                          const float* __restrict__ cb, int32_t M, int32_t Ks, int32_t L,
                                                          uint8_t* __restrict__ out) {
-  __shared__ double xs[RE_JT][RE_ROWS];
-  __shared__ double cw[RE_CT][RE_JT + 1];
-  __shared__ double bd[4][RE_ROWS];
-  __shared__ int32_t bc[4][RE_ROWS];
-  __shared__ int32_t rl[RE_ROWS];
+  __shared__ double xs[PE_JT][PE_ROWS];
+  __shared__ double cw[PE_CT][PE_JT + 1];
+  __shared__ double bd[4][PE_ROWS];
+  __shared__ int32_t bc[4][PE_ROWS];
+  __shared__ int32_t rl[PE_ROWS];
   const int tid = threadIdx.x, r = tid & 63, cg = tid >> 6;
-  const int64_t row0 = (int64_t)blockIdx.x * RE_ROWS;
+  const int64_t row0 = (int64_t)blockIdx.x * PE_ROWS;
   const int32_t m = (int32_t)blockIdx.y;
-  if (tid < RE_ROWS) rl[tid] = row0 + tid < n ? (int32_t)lists[row0 + tid] : 0;
+  if (tid < PE_ROWS) rl[tid] = row0 + tid < n ? (int32_t)lists[row0 + tid] : 0;
   double best = __builtin_inf();
   int32_t best_c = 0;
-  for (int32_t c0 = 0; c0 < Ks; c0 += RE_CT) {
-    double acc[RE_PER];
+  for (int32_t c0 = 0; c0 < Ks; c0 += PE_CT) {
+    double acc[PE_PER];
 #pragma unroll
-    for (int e = 0; e < RE_PER; ++e) acc[e] = 0.0;
-    for (int32_t j0 = 0; j0 < L; j0 += RE_JT) {
-      const int32_t jn = min(RE_JT, L - j0);
+    for (int e = 0; e < PE_PER; ++e) acc[e] = 0.0;
+    for (int32_t j0 = 0; j0 < L; j0 += PE_JT) {
+      const int32_t jn = min(PE_JT, L - j0);
       __syncthreads();
-      for (int i = tid; i < RE_ROWS * RE_JT; i += 256) {
-        const int j = i % RE_JT, rr = i / RE_JT;
+      for (int i = tid; i < PE_ROWS * PE_JT; i += 256) {
+        const int j = i % PE_JT, rr = i / PE_JT;
         const int64_t row = row0 + rr;
         const int32_t col = m * L + j0 + j;
         xs[j][rr] = (j < jn && row < n) ? (double)x[row * rs + (int64_t)col * cs] - (double)G[(int64_t)rl[rr] * d + col] : 0.0;
       }
-      for (int i = tid; i < RE_CT * RE_JT; i += 256) {
-        const int j = i % RE_JT, cc = i / RE_JT;
+      for (int i = tid; i < PE_CT * PE_JT; i += 256) {
+        const int j = i % PE_JT, cc = i / PE_JT;
         cw[cc][j] = (j < jn && c0 + cc < Ks) ? (double)cb[((int64_t)m * Ks + c0 + cc) * L + j0 + j] : 0.0;
       }
       __syncthreads();
       for (int32_t j = 0; j < jn; ++j) {
         const double xv = xs[j][r];
 #pragma unroll
-        for (int e = 0; e < RE_PER; ++e) acc[e] = ivfr_sqdist_step(acc[e], xv, cw[cg * RE_PER + e][j]);
+        for (int e = 0; e < PE_PER; ++e) acc[e] = pq_sqdist_step(acc[e], xv, cw[cg * PE_PER + e][j]);
       }
     }
 #pragma unroll
-    for (int e = 0; e < RE_PER; ++e) {
-      const int32_t c = c0 + cg * RE_PER + e;
+    for (int e = 0; e < PE_PER; ++e) {
+      const int32_t c = c0 + cg * PE_PER + e;
       if (c < Ks && acc[e] < best) {                              // ascending c, strict: ties stay with the lower c
         best = acc[e];
         best_c = c;
@@ -238,7 +194,7 @@ __global__ __launch_bounds__(256) void ivfr_encode_kernel(const InT* __restrict_
   bd[cg][r] = best;
   bc[cg][r] = best_c;
   __syncthreads();
-  if (tid < RE_ROWS && row0 + tid < n) {
+  if (tid < PE_ROWS && row0 + tid < n) {
     double b = bd[0][tid];
     int32_t c = bc[0][tid];
 #pragma unroll
@@ -282,7 +238,7 @@ void launch_ivfr_scan_select(const uint32_t* codes, const uint32_t* rowid, const
                              const uint32_t* list_rows, const uint64_t* allow, int32_t k, int32_t nslab, uint64_t* part, hipStream_t stream) {
   if (nq <= 0 || nslab <= 0) return;
   const int32_t MQ = (M + 3) / 4;
-  const int lds = IVFR_SLAB_KEYS * 8 + 4 * MQ * Ks * 4 + (2 * nprobe + 1) * 4;
+  const int lds = PQ_SLAB_KEYS * 8 + 4 * MQ * Ks * 4 + (2 * nprobe + 1) * 4;
   ensure_dynamic_lds((const void*)ivfr_scan_select_kernel);
   ivfr_scan_select_kernel<<<dim3((unsigned)nslab, (unsigned)nq), IVFR_THREADS, lds, stream>>>(codes, rowid, blk_table, list_off, M, MQ, Ks, tab,
                                                                                              probes, pref, nprobe, list_rows, allow, k, nslab, part);
@@ -294,7 +250,7 @@ void launch_ivfr_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_
                         const float* cb, int32_t M, int32_t Ks, int32_t L, uint8_t* out, hipStream_t stream) {
   for (int64_t r = 0; r < n; r += IVFR_STEP) {
     const int64_t mm = std::min(IVFR_STEP, n - r);
-    const dim3 grid((unsigned)((mm + RE_ROWS - 1) / RE_ROWS), (unsigned)M);
+    const dim3 grid((unsigned)((mm + PE_ROWS - 1) / PE_ROWS), (unsigned)M);
     if (dtype == 0)
       ivfr_encode_kernel<float><<<grid, 256, 0, stream>>>((const float*)x + r * rs, rs, cs, mm, G, d, lists + r, cb, M, Ks, L, out + r * M);
     else

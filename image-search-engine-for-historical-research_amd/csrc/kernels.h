@@ -360,6 +360,7 @@ void launch_lsh_encode(const void* X, int dtype, int64_t n, int32_t d, int64_t r
 // pq.hip -- exact ADC top-K on product-quantized codes (api_pq.hip): codebooks [M][Ks][L] f32, gallery blocks of 64 rows with the
 // code bytes four books to a dword and the dwords transposed, codes[block][w < ceil(M / 4)][64]; distance tables [nq][M][Ks] f32;
 // a float32 matrix [nq][round_up(n, 64)] of NEGATED distances (NaN = row not admitted) for launch_dense_topk
+// (the device code pq.hip, ivfpq.hip and ivfpq_residual.hip share is pq_device.h)
 void launch_pq_check(const uint8_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream);
 void launch_pq_ingest(const uint8_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream);
 void launch_pq_table(const void* x, int dtype, int64_t rs, int64_t cs, int64_t nq, const float* cb, int32_t M, int32_t Ks, int32_t L,

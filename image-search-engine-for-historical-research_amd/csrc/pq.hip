@@ -6,8 +6,9 @@
 // row's code in book m; the bytes of the books M .. 4 MQ - 1 are zero.  Lane l of a wave owns row 64 * block + l, one book-quad
 // of the 64 rows is one coalesced 256-byte read.
 //
-//   pq_sqdist         THE arithmetic: sum_j (double(x_j) - double(c_j))^2 in float64, ascending j, a separate multiply and add
-//                     per term (no contraction).  The table rounds it once to float32, the encoder takes its argmin
+//   pq_device.h       the pieces shared with ivfpq.hip and ivfpq_residual.hip.  pq_sqdist is THE arithmetic: sum_j (double(x_j) -
+//                     double(c_j))^2 in float64, ascending j, a separate multiply and add per term (no contraction).  The table
+//                     rounds it once to float32, the encoder takes its argmin; pq_adc_row is the scan's row sum
 //   pq_table_kernel   T[q][m][c] = (float)pq_sqdist(x[q][m L ..], C[m][c]), thread = (q, m, c)
 //   pq_encode_kernel  code[i][m] = argmin_c pq_sqdist(x[i][m L ..], C[m][c]), ties to the lower c.  A workgroup takes 64 rows of
 //                     one book; row and codeword slices pass through LDS as float64, 8 accumulators per thread
@@ -22,29 +23,9 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "pq_device.h"
 
 namespace mi {
-
-// ---- the one place the squared distance of a sub-vector is computed.  fp contraction is off: hipcc would otherwise fuse d * d + acc
-template <typename FX, typename FC>
-__device__ __forceinline__ double pq_sqdist(FX x, FC c, int32_t L) {
-#pragma clang fp contract(off)
-  double acc = 0.0;
-  for (int32_t j = 0; j < L; ++j) {
-    const double d = x(j) - c(j);
-    const double p = d * d;
-    acc = acc + p;
-  }
-  return acc;
-}
-
-// one more term of the same chain (the encoder walks j in slices)
-__device__ __forceinline__ double pq_sqdist_step(double acc, double x, double c) {
-#pragma clang fp contract(off)
-  const double d = x - c;
-  const double p = d * d;
-  return acc + p;
-}
 
 // ---- code bytes >= ks raise the flag (device-resident codes; host codes are checked on the host)
 __global__ __launch_bounds__(256) void pq_check_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t M, int32_t ks, int64_t m,
@@ -63,13 +44,8 @@ __global__ __launch_bounds__(256) void pq_ingest_kernel(const uint8_t* __restric
   if (i >= m * MQ) return;
   const int64_t r = i % m;
   const int32_t w = (int32_t)(i / m);
-  const uint8_t* p = src + r * stride;
-  uint32_t v = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b)
-    if (4 * w + b < M) v |= (uint32_t)p[4 * w + b] << (8 * b);
   const int64_t row = row0 + r;
-  codes[((row >> 6) * MQ + w) * 64 + (row & 63)] = v;
+  codes[((row >> 6) * MQ + w) * 64 + (row & 63)] = pq_pack_dword(src + r * stride, w, M);
 }
 
 // ---- table
@@ -89,9 +65,8 @@ __global__ __launch_bounds__(256) void pq_table_kernel(const InT* __restrict__ x
 
 // ---- encoder.  Workgroup = 64 rows x one book; thread t: row t & 63, codeword group t >> 6 (one wave each).  The codewords
 // pass in tiles of PE_CT = 32 (8 per thread), the columns in slices of PE_JT = 64; xs[j][row] and cs[c][j] are float64 in LDS
-// (xs: consecutive lanes, consecutive addresses; cs: one address per wave, a broadcast).
-constexpr int PE_ROWS = 64, PE_CT = 32, PE_JT = 64, PE_PER = PE_CT / 4;
-
+// (xs: consecutive lanes, consecutive addresses; cs: one address per wave, a broadcast).  The tile constants PE_* are pq_device.h's: ivfr_encode_kernel
+// (ivfpq_residual.hip) is this kernel on residuals and keeps the same tiling.
 template <typename InT>
 __global__ __launch_bounds__(256) void pq_encode_kernel(const InT* __restrict__ x, int64_t rs, int64_t cs, int64_t n,
                                                        const float* __restrict__ cb, int32_t M, int32_t Ks, int32_t L,
@@ -160,28 +135,8 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(const InT* __restrict__ 
 constexpr int PS_THREADS = 512, PS_WAVES = PS_THREADS / 64;
 constexpr int PS_LDS_BUDGET = 128 * 1024;
 
-template <int QT> struct PqVec;
-template <> struct PqVec<1> { using type = float; };
-template <> struct PqVec<2> { using type = float2; };
-template <> struct PqVec<4> { using type = float4; };
-
-template <int QT>
-__device__ __forceinline__ void pq_acc(float (&acc)[QT], const typename PqVec<QT>::type v);
-template <> __device__ __forceinline__ void pq_acc<1>(float (&acc)[1], const float v) { acc[0] = acc[0] + v; }
-template <> __device__ __forceinline__ void pq_acc<2>(float (&acc)[2], const float2 v) {
-  acc[0] = acc[0] + v.x;
-  acc[1] = acc[1] + v.y;
-}
-template <> __device__ __forceinline__ void pq_acc<4>(float (&acc)[4], const float4 v) {
-  acc[0] = acc[0] + v.x;
-  acc[1] = acc[1] + v.y;
-  acc[2] = acc[2] + v.z;
-  acc[3] = acc[3] + v.w;
-}
-
-// grid = (query tiles, slabs).  tab: [nq][M][Ks] f32.  The LDS image holds 4 MQ books: the entries of the books M .. 4 MQ - 1
-// are +0.0 and the code bytes of those books are 0, so a whole dword of codes is walked without a branch and the extra adds
-// change nothing (the running sum is never -0.0: it starts at +0.0 and takes non-negative terms).
+// grid = (query tiles, slabs).  tab: [nq][M][Ks] f32.  The LDS image holds 4 MQ books, zero entries for the books beyond M
+// (pq_adc_row, pq_device.h).
 template <int QT>
 __global__ __launch_bounds__(PS_THREADS) void pq_scan_kernel(const uint32_t* __restrict__ codes, int32_t M, int32_t MQ, int32_t Ks,
                                                             int64_t nblk, int64_t blk_per, int64_t n, const float* __restrict__ tab,
@@ -201,25 +156,13 @@ __global__ __launch_bounds__(PS_THREADS) void pq_scan_kernel(const uint32_t* __r
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t b0 = (int64_t)blockIdx.y * blk_per, b1 = min(nblk, b0 + blk_per);
   for (int64_t b = b0 + wave; b < b1; b += PS_WAVES) {               // wave-uniform
-    const uint32_t* src = codes + b * MQ * 64 + lane;
-    float acc[QT];
-#pragma unroll
-    for (int t = 0; t < QT; ++t) acc[t] = 0.0f;
-#pragma unroll 4
-    for (int32_t w = 0; w < MQ; ++w) {
-      const uint32_t g = src[(int64_t)w * 64];
-      const int32_t base = 4 * w * Ks;
-      pq_acc<QT>(acc, tv[base + (int32_t)(g & 255u)]);
-      pq_acc<QT>(acc, tv[base + Ks + (int32_t)((g >> 8) & 255u)]);
-      pq_acc<QT>(acc, tv[base + 2 * Ks + (int32_t)((g >> 16) & 255u)]);
-      pq_acc<QT>(acc, tv[base + 3 * Ks + (int32_t)(g >> 24)]);
-    }
+    const PqSums<QT> acc = pq_adc_row<QT>(tv, codes + b * MQ * 64 + lane, MQ, Ks);
     const int64_t row = b * 64 + lane;
     bool ok = row < n;
     if (allow) ok = ok && ((allow[b] >> lane) & 1ull);
 #pragma unroll
     for (int t = 0; t < QT; ++t)
-      if (q0 + t < nq) mat[(int64_t)(q0 + t) * npad + row] = ok ? -acc[t] : __builtin_nanf("");
+      if (q0 + t < nq) mat[(int64_t)(q0 + t) * npad + row] = ok ? -acc.v[t] : __builtin_nanf("");
   }
 }
 
