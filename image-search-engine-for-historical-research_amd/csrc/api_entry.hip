@@ -122,6 +122,7 @@ int mi_knn_phase1_device(mi_gallery* g, const float* q_dev, int64_t nq, int32_t 
 int mi_kth_of_gathered_device(const float* gathered_dev, int32_t nshards, int64_t nq, int32_t k, float* out_L_dev,
                               void* stream) {
   REQUIRE(gathered_dev && out_L_dev, "null pointer");
+  REQUIRE(nq >= 1 && k >= 1, "bad sizes (nq and k must be at least 1)");
   REQUIRE(nshards >= 1 && (int64_t)nshards * k <= 8192, "nshards * k too large (the merge takes at most 8192 entries per query)");
   launch_kth_of_gathered(gathered_dev, nshards, nq, k, out_L_dev, (hipStream_t)stream);
   HIPC(hipGetLastError());
@@ -141,6 +142,7 @@ int mi_knn_phase2_device(mi_gallery* g, int64_t nq, int32_t k, const float* L_de
 int mi_topk_merge_device(const double* score64_dev, const int64_t* idx_dev, int32_t nshards, int64_t nq, int32_t k,
                          int64_t* out_idx_dev, float* out_score_dev, void* stream) {
   REQUIRE(score64_dev && idx_dev && out_idx_dev, "null pointer");
+  REQUIRE(nq >= 1 && k >= 1, "bad sizes (nq and k must be at least 1)");
   REQUIRE(nshards >= 1 && (int64_t)nshards * k <= 8192, "nshards * k too large");
   launch_merge(score64_dev, idx_dev, nshards, nq, k, nq * (int64_t)k, out_idx_dev, out_score_dev, (hipStream_t)stream);
   HIPC(hipGetLastError());
@@ -150,6 +152,7 @@ int mi_topk_merge_device(const double* score64_dev, const int64_t* idx_dev, int3
 int mi_topk_merge_strided_device(const double* score64_dev, const int64_t* idx_dev, int64_t shard_stride, int32_t nshards,
                                  int64_t nq, int32_t k, int64_t* out_idx_dev, float* out_score_dev, void* stream) {
   REQUIRE(score64_dev && idx_dev && out_idx_dev, "null pointer");
+  REQUIRE(nq >= 1 && k >= 1, "bad sizes (nq and k must be at least 1)");
   REQUIRE(nshards >= 1 && (int64_t)nshards * k <= 8192, "nshards * k too large");
   REQUIRE(shard_stride >= nq * (int64_t)k, "shard_stride smaller than one shard's list");
   launch_merge(score64_dev, idx_dev, nshards, nq, k, shard_stride, out_idx_dev, out_score_dev, (hipStream_t)stream);
@@ -194,6 +197,7 @@ int mi_aqe_combine_device(const float* rows_dev, int64_t nq, int32_t d, int32_t 
 int mi_aqe_finish_device(const double* sum_dev, int64_t nq, int32_t d, double eps, float* out_q_dev,
                          double* out_q64_dev, void* stream) {
   REQUIRE(sum_dev && out_q_dev, "null pointer");
+  REQUIRE(nq >= 1 && d >= 1, "bad sizes");
   launch_aqe_finish(sum_dev, nq, d, eps, out_q_dev, out_q64_dev, (hipStream_t)stream);
   HIPC(hipGetLastError());
   return MI_OK;

@@ -593,7 +593,9 @@ int mi_search_join(mi_gallery* g, void* stream);
  *          (unsorted) to out_approx_dev [nq][k] (-inf padded when the shard has < k rows). */
 int mi_knn_phase1_device(mi_gallery* g, const float* q_dev, int64_t nq, int32_t k,
                          float* out_approx_dev, void* stream);
-/* K-th largest of the gathered [g][nq][k] approximate values -> lower bound L [nq]. */
+/* K-th largest of the gathered [nshards][nq][k] approximate values -> lower bound L [nq].  The order is that of the
+ * selection keys: NaN below -inf, -0.0 below +0.0, otherwise numeric; the answer is one of the gathered values, bit for bit
+ * (some NaN when the K-th is a NaN).  nq >= 1, k >= 1, nshards >= 1 and nshards * k <= 8192, refused otherwise. */
 int mi_kth_of_gathered_device(const float* gathered_dev, int32_t nshards, int64_t nq, int32_t k,
                               float* out_L_dev, void* stream);
 /* phase 2: exact f64 re-score of every local row whose approximate score is within the rigorous error
@@ -602,13 +604,18 @@ int mi_knn_phase2_device(mi_gallery* g, int64_t nq, int32_t k, const float* L_de
                          int64_t* out_idx_dev, float* out_score_dev, double* out_score64_dev,
                          void* stream);
 /* merge of [nshards][nq][k] exact lists -> [nq][k] by (score64 desc, idx asc).  Every list must be what phase 2 emits:
- * sorted in that order, padded with -1 / -inf at the end; row ids of different shards are disjoint (row shards). */
+ * sorted in that order, padded with -1 / -inf at the end; row ids of different shards are disjoint (row shards).
+ * The order in full: an entry with idx < 0 is padding whatever its score and comes after everything; among the others a NaN
+ * score comes after every number (-inf included), NaNs among themselves by ascending idx; numbers by descending score with
+ * -0.0 == +0.0, equal scores by ascending idx -- across the lists as within one.  out_score is (float)score64 (a value beyond
+ * the float32 range becomes +-inf), may be NULL; slots beyond the valid entries of all lists together hold -1 / -inf.
+ * nq >= 1, k >= 1, nshards >= 1 and nshards * k <= 8192, refused otherwise. */
 int mi_topk_merge_device(const double* score64_dev, const int64_t* idx_dev, int32_t nshards,
                          int64_t nq, int32_t k, int64_t* out_idx_dev, float* out_score_dev,
                          void* stream);
 /* Same merge for lists that arrive interleaved per shard: shard g's scores start at score64_dev + g * shard_stride and its
  * indices at idx_dev + g * shard_stride (elements of 8 bytes), e.g. one all-gather of a packed [2][nq][k] buffer per rank
- * (scores, then indices) instead of two collectives. */
+ * (scores, then indices) instead of two collectives.  shard_stride >= nq * k; what lies between the lists is not read. */
 int mi_topk_merge_strided_device(const double* score64_dev, const int64_t* idx_dev, int64_t shard_stride,
                                  int32_t nshards, int64_t nq, int32_t k, int64_t* out_idx_dev,
                                  float* out_score_dev, void* stream);
@@ -617,7 +624,8 @@ int mi_topk_merge_strided_device(const double* score64_dev, const int64_t* idx_d
  * :288-301): q' = sum_j ((k-j)/k)^w * G[ranks[j,q]], q' /= (||q'|| + eps), then a full re-search.
  * ranks: element (j,q) at ranks[j*rank_stride_j + q*rank_stride_q], global row ids (int64).
  * partial: this shard's contribution sum (rows it owns) as f64 [nq][d]; finish: normalise the
- * (all-reduced) sum into f32 queries [nq][d]. */
+ * (all-reduced) sum into f32 queries [nq][d] (out_q64_dev, may be NULL: the same in f64 before the conversion; an all-zero
+ * row stays zero for eps > 0); nq >= 1 and d >= 1, refused otherwise. */
 int mi_aqe_partial_device(mi_gallery* g, const int64_t* ranks_dev, int64_t rank_stride_j,
                           int64_t rank_stride_q, int64_t nq, int32_t k_qe, double w,
                           double* out_sum_dev, void* stream);
