@@ -16,21 +16,10 @@ int mi_knn_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t r
   int rc = strided_extent(nq, g->d, row_stride, col_stride, &elems);
   if (rc != MI_OK) return rc;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
-  auto stage = [&](int slot, size_t bytes) -> void* {
-    if (g->io_cap[slot] < bytes) {
-      (void)hipFree(g->io_buf[slot]);
-      g->io_buf[slot] = nullptr;
-      g->io_cap[slot] = 0;
-      const size_t want = bytes + bytes / 4 + 256;
-      if (device_malloc(&g->io_buf[slot], want) != hipSuccess) return nullptr;
-      g->io_cap[slot] = want;
-    }
-    return g->io_buf[slot];
-  };
   if ((rc = check_k(g, k)) != MI_OK) return rc;            // before sizing buffers by k
-  void* qd = stage(0, (size_t)elems * esz);
-  int64_t* idx_d = (int64_t*)stage(1, (size_t)nq * k * 8);
-  float* sc_d = (float*)stage(2, (size_t)nq * k * 4);
+  void* qd = io_stage(g->io_q, (size_t)elems * esz);
+  int64_t* idx_d = (int64_t*)io_stage(g->io_idx, (size_t)nq * k * 8);
+  float* sc_d = (float*)io_stage(g->io_sc, (size_t)nq * k * 4);
   auto done = [&](int code) { return code; };
   if (!qd || !idx_d || !sc_d) return fail(MI_ERR_NOMEM, "staging buffers of mi_knn_search");
   if (hipMemcpy(qd, q, (size_t)elems * esz, hipMemcpyHostToDevice) != hipSuccess)
@@ -215,23 +204,14 @@ int mi_aqe_search(mi_gallery* g, const int64_t* ranks, int64_t rank_stride_j, in
   int64_t elems;
   int rc = strided_extent(k_qe, nq, rank_stride_j, rank_stride_q, &elems);
   if (rc != MI_OK) return rc;
-  std::vector<void*> tmp;
-  auto alloc = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (device_malloc(&p, bytes + 256) != hipSuccess) return nullptr;
-    tmp.push_back(p);
-    return p;
-  };
-  auto done = [&](int code) {
-    for (void* p : tmp) (void)hipFree(p);
-    return code;
-  };
-  int64_t* ranks_d = (int64_t*)alloc((size_t)elems * 8);
-  double* sum_d = (double*)alloc((size_t)nq * g->d * 8);
-  double* q64_d = (double*)alloc((size_t)nq * g->d * 8);
-  float* q_d = (float*)alloc((size_t)nq * g->d * 4);
-  int64_t* idx_d = (int64_t*)alloc((size_t)nq * k * 8);
-  float* sc_d = (float*)alloc((size_t)nq * k * 4);
+  TmpAlloc tmp;                                   // (freed on return: every way out is behind a synchronous copy or search)
+  auto done = [&](int code) { return code; };
+  int64_t* ranks_d = tmp.get<int64_t>((size_t)elems);
+  double* sum_d = tmp.get<double>((size_t)nq * g->d);
+  double* q64_d = tmp.get<double>((size_t)nq * g->d);
+  float* q_d = tmp.get<float>((size_t)nq * g->d);
+  int64_t* idx_d = tmp.get<int64_t>((size_t)nq * k);
+  float* sc_d = tmp.get<float>((size_t)nq * k);
   if (!ranks_d || !sum_d || !q64_d || !q_d || !idx_d || !sc_d) return done(fail(MI_ERR_NOMEM, "aqe buffers"));
   // validate the row ids on the host: an out-of-range id must not become a wild gather
   for (int64_t j = 0; j < k_qe; ++j)

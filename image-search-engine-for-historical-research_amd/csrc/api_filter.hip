@@ -36,20 +36,11 @@ static void sub_free(mi_gallery* s) {
     (void)hipEventDestroy(e.second);
   }
   for (void* p : {(void*)s->gal_f32, s->gal_img, (void*)s->rowstat, (void*)s->gstat3, s->samp_img, (void*)s->samp_scores,
-                  (void*)s->samp_f32, s->io_buf[0], s->io_buf[1], s->io_buf[2]})
+                  (void*)s->samp_f32})
     (void)hipFree(p);
-  range_scratch_free(s);
+  s->scratch.reset();
   s->stream = nullptr;
   delete s;
-}
-
-void filter_scratch_free(mi_gallery* g) {
-  auto& f = g->filt;
-  sub_free(f.sub);
-  for (void* p : {(void*)f.bits, (void*)f.bcnt, (void*)f.boff, (void*)f.rows, (void*)f.idx, (void*)f.sidx, (void*)f.sc,
-                  (void*)f.ssc, (void*)f.ok, f.qbuf})
-    (void)hipFree(p);
-  f = mi_gallery::FilterScratch{};
 }
 
 void filter_invalidate(mi_gallery* g) {
@@ -63,19 +54,6 @@ void filter_release_sub(mi_gallery* g) {
   f.sub = nullptr;
   f.sub_cap = 0;
   f.valid = false;
-}
-
-template <typename A, typename B>
-static int grow2(A** a, B** b, size_t* cap, size_t count) {
-  if (*a && *b && *cap >= count) return MI_OK;
-  size_t ca = 0, cb = 0;
-  (void)hipFree(*a);
-  (void)hipFree(*b);
-  *a = nullptr, *b = nullptr, *cap = 0;
-  int rc;
-  if ((rc = device_grow(a, &ca, count)) != MI_OK || (rc = device_grow(b, &cb, count)) != MI_OK) return rc;
-  *cap = std::min(ca, cb);
-  return MI_OK;
 }
 
 // the search options of the parent, for the sub-gallery's searches (the answers do not depend on them; the schedule does)
@@ -124,8 +102,8 @@ static int sub_prepare(mi_gallery* g, const std::vector<uint64_t>& key, const ui
     mi_gallery* sg = f.sub;
     const int64_t nblk = filter_blocks(g->n);
     int rc;
-    if ((rc = device_grow(&f.rows, &f.rows_cap, (size_t)allowed)) != MI_OK) return rc;
-    if ((rc = grow2(&f.bcnt, &f.boff, &f.blk_cap, (size_t)nblk + 1)) != MI_OK) return rc;
+    if ((rc = f.rows.grow((size_t)allowed)) != MI_OK) return rc;
+    if ((rc = grow_all((size_t)nblk + 1, f.bcnt, f.boff)) != MI_OK) return rc;
     const int64_t mpad = round_up(allowed, TILE);
     launch_filter_compact(bits_dev, g->n, f.bcnt, f.boff, f.rows, s);
     launch_subset_gather(g->gal_f32, g->gal_img, g->rowstat, f.rows, allowed, mpad, g->dp, sg->gal_f32, sg->gal_img, sg->rowstat,
@@ -160,8 +138,8 @@ static int compact_search(mi_gallery* g, const void* q_dev, int dtype, int64_t r
   if (rc != MI_OK) return rc;
   mi_gallery* sg = f.sub;
   const int32_t ke = (int32_t)std::min<int64_t>(k, allowed);
-  if ((rc = grow2(&f.sidx, &f.ssc, &f.sout_cap, (size_t)nq * ke)) != MI_OK) return rc;
-  if ((rc = grow2(&f.idx, &f.sc, &f.out_cap, (size_t)nq * k)) != MI_OK) return rc;
+  if ((rc = grow_all((size_t)nq * ke, f.sidx, f.ssc)) != MI_OK) return rc;
+  if ((rc = grow_all((size_t)nq * k, f.idx, f.sc)) != MI_OK) return rc;
   if ((rc = search_sync(sg, q_dev, dtype, rs, cs, sg->norm_mode, nq, ke, f.sidx, f.ssc, nullptr)) != MI_OK) return rc;
   launch_filter_remap(f.sidx, f.ssc, nq, ke, k, f.rows, allowed, g->row_offset, f.idx, f.sc, s);
   HIPC(hipGetLastError());
@@ -268,18 +246,7 @@ int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, in
   }
 
   // queries: the host staging of mi_knn_search (grow-only slot 0)
-  auto stage = [&](int slot, size_t bytes) -> void* {
-    if (g->io_cap[slot] < bytes) {
-      (void)hipFree(g->io_buf[slot]);
-      g->io_buf[slot] = nullptr;
-      g->io_cap[slot] = 0;
-      const size_t want = bytes + bytes / 4 + 256;
-      if (device_malloc(&g->io_buf[slot], want) != hipSuccess) return nullptr;
-      g->io_cap[slot] = want;
-    }
-    return g->io_buf[slot];
-  };
-  void* qd = stage(0, (size_t)elems * esz);
+  void* qd = io_stage(g->io_q, (size_t)elems * esz);
   if (!qd) return done(fail(MI_ERR_NOMEM, "staging buffer of mi_knn_search_filtered"));
   if (hipMemcpy(qd, q, (size_t)elems * esz, hipMemcpyHostToDevice) != hipSuccess)
     return done(fail(MI_ERR_HIP, "H2D query copy failed"));
@@ -287,7 +254,7 @@ int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, in
   const uint64_t* bits_dev = allow_memspace == MI_DEVICE ? allow_bits : nullptr;
   auto upload_bits = [&]() -> int {
     if (bits_dev) return MI_OK;
-    int r = device_grow(&f.bits, &f.bits_cap, (size_t)nwords);
+    int r = f.bits.grow((size_t)nwords);
     if (r != MI_OK) return r;
     HIPC(hipMemcpy(f.bits, key.data(), (size_t)nwords * 8, hipMemcpyHostToDevice));
     bits_dev = f.bits;
@@ -308,11 +275,11 @@ int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, in
   const int32_t covers = kp >= g->n ? 1 : 0;
   info.kprime = kp;
   if ((rc = upload_bits()) != MI_OK) return done(rc);
-  int64_t* tidx = (int64_t*)stage(1, (size_t)nq * kp * 8);
-  float* tsc = (float*)stage(2, (size_t)nq * kp * 4);
+  int64_t* tidx = (int64_t*)io_stage(g->io_idx, (size_t)nq * kp * 8);
+  float* tsc = (float*)io_stage(g->io_sc, (size_t)nq * kp * 4);
   if (!tidx || !tsc) return done(fail(MI_ERR_NOMEM, "staging buffers of mi_knn_search_filtered"));
-  if ((rc = grow2(&f.idx, &f.sc, &f.out_cap, (size_t)nq * k)) != MI_OK) return done(rc);
-  if ((rc = device_grow(&f.ok, &f.ok_cap, (size_t)nq)) != MI_OK) return done(rc);
+  if ((rc = grow_all((size_t)nq * k, f.idx, f.sc)) != MI_OK) return done(rc);
+  if ((rc = f.ok.grow((size_t)nq)) != MI_OK) return done(rc);
   if ((rc = search_sync(g, qd, dtype, row_stride, col_stride, g->norm_mode, nq, kp, tidx, tsc, nullptr)) != MI_OK)
     return done(rc);
   launch_filter_overfetch(tidx, tsc, nq, kp, k, bits_dev, g->n, g->row_offset, covers, f.idx, f.sc, f.ok, s);
@@ -339,7 +306,7 @@ int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, in
     else
       for (int32_t c = 0; c < d; ++c) std::memcpy(dst + (size_t)c * esz, src + (size_t)c * col_stride * esz, esz);
   }
-  if ((rc = device_grow(reinterpret_cast<char**>(&f.qbuf), &f.qbuf_cap, packed.size())) != MI_OK) return done(rc);
+  if ((rc = f.qbuf.grow(packed.size())) != MI_OK) return done(rc);
   if (hipMemcpy(f.qbuf, packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess)
     return done(fail(MI_ERR_HIP, "H2D copy of the re-run queries failed"));
   std::vector<int64_t> ridx((size_t)m * k);

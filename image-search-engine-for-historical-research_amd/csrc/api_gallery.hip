@@ -45,12 +45,8 @@ int mi_gallery_destroy(mi_gallery* g) {
   (void)hipFree(g->samp_img);
   (void)hipFree(g->samp_scores);
   (void)hipFree(g->samp_f32);
-  for (void* b : g->io_buf) (void)hipFree(b);
-  range_scratch_free(g);
-  filter_scratch_free(g);
-  l2_scratch_free(g);
-  refine_scratch_free(g);
-  remove_scratch_free(g);
+  filter_release_sub(g);
+  g->scratch.reset();
   (void)hipFree(g->dif_ids);
   (void)hipFree(g->dif_vals);
   if (g->stream) (void)hipStreamDestroy(g->stream);

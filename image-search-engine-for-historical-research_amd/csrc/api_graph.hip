@@ -9,33 +9,22 @@ struct mi_graph {
   mi_gallery* rows = nullptr;
   int64_t n = 0;                       // rows of the gallery when the table was made: a search refuses any other number
   int32_t R = 0, ne = 0;
-  int32_t* adj = nullptr;              // [n][R], -1 = padding
-  int32_t* entries = nullptr;          // [ne]
-  // grow-only workspace of the searches
-  void* qraw = nullptr;                // queries of a host call as given
-  size_t qraw_cap = 0;                 // bytes
-  float* qpad = nullptr;               // [nq][dp]
-  size_t qpad_cap = 0;
-  uint32_t* vis = nullptr;             // [queries of a chunk][ceil(n / 32)] visited bitmaps
-  size_t vis_cap = 0;                  // words
-  int64_t* oidx = nullptr;             // results of a host call
-  float* oval = nullptr;
-  double* oval64 = nullptr;
-  int32_t* ovis = nullptr;
-  size_t oidx_cap = 0, oval_cap = 0, oval64_cap = 0, ovis_cap = 0;
+  DeviceBuf<int32_t> adj;              // [n][R], -1 = padding
+  DeviceBuf<int32_t> entries;          // [ne]
+  // grow-only workspace of the searches (all of these free themselves when the handle is deleted)
+  DeviceBuf<char> qraw;                // queries of a host call as given
+  DeviceBuf<float> qpad;               // [nq][dp]
+  DeviceBuf<uint32_t> vis;             // [queries of a chunk][ceil(n / 32)] visited bitmaps
+  DeviceBuf<int64_t> oidx;             // results of a host call
+  DeviceBuf<float> oval;
+  DeviceBuf<double> oval64;
+  DeviceBuf<int32_t> ovis;
   std::mutex mu;
 };
 
 // bytes of visited bitmaps one launch may use: a batch whose bitmaps need more is searched in chunks of queries
 constexpr size_t GRAPH_VIS_BYTES = (size_t)256 << 20;
 constexpr int64_t GRAPH_BUILD_BATCH = 8192;      // rows per exact search of mi_graph_build
-
-static void graph_free(mi_graph* gr) {
-  for (void* p : {(void*)gr->adj, (void*)gr->entries, gr->qraw, (void*)gr->qpad, (void*)gr->vis, (void*)gr->oidx, (void*)gr->oval,
-                  (void*)gr->oval64, (void*)gr->ovis})
-    (void)hipFree(p);
-  delete gr;
-}
 
 // what both search forms check before the handle is read
 static int graph_search_check(const mi_graph* gr, int64_t nq, int32_t k, int32_t ef) {
@@ -56,10 +45,10 @@ static int graph_enqueue(mi_graph* gr, const void* src, int dtype, int64_t rs, i
                          int64_t* out_idx, float* out_val, double* out_val64, int32_t* out_visited, hipStream_t s) {
   mi_gallery* g = gr->rows;
   int rc;
-  if ((rc = device_grow(&gr->qpad, &gr->qpad_cap, (size_t)nq * g->dp)) != MI_OK) return rc;
+  if ((rc = gr->qpad.grow((size_t)nq * g->dp)) != MI_OK) return rc;
   const int64_t words = (gr->n + 31) / 32;
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(GRAPH_VIS_BYTES / 4) / words));
-  if ((rc = device_grow(&gr->vis, &gr->vis_cap, (size_t)chunk * words)) != MI_OK) return rc;
+  if ((rc = gr->vis.grow((size_t)chunk * words)) != MI_OK) return rc;
   launch_l2_augment(src, dtype, nq, g->ud, rs, cs, gr->qpad, g->dp, s);
   for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
     const int64_t b = std::min<int64_t>(chunk, nq - q0);
@@ -80,10 +69,10 @@ static int graph_alloc(mi_gallery* rows, int32_t R, int32_t ne, mi_graph** out) 
   gr->n = rows->n;
   gr->R = R;
   gr->ne = ne;
-  hipError_t e = device_malloc((void**)&gr->adj, (size_t)gr->n * R * 4);
-  if (e == hipSuccess) e = device_malloc((void**)&gr->entries, (size_t)ne * 4);
+  hipError_t e = gr->adj.alloc((size_t)gr->n * R);
+  if (e == hipSuccess) e = gr->entries.alloc((size_t)ne);
   if (e != hipSuccess) {
-    graph_free(gr);
+    delete gr;
     return fail(e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, std::string("graph table: ") + hipGetErrorString(e));
   }
   *out = gr;
@@ -123,7 +112,7 @@ int mi_graph_create(mi_gallery* rows, const int32_t* neighbors, int32_t R, int n
   hipError_t e = hipMemcpy(gr->adj, tab, cnt * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(gr->entries, entries, (size_t)ne * 4, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
-    graph_free(gr);
+    delete gr;
     return fail(MI_ERR_HIP, std::string("graph table copy: ") + hipGetErrorString(e));
   }
   *out = gr;
@@ -151,7 +140,7 @@ int mi_graph_build(mi_gallery* rows, int32_t R, int32_t ne, mi_graph** out) {
   if ((rc = graph_alloc(g, R, nent, &gr)) != MI_OK) return rc;
   auto bail = [&](int code) {
     (void)hipStreamSynchronize(s);
-    graph_free(gr);
+    delete gr;
     return code;
   };
   TmpAlloc tmp;                                   // (freed on return; every path out of here has synchronised `s`)
@@ -237,7 +226,7 @@ int mi_graph_destroy(mi_graph* gr) {
   if (!gr) return MI_OK;
   (void)hipSetDevice(gr->rows->device);
   (void)hipDeviceSynchronize();
-  graph_free(gr);
+  delete gr;
   return MI_OK;
 }
 
@@ -273,13 +262,10 @@ int mi_graph_search(mi_graph* gr, const void* q, int64_t nq, int dtype, int64_t 
   int64_t elems;
   if ((rc = strided_extent(nq, g->ud, row_stride, col_stride, &elems)) != MI_OK) return rc;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
-  char* raw = (char*)gr->qraw;
-  rc = device_grow(&raw, &gr->qraw_cap, (size_t)elems * esz);
-  gr->qraw = raw;
-  if (rc != MI_OK) return rc;
+  if ((rc = gr->qraw.grow((size_t)elems * esz)) != MI_OK) return rc;
   const size_t cnt = (size_t)nq * k;
-  if ((rc = device_grow(&gr->oidx, &gr->oidx_cap, cnt)) != MI_OK || (rc = device_grow(&gr->oval, &gr->oval_cap, cnt)) != MI_OK ||
-      (rc = device_grow(&gr->oval64, &gr->oval64_cap, cnt)) != MI_OK || (rc = device_grow(&gr->ovis, &gr->ovis_cap, (size_t)nq)) != MI_OK)
+  if ((rc = gr->oidx.grow(cnt)) != MI_OK || (rc = gr->oval.grow(cnt)) != MI_OK ||
+      (rc = gr->oval64.grow(cnt)) != MI_OK || (rc = gr->ovis.grow((size_t)nq)) != MI_OK)
     return rc;
   HIPC(hipMemcpyAsync(gr->qraw, q, (size_t)elems * esz, hipMemcpyHostToDevice, s));
   if ((rc = graph_enqueue(gr, gr->qraw, dtype, row_stride, col_stride, nq, k, ef, gr->oidx, gr->oval, gr->oval64, gr->ovis, s)) !=

@@ -8,11 +8,6 @@
 
 // (struct mi_hamming: api_internal.h -- api_lsh.hip appends to its code storage)
 
-static int64_t hm_scratch_bytes(const mi_hamming* h) {
-  return (int64_t)(h->qraw_cap + h->qw_cap * 4 + h->mat_cap * 2 + h->bits_cap * 8 + h->oidx_cap * 8 + h->odist_cap * 4 +
-                   h->rmask_cap * 8 + h->roffs_cap * 2 + h->rseg_cap * 4 + h->rstage_cap * 8 + h->rlims_cap * 8);
-}
-
 // m host rows of nb bytes at `stride` -> packed device rows, on stream s
 static int hm_copy_rows(uint8_t* dst, const uint8_t* src, int64_t stride, int32_t nb, int64_t m, hipStream_t s) {
   if (stride == nb || m == 1) HIPC(hipMemcpyAsync(dst, src, (size_t)m * nb, hipMemcpyHostToDevice, s));
@@ -52,7 +47,7 @@ static int hm_search_core(mi_hamming* h, int64_t nq, int32_t k, const uint64_t* 
   const int64_t budget = g_hamming_matrix_bytes.load();
   const int64_t qc = npad == 0 ? nq : std::max<int64_t>(1, std::min<int64_t>(nq, budget / (npad * 2)));
   int rc;
-  if ((rc = device_grow(&h->mat, &h->mat_cap, (size_t)std::max<int64_t>(qc * npad, 64))) != MI_OK) return rc;
+  if ((rc = h->mat.grow((size_t)std::max<int64_t>(qc * npad, 64))) != MI_OK) return rc;
   for (int64_t q0 = 0; q0 < nq; q0 += qc) {
     const int32_t b = (int32_t)std::min<int64_t>(qc, nq - q0);
     launch_hamming_dist(h->codes, h->nbits, h->n, h->qw + q0 * h->wq, b, allow_dev, h->mat, s);
@@ -85,9 +80,9 @@ static int hr_prepare(mi_hamming* h, int64_t nq, int64_t b0, HrPlan* p) {
   p->qc = qc;
   p->nchunks = (nq + qc - 1) / qc;
   int rc;
-  if ((rc = device_grow(&h->rmask, &h->rmask_cap, (size_t)(nbl * qc))) != MI_OK) return rc;
-  if ((rc = device_grow(&h->roffs, &h->roffs_cap, (size_t)(nbl * qc))) != MI_OK) return rc;
-  return device_grow(&h->rseg, &h->rseg_cap, (size_t)(nseg * qc));
+  if ((rc = h->rmask.grow((size_t)(nbl * qc))) != MI_OK) return rc;
+  if ((rc = h->roffs.grow((size_t)(nbl * qc))) != MI_OK) return rc;
+  return h->rseg.grow((size_t)(nseg * qc));
 }
 
 static HammingRangeArgs hr_args(const mi_hamming* h, const HrCall& c, const HrPlan& p, int64_t q0) {
@@ -154,7 +149,7 @@ static int hr_host(mi_hamming* h, const HrCall& c, int64_t max_results, int64_t*
   HrPlan p;
   int rc;
   if ((rc = hr_prepare(h, c.nq, c.qw ? 0 : (c.row0 + 1) >> 6, &p)) != MI_OK) return rc;
-  if ((rc = device_grow(&h->rlims, &h->rlims_cap, (size_t)c.nq + 1)) != MI_OK) return rc;
+  if ((rc = h->rlims.grow((size_t)c.nq + 1)) != MI_OK) return rc;
   if ((rc = hr_count(h, c, p, h->rlims, s)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(out_lims, h->rlims, ((size_t)c.nq + 1) * 8, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
@@ -165,10 +160,10 @@ static int hr_host(mi_hamming* h, const HrCall& c, int64_t max_results, int64_t*
   if (total == 0) return MI_OK;
   int64_t most = 0;                                   // hits of the fullest chunk
   for (int64_t q0 = 0; q0 < c.nq; q0 += p.qc) most = std::max(most, out_lims[std::min(q0 + p.qc, c.nq)] - out_lims[q0]);
-  if ((rc = device_grow(&h->rstage, &h->rstage_cap, (size_t)most)) != MI_OK) return rc;
-  if ((rc = device_grow(&h->oidx, &h->oidx_cap, (size_t)total)) != MI_OK) return rc;
-  if (out_dist && (rc = device_grow(&h->odist, &h->odist_cap, (size_t)total)) != MI_OK) return rc;
-  if ((rc = hr_fill(h, c, p, h->rlims, total, h->oidx, out_dist ? h->odist : nullptr, s)) != MI_OK) return rc;
+  if ((rc = h->rstage.grow((size_t)most)) != MI_OK) return rc;
+  if ((rc = h->oidx.grow((size_t)total)) != MI_OK) return rc;
+  if (out_dist && (rc = h->odist.grow((size_t)total)) != MI_OK) return rc;
+  if ((rc = hr_fill(h, c, p, h->rlims, total, h->oidx, out_dist ? h->odist.get() : nullptr, s)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(out_idx, h->oidx, (size_t)total * 8, hipMemcpyDeviceToHost, s));
   if (out_dist) HIPC(hipMemcpyAsync(out_dist, h->odist, (size_t)total * 4, hipMemcpyDeviceToHost, s));
   HIPC(hipStreamSynchronize(s));
@@ -199,14 +194,14 @@ int mi_hamming_create(const void* codes, int64_t n, int32_t nbits, int64_t row_s
   h->nb = nbits / 8;
   h->W32 = (nbits + 31) / 32;
   h->wq = hamming_query_words(h->W32);
-  h->codes_bytes = (size_t)((capacity + 63) / 64) * h->W32 * 64 * 4;
+  const size_t codes_words = (size_t)((capacity + 63) / 64) * h->W32 * 64;
   auto cleanup = [&](int code) {
     mi_hamming_destroy(h);
     return code;
   };
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = device_malloc((void**)&h->codes, h->codes_bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(h->codes, 0, h->codes_bytes, h->stream);
+  if (e == hipSuccess) e = h->codes.alloc(codes_words);
+  if (e == hipSuccess) e = hipMemsetAsync(h->codes, 0, codes_words * 4, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess)
     return cleanup(fail(e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, std::string("binary index: ") + hipGetErrorString(e)));
@@ -270,7 +265,7 @@ int mi_hamming_info(const mi_hamming* h, int64_t* n, int32_t* nbits, int32_t* de
   if (device) *device = h->device;
   if (row_offset) *row_offset = h->row_offset;
   if (capacity) *capacity = h->cap;
-  if (hbm_bytes) *hbm_bytes = (int64_t)h->codes_bytes + hm_scratch_bytes(h);
+  if (hbm_bytes) *hbm_bytes = (int64_t)h->bufs.bytes();
   return MI_OK;
 }
 
@@ -315,25 +310,16 @@ int mi_hamming_search(mi_hamming* h, const void* q_codes, int64_t nq, int64_t q_
   hipStream_t s = h->stream;
   int rc;
   const size_t cnt = (size_t)nq * k;
-  if ((rc = device_grow(&h->qraw, &h->qraw_cap, (size_t)nq * h->nb)) != MI_OK) return rc;
-  if ((rc = device_grow(&h->qw, &h->qw_cap, (size_t)nq * h->wq)) != MI_OK) return rc;
-  if ((rc = device_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
-  if (out_dist && (rc = device_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
-  const uint64_t* allow_dev = allow_bits;
-  if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
-    const size_t words = (size_t)((h->n + 63) / 64);
-    if ((rc = device_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
-    HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
-    allow_dev = h->bits;
-  }
+  if ((rc = h->qraw.grow((size_t)nq * h->nb)) != MI_OK) return rc;
+  if ((rc = h->qw.grow((size_t)nq * h->wq)) != MI_OK) return rc;
+  if ((rc = h->oidx.grow(cnt)) != MI_OK) return rc;
+  if (out_dist && (rc = h->odist.grow(cnt)) != MI_OK) return rc;
+  const uint64_t* allow_dev;
+  if ((rc = allow_on_device(h->bits, allow_bits, allow_memspace, h->n, s, &allow_dev)) != MI_OK) return rc;
   if ((rc = hm_copy_rows(h->qraw, (const uint8_t*)q_codes, q_row_stride_bytes, h->nb, nq, s)) != MI_OK) return rc;
   launch_hamming_query_words(h->qraw, h->nb, h->nbits, nq, h->qw, s);
-  if ((rc = hm_search_core(h, nq, k, allow_dev, h->oidx, out_dist ? h->odist : nullptr, s)) != MI_OK) return rc;
-  HIPC(hipMemcpyAsync(out_idx, h->oidx, cnt * 8, hipMemcpyDeviceToHost, s));
-  if (out_dist) HIPC(hipMemcpyAsync(out_dist, h->odist, cnt * 4, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return MI_OK;
+  if ((rc = hm_search_core(h, nq, k, allow_dev, h->oidx, out_dist ? h->odist.get() : nullptr, s)) != MI_OK) return rc;
+  return topk_to_host(out_idx, h->oidx, out_dist, h->odist.get(), cnt, s, t0, out_seconds);
 }
 
 int mi_hamming_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, int32_t k, const uint64_t* allow_bits_dev,
@@ -346,7 +332,7 @@ int mi_hamming_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t nq, in
   HIPC(hipSetDevice(h->device));
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  if ((rc = device_grow(&h->qw, &h->qw_cap, (size_t)nq * h->wq)) != MI_OK) return rc;
+  if ((rc = h->qw.grow((size_t)nq * h->wq)) != MI_OK) return rc;
   launch_hamming_query_words(q_dev, h->nb, h->nbits, nq, h->qw, s);
   return hm_search_core(h, nq, k, allow_bits_dev, out_idx_dev, out_dist_dev, s);
 }
@@ -371,16 +357,10 @@ int mi_hamming_range_search(mi_hamming* h, const void* q_codes, int64_t nq, int6
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   int rc;
-  if ((rc = device_grow(&h->qraw, &h->qraw_cap, (size_t)nq * h->nb)) != MI_OK) return rc;
-  if ((rc = device_grow(&h->qw, &h->qw_cap, (size_t)nq * h->wq)) != MI_OK) return rc;
+  if ((rc = h->qraw.grow((size_t)nq * h->nb)) != MI_OK) return rc;
+  if ((rc = h->qw.grow((size_t)nq * h->wq)) != MI_OK) return rc;
   HrCall c;
-  c.allow = allow_bits;
-  if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
-    const size_t words = (size_t)((h->n + 63) / 64);
-    if ((rc = device_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
-    HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
-    c.allow = h->bits;
-  }
+  if ((rc = allow_on_device(h->bits, allow_bits, allow_memspace, h->n, s, &c.allow)) != MI_OK) return rc;
   if ((rc = hm_copy_rows(h->qraw, (const uint8_t*)q_codes, q_row_stride_bytes, h->nb, nq, s)) != MI_OK) return rc;
   launch_hamming_query_words(h->qraw, h->nb, h->nbits, nq, h->qw, s);
   c.qw = h->qw;
@@ -409,11 +389,11 @@ int mi_hamming_range_search_device(mi_hamming* h, const uint8_t* q_dev, int64_t 
   }
   int rc;
   HrPlan p;
-  if ((rc = device_grow(&h->qw, &h->qw_cap, (size_t)nq * h->wq)) != MI_OK) return rc;
+  if ((rc = h->qw.grow((size_t)nq * h->wq)) != MI_OK) return rc;
   if ((rc = hr_prepare(h, nq, 0, &p)) != MI_OK) return rc;
   // the hits of one chunk: at most the caller's capacity (beyond it nothing is written), at most every row for every query
   const int64_t stage = std::min<int64_t>(max_results, std::min(p.qc, nq) * h->n);
-  if (stage > 0 && (rc = device_grow(&h->rstage, &h->rstage_cap, (size_t)stage)) != MI_OK) return rc;
+  if (stage > 0 && (rc = h->rstage.grow((size_t)stage)) != MI_OK) return rc;
   launch_hamming_query_words(q_dev, h->nb, h->nbits, nq, h->qw, s);
   HrCall c;
   c.qw = h->qw;
@@ -453,9 +433,7 @@ int mi_hamming_destroy(mi_hamming* h) {
   if (!h) return MI_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->codes, (void*)h->qraw, (void*)h->qw, (void*)h->mat, (void*)h->bits, (void*)h->oidx, (void*)h->odist,
-                  (void*)h->rmask, (void*)h->roffs, (void*)h->rseg, (void*)h->rstage, (void*)h->rlims})
-    (void)hipFree(p);
+  h->bufs.reset();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return MI_OK;

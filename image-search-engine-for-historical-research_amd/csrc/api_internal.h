@@ -23,6 +23,7 @@
 //   api_graph.hip     graph index (mi_graph): neighbour table over a gallery's rows, best-first search (graph_search.hip), table
 //                     from exact nearest-neighbour lists (graph_build.hip)
 // Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index family)
+// The handles' grow-only device buffers own themselves: device_buf.h (DeviceBuf<T> and the per-handle DeviceBufSet; host code only)
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -95,6 +96,7 @@ MI_INTERNAL const char* last_error_message();
   do {                     \
     if (!(cond)) return fail(MI_ERR_INVALID, msg); \
   } while (0)
+#include "device_buf.h"   // DeviceBuf<T>, DeviceBufSet, grow_all
 
 
 // The host half of a row removal on a PQ or an IVF-PQ index (mi_pq_remove_rows, mi_ivfpq_remove_rows; defined in api_pq.hip): the
@@ -241,48 +243,43 @@ struct mi_gallery {
   size_t ev_used = 0;
   std::vector<float> launch_ms_log;   // duration of every timed scoring launch since the last statistics reset (capped)
   hipStream_t ev_stream = nullptr;
-  // grow-only device staging of the host entry point mi_knn_search (queries in, results out): a hipMalloc / hipFree
-  // pair per call costs more than a single-query search
-  void* io_buf[3] = {nullptr, nullptr, nullptr};
-  size_t io_cap[3] = {0, 0, 0};
-  // grow-only device buffers of the range search (api_range.hip), freed with the handle
+  // Every grow-only device buffer below is a DeviceBuf on `scratch`: it dies with the handle (scratch.reset() in the destroy),
+  // and nothing else has to name it.  The primary storage above and the workspace arena are NOT: their ownership is traded with
+  // the process's spare slots (api_state.hip), so they stay bare pointers freed by hand.
+  DeviceBufSet scratch;
+  // device staging of the host entry point mi_knn_search (queries in, results out; io_stage): a hipMalloc / hipFree pair per
+  // call costs more than a single-query search
+  DeviceBuf<char> io_q{scratch}, io_idx{scratch}, io_sc{scratch};
+  // the range search (api_range.hip)
   struct RangeScratch {
-    uint32_t* rows = nullptr;              // [QB][surv_cap] rows handed to the exact re-score
-    uint32_t* rcnt = nullptr;              // [QB]
-    double* sc = nullptr;                  // [QB][surv_cap] their f64 scores
-    uint32_t lcap = 0;                     // surv_cap the three above were sized for
-    uint64_t* akey = nullptr;              // hits of the batch, chunk after chunk
-    uint32_t* arow = nullptr;
-    size_t acap = 0;
-    uint64_t* bkey[2] = {nullptr, nullptr};   // hits of the batch in CSR order (ping-pong of the merge passes)
-    uint32_t* brow[2] = {nullptr, nullptr};
-    size_t bcap = 0;
-    uint64_t* coff = nullptr;              // [chunks][QB] offset of query q's hits of chunk c in akey / arow
-    uint32_t* ccnt = nullptr;              // [chunks][QB] their number
-    size_t ccap = 0;                       // chunks
-    int64_t* lims = nullptr;               // [QB + 1]
-    unsigned long long* total = nullptr;   // hits of the current chunk
-  } range;
+    explicit RangeScratch(DeviceBufSet& s) : rows(s), rcnt(s), sc(s), akey(s), arow(s), bkey{DeviceBuf<uint64_t>(s), DeviceBuf<uint64_t>(s)},
+                                             brow{DeviceBuf<uint32_t>(s), DeviceBuf<uint32_t>(s)}, coff(s), ccnt(s), lims(s), total(s) {}
+    DeviceBuf<uint32_t> rows;              // [QB][surv_cap] rows handed to the exact re-score (these three: exactly that size)
+    DeviceBuf<uint32_t> rcnt;              // [QB]
+    DeviceBuf<double> sc;                  // [QB][surv_cap] their f64 scores
+    DeviceBuf<uint64_t> akey;              // hits of the batch, chunk after chunk
+    DeviceBuf<uint32_t> arow;
+    DeviceBuf<uint64_t> bkey[2];           // hits of the batch in CSR order (ping-pong of the merge passes)
+    DeviceBuf<uint32_t> brow[2];
+    DeviceBuf<uint64_t> coff;              // [chunks][QB] offset of query q's hits of chunk c in akey / arow
+    DeviceBuf<uint32_t> ccnt;              // [chunks][QB] their number
+    DeviceBuf<int64_t> lims;               // [QB + 1]
+    DeviceBuf<unsigned long long> total;   // hits of the current chunk
+  } range{scratch};
   // filtered top-K search (api_filter.hip): grow-only device buffers and the compacted sub-gallery, freed with the handle, never
   // handed to the spare-buffer slots; invalidated by mi_gallery_append*, mi_gallery_set_image_dtype and mi_gallery_remove_rows (filter_invalidate)
   int filter_path = 0;                 // option "filter_path": 0 = auto, 1 = always compact, 2 = always over-fetch
   double filter_compact_max = 0.15;    // option "filter_compact_max": auto compacts at selectivity <= this
   int filter_cache = 1;                // option "filter_cache": keep the sub-gallery for the next call with the same bitmap
   struct FilterScratch {
-    uint64_t* bits = nullptr;            // device copy of a host bitmap
-    size_t bits_cap = 0;                 // words
-    uint32_t* bcnt = nullptr;            // [blocks] allowed rows per compaction workgroup, then their offsets [blocks + 1]
-    uint32_t* boff = nullptr;
-    size_t blk_cap = 0;
-    uint32_t* rows = nullptr;            // allowed local rows of the sub-gallery's bitmap, ascending
-    size_t rows_cap = 0;
-    int64_t *idx = nullptr, *sidx = nullptr;   // [nq][k] answer of the call / [nq][k_eff] answer of the sub-gallery
-    float *sc = nullptr, *ssc = nullptr;
-    size_t out_cap = 0, sout_cap = 0;    // entries
-    uint32_t* ok = nullptr;              // [nq] over-fetch certificate per query
-    size_t ok_cap = 0;
-    void* qbuf = nullptr;                // queries the over-fetch could not certify, packed
-    size_t qbuf_cap = 0;                 // bytes
+    explicit FilterScratch(DeviceBufSet& s) : bits(s), bcnt(s), boff(s), rows(s), idx(s), sidx(s), sc(s), ssc(s), ok(s), qbuf(s) {}
+    DeviceBuf<uint64_t> bits;            // device copy of a host bitmap
+    DeviceBuf<uint32_t> bcnt, boff;      // [blocks] allowed rows per compaction workgroup, then their offsets [blocks + 1]
+    DeviceBuf<uint32_t> rows;            // allowed local rows of the sub-gallery's bitmap, ascending
+    DeviceBuf<int64_t> idx, sidx;        // [nq][k] answer of the call / [nq][k_eff] answer of the sub-gallery
+    DeviceBuf<float> sc, ssc;
+    DeviceBuf<uint32_t> ok;              // [nq] over-fetch certificate per query
+    DeviceBuf<char> qbuf;                // queries the over-fetch could not certify, packed
     mi_gallery* sub = nullptr;           // compacted sub-gallery (shares the parent's stream)
     int64_t sub_cap = 0;                 // rows its buffers hold
     bool valid = false;                  // sub holds the rows `key` allows of a parent of key_n rows
@@ -290,41 +287,31 @@ struct mi_gallery {
     std::vector<uint64_t> key;           // the bitmap it was built from (bits at or beyond key_n cleared)
     std::vector<uint64_t> last_key;      // the bitmap of the previous call (auto compacts a bitmap it sees twice in a row)
     int64_t last_key_n = -1;
-  } filt;
-  // squared-L2 search (api_l2.hip): grow-only device buffers, freed with the handle
+  } filt{scratch};
+  // squared-L2 search (api_l2.hip)
   struct L2Scratch {
-    void* qraw = nullptr;                // queries of a host call as given
-    size_t qraw_cap = 0;                 // bytes
-    float* qaug = nullptr;               // [nq][dp] extended queries
-    size_t qaug_cap = 0;                 // floats
-    int64_t* ids = nullptr;              // [nq][ke] rows the selection certified
-    size_t ids_cap = 0;
-    int64_t* oidx = nullptr;             // [nq][k] results of a host call
-    float* odist = nullptr;
-    double* odist64 = nullptr;
-    size_t out_cap = 0;
-  } l2;
-  // re-ranking of shortlists (api_refine.hip): grow-only device buffers, freed with the handle
+    explicit L2Scratch(DeviceBufSet& s) : qraw(s), qaug(s), ids(s), oidx(s), odist(s), odist64(s) {}
+    DeviceBuf<char> qraw;                // queries of a host call as given
+    DeviceBuf<float> qaug;               // [nq][dp] extended queries
+    DeviceBuf<int64_t> ids;              // [nq][ke] rows the selection certified
+    DeviceBuf<int64_t> oidx;             // [nq][k] results of a host call
+    DeviceBuf<float> odist;
+    DeviceBuf<double> odist64;
+  } l2{scratch};
+  // re-ranking of shortlists (api_refine.hip)
   struct RefineScratch {
-    void* qraw = nullptr;                // queries of a host call as given
-    size_t qraw_cap = 0;                 // bytes
-    float* qpad = nullptr;               // [nq][dp] queries with 16-byte aligned rows
-    size_t qpad_cap = 0;                 // floats
-    double* val = nullptr;               // [nq][kc] f64 value of every candidate
-    size_t val_cap = 0;
-    int64_t* cand = nullptr;             // [nq][kc] candidates of a host call
-    size_t cand_cap = 0;
-    int64_t* oidx = nullptr;             // [nq][k] results of a host call
-    float* oval = nullptr;
-    double* oval64 = nullptr;
-    size_t out_cap = 0;
-  } refine;
-  // row removal (api_remove.hip): one grow-only arena -- staging area of "remove_block_rows" rows in the gallery's own layout,
-  // keep-list, bitmap, scan buffers --, freed with the handle, never handed to the spare-buffer slots
-  struct RemoveScratch {
-    void* arena = nullptr;
-    size_t bytes = 0;
-  } rm;
+    explicit RefineScratch(DeviceBufSet& s) : qraw(s), qpad(s), val(s), cand(s), oidx(s), oval(s), oval64(s) {}
+    DeviceBuf<char> qraw;                // queries of a host call as given
+    DeviceBuf<float> qpad;               // [nq][dp] queries with 16-byte aligned rows
+    DeviceBuf<double> val;               // [nq][kc] f64 value of every candidate
+    DeviceBuf<int64_t> cand;             // [nq][kc] candidates of a host call
+    DeviceBuf<int64_t> oidx;             // [nq][k] results of a host call
+    DeviceBuf<float> oval;
+    DeviceBuf<double> oval64;
+  } refine{scratch};
+  // row removal (api_remove.hip): one arena of exactly the bytes the largest call needed -- staging area of "remove_block_rows"
+  // rows in the gallery's own layout, keep-list, bitmap, scan buffers
+  DeviceBuf<char> rm_arena{scratch};
   // diffusion state (offline matrix rows kept on the device for the online stage); dropped by mi_gallery_remove_rows
   int32_t* dif_ids = nullptr;
   float* dif_vals = nullptr;
@@ -338,28 +325,22 @@ struct mi_hamming {
   int device = 0;
   int64_t n = 0, cap = 0, row_offset = 0;
   int32_t nbits = 0, nb = 0, W32 = 0, wq = 0;      // bits, bytes, 32-bit words of a code; words of a stored query
-  uint32_t* codes = nullptr;                       // [ceil(cap / 64)][W32][64]
-  size_t codes_bytes = 0;
+  DeviceBufSet bufs;                               // every device allocation of the handle: hbm_bytes is bufs.bytes()
+  DeviceBuf<uint32_t> codes{bufs};                 // [ceil(cap / 64)][W32][64], exactly
   hipStream_t stream = nullptr;
-  uint8_t* qraw = nullptr;                         // query bytes of a host call, packed [nq][nb]
-  size_t qraw_cap = 0;
-  uint32_t* qw = nullptr;                          // [nq][wq]
-  size_t qw_cap = 0;
-  uint16_t* mat = nullptr;                         // distance matrix [queries of a chunk][round_up(n, 64)]
-  size_t mat_cap = 0;
-  uint64_t* bits = nullptr;                        // device copy of a host bitmap
-  size_t bits_cap = 0;
-  int64_t* oidx = nullptr;                         // results of a host call
-  int32_t* odist = nullptr;
-  size_t oidx_cap = 0, odist_cap = 0;
+  DeviceBuf<uint8_t> qraw{bufs};                   // query bytes of a host call, packed [nq][nb]
+  DeviceBuf<uint32_t> qw{bufs};                    // [nq][wq]
+  DeviceBuf<uint16_t> mat{bufs};                   // distance matrix [queries of a chunk][round_up(n, 64)]
+  DeviceBuf<uint64_t> bits{bufs};                  // device copy of a host bitmap
+  DeviceBuf<int64_t> oidx{bufs};                   // results of a host call
+  DeviceBuf<int32_t> odist{bufs};
   // radius search (hamming_range.hip): ballots, prefixes and segment sums of one chunk of queries, the chunk's hits in id order,
   // CSR offsets of a host call
-  unsigned long long* rmask = nullptr;
-  uint16_t* roffs = nullptr;
-  uint32_t* rseg = nullptr;
-  unsigned long long* rstage = nullptr;
-  int64_t* rlims = nullptr;
-  size_t rmask_cap = 0, roffs_cap = 0, rseg_cap = 0, rstage_cap = 0, rlims_cap = 0;
+  DeviceBuf<unsigned long long> rmask{bufs};
+  DeviceBuf<uint16_t> roffs{bufs};
+  DeviceBuf<uint32_t> rseg{bufs};
+  DeviceBuf<unsigned long long> rstage{bufs};
+  DeviceBuf<int64_t> rlims{bufs};
   std::mutex mu;
 };
 
@@ -399,10 +380,7 @@ MI_INTERNAL int gallery_alloc(mi_gallery* g);
 MI_INTERNAL int gallery_create_any(const void* data, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
                                    int memspace, int norm_mode, int metric, int device, int64_t row_offset, int64_t capacity,
                                    mi_gallery** out);
-// ---- api_range.hip
-MI_INTERNAL void range_scratch_free(mi_gallery* g);
 // ---- api_filter.hip
-MI_INTERNAL void filter_scratch_free(mi_gallery* g);
 MI_INTERNAL void filter_release_sub(mi_gallery* g);     // frees the compacted sub-gallery (option "filter_cache" 0)
 MI_INTERNAL void filter_invalidate(mi_gallery* g);      // rows or image type of the parent changed: the sub-gallery is stale
 // mi_knn_search_filtered (argument checks included); l2_caller: mi_knn_search_l2 on its own gallery, which HOLDS the handle's
@@ -410,25 +388,34 @@ MI_INTERNAL void filter_invalidate(mi_gallery* g);      // rows or image type of
 MI_INTERNAL int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                                      int32_t k, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
                                      mi_filter_info* out_info, double* out_seconds, bool l2_caller);
-// ---- api_l2.hip
-MI_INTERNAL void l2_scratch_free(mi_gallery* g);
-// ---- api_refine.hip
-MI_INTERNAL void refine_scratch_free(mi_gallery* g);
-// ---- api_remove.hip
-MI_INTERNAL void remove_scratch_free(mi_gallery* g);
-// ---- helpers of the index handles (static: every translation unit has its own, nothing is exported)
-// a grow-only device buffer of `count` elements (contents are not kept): a quarter of spare, so that a slowly growing request does
-// not reallocate every call
-static inline size_t grow_capacity(size_t count) { return count + count / 4 + 64; }
-template <typename T>
-static int device_grow(T** p, size_t* cap, size_t count) {
-  if (*p && *cap >= count) return MI_OK;
-  (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = grow_capacity(count);
-  HIPC(device_malloc((void**)p, want * sizeof(T)));
-  *cap = want;
+// ---- helpers of the handles (static: every translation unit has its own, nothing is exported)
+// the staging of a host search on a gallery (mi_gallery::io_*): `bytes` bytes, NULL when out of memory.  Sized in bytes, with its
+// own spare of a quarter + 256
+static inline void* io_stage(DeviceBuf<char>& b, size_t bytes) {
+  return b.ensure(bytes, bytes + bytes / 4 + 256) == MI_OK ? b.get() : nullptr;
+}
+// the allow bitmap of a search on an index of n rows, where the kernels read it: the caller's device pointer, or the host words
+// copied into `bits` on `stream`
+static inline int allow_on_device(DeviceBuf<uint64_t>& bits, const uint64_t* allow_bits, int memspace, int64_t n, hipStream_t stream,
+                                  const uint64_t** allow_dev) {
+  *allow_dev = allow_bits;
+  if (!allow_bits || memspace != MI_HOST || n <= 0) return MI_OK;
+  const size_t words = (size_t)((n + 63) / 64);
+  int rc;
+  if ((rc = bits.grow(words)) != MI_OK) return rc;
+  HIPC(hipMemcpyAsync(bits, allow_bits, words * 8, hipMemcpyHostToDevice, stream));
+  *allow_dev = bits;
+  return MI_OK;
+}
+// the tail of a host top-K search on an index: `cnt` ids and (when asked for) distances back to the caller, the stream drained,
+// the call's wall time since t0
+template <typename D>
+static int topk_to_host(int64_t* out_idx, const int64_t* idx_dev, D* out_dist, const D* dist_dev, size_t cnt, hipStream_t s,
+                        std::chrono::steady_clock::time_point t0, double* out_seconds) {
+  HIPC(hipMemcpyAsync(out_idx, idx_dev, cnt * 8, hipMemcpyDeviceToHost, s));
+  if (out_dist) HIPC(hipMemcpyAsync(out_dist, dist_dev, cnt * sizeof(D), hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return MI_OK;
 }
 // api_pq.hip, api_pq_train.hip, api_ivfpq.hip: host rows (any strides, in elements) hold no NaN and no infinity
@@ -455,14 +442,14 @@ static inline bool codes_below(const uint8_t* p, int64_t rows, int64_t stride, i
       if (p[r * stride + b] >= limit) return false;
   return true;
 }
-// `rows` host rows of d elements from row r0 on -> *xraw (grown to fit), packed [rows][d] in their own type, on `stream`.  Rows that
+// `rows` host rows of d elements from row r0 on -> xraw (grown to fit), packed [rows][d] in their own type, on `stream`.  Rows that
 // are not contiguous are packed on the host first, in `pack` (the copy has completed on return in that case)
-static inline int stage_host_rows(char** xraw, size_t* cap, int32_t d, hipStream_t stream, const void* x, int64_t r0, int64_t rows,
+static inline int stage_host_rows(DeviceBuf<char>& xraw, int32_t d, hipStream_t stream, const void* x, int64_t r0, int64_t rows,
                                   int dtype, int64_t rs, int64_t cs, std::vector<char>& pack) {
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   const size_t bytes = (size_t)rows * d * esz;
   int rc;
-  if ((rc = device_grow(xraw, cap, bytes)) != MI_OK) return rc;
+  if ((rc = xraw.grow(bytes)) != MI_OK) return rc;
   const char* src = (const char*)x + (size_t)r0 * rs * esz;
   if (!(cs == 1 && (rs == d || rows == 1))) {
     pack.resize(bytes);
@@ -471,7 +458,7 @@ static inline int stage_host_rows(char** xraw, size_t* cap, int32_t d, hipStream
         std::memcpy(pack.data() + ((size_t)r * d + c) * esz, src + ((size_t)r * rs + (size_t)c * cs) * esz, esz);
     src = pack.data();
   }
-  HIPC(hipMemcpyAsync(*xraw, src, bytes, hipMemcpyHostToDevice, stream));
+  HIPC(hipMemcpyAsync(xraw, src, bytes, hipMemcpyHostToDevice, stream));
   if (src == pack.data()) HIPC(hipStreamSynchronize(stream));
   return MI_OK;
 }

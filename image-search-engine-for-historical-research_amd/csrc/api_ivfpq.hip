@@ -15,41 +15,33 @@ struct mi_ivfpq {
   int32_t d = 0, m = 0, ks = 0, L = 0, MQ = 0, nlist = 0;
   bool residual = false;                           // codes quantize the residual against the row's list
   std::vector<float> cb_host, coarse_host;         // [m][ks][L], [nlist][d]
-  float *cb = nullptr, *coarse = nullptr;
+  DeviceBufSet bufs;                               // every device allocation of the handle: hbm_bytes is bufs.bytes()
+  DeviceBuf<float> cb{bufs}, coarse{bufs};         // (down to `flag`: exactly their size, allocated at creation)
   int64_t pool_blocks = 0, pool_used = 0;          // ceil(cap / 64) + nlist: every list may end in a partly filled block
   std::vector<uint32_t> free_blocks;               // blocks below pool_used that a removal emptied: taken first, last in first out
-  uint32_t* codes = nullptr;                       // [pool_blocks][MQ][64]
-  uint32_t* rowid = nullptr;                       // [pool_blocks][64]
-  uint32_t* blk_table = nullptr;                   // [pool_blocks]: the blocks of list 0, of list 1, ...
-  int32_t* list_off = nullptr;                     // [nlist + 1] into blk_table, followed by
+  DeviceBuf<uint32_t> codes{bufs};                 // [pool_blocks][MQ][64]
+  DeviceBuf<uint32_t> rowid{bufs};                 // [pool_blocks][64]
+  DeviceBuf<uint32_t> blk_table{bufs};             // [pool_blocks]: the blocks of list 0, of list 1, ...
+  DeviceBuf<int32_t> list_off{bufs};               // [nlist + 1] into blk_table, followed by
   uint32_t* list_rows = nullptr;                   // [nlist] rows per list (the same allocation)
   std::vector<std::vector<uint32_t>> blocks;       // per list
   std::vector<int64_t> list_size;                  // rows per list
   std::vector<int64_t> slot_of_row;                // pblock * 64 + lane
   std::vector<uint8_t> list_of_row;
-  uint32_t* flag = nullptr;
+  DeviceBuf<uint32_t> flag{bufs};                  // (256 bytes)
   hipStream_t stream = nullptr;
-  char* xraw = nullptr;                            // rows / queries of a host call, packed [rows][d] in their own type
-  uint8_t *cbytes = nullptr, *lbytes = nullptr;    // packed code bytes [rows][m] and list ids [rows] on their way in
-  int64_t* slots = nullptr;
-  float* tab = nullptr;                            // [queries of a chunk][m][ks]; residual: [queries of a chunk][nprobe][m][ks]
-  int32_t *praw = nullptr, *pnorm = nullptr, *pref = nullptr, *pex = nullptr;   // probes: chosen, normalised, prefix; a host call's own
-  uint64_t* part = nullptr;                        // [queries of a chunk][slabs][k]
-  uint64_t* bits = nullptr;
-  uint32_t* rmpref = nullptr;                      // mi_ivfpq_remove_rows: prefix counts per bitmap word
-  int64_t* oidx = nullptr;
-  float* odist = nullptr;
-  size_t rmpref_cap = 0;
-  size_t xraw_cap = 0, cbytes_cap = 0, lbytes_cap = 0, slots_cap = 0, tab_cap = 0, praw_cap = 0, pnorm_cap = 0, pref_cap = 0, pex_cap = 0,
-         part_cap = 0, bits_cap = 0, oidx_cap = 0, odist_cap = 0;
+  DeviceBuf<char> xraw{bufs};                      // rows / queries of a host call, packed [rows][d] in their own type
+  DeviceBuf<uint8_t> cbytes{bufs}, lbytes{bufs};   // packed code bytes [rows][m] and list ids [rows] on their way in
+  DeviceBuf<int64_t> slots{bufs};
+  DeviceBuf<float> tab{bufs};                      // [queries of a chunk][m][ks]; residual: [queries of a chunk][nprobe][m][ks]
+  DeviceBuf<int32_t> praw{bufs}, pnorm{bufs}, pref{bufs}, pex{bufs};   // probes: chosen, normalised, prefix; a host call's own
+  DeviceBuf<uint64_t> part{bufs};                  // [queries of a chunk][slabs][k]
+  DeviceBuf<uint64_t> bits{bufs};
+  DeviceBuf<uint32_t> rmpref{bufs};                // mi_ivfpq_remove_rows: prefix counts per bitmap word
+  DeviceBuf<int64_t> oidx{bufs};
+  DeviceBuf<float> odist{bufs};
   std::mutex mu;
 };
-
-static int64_t ivf_scratch_bytes(const mi_ivfpq* h) {
-  return (int64_t)(h->xraw_cap + h->cbytes_cap + h->lbytes_cap + h->slots_cap * 8 + h->tab_cap * 4 +
-                   (h->praw_cap + h->pnorm_cap + h->pref_cap + h->pex_cap) * 4 + h->part_cap * 8 + h->bits_cap * 8 + h->oidx_cap * 8 +
-                   h->odist_cap * 4 + h->rmpref_cap * 4);
-}
 
 // ---- host bookkeeping.  A failed call puts the lists back: rows it already scattered sit in slots beyond their list's fill,
 // which the scan does not admit and the next append overwrites
@@ -114,7 +106,7 @@ static int ivf_scatter_rows(mi_ivfpq* h, const uint8_t* src_dev, int64_t stride,
   ivf_place(h, lists_host, rows, slots.data());
   // cannot happen while ivf_place's bound holds; a slot beyond the pool must never reach the scatter
   REQUIRE(h->pool_used <= h->pool_blocks, "internal: the block pool is exhausted");
-  if ((rc = device_grow(&h->slots, &h->slots_cap, (size_t)rows)) != MI_OK) return rc;
+  if ((rc = h->slots.grow((size_t)rows)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(h->slots, slots.data(), (size_t)rows * 8, hipMemcpyHostToDevice, h->stream));
   launch_ivf_scatter(src_dev, stride, h->m, h->slots, row0, rows, h->codes, h->rowid, h->stream);
   HIPC(hipGetLastError());
@@ -153,7 +145,7 @@ static int ivf_ingest(mi_ivfpq* h, const void* codes, const uint8_t* list_ids, i
   const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / h->m);
   std::vector<int64_t> slots;
   rc = MI_OK;
-  if (memspace == MI_HOST) rc = device_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m);
+  if (memspace == MI_HOST) rc = h->cbytes.grow((size_t)std::min(step, rows) * h->m);
   for (int64_t r = 0; r < rows && rc == MI_OK; r += step) {
     const int64_t mm = std::min(step, rows - r);
     const uint8_t* src = (const uint8_t*)codes + r * stride;
@@ -203,11 +195,11 @@ static int ivf_search_core(mi_ivfpq* h, const void* q_dev, int dtype, int64_t rs
                            : std::min<int64_t>({nq, 65535, budget / std::max<int64_t>(1, nslab * k * 8), ((int64_t)256 << 20) / (per * 4)});
   qc = std::max<int64_t>(1, qc);
   int rc;
-  if ((rc = device_grow(&h->tab, &h->tab_cap, (size_t)(qc * tabs))) != MI_OK) return rc;
-  if ((rc = device_grow(&h->praw, &h->praw_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
-  if ((rc = device_grow(&h->pnorm, &h->pnorm_cap, (size_t)(qc * nprobe))) != MI_OK) return rc;
-  if ((rc = device_grow(&h->pref, &h->pref_cap, (size_t)(qc * (nprobe + 1)))) != MI_OK) return rc;
-  if ((rc = device_grow(&h->part, &h->part_cap, (size_t)(qc * nslab * k))) != MI_OK) return rc;
+  if ((rc = h->tab.grow((size_t)(qc * tabs))) != MI_OK) return rc;
+  if ((rc = h->praw.grow((size_t)(qc * nprobe))) != MI_OK) return rc;
+  if ((rc = h->pnorm.grow((size_t)(qc * nprobe))) != MI_OK) return rc;
+  if ((rc = h->pref.grow((size_t)(qc * (nprobe + 1)))) != MI_OK) return rc;
+  if ((rc = h->part.grow((size_t)(qc * nslab * k))) != MI_OK) return rc;
   // stage_ms (mi_ivfpq_search_stages_device): HIP events around the table and the scan of every chunk, read after each chunk
   // the guard destroys them on every way out of this function
   struct StageEvents {
@@ -306,13 +298,13 @@ static int ivf_create(bool residual, const float* coarse_host, int32_t nlist, co
     return code;
   };
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = device_malloc((void**)&h->codes, codes_bytes);
-  if (e == hipSuccess) e = device_malloc((void**)&h->rowid, id_bytes);
-  if (e == hipSuccess) e = device_malloc((void**)&h->blk_table, (size_t)h->pool_blocks * 4);
-  if (e == hipSuccess) e = device_malloc((void**)&h->list_off, (2 * (size_t)nlist + 1) * 4);
-  if (e == hipSuccess) e = device_malloc((void**)&h->cb, cb_count * 4);
-  if (e == hipSuccess) e = device_malloc((void**)&h->coarse, co_count * 4);
-  if (e == hipSuccess) e = device_malloc((void**)&h->flag, 256);
+  if (e == hipSuccess) e = h->codes.alloc(codes_bytes / 4);
+  if (e == hipSuccess) e = h->rowid.alloc(id_bytes / 4);
+  if (e == hipSuccess) e = h->blk_table.alloc((size_t)h->pool_blocks);
+  if (e == hipSuccess) e = h->list_off.alloc(2 * (size_t)nlist + 1);
+  if (e == hipSuccess) e = h->cb.alloc(cb_count);
+  if (e == hipSuccess) e = h->coarse.alloc(co_count);
+  if (e == hipSuccess) e = h->flag.alloc(64);
   if (e == hipSuccess) e = hipMemsetAsync(h->codes, 0, codes_bytes, h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(h->rowid, 0xFF, id_bytes, h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(h->blk_table, 0, (size_t)h->pool_blocks * 4, h->stream);
@@ -392,7 +384,7 @@ int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t ro
     const void* xp = (const char*)x + (size_t)r * row_stride * esz;
     int64_t rs = row_stride, cs = col_stride;
     if (memspace == MI_HOST) {
-      if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+      if ((rc = stage_host_rows(h->xraw, h->d, h->stream, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
       xp = h->xraw;
       rs = h->d;
       cs = 1;
@@ -406,8 +398,8 @@ int mi_ivfpq_add(mi_ivfpq* h, const void* x, int64_t rows, int dtype, int64_t ro
     HIPC(hipStreamSynchronize(s));
     return ivf_scatter_rows(h, h->cbytes, h->m, lists.data(), mk.n + r, mm, slots);
   };
-  int rc = device_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m);
-  if (rc == MI_OK) rc = device_grow(&h->lbytes, &h->lbytes_cap, (size_t)std::min(step, rows));
+  int rc = h->cbytes.grow((size_t)std::min(step, rows) * h->m);
+  if (rc == MI_OK) rc = h->lbytes.grow((size_t)std::min(step, rows));
   for (int64_t r = 0; r < rows && rc == MI_OK; r += step) rc = block(r, std::min(step, rows - r));
   if (rc == MI_OK) rc = ivf_publish(h);
   if (rc != MI_OK) {
@@ -445,15 +437,15 @@ int mi_ivfpq_residual_rows(mi_ivfpq* h, const void* x, int64_t rows, int dtype, 
   const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * 8));
   const int64_t most = std::min(step, rows);
   int rc;
-  if ((rc = device_grow(&h->lbytes, &h->lbytes_cap, (size_t)most)) != MI_OK) return rc;
-  if (out_memspace == MI_HOST && (rc = device_grow(&h->odist, &h->odist_cap, (size_t)(most * h->d))) != MI_OK) return rc;
+  if ((rc = h->lbytes.grow((size_t)most)) != MI_OK) return rc;
+  if (out_memspace == MI_HOST && (rc = h->odist.grow((size_t)(most * h->d))) != MI_OK) return rc;
   std::vector<char> pack;
   for (int64_t r = 0; r < rows; r += step) {
     const int64_t mm = std::min(step, rows - r);
     const void* xp = (const char*)x + (size_t)r * row_stride * esz;
     int64_t rs = row_stride, cs = col_stride;
     if (memspace == MI_HOST) {
-      if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+      if ((rc = stage_host_rows(h->xraw, h->d, h->stream, x, r, mm, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
       xp = h->xraw;
       rs = h->d;
       cs = 1;
@@ -486,11 +478,11 @@ int mi_ivfpq_probe(mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t ro
   hipStream_t s = h->stream;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)h->d * (int64_t)esz));
-  if ((rc = device_grow(&h->praw, &h->praw_cap, (size_t)(std::min(step, nq) * nprobe))) != MI_OK) return rc;
+  if ((rc = h->praw.grow((size_t)(std::min(step, nq) * nprobe))) != MI_OK) return rc;
   std::vector<char> pack;
   for (int64_t q0 = 0; q0 < nq; q0 += step) {
     const int64_t b = std::min(step, nq - q0);
-    if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+    if ((rc = stage_host_rows(h->xraw, h->d, h->stream, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
     launch_ivf_probe(h->xraw, dtype, h->d, 1, b, h->coarse, h->nlist, h->d, nprobe, h->praw, s);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(out_lists_host + q0 * nprobe, h->praw, (size_t)(b * nprobe) * 4, hipMemcpyDeviceToHost, s));
@@ -526,29 +518,20 @@ int mi_ivfpq_search(mi_ivfpq* h, const void* q, int64_t nq, int dtype, int64_t r
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t cnt = (size_t)nq * k;
-  if ((rc = device_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
-  if (out_dist && (rc = device_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
-  const uint64_t* allow_dev = allow_bits;
-  if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
-    const size_t words = (size_t)((h->n + 63) / 64);
-    if ((rc = device_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
-    HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
-    allow_dev = h->bits;
-  }
+  if ((rc = h->oidx.grow(cnt)) != MI_OK) return rc;
+  if (out_dist && (rc = h->odist.grow(cnt)) != MI_OK) return rc;
+  const uint64_t* allow_dev;
+  if ((rc = allow_on_device(h->bits, allow_bits, allow_memspace, h->n, s, &allow_dev)) != MI_OK) return rc;
   if (probes_host) {
-    if ((rc = device_grow(&h->pex, &h->pex_cap, (size_t)(nq * nprobe))) != MI_OK) return rc;
+    if ((rc = h->pex.grow((size_t)(nq * nprobe))) != MI_OK) return rc;
     HIPC(hipMemcpyAsync(h->pex, probes_host, (size_t)(nq * nprobe) * 4, hipMemcpyHostToDevice, s));
   }
   std::vector<char> pack;
-  if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
-  if ((rc = ivf_search_core(h, h->xraw, dtype, h->d, 1, nq, k, nprobe, probes_host ? h->pex : nullptr, allow_dev, h->oidx,
-                            out_dist ? h->odist : nullptr, s)) != MI_OK)
+  if ((rc = stage_host_rows(h->xraw, h->d, h->stream, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+  if ((rc = ivf_search_core(h, h->xraw, dtype, h->d, 1, nq, k, nprobe, probes_host ? h->pex.get() : nullptr, allow_dev, h->oidx,
+                            out_dist ? h->odist.get() : nullptr, s)) != MI_OK)
     return rc;
-  HIPC(hipMemcpyAsync(out_idx, h->oidx, cnt * 8, hipMemcpyDeviceToHost, s));
-  if (out_dist) HIPC(hipMemcpyAsync(out_dist, h->odist, cnt * 4, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return MI_OK;
+  return topk_to_host(out_idx, h->oidx, out_dist, h->odist.get(), cnt, s, t0, out_seconds);
 }
 
 int mi_ivfpq_search_device(mi_ivfpq* h, const float* q_dev, int64_t nq, int32_t k, int32_t nprobe, const int32_t* probes_dev,
@@ -596,9 +579,7 @@ int mi_ivfpq_info(const mi_ivfpq* h, int64_t* n, int32_t* d, int32_t* m, int32_t
   if (device) *device = h->device;
   if (row_offset) *row_offset = h->row_offset;
   if (capacity) *capacity = h->cap;
-  if (hbm_bytes)
-    *hbm_bytes = h->pool_blocks * ((int64_t)h->MQ * 256 + 256 + 4) + (2 * (int64_t)h->nlist + 1) * 4 +
-                 (int64_t)(h->cb_host.size() + h->coarse_host.size()) * 4 + 256 + ivf_scratch_bytes(h);
+  if (hbm_bytes) *hbm_bytes = (int64_t)h->bufs.bytes();
   return MI_OK;
 }
 
@@ -666,8 +647,8 @@ int mi_ivfpq_remove_rows(mi_ivfpq* h, const uint64_t* remove_bits, int memspace,
   if (plan.removed == 0) return MI_OK;                        // nothing changes
   const int64_t m = n - plan.removed;                         // n'
   const int64_t nwords = (n + 63) / 64;
-  if ((rc = device_grow(&h->bits, &h->bits_cap, (size_t)nwords)) != MI_OK) return rc;
-  if ((rc = device_grow(&h->rmpref, &h->rmpref_cap, (size_t)nwords + 1)) != MI_OK) return rc;
+  if ((rc = h->bits.grow((size_t)nwords)) != MI_OK) return rc;
+  if ((rc = h->rmpref.grow((size_t)nwords + 1)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(h->bits, plan.keep.data(), (size_t)nwords * 8, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpyAsync(h->rmpref, plan.prefix.data(), ((size_t)nwords + 1) * 4, hipMemcpyHostToDevice, s));
   // the tables on the device are those of the last publish: the chains and fills before the removal
@@ -702,10 +683,7 @@ int mi_ivfpq_destroy(mi_ivfpq* h) {
   if (!h) return MI_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->codes, (void*)h->rowid, (void*)h->blk_table, (void*)h->list_off, (void*)h->cb, (void*)h->coarse, (void*)h->flag,
-                  (void*)h->xraw, (void*)h->cbytes, (void*)h->lbytes, (void*)h->slots, (void*)h->tab, (void*)h->praw, (void*)h->pnorm,
-                  (void*)h->pref, (void*)h->pex, (void*)h->part, (void*)h->bits, (void*)h->rmpref, (void*)h->oidx, (void*)h->odist})
-    (void)hipFree(p);
+  h->bufs.reset();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return MI_OK;

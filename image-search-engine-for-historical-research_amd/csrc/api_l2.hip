@@ -5,26 +5,6 @@
 // then takes the distances of those K rows in the direct form and orders them.
 #include "api_internal.h"
 
-void l2_scratch_free(mi_gallery* g) {
-  auto& l = g->l2;
-  for (void* p : {l.qraw, (void*)l.qaug, (void*)l.ids, (void*)l.oidx, (void*)l.odist, (void*)l.odist64}) (void)hipFree(p);
-  l = mi_gallery::L2Scratch{};
-}
-
-static int l2_grow_out(mi_gallery* g, size_t count) {
-  auto& l = g->l2;
-  if (l.oidx && l.odist && l.odist64 && l.out_cap >= count) return MI_OK;
-  size_t a = 0, b = 0, c = 0;
-  for (void* p : {(void*)l.oidx, (void*)l.odist, (void*)l.odist64}) (void)hipFree(p);
-  l.oidx = nullptr, l.odist = nullptr, l.odist64 = nullptr, l.out_cap = 0;
-  int rc;
-  if ((rc = device_grow(&l.oidx, &a, count)) != MI_OK || (rc = device_grow(&l.odist, &b, count)) != MI_OK ||
-      (rc = device_grow(&l.odist64, &c, count)) != MI_OK)
-    return rc;
-  l.out_cap = std::min({a, b, c});
-  return MI_OK;
-}
-
 #define REQUIRE_L2(g) REQUIRE((g)->metric == MI_METRIC_L2, "not a squared-L2 gallery (mi_gallery_create_l2)")
 
 // host results of a call: [nq][k] from the handle's output buffers, after the work on `s`
@@ -44,13 +24,8 @@ static int l2_stage_queries(mi_gallery* g, const void* q, int64_t nq, int dtype,
   int rc = strided_extent(nq, g->ud, rs, cs, &elems);
   if (rc != MI_OK) return rc;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
-  char* raw = (char*)g->l2.qraw;
-  if ((rc = device_grow(&raw, &g->l2.qraw_cap, (size_t)elems * esz)) != MI_OK) {
-    g->l2.qraw = raw;
-    return rc;
-  }
-  g->l2.qraw = raw;
-  if ((rc = device_grow(&g->l2.qaug, &g->l2.qaug_cap, (size_t)nq * g->dp)) != MI_OK) return rc;
+  if ((rc = g->l2.qraw.grow((size_t)elems * esz)) != MI_OK) return rc;
+  if ((rc = g->l2.qaug.grow((size_t)nq * g->dp)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(g->l2.qraw, q, (size_t)elems * esz, hipMemcpyHostToDevice, g->stream));
   launch_l2_augment(g->l2.qraw, dtype, nq, g->ud, rs, cs, g->l2.qaug, g->dp, g->stream);
   HIPC(hipGetLastError());
@@ -116,13 +91,13 @@ int mi_knn_search_l2(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_
   int32_t ke = (int32_t)std::min<int64_t>(k, g->n);
   if (allow_bits && g->n >= 1) {
     ke = k;
-    if ((rc = device_grow(&g->l2.ids, &g->l2.ids_cap, (size_t)nq * ke)) != MI_OK) return rc;
+    if ((rc = g->l2.ids.grow((size_t)nq * ke)) != MI_OK) return rc;
     HIPC(hipMemcpyAsync(g->l2.ids, sel.data(), (size_t)nq * ke * 8, hipMemcpyHostToDevice, s));
   } else if (ke >= 1) {
-    if ((rc = device_grow(&g->l2.ids, &g->l2.ids_cap, (size_t)nq * ke)) != MI_OK) return rc;
+    if ((rc = g->l2.ids.grow((size_t)nq * ke)) != MI_OK) return rc;
     if ((rc = search_sync(g, g->l2.qaug, MI_F32, g->dp, 1, MI_NORM_NONE, nq, ke, g->l2.ids, nullptr, nullptr)) != MI_OK) return rc;
   }
-  if ((rc = l2_grow_out(g, (size_t)nq * k)) != MI_OK) return rc;
+  if ((rc = grow_all((size_t)nq * k, g->l2.oidx, g->l2.odist, g->l2.odist64)) != MI_OK) return rc;
   launch_l2_tail(g->gal_f32, g->l2.qaug, g->dp, ud, g->n, g->row_offset, g->l2.ids, ke, k, nq, g->l2.oidx, g->l2.odist,
                  g->l2.odist64, s);
   if ((rc = l2_copy_out(g, nq, k, out_idx, out_dist, out_dist64, s)) != MI_OK) return rc;
@@ -141,8 +116,8 @@ int mi_knn_search_l2_device(mi_gallery* g, const float* q_dev, int64_t nq, int32
   hipStream_t s = (hipStream_t)stream;
   const int32_t ke = (int32_t)std::min<int64_t>(k, g->n);
   int rc;
-  if ((rc = device_grow(&g->l2.qaug, &g->l2.qaug_cap, (size_t)nq * g->dp)) != MI_OK) return rc;
-  if ((rc = device_grow(&g->l2.ids, &g->l2.ids_cap, (size_t)nq * std::max<int32_t>(ke, 1))) != MI_OK) return rc;
+  if ((rc = g->l2.qaug.grow((size_t)nq * g->dp)) != MI_OK) return rc;
+  if ((rc = g->l2.ids.grow((size_t)nq * std::max<int32_t>(ke, 1))) != MI_OK) return rc;
   launch_l2_augment(q_dev, MI_F32, nq, g->ud, g->ud, 1, g->l2.qaug, g->dp, s);
   if (ke >= 1 && (rc = search_device(g, g->l2.qaug, MI_F32, g->dp, 1, MI_NORM_NONE, nq, ke, g->l2.ids, nullptr, nullptr,
                                      g->force_exact != 0, s, /*allow_async=*/false, /*caller_checks_flags=*/false)) != MI_OK)
@@ -168,7 +143,7 @@ int mi_knn_dense64_search_l2(mi_gallery* g, const void* q, int64_t nq, int dtype
   int rc;
   if ((rc = join_tails(g, s)) != MI_OK) return rc;
   if ((rc = l2_stage_queries(g, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
-  if ((rc = l2_grow_out(g, (size_t)nq * k)) != MI_OK) return rc;
+  if ((rc = grow_all((size_t)nq * k, g->l2.oidx, g->l2.odist, g->l2.odist64)) != MI_OK) return rc;
   const int32_t ke = (int32_t)std::min<int64_t>(k, g->n);
   TmpAlloc tmp;
   if (ke >= 1) {

@@ -10,36 +10,23 @@ struct mi_pq {
   int64_t n = 0, cap = 0, row_offset = 0;
   int32_t d = 0, m = 0, ks = 0, L = 0, MQ = 0;     // columns, books, codewords per book, columns per book, dwords of a code
   std::vector<float> cb_host;                      // [m][ks][L]
-  float* cb = nullptr;
-  uint32_t* codes = nullptr;                       // [ceil(cap / 64)][MQ][64]
-  size_t codes_bytes = 0;
-  uint32_t* flag = nullptr;                        // raised by the check of device-resident codes
+  DeviceBufSet bufs;                               // every device allocation of the handle: hbm_bytes is bufs.bytes()
+  DeviceBuf<float> cb{bufs};                       // (cb, codes, flag: exactly their size, allocated at creation)
+  DeviceBuf<uint32_t> codes{bufs};                 // [ceil(cap / 64)][MQ][64]
+  DeviceBuf<uint32_t> flag{bufs};                  // raised by the check of device-resident codes (256 bytes)
   hipStream_t stream = nullptr;
-  char* xraw = nullptr;                            // rows / queries of a host call, packed [rows][d] in their own type
-  size_t xraw_cap = 0;
-  uint8_t* cbytes = nullptr;                       // packed code bytes [rows][m]: host codes on their way in, encoder output
-  size_t cbytes_cap = 0;
-  float* tab = nullptr;                            // distance tables [queries of a chunk][m][ks]
-  size_t tab_cap = 0;
-  float* mat = nullptr;                            // negated distances [queries of a chunk][round_up(n, 64)]
-  size_t mat_cap = 0;
-  int64_t* tidx = nullptr;                         // [queries of a chunk][ke] what the selection returns
-  float* tneg = nullptr;
-  size_t tidx_cap = 0, tneg_cap = 0;
-  uint64_t* bits = nullptr;                        // device copy of a host bitmap
-  size_t bits_cap = 0;
-  int64_t* oidx = nullptr;                         // results of a host call
-  float* odist = nullptr;
-  size_t oidx_cap = 0, odist_cap = 0;
-  uint32_t *rmpref = nullptr, *rmstage = nullptr;  // mi_pq_remove_rows: prefix counts per bitmap word; staging blocks [..][MQ][64]
-  size_t rmpref_cap = 0, rmstage_cap = 0;
+  DeviceBuf<char> xraw{bufs};                      // rows / queries of a host call, packed [rows][d] in their own type
+  DeviceBuf<uint8_t> cbytes{bufs};                 // packed code bytes [rows][m]: host codes on their way in, encoder output
+  DeviceBuf<float> tab{bufs};                      // distance tables [queries of a chunk][m][ks]
+  DeviceBuf<float> mat{bufs};                      // negated distances [queries of a chunk][round_up(n, 64)]
+  DeviceBuf<int64_t> tidx{bufs};                   // [queries of a chunk][ke] what the selection returns
+  DeviceBuf<float> tneg{bufs};
+  DeviceBuf<uint64_t> bits{bufs};                  // device copy of a host bitmap
+  DeviceBuf<int64_t> oidx{bufs};                   // results of a host call
+  DeviceBuf<float> odist{bufs};
+  DeviceBuf<uint32_t> rmpref{bufs}, rmstage{bufs}; // mi_pq_remove_rows: prefix counts per bitmap word; staging blocks [..][MQ][64]
   std::mutex mu;
 };
-
-static int64_t pq_scratch_bytes(const mi_pq* h) {
-  return (int64_t)(h->xraw_cap + h->cbytes_cap + h->tab_cap * 4 + h->mat_cap * 4 + h->tidx_cap * 8 + h->tneg_cap * 4 + h->bits_cap * 8 +
-                   h->oidx_cap * 8 + h->odist_cap * 4 + h->rmpref_cap * 4 + h->rmstage_cap * 4);
-}
 
 // rows of code bytes (host: checked by the caller; device: checked here) -> rows n .. n + rows of the index, synchronous on the
 // handle's stream.  A device code byte >= ks: MI_ERR_INVALID, nothing written.
@@ -65,7 +52,7 @@ static int pq_ingest(mi_pq* h, const void* codes, int64_t rows, int64_t stride, 
   }
   const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / h->m);
   int rc;
-  if ((rc = device_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
+  if ((rc = h->cbytes.grow((size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
   for (int64_t r = 0; r < rows; r += step) {
     const int64_t mm = std::min(step, rows - r);
     const uint8_t* src = (const uint8_t*)codes + r * stride;
@@ -86,12 +73,12 @@ static int pq_encode_blocks(mi_pq* h, const void* x, int64_t rows, int dtype, in
   const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * (int64_t)esz));
   hipStream_t s = h->stream;
   int rc;
-  if ((rc = device_grow(&h->cbytes, &h->cbytes_cap, (size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
+  if ((rc = h->cbytes.grow((size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
   std::vector<char> pack;
   for (int64_t r = 0; r < rows; r += step) {
     const int64_t mm = std::min(step, rows - r);
     if (memspace == MI_HOST) {
-      if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, x, r, mm, dtype, rs, cs, pack)) != MI_OK) return rc;
+      if ((rc = stage_host_rows(h->xraw, h->d, h->stream, x, r, mm, dtype, rs, cs, pack)) != MI_OK) return rc;
       launch_pq_encode(h->xraw, dtype, h->d, 1, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
     } else {
       launch_pq_encode((const char*)x + (size_t)r * rs * esz, dtype, rs, cs, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
@@ -120,10 +107,10 @@ static int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, in
   const int32_t ke = (int32_t)std::min<int64_t>(k, npad);
   const int64_t per = (int64_t)h->m * h->ks;
   int rc;
-  if ((rc = device_grow(&h->tab, &h->tab_cap, (size_t)(qc * per))) != MI_OK) return rc;
-  if ((rc = device_grow(&h->mat, &h->mat_cap, (size_t)(qc * npad))) != MI_OK) return rc;
-  if ((rc = device_grow(&h->tidx, &h->tidx_cap, (size_t)(qc * ke))) != MI_OK) return rc;
-  if ((rc = device_grow(&h->tneg, &h->tneg_cap, (size_t)(qc * ke))) != MI_OK) return rc;
+  if ((rc = h->tab.grow((size_t)(qc * per))) != MI_OK) return rc;
+  if ((rc = h->mat.grow((size_t)(qc * npad))) != MI_OK) return rc;
+  if ((rc = h->tidx.grow((size_t)(qc * ke))) != MI_OK) return rc;
+  if ((rc = h->tneg.grow((size_t)(qc * ke))) != MI_OK) return rc;
   for (int64_t q0 = 0; q0 < nq; q0 += qc) {
     const int32_t b = (int32_t)std::min<int64_t>(qc, nq - q0);
     launch_pq_table((const char*)q_dev + (size_t)q0 * rs * esz, dtype, rs, cs, b, h->cb, h->m, h->ks, h->L, h->tab, s);
@@ -190,16 +177,16 @@ int mi_pq_create(const float* codebooks_host, int32_t d, int32_t m, int32_t ks, 
   h->L = d / m;
   h->MQ = (m + 3) / 4;
   h->cb_host.assign(codebooks_host, codebooks_host + cb_count);
-  h->codes_bytes = (size_t)((capacity + 63) / 64) * h->MQ * 64 * 4;
+  const size_t codes_words = (size_t)((capacity + 63) / 64) * h->MQ * 64;
   auto cleanup = [&](int code) {
     mi_pq_destroy(h);
     return code;
   };
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = device_malloc((void**)&h->codes, h->codes_bytes);
-  if (e == hipSuccess) e = device_malloc((void**)&h->cb, cb_count * 4);
-  if (e == hipSuccess) e = device_malloc((void**)&h->flag, 256);
-  if (e == hipSuccess) e = hipMemsetAsync(h->codes, 0, h->codes_bytes, h->stream);
+  if (e == hipSuccess) e = h->codes.alloc(codes_words);
+  if (e == hipSuccess) e = h->cb.alloc(cb_count);
+  if (e == hipSuccess) e = h->flag.alloc(64);
+  if (e == hipSuccess) e = hipMemsetAsync(h->codes, 0, codes_words * 4, h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(h->flag, 0, 256, h->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(h->cb, h->cb_host.data(), cb_count * 4, hipMemcpyHostToDevice, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
@@ -278,11 +265,11 @@ int mi_pq_dtable(mi_pq* h, const void* q, int64_t nq, int dtype, int64_t row_str
   hipStream_t s = h->stream;
   const int64_t per = (int64_t)h->m * h->ks;
   const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / (per * 4));
-  if ((rc = device_grow(&h->tab, &h->tab_cap, (size_t)(std::min(step, nq) * per))) != MI_OK) return rc;
+  if ((rc = h->tab.grow((size_t)(std::min(step, nq) * per))) != MI_OK) return rc;
   std::vector<char> pack;
   for (int64_t q0 = 0; q0 < nq; q0 += step) {
     const int64_t b = std::min(step, nq - q0);
-    if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+    if ((rc = stage_host_rows(h->xraw, h->d, h->stream, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
     launch_pq_table(h->xraw, dtype, h->d, 1, b, h->cb, h->m, h->ks, h->L, h->tab, s);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(out_table_host + q0 * per, h->tab, (size_t)(b * per) * 4, hipMemcpyDeviceToHost, s));
@@ -308,23 +295,14 @@ int mi_pq_search(mi_pq* h, const void* q, int64_t nq, int dtype, int64_t row_str
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
   const size_t cnt = (size_t)nq * k;
-  if ((rc = device_grow(&h->oidx, &h->oidx_cap, cnt)) != MI_OK) return rc;
-  if (out_dist && (rc = device_grow(&h->odist, &h->odist_cap, cnt)) != MI_OK) return rc;
-  const uint64_t* allow_dev = allow_bits;
-  if (allow_bits && allow_memspace == MI_HOST && h->n > 0) {
-    const size_t words = (size_t)((h->n + 63) / 64);
-    if ((rc = device_grow(&h->bits, &h->bits_cap, words)) != MI_OK) return rc;
-    HIPC(hipMemcpyAsync(h->bits, allow_bits, words * 8, hipMemcpyHostToDevice, s));
-    allow_dev = h->bits;
-  }
+  if ((rc = h->oidx.grow(cnt)) != MI_OK) return rc;
+  if (out_dist && (rc = h->odist.grow(cnt)) != MI_OK) return rc;
+  const uint64_t* allow_dev;
+  if ((rc = allow_on_device(h->bits, allow_bits, allow_memspace, h->n, s, &allow_dev)) != MI_OK) return rc;
   std::vector<char> pack;
-  if ((rc = stage_host_rows(&h->xraw, &h->xraw_cap, h->d, h->stream, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
-  if ((rc = pq_search_core(h, h->xraw, dtype, h->d, 1, nq, k, allow_dev, h->oidx, out_dist ? h->odist : nullptr, s)) != MI_OK) return rc;
-  HIPC(hipMemcpyAsync(out_idx, h->oidx, cnt * 8, hipMemcpyDeviceToHost, s));
-  if (out_dist) HIPC(hipMemcpyAsync(out_dist, h->odist, cnt * 4, hipMemcpyDeviceToHost, s));
-  HIPC(hipStreamSynchronize(s));
-  if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  return MI_OK;
+  if ((rc = stage_host_rows(h->xraw, h->d, h->stream, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
+  if ((rc = pq_search_core(h, h->xraw, dtype, h->d, 1, nq, k, allow_dev, h->oidx, out_dist ? h->odist.get() : nullptr, s)) != MI_OK) return rc;
+  return topk_to_host(out_idx, h->oidx, out_dist, h->odist.get(), cnt, s, t0, out_seconds);
 }
 
 int mi_pq_search_device(mi_pq* h, const float* q_dev, int64_t nq, int32_t k, const uint64_t* allow_bits_dev, int64_t* out_idx_dev,
@@ -348,7 +326,7 @@ int mi_pq_info(const mi_pq* h, int64_t* n, int32_t* d, int32_t* m, int32_t* ks, 
   if (device) *device = h->device;
   if (row_offset) *row_offset = h->row_offset;
   if (capacity) *capacity = h->cap;
-  if (hbm_bytes) *hbm_bytes = (int64_t)h->codes_bytes + (int64_t)h->cb_host.size() * 4 + 256 + pq_scratch_bytes(h);
+  if (hbm_bytes) *hbm_bytes = (int64_t)h->bufs.bytes();
   return MI_OK;
 }
 
@@ -412,10 +390,10 @@ int mi_pq_remove_rows(mi_pq* h, const uint64_t* remove_bits, int memspace, int64
     const int64_t blk_words = (int64_t)h->MQ * 64;
     const int64_t start = plan.first / 64;                    // the blocks before the first row that leaves stay as they are
     const int64_t B = std::min<int64_t>(g_pq_remove_block_rows.load(), (nwords - start) * 64) / 64;   // source blocks per chunk
-    if ((rc = device_grow(&h->bits, &h->bits_cap, (size_t)nwords)) != MI_OK) return rc;
-    if ((rc = device_grow(&h->rmpref, &h->rmpref_cap, (size_t)nwords + 1)) != MI_OK) return rc;
+    if ((rc = h->bits.grow((size_t)nwords)) != MI_OK) return rc;
+    if ((rc = h->rmpref.grow((size_t)nwords + 1)) != MI_OK) return rc;
     // a chunk's first survivor may sit in any lane of its destination block: one block more than the chunk's rows fill
-    if ((rc = device_grow(&h->rmstage, &h->rmstage_cap, (size_t)((B + 1) * blk_words))) != MI_OK) return rc;
+    if ((rc = h->rmstage.grow((size_t)((B + 1) * blk_words))) != MI_OK) return rc;
     HIPC(hipMemcpyAsync(h->bits, plan.keep.data(), (size_t)nwords * 8, hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(h->rmpref, plan.prefix.data(), ((size_t)nwords + 1) * 4, hipMemcpyHostToDevice, s));
     for (int64_t b0 = start; b0 < nwords; b0 += B) {
@@ -438,9 +416,7 @@ int mi_pq_destroy(mi_pq* h) {
   if (!h) return MI_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  for (void* p : {(void*)h->codes, (void*)h->cb, (void*)h->flag, (void*)h->xraw, (void*)h->cbytes, (void*)h->tab, (void*)h->mat,
-                  (void*)h->tidx, (void*)h->tneg, (void*)h->bits, (void*)h->oidx, (void*)h->odist, (void*)h->rmpref, (void*)h->rmstage})
-    (void)hipFree(p);
+  h->bufs.reset();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return MI_OK;

@@ -7,58 +7,16 @@
 // by (score desc, row asc) on the device and copied out once per batch.
 #include "api_internal.h"
 
-void range_scratch_free(mi_gallery* g) {
-  auto& r = g->range;
-  for (void* p : {(void*)r.rows, (void*)r.rcnt, (void*)r.sc, (void*)r.akey, (void*)r.arow, (void*)r.bkey[0], (void*)r.bkey[1],
-                  (void*)r.brow[0], (void*)r.brow[1], (void*)r.coff, (void*)r.ccnt, (void*)r.lims, (void*)r.total})
-    (void)hipFree(p);
-  r = mi_gallery::RangeScratch{};
-}
-
-// two grow-only device buffers of `count` elements each, one capacity; the first `keep` elements survive a reallocation
-template <typename T>
-static int regrow(T** p, size_t want, size_t keep) {
-  void* q = nullptr;
-  HIPC(device_malloc(&q, want * sizeof(T)));
-  if (keep && *p) {
-    const hipError_t e = hipMemcpy(q, *p, keep * sizeof(T), hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(q);
-      return fail(MI_ERR_HIP, std::string("range buffer copy: ") + hipGetErrorString(e));
-    }
-  }
-  (void)hipFree(*p);
-  *p = reinterpret_cast<T*>(q);
-  return MI_OK;
-}
-template <typename A, typename B>
-static int grow_pair(A** a, B** b, size_t* cap, size_t count, size_t keep = 0) {
-  if (*cap >= count && *a && *b) return MI_OK;
-  const size_t want = grow_capacity(count);
-  int rc;
-  if ((rc = regrow(a, want, keep)) != MI_OK || (rc = regrow(b, want, keep)) != MI_OK) {
-    *cap = 0;
-    return rc;
-  }
-  *cap = want;
-  return MI_OK;
-}
-
+// the buffers the exact re-score fills, exactly [QB][the workspace's survivor rows]: sized again when that number changes
 static int range_scratch_ensure(mi_gallery* g) {
   auto& r = g->range;
-  if (r.lcap != g->ws.cap || !r.rows) {
-    (void)hipFree(r.rows);
-    (void)hipFree(r.rcnt);
-    (void)hipFree(r.sc);
-    r.rows = nullptr, r.rcnt = nullptr, r.sc = nullptr, r.lcap = 0;
-    HIPC(device_malloc((void**)&r.rows, (size_t)QB * g->ws.cap * sizeof(uint32_t)));
-    HIPC(device_malloc((void**)&r.rcnt, (size_t)QB * sizeof(uint32_t)));
-    HIPC(device_malloc((void**)&r.sc, (size_t)QB * g->ws.cap * sizeof(double)));
-    r.lcap = g->ws.cap;
-  }
-  if (!r.lims) HIPC(device_malloc((void**)&r.lims, (size_t)(QB + 1) * sizeof(int64_t)));
-  if (!r.total) HIPC(device_malloc((void**)&r.total, sizeof(unsigned long long)));
-  return MI_OK;
+  const size_t lists = (size_t)QB * g->ws.cap;
+  if (r.rows.count() != lists) r.rows.reset(), r.rcnt.reset(), r.sc.reset();
+  int rc;
+  if ((rc = r.rows.grow_exact(lists)) != MI_OK || (rc = r.rcnt.grow_exact(QB)) != MI_OK || (rc = r.sc.grow_exact(lists)) != MI_OK)
+    return rc;
+  if ((rc = r.lims.grow_exact(QB + 1)) != MI_OK) return rc;
+  return r.total.grow_exact(1);
 }
 
 // one batch (nb <= QB queries): scoring chunks, re-score, kept hits; then lims (host, batch-relative) and the
@@ -93,8 +51,10 @@ static int range_batch(mi_gallery* g, const void* src, int dtype, int64_t rs, in
     const int64_t row0 = t * TILE, row1 = std::min<int64_t>(g->n, (t + cur) * TILE);
     int rc;
     // room for every row this chunk can keep, and for its counts / offsets
-    if ((rc = grow_pair(&r.akey, &r.arow, &r.acap, (size_t)base + (size_t)nb * ws.cap, (size_t)base)) != MI_OK) return rc;
-    if ((rc = grow_pair(&r.coff, &r.ccnt, &r.ccap, (size_t)(nchunks + 1) * QB, (size_t)nchunks * QB)) != MI_OK) return rc;
+    const size_t hits_room = (size_t)base + (size_t)nb * ws.cap;
+    if ((rc = r.akey.grow_keep(hits_room, (size_t)base)) != MI_OK || (rc = r.arow.grow_keep(hits_room, (size_t)base)) != MI_OK) return rc;
+    if ((rc = r.coff.grow_keep((size_t)(nchunks + 1) * QB, (size_t)nchunks * QB)) != MI_OK) return rc;
+    if ((rc = r.ccnt.grow_keep((size_t)(nchunks + 1) * QB, (size_t)nchunks * QB)) != MI_OK) return rc;
     launch_range_chunk_begin(st, qpad, r.total, s);
     if (dense) {
       launch_range_rows(st, nb, r.rows, r.rcnt, 1, (uint32_t)row0, (uint32_t)(row1 - row0), s);
@@ -135,9 +95,9 @@ static int range_batch(mi_gallery* g, const void* src, int dtype, int64_t rs, in
       }
       launch_range_rows(st, nb, r.rows, r.rcnt, 0, 0u, 0u, s);
     }
-    launch_rescore(g->gal_f32, ws.q_f32, g->dp, nb, r.rows, r.rcnt, r.lcap, r.sc, s, (uint32_t)g->rescore_grid_x, last_row);
-    launch_range_keep(r.rows, r.rcnt, r.sc, r.lcap, nb, min_score, r.total, r.coff + (size_t)nchunks * QB,
-                      r.ccnt + (size_t)nchunks * QB, r.akey, r.arow, (uint64_t)base, (uint64_t)r.acap, ws.flags, s);
+    launch_rescore(g->gal_f32, ws.q_f32, g->dp, nb, r.rows, r.rcnt, ws.cap, r.sc, s, (uint32_t)g->rescore_grid_x, last_row);
+    launch_range_keep(r.rows, r.rcnt, r.sc, ws.cap, nb, min_score, r.total, r.coff + (size_t)nchunks * QB,
+                      r.ccnt + (size_t)nchunks * QB, r.akey, r.arow, (uint64_t)base, (uint64_t)r.akey.count(), ws.flags, s);
     HIPC(hipGetLastError());
     uint32_t flags = 0;
     unsigned long long hits = 0;
@@ -177,14 +137,8 @@ static int range_batch(mi_gallery* g, const void* src, int dtype, int64_t rs, in
   if (total == 0 || total > room) return MI_OK;       // nothing to order, or it would not fit the caller's arrays
   int64_t max_cnt = 0;
   for (int32_t q = 0; q < nb; ++q) max_cnt = std::max(max_cnt, lims_h[q + 1] - lims_h[q]);
-  if (r.bcap < (size_t)total) {
-    size_t c = r.bcap;
-    int rc;
-    if ((rc = grow_pair(&r.bkey[0], &r.brow[0], &c, (size_t)total)) != MI_OK) return rc;
-    c = r.bcap;
-    if ((rc = grow_pair(&r.bkey[1], &r.brow[1], &c, (size_t)total)) != MI_OK) return rc;
-    r.bcap = c;
-  }
+  int rc;
+  if ((rc = grow_all((size_t)total, r.bkey[0], r.brow[0], r.bkey[1], r.brow[1])) != MI_OK) return rc;
   launch_range_gather(r.akey, r.arow, r.coff, r.ccnt, (int32_t)nchunks, QB, nb, r.lims, r.bkey[0], r.brow[0], s);
   launch_range_sort_runs(r.bkey[0], r.brow[0], r.lims, nb, max_cnt, s);
   int cur = 0;
@@ -193,8 +147,8 @@ static int range_batch(mi_gallery* g, const void* src, int dtype, int64_t rs, in
     cur ^= 1;
   }
   // the emit staging: the other ping-pong buffer holds total * 12 bytes, enough for the int64 ids (8) + f32 scores (4)
-  int64_t* idx_d = reinterpret_cast<int64_t*>(r.bkey[cur ^ 1]);
-  float* sc_d = reinterpret_cast<float*>(r.brow[cur ^ 1]);
+  int64_t* idx_d = reinterpret_cast<int64_t*>(r.bkey[cur ^ 1].get());
+  float* sc_d = reinterpret_cast<float*>(r.brow[cur ^ 1].get());
   launch_range_emit(r.bkey[cur], r.brow[cur], total, g->row_offset, idx_d, sc_d, s);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(s));      // the handle's stream does not block: the caller's hipMemcpy would not wait for it
@@ -252,15 +206,8 @@ int mi_range_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t
   };
   // queries: the host staging of mi_knn_search (grow-only slot 0)
   const size_t qbytes = (size_t)elems * esz;
-  if (g->io_cap[0] < qbytes) {
-    (void)hipFree(g->io_buf[0]);
-    g->io_buf[0] = nullptr;
-    g->io_cap[0] = 0;
-    const size_t want = qbytes + qbytes / 4 + 256;
-    if (device_malloc(&g->io_buf[0], want) != hipSuccess) return done(fail(MI_ERR_NOMEM, "staging buffer of mi_range_search"));
-    g->io_cap[0] = want;
-  }
-  if (hipMemcpy(g->io_buf[0], q, qbytes, hipMemcpyHostToDevice) != hipSuccess)
+  if (!io_stage(g->io_q, qbytes)) return done(fail(MI_ERR_NOMEM, "staging buffer of mi_range_search"));
+  if (hipMemcpy(g->io_q, q, qbytes, hipMemcpyHostToDevice) != hipSuccess)
     return done(fail(MI_ERR_HIP, "H2D query copy failed"));
   // more than one batch: the hits are held on the host until the total is known (nothing reaches out_idx / out_score unless
   // all of them fit); one batch: straight into the caller's arrays
@@ -271,7 +218,7 @@ int mi_range_search(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t
   int64_t cum = 0;
   for (int64_t q0 = 0; q0 < nq; q0 += QB) {
     const int32_t b = (int32_t)std::min<int64_t>(QB, nq - q0);
-    const char* src = (const char*)g->io_buf[0] + (size_t)q0 * row_stride * esz;
+    const char* src = g->io_q.get() + (size_t)q0 * row_stride * esz;
     bool exact = g->force_exact != 0, overflowed = false;
     const int64_t room = std::max<int64_t>(0, max_results - cum);   // past the capacity, later batches are only counted
     int64_t* idx_d = nullptr;

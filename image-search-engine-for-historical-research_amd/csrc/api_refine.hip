@@ -4,26 +4,6 @@
 // on any other.  Kernels in refine.hip: one gather launch over (slab of candidates, query), one sort workgroup per query.
 #include "api_internal.h"
 
-void refine_scratch_free(mi_gallery* g) {
-  auto& r = g->refine;
-  for (void* p : {r.qraw, (void*)r.qpad, (void*)r.val, (void*)r.cand, (void*)r.oidx, (void*)r.oval, (void*)r.oval64}) (void)hipFree(p);
-  r = mi_gallery::RefineScratch{};
-}
-
-static int refine_grow_out(mi_gallery* g, size_t count) {
-  auto& r = g->refine;
-  if (r.oidx && r.oval && r.oval64 && r.out_cap >= count) return MI_OK;
-  size_t a = 0, b = 0, c = 0;
-  for (void* p : {(void*)r.oidx, (void*)r.oval, (void*)r.oval64}) (void)hipFree(p);
-  r.oidx = nullptr, r.oval = nullptr, r.oval64 = nullptr, r.out_cap = 0;
-  int rc;
-  if ((rc = device_grow(&r.oidx, &a, count)) != MI_OK || (rc = device_grow(&r.oval, &b, count)) != MI_OK ||
-      (rc = device_grow(&r.oval64, &c, count)) != MI_OK)
-    return rc;
-  r.out_cap = std::min({a, b, c});
-  return MI_OK;
-}
-
 // the argument checks both forms share: they answer before the handle is read
 static int refine_check(const mi_gallery* g, int64_t nq, int32_t kc, int64_t cand_stride, int32_t k) {
   REQUIRE(g, "null handle");
@@ -40,8 +20,8 @@ static int refine_enqueue(mi_gallery* g, const void* src, int dtype, int64_t rs,
                           hipStream_t s) {
   auto& r = g->refine;
   int rc;
-  if ((rc = device_grow(&r.qpad, &r.qpad_cap, (size_t)nq * g->dp)) != MI_OK) return rc;
-  if ((rc = device_grow(&r.val, &r.val_cap, (size_t)nq * kc)) != MI_OK) return rc;
+  if ((rc = r.qpad.grow((size_t)nq * g->dp)) != MI_OK) return rc;
+  if ((rc = r.val.grow((size_t)nq * kc)) != MI_OK) return rc;
   // rows of stride dp, the caller's ud columns (what follows them is never read: both wave sums stop at ud)
   launch_l2_augment(src, dtype, nq, g->ud, rs, cs, r.qpad, g->dp, s);
   launch_refine(g->gal_f32, r.qpad, g->dp, g->ud, g->n, g->row_offset, g->metric == MI_METRIC_L2 ? 1 : 0, cand_dev, kc, cand_stride,
@@ -84,12 +64,9 @@ int mi_refine(mi_gallery* rows, const void* q, int64_t nq, int dtype, int64_t ro
   int64_t elems;
   if ((rc = strided_extent(nq, g->ud, row_stride, col_stride, &elems)) != MI_OK) return rc;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
-  char* raw = (char*)r.qraw;
-  rc = device_grow(&raw, &r.qraw_cap, (size_t)elems * esz);
-  r.qraw = raw;
-  if (rc != MI_OK) return rc;
-  if ((rc = device_grow(&r.cand, &r.cand_cap, (size_t)nq * kc)) != MI_OK) return rc;
-  if ((rc = refine_grow_out(g, (size_t)nq * k)) != MI_OK) return rc;
+  if ((rc = r.qraw.grow((size_t)elems * esz)) != MI_OK) return rc;
+  if ((rc = r.cand.grow((size_t)nq * kc)) != MI_OK) return rc;
+  if ((rc = grow_all((size_t)nq * k, r.oidx, r.oval, r.oval64)) != MI_OK) return rc;
   HIPC(hipMemcpyAsync(r.qraw, q, (size_t)elems * esz, hipMemcpyHostToDevice, s));
   HIPC(hipMemcpy2DAsync(r.cand, (size_t)kc * 8, cand, (size_t)cand_stride * 8, (size_t)kc * 8, (size_t)nq, hipMemcpyHostToDevice, s));
   if ((rc = refine_enqueue(g, r.qraw, dtype, row_stride, col_stride, nq, r.cand, kc, kc, k, r.oidx, r.oval, r.oval64, s)) != MI_OK)
@@ -112,7 +89,7 @@ int mi_debug_l2_tail_device(mi_gallery* g, const float* q_dev, int64_t nq, const
   REQUIRE(g->metric == MI_METRIC_L2, "not a squared-L2 gallery (mi_gallery_create_l2)");
   HIPC(hipSetDevice(g->device));
   int rc;
-  if ((rc = device_grow(&g->refine.qpad, &g->refine.qpad_cap, (size_t)nq * g->dp)) != MI_OK) return rc;
+  if ((rc = g->refine.qpad.grow((size_t)nq * g->dp)) != MI_OK) return rc;
   launch_l2_augment(q_dev, MI_F32, nq, g->ud, g->ud, 1, g->refine.qpad, g->dp, (hipStream_t)stream);
   launch_l2_tail(g->gal_f32, g->refine.qpad, g->dp, g->ud, g->n, g->row_offset, ids_dev, ke, k, nq, out_idx_dev, nullptr,
                  out_dist64_dev, (hipStream_t)stream);

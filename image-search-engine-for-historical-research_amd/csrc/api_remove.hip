@@ -7,11 +7,6 @@
 
 constexpr int64_t REMOVE_BLOCK_ROWS_DEFAULT = 32768;     // 403 MB of staging at D = 2048; a first choice, no sweep yet
 
-void remove_scratch_free(mi_gallery* g) {
-  (void)hipFree(g->rm.arena);
-  g->rm = mi_gallery::RemoveScratch{};
-}
-
 static void diffusion_state_free(mi_gallery* g) {
   (void)hipFree(g->dif_ids);
   (void)hipFree(g->dif_vals);
@@ -87,12 +82,8 @@ int mi_gallery_remove_rows(mi_gallery* g, const uint64_t* remove_bits, int memsp
     const size_t sz[6] = {al((size_t)B * g->dp * 4), al((size_t)B * img_row), al((size_t)B * sizeof(RowStat)), al((size_t)m * 4),
                           al((size_t)nwords * 8), al((size_t)(nblk + 1) * 4)};
     const size_t need = arena_bytes(B);
-    if (g->rm.bytes < need) {
-      remove_scratch_free(g);
-      HIPC(device_malloc(&g->rm.arena, need));
-      g->rm.bytes = need;
-    }
-    char* p = (char*)g->rm.arena;
+    if ((rc = g->rm_arena.grow_exact(need)) != MI_OK) return rc;
+    char* p = g->rm_arena;
     float* stg_f32 = (float*)p;               p += sz[0];
     void* stg_img = p;                        p += sz[1];
     RowStat* stg_stat = (RowStat*)p;          p += sz[2];

@@ -1,0 +1,159 @@
+// csrc/device_buf.h on the host alone: the HIP runtime, device_malloc and fail are replaced by malloc / free / memcpy stand-ins that
+// count live allocations, and the buffer type is driven through every state.  Built and run by test_device_buf_cpu.py with the
+// host compiler under -fsanitize=address,undefined.  Exit status 0 = every check held and nothing is left allocated.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <utility>
+
+// ---- stand-ins for what api_internal.h has in scope when it includes the header
+enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorUnknown = 999 };
+enum hipMemcpyKind { hipMemcpyDeviceToDevice = 3 };
+enum { MI_OK = 0, MI_ERR_NOMEM = 2, MI_ERR_HIP = 3 };
+
+static long g_live = 0, g_allocs = 0, g_frees = 0;
+static long g_fail_in = -1;                  // > 0: that many allocations from now, one fails
+static hipError_t g_fail_with = hipErrorOutOfMemory;
+static std::string g_events;                 // 'A' / 'F' in the order they happened
+static std::string g_last_error;
+
+static hipError_t device_malloc(void** p, size_t bytes) {
+  if (g_fail_in > 0 && --g_fail_in == 0) {
+    *p = nullptr;
+    return g_fail_with;
+  }
+  *p = std::malloc(bytes);
+  ++g_live, ++g_allocs;
+  g_events += 'A';
+  return hipSuccess;
+}
+static hipError_t hipFree(void* p) {
+  if (p) --g_live, ++g_frees, g_events += 'F';
+  std::free(p);
+  return hipSuccess;
+}
+static hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) {
+  std::memcpy(dst, src, bytes);
+  return hipSuccess;
+}
+static const char* hipGetErrorString(hipError_t e) { return e == hipErrorOutOfMemory ? "out of memory" : "error"; }
+static int fail(int code, const std::string& msg) {
+  g_last_error = msg;
+  return code;
+}
+
+#include "../image-search-engine-for-historical-research_amd/csrc/device_buf.h"
+
+static int g_failed = 0;
+#define CHECK(cond)                                                      \
+  do {                                                                   \
+    if (!(cond)) {                                                       \
+      std::printf("FAILED line %d: %s\n", __LINE__, #cond);              \
+      ++g_failed;                                                        \
+    }                                                                    \
+  } while (0)
+
+int main() {
+  // the capacity formula: a quarter of spare and 64 elements
+  CHECK(grow_capacity(0) == 64 && grow_capacity(1) == 65 && grow_capacity(3) == 67 && grow_capacity(4) == 69);
+  CHECK(grow_capacity(1000) == 1314 && grow_capacity(((size_t)1 << 33) + 3) == ((size_t)1 << 33) + 3 + ((size_t)1 << 31) + 64);
+  {
+    DeviceBuf<uint32_t> b;
+    CHECK(b.get() == nullptr && b.count() == 0 && b.bytes() == 0);
+    // grow: allocates grow_capacity(count) elements
+    CHECK(b.grow(100) == MI_OK && b.count() == grow_capacity(100) && b.bytes() == grow_capacity(100) * 4 && g_live == 1);
+    uint32_t* p0 = b;
+    for (size_t i = 0; i < b.count(); ++i) p0[i] = (uint32_t)i;              // (the sanitizer checks the size is real)
+    // ... a no-op at or below the capacity
+    const long a0 = g_allocs, f0 = g_frees;
+    CHECK(b.grow(1) == MI_OK && b.grow(100) == MI_OK && b.grow(b.count()) == MI_OK);
+    CHECK(b.get() == p0 && g_allocs == a0 && g_frees == f0);
+    // ... and above it frees BEFORE it allocates (never two generations of one buffer at once)
+    g_events.clear();
+    const size_t c0 = b.count();
+    CHECK(b.grow(c0 + 1) == MI_OK && g_events == "FA" && b.count() == grow_capacity(c0 + 1) && g_live == 1);
+    // exact sizes: no slack, grow-only
+    DeviceBuf<double> e;
+    CHECK(e.grow_exact(10) == MI_OK && e.count() == 10 && e.bytes() == 80);
+    const double* e0 = e;
+    CHECK(e.grow_exact(7) == MI_OK && e.get() == e0 && e.count() == 10);
+    CHECK(e.grow_exact(11) == MI_OK && e.count() == 11);
+    CHECK(e.alloc(3) == hipSuccess && e.count() == 3);                       // alloc: exactly that, whatever was there
+    // a request of one size in elements with a capacity of the caller's own (the byte-sized staging of the gallery)
+    DeviceBuf<char> io;
+    CHECK(io.ensure(1000, 1000 + 250 + 256) == MI_OK && io.count() == 1506);
+    CHECK(io.ensure(1506, 1) == MI_OK && io.count() == 1506);
+    // grow_keep: the prefix survives, the new block is there before the old one goes
+    DeviceBuf<uint64_t> k;
+    CHECK(k.grow_keep(10, 0) == MI_OK && k.count() == grow_capacity(10));
+    for (size_t i = 0; i < k.count(); ++i) k.get()[i] = 1000 + i;
+    const size_t kc = k.count();
+    g_events.clear();
+    CHECK(k.grow_keep(kc, kc) == MI_OK && g_events.empty());                 // enough room: nothing happens
+    CHECK(k.grow_keep(kc + 50, kc) == MI_OK && g_events == "AF" && k.count() == grow_capacity(kc + 50));
+    bool same = true;
+    for (size_t i = 0; i < kc; ++i) same = same && k.get()[i] == 1000 + i;
+    CHECK(same);
+    // move: the source is left empty, nothing is allocated or freed; move assignment frees what the target held
+    const long live0 = g_live;
+    uint64_t* kp = k;
+    DeviceBuf<uint64_t> m(std::move(k));
+    CHECK(k.get() == nullptr && k.count() == 0 && k.bytes() == 0 && m.get() == kp && g_live == live0);
+    DeviceBuf<uint64_t> n;
+    CHECK(n.grow(5) == MI_OK && g_live == live0 + 1);
+    n = std::move(m);
+    CHECK(n.get() == kp && m.get() == nullptr && m.bytes() == 0 && g_live == live0);
+    CHECK(k.grow(3) == MI_OK && k.count() == grow_capacity(3));              // a moved-from buffer is an empty one
+    // reset: frees, empties, and may be repeated
+    b.reset();
+    CHECK(b.get() == nullptr && b.bytes() == 0);
+    const long f1 = g_frees;
+    b.reset();
+    CHECK(g_frees == f1 && b.get() == nullptr);
+    // a failed allocation: the error comes back through fail(), the buffer is empty (the old block is gone: contents are never
+    // kept), and the next call works
+    CHECK(b.grow(10) == MI_OK);
+    g_fail_in = 1, g_fail_with = hipErrorOutOfMemory, g_last_error.clear();
+    CHECK(b.grow(1000) == MI_ERR_NOMEM && b.get() == nullptr && b.count() == 0 && !g_last_error.empty());
+    g_fail_in = 1, g_fail_with = hipErrorUnknown;
+    CHECK(b.grow(1000) == MI_ERR_HIP && b.get() == nullptr);
+    CHECK(b.grow(1000) == MI_OK && b.count() == grow_capacity(1000));
+    g_fail_in = 1, g_fail_with = hipErrorOutOfMemory;
+    CHECK(n.grow_keep(n.count() + 1, 4) == MI_ERR_NOMEM && n.get() == nullptr && n.bytes() == 0);
+    g_fail_in = 1;
+    CHECK(e.alloc(5) == hipErrorOutOfMemory && e.get() == nullptr && e.bytes() == 0);
+    g_fail_in = -1;
+    // grow_all: every buffer its own count; stops at the first failure
+    DeviceBuf<int64_t> x;
+    DeviceBuf<float> y;
+    CHECK(grow_all(20, x, y) == MI_OK && x.count() == grow_capacity(20) && y.count() == grow_capacity(20));
+    g_fail_in = 2;
+    CHECK(grow_all(500, x, y) == MI_ERR_NOMEM && x.count() == grow_capacity(500) && y.get() == nullptr);
+    g_fail_in = -1;
+  }
+  CHECK(g_live == 0);                        // every buffer above freed itself at the end of its scope
+  {
+    // a set reaches the buffers constructed on it -- and only those -- for the byte sum and the reset
+    DeviceBufSet set;
+    DeviceBuf<uint16_t> a(set), b(set);
+    DeviceBuf<uint16_t> loose;
+    CHECK(set.bytes() == 0);
+    CHECK(a.grow(10) == MI_OK && b.grow_exact(3) == MI_OK && loose.grow(1) == MI_OK);
+    CHECK(set.bytes() == grow_capacity(10) * 2 + 6);
+    // the memory moves between buffers, their place in the set does not
+    b = std::move(loose);
+    CHECK(set.bytes() == grow_capacity(10) * 2 + grow_capacity(1) * 2 && g_live == 2);
+    DeviceBuf<uint16_t> out(std::move(a));
+    CHECK(set.bytes() == grow_capacity(1) * 2 && out.count() == grow_capacity(10));
+    set.reset();
+    CHECK(set.bytes() == 0 && b.get() == nullptr && g_live == 1 && out.get() != nullptr);
+    set.reset();
+    CHECK(g_live == 1);
+  }
+  CHECK(g_live == 0 && g_allocs == g_frees);
+  if (g_failed) return 1;
+  std::printf("device_buf_check ok: %ld allocations, all freed\n", g_allocs);
+  return 0;
+}
