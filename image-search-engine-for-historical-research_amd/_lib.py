@@ -134,6 +134,17 @@ SIGNATURES = {
     "mi_pq_get_codebooks": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi_pq_remove_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64p]),
     "mi_pq_destroy": (C.c_int, [C.c_void_p]),
+    "mi_pq_decode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "mi_pq_graph_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mi_pq_graph_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mi_pq_graph_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i64p]),
+    "mi_pq_graph_get_neighbors": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "mi_pq_graph_get_entries": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_pq_graph_destroy": (C.c_int, [C.c_void_p]),
+    "mi_pq_graph_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_pq_graph_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "mi_pq_train": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_pq_train_timing": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -1884,9 +1895,135 @@ class PQIndex:
             check(load().mi_pq_get_codes(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def decode(self, row0=0, nrows=None):
+        """-> float32 [nrows, d]: the rows reconstructed from their codes, codebooks[j][code[:, j]] side by side (nanopq's
+        pq.decode; mi_pq_decode)."""
+        nrows = self.n - row0 if nrows is None else int(nrows)
+        out = np.empty((nrows, self.d), dtype=np.float32)
+        with self._lock:
+            check(load().mi_pq_decode(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def close(self):
         if self._h is not None and self._h.value:
             check(load().mi_pq_destroy(self._h))
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+PQ_GRAPH_MAX_SHORTLIST = 2048     # a graph search returns at most ef <= 2048 rows: the longest shortlist refine= can ask for
+
+
+class PQGraphIndex:
+    """A neighbour graph over the codes of a PQIndex (a `mi_pq_graph` handle): best-first search from a set of
+    entry rows on ADC distances, the role of the reference's PQ + HNSW matchers.  No raw rows are resident.  Which rows the graph
+    reaches is approximate; the answer given graph, entry rows, codebooks, codes and query is exact: a row's distance has the bits
+    it has in PQIndex.search, the order is (distance asc, id asc).  The PQIndex must outlive the graph and is not changed by it;
+    after pq.add / pq.append_codes / pq.remove a search raises (build a new graph)."""
+
+    def __init__(self, handle, pq):
+        self._h = C.c_void_p(handle)
+        self._lock = threading.Lock()
+        self.pq = pq
+        n, R, ne = C.c_int64(), C.c_int32(), C.c_int32()
+        check(load().mi_pq_graph_info(self._h, n, R, ne, None))
+        self.n, self.R, self.n_entry = n.value, R.value, ne.value
+
+    @classmethod
+    def build(cls, pq, R=32, n_entry=16):
+        """mi_pq_graph_build: GraphIndex.build's table over ADC distances -- row i's query is its own reconstruction -- from the
+        exhaustive search of the PQ index; min(n_entry, n) evenly spaced entry rows.  Deterministic; runs on the device."""
+        R, n_entry = _graph_build_shape(pq.n, R, n_entry)
+        h = C.c_void_p()
+        with pq._lock:
+            check(load().mi_pq_graph_build(pq._h, R, n_entry, C.byref(h)))
+        return cls(h.value, pq)
+
+    @classmethod
+    def from_neighbors(cls, pq, table, entries):
+        """mi_pq_graph_create: table integer [n, R] of LOCAL rows (-1 = padding; self-loops and repeats are legal), entries
+        integer [ne] local rows -- GraphIndex.neighbors of a graph over the raw rows, for one.  Bad input raises ValueError before
+        the device is touched."""
+        t, e = _graph_table(pq.n, table, entries)
+        h = C.c_void_p()
+        with pq._lock:
+            check(load().mi_pq_graph_create(pq._h, C.c_void_p(t.ctypes.data), t.shape[1], MI_HOST, C.c_void_p(e.ctypes.data),
+                                            e.shape[0], C.byref(h)))
+        return cls(h.value, pq)
+
+    @property
+    def neighbors(self):
+        """The table, int32 [n, R]."""
+        out = np.empty((self.n, self.R), np.int32)
+        with self._lock:
+            check(load().mi_pq_graph_get_neighbors(self._h, 0, self.n, C.c_void_p(out.ctypes.data)))
+        return out
+
+    @property
+    def entries(self):
+        """The entry rows, int32 [n_entry]."""
+        out = np.empty(self.n_entry, np.int32)
+        with self._lock:
+            check(load().mi_pq_graph_get_entries(self._h, C.c_void_p(out.ctypes.data)))
+        return out
+
+    @property
+    def hbm_bytes(self):
+        """Table, entries and the grow-only workspace of the searches (the PQ index counts its own)."""
+        hb = C.c_int64()
+        check(load().mi_pq_graph_info(self._h, None, None, None, hb))
+        return hb.value
+
+    def search(self, q, k, ef=None, return_visited=False, refine=None, k_factor=1):
+        """-> (ids int64 [Q, k], dist float32 [Q, k], seconds); ef (the size of the candidate list W) defaults to max(k, 64),
+        1 <= k <= ef <= 2048.  Fewer than k rows reached: ids -1, distances +inf.  return_visited: int32 [Q], the rows evaluated
+        per query, appended to the tuple.
+        refine=<Gallery of the raw rows>: the graph search takes min(k * k_factor, n, 2048) ids (never fewer than k) on the device
+        with ef raised to that number where it is below, the gallery re-ranks them there (Gallery.refine; queries rounded to
+        float32) and the distances returned are its exact float32 values."""
+        k, ef = _graph_search_shape(k, ef)
+        a, code, rs, cs = self.pq._rows(q)
+        nq = a.shape[0]
+        if refine is not None:
+            if return_visited:
+                raise ValueError("return_visited is not available with refine")
+            kc = min(refine_kc(k, k_factor, self.n), PQ_GRAPH_MAX_SHORTLIST)       # (k <= ef <= 2048: never below k)
+            efc = max(ef, kc)
+
+            def dev(xq, m, kcand, cand_ptr, bits_ptr, stream):
+                with self._lock:
+                    self.search_device(xq.data_ptr(), m, kcand, cand_ptr, ef=efc, stream=stream)
+            return _search_refined(refine, a, k, kc, None, dev, self.pq.device)
+        idx = np.empty((nq, k), dtype=np.int64)
+        dist = np.empty((nq, k), dtype=np.float32)
+        vis = np.empty(nq, dtype=np.int32)
+        secs = C.c_double()
+        with self._lock:
+            check(load().mi_pq_graph_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, ef, C.c_void_p(idx.ctypes.data),
+                                            C.c_void_p(dist.ctypes.data), C.c_void_p(vis.ctypes.data), C.byref(secs)))
+        out = (idx, dist, secs.value)
+        return out + (vis,) if return_visited else out
+
+    def search_device(self, q_ptr, nq, k, idx_ptr, ef=None, dist_ptr=None, visited_ptr=None, stream=None):
+        """mi_pq_graph_search_device: q_ptr packed float32 [nq][d] on the device; enqueued on `stream`, no synchronisation."""
+        k, ef = _graph_search_shape(k, ef)
+        check(load().mi_pq_graph_search_device(self._h, C.c_void_p(q_ptr), int(nq), k, ef, C.c_void_p(idx_ptr), C.c_void_p(dist_ptr),
+                                               C.c_void_p(visited_ptr), C.c_void_p(stream)))
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            check(load().mi_pq_graph_destroy(self._h))
             self._h = None
 
     def __enter__(self):

@@ -22,6 +22,8 @@
 //   api_lsh.hip       LSH codes (mi_lsh_encode*, mi_hamming_append_lsh_device): f64 projection to sign bits, fused (lsh.hip)
 //   api_graph.hip     graph index (mi_graph): neighbour table over a gallery's rows, best-first search (graph_search.hip), table
 //                     from exact nearest-neighbour lists (graph_build.hip)
+//   api_pq_graph.hip  graph index over PQ codes (mi_pq_graph): neighbour table over the rows of a mi_pq index, best-first search on
+//                     ADC distances (pq_graph_search.hip), table from the exhaustive ADC search of the decoded rows
 // Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index family)
 // The handles' grow-only device buffers own themselves: device_buf.h (DeviceBuf<T> and the per-handle DeviceBufSet; host code only)
 #pragma once
@@ -343,6 +345,36 @@ struct mi_hamming {
   DeviceBuf<int64_t> rlims{bufs};
   std::mutex mu;
 };
+
+// the PQ index (api_pq.hip; api_pq_graph.hip searches a neighbour graph over its codes)
+struct mi_pq {
+  int device = 0;
+  int64_t n = 0, cap = 0, row_offset = 0;
+  int32_t d = 0, m = 0, ks = 0, L = 0, MQ = 0;     // columns, books, codewords per book, columns per book, dwords of a code
+  std::vector<float> cb_host;                      // [m][ks][L]
+  DeviceBufSet bufs;                               // every device allocation of the handle: hbm_bytes is bufs.bytes()
+  DeviceBuf<float> cb{bufs};                       // (cb, codes, flag: exactly their size, allocated at creation)
+  DeviceBuf<uint32_t> codes{bufs};                 // [ceil(cap / 64)][MQ][64]
+  DeviceBuf<uint32_t> flag{bufs};                  // raised by the check of device-resident codes (256 bytes)
+  hipStream_t stream = nullptr;
+  DeviceBuf<char> xraw{bufs};                      // rows / queries of a host call, packed [rows][d] in their own type
+  DeviceBuf<uint8_t> cbytes{bufs};                 // packed code bytes [rows][m]: host codes on their way in, encoder output
+  DeviceBuf<float> tab{bufs};                      // distance tables [queries of a chunk][m][ks]
+  DeviceBuf<float> mat{bufs};                      // negated distances [queries of a chunk][round_up(n, 64)]
+  DeviceBuf<int64_t> tidx{bufs};                   // [queries of a chunk][ke] what the selection returns
+  DeviceBuf<float> tneg{bufs};
+  DeviceBuf<uint64_t> bits{bufs};                  // device copy of a host bitmap
+  DeviceBuf<int64_t> oidx{bufs};                   // results of a host call
+  DeviceBuf<float> odist{bufs};
+  DeviceBuf<uint32_t> rmpref{bufs}, rmstage{bufs}; // mi_pq_remove_rows: prefix counts per bitmap word; staging blocks [..][MQ][64]
+  // bumped by every call that changes the rows (mi_pq_add, mi_pq_append_codes, mi_pq_remove_rows): what a mi_pq_graph records,
+  // since rows can leave and as many come back.  Internal; nothing reports it
+  uint64_t mod = 0;
+  std::mutex mu;
+};
+// the search proper on stream s (api_pq.hip): queries on the device (any strides), results go to device buffers
+MI_INTERNAL int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k,
+                               const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s);
 
 // ---- api_state.hip
 MI_INTERNAL int ws_free(Workspace& ws);

@@ -5,29 +5,6 @@
 // alone (float64 table entries rounded once, float32 sums in book order, order by (distance, id)): no certificate, no flag.
 #include "api_internal.h"
 
-struct mi_pq {
-  int device = 0;
-  int64_t n = 0, cap = 0, row_offset = 0;
-  int32_t d = 0, m = 0, ks = 0, L = 0, MQ = 0;     // columns, books, codewords per book, columns per book, dwords of a code
-  std::vector<float> cb_host;                      // [m][ks][L]
-  DeviceBufSet bufs;                               // every device allocation of the handle: hbm_bytes is bufs.bytes()
-  DeviceBuf<float> cb{bufs};                       // (cb, codes, flag: exactly their size, allocated at creation)
-  DeviceBuf<uint32_t> codes{bufs};                 // [ceil(cap / 64)][MQ][64]
-  DeviceBuf<uint32_t> flag{bufs};                  // raised by the check of device-resident codes (256 bytes)
-  hipStream_t stream = nullptr;
-  DeviceBuf<char> xraw{bufs};                      // rows / queries of a host call, packed [rows][d] in their own type
-  DeviceBuf<uint8_t> cbytes{bufs};                 // packed code bytes [rows][m]: host codes on their way in, encoder output
-  DeviceBuf<float> tab{bufs};                      // distance tables [queries of a chunk][m][ks]
-  DeviceBuf<float> mat{bufs};                      // negated distances [queries of a chunk][round_up(n, 64)]
-  DeviceBuf<int64_t> tidx{bufs};                   // [queries of a chunk][ke] what the selection returns
-  DeviceBuf<float> tneg{bufs};
-  DeviceBuf<uint64_t> bits{bufs};                  // device copy of a host bitmap
-  DeviceBuf<int64_t> oidx{bufs};                   // results of a host call
-  DeviceBuf<float> odist{bufs};
-  DeviceBuf<uint32_t> rmpref{bufs}, rmstage{bufs}; // mi_pq_remove_rows: prefix counts per bitmap word; staging blocks [..][MQ][64]
-  std::mutex mu;
-};
-
 // rows of code bytes (host: checked by the caller; device: checked here) -> rows n .. n + rows of the index, synchronous on the
 // handle's stream.  A device code byte >= ks: MI_ERR_INVALID, nothing written.
 static int pq_ingest(mi_pq* h, const void* codes, int64_t rows, int64_t stride, int memspace) {
@@ -90,8 +67,8 @@ static int pq_encode_blocks(mi_pq* h, const void* x, int64_t rows, int dtype, in
 }
 
 // the search proper on stream s: queries on the device (any strides), results go to device buffers
-static int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k,
-                          const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s) {
+int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k,
+                   const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s) {
   const int64_t npad = round_up(h->n, 64);
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   if (npad == 0) {
@@ -215,6 +192,7 @@ int mi_pq_append_codes(mi_pq* h, const void* codes, int64_t rows, int64_t row_st
   const int rc = pq_ingest(h, codes, rows, row_stride_bytes, memspace);
   if (rc != MI_OK) return rc;
   h->n += rows;
+  ++h->mod;
   return MI_OK;
 }
 
@@ -235,6 +213,7 @@ int mi_pq_add(mi_pq* h, const void* x, int64_t rows, int dtype, int64_t row_stri
   });
   if (rc != MI_OK) return rc;
   h->n = n0 + rows;
+  ++h->mod;
   return MI_OK;
 }
 
@@ -354,6 +333,27 @@ int mi_pq_get_codes(mi_pq* h, int64_t row0, int64_t nrows, uint8_t* out_host) {
   return MI_OK;
 }
 
+int mi_pq_decode(mi_pq* h, int64_t row0, int64_t nrows, float* out_host) {
+  REQUIRE(h, "null handle");
+  REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= h->n, "row range outside the index");
+  REQUIRE(out_host || nrows == 0, "null pointer: out_host");
+  if (nrows == 0) return MI_OK;
+  std::lock_guard<std::mutex> lock(h->mu);
+  HIPC(hipSetDevice(h->device));
+  hipStream_t s = h->stream;
+  const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * 4));
+  int rc;
+  if ((rc = h->xraw.grow((size_t)std::min(step, nrows) * h->d * 4)) != MI_OK) return rc;
+  for (int64_t r = 0; r < nrows; r += step) {
+    const int64_t mm = std::min(step, nrows - r);
+    launch_pq_decode(h->codes, h->m, h->ks, h->L, h->cb, row0 + r, mm, (float*)h->xraw.get(), s);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(out_host + r * h->d, h->xraw, (size_t)mm * h->d * 4, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));                 // the staging buffer is reused by the next block
+  }
+  return MI_OK;
+}
+
 int mi_pq_get_codebooks(const mi_pq* h, float* out_host) {
   REQUIRE(h, "null handle");
   REQUIRE(out_host, "null pointer: out_host");
@@ -408,6 +408,7 @@ int mi_pq_remove_rows(mi_pq* h, const uint64_t* remove_bits, int memspace, int64
     HIPC(hipStreamSynchronize(s));
   }
   h->n = m;
+  ++h->mod;
   if (out_removed) *out_removed = plan.removed;
   return MI_OK;
 }

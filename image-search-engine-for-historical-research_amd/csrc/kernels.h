@@ -374,6 +374,18 @@ void launch_pq_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, con
 void launch_pq_emit(const int64_t* tidx, const float* tneg, int64_t nq, int32_t ke, int32_t k, int64_t row_offset, int64_t* out_idx,
                     float* out_dist, hipStream_t stream);
 
+// pq_graph_search.hip -- best-first search of a neighbour graph over the codes of a PQ index (api_pq_graph.hip): graph_search.hip's
+// traversal with pq.hip's distances.  tab [nq][M][Ks] f32 as launch_pq_table writes it, codes in the index's transposed blocks; adj,
+// entries, vis and the limits as for launch_graph_search; out_dist and out_visited may be NULL.  Dynamic LDS pq_graph_lds_bytes
+// (at most 99856 bytes).  launch_pq_decode: rows [row0, row0 + nrows) reconstructed, out [nrows][M L] f32
+size_t pq_graph_lds_bytes(int32_t M, int32_t Ks, int32_t ef);
+void launch_pq_graph_search(const uint32_t* codes, int32_t M, int32_t Ks, const float* tab, int64_t n, int64_t row_offset,
+                            const int32_t* adj, int32_t R, const int32_t* entries, int32_t ne, int32_t k, int32_t ef, int64_t nq,
+                            uint32_t* vis, int64_t vis_words, int64_t* out_idx, float* out_dist, int32_t* out_visited,
+                            hipStream_t stream);
+void launch_pq_decode(const uint32_t* codes, int32_t M, int32_t Ks, int32_t L, const float* cb, int64_t row0, int64_t nrows, float* out,
+                      hipStream_t stream);
+
 // pq_train.hip -- learning PQ codebooks (api_pq_train.hip): Lloyd's iteration around launch_pq_encode.  cb [M][Ks][L] f32 is updated
 // in place (a codeword without members keeps its value); codes [n][M] bytes, cols [M][n] bytes (one contiguous column per book)
 void launch_pq_init_rows(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, int32_t M, int32_t Ks, int32_t L, float* cb,

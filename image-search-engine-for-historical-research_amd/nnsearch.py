@@ -499,6 +499,17 @@ def matching_Nano_PQ_hip(K, embedded_features_train, embedded_features_test, dat
     return idx, (t2 - t1) / max(num_test, 1)
 
 
+def _fill_short_rows(idx, num_train):
+    """Rows of idx [Q, K] with trailing -1s get the lowest indices not in the answer behind what was found, as the reference's
+    graph matchers do (src/utils/nnsearch.py:532-534, 574-576)."""
+    K = idx.shape[1]
+    for row in np.flatnonzero((idx < 0).any(axis=1)):
+        got = idx[row][idx[row] >= 0]
+        miss = np.flatnonzero(~np.isin(np.arange(num_train), got))
+        idx[row] = np.concatenate((got, miss))[:K]
+    return idx
+
+
 def _graph_path(dataset, R):
     return os.path.join(os.path.dirname(_gallery_path(dataset)), "mi355_graph_R%d.npz" % R)
 
@@ -559,16 +570,127 @@ def matching_HNSW_hip(K, embedded_features_train, embedded_features_test, datase
             t2 = time.time()
     finally:
         rows.close()
-    for row in np.flatnonzero((idx < 0).any(axis=1)):
-        got = idx[row][idx[row] >= 0]
-        miss = np.flatnonzero(~np.isin(np.arange(num_train), got))
-        idx[row] = np.concatenate((got, miss))[:K]
-    return idx, (t2 - t1) / max(num_test, 1)
+    return _fill_short_rows(idx, num_train), (t2 - t1) / max(num_test, 1)
+
+
+def _pq_graph_shape(K, num_train, m):
+    """(K, R) of the PQ + HNSW matchers; raises ValueError outside 1 <= m <= 32, 1 <= K <= min(N, 2048), N >= 2."""
+    K, m = int(K), int(m)
+    if m < 1 or 2 * m > _lib.GRAPH_MAX_R:
+        raise ValueError("m = %d: the graph holds R = 2 * m <= %d neighbours per row" % (m, _lib.GRAPH_MAX_R))
+    if K < 1 or K > num_train:
+        raise ValueError("K = %d, the database holds %d rows" % (K, num_train))
+    if K > TOPK_PATH_MAX_K:
+        raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
+    _lib._graph_build_shape(num_train, 2 * m, 16)
+    return K, 2 * m
+
+
+def matching_HNSW_PQ_hip(K, Codewords, embedded_features_test, CW_idx, m=4):
+    """Same signature and return shape as matching_HNSW_PQ (src/utils/nnsearch.py:541-582), plus m (the reference fixes 4): a
+    neighbour graph over the PQ codes CW_idx [N, N_books] under Codewords [N_words, dim] (book j is the column block j * L ..
+    (j + 1) * L), searched best-first on asymmetric distances with a candidate list of K rows (the reference searches with
+    ef=K, :573) -> (idx int64 [Q, K], time_per_query).  Queries are L2-normalised in their own precision as :546-548 does.
+    THE GRAPH IS THIS LIBRARY'S, not the reference's: _lib.PQGraphIndex.build with R = 2 * m neighbours per row and 16 evenly
+    spaced entry rows, built over the codes as given.  The codes are NOT de-duplicated: the reference's
+    np.unique / reverse-index expansion returns the rows of a code together, which is what the order (distance asc, id asc) gives
+    when the duplicates are reached.  What is exact is the search GIVEN the graph: the distances of matching_PQ_Net_hip, ties to
+    the lower index.  Where fewer than K rows are reached the tail is filled with the lowest indices not in the answer, as
+    :574-576 does.  N_words <= 256, dim % N_books == 0, 1 <= m <= 32, 1 <= K <= min(N, 2048), N >= 2; CW_idx must be an integer
+    array with values in [0, N_words).  Bad input raises ValueError before the device is touched.  It is no (K, train, test)
+    matcher and therefore not in MATCHING_METHODS.  The timer spans what the reference's spans: the search only,
+    device-synchronised."""
+    cw, q, codes = np.asarray(Codewords), np.asarray(embedded_features_test), np.asarray(CW_idx)
+    if cw.ndim != 2 or q.ndim != 2 or codes.ndim != 2 or q.shape[1] != cw.shape[1]:
+        raise ValueError("expected Codewords [N_words, dim], embedded_features_test [Q, dim] and CW_idx [N, N_books], got %s, %s and %s"
+                         % (cw.shape, q.shape, codes.shape))
+    n_words, dim = cw.shape
+    n_books = codes.shape[1]
+    if n_books < 1 or dim % n_books:
+        raise ValueError("dim = %d is no multiple of N_books = %d" % (dim, n_books))
+    if n_words > _lib.PQ_MAX_WORDS:
+        raise ValueError("N_words = %d, a code byte holds at most %d codewords per book" % (n_words, _lib.PQ_MAX_WORDS))
+    num_train, num_test = codes.shape[0], q.shape[0]
+    K, R = _pq_graph_shape(K, num_train, m)
+    if not np.issubdtype(q.dtype, np.floating):
+        raise ValueError("embedded_features_test must be a floating-point array (got %s)" % q.dtype)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = q / np.expand_dims(np.linalg.norm(q, axis=1), axis=1)
+    if not np.isfinite(q).all():
+        raise ValueError("embedded_features_test: rows must be finite and non-zero")
+    books = _lib.pq_codebooks(cw.reshape(n_words, n_books, dim // n_books).transpose(1, 0, 2))
+    code_rows, _ = _lib.pq_code_rows(codes, n_books, n_words)      # (raises ValueError on non-integer or out-of-range codes)
+    with _lib.PQIndex.from_codes(books, code_rows) as pq, _lib.PQGraphIndex.build(pq, R=R, n_entry=16) as g:
+        t1 = time.time()
+        idx, _, _ = g.search(q, K, ef=K)                   # (synchronous: the results are on the host when it returns)
+        t2 = time.time()
+    return _fill_short_rows(idx, num_train), (t2 - t1) / max(num_test, 1)
+
+
+def _pq_graph_path(dataset, n_books, n_words, R):
+    return os.path.join(os.path.dirname(_gallery_path(dataset)), "mi355_pqgraph_M%d_Ks%d_R%d.npz" % (n_books, n_words, R))
+
+
+def matching_HNSW_NanoPQ_hip(K, embedded_features, embedded_features_test, dataset=None, N_books=16, N_words=256, m=4, ef=8,
+                             ifgenerate=True):
+    """Same signature and return shape as matching_HNSW_NanoPQ (src/utils/nnsearch.py:585-683), `--matching_method PQ_HNSW`: both
+    sides L2-normalised and cast to float32, codebooks of N_books books of N_words codewords learned on the database rows
+    (_lib.pq_train: 20 iterations, seed 42), rows encoded, a neighbour graph built over the codes and searched best-first on
+    asymmetric distances with a candidate list of K rows (the reference searches with ef=K, :675; its `ef` argument is
+    efConstruction, which this build has no use for and ignores) -> (idx int64 [Q, K], time_per_query).  No raw row stays on the
+    device: the index is N_books + 8 * m bytes per row.  THE GRAPH IS THIS LIBRARY'S, not the reference's:
+    _lib.PQGraphIndex.build with R = 2 * m neighbours per row and 16 evenly spaced entry rows.  The codes are
+    NOT de-duplicated: the reference's np.unique / dict_recover expansion returns the rows of a code together, which is what
+    the order (distance asc, id asc) gives when the duplicates are reached.  What is exact is the search GIVEN codebooks, codes
+    and graph: the distances of matching_Nano_PQ_hip, ties to the lower index.  Where fewer than K rows are reached the tail is
+    filled with the lowest indices not in the answer, as :676-678 does.  N_words <= 256 (one byte per book; the reference's
+    entry points pass 2**13, which this build does not take), 1 <= m <= 32, 1 <= K <= min(N, 2048), N >= max(2, N_words).  With
+    a `dataset` codebooks, table and entry rows persist in one file outputs/<dataset>/mi355_pqgraph_M<M>_Ks<Ks>_R<R>.npz (written
+    to a temporary name and renamed): learned, built and written iff `ifgenerate`, otherwise loaded -- a missing file raises
+    FileNotFoundError, as the reference's open() does; dataset=None writes nothing (and needs ifgenerate).  The timer spans what
+    the reference's spans (:670-682): the search only, device-synchronised.  Learning is deterministic (see _lib.pq_train) but
+    does not reproduce nanopq's random draw of initial rows.  Bad input raises ValueError before the device is touched."""
+    N_books, N_words = int(N_books), int(N_words)
+    if N_words < 2 or N_words > _lib.PQ_MAX_WORDS:
+        raise ValueError("N_words = %d: a code byte holds 2 .. %d codewords per book" % (N_words, _lib.PQ_MAX_WORDS))
+    train = _l2_rows_f32(embedded_features, "embedded_features")
+    test = _l2_rows_f32(embedded_features_test, "embedded_features_test")
+    if train.shape[1] != test.shape[1]:
+        raise ValueError("expected rows [N, dim] and queries [Q, dim], got %s and %s" % (train.shape, test.shape))
+    num_train, num_test = train.shape[0], test.shape[0]
+    K, R = _pq_graph_shape(K, num_train, m)
+    L = _lib._pq_train_shape(num_train, train.shape[1], N_books, N_words, 20)
+    if dataset is None and not ifgenerate:
+        raise ValueError("ifgenerate=False loads codebooks and graph of a dataset: give one")
+    if ifgenerate:
+        books, _ = _lib.pq_train(train, N_books, N_words, iters=20, seed=42)
+    else:
+        with np.load(_pq_graph_path(dataset, N_books, N_words, R)) as z:     # (FileNotFoundError when it was never generated)
+            books = z["codebooks"]
+            table, entries = _lib._graph_table(num_train, z["neighbors"], z["entries"])
+        if books.shape != (N_books, N_words, L) or table.shape[1] != R:
+            raise ValueError("stored codebooks of shape %s and table of shape %s, this call takes %s and [%d, %d]"
+                             % (books.shape, table.shape, (N_books, N_words, L), num_train, R))
+    with _lib.PQIndex.empty(books, num_train) as pq:
+        pq.add(train)
+        g = _lib.PQGraphIndex.build(pq, R=R, n_entry=16) if ifgenerate else _lib.PQGraphIndex.from_neighbors(pq, table, entries)
+        with g:
+            if ifgenerate and dataset is not None:
+                path = _pq_graph_path(dataset, N_books, N_words, R)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                tmp = "%s.tmp.%d.%s.npz" % (path, os.getpid(), uuid.uuid4().hex[:12])
+                with _path_lock(path):
+                    np.savez(tmp, codebooks=books, neighbors=g.neighbors, entries=g.entries)
+                    os.replace(tmp, path)
+            t1 = time.time()
+            idx, _, _ = g.search(test, K, ef=K)            # (synchronous: the results are on the host when it returns)
+            t2 = time.time()
+    return _fill_short_rows(idx, num_train), (t2 - t1) / max(num_test, 1)
 
 
 # the matchers of this build by the name the reference's entry points dispatch on (--matching_method, src/offline.py:107-118)
 MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip, "PQ": matching_Nano_PQ_hip,
-                    "HNSW": matching_HNSW_hip}
+                    "HNSW": matching_HNSW_hip, "PQ_HNSW": matching_HNSW_NanoPQ_hip}
 
 
 def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test):

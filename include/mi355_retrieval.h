@@ -466,6 +466,58 @@ int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stri
  * numbers that ran go to out_assignments / out_updates (may be NULL). */
 int mi_pq_train_timing(int32_t capacity, float* out_assign_ms, float* out_update_ms, int32_t* out_assignments, int32_t* out_updates);
 
+/* ---- graph index over PQ codes: best-first search of a neighbour graph whose rows are the codes of ONE mi_pq index, the role of
+ * the reference's PQ + HNSW matchers (matching_HNSW_PQ, matching_HNSW_NanoPQ, matching_PQ_HNSW_faiss; src/utils/nnsearch.py:541-683,
+ * 802-825).  DESIGN.md 5.16b.  No raw rows are resident: the index is the m code bytes and the 4 R table bytes of a row, and a
+ * query's cost does not grow with n.  What is approximate is WHICH rows the graph reaches; given table, entries, codebooks,
+ * codes and query the answer is fully determined:
+ *   value      of a row: mi_pq_search's distance, bit for bit -- table entries T[j][c] the float64 sums rounded once to float32
+ *              (the bits of mi_pq_dtable), the distance their float32 sum in ascending book order; +inf is an ordinary value
+ *   order      (distance asc, id asc)
+ *   traversal  mi_graph_search's start / step / stop / answer, word for word, with 1 <= k <= ef <= 2048: the visited set is exact,
+ *              a row pushed out of W stays visited and is never expanded, and there are n expansions at the most whatever the
+ *              table holds
+ *   answer     the first k rows of W: ids row_offset + local row as mi_pq_search reports them, distances float32; fewer than k
+ *              rows in W: trailing ids -1, distances +inf.  out_visited (int32 [nq], may be NULL): the number of rows evaluated,
+ *              entries included.
+ * The mi_pq handle must outlive the graph.  The graph records the index's rows and an internal modification count that
+ * mi_pq_add, mi_pq_append_codes and mi_pq_remove_rows bump: after any of them -- also after a removal and an addition that
+ * restore n -- a search returns MI_ERR_INVALID and reads no table.  The index itself is not changed by anything here.
+ * mi_pq_graph_create takes a caller's table: neighbors [n][R] packed int32 of LOCAL rows in host or device memory, -1 being
+ * padding anywhere in a row, n the index's rows (1 <= n <= 2^31 - 1), 1 <= R <= 64; entries int32 [ne] in host memory,
+ * 1 <= ne <= 64.  An entry outside [0, n) or a table value below -1 or >= n is MI_ERR_INVALID; self-loops and repeats are legal.
+ * (One use: mi_graph_get_neighbors of a graph built on the raw rows, searched on the codes once the raw gallery is closed.)
+ * mi_pq_graph_build makes the table on the device, R even in [2, 64], 1 <= ne <= 64, n >= 2, the same bytes on every call: it is
+ * mi_graph_build's F, B, N and entries over another value matrix -- row i's query is its own reconstruction, the float32
+ * concatenation of C[j][code[i][j]], and its values are the distances above, from the exhaustive search (mi_pq_search_device with
+ * k = min(R + 1, n), whose answers are in the order already).  Rows with identical codes are whole tie classes at distance 0; the
+ * order and the rule "drop i, or the last row where i is absent" settle them.  The build is an n x n pass through the distance
+ * matrix of the PQ index, in chunks within "pq_matrix_bytes".
+ * Not built: an allow bitmap, sharding, updating a graph in place, ks > 256, the training of faiss's IndexHNSWPQ. */
+typedef struct mi_pq_graph mi_pq_graph; /* opaque */
+int mi_pq_graph_create(mi_pq* codes, const int32_t* neighbors, int32_t R, int neighbors_memspace, const int32_t* entries,
+                       int32_t ne, mi_pq_graph** out);
+int mi_pq_graph_build(mi_pq* codes, int32_t R, int32_t ne, mi_pq_graph** out);
+/* n, R, ne, hbm_bytes (any may be NULL; hbm_bytes: table, entries and the grow-only workspace the handle holds right now); the
+ * table rows [row0, row0 + nrows) and the ne entries into host memory */
+int mi_pq_graph_info(const mi_pq_graph* gr, int64_t* n, int32_t* R, int32_t* ne, int64_t* hbm_bytes);
+int mi_pq_graph_get_neighbors(mi_pq_graph* gr, int64_t row0, int64_t nrows, int32_t* out_host);
+int mi_pq_graph_get_entries(mi_pq_graph* gr, int32_t* out_host);
+int mi_pq_graph_destroy(mi_pq_graph* gr); /* NULL is MI_OK */
+/* Host form: queries as for mi_pq_search (any strides, MI_F32 or MI_F64; non-finite queries are MI_ERR_INVALID); synchronous, on
+ * the PQ index's stream.  out_dist and out_visited may be NULL.  nq == 0 is MI_OK and writes nothing. */
+int mi_pq_graph_search(mi_pq_graph* gr, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                       int32_t ef, int64_t* out_idx, float* out_dist, int32_t* out_visited, double* out_seconds);
+/* q_dev [nq][d] packed f32; enqueued on `stream`, no synchronisation.  A non-finite query leaves the order of ITS answer
+ * unspecified (nothing is read or written out of bounds).  The queries' tables and the visited bitmaps live in buffers of the
+ * graph handle (grown when a larger call comes; a batch whose bitmaps or tables would exceed 256 MiB runs in chunks of queries):
+ * calls on one handle must be serialised by the caller and enqueued on ONE stream. */
+int mi_pq_graph_search_device(mi_pq_graph* gr, const float* q_dev, int64_t nq, int32_t k, int32_t ef, int64_t* out_idx_dev,
+                              float* out_dist_dev, int32_t* out_visited_dev, void* stream);
+/* nanopq's pq.decode: rows [row0, row0 + nrows) of a PQ index reconstructed, float32 [nrows][d], to a host buffer; column
+ * j L + i of a row is C[j][code[j]][i].  Synchronous, on the index's stream. */
+int mi_pq_decode(mi_pq* h, int64_t row0, int64_t nrows, float* out_host);
+
 /* ---- IVF index over PQ codes: exact ADC top-K over the rows of the probed lists.  The reference's matching_PQ_Net_bucket(K,
  * Codewords, Query, N_books, CW_idx, Gallery_features, n_clusters) (src/utils/nnsearch.py:949-998), faiss IndexIVFPQ with
  * by_residual = false.  DESIGN.md 5.14c.  nlist lists (2 <= nlist <= 256: a list id is one byte, like a code) with coarse centroids
