@@ -990,48 +990,51 @@ def _graph_table(n, table, entries):
     return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(e, dtype=np.int32)
 
 
-class GraphIndex:
-    """A neighbour graph over the rows of a Gallery (a `mi_graph` handle; DESIGN.md 5.16): best-first search from a set of entry
-    rows, the role of the reference's HNSW matchers.  Which rows the graph reaches is approximate; the answer given graph, entry
-    rows, stored rows and query is exact: values are Gallery.refine's (direct-form float64 squared distances on an L2 gallery,
-    float64 inner products against the stored row on any other), the order is (value best first, id ascending).  The gallery
-    must outlive the index; after gallery.append* / gallery.remove a search raises (build a new graph)."""
+class _GraphBase:
+    """What GraphIndex and PQGraphIndex share: the handle of a `<_PREFIX>*` graph over an owner index (kept as the attribute
+    _OWNER names, which must outlive the graph), its table and its entry rows."""
+    _PREFIX = _OWNER = None
+    _INFO_EXTRA = ()                   # arguments of <_PREFIX>_info behind n, R and ne
 
-    def __init__(self, handle, gallery):
+    def __init__(self, handle, owner):
         self._h = C.c_void_p(handle)
         self._lock = threading.Lock()
-        self.gallery = gallery
+        setattr(self, self._OWNER, owner)
         n, R, ne = C.c_int64(), C.c_int32(), C.c_int32()
-        check(load().mi_graph_info(self._h, n, R, ne))
+        check(self._fn("info")(self._h, n, R, ne, *self._INFO_EXTRA))
         self.n, self.R, self.n_entry = n.value, R.value, ne.value
 
     @classmethod
-    def build(cls, gallery, R=32, n_entry=16):
-        """mi_graph_build: per row its R / 2 nearest rows, up to R / 2 reverse edges, then further nearest rows up to R entries;
-        min(n_entry, n) evenly spaced entry rows.  Deterministic; runs on the device."""
-        R, n_entry = _graph_build_shape(gallery.n, R, n_entry)
-        h = C.c_void_p()
-        with gallery._lock:
-            check(load().mi_graph_build(gallery._h, R, n_entry, C.byref(h)))
-        return cls(h.value, gallery)
+    def _fn(cls, name):
+        return getattr(load(), "%s_%s" % (cls._PREFIX, name))
 
     @classmethod
-    def from_neighbors(cls, gallery, table, entries):
-        """mi_graph_create: table integer [n, R] of LOCAL rows (-1 = padding; self-loops and repeats are legal), entries integer
-        [ne] local rows.  Bad input raises ValueError before the device is touched."""
-        t, e = _graph_table(gallery.n, table, entries)
+    def build(cls, owner, R=32, n_entry=16):
+        """<_PREFIX>_build: per row its R / 2 nearest rows, up to R / 2 reverse edges, then further nearest rows up to R entries;
+        min(n_entry, n) evenly spaced entry rows.  Deterministic; runs on the device."""
+        R, n_entry = _graph_build_shape(owner.n, R, n_entry)
         h = C.c_void_p()
-        with gallery._lock:
-            check(load().mi_graph_create(gallery._h, C.c_void_p(t.ctypes.data), t.shape[1], MI_HOST, C.c_void_p(e.ctypes.data),
-                                         e.shape[0], C.byref(h)))
-        return cls(h.value, gallery)
+        with owner._lock:
+            check(cls._fn("build")(owner._h, R, n_entry, C.byref(h)))
+        return cls(h.value, owner)
+
+    @classmethod
+    def from_neighbors(cls, owner, table, entries):
+        """<_PREFIX>_create: table integer [n, R] of LOCAL rows (-1 = padding; self-loops and repeats are legal), entries integer
+        [ne] local rows.  Bad input raises ValueError before the device is touched."""
+        t, e = _graph_table(owner.n, table, entries)
+        h = C.c_void_p()
+        with owner._lock:
+            check(cls._fn("create")(owner._h, C.c_void_p(t.ctypes.data), t.shape[1], MI_HOST, C.c_void_p(e.ctypes.data), e.shape[0],
+                                    C.byref(h)))
+        return cls(h.value, owner)
 
     @property
     def neighbors(self):
         """The table, int32 [n, R]."""
         out = np.empty((self.n, self.R), np.int32)
         with self._lock:
-            check(load().mi_graph_get_neighbors(self._h, 0, self.n, C.c_void_p(out.ctypes.data)))
+            check(self._fn("get_neighbors")(self._h, 0, self.n, C.c_void_p(out.ctypes.data)))
         return out
 
     @property
@@ -1039,8 +1042,35 @@ class GraphIndex:
         """The entry rows, int32 [n_entry]."""
         out = np.empty(self.n_entry, np.int32)
         with self._lock:
-            check(load().mi_graph_get_entries(self._h, C.c_void_p(out.ctypes.data)))
+            check(self._fn("get_entries")(self._h, C.c_void_p(out.ctypes.data)))
         return out
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            check(self._fn("destroy")(self._h))
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GraphIndex(_GraphBase):
+    """A neighbour graph over the rows of a Gallery (a `mi_graph` handle; DESIGN.md 5.16): best-first search from a set of entry
+    rows, the role of the reference's HNSW matchers.  Which rows the graph reaches is approximate; the answer given graph, entry
+    rows, stored rows and query is exact: values are Gallery.refine's (direct-form float64 squared distances on an L2 gallery,
+    float64 inner products against the stored row on any other), the order is (value best first, id ascending).  The gallery
+    must outlive the index; after gallery.append* / gallery.remove a search raises (build a new graph)."""
+
+    _PREFIX, _OWNER = "mi_graph", "gallery"
 
     def search(self, q, k, ef=None, return_visited=False, return_values64=False):
         """-> (ids int64 [Q, k], values float32 [Q, k], seconds); ef (the size of the candidate list W) defaults to max(k, 64),
@@ -1068,23 +1098,6 @@ class GraphIndex:
         k, ef = _graph_search_shape(k, ef)
         check(load().mi_graph_search_device(self._h, C.c_void_p(q_ptr), int(nq), k, ef, C.c_void_p(idx_ptr), C.c_void_p(val_ptr),
                                             C.c_void_p(val64_ptr), C.c_void_p(visited_ptr), C.c_void_p(stream)))
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            check(load().mi_graph_destroy(self._h))
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def refine_kc(k, k_factor, n):
@@ -1925,58 +1938,16 @@ class PQIndex:
 PQ_GRAPH_MAX_SHORTLIST = 2048     # a graph search returns at most ef <= 2048 rows: the longest shortlist refine= can ask for
 
 
-class PQGraphIndex:
+class PQGraphIndex(_GraphBase):
     """A neighbour graph over the codes of a PQIndex (a `mi_pq_graph` handle): best-first search from a set of
     entry rows on ADC distances, the role of the reference's PQ + HNSW matchers.  No raw rows are resident.  Which rows the graph
     reaches is approximate; the answer given graph, entry rows, codebooks, codes and query is exact: a row's distance has the bits
     it has in PQIndex.search, the order is (distance asc, id asc).  The PQIndex must outlive the graph and is not changed by it;
-    after pq.add / pq.append_codes / pq.remove a search raises (build a new graph)."""
+    after pq.add / pq.append_codes / pq.remove a search raises (build a new graph).  build: GraphIndex.build's table over ADC
+    distances -- row i's query is its own reconstruction -- from the exhaustive search of the PQ index; from_neighbors takes
+    GraphIndex.neighbors of a graph over the raw rows, for one."""
 
-    def __init__(self, handle, pq):
-        self._h = C.c_void_p(handle)
-        self._lock = threading.Lock()
-        self.pq = pq
-        n, R, ne = C.c_int64(), C.c_int32(), C.c_int32()
-        check(load().mi_pq_graph_info(self._h, n, R, ne, None))
-        self.n, self.R, self.n_entry = n.value, R.value, ne.value
-
-    @classmethod
-    def build(cls, pq, R=32, n_entry=16):
-        """mi_pq_graph_build: GraphIndex.build's table over ADC distances -- row i's query is its own reconstruction -- from the
-        exhaustive search of the PQ index; min(n_entry, n) evenly spaced entry rows.  Deterministic; runs on the device."""
-        R, n_entry = _graph_build_shape(pq.n, R, n_entry)
-        h = C.c_void_p()
-        with pq._lock:
-            check(load().mi_pq_graph_build(pq._h, R, n_entry, C.byref(h)))
-        return cls(h.value, pq)
-
-    @classmethod
-    def from_neighbors(cls, pq, table, entries):
-        """mi_pq_graph_create: table integer [n, R] of LOCAL rows (-1 = padding; self-loops and repeats are legal), entries
-        integer [ne] local rows -- GraphIndex.neighbors of a graph over the raw rows, for one.  Bad input raises ValueError before
-        the device is touched."""
-        t, e = _graph_table(pq.n, table, entries)
-        h = C.c_void_p()
-        with pq._lock:
-            check(load().mi_pq_graph_create(pq._h, C.c_void_p(t.ctypes.data), t.shape[1], MI_HOST, C.c_void_p(e.ctypes.data),
-                                            e.shape[0], C.byref(h)))
-        return cls(h.value, pq)
-
-    @property
-    def neighbors(self):
-        """The table, int32 [n, R]."""
-        out = np.empty((self.n, self.R), np.int32)
-        with self._lock:
-            check(load().mi_pq_graph_get_neighbors(self._h, 0, self.n, C.c_void_p(out.ctypes.data)))
-        return out
-
-    @property
-    def entries(self):
-        """The entry rows, int32 [n_entry]."""
-        out = np.empty(self.n_entry, np.int32)
-        with self._lock:
-            check(load().mi_pq_graph_get_entries(self._h, C.c_void_p(out.ctypes.data)))
-        return out
+    _PREFIX, _OWNER, _INFO_EXTRA = "mi_pq_graph", "pq", (None,)
 
     @property
     def hbm_bytes(self):
@@ -2020,23 +1991,6 @@ class PQGraphIndex:
         k, ef = _graph_search_shape(k, ef)
         check(load().mi_pq_graph_search_device(self._h, C.c_void_p(q_ptr), int(nq), k, ef, C.c_void_p(idx_ptr), C.c_void_p(dist_ptr),
                                                C.c_void_p(visited_ptr), C.c_void_p(stream)))
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            check(load().mi_pq_graph_destroy(self._h))
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 IVF_MAX_LISTS = 256

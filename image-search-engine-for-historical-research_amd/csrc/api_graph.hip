@@ -1,16 +1,133 @@
 // Graph index over the stored rows of a gallery (mi_graph*; the role of the reference's HNSW matchers).  DESIGN.md 5.16.
-// The handle holds a neighbour table int32 [n][R] and up to 64 entry rows on the device, plus the workspace of its searches;
-// the rows, their metric and the stream of the host entry points are the gallery's.  Kernels: graph_search.hip (one workgroup
-// per query, best-first traversal), graph_build.hip (table from exact nearest-neighbour lists); the lists themselves come from
-// the verified search of the gallery (search_sync) followed by launch_refine, which puts them in the graph's own order.
+// The handle holds a GraphTable (neighbour table int32 [n][R] and up to 64 entry rows on the device), plus the workspace of its
+// searches; the rows, their metric and the stream of the host entry points are the gallery's.  Kernels: graph_search.hip (one
+// workgroup per query, best-first traversal), graph_build.hip (table from exact nearest-neighbour lists); the lists themselves
+// come from the verified search of the gallery (search_sync) followed by launch_refine, which puts them in the graph's own order.
+// The first half of the file is what every graph index does with its table (declared in api_internal.h; api_pq_graph.hip calls it).
 #include "api_internal.h"
+
+// ---- shared by the graph indexes
+
+// what both search forms check before the handle is read
+int graph_search_check(const void* gr, int64_t nq, int32_t k, int32_t ef) {
+  REQUIRE(gr, "null handle");
+  REQUIRE(ef >= 1 && ef <= GRAPH_MAX_EF, "ef must be in [1, 2048]");
+  REQUIRE(k >= 1 && k <= ef, "k must be in [1, ef]");
+  REQUIRE(nq >= 0, "nq must be >= 0");
+  return MI_OK;
+}
+
+int graph_create_check(const void* owner, const int32_t* neighbors, int32_t R, int neighbors_memspace, const int32_t* entries,
+                       int32_t ne, const void* out) {
+  REQUIRE(owner, "null handle");
+  REQUIRE(neighbors, "null pointer: neighbors");
+  REQUIRE(entries, "null pointer: entries");
+  REQUIRE(out, "null pointer: out");
+  REQUIRE(R >= 1 && R <= GRAPH_MAX_R, "R must be in [1, 64]");
+  REQUIRE(ne >= 1 && ne <= GRAPH_MAX_ENTRIES, "ne must be in [1, 64]");
+  REQUIRE(neighbors_memspace == MI_HOST || neighbors_memspace == MI_DEVICE, "neighbors_memspace must be MI_HOST or MI_DEVICE");
+  for (int32_t i = 0; i < ne; ++i) REQUIRE(entries[i] >= 0, "entry rows must lie in [0, n)");
+  return MI_OK;
+}
+
+int graph_build_check(const void* owner, int32_t R, int32_t ne, const void* out) {
+  REQUIRE(owner, "null handle");
+  REQUIRE(out, "null pointer: out");
+  REQUIRE(R >= 2 && R <= GRAPH_MAX_R && R % 2 == 0, "R must be even and in [2, 64]");
+  REQUIRE(ne >= 1 && ne <= GRAPH_MAX_ENTRIES, "ne must be in [1, 64]");
+  return MI_OK;
+}
+
+int graph_build_rows_check(int64_t n) {
+  REQUIRE(n >= 2, "a graph is built over at least two rows");
+  REQUIRE(n <= 0x7fffffff, "a graph takes at most 2^31 - 1 rows");
+  return MI_OK;
+}
+
+int graph_table_alloc(GraphTable& t, int64_t n, int32_t R, int32_t ne, const char* name) {
+  const hipError_t e = t.alloc(n, R, ne);
+  if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, std::string(name) + " table: " + hipGetErrorString(e));
+  return MI_OK;
+}
+
+int graph_table_from_neighbors(GraphTable& t, int64_t n, int device, const char* name, const int32_t* neighbors, int32_t R,
+                               int neighbors_memspace, const int32_t* entries, int32_t ne) {
+  REQUIRE(n <= 0x7fffffff, "a graph takes at most 2^31 - 1 rows");
+  for (int32_t i = 0; i < ne; ++i) REQUIRE(entries[i] < n, "entry rows must lie in [0, n)");
+  HIPC(hipSetDevice(device));
+  const size_t cnt = (size_t)n * R;
+  std::vector<int32_t> staged;
+  const int32_t* tab = neighbors;
+  if (neighbors_memspace == MI_DEVICE) {
+    staged.resize(cnt);
+    HIPC(hipMemcpy(staged.data(), neighbors, cnt * 4, hipMemcpyDeviceToHost));
+    tab = staged.data();
+  }
+  for (size_t i = 0; i < cnt; ++i) REQUIRE(tab[i] >= -1 && tab[i] < n, "table values must be -1 (padding) or lie in [0, n)");
+  int rc = graph_table_alloc(t, n, R, ne, name);
+  if (rc != MI_OK) return rc;
+  hipError_t e = hipMemcpy(t.adj, tab, cnt * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(t.entries, entries, (size_t)ne * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    t.adj.reset(), t.entries.reset();
+    return fail(MI_ERR_HIP, std::string(name) + " table copy: " + hipGetErrorString(e));
+  }
+  return MI_OK;
+}
+
+GraphBuildWs graph_build_workspace(TmpAlloc& tmp, int64_t n, int32_t R) {
+  int32_t* F = tmp.get<int32_t>((size_t)n * R);
+  int32_t* B = tmp.get<int32_t>((size_t)n * R);
+  uint32_t* cnt = tmp.get<uint32_t>((size_t)n * 2);
+  return {F, B, cnt, tmp.get<unsigned long long>((size_t)n + 1)};
+}
+
+int graph_table_finish(GraphTable& t, const GraphBuildWs& ws, TmpAlloc& tmp, const char* name, hipStream_t s) {
+  const int64_t n = t.n;
+  const std::string what = std::string(name) + " build: ";
+  hipError_t e = hipMemsetAsync(ws.cnt, 0, (size_t)n * 2 * 4, s);
+  if (e != hipSuccess) return fail(MI_ERR_HIP, what + hipGetErrorString(e));
+  launch_graph_rev_count(ws.F, n, t.R, ws.cnt, ws.off, s);
+  unsigned long long total = 0;
+  e = hipMemcpyAsync(&total, ws.off + n, 8, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return fail(MI_ERR_HIP, what + hipGetErrorString(e));
+  unsigned long long* edges = tmp.get<unsigned long long>((size_t)std::max<unsigned long long>(total, 1));
+  if (!edges) return fail(MI_ERR_NOMEM, what + "reverse edges");
+  launch_graph_table(ws.F, n, t.R, ws.off, ws.cnt + n, edges, ws.B, t.adj, s);
+  std::vector<int32_t> ent((size_t)t.ne);
+  for (int32_t i = 0; i < t.ne; ++i) ent[i] = (int32_t)(((__int128)i * n) / t.ne);
+  e = hipMemcpyAsync(t.entries, ent.data(), (size_t)t.ne * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return fail(MI_ERR_HIP, what + hipGetErrorString(e));
+  return MI_OK;
+}
+
+int graph_table_get_neighbors(const GraphTable& t, std::mutex& mu, int device, int64_t row0, int64_t nrows, int32_t* out_host) {
+  REQUIRE(nrows >= 0 && row0 >= 0, "negative row range");
+  REQUIRE(nrows == 0 || out_host, "null pointer: out");
+  REQUIRE(row0 + nrows <= t.n, "row range beyond the table");
+  if (nrows == 0) return MI_OK;
+  std::lock_guard<std::mutex> lock(mu);
+  HIPC(hipSetDevice(device));
+  HIPC(hipMemcpy(out_host, t.adj + (size_t)row0 * t.R, (size_t)nrows * t.R * 4, hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+int graph_table_get_entries(const GraphTable& t, std::mutex& mu, int device, int32_t* out_host) {
+  REQUIRE(out_host, "null pointer: out");
+  std::lock_guard<std::mutex> lock(mu);
+  HIPC(hipSetDevice(device));
+  HIPC(hipMemcpy(out_host, t.entries, (size_t)t.ne * 4, hipMemcpyDeviceToHost));
+  return MI_OK;
+}
+
+// ---- mi_graph
 
 struct mi_graph {
   mi_gallery* rows = nullptr;
-  int64_t n = 0;                       // rows of the gallery when the table was made: a search refuses any other number
-  int32_t R = 0, ne = 0;
-  DeviceBuf<int32_t> adj;              // [n][R], -1 = padding
-  DeviceBuf<int32_t> entries;          // [ne]
+  GraphTable table;                    // table.n: rows of the gallery when it was made; a search refuses any other number
   // grow-only workspace of the searches (all of these free themselves when the handle is deleted)
   DeviceBuf<char> qraw;                // queries of a host call as given
   DeviceBuf<float> qpad;               // [nq][dp]
@@ -22,21 +139,8 @@ struct mi_graph {
   std::mutex mu;
 };
 
-// bytes of visited bitmaps one launch may use: a batch whose bitmaps need more is searched in chunks of queries
-constexpr size_t GRAPH_VIS_BYTES = (size_t)256 << 20;
-constexpr int64_t GRAPH_BUILD_BATCH = 8192;      // rows per exact search of mi_graph_build
-
-// what both search forms check before the handle is read
-static int graph_search_check(const mi_graph* gr, int64_t nq, int32_t k, int32_t ef) {
-  REQUIRE(gr, "null handle");
-  REQUIRE(ef >= 1 && ef <= GRAPH_MAX_EF, "ef must be in [1, 2048]");
-  REQUIRE(k >= 1 && k <= ef, "k must be in [1, ef]");
-  REQUIRE(nq >= 0, "nq must be >= 0");
-  return MI_OK;
-}
-
 static int graph_fresh(const mi_graph* gr) {
-  REQUIRE(gr->rows->n == gr->n, "the gallery has been appended to or had rows removed since the graph was made: build a new graph");
+  REQUIRE(gr->rows->n == gr->table.n, "the gallery has been appended to or had rows removed since the graph was made: build a new graph");
   return MI_OK;
 }
 
@@ -44,17 +148,17 @@ static int graph_fresh(const mi_graph* gr) {
 static int graph_enqueue(mi_graph* gr, const void* src, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k, int32_t ef,
                          int64_t* out_idx, float* out_val, double* out_val64, int32_t* out_visited, hipStream_t s) {
   mi_gallery* g = gr->rows;
+  const GraphTable& t = gr->table;
   int rc;
   if ((rc = gr->qpad.grow((size_t)nq * g->dp)) != MI_OK) return rc;
-  const int64_t words = (gr->n + 31) / 32;
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(GRAPH_VIS_BYTES / 4) / words));
+  const auto [words, chunk] = graph_vis_chunks(t.n, nq);
   if ((rc = gr->vis.grow((size_t)chunk * words)) != MI_OK) return rc;
   launch_l2_augment(src, dtype, nq, g->ud, rs, cs, gr->qpad, g->dp, s);
   for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
     const int64_t b = std::min<int64_t>(chunk, nq - q0);
     HIPC(hipMemsetAsync(gr->vis, 0, (size_t)b * words * 4, s));
-    launch_graph_search(g->gal_f32, gr->qpad + (size_t)q0 * g->dp, g->dp, g->ud, gr->n, g->row_offset,
-                        g->metric == MI_METRIC_L2 ? 1 : 0, gr->adj, gr->R, gr->entries, gr->ne, k, ef, b, gr->vis, words,
+    launch_graph_search(g->gal_f32, gr->qpad + (size_t)q0 * g->dp, g->dp, g->ud, t.n, g->row_offset,
+                        g->metric == MI_METRIC_L2 ? 1 : 0, t.adj, t.R, t.entries, t.ne, k, ef, b, gr->vis, words,
                         out_idx + q0 * k, out_val ? out_val + q0 * k : nullptr, out_val64 ? out_val64 + q0 * k : nullptr,
                         out_visited ? out_visited + q0 : nullptr, s);
   }
@@ -62,98 +166,55 @@ static int graph_enqueue(mi_graph* gr, const void* src, int dtype, int64_t rs, i
   return MI_OK;
 }
 
-// a handle over `rows` with room for the table and the entries (neither filled)
-static int graph_alloc(mi_gallery* rows, int32_t R, int32_t ne, mi_graph** out) {
-  mi_graph* gr = new mi_graph();
-  gr->rows = rows;
-  gr->n = rows->n;
-  gr->R = R;
-  gr->ne = ne;
-  hipError_t e = gr->adj.alloc((size_t)gr->n * R);
-  if (e == hipSuccess) e = gr->entries.alloc((size_t)ne);
-  if (e != hipSuccess) {
-    delete gr;
-    return fail(e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, std::string("graph table: ") + hipGetErrorString(e));
-  }
-  *out = gr;
-  return MI_OK;
-}
-
 extern "C" {
 
 int mi_graph_create(mi_gallery* rows, const int32_t* neighbors, int32_t R, int neighbors_memspace, const int32_t* entries,
                     int32_t ne, mi_graph** out) {
-  REQUIRE(rows, "null handle");
-  REQUIRE(neighbors, "null pointer: neighbors");
-  REQUIRE(entries, "null pointer: entries");
-  REQUIRE(out, "null pointer: out");
-  REQUIRE(R >= 1 && R <= GRAPH_MAX_R, "R must be in [1, 64]");
-  REQUIRE(ne >= 1 && ne <= GRAPH_MAX_ENTRIES, "ne must be in [1, 64]");
-  REQUIRE(neighbors_memspace == MI_HOST || neighbors_memspace == MI_DEVICE, "neighbors_memspace must be MI_HOST or MI_DEVICE");
-  for (int32_t i = 0; i < ne; ++i) REQUIRE(entries[i] >= 0, "entry rows must lie in [0, n)");
-  std::lock_guard<std::mutex> lock(rows->mu);
-  const int64_t n = rows->n;
-  REQUIRE(n >= 1, "the gallery holds no rows");
-  REQUIRE(n <= 0x7fffffff, "a graph takes at most 2^31 - 1 rows");
-  for (int32_t i = 0; i < ne; ++i) REQUIRE(entries[i] < n, "entry rows must lie in [0, n)");
-  HIPC(hipSetDevice(rows->device));
-  const size_t cnt = (size_t)n * R;
-  std::vector<int32_t> staged;
-  const int32_t* tab = neighbors;
-  if (neighbors_memspace == MI_DEVICE) {
-    staged.resize(cnt);
-    HIPC(hipMemcpy(staged.data(), neighbors, cnt * 4, hipMemcpyDeviceToHost));
-    tab = staged.data();
-  }
-  for (size_t i = 0; i < cnt; ++i) REQUIRE(tab[i] >= -1 && tab[i] < n, "table values must be -1 (padding) or lie in [0, n)");
-  mi_graph* gr = nullptr;
-  int rc = graph_alloc(rows, R, ne, &gr);
+  int rc = graph_create_check(rows, neighbors, R, neighbors_memspace, entries, ne, out);
   if (rc != MI_OK) return rc;
-  hipError_t e = hipMemcpy(gr->adj, tab, cnt * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(gr->entries, entries, (size_t)ne * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
+  std::lock_guard<std::mutex> lock(rows->mu);
+  REQUIRE(rows->n >= 1, "the gallery holds no rows");
+  mi_graph* gr = new mi_graph();
+  gr->rows = rows;
+  if ((rc = graph_table_from_neighbors(gr->table, rows->n, rows->device, "graph", neighbors, R, neighbors_memspace, entries, ne)) != MI_OK) {
     delete gr;
-    return fail(MI_ERR_HIP, std::string("graph table copy: ") + hipGetErrorString(e));
+    return rc;
   }
   *out = gr;
   return MI_OK;
 }
 
 int mi_graph_build(mi_gallery* rows, int32_t R, int32_t ne, mi_graph** out) {
-  REQUIRE(rows, "null handle");
-  REQUIRE(out, "null pointer: out");
-  REQUIRE(R >= 2 && R <= GRAPH_MAX_R && R % 2 == 0, "R must be even and in [2, 64]");
-  REQUIRE(ne >= 1 && ne <= GRAPH_MAX_ENTRIES, "ne must be in [1, 64]");
+  int rc = graph_build_check(rows, R, ne, out);
+  if (rc != MI_OK) return rc;
   mi_gallery* g = rows;
   std::lock_guard<std::mutex> lock(g->mu);
   const int64_t n = g->n;
-  REQUIRE(n >= 2, "a graph is built over at least two rows");
-  REQUIRE(n <= 0x7fffffff, "a graph takes at most 2^31 - 1 rows");
+  if ((rc = graph_build_rows_check(n)) != MI_OK) return rc;
   HIPC(hipSetDevice(g->device));
   hipStream_t s = g->stream;
   const bool l2 = g->metric == MI_METRIC_L2;
   const int32_t ks = (int32_t)std::min<int64_t>(R + 1, n);
-  const int32_t nent = (int32_t)std::min<int64_t>(ne, n);
-  int rc;
   if ((rc = join_tails(g, s)) != MI_OK) return rc;
-  mi_graph* gr = nullptr;
-  if ((rc = graph_alloc(g, R, nent, &gr)) != MI_OK) return rc;
+  mi_graph* gr = new mi_graph();
+  gr->rows = g;
+  if ((rc = graph_table_alloc(gr->table, n, R, (int32_t)std::min<int64_t>(ne, n), "graph")) != MI_OK) {
+    delete gr;
+    return rc;
+  }
   auto bail = [&](int code) {
     (void)hipStreamSynchronize(s);
     delete gr;
     return code;
   };
-  TmpAlloc tmp;                                   // (freed on return; every path out of here has synchronised `s`)
+  TmpAlloc tmp;                                  // (freed on return; every path out of here has synchronised `s`)
   const int64_t bmax = std::min<int64_t>(GRAPH_BUILD_BATCH, n);
-  int32_t* F = tmp.get<int32_t>((size_t)n * R);
-  int32_t* B = tmp.get<int32_t>((size_t)n * R);
-  uint32_t* cnt = tmp.get<uint32_t>((size_t)n * 2);               // counts, then fill cursors
-  unsigned long long* off = tmp.get<unsigned long long>((size_t)n + 1);
+  const GraphBuildWs ws = graph_build_workspace(tmp, n, R);
   int64_t* ids = tmp.get<int64_t>((size_t)bmax * ks);
   int64_t* ord = tmp.get<int64_t>((size_t)bmax * ks);
   double* val = tmp.get<double>((size_t)bmax * ks);
   float* qaug = l2 ? tmp.get<float>((size_t)bmax * g->dp) : nullptr;
-  if (!F || !B || !cnt || !off || !ids || !ord || !val || (l2 && !qaug)) return bail(fail(MI_ERR_NOMEM, "graph build workspace"));
+  if (!ws.F || !ws.B || !ws.cnt || !ws.off || !ids || !ord || !val || (l2 && !qaug)) return bail(fail(MI_ERR_NOMEM, "graph build workspace"));
   // forward lists: the exact search of every stored row against the gallery, through the verified loop (a raised flag is answered
   // again inside search_sync), then the values and the order of mi_refine over what it returned
   for (int64_t r0 = 0; r0 < n; r0 += bmax) {
@@ -168,58 +229,32 @@ int mi_graph_build(mi_gallery* rows, int32_t R, int32_t ne, mi_graph** out) {
     }
     if (rc != MI_OK) return bail(rc);
     launch_refine(g->gal_f32, src, g->dp, g->ud, n, g->row_offset, l2 ? 1 : 0, ids, ks, ks, ks, b, val, ord, nullptr, nullptr, s);
-    launch_graph_forward(ord, ks, r0, b, g->row_offset, n, R, F, s);
+    launch_graph_forward(ord, ks, r0, b, g->row_offset, n, R, ws.F, s);
     hipError_t e = hipStreamSynchronize(s);        // (ids / ord / val are reused by the next batch's search)
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("graph build: ") + hipGetErrorString(e)));
   }
-  hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n * 2 * 4, s);
-  if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("graph build: ") + hipGetErrorString(e)));
-  launch_graph_rev_count(F, n, R, cnt, off, s);
-  unsigned long long total = 0;
-  e = hipMemcpyAsync(&total, off + n, 8, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("graph build: ") + hipGetErrorString(e)));
-  unsigned long long* edges = tmp.get<unsigned long long>((size_t)std::max<unsigned long long>(total, 1));
-  if (!edges) return bail(fail(MI_ERR_NOMEM, "graph build: reverse edges"));
-  launch_graph_table(F, n, R, off, cnt + n, edges, B, gr->adj, s);
-  std::vector<int32_t> ent((size_t)nent);
-  for (int32_t t = 0; t < nent; ++t) ent[t] = (int32_t)(((__int128)t * n) / nent);
-  e = hipMemcpyAsync(gr->entries, ent.data(), (size_t)nent * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("graph build: ") + hipGetErrorString(e)));
+  if ((rc = graph_table_finish(gr->table, ws, tmp, "graph", s)) != MI_OK) return bail(rc);
   *out = gr;
   return MI_OK;
 }
 
 int mi_graph_info(const mi_graph* gr, int64_t* n, int32_t* R, int32_t* ne) {
   REQUIRE(gr, "null handle");
-  if (n) *n = gr->n;
-  if (R) *R = gr->R;
-  if (ne) *ne = gr->ne;
+  if (n) *n = gr->table.n;
+  if (R) *R = gr->table.R;
+  if (ne) *ne = gr->table.ne;
   return MI_OK;
 }
 
 int mi_graph_get_neighbors(mi_graph* gr, int64_t row0, int64_t nrows, int32_t* out_host) {
   REQUIRE(gr, "null handle");
-  REQUIRE(nrows >= 0 && row0 >= 0, "negative row range");
-  REQUIRE(nrows == 0 || out_host, "null pointer: out");
-  REQUIRE(row0 + nrows <= gr->n, "row range beyond the table");
-  if (nrows == 0) return MI_OK;
-  std::lock_guard<std::mutex> lock(gr->mu);
-  HIPC(hipSetDevice(gr->rows->device));
-  HIPC(hipMemcpy(out_host, gr->adj + (size_t)row0 * gr->R, (size_t)nrows * gr->R * 4, hipMemcpyDeviceToHost));
-  return MI_OK;
+  return graph_table_get_neighbors(gr->table, gr->mu, gr->rows->device, row0, nrows, out_host);
 }
 
 int mi_graph_get_entries(mi_graph* gr, int32_t* out_host) {
   REQUIRE(gr, "null handle");
-  REQUIRE(out_host, "null pointer: out");
-  std::lock_guard<std::mutex> lock(gr->mu);
-  HIPC(hipSetDevice(gr->rows->device));
-  HIPC(hipMemcpy(out_host, gr->entries, (size_t)gr->ne * 4, hipMemcpyDeviceToHost));
-  return MI_OK;
+  return graph_table_get_entries(gr->table, gr->mu, gr->rows->device, out_host);
 }
 
 int mi_graph_destroy(mi_graph* gr) {

@@ -21,11 +21,14 @@
 //                     (row removal of both PQ handles: mi_pq_remove_rows in api_pq.hip, mi_ivfpq_remove_rows here; kernels in pq_remove.hip)
 //   api_lsh.hip       LSH codes (mi_lsh_encode*, mi_hamming_append_lsh_device): f64 projection to sign bits, fused (lsh.hip)
 //   api_graph.hip     graph index (mi_graph): neighbour table over a gallery's rows, best-first search (graph_search.hip), table
-//                     from exact nearest-neighbour lists (graph_build.hip)
+//                     from exact nearest-neighbour lists (graph_build.hip); and what every graph index does with its table
+//                     (graph_table_*, graph_*_check: the checks, create from a caller's table, the tail of a build, the getters)
 //   api_pq_graph.hip  graph index over PQ codes (mi_pq_graph): neighbour table over the rows of a mi_pq index, best-first search on
 //                     ADC distances (pq_graph_search.hip), table from the exhaustive ADC search of the decoded rows
-// Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index family)
-// The handles' grow-only device buffers own themselves: device_buf.h (DeviceBuf<T> and the per-handle DeviceBufSet; host code only)
+// Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index
+// family), graph_walk.h (the best-first walk of both graph indexes)
+// The handles' grow-only device buffers own themselves: device_buf.h (DeviceBuf<T> and the per-handle DeviceBufSet; host code only);
+// graph_table.h (GraphTable: the neighbour table and entry rows both graph handles hold)
 #pragma once
 #include "../../include/mi355_retrieval.h"
 
@@ -99,6 +102,7 @@ MI_INTERNAL const char* last_error_message();
     if (!(cond)) return fail(MI_ERR_INVALID, msg); \
   } while (0)
 #include "device_buf.h"   // DeviceBuf<T>, DeviceBufSet, grow_all
+#include "graph_table.h"  // GraphTable
 
 
 // The host half of a row removal on a PQ or an IVF-PQ index (mi_pq_remove_rows, mi_ivfpq_remove_rows; defined in api_pq.hip): the
@@ -156,6 +160,36 @@ struct TmpAlloc {
     return reinterpret_cast<T*>(p);
   }
 };
+// ---- what mi_graph and mi_pq_graph do with their GraphTable (api_graph.hip).  `name` ("graph", "PQ graph") opens the messages.
+// The caller holds the owner's lock wherever the owner's rows are read
+constexpr size_t GRAPH_VIS_BYTES = (size_t)256 << 20;      // visited bitmaps of one launch: a batch that needs more goes in chunks
+constexpr int64_t GRAPH_BUILD_BATCH = 8192;                // rows per exact search of a build
+MI_INTERNAL int graph_search_check(const void* gr, int64_t nq, int32_t k, int32_t ef);
+MI_INTERNAL int graph_create_check(const void* owner, const int32_t* neighbors, int32_t R, int neighbors_memspace,
+                                   const int32_t* entries, int32_t ne, const void* out);
+MI_INTERNAL int graph_build_check(const void* owner, int32_t R, int32_t ne, const void* out);
+MI_INTERNAL int graph_build_rows_check(int64_t n);
+MI_INTERNAL int graph_table_alloc(GraphTable& t, int64_t n, int32_t R, int32_t ne, const char* name);
+// the caller's table (host or device) and entries over n >= 1 rows: checked, copied into `t`; on failure nothing stays allocated
+MI_INTERNAL int graph_table_from_neighbors(GraphTable& t, int64_t n, int device, const char* name, const int32_t* neighbors, int32_t R,
+                                           int neighbors_memspace, const int32_t* entries, int32_t ne);
+// the workspace of a build besides the forward-list loop's own: forward lists, scratch, counts then fill cursors, offsets
+struct GraphBuildWs {
+  int32_t *F, *B;
+  uint32_t* cnt;
+  unsigned long long* off;
+};
+MI_INTERNAL GraphBuildWs graph_build_workspace(TmpAlloc& tmp, int64_t n, int32_t R);
+// the tail of a build: t.adj from the forward lists ws.F, the evenly spaced entries; `s` is synchronised where it returns MI_OK
+MI_INTERNAL int graph_table_finish(GraphTable& t, const GraphBuildWs& ws, TmpAlloc& tmp, const char* name, hipStream_t s);
+MI_INTERNAL int graph_table_get_neighbors(const GraphTable& t, std::mutex& mu, int device, int64_t row0, int64_t nrows, int32_t* out_host);
+MI_INTERNAL int graph_table_get_entries(const GraphTable& t, std::mutex& mu, int device, int32_t* out_host);
+// visited bitmaps of a search of nq queries: words per query, queries per launch
+struct GraphVisChunks { int64_t words, chunk; };
+static inline GraphVisChunks graph_vis_chunks(int64_t n, int64_t nq) {
+  const int64_t words = (n + 31) / 32;
+  return {words, std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(GRAPH_VIS_BYTES / 4) / words))};
+}
 // what phase 1 of one batch will do (pure arithmetic on the shapes; plan_phase1)
 struct P1Plan {
   int32_t nq = 0, k = 0, qpad = 0;

@@ -74,6 +74,7 @@ class DeviceBuf : public DeviceBufBase {
  public:
   DeviceBuf() : DeviceBufBase(nullptr) {}
   explicit DeviceBuf(DeviceBufSet& set) : DeviceBufBase(&set) {}
+  explicit DeviceBuf(DeviceBufSet* set) : DeviceBufBase(set) {}      // NULL: in no set
   DeviceBuf(DeviceBuf&& o) noexcept : DeviceBufBase(nullptr) { take(o); }
   DeviceBuf& operator=(DeviceBuf&& o) noexcept {
     if (this != &o) take(o);

@@ -286,8 +286,8 @@ void launch_refine(const float* gal_f32, const float* qry, int32_t dp, int32_t d
                    const int64_t* cand, int32_t kc, int64_t cand_stride, int32_t k, int64_t nq, double* val, int64_t* out_idx,
                    float* out_val, double* out_val64, hipStream_t stream);
 
-// graph_search.hip -- best-first search of a neighbour graph on the stored f32 rows (api_graph.hip; values by l2_wave.h): one
-// workgroup per query, W (the best ef rows, sorted) in LDS, an exact visited bitmap of vis_words 32-bit words per query in `vis`
+// graph_search.hip -- best-first search of a neighbour graph on the stored f32 rows (api_graph.hip; the walk of graph_walk.h with
+// values by l2_wave.h): one workgroup per query, W (the best ef rows, sorted) in LDS, an exact visited bitmap of vis_words 32-bit words per query in `vis`
 // ([nq][vis_words], all zero when the launch starts).  adj [n][R] int32 (-1 = padding), entries [ne <= 64], 1 <= k <= ef <=
 // GRAPH_MAX_EF, R <= GRAPH_MAX_R.  out_val, out_val64, out_visited may be NULL.
 constexpr int GRAPH_MAX_EF = 2048, GRAPH_MAX_R = 64, GRAPH_MAX_ENTRIES = 64;
@@ -374,8 +374,8 @@ void launch_pq_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, con
 void launch_pq_emit(const int64_t* tidx, const float* tneg, int64_t nq, int32_t ke, int32_t k, int64_t row_offset, int64_t* out_idx,
                     float* out_dist, hipStream_t stream);
 
-// pq_graph_search.hip -- best-first search of a neighbour graph over the codes of a PQ index (api_pq_graph.hip): graph_search.hip's
-// traversal with pq.hip's distances.  tab [nq][M][Ks] f32 as launch_pq_table writes it, codes in the index's transposed blocks; adj,
+// pq_graph_search.hip -- best-first search of a neighbour graph over the codes of a PQ index (api_pq_graph.hip): the walk of
+// graph_walk.h with pq.hip's distances.  tab [nq][M][Ks] f32 as launch_pq_table writes it, codes in the index's transposed blocks; adj,
 // entries, vis and the limits as for launch_graph_search; out_dist and out_visited may be NULL.  Dynamic LDS pq_graph_lds_bytes
 // (at most 99856 bytes).  launch_pq_decode: rows [row0, row0 + nrows) reconstructed, out [nrows][M L] f32
 size_t pq_graph_lds_bytes(int32_t M, int32_t Ks, int32_t ef);

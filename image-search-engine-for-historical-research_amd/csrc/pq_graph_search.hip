@@ -1,57 +1,83 @@
 // Best-first search of a neighbour graph over the CODES of a PQ index (mi_pq_graph; the role of the reference's PQ + HNSW
-// matchers), and the decoder that gives the build its queries.
+// matchers): the scorer of graph_walk.h for PQ codes, and the decoder that gives the build its queries.
 //
-// The traversal is graph_search.hip's, step for step; what differs is what a row costs.  There a row is an 8 KiB gather by a
-// whole wave; here it is ceil(M / 4) dwords read by ONE lane and M reads of the query's distance table, which stays in LDS for
-// the whole search.  One workgroup of four waves per query:
-//   0. the query's table [M][Ks] (made by pq_table_kernel: the bits of mi_pq_dtable) -> LDS in pq_adc_row's image, 4 MQ books;
-//   1. every thread scans its share of W for the first place not yet expanded, one LDS atomicMin picks the first of all;
-//   2. wave 0 reads that row's R table entries, drops -1s, ids outside [0, n), repeats within the row (compared in LDS) and rows
-//      whose bit in the query's visited bitmap is set (exact: n bits per query in HBM, atomicOr because two lanes may share a
-//      word; the bitmap belongs to this workgroup alone), and compacts the rest by a ballot;
-//   3. lane t of wave 0 evaluates new row t: pq_adc_row, float32 adds in ascending book order, the bits of mi_pq_search.  The
-//      codes lie in the index's transposed blocks [block][MQ][64], so a row's code is MQ dwords 256 bytes apart and a dword is
-//      the widest load that layout has; the 64 lanes of a block read 64 consecutive dwords;
-//   4. the up to 64 new rows are ordered by rank among themselves;
-//   5. W and the new rows merge by rank into the other half of the double buffer; places >= ef fall off (and stay visited).
+// What differs from graph_search.hip is what a row costs.  There a row is an 8 KiB gather by a whole wave; here it is
+// ceil(M / 4) dwords read by ONE lane and M reads of the query's distance table, which the kernel copies to LDS before the walk
+// ([M][Ks], made by pq_table_kernel: the bits of mi_pq_dtable; in pq_adc_row's image, 4 MQ books) and which stays there for the
+// whole search.  Lane t of wave 0 evaluates new row t: pq_adc_row, float32 adds in ascending book order, the bits of
+// mi_pq_search.  The codes lie in the index's transposed blocks [block][MQ][64], so a row's code is MQ dwords 256 bytes apart and
+// a dword is the widest load that layout has; the 64 lanes of a block read 64 consecutive dwords.
 // A place of W is ONE 64-bit word: pq_key(distance, row) -- float bits above, the 31-bit local row below -- with the `expanded`
 // mark in bit 31 of the low word, masked out of every comparison.  Distances are >= +0.0 or +inf, so the integer order of the
 // masked keys IS (distance asc, id asc), and keys of distinct rows are distinct: no tie class.
 //
-// Workgroup size.  Steps 2 to 4 are one wave's work (at most 64 rows).  The other three waves are kept for steps 0, 1 and 5: the
-// table copy (up to 16384 floats), the scan of W and above all the merge, which at ef = 2048 is 2048 binary searches per step
-// -- 8 per thread with 256 threads, 32 with 64.  At small ef they idle at the barriers, which costs little: the workgroup is
-// LDS-bound to one or two per CU either way.
-//
 // Dynamic LDS, in bytes (pq_graph_lds_bytes): table 16 MQ Ks (at most 65536) | W 8 ef | other half 8 ef | new keys as evaluated
 // 512 | new keys in the order 512 | table entries as read 256 | new ids 256 | control 16.  The largest carve the contract admits
 // (M = 64, Ks = 256, ef = 2048) is 65536 + 32768 + 1552 = 99856 bytes of the 160 KiB of a CU.
-// No atomics across workgroups, no grid barrier; results leave by ordinary vector stores.
 #include <algorithm>
 
+#include "graph_walk.h"
 #include "kernels.h"
 #include "pq_device.h"
 
 namespace mi {
 
 constexpr uint64_t PG_EXPANDED = 0x80000000ull;
-constexpr uint32_t PG_NONE = 0xffffffffu;
 
-__device__ __forceinline__ uint64_t pg_bare(uint64_t key) { return key & ~PG_EXPANDED; }
+struct PgCodes {
+  typedef uint64_t Place;
+  struct List {
+    uint64_t* k;
+    __device__ __forceinline__ Place load(int j) const { return k[j]; }
+    __device__ __forceinline__ void store(int j, Place p) const { k[j] = p; }
+    __device__ __forceinline__ void mark(int j, Place) const { k[j] |= PG_EXPANDED; }
+  };
+  static __device__ __forceinline__ Place bare(Place p) { return p & ~PG_EXPANDED; }
+  static __device__ __forceinline__ bool before(Place a, Place b) { return a < b; }
+  static __device__ __forceinline__ bool expanded(Place p) { return p & PG_EXPANDED; }
+  static __device__ __forceinline__ uint32_t row(Place p) { return (uint32_t)p & 0x7fffffffu; }
 
-// number of places of the sorted list keys[0, len) that come before `key` (a bare key)
-__device__ __forceinline__ int pg_rank(const uint64_t* keys, int len, uint64_t key) {
-  int lo = 0, hi = len;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (pg_bare(keys[mid]) < key) lo = mid + 1;
-    else hi = mid;
+  List w, w2, nw, sn;
+  uint32_t *n_id, *s_raw, *s_ctl;
+  const float* tl;                 // the query's table in LDS
+  const uint32_t* codes;
+  int32_t MQ, Ks;
+  int64_t row_offset;
+  int64_t* out_idx;
+  float* out_dist;
+
+  // behind the table
+  __device__ __forceinline__ void carve(char* smem, int ef) {
+    w.k = reinterpret_cast<uint64_t*>(smem);
+    w2.k = w.k + ef;
+    nw.k = w2.k + ef;
+    sn.k = nw.k + 64;
+    s_raw = reinterpret_cast<uint32_t*>(sn.k + 64);
+    n_id = s_raw + 64;
+    s_ctl = n_id + 64;
   }
-  return lo;
-}
+  // one lane per new row
+  __device__ __forceinline__ void evaluate(int m, int t) const {
+    if (t < m) {
+      const uint32_t r = n_id[t];
+      const uint32_t* src = codes + (int64_t)(r >> 6) * MQ * 64 + (r & 63u);
+      nw.k[t] = pq_key(pq_adc_row<1>(tl, src, MQ, Ks).v[0], r);
+    }
+  }
+  __device__ __forceinline__ void emit(int64_t o, int i, bool have) const {
+    int64_t id = -1;
+    float v = INFINITY;
+    if (have) {
+      id = row_offset + (int64_t)row(w.k[i]);
+      v = pq_key_dist(w.k[i]);
+    }
+    out_idx[o] = id;
+    if (out_dist) out_dist[o] = v;
+  }
+};
 
-// codes [ceil(cap / 64)][MQ][64]; tab [gridDim.x][real = M Ks]; adj [n][R]; entries [ne]; vis [gridDim.x][vis_words], all zero
-// on entry (the caller clears it before every launch); dynamic LDS: pq_graph_lds_bytes(MQ, Ks, ef)
+// codes [ceil(cap / 64)][MQ][64]; tab [gridDim.x][real = M Ks]; adj, entries, vis as graph_walk takes them; dynamic LDS:
+// pq_graph_lds_bytes(MQ, Ks, ef)
 __global__ __launch_bounds__(256) void pq_graph_search_kernel(const uint32_t* __restrict__ codes, int32_t MQ, int32_t Ks, int32_t real,
                                                               const float* __restrict__ tab, int64_t n, int64_t row_offset,
                                                               const int32_t* __restrict__ adj, int32_t R,
@@ -62,114 +88,12 @@ __global__ __launch_bounds__(256) void pq_graph_search_kernel(const uint32_t* __
   extern __shared__ __attribute__((aligned(16))) char pg_smem[];
   const int32_t ent = 4 * MQ * Ks;
   float* tl = reinterpret_cast<float*>(pg_smem);
-  uint64_t* wk = reinterpret_cast<uint64_t*>(tl + ent);   // W; wk2 is the half the next merge writes
-  uint64_t* wk2 = wk + ef;
-  uint64_t* n_key = wk2 + ef;                          // new rows as evaluated
-  uint64_t* s_key = n_key + 64;                        // new rows in the order
-  uint32_t* s_raw = reinterpret_cast<uint32_t*>(s_key + 64);   // the table entries of the expanded row as read
-  uint32_t* n_id = s_raw + 64;                         // new rows, compacted
-  uint32_t* s_ctl = n_id + 64;                         // [0] first unexpanded place, [1] number of new rows
-
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  const int64_t q = blockIdx.x;
-  uint32_t* myvis = vis + q * vis_words;
-  int wn = 0;
-  int64_t visited = 0;
-
-  // ---- start: the table, and the distinct entry rows as the first batch of new rows, none of them expanded
-  pq_slab_load_table<256>(tl, tab + q * real, ent, real, t);
-  if (wv == 0) {
-    const int32_t e = lane < ne ? entries[lane] : -1;
-    s_raw[lane] = (uint32_t)e;
-  }
-  __syncthreads();
-  for (int64_t step = -1; step < n; ++step) {
-    if (step >= 0) {
-      // 1. the first place of W that is not yet expanded
-      if (t == 0) s_ctl[0] = PG_NONE;
-      __syncthreads();
-      for (int i = t; i < wn; i += 256)
-        if (!(wk[i] & PG_EXPANDED)) {
-          atomicMin(&s_ctl[0], (uint32_t)i);
-          break;
-        }
-      __syncthreads();
-      const uint32_t first = s_ctl[0];
-      if (first == PG_NONE) break;                     // (uniform: every thread reads the same word)
-      const uint32_t row = (uint32_t)wk[first] & 0x7fffffffu;
-      if (wv == 0) s_raw[lane] = lane < R ? (uint32_t)adj[(int64_t)row * R + lane] : PG_NONE;
-      __syncthreads();
-      if (t == 0) wk[first] |= PG_EXPANDED;
-    }
-    // 2. wave 0: valid, first occurrence within the row, not visited -> n_id[0, m)
-    if (wv == 0) {
-      const int cnt = step < 0 ? ne : R;
-      const uint32_t c = s_raw[lane];
-      bool keep = lane < cnt && (int32_t)c >= 0 && (int64_t)c < n;
-      if (keep)
-        for (int j = 0; j < lane; ++j)
-          if (s_raw[j] == c) {
-            keep = false;
-            break;
-          }
-      if (keep) {
-        const uint32_t bit = 1u << (c & 31);
-        keep = (atomicOr(&myvis[c >> 5], bit) & bit) == 0;
-      }
-      const unsigned long long m = __ballot(keep);
-      if (keep) n_id[__popcll(m & ((1ull << lane) - 1))] = c;
-      if (lane == 0) s_ctl[1] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    const int m = (int)s_ctl[1];
-    visited += m;
-    if (m == 0) continue;                              // (uniform)
-    // 3. one lane per new row
-    if (t < m) {
-      const uint32_t row = n_id[t];
-      const uint32_t* src = codes + (int64_t)(row >> 6) * MQ * 64 + (row & 63u);
-      n_key[t] = pq_key(pq_adc_row<1>(tl, src, MQ, Ks).v[0], row);
-    }
-    __syncthreads();
-    // 4. the new rows in the order (their keys are distinct)
-    if (t < m) {
-      const uint64_t key = n_key[t];
-      int r = 0;
-      for (int j = 0; j < m; ++j) r += n_key[j] < key ? 1 : 0;
-      s_key[r] = key;
-    }
-    __syncthreads();
-    // 5. merge by rank into the other half; what lands at ef or beyond is pushed out (and stays visited)
-    for (int i = t; i < wn; i += 256) {
-      const uint64_t key = wk[i];
-      const int p = i + pg_rank(s_key, m, pg_bare(key));
-      if (p < ef) wk2[p] = key;
-    }
-    if (t < m) {
-      const uint64_t key = s_key[t];
-      const int p = t + pg_rank(wk, wn, key);
-      if (p < ef) wk2[p] = key;
-    }
-    wn = min(wn + m, ef);
-    {
-      uint64_t* tk = wk;
-      wk = wk2, wk2 = tk;
-    }
-    __syncthreads();
-  }
-
-  // ---- answer: the first k places of W
-  for (int i = t; i < k; i += 256) {
-    int64_t id = -1;
-    float v = INFINITY;
-    if (i < wn) {
-      id = row_offset + (int64_t)(pq_key_row(wk[i]) & 0x7fffffffu);
-      v = pq_key_dist(wk[i]);
-    }
-    out_idx[q * k + i] = id;
-    if (out_dist) out_dist[q * k + i] = v;
-  }
-  if (out_visited && t == 0) out_visited[q] = (int32_t)visited;
+  PgCodes p;
+  p.carve(reinterpret_cast<char*>(tl + ent), ef);
+  p.tl = tl, p.codes = codes, p.MQ = MQ, p.Ks = Ks, p.row_offset = row_offset, p.out_idx = out_idx, p.out_dist = out_dist;
+  // the table; the walk's first barrier stands between this copy and its first reader
+  pq_slab_load_table<256>(tl, tab + (int64_t)blockIdx.x * real, ent, real, threadIdx.x);
+  graph_walk(p, n, adj, R, entries, ne, k, ef, vis, vis_words, out_visited);
 }
 
 // out [nrows][M L]: row row0 + r reconstructed, the concatenation of C[j][code[j]] (nanopq's pq.decode)

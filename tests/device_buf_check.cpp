@@ -1,4 +1,4 @@
-// csrc/device_buf.h on the host alone: the HIP runtime, device_malloc and fail are replaced by malloc / free / memcpy stand-ins that
+// csrc/device_buf.h (and csrc/graph_table.h, which needs nothing more) on the host alone: the HIP runtime, device_malloc and fail are replaced by malloc / free / memcpy stand-ins that
 // count live allocations, and the buffer type is driven through every state.  Built and run by test_device_buf_cpu.py with the
 // host compiler under -fsanitize=address,undefined.  Exit status 0 = every check held and nothing is left allocated.
 #include <cstdint>
@@ -45,6 +45,7 @@ static int fail(int code, const std::string& msg) {
 }
 
 #include "../image-search-engine-for-historical-research_amd/csrc/device_buf.h"
+#include "../image-search-engine-for-historical-research_amd/csrc/graph_table.h"
 
 static int g_failed = 0;
 #define CHECK(cond)                                                      \
@@ -151,6 +152,22 @@ int main() {
     CHECK(set.bytes() == 0 && b.get() == nullptr && g_live == 1 && out.get() != nullptr);
     set.reset();
     CHECK(g_live == 1);
+  }
+  CHECK(g_live == 0 && g_allocs == g_frees);
+  {
+    // the neighbour table of the graph handles (csrc/graph_table.h) on a set: exactly the table and the entries; when the second
+    // allocation fails nothing stays allocated, and the next request works
+    DeviceBufSet set;
+    GraphTable t(&set);
+    CHECK(t.alloc(10, 4, 3) == hipSuccess && t.n == 10 && t.R == 4 && t.ne == 3 && set.bytes() == 10 * 4 * 4 + 3 * 4 && g_live == 2);
+    g_fail_in = 2, g_fail_with = hipErrorOutOfMemory;
+    CHECK(t.alloc(1000, 8, 5) == hipErrorOutOfMemory);
+    CHECK(t.adj.get() == nullptr && t.entries.get() == nullptr && set.bytes() == 0 && g_live == 0);
+    g_fail_in = -1;
+    CHECK(t.alloc(7, 2, 1) == hipSuccess && set.bytes() == 7 * 2 * 4 + 4);
+    for (size_t i = 0; i < t.adj.count(); ++i) t.adj.get()[i] = -1;          // (the sanitizer checks the size is real)
+    GraphTable loose;                                                        // on no set: counted nowhere, freed all the same
+    CHECK(loose.alloc(3, 2, 1) == hipSuccess && set.bytes() == 7 * 2 * 4 + 4 && g_live == 4);
   }
   CHECK(g_live == 0 && g_allocs == g_frees);
   if (g_failed) return 1;
