@@ -4,6 +4,7 @@ There is no CPU fallback: if the shared library is missing or a call fails, a Ru
 raised.  `load()` never builds; build with `python image-search-engine-for-historical-research_amd/build.py`
 or `__graft_entry__.build()`.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -364,12 +365,114 @@ def allow_ranges(ranges, n, row_offset=0):
     return allow_bitmap(mask, n)
 
 
-class Gallery:
-    """One gallery row shard resident on one MI355X (a `mi_gallery` handle)."""
+def _allow_words(allow, n, row_offset):
+    """The host words of `allow` (anything allow_bitmap takes) as the library reads them, None for allow None.  An empty bitmap
+    (n = 0) becomes one zero word: the library wants a pointer all the same."""
+    if allow is None:
+        return None
+    bits = np.asarray(allow_bitmap(allow, n, row_offset))
+    return np.zeros(1, "<u8") if bits.size == 0 else bits
+
+
+def _resolve_allow(allow, allow_ptr, n, row_offset):
+    """The allow arguments of a host-ABI search -> (keepalive, c_void_p | None, memspace): the words of `allow` on the host
+    (keepalive owns them), the device bitmap at allow_ptr, or no bitmap.  Raises ValueError when both are given."""
+    if allow is not None and allow_ptr is not None:
+        raise ValueError("give at most one of allow and allow_ptr")
+    if allow_ptr is not None:
+        return None, C.c_void_p(int(allow_ptr)), MI_DEVICE
+    bits = _allow_words(allow, n, row_offset)
+    return bits, None if bits is None else C.c_void_p(bits.ctypes.data), MI_HOST
+
+
+def _upload_allow(bits, tdev):
+    """Host allow words -> int64 tensor on the torch device `tdev` (None stays None)."""
+    import torch
+    return None if bits is None else torch.from_numpy(np.ascontiguousarray(bits).view(np.int64)).to(tdev)
+
+
+def _range_capacity(nq, max_results):
+    """First capacity of a range search: max_results, by default Q * 1024."""
+    return int(max_results) if max_results is not None else nq * 1024
+
+
+def _range_call(lock, call, nq, max_results, dtype):
+    """The capacity protocol of the host range searches: `call(cap, lims, idx, val, secs)` -> rc under `lock`, once more with
+    exactly lims[-1] when the first capacity was too small -> (lims int64 [nq+1], idx int64, val `dtype`, seconds)."""
+    cap = _range_capacity(nq, max_results)
+    lims = np.zeros(nq + 1, dtype=np.int64)
+    secs = C.c_double()
+    with lock:
+        for attempt in range(2):
+            idx = np.empty(cap, dtype=np.int64)
+            val = np.empty(cap, dtype=dtype)
+            rc = call(cap, lims.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p),
+                      C.byref(secs))
+            if rc != MI_ERR_CAPACITY or attempt == 1:
+                break
+            cap = int(lims[-1])
+        check(rc)
+    total = int(lims[-1])
+    return lims, idx[:total], val[:total], secs.value
+
+
+def _hbm_bytes(info, nouts):
+    """The hbm_bytes property of a handle class: the last output of the library's `info`, behind `nouts` outputs not asked for."""
+    def hbm_bytes(self):
+        hb = C.c_int64()
+        check(getattr(load(), info)(self._h, *(None,) * nouts, hb))
+        return hb.value
+    return property(hbm_bytes)
+
+
+class _Closing:
+    """`with` support and a __del__ that never raises, for a class with a close()."""
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Handle(_Closing):
+    """Owner of one library handle: `_h` (None once closed), the lock that serialises the calls on it (a handle is not
+    re-entrant: Flask threads in online.py) and close() through the destroy function the class names."""
+    _DESTROY = None
 
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
-        self._lock = threading.Lock()      # the handle is not re-entrant (Flask threads in online.py)
+        self._lock = threading.Lock()
+
+    def close(self):
+        """Destroys the handle; closing twice is fine.  A destroy the library refuses (mi_gallery_destroy while an online chain
+        is built on the gallery) raises RuntimeError and the handle stays valid."""
+        if self._h is not None and self._h.value:
+            check(getattr(load(), self._DESTROY)(self._h))
+            self._h = None
+
+    def _topk(self, nq, k, dtypes, call):
+        """A top-k call of the host ABI: allocates ids int64 [nq, k] and one value array [nq, k] per dtype, makes
+        `call(ids, *values, seconds)` -> rc on their addresses under the lock -> (ids, *values, seconds)."""
+        outs = [np.empty((nq, k), dtype=t) for t in (np.int64, *dtypes)]
+        secs = C.c_double()
+        with self._lock:
+            check(call(*[o.ctypes.data for o in outs], C.byref(secs)))
+        return (*outs, secs.value)
+
+
+class Gallery(_Handle):
+    """One gallery row shard resident on one MI355X (a `mi_gallery` handle)."""
+    _DESTROY = "mi_gallery_destroy"
+
+    def __init__(self, handle):
+        super().__init__(handle)
         n, d = C.c_int64(), C.c_int32()
         nm, dev = C.c_int32(), C.c_int32()
         off, hb = C.c_int64(), C.c_int64()
@@ -499,34 +602,20 @@ class Gallery:
     def save(self, path):
         check(load().mi_gallery_save(self._h, os.fsencode(path)))
 
-    def close(self):
-        """mi_gallery_destroy.  Refused (RuntimeError, the handle stays valid) while an online chain is built on the gallery."""
-        if self._h is not None and self._h.value:
-            rc = load().mi_gallery_destroy(self._h)
-            if rc:
-                check(rc)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # ---- host API
-    def search(self, queries, k):
-        """-> (idx int64 [Q,k], scores float32 [Q,k], seconds)."""
-        a, code, rs, cs = _strided(queries)
+    def _queries(self, q):
+        """(array, dtype code, row stride, col stride) of queries [Q, d], _strided's; raises ValueError on another d."""
+        a, code, rs, cs = _strided(q)
         if a.shape[1] != self.d:
             raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        return a, code, rs, cs
+
+    def search(self, queries, k):
+        """-> (idx int64 [Q,k], scores float32 [Q,k], seconds)."""
+        a, code, rs, cs = self._queries(queries)
         nq = a.shape[0]
-        idx = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_knn_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
-                                       idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p), C.byref(secs)))
-        return idx, sc, secs.value
+        return self._topk(nq, k, (np.float32,), lambda idx, sc, secs: load().mi_knn_search(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, idx, sc, secs))
 
     def search_filtered(self, queries, k, allow=None, allow_ptr=None):
         """Exact top-k over the rows `allow` admits (anything allow_bitmap takes: bool mask, global ids, AllowBits words) or,
@@ -535,62 +624,33 @@ class Gallery:
         -inf.  Ties go to the lower id; every score is the one `search` gives that row."""
         if (allow is None) == (allow_ptr is None):
             raise ValueError("give exactly one of allow and allow_ptr")
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         nq = a.shape[0]
-        if allow is not None:
-            bits = allow_bitmap(allow, self.n, self.row_offset)
-            bits_p, memspace = C.c_void_p(bits.ctypes.data), MI_HOST
-        else:
-            bits, bits_p, memspace = None, C.c_void_p(int(allow_ptr)), MI_DEVICE
-        idx = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        secs = C.c_double()
+        bits, bits_p, memspace = _resolve_allow(allow, allow_ptr, self.n, self.row_offset)
         info = FilterInfo()
-        with self._lock:
-            check(load().mi_knn_search_filtered(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, int(k), bits_p,
-                                                memspace, idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
-                                                C.byref(info), C.byref(secs)))
-        return idx, sc, secs.value, info.as_dict()
+        idx, sc, secs = self._topk(nq, k, (np.float32,), lambda idx, sc, secs: load().mi_knn_search_filtered(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, int(k), bits_p, memspace, idx, sc, C.byref(info), secs))
+        return idx, sc, secs, info.as_dict()
 
     def search_l2(self, queries, k, allow=None):
         """Exact squared-L2 top-k of a gallery built by l2_from_host -> (ids int64 [Q,k], dist float32 [Q,k], dist64 float64
         [Q,k], info dict, seconds): distances ascending, ties to the lower id, fewer than k rows -> ids -1, distances +inf.
         allow: anything allow_bitmap takes (bool mask, global ids, AllowBits words) restricts the search to those rows."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         nq, k = a.shape[0], int(k)
-        bits = None if allow is None else allow_bitmap(allow, self.n, self.row_offset)
-        idx = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
-        dist64 = np.empty((nq, k), dtype=np.float64)
-        secs = C.c_double()
+        bits, bits_p, memspace = _resolve_allow(allow, None, self.n, self.row_offset)
         info = FilterInfo()
-        with self._lock:
-            check(load().mi_knn_search_l2(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
-                                          None if bits is None else C.c_void_p(bits.ctypes.data), MI_HOST,
-                                          idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
-                                          dist64.ctypes.data_as(C.c_void_p), C.byref(info), C.byref(secs)))
-        return idx, dist, dist64, info.as_dict(), secs.value
+        idx, dist, dist64, secs = self._topk(nq, k, (np.float32, np.float64), lambda idx, dist, dist64, secs: load().mi_knn_search_l2(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, bits_p, memspace, idx, dist, dist64, C.byref(info), secs))
+        return idx, dist, dist64, info.as_dict(), secs
 
     def dense64_search_l2(self, queries, k):
         """Every direct-form float64 distance of the gallery + exact top-k (no threshold logic): the independent checker of
         search_l2.  -> (ids int64 [Q,k], dist float32 [Q,k], dist64 float64 [Q,k], seconds)."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         nq, k = a.shape[0], int(k)
-        idx = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
-        dist64 = np.empty((nq, k), dtype=np.float64)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_knn_dense64_search_l2(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
-                                                  idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
-                                                  dist64.ctypes.data_as(C.c_void_p), C.byref(secs)))
-        return idx, dist, dist64, secs.value
+        return self._topk(nq, k, (np.float32, np.float64), lambda idx, dist, dist64, secs: load().mi_knn_dense64_search_l2(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, idx, dist, dist64, secs))
 
     def search_l2_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, dist64_ptr=None, stream=None):
         check(load().mi_knn_search_l2_device(self._h, C.c_void_p(q_ptr), nq, k, C.c_void_p(idx_ptr), C.c_void_p(dist_ptr),
@@ -603,23 +663,14 @@ class Gallery:
         An L2 gallery gives direct-form squared distances ascending (the bits of search_l2), any other gallery inner products
         against the stored row descending, the query used as given.  Fewer than k distinct candidates: ids -1, values +inf /
         -inf.  1 <= kc <= 8192, 1 <= k <= kc."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         c = np.asarray(cand)
         if c.ndim != 2 or c.shape[0] != a.shape[0] or c.dtype == np.bool_ or not np.issubdtype(c.dtype, np.integer):
             raise ValueError("cand must be an integer array [Q = %d, kc] (got %s %s)" % (a.shape[0], c.dtype, c.shape))
         c = np.ascontiguousarray(c, dtype=np.int64)
         nq, kc, k = a.shape[0], c.shape[1], int(k)
-        idx = np.empty((nq, k), dtype=np.int64)
-        val = np.empty((nq, k), dtype=np.float32)
-        val64 = np.empty((nq, k), dtype=np.float64)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_refine(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, C.c_void_p(c.ctypes.data), kc, kc, k,
-                                   idx.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p),
-                                   val64.ctypes.data_as(C.c_void_p), C.byref(secs)))
-        return idx, val, val64, secs.value
+        return self._topk(nq, k, (np.float32, np.float64), lambda idx, val, val64, secs: load().mi_refine(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, C.c_void_p(c.ctypes.data), kc, kc, k, idx, val, val64, secs))
 
     def refine_device(self, q_ptr, nq, cand_ptr, kc, k, idx_ptr, val_ptr=None, val64_ptr=None, stream=None, cand_stride=None):
         """mi_refine_device: q_ptr packed float32 [nq][d], cand_ptr int64 [nq][cand_stride or kc] on the device; enqueued on
@@ -633,27 +684,12 @@ class Gallery:
         (lims int64 [Q+1], idx int64 [lims[-1]], scores float32 [lims[-1]], seconds).  The hits of query i are
         idx/scores[lims[i]:lims[i+1]], ordered by (score desc, id asc).  The first call's capacity is `max_results`
         (default Q * 1024); if the hits do not fit, the call is made once more with exactly lims[-1]."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         nq = a.shape[0]
-        cap = int(max_results) if max_results is not None else nq * 1024
-        lims = np.zeros(nq + 1, dtype=np.int64)
-        secs = C.c_double()
-        with self._lock:
-            lib = load()
-            for attempt in range(2):
-                idx = np.empty(cap, dtype=np.int64)
-                sc = np.empty(cap, dtype=np.float32)
-                rc = lib.mi_range_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, float(min_score), cap,
-                                         lims.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p),
-                                         sc.ctypes.data_as(C.c_void_p), C.byref(secs))
-                if rc != MI_ERR_CAPACITY or attempt == 1:
-                    break
-                cap = int(lims[-1])
-            check(rc)
-        total = int(lims[-1])
-        return lims, idx[:total], sc[:total], secs.value
+        return _range_call(
+            self._lock, lambda cap, lims, idx, sc, secs: load().mi_range_search(
+                self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, float(min_score), cap, lims, idx, sc, secs),
+            nq, max_results, np.float32)
 
     def aqe_search(self, ranks, k_qe, w, k, eps=1e-6, return_qexp=False):
         """ranks [K_in, Q] int64 (any strides) -> (idx [Q,k], scores [Q,k], qexp [Q,D] f64 | None, seconds)."""
@@ -663,54 +699,30 @@ class Gallery:
         if any(s % 8 or s < 0 for s in r.strides):
             r = np.ascontiguousarray(r)
         nq = r.shape[1]
-        idx = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
         qx = np.empty((nq, self.d), dtype=np.float64) if return_qexp else None
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_aqe_search(self._h, r.ctypes.data_as(C.c_void_p), r.strides[0] // 8, r.strides[1] // 8,
-                                       nq, k_qe, float(w), float(eps), k, idx.ctypes.data_as(C.c_void_p),
-                                       sc.ctypes.data_as(C.c_void_p),
-                                       qx.ctypes.data_as(C.c_void_p) if return_qexp else None, C.byref(secs)))
-        return idx, sc, qx, secs.value
+        idx, sc, secs = self._topk(nq, k, (np.float32,), lambda idx, sc, secs: load().mi_aqe_search(
+            self._h, r.ctypes.data_as(C.c_void_p), r.strides[0] // 8, r.strides[1] // 8, nq, k_qe, float(w), float(eps), k, idx, sc,
+            qx.ctypes.data_as(C.c_void_p) if return_qexp else None, secs))
+        return idx, sc, qx, secs
 
     def dense64_search(self, queries, k):
         """Every score of the gallery in float64 + exact top-k (no threshold logic): the independent checker of the filtered
         search.  -> (idx int64 [Q,k], scores float32 [Q,k], scores float64 [Q,k], seconds)."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         nq = a.shape[0]
-        idx = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        sc64 = np.empty((nq, k), dtype=np.float64)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_knn_dense64_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
-                                               idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
-                                               sc64.ctypes.data_as(C.c_void_p), C.byref(secs)))
-        return idx, sc, sc64, secs.value
+        return self._topk(nq, k, (np.float32, np.float64), lambda idx, sc, sc64, secs: load().mi_knn_dense64_search(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, idx, sc, sc64, secs))
 
     def dense_search(self, queries, k):
         """Exact f32 inner-product top-k for large k (k <= 4096): -> (idx [Q,k], scores [Q,k], seconds)."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         nq = a.shape[0]
-        idx = np.empty((nq, k), dtype=np.int64)
-        sc = np.empty((nq, k), dtype=np.float32)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_knn_dense_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k,
-                                             idx.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
-                                             C.byref(secs)))
-        return idx, sc, secs.value
+        return self._topk(nq, k, (np.float32,), lambda idx, sc, secs: load().mi_knn_dense_search(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, idx, sc, secs))
 
     def rank_all(self, queries, query_norm=-1, return_scores=False):
         """Full-length ranking: -> (idx int64 [Q,N][, scores float32 [Q,N]], seconds)."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         nq = a.shape[0]
         idx = np.empty((nq, self.n), dtype=np.int64)
         sc = np.empty((nq, self.n), dtype=np.float32) if return_scores else None
@@ -723,9 +735,7 @@ class Gallery:
 
     def rank_prefix(self, queries, keep, query_norm=-1, return_scores=False):
         """The first `keep` columns of the full-length ranking: -> (idx int64 [Q,keep][, scores float32 [Q,keep]], seconds)."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         nq, keep = a.shape[0], int(keep)
         idx = np.empty((nq, keep), dtype=np.int64)
         sc = np.empty((nq, keep), dtype=np.float32) if return_scores else None
@@ -739,9 +749,7 @@ class Gallery:
     def rank_positions(self, queries, row_ids, query_norm=-1):
         """Zero-based positions of the listed rows in every query's full ranking (score desc, idx asc), counted on the
         device.  row_ids int64 [Q, m] of global ids, -1 = padding -> position -1.  Returns int64 [Q, m]."""
-        a, code, rs, cs = _strided(queries)
-        if a.shape[1] != self.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.d))
+        a, code, rs, cs = self._queries(queries)
         ids = np.ascontiguousarray(row_ids, dtype=np.int64)
         if ids.ndim != 2 or ids.shape[0] != a.shape[0]:
             raise ValueError("row_ids must be [Q, m]")
@@ -990,15 +998,14 @@ def _graph_table(n, table, entries):
     return np.ascontiguousarray(t, dtype=np.int32), np.ascontiguousarray(e, dtype=np.int32)
 
 
-class _GraphBase:
+class _GraphBase(_Handle):
     """What GraphIndex and PQGraphIndex share: the handle of a `<_PREFIX>*` graph over an owner index (kept as the attribute
     _OWNER names, which must outlive the graph), its table and its entry rows."""
     _PREFIX = _OWNER = None
     _INFO_EXTRA = ()                   # arguments of <_PREFIX>_info behind n, R and ne
 
     def __init__(self, handle, owner):
-        self._h = C.c_void_p(handle)
-        self._lock = threading.Lock()
+        super().__init__(handle)
         setattr(self, self._OWNER, owner)
         n, R, ne = C.c_int64(), C.c_int32(), C.c_int32()
         check(self._fn("info")(self._h, n, R, ne, *self._INFO_EXTRA))
@@ -1045,23 +1052,6 @@ class _GraphBase:
             check(self._fn("get_entries")(self._h, C.c_void_p(out.ctypes.data)))
         return out
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            check(self._fn("destroy")(self._h))
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class GraphIndex(_GraphBase):
     """A neighbour graph over the rows of a Gallery (a `mi_graph` handle): best-first search from a set of entry
@@ -1070,27 +1060,19 @@ class GraphIndex(_GraphBase):
     float64 inner products against the stored row on any other), the order is (value best first, id ascending).  The gallery
     must outlive the index; after gallery.append* / gallery.remove a search raises (build a new graph)."""
 
-    _PREFIX, _OWNER = "mi_graph", "gallery"
+    _PREFIX, _OWNER, _DESTROY = "mi_graph", "gallery", "mi_graph_destroy"
 
     def search(self, q, k, ef=None, return_visited=False, return_values64=False):
         """-> (ids int64 [Q, k], values float32 [Q, k], seconds); ef (the size of the candidate list W) defaults to max(k, 64),
         1 <= k <= ef <= 2048.  Fewer than k rows reached: ids -1, values +inf (L2) / -inf.  return_values64: the float64 values
         in place of their float32 cast; return_visited: int32 [Q], the rows evaluated per query, appended to the tuple."""
         k, ef = _graph_search_shape(k, ef)
-        a, code, rs, cs = _strided(q)
-        if a.shape[1] != self.gallery.d:
-            raise ValueError("query dimension %d != gallery dimension %d" % (a.shape[1], self.gallery.d))
+        a, code, rs, cs = self.gallery._queries(q)
         nq = a.shape[0]
-        idx = np.empty((nq, k), dtype=np.int64)
-        val = np.empty((nq, k), dtype=np.float32)
-        val64 = np.empty((nq, k), dtype=np.float64)
         vis = np.empty(nq, dtype=np.int32)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_graph_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, ef, C.c_void_p(idx.ctypes.data),
-                                         C.c_void_p(val.ctypes.data), C.c_void_p(val64.ctypes.data), C.c_void_p(vis.ctypes.data),
-                                         C.byref(secs)))
-        out = (idx, val64 if return_values64 else val, secs.value)
+        idx, val, val64, secs = self._topk(nq, k, (np.float32, np.float64), lambda idx, val, val64, secs: load().mi_graph_search(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, ef, idx, val, val64, C.c_void_p(vis.ctypes.data), secs))
+        out = (idx, val64 if return_values64 else val, secs)
         return out + (vis,) if return_visited else out
 
     def search_device(self, q_ptr, nq, k, idx_ptr, ef=None, val_ptr=None, val64_ptr=None, visited_ptr=None, stream=None):
@@ -1108,11 +1090,19 @@ def refine_kc(k, k_factor, n):
     return max(k, min(k * f, int(n), REFINE_MAX_KC))
 
 
-def _search_refined(rows, q, k, kc, allow_bits, search_device, device):
-    """The refine= path of the index searches: q float32 [Q, d] host rows; search_device(q_dev, nq, kc, cand_ptr, allow_ptr,
-    stream) enqueues the index's own device search for kc ids per query; rows.refine_device follows on the same stream, and only
-    the final k ids and exact values come back -> (ids int64 [Q,k], val float32 [Q,k], seconds)."""
+_NO_ALLOW = (None, None, MI_HOST)          # what _resolve_allow gives a search without an allow list
+
+
+def _search_refined(rows, q, k, kc, allow, device, lock, search_device, stage=None, **kw):
+    """The refine= path of the index searches: q float32 [Q, d] host rows, allow what _resolve_allow returned.  The index's own
+    search_device(q_ptr, nq, kc, cand_ptr, stream=, allow_ptr= where there are allow words, **kw) is enqueued under `lock`
+    (None: no lock) for kc ids per query; rows.refine_device follows on the same stream, and only the final k ids and exact
+    values come back -> (ids int64 [Q,k], val float32 [Q,k], seconds).  An index that does not search the float32 rows as they
+    are gives stage(xq, stream) -> (the device tensor its search reads as queries, {keyword: device tensor passed as pointer})."""
     import torch
+    bits, _, memspace = allow
+    if memspace == MI_DEVICE:
+        raise ValueError("refine takes allow, not allow_ptr")
     if not isinstance(rows, Gallery):
         raise ValueError("refine must be a Gallery that holds the raw rows (got %s)" % type(rows).__name__)
     a = np.ascontiguousarray(q, dtype=np.float32)
@@ -1127,30 +1117,29 @@ def _search_refined(rows, q, k, kc, allow_bits, search_device, device):
     t0 = time.perf_counter()
     stream = torch.cuda.current_stream(tdev).cuda_stream
     xq = torch.from_numpy(a).to(tdev)
-    bits_dev = None if allow_bits is None else torch.from_numpy(np.ascontiguousarray(allow_bits).view(np.int64)).to(tdev)
+    bits_dev = _upload_allow(bits, tdev)
     cand = torch.empty((nq, kc), dtype=torch.int64, device=tdev)
     idx = torch.empty((nq, k), dtype=torch.int64, device=tdev)
     val = torch.empty((nq, k), dtype=torch.float32, device=tdev)
-    search_device(xq, nq, kc, cand.data_ptr(), None if bits_dev is None else bits_dev.data_ptr(), stream)
+    q_dev, staged = (xq, {}) if stage is None else stage(xq, stream)
+    kw.update((name, t.data_ptr()) for name, t in staged.items())
+    if bits_dev is not None:
+        kw["allow_ptr"] = bits_dev.data_ptr()
+    with lock or contextlib.nullcontext():
+        search_device(q_dev.data_ptr(), nq, kc, cand.data_ptr(), stream=stream, **kw)
     with rows._lock:
         rows.refine_device(xq.data_ptr(), nq, cand.data_ptr(), kc, k, idx.data_ptr(), val_ptr=val.data_ptr(), stream=stream)
         ids, vv = idx.cpu().numpy(), val.cpu().numpy()           # (synchronises with the stream the work is on)
     return ids, vv, time.perf_counter() - t0
 
 
-def _allow_words(allow, n, row_offset):
-    if allow is None:
-        return None
-    bits = np.asarray(allow_bitmap(allow, n, row_offset))
-    return bits if bits.size else np.zeros(1, "<u8")
-
-
-class BinaryGallery:
+class BinaryGallery(_Handle):
     """Binary index on one MI355X (a `mi_hamming` handle): exact Hamming top-k on packed codes, ties to the lower id."""
+    _DESTROY = "mi_hamming_destroy"
+    hbm_bytes = _hbm_bytes("mi_hamming_info", 5)
 
     def __init__(self, handle):
-        self._h = C.c_void_p(handle)
-        self._lock = threading.Lock()
+        super().__init__(handle)
         n, nbits, dev, off, cap, hb = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
         check(load().mi_hamming_info(self._h, n, nbits, dev, off, cap, hb))
         self.n, self.nbits, self.device, self.row_offset, self.capacity = n.value, nbits.value, dev.value, off.value, cap.value
@@ -1180,12 +1169,6 @@ class BinaryGallery:
         check(load().mi_hamming_create(None, 0, int(nbits), int(nbits) // 8, MI_HOST, device, row_offset, int(capacity),
                                        C.byref(h)))
         return cls(h.value)
-
-    @property
-    def hbm_bytes(self):
-        hb = C.c_int64()
-        check(load().mi_hamming_info(self._h, None, None, None, None, None, hb))
-        return hb.value
 
     def append(self, codes):
         a, stride = _code_rows(codes, self.nbits // 8)
@@ -1218,60 +1201,20 @@ class BinaryGallery:
         are its exact float32 values."""
         a, stride = _code_rows(qcodes, self.nbits // 8)
         nq, k = a.shape[0], int(k)
-        if allow is not None and allow_ptr is not None:
-            raise ValueError("give at most one of allow and allow_ptr")
+        resolved = bits, bits_p, memspace = _resolve_allow(allow, allow_ptr, self.n, self.row_offset)
         if refine is not None:
             import torch
             if refine_queries is None or np.shape(refine_queries)[0] != nq:
                 raise ValueError("refine: give refine_queries [Q = %d, d], the raw queries behind the codes" % nq)
-            if allow_ptr is not None:
-                raise ValueError("refine takes allow, not allow_ptr")
             packed = np.ascontiguousarray(a)
-
-            def dev(xq, m, kc, cand_ptr, bits_ptr, stream):
-                qc = torch.from_numpy(packed).to(xq.device)
-                with self._lock:
-                    self.search_device(qc.data_ptr(), m, kc, cand_ptr, allow_ptr=bits_ptr, stream=stream)
-            return _search_refined(refine, refine_queries, k, refine_kc(k, k_factor, self.n),
-                                   _allow_words(allow, self.n, self.row_offset), dev, self.device)
-        bits, bits_p, memspace = None, None, MI_HOST
-        if allow is not None:
-            bits = allow_bitmap(allow, self.n, self.row_offset)
-            if bits.size == 0:
-                bits = np.zeros(1, "<u8")
-            bits_p = C.c_void_p(bits.ctypes.data)
-        elif allow_ptr is not None:
-            bits_p, memspace = C.c_void_p(int(allow_ptr)), MI_DEVICE
-        idx = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.int32)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_hamming_search(self._h, C.c_void_p(a.ctypes.data), nq, stride, k, bits_p, memspace,
-                                           idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p), C.byref(secs)))
-        return idx, dist, secs.value
+            return _search_refined(refine, refine_queries, k, refine_kc(k, k_factor, self.n), resolved, self.device, self._lock,
+                                   self.search_device, stage=lambda xq, stream: (torch.from_numpy(packed).to(xq.device), {}))
+        return self._topk(nq, k, (np.int32,), lambda idx, dist, secs: load().mi_hamming_search(
+            self._h, C.c_void_p(a.ctypes.data), nq, stride, k, bits_p, memspace, idx, dist, secs))
 
     def search_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, allow_ptr=None, stream=None):
         check(load().mi_hamming_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(allow_ptr),
                                               C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), C.c_void_p(stream)))
-
-    def _range_call(self, call, nq, max_results):
-        """The capacity protocol of Gallery.range_search: `call(cap, lims, idx, dist, secs)` -> rc, once more with exactly
-        lims[-1] when the first capacity (max_results, default Q * 1024) was too small."""
-        cap = int(max_results) if max_results is not None else nq * 1024
-        lims = np.zeros(nq + 1, dtype=np.int64)
-        secs = C.c_double()
-        with self._lock:
-            for attempt in range(2):
-                idx = np.empty(cap, dtype=np.int64)
-                dist = np.empty(cap, dtype=np.int32)
-                rc = call(cap, lims.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
-                          C.byref(secs))
-                if rc != MI_ERR_CAPACITY or attempt == 1:
-                    break
-                cap = int(lims[-1])
-            check(rc)
-        total = int(lims[-1])
-        return lims, idx[:total], dist[:total], secs.value
 
     def range_search(self, qcodes, radius, allow=None, max_results=None, allow_ptr=None):
         """Every admitted row within `radius` bits (inclusive) of each query ->
@@ -1280,19 +1223,12 @@ class BinaryGallery:
         search().  The first call's capacity is `max_results` (default Q * 1024); if the hits do not fit, the call is made once
         more with exactly lims[-1]."""
         a, stride = _code_rows(qcodes, self.nbits // 8)
-        if allow is not None and allow_ptr is not None:
-            raise ValueError("give at most one of allow and allow_ptr")
-        bits, bits_p, memspace = None, None, MI_HOST
-        if allow is not None:
-            bits = _allow_words(allow, self.n, self.row_offset)
-            bits_p = C.c_void_p(bits.ctypes.data)
-        elif allow_ptr is not None:
-            bits_p, memspace = C.c_void_p(int(allow_ptr)), MI_DEVICE
+        bits, bits_p, memspace = _resolve_allow(allow, allow_ptr, self.n, self.row_offset)
         lib = load()
-        return self._range_call(
-            lambda cap, lims, idx, dist, secs: lib.mi_hamming_range_search(
+        return _range_call(
+            self._lock, lambda cap, lims, idx, dist, secs: lib.mi_hamming_range_search(
                 self._h, C.c_void_p(a.ctypes.data), a.shape[0], stride, int(radius), bits_p, memspace, cap, lims, idx, dist, secs),
-            a.shape[0], max_results)
+            a.shape[0], max_results, np.int32)
 
     def range_search_device(self, q_ptr, nq, radius, max_results, lims_ptr, idx_ptr, dist_ptr=None, allow_ptr=None, stream=None):
         """Enqueued on `stream` without synchronising (mi_hamming_range_search_device): lims [nq + 1] int64, ids / dist
@@ -1306,10 +1242,10 @@ class BinaryGallery:
         seconds): the hits of row row0 + i are the rows j > row0 + i within `radius` bits, by (distance asc, j asc)
         (mi_hamming_self_range).  Capacity as in range_search."""
         lib = load()
-        return self._range_call(
-            lambda cap, lims, idx, dist, secs: lib.mi_hamming_self_range(self._h, int(row0), int(nrows), int(radius), cap, lims,
-                                                                         idx, dist, secs),
-            int(nrows), max_results)
+        return _range_call(
+            self._lock, lambda cap, lims, idx, dist, secs: lib.mi_hamming_self_range(self._h, int(row0), int(nrows), int(radius), cap,
+                                                                                     lims, idx, dist, secs),
+            int(nrows), max_results, np.int32)
 
     def get_codes(self, row0=0, nrows=None):
         nrows = self.n - row0 if nrows is None else int(nrows)
@@ -1317,17 +1253,6 @@ class BinaryGallery:
         with self._lock:
             check(load().mi_hamming_get_codes(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
         return out
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            check(load().mi_hamming_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 LSH_MAX_BITS, LSH_MAX_DIM = 4096, 4096
@@ -1389,7 +1314,7 @@ def lsh_encode_device(x_ptr, n, d, r_ptr, nbits, out_ptr, thr_ptr=None, dtype=MI
                                       int(nbits // 8 if out_row_stride is None else out_row_stride), C.c_void_p(stream)))
 
 
-class LSHIndex:
+class LSHIndex(_Closing):
     """LSH index on one MI355X, faiss IndexLSH(d, nbits) without trained thresholds: a BinaryGallery of the codes
     bit j = (x . R[j] >= thresholds[j]) plus R float64 [nbits, d] and the thresholds on the device.  Rows are encoded straight
     into the gallery's code storage; a search encodes its queries on the device and runs the exact Hamming top-k there, by
@@ -1491,6 +1416,16 @@ class LSHIndex:
             out[r:r + blk.shape[0]] = codes.cpu().numpy()
         return out
 
+    def _encode_on_device(self, a, code, stream):
+        """Host rows [rows, d] of dtype `code` (or a tensor of them already on the device) -> (the device rows, their codes uint8
+        [rows, nbits / 8] on the device), the encoding enqueued on `stream`."""
+        import torch
+        xq = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(self._tdev)
+        qcodes = torch.empty((xq.shape[0], self.nbits // 8), dtype=torch.uint8, device=self._tdev)
+        lsh_encode_device(xq.data_ptr(), xq.shape[0], self.d, self._R.data_ptr(), self.nbits, qcodes.data_ptr(),
+                          thr_ptr=self._thr_ptr(), dtype=code, stream=stream)
+        return xq, qcodes
+
     def search(self, q, k, allow=None, refine=None, k_factor=1):
         """refine=<Gallery of the raw rows>: the Hamming search takes refine_kc(k, k_factor, n) ids, the gallery re-ranks them on
         the device (Gallery.refine) and the distances returned are its exact float32 values.  Otherwise:
@@ -1503,31 +1438,19 @@ class LSHIndex:
         nq, k = a.shape[0], int(k)
         if not 1 <= k <= 2048:
             raise ValueError("k must be in [1, 2048]")
-        bits = None
-        if allow is not None:
-            bits = np.asarray(allow_bitmap(allow, self.gallery.n, self.gallery.row_offset))
-            if bits.size == 0:
-                bits = np.zeros(1, "<u8")
+        bits = _allow_words(allow, self.gallery.n, self.gallery.row_offset)
         if refine is not None:
-            a32 = np.ascontiguousarray(a, dtype=np.float32)
-
-            def dev(xq, m, kc, cand_ptr, bits_ptr, stream):
-                qcodes = torch.empty((m, self.nbits // 8), dtype=torch.uint8, device=self._tdev)
-                lsh_encode_device(xq.data_ptr(), m, self.d, self._R.data_ptr(), self.nbits, qcodes.data_ptr(), thr_ptr=self._thr_ptr(),
-                                  dtype=MI_F32, stream=stream)
-                self.gallery.search_device(qcodes.data_ptr(), m, kc, cand_ptr, allow_ptr=bits_ptr, stream=stream)
-            return _search_refined(refine, a32, k, refine_kc(k, k_factor, self.gallery.n), bits, dev, self.device)
+            return _search_refined(refine, np.ascontiguousarray(a, dtype=np.float32), k, refine_kc(k, k_factor, self.gallery.n),
+                                   (bits, None, MI_HOST), self.device, None, self.gallery.search_device,
+                                   stage=lambda xq, stream: (self._encode_on_device(xq, MI_F32, stream)[1], {}))
         if nq == 0:
             return np.empty((0, k), np.int64), np.empty((0, k), np.int32), 0.0
         t0 = time.perf_counter()
         stream = self._stream()
-        xq = torch.from_numpy(np.ascontiguousarray(a)).to(self._tdev)
-        bits_dev = None if bits is None else torch.from_numpy(bits.view(np.int64)).to(self._tdev)
-        qcodes = torch.empty((nq, self.nbits // 8), dtype=torch.uint8, device=self._tdev)
+        xq, qcodes = self._encode_on_device(a, code, stream)
+        bits_dev = _upload_allow(bits, self._tdev)
         idx = torch.empty((nq, k), dtype=torch.int64, device=self._tdev)
         dist = torch.empty((nq, k), dtype=torch.int32, device=self._tdev)
-        lsh_encode_device(xq.data_ptr(), nq, self.d, self._R.data_ptr(), self.nbits, qcodes.data_ptr(), thr_ptr=self._thr_ptr(),
-                          dtype=code, stream=stream)
         self.gallery.search_device(qcodes.data_ptr(), nq, k, idx.data_ptr(), dist_ptr=dist.data_ptr(),
                                    allow_ptr=None if bits_dev is None else bits_dev.data_ptr(), stream=stream)
         ids, dd = idx.cpu().numpy(), dist.cpu().numpy()              # (synchronises with the stream the work is on)
@@ -1548,13 +1471,10 @@ class LSHIndex:
         bits = _allow_words(allow, self.gallery.n, self.gallery.row_offset)
         t0 = time.perf_counter()
         stream = self._stream()
-        xq = torch.from_numpy(np.ascontiguousarray(a)).to(self._tdev)
-        bits_dev = None if bits is None else torch.from_numpy(bits.view(np.int64)).to(self._tdev)
-        qcodes = torch.empty((nq, self.nbits // 8), dtype=torch.uint8, device=self._tdev)
+        xq, qcodes = self._encode_on_device(a, code, stream)
+        bits_dev = _upload_allow(bits, self._tdev)
         lims = torch.empty(nq + 1, dtype=torch.int64, device=self._tdev)
-        lsh_encode_device(xq.data_ptr(), nq, self.d, self._R.data_ptr(), self.nbits, qcodes.data_ptr(), thr_ptr=self._thr_ptr(),
-                          dtype=code, stream=stream)
-        cap = int(max_results) if max_results is not None else nq * 1024
+        cap = _range_capacity(nq, max_results)
         for attempt in range(2):
             idx = torch.empty(max(cap, 1), dtype=torch.int64, device=self._tdev)
             dist = torch.empty(max(cap, 1), dtype=torch.int32, device=self._tdev)
@@ -1576,18 +1496,6 @@ class LSHIndex:
         if self.gallery is not None:
             self.gallery.close()
             self.gallery = self._R = self._thr = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 PQ_MAX_BOOKS, PQ_MAX_WORDS, PQ_MAX_DIM = 64, 256, 4096
@@ -1727,11 +1635,9 @@ def pq_train_timing():
 
 def _remove_rows(index, name, rows):
     """Gallery.remove for a PQIndex / IVFPQIndex: the bitmap of `rows`, the call `name` of the library, `kept`, index.n."""
-    bits = allow_bitmap(rows, index.n, index.row_offset)
+    bits = _allow_words(rows, index.n, index.row_offset)      # (an empty index: one zero word)
     gone = np.unpackbits(np.ascontiguousarray(bits).view(np.uint8), bitorder="little")[:index.n].astype(np.bool_)
     kept = np.flatnonzero(~gone).astype(np.int64) + int(index.row_offset)
-    if bits.size == 0:
-        bits = np.zeros(1, "<u8")                               # an empty index: the library wants a pointer all the same
     removed = C.c_int64()
     with index._lock:
         check(getattr(load(), name)(index._h, C.c_void_p(bits.ctypes.data), MI_HOST, C.byref(removed)))
@@ -1741,12 +1647,13 @@ def _remove_rows(index, name, rows):
     return kept
 
 
-class PQIndex:
+class PQIndex(_Handle):
     """PQ index on one MI355X (a `mi_pq` handle): exact ADC top-k on product-quantized codes by (distance asc, id asc)."""
+    _DESTROY = "mi_pq_destroy"
+    hbm_bytes = _hbm_bytes("mi_pq_info", 7)
 
     def __init__(self, handle):
-        self._h = C.c_void_p(handle)
-        self._lock = threading.Lock()
+        super().__init__(handle)
         n, cap, off, hb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         d, m, ks, dev = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         check(load().mi_pq_info(self._h, n, d, m, ks, dev, off, cap, hb))
@@ -1798,12 +1705,6 @@ class PQIndex:
         idx.train_moved = moved
         idx.add(x)
         return idx
-
-    @property
-    def hbm_bytes(self):
-        hb = C.c_int64()
-        check(load().mi_pq_info(self._h, None, None, None, None, None, None, None, hb))
-        return hb.value
 
     @property
     def codebooks(self):
@@ -1861,32 +1762,11 @@ class PQIndex:
         them there (Gallery.refine; queries rounded to float32) and the distances returned are its exact float32 values."""
         a, code, rs, cs = self._rows(q)
         nq, k = a.shape[0], int(k)
-        if allow is not None and allow_ptr is not None:
-            raise ValueError("give at most one of allow and allow_ptr")
+        resolved = bits, bits_p, memspace = _resolve_allow(allow, allow_ptr, self.n, self.row_offset)
         if refine is not None:
-            if allow_ptr is not None:
-                raise ValueError("refine takes allow, not allow_ptr")
-
-            def dev(xq, m, kc, cand_ptr, bits_ptr, stream):
-                with self._lock:
-                    self.search_device(xq.data_ptr(), m, kc, cand_ptr, allow_ptr=bits_ptr, stream=stream)
-            return _search_refined(refine, a, k, refine_kc(k, k_factor, self.n), _allow_words(allow, self.n, self.row_offset), dev,
-                                   self.device)
-        bits, bits_p, memspace = None, None, MI_HOST
-        if allow is not None:
-            bits = allow_bitmap(allow, self.n, self.row_offset)
-            if bits.size == 0:
-                bits = np.zeros(1, "<u8")
-            bits_p = C.c_void_p(bits.ctypes.data)
-        elif allow_ptr is not None:
-            bits_p, memspace = C.c_void_p(int(allow_ptr)), MI_DEVICE
-        idx = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_pq_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, bits_p, memspace,
-                                      idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p), C.byref(secs)))
-        return idx, dist, secs.value
+            return _search_refined(refine, a, k, refine_kc(k, k_factor, self.n), resolved, self.device, self._lock, self.search_device)
+        return self._topk(nq, k, (np.float32,), lambda idx, dist, secs: load().mi_pq_search(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, bits_p, memspace, idx, dist, secs))
 
     def search_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, allow_ptr=None, stream=None):
         """q_ptr: packed float32 [nq][d] on the device; enqueued on `stream`, no synchronisation."""
@@ -1917,23 +1797,6 @@ class PQIndex:
             check(load().mi_pq_decode(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def close(self):
-        if self._h is not None and self._h.value:
-            check(load().mi_pq_destroy(self._h))
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 PQ_GRAPH_MAX_SHORTLIST = 2048     # a graph search returns at most ef <= 2048 rows: the longest shortlist refine= can ask for
 
@@ -1947,14 +1810,9 @@ class PQGraphIndex(_GraphBase):
     distances -- row i's query is its own reconstruction -- from the exhaustive search of the PQ index; from_neighbors takes
     GraphIndex.neighbors of a graph over the raw rows, for one."""
 
-    _PREFIX, _OWNER, _INFO_EXTRA = "mi_pq_graph", "pq", (None,)
-
-    @property
-    def hbm_bytes(self):
-        """Table, entries and the grow-only workspace of the searches (the PQ index counts its own)."""
-        hb = C.c_int64()
-        check(load().mi_pq_graph_info(self._h, None, None, None, hb))
-        return hb.value
+    _PREFIX, _OWNER, _INFO_EXTRA, _DESTROY = "mi_pq_graph", "pq", (None,), "mi_pq_graph_destroy"
+    # table, entries and the grow-only workspace of the searches (the PQ index counts its own)
+    hbm_bytes = _hbm_bytes("mi_pq_graph_info", 3)
 
     def search(self, q, k, ef=None, return_visited=False, refine=None, k_factor=1):
         """-> (ids int64 [Q, k], dist float32 [Q, k], seconds); ef (the size of the candidate list W) defaults to max(k, 64),
@@ -1970,20 +1828,10 @@ class PQGraphIndex(_GraphBase):
             if return_visited:
                 raise ValueError("return_visited is not available with refine")
             kc = min(refine_kc(k, k_factor, self.n), PQ_GRAPH_MAX_SHORTLIST)       # (k <= ef <= 2048: never below k)
-            efc = max(ef, kc)
-
-            def dev(xq, m, kcand, cand_ptr, bits_ptr, stream):
-                with self._lock:
-                    self.search_device(xq.data_ptr(), m, kcand, cand_ptr, ef=efc, stream=stream)
-            return _search_refined(refine, a, k, kc, None, dev, self.pq.device)
-        idx = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
+            return _search_refined(refine, a, k, kc, _NO_ALLOW, self.pq.device, self._lock, self.search_device, ef=max(ef, kc))
         vis = np.empty(nq, dtype=np.int32)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_pq_graph_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, ef, C.c_void_p(idx.ctypes.data),
-                                            C.c_void_p(dist.ctypes.data), C.c_void_p(vis.ctypes.data), C.byref(secs)))
-        out = (idx, dist, secs.value)
+        out = self._topk(nq, k, (np.float32,), lambda idx, dist, secs: load().mi_pq_graph_search(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, ef, idx, dist, C.c_void_p(vis.ctypes.data), secs))
         return out + (vis,) if return_visited else out
 
     def search_device(self, q_ptr, nq, k, idx_ptr, ef=None, dist_ptr=None, visited_ptr=None, stream=None):
@@ -2025,7 +1873,7 @@ def ivf_list_ids(lists, rows, nlist):
     return np.ascontiguousarray(a, dtype=np.uint8)
 
 
-class IVFPQIndex:
+class IVFPQIndex(_Handle):
     """IVF index over PQ codes on one MI355X (a `mi_ivfpq` handle): the exact ADC top-k of PQIndex.search over the rows whose
     list is one of a query's probed lists, by (distance asc, id asc).  by_residual=True at creation gives faiss's IndexIVFPQ
     default: a code quantizes double(x) - double(coarse[list]) and a query has one float64-summed table per probed list; the kind
@@ -2034,10 +1882,11 @@ class IVFPQIndex:
     carries `.coarse` [nlist, d] and `.codebooks` [M, Ks, L], float32 copies of the arrays it was created with -- the handle has no
     getter for them, and knn.ANN's callers and the tests need them to restate an answer; and `train()` is the training half of
     fit() as a classmethod of its own, which knn.ANN uses to train on a sample and add all rows."""
+    _DESTROY = "mi_ivfpq_destroy"
+    hbm_bytes = _hbm_bytes("mi_ivfpq_info", 8)
 
     def __init__(self, handle):
-        self._h = C.c_void_p(handle)
-        self._lock = threading.Lock()
+        super().__init__(handle)
         self._info()
         kind = C.c_int32()
         check(load().mi_ivfpq_is_residual(self._h, C.byref(kind)))
@@ -2144,12 +1993,6 @@ class IVFPQIndex:
         idx.add(x)
         return idx
 
-    @property
-    def hbm_bytes(self):
-        hb = C.c_int64()
-        check(load().mi_ivfpq_info(self._h, None, None, None, None, None, None, None, None, hb))
-        return hb.value
-
     def _rows(self, x):
         a, code, rs, cs = _strided(x)
         if a.shape[1] != self.d:
@@ -2229,8 +2072,7 @@ class IVFPQIndex:
         there (Gallery.refine; queries rounded to float32) and the distances returned are its exact float32 values."""
         a, code, rs, cs = self._rows(q)
         nq, k = a.shape[0], int(k)
-        if allow is not None and allow_ptr is not None:
-            raise ValueError("give at most one of allow and allow_ptr")
+        resolved = bits, bits_p, memspace = _resolve_allow(allow, allow_ptr, self.n, self.row_offset)
         pr, pr_p = None, None
         if probes is not None:
             pr = np.asarray(probes)
@@ -2244,31 +2086,13 @@ class IVFPQIndex:
         nprobe = self._nprobe(nprobe)
         if refine is not None:
             import torch
-            if allow_ptr is not None:
-                raise ValueError("refine takes allow, not allow_ptr")
 
-            def dev(xq, m, kc, cand_ptr, bits_ptr, stream):
-                pr_dev = None if pr is None else torch.from_numpy(pr).to(xq.device)
-                with self._lock:
-                    self.search_device(xq.data_ptr(), m, kc, cand_ptr, nprobe=nprobe, probes_ptr=None if pr_dev is None else pr_dev.data_ptr(),
-                                       allow_ptr=bits_ptr, stream=stream)
-            return _search_refined(refine, a, k, refine_kc(k, k_factor, self.n), _allow_words(allow, self.n, self.row_offset), dev,
-                                   self.device)
-        bits, bits_p, memspace = None, None, MI_HOST
-        if allow is not None:
-            bits = allow_bitmap(allow, self.n, self.row_offset)
-            if bits.size == 0:
-                bits = np.zeros(1, "<u8")
-            bits_p = C.c_void_p(bits.ctypes.data)
-        elif allow_ptr is not None:
-            bits_p, memspace = C.c_void_p(int(allow_ptr)), MI_DEVICE
-        idx = np.empty((nq, k), dtype=np.int64)
-        dist = np.empty((nq, k), dtype=np.float32)
-        secs = C.c_double()
-        with self._lock:
-            check(load().mi_ivfpq_search(self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, nprobe, pr_p, bits_p, memspace,
-                                         idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p), C.byref(secs)))
-        return idx, dist, secs.value
+            def stage(xq, stream):
+                return xq, {"probes_ptr": torch.from_numpy(pr).to(xq.device)}
+            return _search_refined(refine, a, k, refine_kc(k, k_factor, self.n), resolved, self.device, self._lock, self.search_device,
+                                   stage=None if pr is None else stage, nprobe=nprobe)
+        return self._topk(nq, k, (np.float32,), lambda idx, dist, secs: load().mi_ivfpq_search(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, nprobe, pr_p, bits_p, memspace, idx, dist, secs))
 
     def search_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, nprobe=1, probes_ptr=None, allow_ptr=None, stream=None):
         """q_ptr: packed float32 [nq][d] on the device; probes_ptr: None or int32 [nq][nprobe] on the device (entries outside
@@ -2303,23 +2127,6 @@ class IVFPQIndex:
         with self._lock:
             check(load().mi_ivfpq_get_rows(self._h, int(row0), nrows, codes.ctypes.data_as(C.c_void_p), lists.ctypes.data_as(C.c_void_p)))
         return codes, lists
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            check(load().mi_ivfpq_destroy(self._h))
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def kth_of_gathered_device(gathered_ptr, nshards, nq, k, out_ptr, stream=None):
@@ -2487,16 +2294,18 @@ def device_count():
     return n.value
 
 
-class OnlineChain:
+class OnlineChain(_Handle):
     """mi_online_*: search -> qge1 expansion -> re-search (src/online.py:108-152) behind one coalescing worker thread of the
     LIBRARY.  `query` blocks inside the C call -- ctypes releases the interpreter lock -- so the request threads of a Python
     server cost the interpreter one foreign call each.  g_rows None: the plain search.  The galleries must outlive it."""
+    _DESTROY = "mi_online_destroy"
 
     def __init__(self, g_search, g_rows, k, k_qe=3, w=4.0, eps=1e-6, max_batch=128, max_wait_us=500):
         h = C.c_void_p()
         check(load().mi_online_create(g_search._h, None if g_rows is None else g_rows._h, k, k_qe, w, eps, max_batch,
                                       max_wait_us, C.byref(h)))
-        self._h, self.k, self.d = h.value, int(k), g_search.d
+        super().__init__(h.value)                # (query() takes no lock: the library coalesces its callers)
+        self.k, self.d = int(k), g_search.d
         self._keep = (g_search, g_rows)
         self._query = load().mi_online_query
 
@@ -2525,14 +2334,3 @@ class OnlineChain:
         a, b = C.c_int64(), C.c_int64()
         check(load().mi_online_stats(self._h, C.byref(a), C.byref(b)))
         return {"chains": a.value, "requests": b.value}
-
-    def close(self):
-        if self._h:
-            check(load().mi_online_destroy(self._h))
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
