@@ -96,6 +96,19 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_graph_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "mi_forest_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mi_forest_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "mi_forest_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                 C.POINTER(C.c_int32)]),
+    "mi_forest_get_splits": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "mi_forest_get_leaves": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "mi_forest_get_dirs": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_forest_destroy": (C.c_int, [C.c_void_p]),
+    "mi_forest_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_void_p, c_f64p]),
+    "mi_forest_candidates_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mi_forest_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, c_f64p]),
+    "mi_forest_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_hamming_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                     C.POINTER(C.c_void_p)]),
     "mi_hamming_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
@@ -1080,6 +1093,179 @@ class GraphIndex(_GraphBase):
         k, ef = _graph_search_shape(k, ef)
         check(load().mi_graph_search_device(self._h, C.c_void_p(q_ptr), int(nq), k, ef, C.c_void_p(idx_ptr), C.c_void_p(val_ptr),
                                             C.c_void_p(val64_ptr), C.c_void_p(visited_ptr), C.c_void_p(stream)))
+
+
+FOREST_MAX_T, FOREST_MAX_L, FOREST_MAX_D, FOREST_LEAF_TARGET = 256, 24, 4096, 64
+
+
+def _forest_check(n, d, T, L):
+    """leaf_max = ceil(n / 2^L) of a forest of T trees with L levels of splits over n rows of d columns; raises ValueError outside
+    1 <= T <= 256, 1 <= L <= 24, 2^L <= n < 2^31, d <= 4096, T * leaf_max <= 8192 (mi_forest_build's and mi_forest_create's checks)."""
+    n, d, T, L = int(n), int(d), int(T), int(L)
+    if T < 1 or T > FOREST_MAX_T:
+        raise ValueError("T = %d: T must be in [1, %d]" % (T, FOREST_MAX_T))
+    if L < 1 or L > FOREST_MAX_L:
+        raise ValueError("L = %d: L must be in [1, %d]" % (L, FOREST_MAX_L))
+    if n >= 2 ** 31 or d > FOREST_MAX_D:
+        raise ValueError("a forest takes fewer than 2^31 rows of d <= %d columns (got %d x %d)" % (FOREST_MAX_D, n, d))
+    if (1 << L) > n:
+        raise ValueError("L = %d: 2^L must not exceed the %d rows of the gallery" % (L, n))
+    leaf_max = -(-n // (1 << L))
+    if T * leaf_max > REFINE_MAX_KC:
+        raise ValueError("T * leaf_max = %d candidates per query: at most %d (more levels or fewer trees)" % (T * leaf_max, REFINE_MAX_KC))
+    return leaf_max
+
+
+def _forest_shape(k_hint, n, n_trees):
+    """The depth ForestIndex.build picks where none is given: the smallest L >= 1 with leaf_max = ceil(n / 2^L) <= 64 and
+    n_trees * leaf_max <= 8192, subject to 2^L <= n and L <= 24 -> (L, leaf_max).  Leaves of up to 64 rows keep a tree's share of the
+    candidates small next to the union of all trees; the second bound is mi_refine's.  k_hint (None: no wish) is the k the caller
+    will search with: a forest whose n_trees * leaf_max slots cannot hold k rows raises.  ValueError where no such L exists
+    (n < 2, n_trees outside [1, 256], n beyond 64 * 2^24 rows)."""
+    n, T = int(n), int(n_trees)
+    if T < 1 or T > FOREST_MAX_T:
+        raise ValueError("n_trees = %d: T must be in [1, %d]" % (T, FOREST_MAX_T))
+    for L in range(1, FOREST_MAX_L + 1):
+        if (1 << L) > n:
+            break
+        leaf_max = -(-n // (1 << L))
+        if leaf_max <= FOREST_LEAF_TARGET and T * leaf_max <= REFINE_MAX_KC:
+            if k_hint is not None and int(k_hint) > T * leaf_max:
+                raise ValueError("k = %d: %d trees with leaves of %d rows give %d candidates per query" % (k_hint, T, leaf_max, T * leaf_max))
+            return L, leaf_max
+    raise ValueError("no depth L in [1, %d] with 2^L <= n = %d gives leaves of at most %d rows and at most %d candidates per query "
+                     "for %d trees" % (FOREST_MAX_L, n, FOREST_LEAF_TARGET, REFINE_MAX_KC, T))
+
+
+def forest_directions(d, T, L, seed=5):
+    """Standard normal float64 [T * L, d] from numpy's seeded Generator: row t * L + l is the direction of level l of tree t."""
+    d, T, L = int(d), int(T), int(L)
+    if d < 1 or T < 1 or L < 1:
+        raise ValueError("forest_directions: d, T and L must be >= 1 (got %d, %d, %d)" % (d, T, L))
+    return np.random.default_rng(seed).standard_normal((T * L, d))
+
+
+def _forest_dirs(dirs, d, T, L):
+    """dirs as float64 [T * L, d] C-contiguous; raises ValueError on another shape or a value that is not finite."""
+    a = np.ascontiguousarray(dirs, dtype=np.float64)
+    if a.shape != (T * L, d):
+        raise ValueError("dirs of shape %s; %d trees of %d levels over %d columns take [%d, %d]" % (a.shape, T, L, d, T * L, d))
+    if not np.isfinite(a).all():
+        raise ValueError("dirs must be finite")
+    return a
+
+
+def _forest_trees(n, d, dirs, splits, leaves):
+    """(dirs float64 [T L, d], splits float64 [T, 2^L - 1], leaves int32 [T, n], T, L) of ForestIndex.from_trees; T and L are read
+    off leaves and splits.  Raises ValueError on arrays of other shapes, a leaf value outside [0, n) and whatever _forest_check
+    refuses."""
+    s, lv = np.asarray(splits), np.asarray(leaves)
+    if lv.dtype == np.bool_ or not np.issubdtype(lv.dtype, np.integer):
+        raise ValueError("leaves must be an integer array (got %s)" % lv.dtype)
+    if lv.ndim != 2 or lv.shape[1] != int(n):
+        raise ValueError("leaves of shape %s; a gallery of %d rows takes [T, %d]" % (lv.shape, n, n))
+    T = lv.shape[0]
+    L = int(s.shape[1] + 1).bit_length() - 1 if s.ndim == 2 else 0
+    if s.ndim != 2 or s.shape[0] != T or s.shape[1] != (1 << L) - 1 or not np.issubdtype(s.dtype, np.floating):
+        raise ValueError("splits of shape %s %s; %d trees take float [%d, 2^L - 1]" % (s.dtype, s.shape, T, T))
+    _forest_check(n, d, T, L)
+    if lv.size and (lv.min() < 0 or lv.max() >= n):
+        raise ValueError("leaf values must lie in [0, %d)" % n)
+    return (_forest_dirs(dirs, int(d), T, L), np.ascontiguousarray(s, dtype=np.float64), np.ascontiguousarray(lv, dtype=np.int32), T, L)
+
+
+class ForestIndex(_Handle):
+    """A forest of random-projection trees over the rows of a Gallery (a `mi_forest` handle), the role of the
+    reference's matching_ANNOY.  T balanced trees; every node of one level of one tree splits its rows at the median of their
+    projection onto that level's direction; a query descends every tree and the rows of the T leaves it reaches are re-ranked
+    exactly.  Which rows the forest reaches is approximate; the answer given directions, trees, stored rows and query is exact:
+    values are Gallery.refine's, the order is (value best first, id ascending).  The gallery must outlive the index; after
+    gallery.append* / gallery.remove a search raises (build a new forest).  These are this library's trees, not annoy's."""
+    _DESTROY = "mi_forest_destroy"
+
+    def __init__(self, handle, gallery):
+        super().__init__(handle)
+        self.gallery = gallery
+        n, d, T, L, lm = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        check(load().mi_forest_info(self._h, n, d, T, L, lm))
+        self.n, self.d, self.n_trees, self.depth, self.leaf_max = n.value, d.value, T.value, L.value, lm.value
+
+    @classmethod
+    def build(cls, gallery, n_trees=100, depth=None, seed=5, dirs=None):
+        """mi_forest_build: n_trees trees of `depth` levels of splits (None: _forest_shape's choice) on the directions `dirs`
+        (float [n_trees * depth, d]; None: forest_directions(d, n_trees, depth, seed)).  Deterministic; runs on the device.  Bad
+        shapes raise ValueError before the device is touched."""
+        T = int(n_trees)
+        L = _forest_shape(None, gallery.n, T)[0] if depth is None else int(depth)
+        _forest_check(gallery.n, gallery.d, T, L)
+        r = forest_directions(gallery.d, T, L, seed) if dirs is None else _forest_dirs(dirs, gallery.d, T, L)
+        h = C.c_void_p()
+        with gallery._lock:
+            check(load().mi_forest_build(gallery._h, C.c_void_p(r.ctypes.data), T, L, C.byref(h)))
+        return cls(h.value, gallery)
+
+    @classmethod
+    def from_trees(cls, gallery, dirs, splits, leaves):
+        """mi_forest_create: dirs float [T * L, d], splits float [T, 2^L - 1], leaves integer [T, n] of LOCAL rows (repeats are
+        legal).  Bad input raises ValueError before the device is touched."""
+        r, s, lv, T, L = _forest_trees(gallery.n, gallery.d, dirs, splits, leaves)
+        h = C.c_void_p()
+        with gallery._lock:
+            check(load().mi_forest_create(gallery._h, C.c_void_p(r.ctypes.data), T, L, C.c_void_p(s.ctypes.data),
+                                          C.c_void_p(lv.ctypes.data), MI_HOST, C.byref(h)))
+        return cls(h.value, gallery)
+
+    def _k(self, k):
+        k = int(k)
+        if k < 1 or k > self.n_trees * self.leaf_max:
+            raise ValueError("k = %d: k must be in [1, T * leaf_max = %d]" % (k, self.n_trees * self.leaf_max))
+        return k
+
+    def search(self, q, k, return_values64=False):
+        """-> (ids int64 [Q, k], values float32 [Q, k], seconds), 1 <= k <= n_trees * leaf_max.  Fewer than k distinct rows in the
+        leaves reached: ids -1, values +inf (L2) / -inf.  return_values64: the float64 values in place of their float32 cast."""
+        k = self._k(k)
+        a, code, rs, cs = self.gallery._queries(q)
+        nq = a.shape[0]
+        idx, val, val64, secs = self._topk(nq, k, (np.float32, np.float64), lambda idx, val, val64, secs: load().mi_forest_search(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, idx, val, val64, secs))
+        return idx, val64 if return_values64 else val, secs
+
+    def search_device(self, q_ptr, nq, k, idx_ptr, val_ptr=None, val64_ptr=None, stream=None):
+        """mi_forest_search_device: q_ptr packed float32 [nq][d] on the device; enqueued on `stream`, no synchronisation."""
+        check(load().mi_forest_search_device(self._h, C.c_void_p(q_ptr), int(nq), self._k(k), C.c_void_p(idx_ptr), C.c_void_p(val_ptr),
+                                             C.c_void_p(val64_ptr), C.c_void_p(stream)))
+
+    def candidates(self, q):
+        """-> int64 [Q, n_trees * leaf_max]: slot t * leaf_max + i is the i-th row (global id) of the leaf the query reaches in
+        tree t, -1 behind a leaf shorter than leaf_max (mi_forest_candidates)."""
+        a, code, rs, cs = self.gallery._queries(q)
+        out = np.empty((a.shape[0], self.n_trees * self.leaf_max), np.int64)
+        with self._lock:
+            check(load().mi_forest_candidates(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs,
+                                              C.c_void_p(out.ctypes.data), None))
+        return out
+
+    def splits(self):
+        """The split values, float64 [n_trees, 2^depth - 1]: node (l, j) at column 2^l - 1 + j."""
+        out = np.empty((self.n_trees, (1 << self.depth) - 1), np.float64)
+        with self._lock:
+            check(load().mi_forest_get_splits(self._h, 0, self.n_trees, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def leaves(self):
+        """The row permutations, int32 [n_trees, n]."""
+        out = np.empty((self.n_trees, self.n), np.int32)
+        with self._lock:
+            check(load().mi_forest_get_leaves(self._h, 0, self.n_trees, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def dirs(self):
+        """The directions, float64 [n_trees * depth, d]."""
+        out = np.empty((self.n_trees * self.depth, self.d), np.float64)
+        with self._lock:
+            check(load().mi_forest_get_dirs(self._h, C.c_void_p(out.ctypes.data)))
+        return out
 
 
 def refine_kc(k, k_factor, n):

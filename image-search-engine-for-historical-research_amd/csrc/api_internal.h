@@ -25,6 +25,9 @@
 //                     (graph_table_*, graph_*_check: the checks, create from a caller's table, the tail of a build, the getters)
 //   api_pq_graph.hip  graph index over PQ codes (mi_pq_graph): neighbour table over the rows of a mi_pq index, best-first search on
 //                     ADC distances (pq_graph_search.hip), table from the exhaustive ADC search of the decoded rows
+//   api_forest.hip    random-projection forest (mi_forest): directions, split values and row permutations over a gallery's rows; f64
+//                     projections of rows and queries by one kernel (forest_project.hip), level-wise build (forest_build.hip), descent
+//                     into candidate slots (forest_search.hip), the answer by launch_refine
 // Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index
 // family), graph_walk.h (the best-first walk of both graph indexes)
 // The handles' grow-only device buffers own themselves: device_buf.h (DeviceBuf<T> and the per-handle DeviceBufSet; host code only);
@@ -84,6 +87,7 @@ extern MI_INTERNAL std::atomic<int64_t> g_hamming_matrix_bytes; // mi_hamming_se
 extern MI_INTERNAL std::atomic<int64_t> g_hamming_range_bytes;  // mi_hamming_range_search* / self_range: bytes of the (block, query) workspace (default 1 GiB)
 extern MI_INTERNAL std::atomic<int> g_hamming_range_early_exit; // ... drop a (block, query) whose partial sums are all above the radius (default 1)
 extern MI_INTERNAL std::atomic<int64_t> g_pq_matrix_bytes;      // mi_pq_search*: bytes of the distance matrix (default 2 GiB); mi_ivfpq_search*: of the partial lists
+extern MI_INTERNAL std::atomic<int64_t> g_forest_build_bytes;   // mi_forest_build: bytes of the scratch of a group of trees (default 1 GiB)
 constexpr size_t SPARE_MAX_BYTES = (size_t)16 << 30;
 MI_INTERNAL void spare_release_locked();
 MI_INTERNAL void spare_ws_release_locked();

@@ -46,6 +46,10 @@ std::atomic<int64_t> g_pq_matrix_bytes{PQ_MATRIX_DEFAULT};
 // in 8 chunks of two launches; a first choice, no sweep yet
 constexpr int64_t PQ_REMOVE_BLOCK_ROWS_DEFAULT = (int64_t)1 << 21;
 std::atomic<int64_t> g_pq_remove_block_rows{PQ_REMOVE_BLOCK_ROWS_DEFAULT};
+// mi_set_global_option("forest_build_bytes", ...): upper limit of the scratch of mi_forest_build (api_forest.hip): the trees go
+// through the build in groups that fit it, one tree at the least
+constexpr int64_t FOREST_BUILD_DEFAULT = (int64_t)1 << 30;
+std::atomic<int64_t> g_forest_build_bytes{FOREST_BUILD_DEFAULT};
 void spare_release_locked() {
   if (g_spare.device < 0) return;
   int cur = 0;
@@ -286,6 +290,10 @@ int mi_set_global_option(const char* name, double value) {
     REQUIRE(value >= 0 && value <= 1e13, "pq_matrix_bytes: bytes of the distance matrix of a PQ index (0 = default, 2 GiB)");
     g_pq_matrix_bytes = value == 0 ? PQ_MATRIX_DEFAULT : (int64_t)value;
   }
+  else if (n == "forest_build_bytes") {
+    REQUIRE(value >= 0 && value <= 1e13, "forest_build_bytes: bytes of the scratch of mi_forest_build (0 = default, 1 GiB)");
+    g_forest_build_bytes = value == 0 ? FOREST_BUILD_DEFAULT : (int64_t)value;
+  }
   else if (n == "release_spares") {
     // gives the spare slots back NOW and leaves the mode alone (a caller that is done with its galleries for a while --
     // nnsearch.drop_cached_galleries -- or a co-tenant that needs the memory)
@@ -310,6 +318,7 @@ int mi_get_global_option(const char* name, double* out_value) {
   else if (n == "hamming_range_bytes") *out_value = (double)g_hamming_range_bytes.load();
   else if (n == "hamming_range_early_exit") *out_value = g_hamming_range_early_exit.load();
   else if (n == "pq_matrix_bytes") *out_value = (double)g_pq_matrix_bytes.load();
+  else if (n == "forest_build_bytes") *out_value = (double)g_forest_build_bytes.load();
   else if (n == "spare_bytes") {
     // device memory this process holds in the spare slots right now (gallery buffers + search workspace of destroyed handles)
     std::lock_guard<std::mutex> lock(g_spare_mu);

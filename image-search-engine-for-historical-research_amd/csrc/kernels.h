@@ -357,6 +357,24 @@ void launch_hamming_range_order(const HammingRangeArgs& a, int64_t row_offset, i
 void launch_lsh_encode(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, const double* R, const double* thr,
                        int32_t nbits, uint8_t* out, int64_t out_rs, uint32_t* codes, int64_t dst_row0, hipStream_t stream);
 
+// forest_project.hip -- the projections of the random-projection forest (api_forest.hip): out[i * out_rs + c * out_cs]
+// = sum_k double(X[i * rs + k * cs]) * R[c][k], f32 rows (any strides, in elements) against float64 directions [C][d], f64 MFMA, K
+// ascending over the instruction's steps of 4.  The bits of a sum depend on the row, the direction and d alone
+void launch_forest_project(const float* X, int64_t m, int32_t d, int64_t rs, int64_t cs, const double* R, int32_t C, double* out,
+                           int64_t out_rs, int64_t out_cs, hipStream_t stream);
+// forest_build.hip -- one level of `tg` trees at once.  Pt [tg][L][n]: the projections of the group, one column after another;
+// node [tg][n]: the node of every row on this level (read from level 1 on); ids [2][tg][n] and hist [tg][256 * forest_sort_blocks(n)]:
+// scratch of the stable LSD radix sort by (node, projection with -0.0 as +0.0, row id).  Writes the level's split values into
+// splits [tg][2^L - 1], the nodes of the next level into `node` and, on the last level, the order into leaves [tg][n]
+constexpr int FOREST_SORT_CHUNK = 2048;                                     // rows per sort workgroup
+static inline int64_t forest_sort_blocks(int64_t n) { return (n + FOREST_SORT_CHUNK - 1) / FOREST_SORT_CHUNK; }
+void launch_forest_level(const double* Pt, int64_t n, int32_t tg, int32_t L, int32_t level, int32_t* node, int32_t* ids, uint32_t* hist,
+                         double* splits, int32_t* leaves, hipStream_t stream);
+// forest_search.hip -- per (query, tree) the descent over the L split levels on the query's projections Pq [nq][T L], then the ids of
+// the leaf reached into cand[q * cand_stride + t * leaf_max ..], -1 behind them
+void launch_forest_descend(const double* Pq, const double* splits, const int32_t* leaves, int64_t n, int32_t T, int32_t L,
+                           int32_t leaf_max, int64_t row_offset, int64_t nq, int64_t* cand, int64_t cand_stride, hipStream_t stream);
+
 // pq.hip -- exact ADC top-K on product-quantized codes (api_pq.hip): codebooks [M][Ks][L] f32, gallery blocks of 64 rows with the
 // code bytes four books to a dword and the dwords transposed, codes[block][w < ceil(M / 4)][64]; distance tables [nq][M][Ks] f32;
 // a float32 matrix [nq][round_up(n, 64)] of NEGATED distances (NaN = row not admitted) for launch_dense_topk

@@ -689,8 +689,70 @@ def matching_HNSW_NanoPQ_hip(K, embedded_features, embedded_features_test, datas
 
 
 # the matchers of this build by the name the reference's entry points dispatch on (--matching_method, src/offline.py:107-118)
+def _forest_path(dataset, T, L):
+    return os.path.join(os.path.dirname(_gallery_path(dataset)), "mi355_forest_T%d_L%d.npz" % (T, L))
+
+
+def matching_ANNOY_hip(K, embedded_features_train, embedded_features_test, metric="euclidean", dataset=None, n_trees=100,
+                       ifgenerate=True):
+    """Same signature and return shape as matching_ANNOY (src/utils/nnsearch.py; src/test_rOP1m.py:156 calls it with 'euclidean' and
+    n_trees=100), `--matching_method ANNOY`: a forest of n_trees random-projection trees over the database rows, a query descends
+    every tree and the rows of the leaves it reaches are ranked by their exact distances -> (idx int64 [Q, K], time_per_query).
+    THE FOREST IS THIS LIBRARY'S, not the reference's: _lib.ForestIndex.build -- one standard normal direction (seed 5) per level of
+    a tree, every node split at the median of its rows' projections, the depth chosen by _lib._forest_shape (leaves of at most 64
+    rows) -- not annoy's two-means hyperplanes, its random numbers, its search_k queue or its file format, and nothing pins it to
+    annoy's trees.  What is exact is the search GIVEN the forest: float64 direct-form distances over the union of
+    the leaves, ties to the lower index.  metric 'euclidean': the raw rows in a squared-L2 gallery; 'angular': rows and queries
+    L2-normalised first (annoy's angular distance sqrt(2 - 2 cos) orders as the squared distance of the normalised rows does);
+    anything else raises ValueError.  Where the leaves hold fewer than K distinct rows the tail is filled with the lowest indices
+    not in the answer.  With a `dataset` the directions, split values and permutations persist as
+    outputs/<dataset>/mi355_forest_T<T>_L<L>.npz (written to a temporary name and renamed): built and written iff `ifgenerate`,
+    otherwise loaded -- a missing file raises FileNotFoundError; dataset=None writes nothing (and needs ifgenerate).
+    1 <= n_trees <= 256, 1 <= K <= min(N, n_trees * leaf_max), N >= 2.  The timer spans what the reference's spans: the search
+    only, device-synchronised.  Bad input raises ValueError before the device is touched."""
+    if metric not in ("euclidean", "angular"):
+        raise ValueError("metric = %r: 'euclidean' or 'angular'" % (metric,))
+    train, test = np.asarray(embedded_features_train), np.asarray(embedded_features_test)
+    if train.ndim != 2 or test.ndim != 2 or train.shape[1] != test.shape[1]:
+        raise ValueError("expected rows [N, dim] and queries [Q, dim], got %s and %s" % (train.shape, test.shape))
+    for name, a in (("embedded_features_train", train), ("embedded_features_test", test)):
+        if not np.issubdtype(a.dtype, np.floating):
+            raise ValueError("%s must be a floating-point array (got %s)" % (name, a.dtype))
+    K, T = int(K), int(n_trees)
+    num_train, num_test = train.shape[0], test.shape[0]
+    if K < 1 or K > num_train:
+        raise ValueError("K = %d, the database holds %d rows" % (K, num_train))
+    L, _ = _lib._forest_shape(K, num_train, T)
+    _lib._forest_check(num_train, train.shape[1], T, L)
+    if dataset is None and not ifgenerate:
+        raise ValueError("ifgenerate=False loads the forest of a dataset: give one")
+    if metric == "angular":
+        train = _l2_rows_f32(train, "embedded_features_train")
+        test = _l2_rows_f32(test, "embedded_features_test")
+    if not ifgenerate:
+        with np.load(_forest_path(dataset, T, L)) as z:              # (FileNotFoundError when it was never generated)
+            trees = _lib._forest_trees(num_train, train.shape[1], z["dirs"], z["splits"], z["leaves"])[:3]
+    rows = Gallery.l2_from_host(train)
+    try:
+        f = _lib.ForestIndex.build(rows, n_trees=T, depth=L, seed=5) if ifgenerate else _lib.ForestIndex.from_trees(rows, *trees)
+        with f:
+            if ifgenerate and dataset is not None:
+                path = _forest_path(dataset, T, L)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                tmp = "%s.tmp.%d.%s.npz" % (path, os.getpid(), uuid.uuid4().hex[:12])
+                with _path_lock(path):
+                    np.savez(tmp, dirs=f.dirs(), splits=f.splits(), leaves=f.leaves())
+                    os.replace(tmp, path)
+            t1 = time.time()
+            idx, _, _ = f.search(test, K)                  # (synchronous: the results are on the host when it returns)
+            t2 = time.time()
+    finally:
+        rows.close()
+    return _fill_short_rows(idx, num_train), (t2 - t1) / max(num_test, 1)
+
+
 MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip, "PQ": matching_Nano_PQ_hip,
-                    "HNSW": matching_HNSW_hip, "PQ_HNSW": matching_HNSW_NanoPQ_hip}
+                    "HNSW": matching_HNSW_hip, "PQ_HNSW": matching_HNSW_NanoPQ_hip, "ANNOY": matching_ANNOY_hip}
 
 
 def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test):

@@ -268,6 +268,72 @@ int mi_graph_search(mi_graph* gr, const void* q, int64_t nq, int dtype, int64_t 
 int mi_graph_search_device(mi_graph* gr, const float* q_dev, int64_t nq, int32_t k, int32_t ef, int64_t* out_idx_dev,
                            float* out_val_dev, double* out_val64_dev, int32_t* out_visited_dev, void* stream);
 
+/* ---- random-projection forest: T balanced trees over the rows of a gallery, the role of the reference's matching_ANNOY
+ * (src/utils/nnsearch.py; its million-image driver's ANN choice, src/test_rOP1m.py:156).  DESIGN.md 5.17.  The forest is this
+ * library's own -- one random direction per LEVEL of a tree, median splits --, not annoy's two-means hyperplanes, its RNG or its
+ * file format.  What is approximate is WHICH rows the forest reaches; everything else is an exact, deterministic function of
+ * directions, trees, stored rows and query.
+ * A handle sits over ONE gallery `rows` (one shard on one device, squared-L2 or inner product, as for mi_refine and mi_graph),
+ * which must outlive it.
+ *   shape       T trees, 1 <= T <= 256, each a complete binary tree with L levels of splits, 1 <= L <= 24, 2^L <= n < 2^31, d <= 4096.
+ *               Node (l, j), 0 <= l < L, 0 <= j < 2^l, owns the slice [floor(j n / 2^l), floor((j + 1) n / 2^l)) of the tree's row
+ *               permutation leaves[t] (int32 [n], LOCAL rows); the slices nest; a leaf is a slice at l = L; leaf_max = ceil(n / 2^L);
+ *               T * leaf_max <= 8192 (mi_refine's kc limit).
+ *   directions  dirs float64 [T L][d] row-major, host memory, every value finite; row c = t L + l serves level l of tree t.  The
+ *               scale of a direction changes nothing.
+ *   projection  P[i][c] = sum_k double(x_i[k]) * dirs[c][k] over the stored f32 row that mi_refine evaluates, on the f64 matrix
+ *               pipe, k ascending over the instruction's steps of 4 from +0.0; the error bound is mi_lsh_encode's,
+ *               (d + 2) 2^-53 sum_k |x r|; -0.0 is ordered as +0.0.  ONE kernel projects the stored rows of a build and the queries
+ *               of a search, and the bits of a sum do not depend on where its row falls in a launch: a query that equals a stored
+ *               row bit for bit gets that row's projections bit for bit.
+ *   build       per tree t, from the identity permutation, for l = 0 .. L - 1, in every node (l, j): the node's rows are ordered by
+ *               (P[row][t L + l] ascending, row id ascending), and with mid = floor((2 j + 1) n / 2^(l + 1))
+ *               split[t][2^l - 1 + j] = P[leaves[t][mid]][t L + l], the smallest projection of the right child.  The permutation as
+ *               the last level leaves it is the tree.  The same bytes on every call; a tree depends on the order of summation only
+ *               where two projections of a node lie within the error bound of each other, and sums that are exact in any order
+ *               give exact trees.  (A NaN projection of a stored row is ordered by its bits: behind +inf, or before -inf when its
+ *               sign bit is set.)  The trees are built in groups whose scratch fits the global option "forest_build_bytes"
+ *               (default 1 GiB), one tree at the least: n (8 L + 12) + ceil(n / 2048) 1024 bytes per tree of a group.
+ *   descent     per query q and tree t: j = 0; for l = 0 .. L - 1: j = 2 j + (Pq[t L + l] >= split[t][2^l - 1 + j]); a NaN goes
+ *               left.  The query is used as given: on an MI_NORM_L2 gallery normalise it yourself, or projections of two scales
+ *               are compared.
+ *   candidates  int64 [nq][T leaf_max]: slot t leaf_max + i holds row_offset + leaves[t][a + i], [a, b) the slice of the leaf
+ *               reached in tree t; slots i >= b - a hold -1.
+ *   answer      mi_refine_device on those candidates: distinct rows, order (value best first, id ascending), mi_refine's float64
+ *               bits and padding; 1 <= k <= T leaf_max.
+ * mi_forest_build makes the trees on the device (rows and projections never cross the host link).  mi_forest_create takes a
+ * caller's trees: splits float64 [T][2^L - 1] and leaves int32 [T][n], both in host or both in device memory (`memspace`); a leaf
+ * value outside [0, n) is MI_ERR_INVALID; repeats are legal (refine counts a row once).
+ * The handle records the gallery's n: after mi_gallery_append* or mi_gallery_remove_rows every search returns MI_ERR_INVALID and
+ * reads no stale table.  Not built: annoy's two-means hyperplanes, a priority queue shared by the trees (search_k), vote
+ * thresholds, sparse directions, an allow bitmap, sharding, updating a forest in place. */
+typedef struct mi_forest mi_forest; /* opaque */
+int mi_forest_build(mi_gallery* rows, const double* dirs, int32_t T, int32_t L, mi_forest** out);
+int mi_forest_create(mi_gallery* rows, const double* dirs, int32_t T, int32_t L, const double* splits, const int32_t* leaves,
+                     int memspace, mi_forest** out);
+/* n, d, T, L, leaf_max (any may be NULL); the tables of trees [tree0, tree0 + ntrees) and all directions into host memory */
+int mi_forest_info(const mi_forest* f, int64_t* n, int32_t* d, int32_t* T, int32_t* L, int32_t* leaf_max);
+int mi_forest_get_splits(mi_forest* f, int32_t tree0, int32_t ntrees, double* out_host);
+int mi_forest_get_leaves(mi_forest* f, int32_t tree0, int32_t ntrees, int32_t* out_host);
+int mi_forest_get_dirs(mi_forest* f, double* out_host);
+int mi_forest_destroy(mi_forest* f); /* NULL is MI_OK */
+/* The candidate slots alone.  Host form: queries of any strides and dtype as in mi_knn_search_l2 (f64 rounded to f32), out_cand
+ * int64 [nq][T leaf_max] in host memory; synchronous, on the gallery's stream.  _device: q_dev [nq][d] packed f32, out_cand_dev
+ * int64 [nq][T leaf_max]; enqueued on `stream`, no synchronisation.  nq == 0 is MI_OK and writes nothing. */
+int mi_forest_candidates(mi_forest* f, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int64_t* out_cand,
+                         double* out_seconds);
+int mi_forest_candidates_device(mi_forest* f, const float* q_dev, int64_t nq, int64_t* out_cand_dev, void* stream);
+/* Host form: queries as above, used as given; out_val (f32) and out_val64 may be NULL; synchronous, on the gallery's stream.
+ * nq == 0 is MI_OK and writes nothing. */
+int mi_forest_search(mi_forest* f, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                     int64_t* out_idx, float* out_val, double* out_val64, double* out_seconds);
+/* q_dev [nq][d] packed f32; enqueued on `stream`, no synchronisation.  It stages the queries, their projections, the candidate
+ * slots and the candidates' values in buffers of the handle (grown when a larger call comes; a batch whose projections, slots and
+ * values would exceed 64 MiB runs in chunks of queries): calls on one handle must be serialised by the caller and enqueued on ONE
+ * stream. */
+int mi_forest_search_device(mi_forest* f, const float* q_dev, int64_t nq, int32_t k, int64_t* out_idx_dev, float* out_val_dev,
+                            double* out_val64_dev, void* stream);
+
 /* ---- binary index: exact Hamming top-K on packed binary codes.  The reference's matching_Greedyhash(K, hash_codes_train,
  * hash_codes_test) (src/utils/nnsearch.py:1001-1013: XOR against every gallery code, sum, argsort, first K) and faiss
  * IndexBinaryFlat (what IndexLSH, src/utils/nnsearch.py:734-745, searches with internally).  DESIGN.md 5.13.
