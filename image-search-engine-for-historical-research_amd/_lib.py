@@ -263,6 +263,10 @@ SIGNATURES = {
                                           C.POINTER(C.c_double)]),
     "mi_synth_fill_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
 }
+# the wide PQ index mirrors mi_pq entry point for entry point (uint16 codes, Ks <= 8192): the same signatures
+SIGNATURES.update(("mi_pqw_" + name, SIGNATURES["mi_pq_" + name]) for name in (
+    "create", "append_codes", "add", "encode", "dtable", "search", "search_device", "info", "get_codes", "get_codebooks", "decode",
+    "destroy", "train"))
 
 _lib = None
 _lock = threading.Lock()
@@ -1685,19 +1689,28 @@ class LSHIndex(_Closing):
 
 
 PQ_MAX_BOOKS, PQ_MAX_WORDS, PQ_MAX_DIM = 64, 256, 4096
+PQW_MAX_WORDS = 8192              # the wide index (WidePQIndex, mi_pqw): uint16 codes
+PQW_SLAB_ROWS = 16384             # the most rows one workgroup of its scan walks (csrc/pq_wide.hip: 64 * PW_WAVES * PW_RPL)
 
 
-def pq_codebooks(codebooks):
+def _pq_check_words(ks, max_words):
+    if not 2 <= ks <= max_words:
+        if max_words == PQ_MAX_WORDS:
+            raise ValueError("Ks = %d codewords per book, a PQ index takes 2 .. %d (one byte per book)" % (ks, max_words))
+        raise ValueError("Ks = %d codewords per book, a wide PQ index takes 2 .. %d" % (ks, max_words))
+
+
+def pq_codebooks(codebooks, max_words=PQ_MAX_WORDS):
     """float32 [M, Ks, L] C-contiguous codebooks (nanopq's pq.codewords, faiss's ProductQuantizer.centroids), checked against
-    what a PQ index takes: 1 <= M <= 64, 2 <= Ks <= 256, M * L <= 4096, finite.  Raises ValueError."""
+    what a PQ index takes: 1 <= M <= 64, 2 <= Ks <= 256 (max_words; PQW_MAX_WORDS for the wide index), M * L <= 4096, finite.
+    Raises ValueError."""
     cb = np.ascontiguousarray(codebooks, dtype=np.float32)
     if cb.ndim != 3:
         raise ValueError("codebooks must be [M, Ks, L] (got shape %s)" % (cb.shape,))
     m, ks, L = cb.shape
     if not 1 <= m <= PQ_MAX_BOOKS:
         raise ValueError("M = %d books, a PQ index takes 1 .. %d" % (m, PQ_MAX_BOOKS))
-    if not 2 <= ks <= PQ_MAX_WORDS:
-        raise ValueError("Ks = %d codewords per book, a PQ index takes 2 .. %d (one byte per book)" % (ks, PQ_MAX_WORDS))
+    _pq_check_words(ks, max_words)
     if L < 1 or m * L > PQ_MAX_DIM:
         raise ValueError("d = M * L = %d, a PQ index takes 1 .. %d" % (m * L, PQ_MAX_DIM))
     if not np.isfinite(cb).all():
@@ -1705,9 +1718,10 @@ def pq_codebooks(codebooks):
     return cb
 
 
-def pq_code_rows(codes, m, ks):
-    """uint8 [rows, m] code rows from any integer array with values in [0, ks) (row stride kept when the array is uint8 with
-    contiguous rows).  Raises ValueError on another dtype, shape or a value outside [0, ks)."""
+def pq_code_rows(codes, m, ks, dtype=np.uint8):
+    """uint8 [rows, m] code rows (dtype: uint16 for the wide index) from any integer array with values in [0, ks) (row stride kept
+    when the array has that type and contiguous rows) -> (rows, row stride in elements).  Raises ValueError on another dtype,
+    shape or a value outside [0, ks)."""
     a = np.asarray(codes)
     if a.ndim != 2 or a.shape[1] != m:
         raise ValueError("codes must be [rows, M = %d] (got shape %s)" % (m, a.shape))
@@ -1715,20 +1729,21 @@ def pq_code_rows(codes, m, ks):
         raise ValueError("codes must be an integer array of codeword indices (got %s)" % a.dtype)
     if a.size and (int(a.min()) < 0 or int(a.max()) >= ks):
         raise ValueError("codes must lie in [0, Ks = %d)" % ks)
-    if a.dtype != np.uint8:
-        a = a.astype(np.uint8)
-    if a.shape[1] > 1 and a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+    size = np.dtype(dtype).itemsize
+    if a.dtype != dtype:
+        a = a.astype(dtype)
+    if a.shape[1] > 1 and a.strides[1] != size or a.strides[0] < a.shape[1] * size or a.strides[0] % size:
         a = np.ascontiguousarray(a)
-    return a, max(int(a.strides[0]), a.shape[1])
+    return a, max(int(a.strides[0]) // size, a.shape[1])
 
 
-def _pq_train_shape(n, d, M, Ks, iters):
-    """The limits of mi_pq_train, answered with ValueError before the library is loaded.  -> L"""
+def _pq_train_shape(n, d, M, Ks, iters, max_words=PQ_MAX_WORDS):
+    """The limits of mi_pq_train (max_words = PQW_MAX_WORDS: of mi_pqw_train), answered with ValueError before the library is
+    loaded.  -> L"""
     n, d, M, Ks, iters = int(n), int(d), int(M), int(Ks), int(iters)
     if not 1 <= M <= PQ_MAX_BOOKS:
         raise ValueError("M = %d books, a PQ index takes 1 .. %d" % (M, PQ_MAX_BOOKS))
-    if not 2 <= Ks <= PQ_MAX_WORDS:
-        raise ValueError("Ks = %d codewords per book, a PQ index takes 2 .. %d (one byte per book)" % (Ks, PQ_MAX_WORDS))
+    _pq_check_words(Ks, max_words)
     if not 1 <= d <= PQ_MAX_DIM:
         raise ValueError("d = %d, a PQ index takes 1 .. %d" % (d, PQ_MAX_DIM))
     if d % M:
@@ -1740,24 +1755,24 @@ def _pq_train_shape(n, d, M, Ks, iters):
     return d // M
 
 
-def _pq_train_init(init, M, Ks, L):
-    cb = pq_codebooks(init)
+def _pq_train_init(init, M, Ks, L, max_words=PQ_MAX_WORDS):
+    cb = pq_codebooks(init, max_words)
     if cb.shape != (M, Ks, L):
         raise ValueError("init of shape %s, the training takes [M, Ks, L] = %s" % (cb.shape, (M, Ks, L)))
     return cb
 
 
-def _pq_train_call(ptr, n, d, code, rs, cs, memspace, M, Ks, iters, cb0, device):
+def _pq_train_call(ptr, n, d, code, rs, cs, memspace, M, Ks, iters, cb0, device, fn="mi_pq_train"):
     L = d // M
     out = np.empty((M, Ks, L), dtype=np.float32)
     moved = np.zeros(iters, dtype=np.int64)
-    check(load().mi_pq_train(C.c_void_p(ptr), int(n), int(d), code, int(rs), int(cs), memspace, M, Ks, iters,
-                             None if cb0 is None else C.c_void_p(cb0.ctypes.data), device, out.ctypes.data_as(C.c_void_p),
-                             moved.ctypes.data_as(C.c_void_p), None))
+    check(getattr(load(), fn)(C.c_void_p(ptr), int(n), int(d), code, int(rs), int(cs), memspace, M, Ks, iters,
+                              None if cb0 is None else C.c_void_p(cb0.ctypes.data), device, out.ctypes.data_as(C.c_void_p),
+                              moved.ctypes.data_as(C.c_void_p), None))
     return out, moved
 
 
-def pq_train(x, M, Ks, iters=20, init=None, init_rows=None, seed=None, device=0):
+def pq_train(x, M, Ks, iters=20, init=None, init_rows=None, seed=None, device=0, _max_words=PQ_MAX_WORDS, _fn="mi_pq_train"):
     """Learns PQ codebooks on the device (mi_pq_train): Lloyd's k-means iteration per book, as a deterministic function of its
     inputs.  x [n, d] float32/float64 (any strides), n >= Ks -> (codebooks float32 [M, Ks, L], moved int64 [iters]).
     The initial codebooks are ONE of
@@ -1776,14 +1791,14 @@ def pq_train(x, M, Ks, iters=20, init=None, init_rows=None, seed=None, device=0)
     a, code, rs, cs = _strided(x)
     n, d = a.shape
     M, Ks, iters = int(M), int(Ks), int(iters)
-    L = _pq_train_shape(n, d, M, Ks, iters)
+    L = _pq_train_shape(n, d, M, Ks, iters, _max_words)
     if (init is not None) + (init_rows is not None) + (seed is not None) > 1:
         raise ValueError("give at most one of init, init_rows and seed")
     if not np.isfinite(a).all():
         raise ValueError("training rows must be finite")
     cb0 = None
     if init is not None:
-        cb0 = _pq_train_init(init, M, Ks, L)
+        cb0 = _pq_train_init(init, M, Ks, L, _max_words)
     elif seed is not None:
         rng = np.random.RandomState(seed)
         init_rows = np.stack([rng.choice(n, Ks, replace=False) for _ in range(M)])
@@ -1794,18 +1809,31 @@ def pq_train(x, M, Ks, iters=20, init=None, init_rows=None, seed=None, device=0)
         if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= n):
             raise ValueError("init_rows must lie in [0, n = %d)" % n)
         cb0 = np.ascontiguousarray(np.stack([a[rows[j], j * L:(j + 1) * L] for j in range(M)]), dtype=np.float32)
-    return _pq_train_call(_base_pointer(a), n, d, code, rs, cs, MI_HOST, M, Ks, iters, cb0, device)
+    return _pq_train_call(_base_pointer(a), n, d, code, rs, cs, MI_HOST, M, Ks, iters, cb0, device, _fn)
 
 
-def pq_train_device(x_ptr, n, d, M, Ks, iters, init=None, dtype=MI_F32, row_stride=None, col_stride=1, device=0):
+def pq_train_device(x_ptr, n, d, M, Ks, iters, init=None, dtype=MI_F32, row_stride=None, col_stride=1, device=0,
+                    _max_words=PQ_MAX_WORDS, _fn="mi_pq_train"):
     """pq_train on device-resident rows (used where they lie; their producer must have completed): element (r, i) at
     x_ptr + (r * row_stride + i * col_stride) elements of `dtype`, row_stride None = d.  init: codebooks [M, Ks, L] or None (the
     rows floor(c * n / Ks)).  Non-finite rows leave the codebooks of the books they touch unspecified."""
     M, Ks, iters = int(M), int(Ks), int(iters)
-    L = _pq_train_shape(n, d, M, Ks, iters)
-    cb0 = None if init is None else _pq_train_init(init, M, Ks, L)
+    L = _pq_train_shape(n, d, M, Ks, iters, _max_words)
+    cb0 = None if init is None else _pq_train_init(init, M, Ks, L, _max_words)
     return _pq_train_call(int(x_ptr), n, d, dtype, d if row_stride is None else row_stride, col_stride, MI_DEVICE, M, Ks, iters, cb0,
-                          device)
+                          device, _fn)
+
+
+def pqw_train(x, M, Ks, iters=20, init=None, init_rows=None, seed=None, device=0):
+    """pq_train with 2 <= Ks <= PQW_MAX_WORDS = 8192 (mi_pqw_train): the same arguments, the same iteration, the same bits -- for
+    Ks <= 256 the result equals pq_train's.  The codebooks of a WidePQIndex."""
+    return pq_train(x, M, Ks, iters, init, init_rows, seed, device, _max_words=PQW_MAX_WORDS, _fn="mi_pqw_train")
+
+
+def pqw_train_device(x_ptr, n, d, M, Ks, iters, init=None, dtype=MI_F32, row_stride=None, col_stride=1, device=0):
+    """pq_train_device with 2 <= Ks <= PQW_MAX_WORDS (mi_pqw_train)."""
+    return pq_train_device(x_ptr, n, d, M, Ks, iters, init, dtype, row_stride, col_stride, device, _max_words=PQW_MAX_WORDS,
+                           _fn="mi_pqw_train")
 
 
 def pq_train_timing():
@@ -1833,16 +1861,20 @@ def _remove_rows(index, name, rows):
     return kept
 
 
-class PQIndex(_Handle):
-    """PQ index on one MI355X (a `mi_pq` handle): exact ADC top-k on product-quantized codes by (distance asc, id asc)."""
-    _DESTROY = "mi_pq_destroy"
-    hbm_bytes = _hbm_bytes("mi_pq_info", 7)
+class _PQBase(_Handle):
+    """What PQIndex (`mi_pq`, byte codes) and WidePQIndex (`mi_pqw`, uint16 codes) share: every entry point but row removal, the
+    library's names behind `_PREFIX`, the code type and the limit on Ks class attributes."""
+    _PREFIX = _CODE = _MAX_WORDS = _TRAIN = None
+
+    @classmethod
+    def _fn(cls, name):
+        return getattr(load(), "%s_%s" % (cls._PREFIX, name))
 
     def __init__(self, handle):
         super().__init__(handle)
         n, cap, off, hb = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         d, m, ks, dev = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
-        check(load().mi_pq_info(self._h, n, d, m, ks, dev, off, cap, hb))
+        check(self._fn("info")(self._h, n, d, m, ks, dev, off, cap, hb))
         self.n, self.d, self.m, self.ks, self.device = n.value, d.value, m.value, ks.value, dev.value
         self.row_offset, self.capacity = off.value, cap.value
 
@@ -1850,7 +1882,7 @@ class PQIndex(_Handle):
     def _create(cls, cb, ptr, n, stride, memspace, device, row_offset, capacity):
         m, ks, L = cb.shape
         h = C.c_void_p()
-        check(load().mi_pq_create(C.c_void_p(cb.ctypes.data), m * L, m, ks, C.c_void_p(ptr), int(n), int(stride), memspace, device,
+        check(cls._fn("create")(C.c_void_p(cb.ctypes.data), m * L, m, ks, C.c_void_p(ptr), int(n), int(stride), memspace, device,
                                   int(row_offset), int(capacity), C.byref(h)))
         return cls(h.value)
 
@@ -1858,23 +1890,24 @@ class PQIndex(_Handle):
     def from_codes(cls, codebooks, codes, device=0, row_offset=0, capacity=0):
         """codebooks [M, Ks, L] float32, codes integer [N, M] with values in [0, Ks); capacity 0 = N, larger leaves room for
         append_codes() / add()."""
-        cb = pq_codebooks(codebooks)
-        a, stride = pq_code_rows(codes, cb.shape[0], cb.shape[1])
+        cb = pq_codebooks(codebooks, cls._MAX_WORDS)
+        a, stride = pq_code_rows(codes, cb.shape[0], cb.shape[1], cls._CODE)
         if capacity and capacity < a.shape[0]:
             raise ValueError("capacity %d below the %d rows given" % (capacity, a.shape[0]))
         return cls._create(cb, a.ctypes.data, a.shape[0], stride, MI_HOST, device, row_offset, capacity)
 
     @classmethod
-    def from_device_ptr(cls, codebooks, ptr, n, device=0, row_offset=0, capacity=0, row_stride_bytes=None):
-        """Device codes [n][M] uint8 -> index, synchronous; the producer of `ptr` must have completed."""
-        cb = pq_codebooks(codebooks)
-        return cls._create(cb, ptr, n, cb.shape[0] if row_stride_bytes is None else row_stride_bytes, MI_DEVICE, device, row_offset,
-                           capacity)
+    def from_device_ptr(cls, codebooks, ptr, n, device=0, row_offset=0, capacity=0, row_stride_bytes=None, row_stride=None):
+        """Device codes [n][M] of the index's code type -> index, synchronous; the producer of `ptr` must have completed.  The
+        distance between two rows: row_stride_bytes (PQIndex: bytes) or row_stride (WidePQIndex: uint16 elements), None = M."""
+        cb = pq_codebooks(codebooks, cls._MAX_WORDS)
+        stride = row_stride_bytes if cls._CODE is np.uint8 else row_stride
+        return cls._create(cb, ptr, n, cb.shape[0] if stride is None else stride, MI_DEVICE, device, row_offset, capacity)
 
     @classmethod
     def empty(cls, codebooks, capacity, device=0, row_offset=0):
         """Appendable index: `capacity` rows allocated, filled by append_codes() / add()."""
-        cb = pq_codebooks(codebooks)
+        cb = pq_codebooks(codebooks, cls._MAX_WORDS)
         if int(capacity) < 1:
             raise ValueError("an empty index needs a capacity")
         return cls._create(cb, None, 0, cb.shape[0], MI_HOST, device, row_offset, capacity)
@@ -1883,7 +1916,7 @@ class PQIndex(_Handle):
     def fit(cls, x, M, Ks, iters=20, seed=42, capacity=0, device=0, row_offset=0):
         """Learns the codebooks on x [n, d] (pq_train with `seed`; seed=None: the library's default initial rows), creates the
         index and adds x.  The move counts of the training are in `.train_moved`."""
-        cb, moved = pq_train(x, M, Ks, iters=iters, seed=seed, device=device)
+        cb, moved = cls._TRAIN(x, M, Ks, iters=iters, seed=seed, device=device)
         n = np.shape(x)[0]
         if capacity and capacity < n:
             raise ValueError("capacity %d below the %d rows given" % (capacity, n))
@@ -1895,7 +1928,7 @@ class PQIndex(_Handle):
     @property
     def codebooks(self):
         out = np.empty((self.m, self.ks, self.d // self.m), dtype=np.float32)
-        check(load().mi_pq_get_codebooks(self._h, out.ctypes.data_as(C.c_void_p)))
+        check(self._fn("get_codebooks")(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def _rows(self, x):
@@ -1905,30 +1938,30 @@ class PQIndex(_Handle):
         return a, code, rs, cs
 
     def append_codes(self, codes):
-        a, stride = pq_code_rows(codes, self.m, self.ks)
+        a, stride = pq_code_rows(codes, self.m, self.ks, self._CODE)
         with self._lock:
-            check(load().mi_pq_append_codes(self._h, C.c_void_p(a.ctypes.data), a.shape[0], stride, MI_HOST))
+            check(self._fn("append_codes")(self._h, C.c_void_p(a.ctypes.data), a.shape[0], stride, MI_HOST))
             self.n += a.shape[0]
 
     def add(self, x):
         """Encodes rows [rows, d] float32/float64 (any strides) on the device and appends their codes."""
         a, code, rs, cs = self._rows(x)
         with self._lock:
-            check(load().mi_pq_add(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST))
+            check(self._fn("add")(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST))
             self.n += a.shape[0]
 
     def add_device(self, x_ptr, rows, dtype=MI_F32, row_stride=None, col_stride=1):
         with self._lock:
-            check(load().mi_pq_add(self._h, C.c_void_p(x_ptr), int(rows), dtype, self.d if row_stride is None else int(row_stride),
+            check(self._fn("add")(self._h, C.c_void_p(x_ptr), int(rows), dtype, self.d if row_stride is None else int(row_stride),
                                    int(col_stride), MI_DEVICE))
             self.n += int(rows)
 
     def encode(self, x):
-        """-> codes uint8 [rows, M]: per book the codeword nearest in float64, ties to the lower index.  The index is unchanged."""
+        """-> codes [rows, M] of the index's code type: per book the codeword nearest in float64, ties to the lower index.  The index is unchanged."""
         a, code, rs, cs = self._rows(x)
-        out = np.empty((a.shape[0], self.m), dtype=np.uint8)
+        out = np.empty((a.shape[0], self.m), dtype=self._CODE)
         with self._lock:
-            check(load().mi_pq_encode(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST,
+            check(self._fn("encode")(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, MI_HOST,
                                       out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -1937,7 +1970,7 @@ class PQIndex(_Handle):
         a, code, rs, cs = self._rows(q)
         out = np.empty((a.shape[0], self.m, self.ks), dtype=np.float32)
         with self._lock:
-            check(load().mi_pq_dtable(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, out.ctypes.data_as(C.c_void_p)))
+            check(self._fn("dtable")(self._h, C.c_void_p(_base_pointer(a)), a.shape[0], code, rs, cs, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def search(self, q, k, allow=None, allow_ptr=None, refine=None, k_factor=1):
@@ -1951,13 +1984,35 @@ class PQIndex(_Handle):
         resolved = bits, bits_p, memspace = _resolve_allow(allow, allow_ptr, self.n, self.row_offset)
         if refine is not None:
             return _search_refined(refine, a, k, refine_kc(k, k_factor, self.n), resolved, self.device, self._lock, self.search_device)
-        return self._topk(nq, k, (np.float32,), lambda idx, dist, secs: load().mi_pq_search(
+        return self._topk(nq, k, (np.float32,), lambda idx, dist, secs: self._fn("search")(
             self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, k, bits_p, memspace, idx, dist, secs))
 
     def search_device(self, q_ptr, nq, k, idx_ptr, dist_ptr=None, allow_ptr=None, stream=None):
         """q_ptr: packed float32 [nq][d] on the device; enqueued on `stream`, no synchronisation."""
-        check(load().mi_pq_search_device(self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(allow_ptr), C.c_void_p(idx_ptr),
+        check(self._fn("search_device")(self._h, C.c_void_p(q_ptr), int(nq), int(k), C.c_void_p(allow_ptr), C.c_void_p(idx_ptr),
                                          C.c_void_p(dist_ptr), C.c_void_p(stream)))
+
+    def get_codes(self, row0=0, nrows=None):
+        nrows = self.n - row0 if nrows is None else int(nrows)
+        out = np.empty((nrows, self.m), dtype=self._CODE)
+        with self._lock:
+            check(self._fn("get_codes")(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def decode(self, row0=0, nrows=None):
+        """-> float32 [nrows, d]: the rows reconstructed from their codes, codebooks[j][code[:, j]] side by side (nanopq's
+        pq.decode; mi_pq_decode)."""
+        nrows = self.n - row0 if nrows is None else int(nrows)
+        out = np.empty((nrows, self.d), dtype=np.float32)
+        with self._lock:
+            check(self._fn("decode")(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+
+class PQIndex(_PQBase):
+    """PQ index on one MI355X (a `mi_pq` handle): exact ADC top-k on product-quantized codes by (distance asc, id asc)."""
+    _DESTROY, _PREFIX, _CODE, _MAX_WORDS, _TRAIN = "mi_pq_destroy", "mi_pq", np.uint8, PQ_MAX_WORDS, staticmethod(pq_train)
+    hbm_bytes = _hbm_bytes("mi_pq_info", 7)
 
     def remove(self, rows):
         """Removes rows in place (mi_pq_remove_rows; faiss IndexPQ.remove_ids): `rows` is anything allow_bitmap takes -- a bool
@@ -1967,21 +2022,13 @@ class PQIndex(_Handle):
         [row_offset, row_offset + n)."""
         return _remove_rows(self, "mi_pq_remove_rows", rows)
 
-    def get_codes(self, row0=0, nrows=None):
-        nrows = self.n - row0 if nrows is None else int(nrows)
-        out = np.empty((nrows, self.m), dtype=np.uint8)
-        with self._lock:
-            check(load().mi_pq_get_codes(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
-        return out
 
-    def decode(self, row0=0, nrows=None):
-        """-> float32 [nrows, d]: the rows reconstructed from their codes, codebooks[j][code[:, j]] side by side (nanopq's
-        pq.decode; mi_pq_decode)."""
-        nrows = self.n - row0 if nrows is None else int(nrows)
-        out = np.empty((nrows, self.d), dtype=np.float32)
-        with self._lock:
-            check(load().mi_pq_decode(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
-        return out
+class WidePQIndex(_PQBase):
+    """Wide PQ index on one MI355X (a `mi_pqw` handle): PQIndex with 2 <= Ks <= PQW_MAX_WORDS = 8192 codewords
+    per book and uint16 codes -- the reference's 16 x 8192 PQ.  The same contract word for word; for Ks <= 256 every output equals
+    PQIndex's bit for bit.  No row removal."""
+    _DESTROY, _PREFIX, _CODE, _MAX_WORDS, _TRAIN = "mi_pqw_destroy", "mi_pqw", np.uint16, PQW_MAX_WORDS, staticmethod(pqw_train)
+    hbm_bytes = _hbm_bytes("mi_pqw_info", 7)
 
 
 PQ_GRAPH_MAX_SHORTLIST = 2048     # a graph search returns at most ef <= 2048 rows: the longest shortlist refine= can ask for

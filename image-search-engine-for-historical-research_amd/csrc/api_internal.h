@@ -16,7 +16,8 @@
 //   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix;
 //                     radius search and self-join through one ballot per (block, query)
 //   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
-//   api_pq_train.hip  learning PQ codebooks (mi_pq_train): deterministic Lloyd iterations on device-resident rows
+//   api_pq_train.hip  learning PQ codebooks (mi_pq_train, mi_pqw_train): deterministic Lloyd iterations on device-resident rows
+//   api_pq_wide.hip   wide PQ index (mi_pqw): uint16 codes, Ks <= 8192, exact ADC top-K with the books passing through LDS in groups
 //   api_ivfpq.hip     IVF index over PQ codes (mi_ivfpq): coarse lists as chains of 64-slot blocks, exact ADC top-K over the probed lists
 //                     (row removal of both PQ handles: mi_pq_remove_rows in api_pq.hip, mi_ivfpq_remove_rows here; kernels in pq_remove.hip)
 //   api_lsh.hip       LSH codes (mi_lsh_encode*, mi_hamming_append_lsh_device): f64 projection to sign bits, fused (lsh.hip)
@@ -413,6 +414,29 @@ struct mi_pq {
 // the search proper on stream s (api_pq.hip): queries on the device (any strides), results go to device buffers
 MI_INTERNAL int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k,
                                const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s);
+
+// the wide PQ index (api_pq_wide.hip): mi_pq with uint16 codes, two books to a dword, Ks <= 8192
+struct mi_pqw {
+  int device = 0;
+  int64_t n = 0, cap = 0, row_offset = 0;
+  int32_t d = 0, m = 0, ks = 0, L = 0, MH = 0;     // columns, books, codewords per book, columns per book, dwords of a code
+  std::vector<float> cb_host;                      // [m][ks][L]
+  DeviceBufSet bufs;                               // every device allocation of the handle: hbm_bytes is bufs.bytes()
+  DeviceBuf<float> cb{bufs};                       // (cb, codes, flag: exactly their size, allocated at creation)
+  DeviceBuf<uint32_t> codes{bufs};                 // [ceil(cap / 64)][MH][64]
+  DeviceBuf<uint32_t> flag{bufs};                  // raised by the check of device-resident codes (256 bytes)
+  hipStream_t stream = nullptr;
+  DeviceBuf<char> xraw{bufs};                      // rows / queries of a host call, packed [rows][d] in their own type
+  DeviceBuf<uint16_t> cwords{bufs};                // packed codes [rows][m]: host codes on their way in, encoder output
+  DeviceBuf<float> tab{bufs};                      // distance tables [queries of a chunk][m][ks]
+  DeviceBuf<float> mat{bufs};                      // negated distances [queries of a chunk][round_up(n, 64)]
+  DeviceBuf<int64_t> tidx{bufs};                   // [queries of a chunk][ke] what the selection returns
+  DeviceBuf<float> tneg{bufs};
+  DeviceBuf<uint64_t> bits{bufs};                  // device copy of a host bitmap
+  DeviceBuf<int64_t> oidx{bufs};                   // results of a host call
+  DeviceBuf<float> odist{bufs};
+  std::mutex mu;
+};
 
 // ---- api_state.hip
 MI_INTERNAL int ws_free(Workspace& ws);

@@ -1,17 +1,18 @@
-// Learning PQ codebooks of the C ABI: mi_pq_train (kernels in csrc/pq_train.hip and pq_encode_kernel of csrc/pq.hip; DESIGN.md
-// 5.14b).  scipy.cluster.vq.kmeans2(minit="matrix") per book -- what nanopq.PQ.fit runs -- made reproducible on the device:
+// Learning PQ codebooks of the C ABI: mi_pq_train and, on uint16 codes with Ks <= 8192, mi_pqw_train -- one body, the code type
+// a template argument (kernels in csrc/pq_train.hip and pq_encode_kernel of csrc/pq.hip).  scipy.cluster.vq.kmeans2(minit="matrix") per book -- what nanopq.PQ.fit runs -- made reproducible on the device:
 // Lloyd's iteration from given centroids, every operation an IEEE float64 operation in a fixed order, centroids rounded to
 // float32 after every iteration.  No handle: the call owns a stream and its buffers and frees them before it returns.
 #include "api_internal.h"
 
 namespace {
 
+template <typename CodeT>
 struct TrainScratch {
   hipStream_t stream = nullptr;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};     // assignment begin / end, update begin / end
   void* xdev = nullptr;                    // host rows, packed [n][d] in their own type
-  uint8_t* codes[2] = {nullptr, nullptr};  // [n][m] of this iteration and of the one before
-  uint8_t* cols = nullptr;                 // [m][n]
+  CodeT* codes[2] = {nullptr, nullptr};    // [n][m] of this iteration and of the one before
+  CodeT* cols = nullptr;                   // [m][n]
   float* cb = nullptr;                     // [m][ks][L], updated in place
   unsigned long long* moved = nullptr;
   ~TrainScratch() {
@@ -23,11 +24,12 @@ struct TrainScratch {
   }
 };
 
-// device times of the calling thread's last mi_pq_train, per iteration that ran (mi_pq_train_timing)
+// device times of the calling thread's last mi_pq_train / mi_pqw_train, per iteration that ran (mi_pq_train_timing)
 thread_local std::vector<float> t_assign_ms, t_update_ms;
 
 // host rows -> packed [n][d] on the device, once.  Rows that are not contiguous pass through a host block of 64 MiB
-int train_upload(TrainScratch& w, const void* x, int64_t n, int32_t d, size_t esz, int64_t rs, int64_t cs) {
+template <typename CodeT>
+int train_upload(TrainScratch<CodeT>& w, const void* x, int64_t n, int32_t d, size_t esz, int64_t rs, int64_t cs) {
   if (cs == 1 && (rs == d || n == 1)) {
     HIPC(hipMemcpyAsync(w.xdev, x, (size_t)n * d * esz, hipMemcpyHostToDevice, w.stream));
     HIPC(hipStreamSynchronize(w.stream));
@@ -47,20 +49,18 @@ int train_upload(TrainScratch& w, const void* x, int64_t n, int32_t d, size_t es
   return MI_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t m,
-                int32_t ks, int32_t iters, const float* init_codebooks_host, int device, float* out_codebooks_host, int64_t* out_moved,
-                double* out_seconds) {
+// the training proper; ks_max and ks_msg are the entry point's limit on ks
+template <typename CodeT>
+int train_run(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t m,
+              int32_t ks, int32_t ks_max, const char* ks_msg, int32_t iters, const float* init_codebooks_host, int device,
+              float* out_codebooks_host, int64_t* out_moved, double* out_seconds) {
   REQUIRE(x, "null pointer: rows");
   REQUIRE(out_codebooks_host, "null pointer: out_codebooks_host");
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");
   REQUIRE(row_stride >= 0 && col_stride >= 0, "negative strides are not supported");
   REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
   REQUIRE(m >= 1 && m <= 64, "m (books) must be in [1, 64]");
-  REQUIRE(ks >= 2 && ks <= 256, "ks (codewords per book) must be in [2, 256]");
+  REQUIRE(ks >= 2 && ks <= ks_max, ks_msg);
   REQUIRE(d >= 1 && d <= 4096, "d must be in [1, 4096]");
   REQUIRE(d % m == 0, "d must be a multiple of m");
   REQUIRE(n >= ks, "training needs at least ks rows (n >= ks)");
@@ -80,8 +80,8 @@ int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stri
   HIPC(hipSetDevice(device));
   const int32_t L = d / m;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
-  const size_t code_bytes = (size_t)n * m;
-  TrainScratch w;
+  const size_t code_bytes = (size_t)n * m * sizeof(CodeT);
+  TrainScratch<CodeT> w;
   HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
   for (hipEvent_t& e : w.ev) HIPC(hipEventCreate(&e));
   if (memspace == MI_HOST) HIPC(device_malloc(&w.xdev, (size_t)n * d * esz));
@@ -115,8 +115,8 @@ int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stri
     return MI_OK;
   };
   for (; t < iters; ++t) {
-    uint8_t* cur = w.codes[t & 1];
-    const uint8_t* prev = w.codes[(t & 1) ^ 1];
+    CodeT* cur = w.codes[t & 1];
+    const CodeT* prev = w.codes[(t & 1) ^ 1];
     unsigned long long moved = (unsigned long long)n * (unsigned long long)m;
     HIPC(hipEventRecord(w.ev[0], s));
     launch_pq_encode(xd, dtype, rs, cs, n, w.cb, m, ks, L, cur, s);
@@ -150,6 +150,25 @@ int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stri
   if ((rc = read_update()) != MI_OK) return rc;
   if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return MI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t m,
+                int32_t ks, int32_t iters, const float* init_codebooks_host, int device, float* out_codebooks_host, int64_t* out_moved,
+                double* out_seconds) {
+  return train_run<uint8_t>(x, n, d, dtype, row_stride, col_stride, memspace, m, ks, 256, "ks (codewords per book) must be in [2, 256]",
+                            iters, init_codebooks_host, device, out_codebooks_host, out_moved, out_seconds);
+}
+
+int mi_pqw_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t m,
+                 int32_t ks, int32_t iters, const float* init_codebooks_host, int device, float* out_codebooks_host, int64_t* out_moved,
+                 double* out_seconds) {
+  return train_run<uint16_t>(x, n, d, dtype, row_stride, col_stride, memspace, m, ks, PQW_MAX_KS,
+                             "ks (codewords per book) must be in [2, 8192]", iters, init_codebooks_host, device, out_codebooks_host,
+                             out_moved, out_seconds);
 }
 
 int mi_pq_train_timing(int32_t capacity, float* out_assign_ms, float* out_update_ms, int32_t* out_assignments, int32_t* out_updates) {

@@ -386,6 +386,8 @@ void launch_pq_table(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n
 // packed code bytes out [n][M]
 void launch_pq_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* cb, int32_t M, int32_t Ks, int32_t L,
                       uint8_t* out, hipStream_t stream);
+void launch_pq_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* cb, int32_t M, int32_t Ks, int32_t L,
+                      uint16_t* out, hipStream_t stream);                // the wide index's codes (pq_wide.hip)
 int32_t pq_query_tile(int32_t M, int32_t Ks, int64_t nq);      // queries per workgroup of the scan (1, 2 or 4): the LDS budget
 void launch_pq_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, const float* tab, int32_t nq, int32_t qt,
                     const uint64_t* allow, float* mat, hipStream_t stream);
@@ -405,7 +407,8 @@ void launch_pq_decode(const uint32_t* codes, int32_t M, int32_t Ks, int32_t L, c
                       hipStream_t stream);
 
 // pq_train.hip -- learning PQ codebooks (api_pq_train.hip): Lloyd's iteration around launch_pq_encode.  cb [M][Ks][L] f32 is updated
-// in place (a codeword without members keeps its value); codes [n][M] bytes, cols [M][n] bytes (one contiguous column per book)
+// in place (a codeword without members keeps its value); codes [n][M] bytes, cols [M][n] bytes (one contiguous column per book).
+// The uint16 overloads are mi_pqw_train's: the same kernels on two-byte codes
 void launch_pq_init_rows(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, int32_t M, int32_t Ks, int32_t L, float* cb,
                          hipStream_t stream);
 void launch_pq_code_columns(const uint8_t* codes, int32_t M, int64_t n, uint8_t* cols, hipStream_t stream);
@@ -413,6 +416,22 @@ void launch_pq_code_columns(const uint8_t* codes, int32_t M, int64_t n, uint8_t*
 void launch_pq_moved(const uint8_t* a, const uint8_t* b, int64_t bytes, unsigned long long* count, hipStream_t stream);
 void launch_pq_update(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const uint8_t* cols, int32_t M, int32_t Ks, int32_t L,
                       float* cb, hipStream_t stream);
+void launch_pq_code_columns(const uint16_t* codes, int32_t M, int64_t n, uint16_t* cols, hipStream_t stream);
+void launch_pq_moved(const uint16_t* a, const uint16_t* b, int64_t bytes, unsigned long long* count, hipStream_t stream);
+void launch_pq_update(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const uint16_t* cols, int32_t M, int32_t Ks, int32_t L,
+                      float* cb, hipStream_t stream);
+
+// pq_wide.hip -- exact ADC top-K on wide PQ codes (api_pq_wide.hip): Ks <= 8192, a code is M uint16.  Gallery blocks
+// of 64 rows, two books to a dword, dwords transposed: codes[block][w < ceil(M / 2)][64].  Tables, matrix, selection and emit are
+// pq.hip's (launch_pq_table, launch_dense_topk, launch_pq_emit); the encoder is launch_pq_encode's uint16 overload
+constexpr int PQW_MAX_KS = 8192;
+void launch_pqw_check(const uint16_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream);
+void launch_pqw_ingest(const uint16_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream);
+int32_t pqw_query_tile(int32_t Ks, int64_t nq);                // queries per workgroup of the scan (1, 2 or 4): the LDS budget
+void launch_pqw_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, const float* tab, int32_t nq, int32_t qt,
+                     const uint64_t* allow, float* mat, hipStream_t stream);
+void launch_pqw_decode(const uint32_t* codes, int32_t M, int32_t Ks, int32_t L, const float* cb, int64_t row0, int64_t nrows, float* out,
+                       hipStream_t stream);
 
 // ivfpq.hip -- inverted-file search over PQ codes (api_ivfpq.hip).  Blocks of 64 slots from one pool: codes [pblock][MQ][64] in
 // the PQ index's transposed form, rowid [pblock][64] the local row of a slot; list l is the chain of blocks

@@ -11,7 +11,8 @@
 //                     rounds it once to float32, the encoder takes its argmin; pq_adc_row is the scan's row sum
 //   pq_table_kernel   T[q][m][c] = (float)pq_sqdist(x[q][m L ..], C[m][c]), thread = (q, m, c)
 //   pq_encode_kernel  code[i][m] = argmin_c pq_sqdist(x[i][m L ..], C[m][c]), ties to the lower c.  A workgroup takes 64 rows of
-//                     one book; row and codeword slices pass through LDS as float64, 8 accumulators per thread
+//                     one book; row and codeword slices pass through LDS as float64, 8 accumulators per thread.  The code type
+//                     is a template argument: bytes here, uint16 for the wide index (pq_wide.hip), any Ks
 //   pq_scan_kernel    the hot path: a workgroup loads the tables of a tile of QT queries into LDS interleaved query-fastest,
 //                     T[m][c][QT], and walks a slab of row blocks; per (row, book) ONE LDS read of 4 QT bytes at the
 //                     data-dependent address (m Ks + code) returns the entry of every query of the tile.  dist = T[0][code_0] +
@@ -67,10 +68,10 @@ __global__ __launch_bounds__(256) void pq_table_kernel(const InT* __restrict__ x
 // pass in tiles of PE_CT = 32 (8 per thread), the columns in slices of PE_JT = 64; xs[j][row] and cs[c][j] are float64 in LDS
 // (xs: consecutive lanes, consecutive addresses; cs: one address per wave, a broadcast).  The tile constants PE_* are pq_device.h's: ivfr_encode_kernel
 // (ivfpq_residual.hip) is this kernel on residuals and keeps the same tiling.
-template <typename InT>
+template <typename InT, typename CodeT>
 __global__ __launch_bounds__(256) void pq_encode_kernel(const InT* __restrict__ x, int64_t rs, int64_t cs, int64_t n,
                                                        const float* __restrict__ cb, int32_t M, int32_t Ks, int32_t L,
-                                                       uint8_t* __restrict__ out) {
+                                                       CodeT* __restrict__ out) {
   __shared__ double xs[PE_JT][PE_ROWS];
   __shared__ double cw[PE_CT][PE_JT + 1];
   __shared__ double bd[4][PE_ROWS];
@@ -127,7 +128,7 @@ __global__ __launch_bounds__(256) void pq_encode_kernel(const InT* __restrict__ 
         c = vc;
       }
     }
-    out[(row0 + tid) * M + m] = (uint8_t)c;
+    out[(row0 + tid) * M + m] = (CodeT)c;
   }
 }
 
@@ -219,16 +220,27 @@ void launch_pq_table(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n
   }
 }
 
-void launch_pq_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* cb, int32_t M, int32_t Ks, int32_t L,
-                      uint8_t* out, hipStream_t stream) {
+template <typename CodeT>
+static void encode_launch(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* cb, int32_t M, int32_t Ks, int32_t L,
+                          CodeT* out, hipStream_t stream) {
   for (int64_t r = 0; r < n; r += PQ_STEP) {
     const int64_t mm = std::min(PQ_STEP, n - r);
     const dim3 grid((unsigned)((mm + PE_ROWS - 1) / PE_ROWS), (unsigned)M);
     if (dtype == 0)
-      pq_encode_kernel<float><<<grid, 256, 0, stream>>>((const float*)x + r * rs, rs, cs, mm, cb, M, Ks, L, out + r * M);
+      pq_encode_kernel<float, CodeT><<<grid, 256, 0, stream>>>((const float*)x + r * rs, rs, cs, mm, cb, M, Ks, L, out + r * M);
     else
-      pq_encode_kernel<double><<<grid, 256, 0, stream>>>((const double*)x + r * rs, rs, cs, mm, cb, M, Ks, L, out + r * M);
+      pq_encode_kernel<double, CodeT><<<grid, 256, 0, stream>>>((const double*)x + r * rs, rs, cs, mm, cb, M, Ks, L, out + r * M);
   }
+}
+
+void launch_pq_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* cb, int32_t M, int32_t Ks, int32_t L,
+                      uint8_t* out, hipStream_t stream) {
+  encode_launch(x, dtype, rs, cs, n, cb, M, Ks, L, out, stream);
+}
+
+void launch_pq_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* cb, int32_t M, int32_t Ks, int32_t L,
+                      uint16_t* out, hipStream_t stream) {
+  encode_launch(x, dtype, rs, cs, n, cb, M, Ks, L, out, stream);
 }
 
 int32_t pq_query_tile(int32_t M, int32_t Ks, int64_t nq) {

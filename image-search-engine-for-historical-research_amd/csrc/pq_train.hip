@@ -3,8 +3,10 @@
 // holds what goes around it.
 //
 //   pq_init_rows_kernel     the default C_0: codeword c of every book is the book's slice of row floor(c n / Ks), rounded to float32
-//   pq_code_columns_kernel  code bytes [n][M] -> one contiguous column per book, cols[M][n]: the update scans a column 256 times
-//   pq_moved_kernel         number of differing bytes of two code arrays, added into a device uint64 (one vector atomic per
+// The code type is a template argument of the three kernels below: bytes for mi_pq_train, uint16 for mi_pqw_train (Ks <= 8192).
+//
+//   pq_code_columns_kernel  codes [n][M] -> one contiguous column per book, cols[M][n]: the update scans a column Ks times
+//   pq_moved_kernel         number of differing codes of two code arrays, added into a device uint64 (one vector atomic per
 //                           workgroup; integer addition has no order problem)
 //   pq_update_kernel        THE centroid update.  One wave owns (book j, codeword c) and a slice of PU_COLS columns.  It walks the
 //                           book's code column PU_ROWS rows at a step: lane l reads the code byte of row 64 b + l, the wave takes
@@ -33,9 +35,10 @@ __global__ __launch_bounds__(256) void pq_init_rows_kernel(const InT* __restrict
   cb[t] = (float)x[row * rs + ((int64_t)j * L + i) * cs];
 }
 
-// grid = (row blocks of 256, M): consecutive threads write consecutive bytes of one column
-__global__ __launch_bounds__(256) void pq_code_columns_kernel(const uint8_t* __restrict__ codes, int32_t M, int64_t row0, int64_t row1,
-                                                             int64_t n, uint8_t* __restrict__ cols) {
+// grid = (row blocks of 256, M): consecutive threads write consecutive codes of one column
+template <typename CodeT>
+__global__ __launch_bounds__(256) void pq_code_columns_kernel(const CodeT* __restrict__ codes, int32_t M, int64_t row0, int64_t row1,
+                                                             int64_t n, CodeT* __restrict__ cols) {
   const int64_t r = row0 + (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (r >= row1) return;
   const int32_t j = (int32_t)blockIdx.y;
@@ -43,8 +46,13 @@ __global__ __launch_bounds__(256) void pq_code_columns_kernel(const uint8_t* __r
 }
 
 // thread = 16 bytes of both arrays (the buffers are 16-byte aligned; the last thread walks the bytes that are left)
-__global__ __launch_bounds__(256) void pq_moved_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, int64_t bytes,
+template <typename CodeT>
+__global__ __launch_bounds__(256) void pq_moved_kernel(const CodeT* __restrict__ ca, const CodeT* __restrict__ cb, int64_t bytes,
                                                       unsigned long long* __restrict__ count) {
+  constexpr int BITS = 8 * (int)sizeof(CodeT);
+  constexpr uint32_t MASK = (1u << BITS) - 1u;
+  const uint8_t* a = reinterpret_cast<const uint8_t*>(ca);
+  const uint8_t* b = reinterpret_cast<const uint8_t*>(cb);
   __shared__ uint32_t part[4];
   const int64_t o = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 16;
   uint32_t diff = 0;
@@ -54,9 +62,10 @@ __global__ __launch_bounds__(256) void pq_moved_kernel(const uint8_t* __restrict
 #pragma unroll
     for (int e = 0; e < 4; ++e)
 #pragma unroll
-      for (int s = 0; s < 32; s += 8) diff += ((w[e] >> s) & 255u) != 0u;
+      for (int s = 0; s < 32; s += BITS) diff += ((w[e] >> s) & MASK) != 0u;
   } else {
-    for (int64_t p = o; p < bytes; ++p) diff += a[p] != b[p];
+    for (int64_t p = o; p < bytes; p += (int64_t)sizeof(CodeT))
+      diff += *reinterpret_cast<const CodeT*>(a + p) != *reinterpret_cast<const CodeT*>(b + p);
   }
 #pragma unroll
   for (int s = 32; s >= 1; s >>= 1) diff += __shfl_down(diff, s, 64);
@@ -73,15 +82,15 @@ constexpr int PU_CPT = 2, PU_COLS = 64 * PU_CPT;      // L = 128: one wave per (
 constexpr int PU_BLOCKS = 8, PU_ROWS = 64 * PU_BLOCKS; // rows of the code column per step: 8 independent byte loads a lane
 constexpr int PU_AHEAD = 4;                           // member rows whose loads are in flight together
 
-template <typename InT>
+template <typename InT, typename CodeT>
 __global__ __launch_bounds__(64) void pq_update_kernel(const InT* __restrict__ x, int64_t rs, int64_t cs, int64_t n,
-                                                      const uint8_t* __restrict__ cols, int32_t Ks, int32_t L,
+                                                      const CodeT* __restrict__ cols, int32_t Ks, int32_t L,
                                                       float* __restrict__ cb) {
 #pragma clang fp contract(off)
   __shared__ uint32_t list[PU_ROWS];
   const int lane = threadIdx.x;
   const int32_t col0 = (int32_t)blockIdx.x * PU_COLS, c = (int32_t)blockIdx.y, j = (int32_t)blockIdx.z;
-  const uint8_t* col = cols + (int64_t)j * n;
+  const CodeT* col = cols + (int64_t)j * n;
   const unsigned long long below = (1ull << lane) - 1ull;
   bool own[PU_CPT];
   const InT* xc[PU_CPT];
@@ -153,27 +162,54 @@ void launch_pq_init_rows(const void* x, int dtype, int64_t rs, int64_t cs, int64
   else pq_init_rows_kernel<double><<<grid, 256, 0, stream>>>((const double*)x, rs, cs, n, M, Ks, L, cb);
 }
 
-void launch_pq_code_columns(const uint8_t* codes, int32_t M, int64_t n, uint8_t* cols, hipStream_t stream) {
+template <typename CodeT>
+static void code_columns_launch(const CodeT* codes, int32_t M, int64_t n, CodeT* cols, hipStream_t stream) {
   const int64_t step = (int64_t)1 << 30;               // rows per launch: the grid stays below 2^31
   for (int64_t r = 0; r < n; r += step) {
     const int64_t mm = std::min(step, n - r);
-    pq_code_columns_kernel<<<dim3((unsigned)((mm + 255) / 256), (unsigned)M), 256, 0, stream>>>(codes, M, r, r + mm, n, cols);
+    pq_code_columns_kernel<CodeT><<<dim3((unsigned)((mm + 255) / 256), (unsigned)M), 256, 0, stream>>>(codes, M, r, r + mm, n, cols);
   }
 }
 
-void launch_pq_moved(const uint8_t* a, const uint8_t* b, int64_t bytes, unsigned long long* count, hipStream_t stream) {
+template <typename CodeT>
+static void moved_launch(const CodeT* a, const CodeT* b, int64_t bytes, unsigned long long* count, hipStream_t stream) {
   const int64_t step = (int64_t)1 << 40;               // bytes per launch, a multiple of 16 x 256
   for (int64_t o = 0; o < bytes; o += step) {
     const int64_t mm = std::min(step, bytes - o);
-    pq_moved_kernel<<<dim3((unsigned)((mm + 4095) / 4096)), 256, 0, stream>>>(a + o, b + o, mm, count);
+    pq_moved_kernel<CodeT><<<dim3((unsigned)((mm + 4095) / 4096)), 256, 0, stream>>>(a + o / (int64_t)sizeof(CodeT),
+                                                                                    b + o / (int64_t)sizeof(CodeT), mm, count);
   }
+}
+
+template <typename CodeT>
+static void update_launch(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const CodeT* cols, int32_t M, int32_t Ks,
+                          int32_t L, float* cb, hipStream_t stream) {
+  const dim3 grid((unsigned)((L + PU_COLS - 1) / PU_COLS), (unsigned)Ks, (unsigned)M);
+  if (dtype == 0) pq_update_kernel<float, CodeT><<<grid, 64, 0, stream>>>((const float*)x, rs, cs, n, cols, Ks, L, cb);
+  else pq_update_kernel<double, CodeT><<<grid, 64, 0, stream>>>((const double*)x, rs, cs, n, cols, Ks, L, cb);
+}
+
+void launch_pq_code_columns(const uint8_t* codes, int32_t M, int64_t n, uint8_t* cols, hipStream_t stream) {
+  code_columns_launch(codes, M, n, cols, stream);
+}
+void launch_pq_code_columns(const uint16_t* codes, int32_t M, int64_t n, uint16_t* cols, hipStream_t stream) {
+  code_columns_launch(codes, M, n, cols, stream);
+}
+
+void launch_pq_moved(const uint8_t* a, const uint8_t* b, int64_t bytes, unsigned long long* count, hipStream_t stream) {
+  moved_launch(a, b, bytes, count, stream);
+}
+void launch_pq_moved(const uint16_t* a, const uint16_t* b, int64_t bytes, unsigned long long* count, hipStream_t stream) {
+  moved_launch(a, b, bytes, count, stream);
 }
 
 void launch_pq_update(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const uint8_t* cols, int32_t M, int32_t Ks, int32_t L,
                       float* cb, hipStream_t stream) {
-  const dim3 grid((unsigned)((L + PU_COLS - 1) / PU_COLS), (unsigned)Ks, (unsigned)M);
-  if (dtype == 0) pq_update_kernel<float><<<grid, 64, 0, stream>>>((const float*)x, rs, cs, n, cols, Ks, L, cb);
-  else pq_update_kernel<double><<<grid, 64, 0, stream>>>((const double*)x, rs, cs, n, cols, Ks, L, cb);
+  update_launch(x, dtype, rs, cs, n, cols, M, Ks, L, cb, stream);
+}
+void launch_pq_update(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const uint16_t* cols, int32_t M, int32_t Ks, int32_t L,
+                      float* cb, hipStream_t stream) {
+  update_launch(x, dtype, rs, cs, n, cols, M, Ks, L, cb, stream);
 }
 
 }  // namespace mi

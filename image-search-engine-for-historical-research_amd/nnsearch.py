@@ -431,8 +431,27 @@ def _pq_words(n_bits_perbook):
     return 1 << n_bits
 
 
-def _pq_books_path(dataset, n_books, n_words):
-    return os.path.join(os.path.dirname(_gallery_path(dataset)), "mi355_pq_M%d_Ks%d.npz" % (n_books, n_words))
+def _pqw_words(n_bits_perbook):
+    n_bits = int(n_bits_perbook)
+    if n_bits < 1 or (1 << n_bits) > _lib.PQW_MAX_WORDS:
+        raise ValueError("n_bits_perbook = %d: a wide PQ index holds Ks <= %d codewords per book (1 .. 13 bits)"
+                         % (n_bits, _lib.PQW_MAX_WORDS))
+    return 1 << n_bits
+
+
+def _pq_books_path(dataset, n_books, n_words, stem="mi355_pq"):
+    return os.path.join(os.path.dirname(_gallery_path(dataset)), "%s_M%d_Ks%d.npz" % (stem, n_books, n_words))
+
+
+def _nano_pq(index_cls, embedded_features, N_books, N_words):
+    """Nano_PQ_hip / Nano_PQ_wide_hip on their index class."""
+    x = _l2_rows_f32(embedded_features, "embedded_features")
+    N_books, N_words = int(N_books), int(N_words)
+    with index_cls.fit(x, N_books, N_words, iters=20, seed=42) as g:
+        books, codes = g.codebooks, g.get_codes()
+    recon = np.concatenate([books[j][codes[:, j]] for j in range(N_books)], axis=1)
+    codewords = np.ascontiguousarray(books.transpose(1, 0, 2)).reshape(N_words, -1)
+    return codes, codewords, recon
 
 
 def Nano_PQ_hip(embedded_features, N_books, N_words):
@@ -442,13 +461,13 @@ def Nano_PQ_hip(embedded_features, N_books, N_words):
     float32 [N, dim], codebooks[j, code[:, j]] gathered on the host).  The iteration is the one nanopq runs
     (scipy.cluster.vq.kmeans2, minit="matrix") in float64 with float32 centroids; nanopq's random draw of the initial rows
     is not reproduced, so the codebooks differ from nanopq's the way two seeds differ."""
-    x = _l2_rows_f32(embedded_features, "embedded_features")
-    N_books, N_words = int(N_books), int(N_words)
-    with _lib.PQIndex.fit(x, N_books, N_words, iters=20, seed=42) as g:
-        books, codes = g.codebooks, g.get_codes()
-    recon = np.concatenate([books[j][codes[:, j]] for j in range(N_books)], axis=1)
-    codewords = np.ascontiguousarray(books.transpose(1, 0, 2)).reshape(N_words, -1)
-    return codes, codewords, recon
+    return _nano_pq(_lib.PQIndex, embedded_features, N_books, N_words)
+
+
+def Nano_PQ_wide_hip(embedded_features, N_books, N_words):
+    """Nano_PQ_hip on the wide index (_lib.WidePQIndex, _lib.pqw_train): N_words <= 8192, codes uint16 [N, N_books]; everything
+    else as there."""
+    return _nano_pq(_lib.WidePQIndex, embedded_features, N_books, N_words)
 
 
 def matching_Nano_PQ_hip(K, embedded_features_train, embedded_features_test, dataset=None, N_books=16, n_bits_perbook=8,
@@ -457,14 +476,31 @@ def matching_Nano_PQ_hip(K, embedded_features_train, embedded_features_test, dat
     L2-normalised and cast to float32 as the reference does (:866-873), codebooks of N_books books of 2^n_bits_perbook
     codewords learned on the database rows (20 iterations, seed 42), rows encoded, exact ADC top-K
     -> (idx int64 [Q, K], time_per_query).  n_bits_perbook <= 8 (Ks <= 256, one byte per book; the reference's entry points pass
-    13, which this build does not take), 1 <= K <= min(N, 2048).  With a `dataset` the codebooks persist as
+    13: matching_Nano_PQ_wide_hip, `PQ13`, takes it), 1 <= K <= min(N, 2048).  With a `dataset` the codebooks persist as
     outputs/<dataset>/mi355_pq_M<M>_Ks<Ks>.npz (written to a temporary name and renamed): learned and written iff `ifgenerate`,
     otherwise loaded -- a missing file raises FileNotFoundError, as the reference's open() does; dataset=None writes nothing
     (and needs ifgenerate).  The timer spans what the reference's spans (:892-900): the search only, device-synchronised.
     Learning is deterministic (see _lib.pq_train) but does not reproduce nanopq's random draw of initial rows.  Bad input raises
     ValueError before the device is touched."""
+    return _matching_nano_pq(_lib.PQIndex, "mi355_pq", K, embedded_features_train, embedded_features_test, dataset, N_books,
+                             _pq_words(n_bits_perbook), ifgenerate)
+
+
+def matching_Nano_PQ_wide_hip(K, embedded_features_train, embedded_features_test, dataset=None, N_books=16, n_bits_perbook=13,
+                              ifgenerate=True):
+    """matching_Nano_PQ_hip on the wide index, with the reference's signature AND its defaults (src/utils/nnsearch.py:847; its
+    entry points pass N_books = 16, n_bits_perbook = 13: src/offline.py:110): 1 <= n_bits_perbook <= 13, Ks = 2^n_bits_perbook <=
+    8192 codewords per book, uint16 codes (_lib.WidePQIndex, _lib.pqw_train).  Normalisation, learning, timer, K and every refusal
+    are matching_Nano_PQ_hip's; the codebooks persist as outputs/<dataset>/mi355_pqw_M<M>_Ks<Ks>.npz.  Learning needs N >= Ks rows.
+    `PQ13` in MATCHING_METHODS."""
+    return _matching_nano_pq(_lib.WidePQIndex, "mi355_pqw", K, embedded_features_train, embedded_features_test, dataset, N_books,
+                             _pqw_words(n_bits_perbook), ifgenerate)
+
+
+def _matching_nano_pq(index_cls, stem, K, embedded_features_train, embedded_features_test, dataset, N_books, n_words, ifgenerate):
+    """The body of matching_Nano_PQ_hip and matching_Nano_PQ_wide_hip: index_cls is _lib.PQIndex or _lib.WidePQIndex, `stem` names
+    the stored codebooks."""
     N_books, K = int(N_books), int(K)
-    n_words = _pq_words(n_bits_perbook)
     train = _l2_rows_f32(embedded_features_train, "embedded_features_train")
     test = _l2_rows_f32(embedded_features_test, "embedded_features_test")
     if train.shape[1] != test.shape[1]:
@@ -474,24 +510,24 @@ def matching_Nano_PQ_hip(K, embedded_features_train, embedded_features_test, dat
         raise ValueError("K = %d, the database holds %d rows" % (K, num_train))
     if K > TOPK_PATH_MAX_K:
         raise ValueError("K <= %d" % TOPK_PATH_MAX_K)
-    L = _lib._pq_train_shape(num_train, train.shape[1], N_books, n_words, 20)
+    L = _lib._pq_train_shape(num_train, train.shape[1], N_books, n_words, 20, index_cls._MAX_WORDS)
     if dataset is None and not ifgenerate:
         raise ValueError("ifgenerate=False loads the codebooks of a dataset: give one")
     if ifgenerate:
-        books, _ = _lib.pq_train(train, N_books, n_words, iters=20, seed=42)
+        books, _ = index_cls._TRAIN(train, N_books, n_words, iters=20, seed=42)
         if dataset is not None:
-            path = _pq_books_path(dataset, N_books, n_words)
+            path = _pq_books_path(dataset, N_books, n_words, stem)
             os.makedirs(os.path.dirname(path), exist_ok=True)
             tmp = "%s.tmp.%d.%s.npz" % (path, os.getpid(), uuid.uuid4().hex[:12])
             with _path_lock(path):
                 np.savez(tmp, codebooks=books)
                 os.replace(tmp, path)
     else:
-        with np.load(_pq_books_path(dataset, N_books, n_words)) as z:        # (FileNotFoundError when it was never generated)
+        with np.load(_pq_books_path(dataset, N_books, n_words, stem)) as z:        # (FileNotFoundError when it was never generated)
             books = z["codebooks"]
         if books.shape != (N_books, n_words, L):
             raise ValueError("stored codebooks of shape %s, this call takes %s" % (books.shape, (N_books, n_words, L)))
-    with _lib.PQIndex.empty(books, num_train) as g:
+    with index_cls.empty(books, num_train) as g:
         g.add(train)
         t1 = time.time()
         idx, _, _ = g.search(test, K)                  # (synchronous: the results are on the host when it returns)
@@ -752,7 +788,8 @@ def matching_ANNOY_hip(K, embedded_features_train, embedded_features_test, metri
 
 
 MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip, "PQ": matching_Nano_PQ_hip,
-                    "HNSW": matching_HNSW_hip, "PQ_HNSW": matching_HNSW_NanoPQ_hip, "ANNOY": matching_ANNOY_hip}
+                    "PQ13": matching_Nano_PQ_wide_hip, "HNSW": matching_HNSW_hip, "PQ_HNSW": matching_HNSW_NanoPQ_hip,
+                    "ANNOY": matching_ANNOY_hip}
 
 
 def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test):

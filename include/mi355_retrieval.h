@@ -449,7 +449,7 @@ int mi_hamming_append_lsh_device(mi_hamming* h, const void* X_dev, int64_t m, in
  *   encoding  code[r][j] = argmin_c of the float64 sum above (before the rounding), ties to the lower c
  * No certificate, no flag, no fallback path.  The handle is a type of its own, ONE row shard on ONE device; none of the mi_gallery
  * entry points takes it.  Codebooks are learned by mi_pq_train (below); mi_ivfpq (further below) searches such codes by inverted
- * lists.  Rows leave through mi_pq_remove_rows (below).  Out of scope: ks > 256, save / load, sharding, re-ranking.
+ * lists.  Rows leave through mi_pq_remove_rows (below).  ks > 256: the wide index mi_pqw (below).  Out of scope: save / load, sharding, re-ranking.
  * mi_pq_create: n rows of `codes` (row i at codes + i * row_stride_bytes; MI_HOST or MI_DEVICE, device rows complete when the
  * call is made) into an index of `capacity` rows (0 = n); codes == NULL with n == 0 and capacity > 0 gives an empty appendable
  * index.  A code byte >= ks is MI_ERR_INVALID (host codes are checked before a device is touched).  Synchronous. */
@@ -531,6 +531,44 @@ int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stri
  * every iteration that ran and the update of every iteration that had one; at most `capacity` values each are written, the
  * numbers that ran go to out_assignments / out_updates (may be NULL). */
 int mi_pq_train_timing(int32_t capacity, float* out_assign_ms, float* out_update_ms, int32_t* out_assignments, int32_t* out_updates);
+
+/* ---- Wide PQ index: mi_pq with up to 8192 codewords per book, the reference's matching_Nano_PQ as its entry points call it
+ * (N_books = 16, n_bits_perbook = 13; src/offline.py:110).  DESIGN.md 5.14f.  m books (1 <= m <= 64) of ks codewords
+ * (2 <= ks <= 8192) of L = d / m floats, d <= 4096; a code is m uint16, element j the codeword of book j, and crosses this
+ * interface as uint16 [rows][row_stride] (row_stride in ELEMENTS, >= m; what lies between the rows is not read).  The handle is
+ * a type of its own and mirrors mi_pq entry point for entry point; table, distance, order, encoding, allow bitmaps, k <= 2048,
+ * the chunking within "pq_matrix_bytes" and every rule of synchronisation are those stated for mi_pq above, word for word, and
+ * for ks <= 256 every output equals mi_pq's on the same codebooks and codes bit for bit.  A code >= ks is MI_ERR_INVALID (host
+ * codes are checked before a device is touched, device codes by a kernel before anything is written).  The gallery holds
+ * 4 * ceil(m / 2) bytes a row.  Out of scope: ks > 8192, row removal, an IVF or graph index over wide codes. */
+typedef struct mi_pqw mi_pqw; /* opaque */
+int mi_pqw_create(const float* codebooks_host, int32_t d, int32_t m, int32_t ks, const void* codes, int64_t n, int64_t row_stride,
+                  int memspace, int device, int64_t row_offset, int64_t capacity, mi_pqw** out);
+int mi_pqw_append_codes(mi_pqw* h, const void* codes, int64_t rows, int64_t row_stride, int memspace);
+int mi_pqw_add(mi_pqw* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace);
+/* out_codes_host [rows][m] uint16 */
+int mi_pqw_encode(mi_pqw* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace,
+                  uint16_t* out_codes_host);
+/* out_table_host [nq][m][ks] float32: 512 KiB a query at 16 x 8192 */
+int mi_pqw_dtable(mi_pqw* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, float* out_table_host);
+int mi_pqw_search(mi_pqw* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
+                  const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_dist, double* out_seconds);
+int mi_pqw_search_device(mi_pqw* h, const float* q_dev, int64_t nq, int32_t k, const uint64_t* allow_bits_dev, int64_t* out_idx_dev,
+                         float* out_dist_dev, void* stream);
+int mi_pqw_info(const mi_pqw* h, int64_t* n, int32_t* d, int32_t* m, int32_t* ks, int32_t* device, int64_t* row_offset,
+                int64_t* capacity, int64_t* hbm_bytes);
+/* Rows [row0, row0 + nrows) as given or encoded, m uint16 each, to a host buffer. */
+int mi_pqw_get_codes(mi_pqw* h, int64_t row0, int64_t nrows, uint16_t* out_host);
+int mi_pqw_get_codebooks(const mi_pqw* h, float* out_host);
+/* As mi_pq_decode: float32 [nrows][d] to a host buffer. */
+int mi_pqw_decode(mi_pqw* h, int64_t row0, int64_t nrows, float* out_host);
+int mi_pqw_destroy(mi_pqw* h); /* NULL is MI_OK */
+/* mi_pq_train with 2 <= ks <= 8192: the same arguments, the same iteration, the same bits (for ks <= 256 the result equals
+ * mi_pq_train's).  3 * n * m * 2 bytes of codes on the device.  mi_pq_train_timing reports the calling thread's last training,
+ * whichever of the two it was. */
+int mi_pqw_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t m,
+                 int32_t ks, int32_t iters, const float* init_codebooks_host, int device, float* out_codebooks_host,
+                 int64_t* out_moved, double* out_seconds);
 
 /* ---- graph index over PQ codes: best-first search of a neighbour graph whose rows are the codes of ONE mi_pq index, the role of
  * the reference's PQ + HNSW matchers (matching_HNSW_PQ, matching_HNSW_NanoPQ, matching_PQ_HNSW_faiss; src/utils/nnsearch.py:541-683,
