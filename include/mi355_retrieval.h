@@ -66,7 +66,12 @@ int mi_device_count(int* count);
  * kernel streams, and per-row rounding-error norms used for the exactness certificate.
  * Synchronous.  MI_DEVICE data is read on a stream of the handle's own (non-blocking, NOT ordered against any stream of the
  * caller): whatever produced `data` must have completed -- synchronise the producing stream first -- and the pointer may be
- * freed as soon as the call returns.  mi_gallery_append_device is the stream-ordered way in. */
+ * freed as soon as the call returns.  mi_gallery_append_device is the stream-ordered way in.
+ * MI_F64 data is read as float64 and leaves the ingest as float32: under MI_NORM_NONE every element is rounded to f32 as it
+ * stands, under the normalising modes it is scaled in float64 by the row's float64 norm and rounded once.  The same holds for
+ * mi_gallery_append and for the queries of every search on a gallery (mi_knn_search, mi_range_search, mi_knn_search_filtered,
+ * mi_knn_dense_search, mi_knn_dense64_search, mi_rank_*, mi_diffusion_online): float64 holding float32 values gives the float32
+ * answer bit for bit, whatever the strides (tests/test_gpu_input_layouts.py). */
 int mi_gallery_create(const void* data, int64_t n, int32_t d, int dtype, int64_t row_stride,
                       int64_t col_stride, int memspace, int norm_mode, int device,
                       int64_t row_offset, mi_gallery** out);
@@ -859,7 +864,8 @@ int mi_diffusion_offline_nodes(mi_gallery* g, int32_t n_trunc, int32_t kd, doubl
  * lies in [0, N) and no row lists an id twice (MI_ERR_INVALID otherwise). */
 int mi_diffusion_set_offline(mi_gallery* g, const int64_t* ids, const float* vals, int32_t n_trunc);
 /* Online stage (src/utils/Reranking.py:238-253): top-k_query neighbours of each query, sims**gamma, weighted sum of
- * their offline rows, top-`trunc` ranks [nq][trunc] (score desc, idx asc) and scores. */
+ * their offline rows, top-`trunc` ranks [nq][trunc] (score desc, idx asc) and scores.  q: nq x d strided host array, f32 | f64,
+ * used as given (not normalised); the query ingest is mi_knn_search's, so f64 queries are rounded to f32. */
 int mi_diffusion_online(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride,
                         int64_t col_stride, int32_t k_query, int32_t gamma, int32_t trunc,
                         int64_t* out_ranks, float* out_scores);
@@ -878,7 +884,8 @@ int mi_desc_ms_finish_device(float* acc_dev, int32_t b, int32_t d, int32_t nscal
 
 /* ---- building blocks of average_query_expansion / database_augmentation (src/utils/Reranking.py:314-432):
  * out_sum[q][:] = sum_j weights[j] * row(ranks[j,q]) in float64 (means / logspace-weighted sums of neighbours), and
- * column sums of a strided matrix (the centring step). */
+ * column sums of a strided matrix (the centring step).  mi_column_sum / mi_column_sum_device: X f32 | f64, any strides; every
+ * element is promoted to float64 and summed in float64 -- MI_F64 input is never rounded to float32. */
 int mi_gather_weighted(mi_gallery* g, const int64_t* ranks, int64_t rank_stride_j, int64_t rank_stride_q, int64_t nq,
                        int32_t k, const double* weights, double* out_sum);
 int mi_column_sum(const void* X, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int device,
