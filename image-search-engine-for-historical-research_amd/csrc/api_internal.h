@@ -16,8 +16,10 @@
 //   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix;
 //                     radius search and self-join through one ballot per (block, query)
 //   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
+//   pq_flat.h         the host functions of both flat PQ indexes, templates over the handle (PqFlat<CodeT> below); api_pq.hip and
+//                     api_pq_wide.hip forward their entry points to them
 //   api_pq_train.hip  learning PQ codebooks (mi_pq_train, mi_pqw_train): deterministic Lloyd iterations on device-resident rows
-//   api_pq_wide.hip   wide PQ index (mi_pqw): uint16 codes, Ks <= 8192, exact ADC top-K with the books passing through LDS in groups
+//   api_pq_wide.hip   wide PQ index (mi_pqw): uint16 codes, Ks <= 8192, the books pass through LDS in groups (pq_wide.hip)
 //   api_ivfpq.hip     IVF index over PQ codes (mi_ivfpq): coarse lists as chains of 64-slot blocks, exact ADC top-K over the probed lists
 //                     (row removal of both PQ handles: mi_pq_remove_rows in api_pq.hip, mi_ivfpq_remove_rows here; kernels in pq_remove.hip)
 //   api_lsh.hip       LSH codes (mi_lsh_encode*, mi_hamming_append_lsh_device): f64 projection to sign bits, fused (lsh.hip)
@@ -385,19 +387,23 @@ struct mi_hamming {
   std::mutex mu;
 };
 
-// the PQ index (api_pq.hip; api_pq_graph.hip searches a neighbour graph over its codes)
-struct mi_pq {
+// what both flat PQ indexes hold (pq_flat.h has the host functions over it): CodeT is a code of one book, uint8_t for mi_pq (Ks <= 256,
+// four books to a dword) and uint16_t for mi_pqw (Ks <= 8192, two)
+template <typename CodeT>
+struct PqFlat {
+  typedef CodeT Code;
+  static constexpr int32_t CODE_VALUES = 1 << (8 * sizeof(CodeT));   // no code of this width reaches it
   int device = 0;
   int64_t n = 0, cap = 0, row_offset = 0;
-  int32_t d = 0, m = 0, ks = 0, L = 0, MQ = 0;     // columns, books, codewords per book, columns per book, dwords of a code
+  int32_t d = 0, m = 0, ks = 0, L = 0, MW = 0;     // columns, books, codewords per book, columns per book, dwords of a code
   std::vector<float> cb_host;                      // [m][ks][L]
   DeviceBufSet bufs;                               // every device allocation of the handle: hbm_bytes is bufs.bytes()
   DeviceBuf<float> cb{bufs};                       // (cb, codes, flag: exactly their size, allocated at creation)
-  DeviceBuf<uint32_t> codes{bufs};                 // [ceil(cap / 64)][MQ][64]
+  DeviceBuf<uint32_t> codes{bufs};                 // [ceil(cap / 64)][MW][64]
   DeviceBuf<uint32_t> flag{bufs};                  // raised by the check of device-resident codes (256 bytes)
   hipStream_t stream = nullptr;
   DeviceBuf<char> xraw{bufs};                      // rows / queries of a host call, packed [rows][d] in their own type
-  DeviceBuf<uint8_t> cbytes{bufs};                 // packed code bytes [rows][m]: host codes on their way in, encoder output
+  DeviceBuf<CodeT> cstage{bufs};                   // packed codes [rows][m]: host codes on their way in, encoder output
   DeviceBuf<float> tab{bufs};                      // distance tables [queries of a chunk][m][ks]
   DeviceBuf<float> mat{bufs};                      // negated distances [queries of a chunk][round_up(n, 64)]
   DeviceBuf<int64_t> tidx{bufs};                   // [queries of a chunk][ke] what the selection returns
@@ -405,38 +411,20 @@ struct mi_pq {
   DeviceBuf<uint64_t> bits{bufs};                  // device copy of a host bitmap
   DeviceBuf<int64_t> oidx{bufs};                   // results of a host call
   DeviceBuf<float> odist{bufs};
-  DeviceBuf<uint32_t> rmpref{bufs}, rmstage{bufs}; // mi_pq_remove_rows: prefix counts per bitmap word; staging blocks [..][MQ][64]
+  std::mutex mu;
+};
+// the PQ index (api_pq.hip; api_pq_graph.hip searches a neighbour graph over its codes)
+struct mi_pq : PqFlat<uint8_t> {
+  DeviceBuf<uint32_t> rmpref{bufs}, rmstage{bufs}; // mi_pq_remove_rows: prefix counts per bitmap word; staging blocks [..][MW][64]
   // bumped by every call that changes the rows (mi_pq_add, mi_pq_append_codes, mi_pq_remove_rows): what a mi_pq_graph records,
   // since rows can leave and as many come back.  Internal; nothing reports it
   uint64_t mod = 0;
-  std::mutex mu;
 };
 // the search proper on stream s (api_pq.hip): queries on the device (any strides), results go to device buffers
 MI_INTERNAL int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k,
                                const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s);
-
-// the wide PQ index (api_pq_wide.hip): mi_pq with uint16 codes, two books to a dword, Ks <= 8192
-struct mi_pqw {
-  int device = 0;
-  int64_t n = 0, cap = 0, row_offset = 0;
-  int32_t d = 0, m = 0, ks = 0, L = 0, MH = 0;     // columns, books, codewords per book, columns per book, dwords of a code
-  std::vector<float> cb_host;                      // [m][ks][L]
-  DeviceBufSet bufs;                               // every device allocation of the handle: hbm_bytes is bufs.bytes()
-  DeviceBuf<float> cb{bufs};                       // (cb, codes, flag: exactly their size, allocated at creation)
-  DeviceBuf<uint32_t> codes{bufs};                 // [ceil(cap / 64)][MH][64]
-  DeviceBuf<uint32_t> flag{bufs};                  // raised by the check of device-resident codes (256 bytes)
-  hipStream_t stream = nullptr;
-  DeviceBuf<char> xraw{bufs};                      // rows / queries of a host call, packed [rows][d] in their own type
-  DeviceBuf<uint16_t> cwords{bufs};                // packed codes [rows][m]: host codes on their way in, encoder output
-  DeviceBuf<float> tab{bufs};                      // distance tables [queries of a chunk][m][ks]
-  DeviceBuf<float> mat{bufs};                      // negated distances [queries of a chunk][round_up(n, 64)]
-  DeviceBuf<int64_t> tidx{bufs};                   // [queries of a chunk][ke] what the selection returns
-  DeviceBuf<float> tneg{bufs};
-  DeviceBuf<uint64_t> bits{bufs};                  // device copy of a host bitmap
-  DeviceBuf<int64_t> oidx{bufs};                   // results of a host call
-  DeviceBuf<float> odist{bufs};
-  std::mutex mu;
-};
+// the wide PQ index (api_pq_wide.hip)
+struct mi_pqw : PqFlat<uint16_t> {};
 
 // ---- api_state.hip
 MI_INTERNAL int ws_free(Workspace& ws);
@@ -528,13 +516,36 @@ static inline int check_host_queries(int32_t d, const void* q, int64_t nq, int d
   REQUIRE(finite, "queries must be finite");
   return MI_OK;
 }
-// the first m bytes of every row (code bytes, list ids) are below `limit`
-static inline bool codes_below(const uint8_t* p, int64_t rows, int64_t stride, int32_t m, int32_t limit) {
-  if (limit >= 256) return true;
+// the first m codes of every row (code bytes or uint16, list ids) are below `limit`
+template <typename CodeT>
+static inline bool codes_below(const CodeT* p, int64_t rows, int64_t stride, int32_t m, int32_t limit) {
+  if (limit >= PqFlat<CodeT>::CODE_VALUES) return true;
   for (int64_t r = 0; r < rows; ++r)
     for (int32_t b = 0; b < m; ++b)
       if (p[r * stride + b] >= limit) return false;
   return true;
+}
+// behind a check launch on `s` (launch_pq_check, launch_ivf_check): *raised = the check raised the handle's flag, which is cleared
+// again for the next check
+static inline int check_flag(uint32_t* flag, hipStream_t s, bool* raised) {
+  uint32_t f = 0;
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(&f, flag, 4, hipMemcpyDeviceToHost, s));
+  HIPC(hipStreamSynchronize(s));
+  if (f) {
+    HIPC(hipMemsetAsync(flag, 0, 4, s));
+    HIPC(hipStreamSynchronize(s));
+  }
+  *raised = f != 0;
+  return MI_OK;
+}
+// the m codes of the row in slot `slot` (block * 64 + lane) of `blocks`, transposed 64-row blocks of `dwords` dwords a code, the
+// first of them block 0 -> dst
+template <typename CodeT>
+static inline void unpack_code_row(const uint32_t* blocks, int64_t slot, int32_t dwords, int32_t m, CodeT* dst) {
+  constexpr int32_t PER = pq_codes_per_dword<CodeT>(), BITS = 8 * sizeof(CodeT);
+  const uint32_t* src = blocks + (slot >> 6) * dwords * 64 + (slot & 63);
+  for (int32_t j = 0; j < m; ++j) dst[j] = (CodeT)(src[(int64_t)(j / PER) * 64] >> (BITS * (j % PER)));
 }
 // `rows` host rows of d elements from row r0 on -> xraw (grown to fit), packed [rows][d] in their own type, on `stream`.  Rows that
 // are not contiguous are packed on the host first, in `pack` (the copy has completed on return in that case)

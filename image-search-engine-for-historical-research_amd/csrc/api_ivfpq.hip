@@ -120,23 +120,14 @@ static int ivf_ingest(mi_ivfpq* h, const void* codes, const uint8_t* list_ids, i
   int rc;
   std::vector<uint8_t> lists_back;
   if (memspace == MI_DEVICE) {
-    uint32_t f = 0;
+    bool bad_code = false, bad_list = false;
     if (h->ks < 256) launch_pq_check((const uint8_t*)codes, stride, h->m, h->ks, rows, h->flag, s);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(&f, h->flag, 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    uint32_t f2 = 0;
-    if (f == 0 && h->nlist < 256) {
+    if ((rc = check_flag(h->flag, s, &bad_code)) != MI_OK) return rc;
+    if (!bad_code && h->nlist < 256) {
       launch_ivf_check(list_ids, h->nlist, rows, h->flag, s);
-      HIPC(hipGetLastError());
-      HIPC(hipMemcpyAsync(&f2, h->flag, 4, hipMemcpyDeviceToHost, s));
-      HIPC(hipStreamSynchronize(s));
+      if ((rc = check_flag(h->flag, s, &bad_list)) != MI_OK) return rc;
     }
-    if (f || f2) {
-      HIPC(hipMemsetAsync(h->flag, 0, 4, s));
-      HIPC(hipStreamSynchronize(s));
-      return fail(MI_ERR_INVALID, f ? "a code byte is >= ks" : "a list id is >= nlist");
-    }
+    if (bad_code || bad_list) return fail(MI_ERR_INVALID, bad_code ? "a code byte is >= ks" : "a list id is >= nlist");
     lists_back.resize((size_t)rows);
     HIPC(hipMemcpy(lists_back.data(), list_ids, (size_t)rows, hipMemcpyDeviceToHost));
     list_ids = lists_back.data();
@@ -421,22 +412,16 @@ int mi_ivfpq_residual_rows(mi_ivfpq* h, const void* x, int64_t rows, int dtype, 
   std::lock_guard<std::mutex> lock(h->mu);
   HIPC(hipSetDevice(h->device));
   hipStream_t s = h->stream;
+  int rc;
   if (list_ids && memspace == MI_DEVICE && h->nlist < 256) {
-    uint32_t f = 0;
+    bool bad_list;
     launch_ivf_check(list_ids, h->nlist, rows, h->flag, s);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(&f, h->flag, 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    if (f) {
-      HIPC(hipMemsetAsync(h->flag, 0, 4, s));
-      HIPC(hipStreamSynchronize(s));
-      return fail(MI_ERR_INVALID, "a list id is >= nlist");
-    }
+    if ((rc = check_flag(h->flag, s, &bad_list)) != MI_OK) return rc;
+    if (bad_list) return fail(MI_ERR_INVALID, "a list id is >= nlist");
   }
   const size_t esz = dtype == MI_F32 ? 4 : 8;
   const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * 8));
   const int64_t most = std::min(step, rows);
-  int rc;
   if ((rc = h->lbytes.grow((size_t)most)) != MI_OK) return rc;
   if (out_memspace == MI_HOST && (rc = h->odist.grow((size_t)(most * h->d))) != MI_OK) return rc;
   std::vector<char> pack;
@@ -613,12 +598,7 @@ int mi_ivfpq_get_rows(mi_ivfpq* h, int64_t row0, int64_t nrows, uint8_t* out_cod
     while (t1 < by_slot.size() && (by_slot[t1].first >> 6) <= b1 && (by_slot[t1].first >> 6) - b0 < 65536) b1 = (by_slot[t1++].first >> 6) + 1;
     buf.resize((size_t)((b1 - b0) * blk_words));
     HIPC(hipMemcpy(buf.data(), h->codes + b0 * blk_words, buf.size() * 4, hipMemcpyDeviceToHost));
-    for (size_t t = t0; t < t1; ++t) {
-      const int64_t slot = by_slot[t].first;
-      const uint32_t* src = buf.data() + ((slot >> 6) - b0) * blk_words + (slot & 63);
-      uint8_t* dst = out_codes_host + by_slot[t].second * h->m;
-      for (int32_t j = 0; j < h->m; ++j) dst[j] = (uint8_t)(src[(int64_t)(j >> 2) * 64] >> (8 * (j & 3)));
-    }
+    for (size_t t = t0; t < t1; ++t) unpack_code_row(buf.data(), by_slot[t].first - b0 * 64, h->MQ, h->m, out_codes_host + by_slot[t].second * h->m);
     t0 = t1;
   }
   return MI_OK;

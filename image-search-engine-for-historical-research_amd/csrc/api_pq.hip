@@ -3,100 +3,13 @@
 // own: codebooks, codes in transposed 64-row blocks, a float32 matrix of negated distances of at most "pq_matrix_bytes" (queries
 // go through it in chunks), grow-only staging for rows, tables, bitmap and results.  The answer is a function of the inputs
 // alone (float64 table entries rounded once, float32 sums in book order, order by (distance, id)): no certificate, no flag.
-#include "api_internal.h"
+// The host functions are pq_flat.h's, shared with the wide index (api_pq_wide.hip): the entry points below forward to them with
+// H = mi_pq.  What only this index has is here: the row removal, and the search core as a symbol for api_pq_graph.hip.
+#include "pq_flat.h"
 
-// rows of code bytes (host: checked by the caller; device: checked here) -> rows n .. n + rows of the index, synchronous on the
-// handle's stream.  A device code byte >= ks: MI_ERR_INVALID, nothing written.
-static int pq_ingest(mi_pq* h, const void* codes, int64_t rows, int64_t stride, int memspace) {
-  hipStream_t s = h->stream;
-  if (memspace == MI_DEVICE) {
-    if (h->ks < 256) {
-      uint32_t f = 0;
-      launch_pq_check((const uint8_t*)codes, stride, h->m, h->ks, rows, h->flag, s);
-      HIPC(hipGetLastError());
-      HIPC(hipMemcpyAsync(&f, h->flag, 4, hipMemcpyDeviceToHost, s));
-      HIPC(hipStreamSynchronize(s));
-      if (f) {
-        HIPC(hipMemsetAsync(h->flag, 0, 4, s));
-        HIPC(hipStreamSynchronize(s));
-        return fail(MI_ERR_INVALID, "a code byte is >= ks");
-      }
-    }
-    launch_pq_ingest((const uint8_t*)codes, stride, h->m, h->n, rows, h->codes, s);
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(s));
-    return MI_OK;
-  }
-  const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / h->m);
-  int rc;
-  if ((rc = h->cbytes.grow((size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
-  for (int64_t r = 0; r < rows; r += step) {
-    const int64_t mm = std::min(step, rows - r);
-    const uint8_t* src = (const uint8_t*)codes + r * stride;
-    if (stride == h->m || mm == 1) HIPC(hipMemcpyAsync(h->cbytes, src, (size_t)mm * h->m, hipMemcpyHostToDevice, s));
-    else HIPC(hipMemcpy2DAsync(h->cbytes, (size_t)h->m, src, (size_t)stride, (size_t)h->m, (size_t)mm, hipMemcpyHostToDevice, s));
-    launch_pq_ingest(h->cbytes, h->m, h->m, h->n + r, mm, h->codes, s);
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(s));                 // the staging buffer is reused by the next block
-  }
-  return MI_OK;
-}
-
-// encodes `rows` rows (host or device) in blocks; after each block `sink(r, mm)` consumes the packed code bytes of rows r .. r + mm
-// in h->cbytes.  Synchronous on the handle's stream.
-template <typename Sink>
-static int pq_encode_blocks(mi_pq* h, const void* x, int64_t rows, int dtype, int64_t rs, int64_t cs, int memspace, Sink sink) {
-  const size_t esz = dtype == MI_F32 ? 4 : 8;
-  const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * (int64_t)esz));
-  hipStream_t s = h->stream;
-  int rc;
-  if ((rc = h->cbytes.grow((size_t)std::min(step, rows) * h->m)) != MI_OK) return rc;
-  std::vector<char> pack;
-  for (int64_t r = 0; r < rows; r += step) {
-    const int64_t mm = std::min(step, rows - r);
-    if (memspace == MI_HOST) {
-      if ((rc = stage_host_rows(h->xraw, h->d, h->stream, x, r, mm, dtype, rs, cs, pack)) != MI_OK) return rc;
-      launch_pq_encode(h->xraw, dtype, h->d, 1, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
-    } else {
-      launch_pq_encode((const char*)x + (size_t)r * rs * esz, dtype, rs, cs, mm, h->cb, h->m, h->ks, h->L, h->cbytes, s);
-    }
-    HIPC(hipGetLastError());
-    if ((rc = sink(r, mm)) != MI_OK) return rc;
-  }
-  return MI_OK;
-}
-
-// the search proper on stream s: queries on the device (any strides), results go to device buffers
 int pq_search_core(mi_pq* h, const void* q_dev, int dtype, int64_t rs, int64_t cs, int64_t nq, int32_t k,
                    const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_dist_dev, hipStream_t s) {
-  const int64_t npad = round_up(h->n, 64);
-  const size_t esz = dtype == MI_F32 ? 4 : 8;
-  if (npad == 0) {
-    launch_pq_emit(nullptr, nullptr, nq, 0, k, h->row_offset, out_idx_dev, out_dist_dev, s);
-    HIPC(hipGetLastError());
-    return MI_OK;
-  }
-  // queries per pass through the matrix: whole tiles of 4, one tile at the least
-  const int64_t budget = g_pq_matrix_bytes.load();
-  int64_t qc = std::min<int64_t>({nq, budget / (npad * 4), (int64_t)1 << 20});
-  qc = std::max<int64_t>(4, qc / 4 * 4);
-  qc = std::min(qc, nq);
-  const int32_t ke = (int32_t)std::min<int64_t>(k, npad);
-  const int64_t per = (int64_t)h->m * h->ks;
-  int rc;
-  if ((rc = h->tab.grow((size_t)(qc * per))) != MI_OK) return rc;
-  if ((rc = h->mat.grow((size_t)(qc * npad))) != MI_OK) return rc;
-  if ((rc = h->tidx.grow((size_t)(qc * ke))) != MI_OK) return rc;
-  if ((rc = h->tneg.grow((size_t)(qc * ke))) != MI_OK) return rc;
-  for (int64_t q0 = 0; q0 < nq; q0 += qc) {
-    const int32_t b = (int32_t)std::min<int64_t>(qc, nq - q0);
-    launch_pq_table((const char*)q_dev + (size_t)q0 * rs * esz, dtype, rs, cs, b, h->cb, h->m, h->ks, h->L, h->tab, s);
-    launch_pq_scan(h->codes, h->m, h->ks, h->n, h->tab, b, pq_query_tile(h->m, h->ks, b), allow_dev, h->mat, s);
-    launch_dense_topk(h->mat, npad, npad, b, ke, 0, h->tidx, h->tneg, s);
-    launch_pq_emit(h->tidx, h->tneg, b, ke, k, h->row_offset, out_idx_dev + q0 * k, out_dist_dev ? out_dist_dev + q0 * k : nullptr, s);
-  }
-  HIPC(hipGetLastError());
-  return MI_OK;
+  return pq_flat_search_core(h, q_dev, dtype, rs, cs, nq, k, allow_dev, out_idx_dev, out_dist_dev, s);
 }
 
 int remove_plan(const uint64_t* remove_bits, int memspace, int64_t n, RemovePlan* plan) {
@@ -125,241 +38,46 @@ extern "C" {
 
 int mi_pq_create(const float* codebooks_host, int32_t d, int32_t m, int32_t ks, const void* codes, int64_t n, int64_t row_stride_bytes,
                  int memspace, int device, int64_t row_offset, int64_t capacity, mi_pq** out) {
-  REQUIRE(out, "null pointer: out");
-  REQUIRE(codebooks_host, "null pointer: codebooks_host");
-  REQUIRE(m >= 1 && m <= 64, "m (books) must be in [1, 64]");
-  REQUIRE(ks >= 2 && ks <= 256, "ks (codewords per book) must be in [2, 256]");
-  REQUIRE(d >= 1 && d <= 4096, "d must be in [1, 4096]");
-  REQUIRE(d % m == 0, "d must be a multiple of m");
-  REQUIRE(n >= 0, "negative number of rows");
-  REQUIRE(capacity >= 0, "negative capacity");
-  REQUIRE(capacity == 0 || capacity >= n, "capacity below the number of rows");
-  REQUIRE(codes || n == 0, "null pointer: codes");
-  REQUIRE(n >= 1 || capacity >= 1, "an empty index needs a capacity");
-  REQUIRE(n == 0 || row_stride_bytes >= m, "row_stride_bytes below m");
-  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
-  if (capacity == 0) capacity = n;
-  REQUIRE(capacity < ((int64_t)1 << 32) - 64, "an index holds fewer than 2^32 - 64 rows");
-  const size_t cb_count = (size_t)ks * d;
-  for (size_t i = 0; i < cb_count; ++i) REQUIRE(std::isfinite(codebooks_host[i]), "codebooks must be finite");
-  REQUIRE(memspace != MI_HOST || codes_below((const uint8_t*)codes, n, row_stride_bytes, m, ks), "a code byte is >= ks");
-  HIPC(hipSetDevice(device));
-  mi_pq* h = new mi_pq();
-  h->device = device;
-  h->cap = capacity;
-  h->row_offset = row_offset;
-  h->d = d;
-  h->m = m;
-  h->ks = ks;
-  h->L = d / m;
-  h->MQ = (m + 3) / 4;
-  h->cb_host.assign(codebooks_host, codebooks_host + cb_count);
-  const size_t codes_words = (size_t)((capacity + 63) / 64) * h->MQ * 64;
-  auto cleanup = [&](int code) {
-    mi_pq_destroy(h);
-    return code;
-  };
-  hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = h->codes.alloc(codes_words);
-  if (e == hipSuccess) e = h->cb.alloc(cb_count);
-  if (e == hipSuccess) e = h->flag.alloc(64);
-  if (e == hipSuccess) e = hipMemsetAsync(h->codes, 0, codes_words * 4, h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(h->flag, 0, 256, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->cb, h->cb_host.data(), cb_count * 4, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess)
-    return cleanup(fail(e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, std::string("PQ index: ") + hipGetErrorString(e)));
-  if (n > 0) {
-    const int rc = pq_ingest(h, codes, n, row_stride_bytes, memspace);
-    if (rc != MI_OK) return cleanup(rc);
-    h->n = n;
-  }
-  *out = h;
-  return MI_OK;
+  return pq_flat_create(codebooks_host, d, m, ks, codes, n, row_stride_bytes, memspace, device, row_offset, capacity, out);
 }
 
 int mi_pq_append_codes(mi_pq* h, const void* codes, int64_t rows, int64_t row_stride_bytes, int memspace) {
-  REQUIRE(h, "null handle");
-  REQUIRE(rows >= 0, "negative number of rows");
-  REQUIRE(codes || rows == 0, "null pointer: codes");
-  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
-  REQUIRE(rows == 0 || row_stride_bytes >= h->m, "row_stride_bytes below m");
-  std::lock_guard<std::mutex> lock(h->mu);
-  REQUIRE(h->n + rows <= h->cap, "index capacity exceeded");
-  if (rows == 0) return MI_OK;
-  REQUIRE(memspace != MI_HOST || codes_below((const uint8_t*)codes, rows, row_stride_bytes, h->m, h->ks), "a code byte is >= ks");
-  HIPC(hipSetDevice(h->device));
-  const int rc = pq_ingest(h, codes, rows, row_stride_bytes, memspace);
-  if (rc != MI_OK) return rc;
-  h->n += rows;
-  ++h->mod;
-  return MI_OK;
+  return pq_flat_append_codes(h, codes, rows, row_stride_bytes, memspace);
 }
 
 int mi_pq_add(mi_pq* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace) {
-  REQUIRE(h, "null handle");
-  REQUIRE_ROWS(x, rows, dtype, row_stride, col_stride, memspace);
-  std::lock_guard<std::mutex> lock(h->mu);
-  REQUIRE(h->n + rows <= h->cap, "index capacity exceeded");
-  if (rows == 0) return MI_OK;
-  HIPC(hipSetDevice(h->device));
-  const int64_t n0 = h->n;
-  // a block's codes land behind the rows that are there; h->n moves only when every block is in
-  const int rc = pq_encode_blocks(h, x, rows, dtype, row_stride, col_stride, memspace, [&](int64_t r, int64_t mm) {
-    launch_pq_ingest(h->cbytes, h->m, h->m, n0 + r, mm, h->codes, h->stream);
-    HIPC(hipGetLastError());
-    HIPC(hipStreamSynchronize(h->stream));
-    return (int)MI_OK;
-  });
-  if (rc != MI_OK) return rc;
-  h->n = n0 + rows;
-  ++h->mod;
-  return MI_OK;
+  return pq_flat_add(h, x, rows, dtype, row_stride, col_stride, memspace);
 }
 
 int mi_pq_encode(mi_pq* h, const void* x, int64_t rows, int dtype, int64_t row_stride, int64_t col_stride, int memspace,
                  uint8_t* out_codes_host) {
-  REQUIRE(h, "null handle");
-  REQUIRE_ROWS(x, rows, dtype, row_stride, col_stride, memspace);
-  REQUIRE(out_codes_host || rows == 0, "null pointer: out_codes_host");
-  if (rows == 0) return MI_OK;
-  std::lock_guard<std::mutex> lock(h->mu);
-  HIPC(hipSetDevice(h->device));
-  return pq_encode_blocks(h, x, rows, dtype, row_stride, col_stride, memspace, [&](int64_t r, int64_t mm) {
-    HIPC(hipMemcpyAsync(out_codes_host + r * h->m, h->cbytes, (size_t)mm * h->m, hipMemcpyDeviceToHost, h->stream));
-    HIPC(hipStreamSynchronize(h->stream));
-    return (int)MI_OK;
-  });
+  return pq_flat_encode(h, x, rows, dtype, row_stride, col_stride, memspace, out_codes_host);
 }
 
 int mi_pq_dtable(mi_pq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, float* out_table_host) {
-  REQUIRE(h, "null handle");
-  REQUIRE(nq >= 0, "nq must be >= 0");
-  REQUIRE(nq == 0 || (q && out_table_host), "null pointer");
-  if (nq == 0) return MI_OK;
-  int rc;
-  if ((rc = check_host_queries(h->d, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
-  std::lock_guard<std::mutex> lock(h->mu);
-  HIPC(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const int64_t per = (int64_t)h->m * h->ks;
-  const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / (per * 4));
-  if ((rc = h->tab.grow((size_t)(std::min(step, nq) * per))) != MI_OK) return rc;
-  std::vector<char> pack;
-  for (int64_t q0 = 0; q0 < nq; q0 += step) {
-    const int64_t b = std::min(step, nq - q0);
-    if ((rc = stage_host_rows(h->xraw, h->d, h->stream, q, q0, b, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
-    launch_pq_table(h->xraw, dtype, h->d, 1, b, h->cb, h->m, h->ks, h->L, h->tab, s);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(out_table_host + q0 * per, h->tab, (size_t)(b * per) * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-  }
-  return MI_OK;
+  return pq_flat_dtable(h, q, nq, dtype, row_stride, col_stride, out_table_host);
 }
 
 int mi_pq_search(mi_pq* h, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride, int32_t k,
                  const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_dist, double* out_seconds) {
-  REQUIRE(h, "null handle");
-  REQUIRE(k >= 1 && k <= 2048, "k must be in [1, 2048]");
-  REQUIRE(nq >= 0, "nq must be >= 0");
-  REQUIRE(nq == 0 || q, "null pointer: queries");
-  REQUIRE(nq == 0 || out_idx, "null pointer: out_idx");
-  REQUIRE(!allow_bits || allow_memspace == MI_HOST || allow_memspace == MI_DEVICE, "allow_memspace must be MI_HOST or MI_DEVICE");
-  if (out_seconds) *out_seconds = 0.0;
-  if (nq == 0) return MI_OK;
-  int rc;
-  if ((rc = check_host_queries(h->d, q, nq, dtype, row_stride, col_stride)) != MI_OK) return rc;
-  std::lock_guard<std::mutex> lock(h->mu);
-  const auto t0 = std::chrono::steady_clock::now();
-  HIPC(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const size_t cnt = (size_t)nq * k;
-  if ((rc = h->oidx.grow(cnt)) != MI_OK) return rc;
-  if (out_dist && (rc = h->odist.grow(cnt)) != MI_OK) return rc;
-  const uint64_t* allow_dev;
-  if ((rc = allow_on_device(h->bits, allow_bits, allow_memspace, h->n, s, &allow_dev)) != MI_OK) return rc;
-  std::vector<char> pack;
-  if ((rc = stage_host_rows(h->xraw, h->d, h->stream, q, 0, nq, dtype, row_stride, col_stride, pack)) != MI_OK) return rc;
-  if ((rc = pq_search_core(h, h->xraw, dtype, h->d, 1, nq, k, allow_dev, h->oidx, out_dist ? h->odist.get() : nullptr, s)) != MI_OK) return rc;
-  return topk_to_host(out_idx, h->oidx, out_dist, h->odist.get(), cnt, s, t0, out_seconds);
+  return pq_flat_search(h, q, nq, dtype, row_stride, col_stride, k, allow_bits, allow_memspace, out_idx, out_dist, out_seconds);
 }
 
 int mi_pq_search_device(mi_pq* h, const float* q_dev, int64_t nq, int32_t k, const uint64_t* allow_bits_dev, int64_t* out_idx_dev,
                         float* out_dist_dev, void* stream) {
-  REQUIRE(h, "null handle");
-  REQUIRE(k >= 1 && k <= 2048, "k must be in [1, 2048]");
-  REQUIRE(nq >= 0, "nq must be >= 0");
-  REQUIRE(nq == 0 || (q_dev && out_idx_dev), "null pointer");
-  if (nq == 0) return MI_OK;
-  HIPC(hipSetDevice(h->device));
-  return pq_search_core(h, q_dev, MI_F32, h->d, 1, nq, k, allow_bits_dev, out_idx_dev, out_dist_dev, (hipStream_t)stream);
+  return pq_flat_search_device(h, q_dev, nq, k, allow_bits_dev, out_idx_dev, out_dist_dev, stream);
 }
 
 int mi_pq_info(const mi_pq* h, int64_t* n, int32_t* d, int32_t* m, int32_t* ks, int32_t* device, int64_t* row_offset, int64_t* capacity,
                int64_t* hbm_bytes) {
-  REQUIRE(h, "null handle");
-  if (n) *n = h->n;
-  if (d) *d = h->d;
-  if (m) *m = h->m;
-  if (ks) *ks = h->ks;
-  if (device) *device = h->device;
-  if (row_offset) *row_offset = h->row_offset;
-  if (capacity) *capacity = h->cap;
-  if (hbm_bytes) *hbm_bytes = (int64_t)h->bufs.bytes();
-  return MI_OK;
+  return pq_flat_info(h, n, d, m, ks, device, row_offset, capacity, hbm_bytes);
 }
 
-int mi_pq_get_codes(mi_pq* h, int64_t row0, int64_t nrows, uint8_t* out_host) {
-  REQUIRE(h, "null handle");
-  REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= h->n, "row range outside the index");
-  REQUIRE(out_host || nrows == 0, "null pointer: out_host");
-  if (nrows == 0) return MI_OK;
-  std::lock_guard<std::mutex> lock(h->mu);
-  HIPC(hipSetDevice(h->device));
-  HIPC(hipStreamSynchronize(h->stream));
-  const int64_t blk_words = (int64_t)h->MQ * 64;
-  const int64_t step = 65536;                      // blocks per copy
-  std::vector<uint32_t> buf;
-  for (int64_t b0 = row0 / 64; b0 * 64 < row0 + nrows; b0 += step) {
-    const int64_t b1 = std::min(b0 + step, (row0 + nrows + 63) / 64);
-    buf.resize((size_t)((b1 - b0) * blk_words));
-    HIPC(hipMemcpy(buf.data(), h->codes + b0 * blk_words, buf.size() * 4, hipMemcpyDeviceToHost));
-    for (int64_t r = std::max(row0, b0 * 64); r < std::min(row0 + nrows, b1 * 64); ++r) {
-      const uint32_t* src = buf.data() + ((r >> 6) - b0) * blk_words + (r & 63);
-      uint8_t* dst = out_host + (r - row0) * h->m;
-      for (int32_t j = 0; j < h->m; ++j) dst[j] = (uint8_t)(src[(int64_t)(j >> 2) * 64] >> (8 * (j & 3)));
-    }
-  }
-  return MI_OK;
-}
+int mi_pq_get_codes(mi_pq* h, int64_t row0, int64_t nrows, uint8_t* out_host) { return pq_flat_get_codes(h, row0, nrows, out_host); }
 
-int mi_pq_decode(mi_pq* h, int64_t row0, int64_t nrows, float* out_host) {
-  REQUIRE(h, "null handle");
-  REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= h->n, "row range outside the index");
-  REQUIRE(out_host || nrows == 0, "null pointer: out_host");
-  if (nrows == 0) return MI_OK;
-  std::lock_guard<std::mutex> lock(h->mu);
-  HIPC(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  const int64_t step = std::max<int64_t>(64, ((int64_t)64 << 20) / ((int64_t)h->d * 4));
-  int rc;
-  if ((rc = h->xraw.grow((size_t)std::min(step, nrows) * h->d * 4)) != MI_OK) return rc;
-  for (int64_t r = 0; r < nrows; r += step) {
-    const int64_t mm = std::min(step, nrows - r);
-    launch_pq_decode(h->codes, h->m, h->ks, h->L, h->cb, row0 + r, mm, (float*)h->xraw.get(), s);
-    HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(out_host + r * h->d, h->xraw, (size_t)mm * h->d * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));                 // the staging buffer is reused by the next block
-  }
-  return MI_OK;
-}
+int mi_pq_decode(mi_pq* h, int64_t row0, int64_t nrows, float* out_host) { return pq_flat_decode(h, row0, nrows, out_host); }
 
-int mi_pq_get_codebooks(const mi_pq* h, float* out_host) {
-  REQUIRE(h, "null handle");
-  REQUIRE(out_host, "null pointer: out_host");
-  std::memcpy(out_host, h->cb_host.data(), h->cb_host.size() * 4);
-  return MI_OK;
-}
+int mi_pq_get_codebooks(const mi_pq* h, float* out_host) { return pq_flat_get_codebooks(h, out_host); }
 
 // Row removal in place (faiss IndexPQ.remove_ids): `codes` compacted stably through a staging area of at most B
 // rows (global option "pq_remove_block_rows").  The rows pass in chunks of B source rows, ascending, from the block of the first
@@ -387,7 +105,7 @@ int mi_pq_remove_rows(mi_pq* h, const uint64_t* remove_bits, int memspace, int64
   // m == first: only trailing rows leave, no survivor lies behind a row that leaves, nothing moves
   if (m > plan.first) {
     const int64_t nwords = (n + 63) / 64;
-    const int64_t blk_words = (int64_t)h->MQ * 64;
+    const int64_t blk_words = (int64_t)h->MW * 64;
     const int64_t start = plan.first / 64;                    // the blocks before the first row that leaves stay as they are
     const int64_t B = std::min<int64_t>(g_pq_remove_block_rows.load(), (nwords - start) * 64) / 64;   // source blocks per chunk
     if ((rc = h->bits.grow((size_t)nwords)) != MI_OK) return rc;
@@ -413,14 +131,6 @@ int mi_pq_remove_rows(mi_pq* h, const uint64_t* remove_bits, int memspace, int64
   return MI_OK;
 }
 
-int mi_pq_destroy(mi_pq* h) {
-  if (!h) return MI_OK;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->bufs.reset();
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-  return MI_OK;
-}
+int mi_pq_destroy(mi_pq* h) { return pq_flat_destroy(h); }
 
 }  // extern "C"

@@ -103,7 +103,7 @@ int mi_pq_graph_build(mi_pq* codes, int32_t R, int32_t ne, mi_pq_graph** out) {
   // graph's order (distance asc, id asc)
   for (int64_t r0 = 0; r0 < n; r0 += bmax) {
     const int64_t b = std::min<int64_t>(bmax, n - r0);
-    launch_pq_decode(h->codes, h->m, h->ks, h->L, h->cb, r0, b, rec, s);
+    launch_pq_decode(h->codes, 1, h->m, h->ks, h->L, h->cb, r0, b, rec, s);
     if ((rc = pq_search_core(h, rec, MI_F32, h->d, 1, b, ks, nullptr, ids, nullptr, s)) != MI_OK) return bail(rc);
     launch_graph_forward(ids, ks, r0, b, h->row_offset, n, R, ws.F, s);
     hipError_t e = hipStreamSynchronize(s);        // (rec / ids are reused by the next batch)

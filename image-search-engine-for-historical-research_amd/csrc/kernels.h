@@ -379,8 +379,17 @@ void launch_forest_descend(const double* Pq, const double* splits, const int32_t
 // code bytes four books to a dword and the dwords transposed, codes[block][w < ceil(M / 4)][64]; distance tables [nq][M][Ks] f32;
 // a float32 matrix [nq][round_up(n, 64)] of NEGATED distances (NaN = row not admitted) for launch_dense_topk
 // (the device code pq.hip, ivfpq.hip and ivfpq_residual.hip share is pq_device.h)
+// Check, ingest, encode and decode exist once for both code widths, bytes and the wide index's uint16 (two books to a dword,
+// codes[block][w < ceil(M / 2)][64]; pq_wide.hip): overloads on the pointer type; launch_pq_decode takes code_bytes = 1 or 2 and
+// writes rows [row0, row0 + nrows) reconstructed, out [nrows][M L] f32
+template <typename CodeT> constexpr int32_t pq_codes_per_dword() { return 4 / (int32_t)sizeof(CodeT); }
+template <typename CodeT> constexpr int32_t pq_code_dwords(int32_t M) { return (M + pq_codes_per_dword<CodeT>() - 1) / pq_codes_per_dword<CodeT>(); }
 void launch_pq_check(const uint8_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream);
+void launch_pq_check(const uint16_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream);
 void launch_pq_ingest(const uint8_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream);
+void launch_pq_ingest(const uint16_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream);
+void launch_pq_decode(const uint32_t* codes, int32_t code_bytes, int32_t M, int32_t Ks, int32_t L, const float* cb, int64_t row0,
+                      int64_t nrows, float* out, hipStream_t stream);
 void launch_pq_table(const void* x, int dtype, int64_t rs, int64_t cs, int64_t nq, const float* cb, int32_t M, int32_t Ks, int32_t L,
                      float* tab, hipStream_t stream);
 // packed code bytes out [n][M]
@@ -397,14 +406,12 @@ void launch_pq_emit(const int64_t* tidx, const float* tneg, int64_t nq, int32_t 
 // pq_graph_search.hip -- best-first search of a neighbour graph over the codes of a PQ index (api_pq_graph.hip): the walk of
 // graph_walk.h with pq.hip's distances.  tab [nq][M][Ks] f32 as launch_pq_table writes it, codes in the index's transposed blocks; adj,
 // entries, vis and the limits as for launch_graph_search; out_dist and out_visited may be NULL.  Dynamic LDS pq_graph_lds_bytes
-// (at most 99856 bytes).  launch_pq_decode: rows [row0, row0 + nrows) reconstructed, out [nrows][M L] f32
+// (at most 99856 bytes).  The build's queries are launch_pq_decode's rows (pq.hip)
 size_t pq_graph_lds_bytes(int32_t M, int32_t Ks, int32_t ef);
 void launch_pq_graph_search(const uint32_t* codes, int32_t M, int32_t Ks, const float* tab, int64_t n, int64_t row_offset,
                             const int32_t* adj, int32_t R, const int32_t* entries, int32_t ne, int32_t k, int32_t ef, int64_t nq,
                             uint32_t* vis, int64_t vis_words, int64_t* out_idx, float* out_dist, int32_t* out_visited,
                             hipStream_t stream);
-void launch_pq_decode(const uint32_t* codes, int32_t M, int32_t Ks, int32_t L, const float* cb, int64_t row0, int64_t nrows, float* out,
-                      hipStream_t stream);
 
 // pq_train.hip -- learning PQ codebooks (api_pq_train.hip): Lloyd's iteration around launch_pq_encode.  cb [M][Ks][L] f32 is updated
 // in place (a codeword without members keeps its value); codes [n][M] bytes, cols [M][n] bytes (one contiguous column per book).
@@ -422,16 +429,13 @@ void launch_pq_update(const void* x, int dtype, int64_t rs, int64_t cs, int64_t 
                       float* cb, hipStream_t stream);
 
 // pq_wide.hip -- exact ADC top-K on wide PQ codes (api_pq_wide.hip): Ks <= 8192, a code is M uint16.  Gallery blocks
-// of 64 rows, two books to a dword, dwords transposed: codes[block][w < ceil(M / 2)][64].  Tables, matrix, selection and emit are
-// pq.hip's (launch_pq_table, launch_dense_topk, launch_pq_emit); the encoder is launch_pq_encode's uint16 overload
+// of 64 rows, two books to a dword, dwords transposed: codes[block][w < ceil(M / 2)][64].  Only the scan is this file's: tables,
+// matrix, selection and emit are pq.hip's (launch_pq_table, launch_dense_topk, launch_pq_emit), and so are check, ingest, encoder and
+// decode (the uint16 overloads above)
 constexpr int PQW_MAX_KS = 8192;
-void launch_pqw_check(const uint16_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream);
-void launch_pqw_ingest(const uint16_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream);
 int32_t pqw_query_tile(int32_t Ks, int64_t nq);                // queries per workgroup of the scan (1, 2 or 4): the LDS budget
 void launch_pqw_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, const float* tab, int32_t nq, int32_t qt,
                      const uint64_t* allow, float* mat, hipStream_t stream);
-void launch_pqw_decode(const uint32_t* codes, int32_t M, int32_t Ks, int32_t L, const float* cb, int64_t row0, int64_t nrows, float* out,
-                       hipStream_t stream);
 
 // ivfpq.hip -- inverted-file search over PQ codes (api_ivfpq.hip).  Blocks of 64 slots from one pool: codes [pblock][MQ][64] in
 // the PQ index's transposed form, rowid [pblock][64] the local row of a slot; list l is the chain of blocks

@@ -9,6 +9,10 @@
 //   pq_device.h       the pieces shared with ivfpq.hip and ivfpq_residual.hip.  pq_sqdist is THE arithmetic: sum_j (double(x_j) -
 //                     double(c_j))^2 in float64, ascending j, a separate multiply and add per term (no contraction).  The table
 //                     rounds it once to float32, the encoder takes its argmin; pq_adc_row is the scan's row sum
+//   pq_check_kernel, pq_ingest_kernel, pq_decode_kernel
+//                     the element-wise kernels, templates on the code type like the encoder: device codes >= ks raise the flag;
+//                     codes [rows][stride] -> dwords of the transposed layout (pq_pack_dword); rows reconstructed from their codes.
+//                     One copy serves this index (bytes, four books to a dword) and the wide one (uint16, two; pq_wide.hip)
 //   pq_table_kernel   T[q][m][c] = (float)pq_sqdist(x[q][m L ..], C[m][c]), thread = (q, m, c)
 //   pq_encode_kernel  code[i][m] = argmin_c pq_sqdist(x[i][m L ..], C[m][c]), ties to the lower c.  A workgroup takes 64 rows of
 //                     one book; row and codeword slices pass through LDS as float64, 8 accumulators per thread.  The code type
@@ -28,8 +32,9 @@
 
 namespace mi {
 
-// ---- code bytes >= ks raise the flag (device-resident codes; host codes are checked on the host)
-__global__ __launch_bounds__(256) void pq_check_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t M, int32_t ks, int64_t m,
+// ---- codes >= ks raise the flag (device-resident codes; host codes are checked on the host)
+template <typename CodeT>
+__global__ __launch_bounds__(256) void pq_check_kernel(const CodeT* __restrict__ src, int64_t stride, int32_t M, int32_t ks, int64_t m,
                                                       uint32_t* __restrict__ flag) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= m * M) return;
@@ -38,15 +43,32 @@ __global__ __launch_bounds__(256) void pq_check_kernel(const uint8_t* __restrict
   if ((int32_t)src[r * stride + b] >= ks) *flag = 1u;
 }
 
-// ---- code bytes [m][stride] -> dwords of rows row0 .. row0 + m of the transposed layout (thread = (dword, row), rows fastest)
-__global__ __launch_bounds__(256) void pq_ingest_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t M, int32_t MQ, int64_t row0,
+// ---- codes [m][stride] -> dwords of rows row0 .. row0 + m of the transposed layout (thread = (dword, row), rows fastest)
+template <typename CodeT>
+__global__ __launch_bounds__(256) void pq_ingest_kernel(const CodeT* __restrict__ src, int64_t stride, int32_t M, int32_t MW, int64_t row0,
                                                        int64_t m, uint32_t* __restrict__ codes) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= m * MQ) return;
+  if (i >= m * MW) return;
   const int64_t r = i % m;
   const int32_t w = (int32_t)(i / m);
   const int64_t row = row0 + r;
-  codes[((row >> 6) * MQ + w) * 64 + (row & 63)] = pq_pack_dword(src + r * stride, w, M);
+  codes[((row >> 6) * MW + w) * 64 + (row & 63)] = pq_pack_dword(src + r * stride, w, M);
+}
+
+// ---- out [nrows][M L]: row row0 + r reconstructed, the concatenation of C[j][code[j]] (nanopq's pq.decode); thread = one element
+template <typename CodeT>
+__global__ __launch_bounds__(256) void pq_decode_kernel(const uint32_t* __restrict__ codes, int32_t M, int32_t Ks, int32_t L,
+                                                       const float* __restrict__ cb, int64_t row0, int64_t nrows,
+                                                       float* __restrict__ out) {
+  constexpr uint32_t PER = pq_codes_per_dword<CodeT>(), BITS = 8 * sizeof(CodeT);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int32_t d = M * L, MW = pq_code_dwords<CodeT>(M);
+  if (i >= nrows * d) return;
+  const int64_t row = row0 + i / d;
+  const int32_t col = (int32_t)(i % d), j = col / L;
+  const uint32_t g = codes[((row >> 6) * MW + (uint32_t)j / PER) * 64 + (row & 63)];
+  const int32_t c = (int32_t)((g >> (BITS * ((uint32_t)j % PER))) & ((1u << BITS) - 1u));
+  out[i] = cb[((int64_t)j * Ks + c) * L + (col - j * L)];
 }
 
 // ---- table
@@ -191,18 +213,48 @@ __global__ __launch_bounds__(256) void pq_emit_kernel(const int64_t* __restrict_
 // ---- launchers
 constexpr int64_t PQ_STEP = (int64_t)1 << 22;                 // rows per launch of the element-wise kernels: grids stay below 2^31
 
-void launch_pq_check(const uint8_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream) {
+template <typename CodeT>
+static void check_launch(const CodeT* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream) {
   for (int64_t r = 0; r < m; r += PQ_STEP) {
     const int64_t mm = std::min(PQ_STEP, m - r);
-    pq_check_kernel<<<dim3((unsigned)((mm * M + 255) / 256)), 256, 0, stream>>>(src + r * stride, stride, M, ks, mm, flag);
+    pq_check_kernel<CodeT><<<dim3((unsigned)((mm * M + 255) / 256)), 256, 0, stream>>>(src + r * stride, stride, M, ks, mm, flag);
+  }
+}
+
+void launch_pq_check(const uint8_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream) {
+  check_launch(src, stride, M, ks, m, flag, stream);
+}
+
+void launch_pq_check(const uint16_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream) {
+  check_launch(src, stride, M, ks, m, flag, stream);
+}
+
+template <typename CodeT>
+static void ingest_launch(const CodeT* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream) {
+  const int32_t MW = pq_code_dwords<CodeT>(M);
+  for (int64_t r = 0; r < m; r += PQ_STEP) {
+    const int64_t mm = std::min(PQ_STEP, m - r);
+    pq_ingest_kernel<CodeT><<<dim3((unsigned)((mm * MW + 255) / 256)), 256, 0, stream>>>(src + r * stride, stride, M, MW, row0 + r, mm, codes);
   }
 }
 
 void launch_pq_ingest(const uint8_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream) {
-  const int32_t MQ = (M + 3) / 4;
-  for (int64_t r = 0; r < m; r += PQ_STEP) {
-    const int64_t mm = std::min(PQ_STEP, m - r);
-    pq_ingest_kernel<<<dim3((unsigned)((mm * MQ + 255) / 256)), 256, 0, stream>>>(src + r * stride, stride, M, MQ, row0 + r, mm, codes);
+  ingest_launch(src, stride, M, row0, m, codes, stream);
+}
+
+void launch_pq_ingest(const uint16_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream) {
+  ingest_launch(src, stride, M, row0, m, codes, stream);
+}
+
+void launch_pq_decode(const uint32_t* codes, int32_t code_bytes, int32_t M, int32_t Ks, int32_t L, const float* cb, int64_t row0,
+                      int64_t nrows, float* out, hipStream_t stream) {
+  const int64_t d = (int64_t)M * L;
+  const int64_t step = std::max<int64_t>(1, ((int64_t)1 << 30) / d);         // rows per launch
+  for (int64_t r = 0; r < nrows; r += step) {
+    const int64_t b = std::min(step, nrows - r);
+    const dim3 grid((unsigned)((b * d + 255) / 256));
+    if (code_bytes == 1) pq_decode_kernel<uint8_t><<<grid, 256, 0, stream>>>(codes, M, Ks, L, cb, row0 + r, b, out + r * d);
+    else pq_decode_kernel<uint16_t><<<grid, 256, 0, stream>>>(codes, M, Ks, L, cb, row0 + r, b, out + r * d);
   }
 }
 

@@ -1,8 +1,9 @@
-// The device code the PQ index family shares (pq.hip, ivfpq.hip, ivfpq_residual.hip): every codebook, table,
-// probe, code and partial list of the three files is made of these pieces, so each exists once and all of them give the same bits.
+// The device code the PQ index family shares (pq.hip, pq_wide.hip, ivfpq.hip, ivfpq_residual.hip): every
+// codebook, table, probe, code and partial list of these files is made of these pieces, so each exists once and all of them give the
+// same bits.
 //
 //   pq_sqdist_step / pq_sqdist  THE arithmetic of a squared distance: float64 subtract, multiply, add, nothing fused
-//   pq_pack_dword               code bytes 4 w .. 4 w + 3 of a row -> a dword of the transposed layout
+//   pq_pack_dword               the codes of a row (bytes: 4 w .. 4 w + 3, uint16: 2 w, 2 w + 1) -> a dword of the transposed layout
 //   PE_*                        the tile constants of the two encoder kernels
 //   pq_adc_row                  the ADC sum of one lane's row: float32 table entries in ascending book order
 //   the slab vocabulary         an IVF query's candidates pass in slabs of 64 blocks = 4096 keys float_bits(dist) << 32 | local row,
@@ -30,12 +31,15 @@ __device__ __forceinline__ double pq_sqdist(FX x, FC c, int32_t L) {
   return acc;
 }
 
-// ---- the dword w of a row's code: byte b is the code in book 4 w + b, the bytes of the books M .. are zero
-__device__ __forceinline__ uint32_t pq_pack_dword(const uint8_t* p, int32_t w, int32_t M) {
+// ---- the dword w of a row's code, PER = 4 (bytes) or 2 (uint16) books to a dword: field b is the code in book PER w + b, the
+// fields of the books M .. are zero
+template <typename CodeT>
+__device__ __forceinline__ uint32_t pq_pack_dword(const CodeT* p, int32_t w, int32_t M) {
+  constexpr int PER = 4 / (int)sizeof(CodeT), BITS = 8 * (int)sizeof(CodeT);
   uint32_t v = 0;
 #pragma unroll
-  for (int b = 0; b < 4; ++b)
-    if (4 * w + b < M) v |= (uint32_t)p[4 * w + b] << (8 * b);
+  for (int b = 0; b < PER; ++b)
+    if (PER * w + b < M) v |= (uint32_t)p[PER * w + b] << (BITS * b);
   return v;
 }
 

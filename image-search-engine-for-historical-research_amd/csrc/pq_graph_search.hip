@@ -1,5 +1,5 @@
 // Best-first search of a neighbour graph over the CODES of a PQ index (mi_pq_graph; the role of the reference's PQ + HNSW
-// matchers): the scorer of graph_walk.h for PQ codes, and the decoder that gives the build its queries.
+// matchers): the scorer of graph_walk.h for PQ codes.  (The decoder that gives the build its queries is pq.hip's.)
 //
 // What differs from graph_search.hip is what a row costs.  There a row is an 8 KiB gather by a whole wave; here it is
 // ceil(M / 4) dwords read by ONE lane and M reads of the query's distance table, which the kernel copies to LDS before the walk
@@ -14,8 +14,6 @@
 // Dynamic LDS, in bytes (pq_graph_lds_bytes): table 16 MQ Ks (at most 65536) | W 8 ef | other half 8 ef | new keys as evaluated
 // 512 | new keys in the order 512 | table entries as read 256 | new ids 256 | control 16.  The largest carve the contract admits
 // (M = 64, Ks = 256, ef = 2048) is 65536 + 32768 + 1552 = 99856 bytes of the 160 KiB of a CU.
-#include <algorithm>
-
 #include "graph_walk.h"
 #include "kernels.h"
 #include "pq_device.h"
@@ -96,20 +94,6 @@ __global__ __launch_bounds__(256) void pq_graph_search_kernel(const uint32_t* __
   graph_walk(p, n, adj, R, entries, ne, k, ef, vis, vis_words, out_visited);
 }
 
-// out [nrows][M L]: row row0 + r reconstructed, the concatenation of C[j][code[j]] (nanopq's pq.decode)
-__global__ __launch_bounds__(256) void pq_decode_kernel(const uint32_t* __restrict__ codes, int32_t M, int32_t Ks, int32_t L,
-                                                       const float* __restrict__ cb, int64_t row0, int64_t nrows,
-                                                       float* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int32_t d = M * L, MQ = (M + 3) / 4;
-  if (i >= nrows * d) return;
-  const int64_t row = row0 + i / d;
-  const int32_t col = (int32_t)(i % d), j = col / L;
-  const uint32_t g = codes[((row >> 6) * MQ + (j >> 2)) * 64 + (row & 63)];
-  const int32_t c = (int32_t)((g >> (8 * (j & 3))) & 255u);
-  out[i] = cb[((int64_t)j * Ks + c) * L + (col - j * L)];
-}
-
 size_t pq_graph_lds_bytes(int32_t M, int32_t Ks, int32_t ef) {
   const size_t MQ = ((size_t)M + 3) / 4;
   return 16 * MQ * (size_t)Ks + 2 * 8 * (size_t)ef + 2 * 64 * 8 + 2 * 64 * 4 + 16;
@@ -124,16 +108,6 @@ void launch_pq_graph_search(const uint32_t* codes, int32_t M, int32_t Ks, const 
   hipLaunchKernelGGL(pq_graph_search_kernel, dim3((unsigned)nq), dim3(256), pq_graph_lds_bytes(M, Ks, ef), stream, codes,
                      (M + 3) / 4, Ks, M * Ks, tab, n, row_offset, adj, R, entries, ne, k, ef, vis, vis_words, out_idx, out_dist,
                      out_visited);
-}
-
-void launch_pq_decode(const uint32_t* codes, int32_t M, int32_t Ks, int32_t L, const float* cb, int64_t row0, int64_t nrows, float* out,
-                      hipStream_t stream) {
-  const int64_t d = (int64_t)M * L;
-  const int64_t step = std::max<int64_t>(1, ((int64_t)1 << 30) / d);         // rows per launch
-  for (int64_t r = 0; r < nrows; r += step) {
-    const int64_t b = std::min(step, nrows - r);
-    pq_decode_kernel<<<dim3((unsigned)((b * d + 255) / 256)), 256, 0, stream>>>(codes, M, Ks, L, cb, row0 + r, b, out + r * d);
-  }
 }
 
 }  // namespace mi

@@ -5,11 +5,9 @@
 // books to a dword, dwords transposed: codes[block][w][lane], w < MH = ceil(M / 2), the low half of dword w is the row's code in
 // book 2 w, the high half in book 2 w + 1 (zero when that book is beyond M).  Lane l of a wave owns row 64 * block + l, one book
 // pair of the 64 rows is one coalesced 256-byte read.  Tables, arithmetic, matrix, selection and emit are the byte index's
-// (launch_pq_table, pq_acc, launch_dense_topk, launch_pq_emit), the encoder is pq_encode_kernel with a uint16 output: for Ks <= 256
-// every output has the bits of mi_pq's.
+// (launch_pq_table, pq_acc, launch_dense_topk, launch_pq_emit), and check, ingest, encoder and decode are pq.hip's kernels with a
+// uint16 code type: for Ks <= 256 every output has the bits of mi_pq's.  What is left here is the one kernel that differs:
 //
-//   pqw_check_kernel   codes >= ks raise the flag (device-resident codes; host codes are checked on the host)
-//   pqw_ingest_kernel  codes [m][stride] uint16 -> dwords of the transposed layout
 //   pqw_scan_kernel    the hot path.  One query's tables are M Ks 4 bytes (512 KiB at 16 x 8192) and do not fit in LDS, so the books
 //                      pass in GROUPS of GP book pairs: a workgroup owns a slab of at most PW_WAVES * PW_RPL row blocks and a tile
 //                      of QT queries; per group it loads 2 GP Ks QT entries into LDS (interleaved query-fastest, T[book][c][QT], +0.0
@@ -18,36 +16,12 @@
 //                      the adds of a row happen in ascending book order whatever GP is, so the bits do not depend on it.  When
 //                      all MH pairs fit (GP = MH) the kernel is one pass.  Output as pq_scan_kernel's: the NEGATED distance into
 //                      the matrix [queries][npad], NaN for rows not admitted
-//   pqw_decode_kernel  rows reconstructed from their codes
 #include <algorithm>
 
 #include "kernels.h"
 #include "pq_device.h"
 
 namespace mi {
-
-__global__ __launch_bounds__(256) void pqw_check_kernel(const uint16_t* __restrict__ src, int64_t stride, int32_t M, int32_t ks, int64_t m,
-                                                       uint32_t* __restrict__ flag) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= m * M) return;
-  const int64_t r = i / M;
-  const int32_t b = (int32_t)(i % M);
-  if ((int32_t)src[r * stride + b] >= ks) *flag = 1u;
-}
-
-// thread = (dword, row), rows fastest
-__global__ __launch_bounds__(256) void pqw_ingest_kernel(const uint16_t* __restrict__ src, int64_t stride, int32_t M, int32_t MH,
-                                                        int64_t row0, int64_t m, uint32_t* __restrict__ codes) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= m * MH) return;
-  const int64_t r = i % m;
-  const int32_t w = (int32_t)(i / m);
-  const int64_t row = row0 + r;
-  const uint16_t* p = src + r * stride;
-  uint32_t v = p[2 * w];
-  if (2 * w + 1 < M) v |= (uint32_t)p[2 * w + 1] << 16;
-  codes[((row >> 6) * MH + w) * 64 + (row & 63)] = v;
-}
 
 // ---- scan
 constexpr int PW_THREADS = 1024, PW_WAVES = PW_THREADS / 64;
@@ -125,38 +99,7 @@ __global__ __launch_bounds__(PW_THREADS) void pqw_scan_kernel(const uint32_t* __
   }
 }
 
-// thread = one output element
-__global__ __launch_bounds__(256) void pqw_decode_kernel(const uint32_t* __restrict__ codes, int32_t M, int32_t Ks, int32_t L,
-                                                        const float* __restrict__ cb, int64_t row0, int64_t nrows,
-                                                        float* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int32_t d = M * L, MH = (M + 1) / 2;
-  if (i >= nrows * d) return;
-  const int64_t row = row0 + i / d;
-  const int32_t col = (int32_t)(i % d), j = col / L;
-  const uint32_t g = codes[((row >> 6) * MH + (j >> 1)) * 64 + (row & 63)];
-  const int32_t c = (int32_t)((g >> (16 * (j & 1))) & 0xffffu);
-  out[i] = cb[((int64_t)j * Ks + c) * L + (col - j * L)];
-}
-
 // ---- launchers
-constexpr int64_t PQW_STEP = (int64_t)1 << 22;                // rows per launch of the element-wise kernels: grids stay below 2^31
-
-void launch_pqw_check(const uint16_t* src, int64_t stride, int32_t M, int32_t ks, int64_t m, uint32_t* flag, hipStream_t stream) {
-  for (int64_t r = 0; r < m; r += PQW_STEP) {
-    const int64_t mm = std::min(PQW_STEP, m - r);
-    pqw_check_kernel<<<dim3((unsigned)((mm * M + 255) / 256)), 256, 0, stream>>>(src + r * stride, stride, M, ks, mm, flag);
-  }
-}
-
-void launch_pqw_ingest(const uint16_t* src, int64_t stride, int32_t M, int64_t row0, int64_t m, uint32_t* codes, hipStream_t stream) {
-  const int32_t MH = (M + 1) / 2;
-  for (int64_t r = 0; r < m; r += PQW_STEP) {
-    const int64_t mm = std::min(PQW_STEP, m - r);
-    pqw_ingest_kernel<<<dim3((unsigned)((mm * MH + 255) / 256)), 256, 0, stream>>>(src + r * stride, stride, M, MH, row0 + r, mm, codes);
-  }
-}
-
 // one book pair of one query is 2 Ks 4 bytes: 64 KiB at Ks = 8192, so QT <= 2 there
 int32_t pqw_query_tile(int32_t Ks, int64_t nq) {
   const int64_t pair = (int64_t)2 * Ks * 4;
@@ -193,16 +136,6 @@ void launch_pqw_scan(const uint32_t* codes, int32_t M, int32_t Ks, int64_t n, co
     case 4: wide_scan_launch<4>(stream, codes, M, Ks, n, tab, nq, allow, mat); break;
     case 2: wide_scan_launch<2>(stream, codes, M, Ks, n, tab, nq, allow, mat); break;
     default: wide_scan_launch<1>(stream, codes, M, Ks, n, tab, nq, allow, mat); break;
-  }
-}
-
-void launch_pqw_decode(const uint32_t* codes, int32_t M, int32_t Ks, int32_t L, const float* cb, int64_t row0, int64_t nrows, float* out,
-                       hipStream_t stream) {
-  const int64_t d = (int64_t)M * L;
-  const int64_t step = std::max<int64_t>(1, ((int64_t)1 << 30) / d);         // rows per launch
-  for (int64_t r = 0; r < nrows; r += step) {
-    const int64_t b = std::min(step, nrows - r);
-    pqw_decode_kernel<<<dim3((unsigned)((b * d + 255) / 256)), 256, 0, stream>>>(codes, M, Ks, L, cb, row0 + r, b, out + r * d);
   }
 }
 

@@ -103,6 +103,25 @@ def test_byte_range_equals_the_byte_index(lib, Ks):
         assert np.array_equal(_bits(w.decode()), _bits(b.decode()))
 
 
+@pytest.mark.parametrize("cls,dtype,Ks", [("PQIndex", np.uint8, 5), ("WidePQIndex", np.uint16, 300)])
+def test_both_widths_pack_and_unpack_strided_host_rows(lib, cls, dtype, Ks):
+    """the packing both indexes share (pq_pack_dword, the host unpack, pq_decode_kernel): M = 3 fills neither a dword of four
+    bytes nor one of two uint16, the rows straddle a 64-row block, the host rows lie M + 2 codes apart"""
+    n, M, L = 130, 3, 2
+    rng = np.random.default_rng(Ks)
+    C = rng.standard_normal((M, Ks, L)).astype(np.float32)
+    codes = rng.integers(0, Ks, size=(n, M)).astype(dtype)
+    codes[0], codes[n - 1] = Ks - 1, Ks - 1                             # the highest codeword is in use
+    q = rng.standard_normal((3, M * L)).astype(np.float32)
+    wide = np.full((n, M + 2), np.iinfo(dtype).max, dtype)              # what lies between the rows is >= ks
+    wide[:, :M] = codes
+    with getattr(lib, cls).from_codes(C, wide[:, :M]) as g:
+        assert np.array_equal(g.get_codes(60, 10), codes[60:70]) and np.array_equal(g.get_codes(), codes)
+        rows = np.concatenate([C[j][codes[60:70, j]] for j in range(M)], axis=1)
+        assert np.array_equal(_bits(g.decode(60, 10)), _bits(rows))
+        assert _same(g.search(q, n), pq_truth(q, C, codes, n))
+
+
 def test_ties_come_back_in_ascending_id(lib):
     M, Ks, L = 3, 300, 2
     C, _, q = _problem(700, M, Ks, L, 5)
