@@ -109,6 +109,16 @@ SIGNATURES = {
     "mi_forest_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, c_f64p]),
     "mi_forest_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_ivfflat_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "mi_ivfflat_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "mi_ivfflat_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), c_i64p]),
+    "mi_ivfflat_list_sizes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_ivfflat_get_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_ivfflat_get_centroids": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_ivfflat_destroy": (C.c_int, [C.c_void_p]),
+    "mi_ivfflat_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mi_ivfflat_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_hamming_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                     C.POINTER(C.c_void_p)]),
     "mi_hamming_append": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
@@ -2360,6 +2370,217 @@ class IVFPQIndex(_Handle):
         with self._lock:
             check(load().mi_ivfpq_get_rows(self._h, int(row0), nrows, codes.ctypes.data_as(C.c_void_p), lists.ctypes.data_as(C.c_void_p)))
         return codes, lists
+
+
+IVFFLAT_MAX_LISTS = 8192          # lists of an IVFFlatIndex (mi_ivfflat)
+IVFFLAT_MAX_K = 2048
+IVFFLAT_SLAB_ROWS = 2048          # positions of a query's candidate sequence one scan workgroup sorts (csrc/kernels.h)
+
+
+def ivfflat_centroids(centroids, d):
+    """float32 [nlist, d] C-contiguous centroids, checked against what an IVF-Flat index takes: 2 <= nlist <= 8192, finite.  Raises
+    ValueError."""
+    g = np.asarray(centroids)
+    if g.ndim == 3 and g.shape[0] == 1:              # what pq_train(x, 1, nlist) returns
+        g = g[0]
+    if g.ndim != 2 or g.dtype == np.bool_ or not (np.issubdtype(g.dtype, np.floating) or np.issubdtype(g.dtype, np.integer)):
+        raise ValueError("centroids must be a numeric array [nlist, d] (got %s %s)" % (g.dtype, g.shape))
+    if not 2 <= g.shape[0] <= IVFFLAT_MAX_LISTS:
+        raise ValueError("nlist = %d lists, an IVF-Flat index takes 2 .. %d" % (g.shape[0], IVFFLAT_MAX_LISTS))
+    if g.shape[1] != int(d):
+        raise ValueError("centroids of %d columns, the gallery has d = %d" % (g.shape[1], d))
+    g = np.ascontiguousarray(g, dtype=np.float32)
+    if not np.isfinite(g).all():
+        raise ValueError("centroids must be finite")
+    return g
+
+
+def ivfflat_list_ids(list_ids, n, nlist):
+    """int32 [n] C-contiguous list ids from any integer array with values in [0, nlist).  Raises ValueError."""
+    a = np.asarray(list_ids)
+    if a.ndim != 1 or a.shape[0] != int(n):
+        raise ValueError("list ids must be [n = %d] (got shape %s)" % (n, a.shape))
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("list ids must be an integer array (got %s)" % a.dtype)
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= nlist):
+        raise ValueError("list ids must lie in [0, nlist = %d)" % nlist)
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _ivfflat_rows(n):
+    n = int(n)
+    if n < 1 or n >= 2 ** 31:
+        raise ValueError("an IVF-Flat index takes a gallery of 1 .. 2^31 - 1 rows (got %d)" % n)
+    return n
+
+
+class IVFFlatIndex(_Handle):
+    """An inverted file over the raw rows of a Gallery (a `mi_ivfflat` handle), faiss IndexIVFFlat: every row
+    belongs to the list of its best centroid, a query evaluates the stored rows of the nprobe lists it probes.  Which rows are
+    reached is approximate; the answer given centroids, lists, stored rows and query is exact: values are Gallery.refine's, the
+    order is (value best first, id ascending).  The rows are not copied: the index costs 4 bytes per row plus the centroids.  The
+    gallery must outlive the index; after gallery.append* / gallery.remove probe and search raise (build a new index).  Nothing
+    routes to this index by default and its speed has not been measured: for large batches the exhaustive search stays the choice."""
+    _DESTROY = "mi_ivfflat_destroy"
+    hbm_bytes = _hbm_bytes("mi_ivfflat_info", 3)
+
+    def __init__(self, handle, gallery):
+        super().__init__(handle)
+        self.gallery = gallery
+        n, d, nlist = C.c_int64(), C.c_int32(), C.c_int32()
+        check(load().mi_ivfflat_info(self._h, n, d, nlist, None))
+        self.n, self.d, self.nlist = n.value, d.value, nlist.value
+
+    @staticmethod
+    def train(x, nlist, iters=20, seed=0, device=0):
+        """-> centroids float32 [nlist, d]: deterministic k-means on x [n, d] with ONE book of nlist full-dimension codewords,
+        pq_train up to 256 lists and pqw_train above that (up to 8192)."""
+        nlist = int(nlist)
+        if not 2 <= nlist <= IVFFLAT_MAX_LISTS:
+            raise ValueError("nlist = %d lists, an IVF-Flat index takes 2 .. %d" % (nlist, IVFFLAT_MAX_LISTS))
+        fit = pq_train if nlist <= PQ_MAX_WORDS else pqw_train
+        return np.ascontiguousarray(fit(x, 1, nlist, iters=iters, seed=seed, device=device)[0][0], dtype=np.float32)
+
+    @classmethod
+    def build(cls, gallery, centroids):
+        """mi_ivfflat_build: every stored row of `gallery` goes to the list of its best centroid (centroids float [nlist, d]), on
+        the device.  Deterministic.  Bad shapes raise ValueError before the device is touched."""
+        _ivfflat_rows(gallery.n)
+        g = ivfflat_centroids(centroids, gallery.d)
+        h = C.c_void_p()
+        with gallery._lock:
+            check(load().mi_ivfflat_build(gallery._h, C.c_void_p(g.ctypes.data), g.shape[0], C.byref(h)))
+        return cls(h.value, gallery)
+
+    @classmethod
+    def from_lists(cls, gallery, centroids, list_ids):
+        """mi_ivfflat_create: list_ids integer [n] in [0, nlist), the list of every row.  Bad input raises ValueError before the
+        device is touched."""
+        n = _ivfflat_rows(gallery.n)
+        g = ivfflat_centroids(centroids, gallery.d)
+        li = ivfflat_list_ids(list_ids, n, g.shape[0])
+        h = C.c_void_p()
+        with gallery._lock:
+            check(load().mi_ivfflat_create(gallery._h, C.c_void_p(g.ctypes.data), g.shape[0], C.c_void_p(li.ctypes.data), MI_HOST,
+                                           C.byref(h)))
+        return cls(h.value, gallery)
+
+    def _nprobe(self, nprobe):
+        nprobe = int(nprobe)
+        if not 1 <= nprobe <= self.nlist:
+            raise ValueError("nprobe = %d, the index has nlist = %d lists (1 .. nlist)" % (nprobe, self.nlist))
+        return nprobe
+
+    def _k(self, k):
+        k = int(k)
+        if not 1 <= k <= IVFFLAT_MAX_K:
+            raise ValueError("k = %d: k must be in [1, %d]" % (k, IVFFLAT_MAX_K))
+        return k
+
+    def _stage(self, q):
+        """Host queries [Q, d] of any float type and strides -> (packed float32 tensor on the gallery's device, torch device, stream):
+        float64 is rounded to float32, as the host entry points of the library do."""
+        import torch
+        a = self.gallery._queries(q)[0]
+        tdev = "cuda:%d" % self.gallery.device
+        xq = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(tdev)
+        return xq, tdev, torch.cuda.current_stream(tdev).cuda_stream
+
+    def probe(self, q, nprobe=1):
+        """-> int32 [Q, nprobe]: per query its nprobe best lists, best first, ties to the lower list (mi_ivfflat_probe_device on the
+        staged queries; synchronous)."""
+        import torch
+        nprobe = self._nprobe(nprobe)
+        xq, tdev, stream = self._stage(q)
+        nq = xq.shape[0]
+        if nq == 0:
+            return np.empty((0, nprobe), np.int32)
+        out = torch.empty((nq, nprobe), dtype=torch.int32, device=tdev)
+        with self._lock:
+            self.probe_device(xq.data_ptr(), nq, nprobe, out.data_ptr(), stream=stream)
+            return out.cpu().numpy()                       # (synchronises with the stream the work is on)
+
+    def probe_device(self, q_ptr, nq, nprobe, out_ptr, stream=None):
+        """mi_ivfflat_probe_device: q_ptr packed float32 [nq][d], out_ptr int32 [nq][nprobe] on the device; enqueued on `stream`."""
+        check(load().mi_ivfflat_probe_device(self._h, C.c_void_p(q_ptr), int(nq), self._nprobe(nprobe), C.c_void_p(out_ptr),
+                                             C.c_void_p(stream)))
+
+    def search(self, q, k, nprobe=1, probes=None, allow=None, return_values64=False, return_scanned=False):
+        """-> (ids int64 [Q, k], values float32 [Q, k], seconds), 1 <= k <= 2048, over the rows of the probed lists, by (value best
+        first, id ascending).  probes: integer [Q, P] of list ids in place of the library's nprobe best lists (then nprobe is P); an
+        entry outside [0, nlist) or repeating an earlier one of its row is no list.  allow: anything allow_bitmap takes.  Fewer than
+        k such rows: ids -1, values +inf (L2) / -inf.  return_values64: the float64 values in place of their float32 cast;
+        return_scanned: a fourth result, int64 [Q], the rows evaluated per query.  The queries, the probes and the bitmap are
+        staged on the device here and mi_ivfflat_search_device does the work; seconds is the wall time of that, staging and the
+        copies back included; synchronous."""
+        import torch
+        k = self._k(k)
+        a = self.gallery._queries(q)[0]
+        nq = a.shape[0]
+        bits = _allow_words(allow, self.n, self.gallery.row_offset)
+        pr = None
+        if probes is not None:
+            pr = np.asarray(probes)
+            if pr.ndim != 2 or pr.shape[0] != nq or pr.dtype == np.bool_ or not np.issubdtype(pr.dtype, np.integer):
+                raise ValueError("probes must be an integer array [Q = %d, P] (got %s %s)" % (nq, pr.dtype, pr.shape))
+            nprobe = pr.shape[1]
+            pr = np.ascontiguousarray(np.where((pr < 0) | (pr >= self.nlist), -1, pr), dtype=np.int32)
+        nprobe = self._nprobe(nprobe)
+        if nq == 0:
+            out = (np.empty((0, k), np.int64), np.empty((0, k), np.float64 if return_values64 else np.float32), 0.0)
+            return (*out, np.empty(0, np.int64)) if return_scanned else out
+        t0 = time.perf_counter()
+        xq, tdev, stream = self._stage(a)
+        bits_dev = _upload_allow(bits, tdev)
+        pr_dev = None if pr is None else torch.from_numpy(pr).to(tdev)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=tdev)
+        val = torch.empty((nq, k), dtype=torch.float32, device=tdev)
+        val64 = torch.empty((nq, k), dtype=torch.float64, device=tdev)
+        scanned = torch.empty((nq,), dtype=torch.int64, device=tdev)
+        with self._lock:
+            self.search_device(xq.data_ptr(), nq, k, idx.data_ptr(), val_ptr=val.data_ptr(), val64_ptr=val64.data_ptr(), nprobe=nprobe,
+                               probes_ptr=None if pr_dev is None else pr_dev.data_ptr(),
+                               allow_ptr=None if bits_dev is None else bits_dev.data_ptr(), scanned_ptr=scanned.data_ptr(), stream=stream)
+            ids, vv = idx.cpu().numpy(), (val64 if return_values64 else val).cpu().numpy()      # (synchronises with the stream)
+            sc = scanned.cpu().numpy()
+        out = (ids, vv, time.perf_counter() - t0)
+        return (*out, sc) if return_scanned else out
+
+    def search_device(self, q_ptr, nq, k, idx_ptr, val_ptr=None, val64_ptr=None, nprobe=1, probes_ptr=None, allow_ptr=None,
+                      scanned_ptr=None, stream=None):
+        """mi_ivfflat_search_device: q_ptr packed float32 [nq][d] on the device; probes_ptr: None or int32 [nq][nprobe] on the
+        device; allow_ptr: None or the bitmap on the device; enqueued on `stream`, no synchronisation."""
+        check(load().mi_ivfflat_search_device(self._h, C.c_void_p(q_ptr), int(nq), self._k(k), self._nprobe(nprobe), C.c_void_p(probes_ptr),
+                                              C.c_void_p(allow_ptr), C.c_void_p(idx_ptr), C.c_void_p(val_ptr), C.c_void_p(val64_ptr),
+                                              C.c_void_p(scanned_ptr), C.c_void_p(stream)))
+
+    def list_sizes(self):
+        """-> int64 [nlist]: the rows of every list."""
+        out = np.empty(self.nlist, dtype=np.int64)
+        check(load().mi_ivfflat_list_sizes(self._h, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def lists(self):
+        """-> (list_off int64 [nlist + 1], list_rows int32 [n]): list l holds the local rows list_rows[list_off[l]:list_off[l + 1]],
+        ascending."""
+        off, rows = np.empty(self.nlist + 1, np.int64), np.empty(self.n, np.int32)
+        with self._lock:
+            check(load().mi_ivfflat_get_lists(self._h, C.c_void_p(off.ctypes.data), C.c_void_p(rows.ctypes.data)))
+        return off, rows
+
+    def list_ids(self):
+        """-> int32 [n]: the list of every row, read back from lists()."""
+        off, rows = self.lists()
+        out = np.empty(self.n, np.int32)
+        out[rows] = np.repeat(np.arange(self.nlist, dtype=np.int32), np.diff(off))
+        return out
+
+    def centroids(self):
+        """-> float32 [nlist, d]."""
+        out = np.empty((self.nlist, self.d), np.float32)
+        with self._lock:
+            check(load().mi_ivfflat_get_centroids(self._h, C.c_void_p(out.ctypes.data)))
+        return out
 
 
 def kth_of_gathered_device(gathered_ptr, nshards, nq, k, out_ptr, stream=None):

@@ -31,6 +31,8 @@
 //   api_forest.hip    random-projection forest (mi_forest): directions, split values and row permutations over a gallery's rows; f64
 //                     projections of rows and queries by one kernel (forest_project.hip), level-wise build (forest_build.hip), descent
 //                     into candidate slots (forest_search.hip), the answer by launch_refine
+//   api_ivfflat.hip   IVF-Flat index (mi_ivfflat): centroids, list offsets and row lists over a gallery's raw rows; probe and assignment
+//                     by launch_refine over the centroid table, list build, scan with selection and merge in ivfflat.hip
 // Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index
 // family), graph_walk.h (the best-first walk of both graph indexes)
 // The handles' grow-only device buffers own themselves: device_buf.h (DeviceBuf<T> and the per-handle DeviceBufSet; host code only);

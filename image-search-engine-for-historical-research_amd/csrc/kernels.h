@@ -474,6 +474,31 @@ void launch_ivfr_encode(const void* x, int dtype, int64_t rs, int64_t cs, int64_
 void launch_ivfr_rows(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const float* G, int32_t d, const uint8_t* lists, float* out,
                       hipStream_t stream);
 
+// ivfflat.hip -- inverted file over the stored f32 rows of a gallery (api_ivfflat.hip).  The value of a (query, row)
+// pair and the order are launch_refine's; a list is a run of local rows, ascending, in list_rows [n] behind list_off int64 [nlist + 1]
+constexpr int IVFFLAT_SLAB_ROWS = 2048;                                     // positions of a query's candidate sequence per scan workgroup
+constexpr int IVFF_MAX_LISTS = 8192, IVFF_MAX_BLOCKS = 1024;
+// rows per workgroup of the list build: 2048 at the least, a multiple of 256, at most IVFF_MAX_BLOCKS workgroups
+static inline int64_t ivff_block_rows(int64_t n) {
+  const int64_t r = ((n + IVFF_MAX_BLOCKS - 1) / IVFF_MAX_BLOCKS + 255) / 256 * 256;
+  return r < 2048 ? 2048 : r;
+}
+void launch_ivff_take_ids(const int64_t* best, int64_t m, int32_t* out, hipStream_t stream);
+void launch_ivff_check(const int32_t* ids, int32_t nlist, int64_t m, uint32_t* flag, hipStream_t stream);
+// ids [n] int32, every one in [0, nlist) -> list_off, list_rows.  Scratch: hist [nlist][ceil(n / ivff_block_rows(n))], sizes [nlist]
+void launch_ivff_lists(const int32_t* ids, int64_t n, int32_t nlist, uint32_t* hist, uint32_t* sizes, int64_t* list_off, int32_t* list_rows,
+                       hipStream_t stream);
+// probes [nq][nprobe], int64 (in_is_i64) or int32: entries outside [0, nlist) and repeats of an earlier entry -> -1 in norm, then
+// the prefix of list sizes pref [nq][nprobe + 1]
+void launch_ivff_prefix(const void* in, int in_is_i64, int64_t nq, int32_t nlist, int32_t nprobe, const int64_t* list_off, int32_t* norm,
+                        int32_t* pref, hipStream_t stream);
+// grid (nslab, nq): nq <= 65535, 1 <= k <= IVFFLAT_SLAB_ROWS; nslab * IVFFLAT_SLAB_ROWS covers every query's candidates; probes: the
+// normalised ones.  part_key / part_id [nq][nslab][k], pcnt [nq][nslab]; any of the four outputs may be NULL
+void launch_ivff_search(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int l2, const int64_t* list_off,
+                        const int32_t* list_rows, const int32_t* probes, const int32_t* pref, int32_t nprobe, const uint64_t* allow,
+                        int32_t k, int32_t nslab, int32_t nq, uint64_t* part_key, int64_t* part_id, uint32_t* pcnt, int64_t row_offset,
+                        int64_t* out_idx, float* out_val, double* out_val64, int64_t* out_scanned, hipStream_t stream);
+
 // pq_remove.hip -- in-place row removal of the PQ and the IVF-PQ index (api_pq.hip, api_ivfpq.hip).  keep [ceil(n / 64)]: the bitmap
 // of the rows that stay (bits at or beyond n clear); prefix [ceil(n / 64) + 1]: the exclusive count of keep bits per word.
 // Flat index, one chunk of source blocks [blk0, blk1): its survivors -> the staging area, whose block 0 stands for block dst_blk0

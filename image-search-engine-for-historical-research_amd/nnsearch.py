@@ -787,9 +787,84 @@ def matching_ANNOY_hip(K, embedded_features_train, embedded_features_test, metri
     return _fill_short_rows(idx, num_train), (t2 - t1) / max(num_test, 1)
 
 
+def _ivfflat_path(dataset, nlist):
+    return os.path.join(os.path.dirname(_gallery_path(dataset)), "mi355_ivfflat_L%d.npz" % nlist)
+
+
+def ivfflat_default_nlist(num_train):
+    """faiss's rule of thumb for the lists of an inverted file, 4 sqrt(N), kept within what the index takes: 2 .. 8192."""
+    return int(min(_lib.IVFFLAT_MAX_LISTS, max(2, round(4 * np.sqrt(int(num_train))))))
+
+
+def matching_IVF_hip(K, embedded_features_train, embedded_features_test, dataset=None, nlist=None, nprobe=8, metric="euclidean",
+                     ifgenerate=True):
+    """An inverted file over the raw database rows, faiss IndexIVFFlat -- the reference's matching_PQ_Net_bucket
+    (src/utils/nnsearch.py:949-998) without the PQ loss --, `--matching_method IVF`, with the reference's return convention
+    -> (idx int64 [Q, K], time_per_query).  nlist centroids are learned on the database rows (_lib.IVFFlatIndex.train: the
+    library's deterministic k-means, seed 0; nlist=None: ivfflat_default_nlist(N) = min(8192, max(2, round(4 sqrt(N))))), every
+    row goes to the list of its nearest centroid, and a query's answer is the exact top K, by float64 direct-form distance with
+    ties to the lower index, among the rows of its nprobe nearest lists; nprobe == nlist is the exhaustive
+    answer of matching_L2_hip.  metric 'euclidean': the raw rows in a squared-L2 gallery; 'angular': rows and queries L2-normalised
+    first; anything else raises ValueError.  Where the probed lists hold fewer than K rows the tail is filled with the lowest indices
+    not in the answer, as the reference's graph matchers do.  With a `dataset` the centroids and the list of every row persist as
+    outputs/<dataset>/mi355_ivfflat_L<nlist>.npz (written to a temporary name and renamed): trained, assigned and written iff
+    `ifgenerate`, otherwise loaded -- a missing file raises FileNotFoundError; dataset=None writes nothing (and needs ifgenerate).
+    2 <= nlist <= min(N, 8192), 1 <= nprobe <= nlist, 1 <= K <= min(N, 2048).  The timer spans the search only,
+    device-synchronised.  Bad input raises ValueError before the device is touched.  The speed of this index has not been measured."""
+    if metric not in ("euclidean", "angular"):
+        raise ValueError("metric = %r: 'euclidean' or 'angular'" % (metric,))
+    train, test = np.asarray(embedded_features_train), np.asarray(embedded_features_test)
+    if train.ndim != 2 or test.ndim != 2 or train.shape[1] != test.shape[1]:
+        raise ValueError("expected rows [N, dim] and queries [Q, dim], got %s and %s" % (train.shape, test.shape))
+    for name, a in (("embedded_features_train", train), ("embedded_features_test", test)):
+        if not np.issubdtype(a.dtype, np.floating):
+            raise ValueError("%s must be a floating-point array (got %s)" % (name, a.dtype))
+    K, nprobe = int(K), int(nprobe)
+    num_train, num_test = train.shape[0], test.shape[0]
+    if K < 1 or K > num_train:
+        raise ValueError("K = %d, the database holds %d rows" % (K, num_train))
+    if K > _lib.IVFFLAT_MAX_K:
+        raise ValueError("K <= %d" % _lib.IVFFLAT_MAX_K)
+    nlist = ivfflat_default_nlist(num_train) if nlist is None else int(nlist)
+    if not 2 <= nlist <= min(num_train, _lib.IVFFLAT_MAX_LISTS):
+        raise ValueError("nlist = %d: 2 .. min(N = %d, %d) lists" % (nlist, num_train, _lib.IVFFLAT_MAX_LISTS))
+    if not 1 <= nprobe <= nlist:
+        raise ValueError("nprobe = %d, the index has nlist = %d lists (1 .. nlist)" % (nprobe, nlist))
+    if dataset is None and not ifgenerate:
+        raise ValueError("ifgenerate=False loads the lists of a dataset: give one")
+    if metric == "angular":
+        train = _l2_rows_f32(train, "embedded_features_train")
+        test = _l2_rows_f32(test, "embedded_features_test")
+    if not ifgenerate:
+        with np.load(_ivfflat_path(dataset, nlist)) as z:            # (FileNotFoundError when it was never generated)
+            cent = _lib.ivfflat_centroids(z["centroids"], train.shape[1])
+            lids = _lib.ivfflat_list_ids(z["list_ids"], num_train, cent.shape[0])
+        if cent.shape[0] != nlist:
+            raise ValueError("stored centroids of shape %s, this call takes [%d, %d]" % (cent.shape, nlist, train.shape[1]))
+    else:
+        cent = _lib.IVFFlatIndex.train(train, nlist, seed=0)
+    rows = Gallery.l2_from_host(train)
+    try:
+        f = _lib.IVFFlatIndex.build(rows, cent) if ifgenerate else _lib.IVFFlatIndex.from_lists(rows, cent, lids)
+        with f:
+            if ifgenerate and dataset is not None:
+                path = _ivfflat_path(dataset, nlist)
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                tmp = "%s.tmp.%d.%s.npz" % (path, os.getpid(), uuid.uuid4().hex[:12])
+                with _path_lock(path):
+                    np.savez(tmp, centroids=f.centroids(), list_ids=f.list_ids())
+                    os.replace(tmp, path)
+            t1 = time.time()
+            idx, _, _ = f.search(test, K, nprobe=nprobe)   # (synchronous: the results are on the host when it returns)
+            t2 = time.time()
+    finally:
+        rows.close()
+    return _fill_short_rows(idx, num_train), (t2 - t1) / max(num_test, 1)
+
+
 MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": matching_Greedyhash_hip, "PQ": matching_Nano_PQ_hip,
                     "PQ13": matching_Nano_PQ_wide_hip, "HNSW": matching_HNSW_hip, "PQ_HNSW": matching_HNSW_NanoPQ_hip,
-                    "ANNOY": matching_ANNOY_hip}
+                    "ANNOY": matching_ANNOY_hip, "IVF": matching_IVF_hip}
 
 
 def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test):

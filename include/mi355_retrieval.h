@@ -339,6 +339,58 @@ int mi_forest_search(mi_forest* f, const void* q, int64_t nq, int dtype, int64_t
 int mi_forest_search_device(mi_forest* f, const float* q_dev, int64_t nq, int32_t k, int64_t* out_idx_dev, float* out_val_dev,
                             double* out_val64_dev, void* stream);
 
+/* ---- IVF-Flat index: an inverted file over the RAW rows of a gallery, faiss IndexIVFFlat -- the reference's
+ * matching_PQ_Net_bucket without the PQ loss.  DESIGN.md 5.18.  What is approximate is WHICH rows a query reaches (the rows of the
+ * lists it probes); everything else is an exact, deterministic function of centroids, lists, stored rows and query.
+ * A handle sits over ONE gallery `rows` (one shard on one device, squared-L2 or inner product, as for mi_refine, mi_graph and
+ * mi_forest), which must outlive it.  The rows are neither copied nor permuted: the index costs 4 bytes per row plus the centroids.
+ *   centroids   float32 [nlist][d] row-major in host memory, every value finite, 2 <= nlist <= 8192, d the caller's d of the
+ *               gallery.  The handle keeps them on the device in rows of the gallery's padded stride.
+ *   value       of (x, centroid) and of (query, row) alike, mi_refine's, with the same lane and column walk: on an L2 gallery the
+ *               direct-form float64 squared distance, smaller is better; on any other gallery the float64 FMA inner product against
+ *               the f32 values as stored or given, larger is better.
+ *   order       (value best first, id ascending), for lists and for rows alike.
+ *   probe       the nprobe best lists of a query in that order, 1 <= nprobe <= nlist: mi_refine over the centroid table.
+ *   assignment  row i belongs to the probe-1 list of its STORED f32 row, the row mi_refine evaluates.
+ *   lists       list_off int64 [nlist + 1], list_rows int32 [n] of LOCAL rows, ascending within a list; empty lists are legal.
+ * mi_ivfflat_build assigns on the device, in chunks of stored rows (no row crosses the host link), and gives the same bytes on
+ * every call.  mi_ivfflat_create takes the caller's list ids, int32 [n] in host or device memory (`memspace`); a value outside
+ * [0, nlist) is MI_ERR_INVALID.
+ *   search      per query the candidates are the rows of the probed lists that the allow bitmap (that of mi_knn_search_filtered:
+ *               ceil(n / 64) words, bit (i & 63) of word (i >> 6) admits local row i; NULL admits all) admits; the answer is the
+ *               best k of them in the order, 1 <= k <= 2048: ids row_offset + local row (int64), values float64 (out_val64) with
+ *               their f32 cast (out_val); either may be NULL.  Fewer than k candidates: trailing ids -1, values +INFINITY (L2) or
+ *               -INFINITY.  out_scanned (int64 [nq], may be NULL): the rows evaluated.  probes (may be NULL): int32 [nq][nprobe],
+ *               the caller's lists in place of the library's; an entry outside [0, nlist) or repeating an earlier entry of its row
+ *               is "no list".  The query is used as given.  nq == 0 is MI_OK and writes nothing.
+ * Consequences: with nprobe == nlist and no bitmap an L2 gallery gives mi_knn_search_l2's ids and dist64 bit for bit; any probe set
+ * gives the answer of mi_knn_search_l2 with the allow bitmap of those lists.  The answer does not depend on the batch or on how it
+ * is split into launches (no atomics, no grid barrier).
+ * The handle records the gallery's n: after mi_gallery_append* or mi_gallery_remove_rows probe and search return MI_ERR_INVALID
+ * and read no stale table.  Not built: updating an index in place, sharding, residuals, a list-major scan that shares a list's
+ * rows between the queries that probe it.  Nothing routes to this index by default, and its speed has not been measured. */
+typedef struct mi_ivfflat mi_ivfflat; /* opaque */
+int mi_ivfflat_build(mi_gallery* rows, const float* centroids, int32_t nlist, mi_ivfflat** out);
+int mi_ivfflat_create(mi_gallery* rows, const float* centroids, int32_t nlist, const int32_t* list_ids, int memspace,
+                      mi_ivfflat** out);
+/* n, d, nlist, hbm_bytes (any may be NULL); the list sizes int64 [nlist], list_off int64 [nlist + 1] and list_rows int32 [n]
+ * (either may be NULL) and the centroids float32 [nlist][d] into host memory */
+int mi_ivfflat_info(const mi_ivfflat* f, int64_t* n, int32_t* d, int32_t* nlist, int64_t* hbm_bytes);
+int mi_ivfflat_list_sizes(mi_ivfflat* f, int64_t* out_sizes);
+int mi_ivfflat_get_lists(mi_ivfflat* f, int64_t* out_list_off, int32_t* out_list_rows);
+int mi_ivfflat_get_centroids(mi_ivfflat* f, float* out_host);
+int mi_ivfflat_destroy(mi_ivfflat* f); /* NULL is MI_OK */
+/* Every query entry point is a device form: q_dev [nq][d] packed f32, probes_dev and allow_dev in device memory (either may be
+ * NULL), outputs in device memory; enqueued on `stream`, no synchronisation.  It stages the queries, the probes, their prefixes
+ * and the partial lists of the scan in buffers of the handle (grown when a larger call comes; a batch whose staging would exceed
+ * 256 MiB runs in chunks of queries): calls on one handle must be serialised by the caller and enqueued on ONE stream.
+ * mi_ivfflat_probe_device writes the probes alone, int32 [nq][nprobe].  Not built: host forms that take queries of any element
+ * type and strides, as mi_knn_search_l2 does (a caller stages its queries as packed f32; the Python binding does). */
+int mi_ivfflat_probe_device(mi_ivfflat* f, const float* q_dev, int64_t nq, int32_t nprobe, int32_t* out_probes_dev, void* stream);
+int mi_ivfflat_search_device(mi_ivfflat* f, const float* q_dev, int64_t nq, int32_t k, int32_t nprobe, const int32_t* probes_dev,
+                             const uint64_t* allow_dev, int64_t* out_idx_dev, float* out_val_dev, double* out_val64_dev,
+                             int64_t* out_scanned_dev, void* stream);
+
 /* ---- binary index: exact Hamming top-K on packed binary codes.  The reference's matching_Greedyhash(K, hash_codes_train,
  * hash_codes_test) (src/utils/nnsearch.py:1001-1013: XOR against every gallery code, sum, argsort, first K) and faiss
  * IndexBinaryFlat (what IndexLSH, src/utils/nnsearch.py:734-745, searches with internally).  DESIGN.md 5.13.
