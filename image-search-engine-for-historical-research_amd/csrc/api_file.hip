@@ -12,7 +12,7 @@ struct FileHeader {
   int64_t version, n, npad, row_offset;
   int32_t d, dp, norm_mode, img_f16;
   float gstat3[3];
-  uint32_t reserved;
+  uint32_t metric;             // MI_METRIC_IP (0: the word was reserved and zero before) | MI_METRIC_L2 (1: d counts the hidden columns)
   uint64_t section_sum[3];     // f32 rows, image, row norms
   uint64_t header_sum;         // of all bytes above
 };
@@ -204,7 +204,6 @@ extern "C" {
 
 int mi_gallery_save(const mi_gallery* g, const char* path) {
   REQUIRE(g && path, "null");
-  REFUSE_L2(g, "mi_gallery_save (the prepared-gallery file)");
   HIPC(hipSetDevice(g->device));
   HIPC(hipStreamSynchronize(g->stream));
   FileHeader h{};
@@ -213,8 +212,9 @@ int mi_gallery_save(const mi_gallery* g, const char* path) {
   h.n = g->n;
   h.npad = g->npad;
   h.row_offset = g->row_offset;
-  h.d = g->d;
+  h.d = g->d;                  // squared-L2 gallery: ud + 3, the sections are written as they lie, hidden columns included
   h.dp = g->dp;
+  h.metric = (uint32_t)g->metric;
   h.norm_mode = g->norm_mode;
   h.img_f16 = g->img_f16;
   HIPC(hipMemcpy(h.gstat3, g->gstat3, 12, hipMemcpyDeviceToHost));
@@ -266,7 +266,10 @@ int mi_gallery_load(const char* path, int device, mi_gallery** out) {
     fclose(f);
     return fail(MI_ERR_IO, "gallery file header checksum mismatch");
   }
-  if (h.n < 1 || h.d < 1 || h.n >= ((int64_t)1 << 32) || h.norm_mode < 0 || h.norm_mode > 2) {
+  // a squared-L2 gallery is a raw gallery of at least one user column and the three hidden ones
+  const bool l2 = h.metric == (uint32_t)MI_METRIC_L2;
+  if (h.n < 1 || h.d < 1 || h.n >= ((int64_t)1 << 32) || h.norm_mode < 0 || h.norm_mode > 2 ||
+      (h.metric != (uint32_t)MI_METRIC_IP && !l2) || (l2 && (h.norm_mode != MI_NORM_NONE || h.d < 4))) {
     fclose(f);
     return fail(MI_ERR_IO, "inconsistent header");
   }
@@ -274,6 +277,9 @@ int mi_gallery_load(const char* path, int device, mi_gallery** out) {
   g->device = device;
   g->n = h.n;
   g->d = h.d;
+  g->metric = (int)h.metric;
+  g->ud = l2 ? h.d - 3 : h.d;
+  g->cap = h.n;
   g->norm_mode = h.norm_mode;
   g->img_f16 = h.img_f16;
   g->row_offset = h.row_offset;

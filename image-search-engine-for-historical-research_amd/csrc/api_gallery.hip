@@ -263,7 +263,9 @@ int gallery_create_any(const void* data, int64_t n, int32_t d, int dtype, int64_
     // rows with a non-finite norm, so a row with an element beyond fp16's range (image norm inf) is looked for on its own;
     // the answer goes into the fourth word of the gstat3 allocation
     const bool raw_f16 = g->img_f16 && norm_mode == MI_NORM_NONE;
-    if (raw_f16) launch_rowstat_img_overflow(g->rowstat, n, reinterpret_cast<uint32_t*>(g->gstat3 + 3), g->stream);
+    // (squared L2: a bias beyond float32 leaves the row's f32 norm non-finite as well, and its user columns may still be inf in
+    // an fp16 image only: any row with a non-finite image norm counts)
+    if (raw_f16) launch_rowstat_img_overflow(g->rowstat, n, reinterpret_cast<uint32_t*>(g->gstat3 + 3), g->stream, /*any_f32=*/l2);
     e = hipStreamSynchronize(g->stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess || !raw_f16) break;

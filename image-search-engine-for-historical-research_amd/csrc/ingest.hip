@@ -933,13 +933,15 @@ __global__ __launch_bounds__(256) void rowstat_max_kernel(const RowStat* __restr
 }
 
 // rowstat_max_kernel skips rows with a non-finite norm, so a row whose f32 norm is finite but whose IMAGE norm is not -- a raw
-// element beyond fp16's range became inf -- is invisible in the maxima: this is what reports it
+// element beyond fp16's range became inf -- is invisible in the maxima: this is what reports it.  any_f32: the f32 norm is not
+// asked (squared-L2 galleries: the norm covers the hidden bias columns, and a bias beyond float32 makes it non-finite over user
+// columns that are finite in f32 and inf in an fp16 image)
 __global__ __launch_bounds__(256) void rowstat_img_overflow_kernel(const RowStat* __restrict__ rowstat, int64_t n,
-                                                                   uint32_t* __restrict__ flag) {
+                                                                   uint32_t* __restrict__ flag, int any_f32) {
   bool hit = false;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const RowStat r = rowstat[i];
-    hit |= isfinite(r.norm_f32) && !isfinite(r.norm_img);
+    hit |= (any_f32 || isfinite(r.norm_f32)) && !isfinite(r.norm_img);
   }
   if (hit) atomicOr(flag, 1u);
 }
@@ -1080,10 +1082,10 @@ void launch_rowstat_max(const RowStat* rowstat, int64_t n, float* out3, hipStrea
   hipLaunchKernelGGL(rowstat_max_kernel, dim3(blocks), dim3(256), 0, stream, rowstat, n, out3);
 }
 
-void launch_rowstat_img_overflow(const RowStat* rowstat, int64_t n, uint32_t* flag, hipStream_t stream) {
+void launch_rowstat_img_overflow(const RowStat* rowstat, int64_t n, uint32_t* flag, hipStream_t stream, bool any_f32) {
   hipMemsetAsync(flag, 0, sizeof(uint32_t), stream);
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(512, (n + 255) / 256));
-  hipLaunchKernelGGL(rowstat_img_overflow_kernel, dim3(blocks), dim3(256), 0, stream, rowstat, n, flag);
+  hipLaunchKernelGGL(rowstat_img_overflow_kernel, dim3(blocks), dim3(256), 0, stream, rowstat, n, flag, any_f32 ? 1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -24,8 +24,9 @@ void launch_build_sample_f32(const float* gal_f32, float* samp_f32, int64_t n, i
 int64_t sample_source_row_host(int64_t i, int64_t n, int64_t n_s);   // row_base: output rows start here (gallery append); src row 0 <-> row_base
 void launch_checksum(const void* data, size_t bytes, unsigned long long* out_dev, hipStream_t stream);   // bytes % 8 == 0
 void launch_rowstat_max(const RowStat* rowstat, int64_t n, float* out3, hipStream_t stream, bool reset = true);
-// *flag = 1 if a row with a finite f32 norm has a non-finite image norm (an element beyond the image type's range), else 0
-void launch_rowstat_img_overflow(const RowStat* rowstat, int64_t n, uint32_t* flag, hipStream_t stream);
+// *flag = 1 if a row with a finite f32 norm (any_f32: any row) has a non-finite image norm (an element beyond the image type's
+// range), else 0
+void launch_rowstat_img_overflow(const RowStat* rowstat, int64_t n, uint32_t* flag, hipStream_t stream, bool any_f32 = false);
 
 // gemm_select.hip -- fp16/bf16 MFMA scoring of gallery tiles [tile0, tile0+ntiles) against nqt query tiles with the
 // fused survivor filter.  first != 0: store every score of the chunk (rows tile0*256.. at position row).

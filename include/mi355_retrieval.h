@@ -169,8 +169,8 @@ int mi_knn_search_filtered(mi_gallery* g, const void* q, int64_t nq, int dtype, 
  * capacity > n the gallery is appendable, and data == NULL with n == 0 gives an empty appendable one (appendable L2 galleries use
  * the bf16 image).  On an L2 gallery mi_gallery_append*, mi_gallery_info, mi_gallery_get_rows, mi_gallery_destroy,
  * mi_gallery_calibrate, mi_gallery_scatter, the options, statistics, flags and diagnostics work on the caller's d; every other
- * entry point that takes a gallery returns MI_ERR_UNSUPPORTED (radius search, save, alpha-QE, diffusion, the online front and
- * sharded search are not defined for this metric).  The _l2 entry points return MI_ERR_INVALID on any other gallery.  The order
+ * entry point that takes a gallery returns MI_ERR_UNSUPPORTED (radius search, alpha-QE, diffusion, the online front and
+ * sharded search are not defined for this metric); mi_gallery_save / mi_gallery_load keep the metric (header word `metric`).  The _l2 entry points return MI_ERR_INVALID on any other gallery.  The order
  * among non-finite distances (non-finite inputs) is unspecified. */
 int mi_gallery_create_l2(const void* data, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
                          int memspace, int device, int64_t row_offset, int64_t capacity, mi_gallery** out);

@@ -3,7 +3,9 @@
 A test-local numpy WRITER restates the file layout a second time, as an encoder (reshape / transpose / per-row chunk
 permutation instead of the reader's offset table), and a numpy model of the ingest arithmetic fills it: the reader must return
 every element where it started, the checks of tests/test_gpu_gallery_reference.py must pass on the clean file and FAIL, each by
-the assertion meant for it, on a deliberately damaged one."""
+the assertion meant for it, on a deliberately damaged one.  Squared-L2 files (header word metric == 1, d = ud + 3) are modelled
+with the numpy restatement of the bias split (_gallery_file.split_bias), and every way the hidden columns can be wrong that the
+suite knows of fails check_l2_columns -- or the existing check that covers it -- by name."""
 import math
 import os
 import struct
@@ -31,14 +33,14 @@ def encode_image(bits):
     return out.reshape(-1)
 
 
-def write_gallery_file(path, rows_f32, image_bits, rowstat, gstat3, d, norm_mode, img_f16, sums=None):
+def write_gallery_file(path, rows_f32, image_bits, rowstat, gstat3, d, norm_mode, img_f16, sums=None, metric=0):
     n, dp = rows_f32.shape
     npad = image_bits.shape[0]
     sec = [np.ascontiguousarray(rows_f32, dtype="<f4").tobytes(), encode_image(np.ascontiguousarray(image_bits, dtype="<u2")).tobytes(),
            np.ascontiguousarray(rowstat, dtype="<f4").tobytes()]
     if sums is None:
         sums = [gf_mod.section_sum(s) for s in sec]
-    head = struct.pack("<8s4q4i3fI3Q", b"MI355GAL", 2, n, npad, 0, d, dp, norm_mode, img_f16, *[float(v) for v in gstat3], 0, *sums)
+    head = struct.pack("<8s4q4i3fI3Q", b"MI355GAL", 2, n, npad, 0, d, dp, norm_mode, img_f16, *[float(v) for v in gstat3], metric, *sums)
     h = 0xcbf29ce484222325
     for byte in head:                                                  # FNV-1a of the header (csrc/api_file.hip host_sum)
         h = ((h ^ byte) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
@@ -272,3 +274,142 @@ def test_tie_window_and_whitened_tolerance():
     gf_mod.check_stored_rows(g(tiny), ref=np.array([[float(tiny) + 0.9e-12]]), whitened=True)
     with pytest.raises(AssertionError, match="stored rows"):
         gf_mod.check_stored_rows(g(tiny), ref=np.array([[float(tiny) + 1.1e-12]]), whitened=True)
+
+
+# ---- squared-L2 files: the hidden columns ------------------------------------------------------------------------------------
+def model_l2_gallery(x, img_f16, sign=1.0, stat_cols=None):
+    """numpy model of an L2 gallery: the user's rows as given, the split of -1/2 ||g||^2 behind them, zeros up to dp; image and
+    rounding norms over the whole augmented row.  sign = -1 / stat_cols = ud model two of the damages."""
+    n, ud = x.shape
+    d = ud + 3
+    dp, npad = -(-d // 64) * 64, -(-n // 256) * 256
+    rows = np.zeros((n, dp), np.float32)
+    rows[:, :ud] = x
+    b, c1, c2, c3 = gf_mod.split_bias(rows[:, :ud], img_f16)
+    rows[:, ud], rows[:, ud + 1], rows[:, ud + 2] = sign * c1, sign * c2, sign * c3
+    return (rows,) + _l2_image_and_stats(rows, npad, img_f16, stat_cols)
+
+
+def _l2_image_and_stats(rows, npad, img_f16, stat_cols=None):
+    n = rows.shape[0]
+    bits = np.zeros((npad, rows.shape[1]), np.uint16)
+    bits[:n] = gf_mod.round16_bits(rows, img_f16)
+    g = rows.astype(np.float64)[:, :stat_cols]
+    b = gf_mod.decode16(bits[:n], img_f16)[:, :stat_cols]
+    stat = np.zeros((npad, 3), np.float32)
+    with np.errstate(invalid="ignore"):
+        for j, v in enumerate((g, b, b - g)):
+            stat[:n, j] = np.sqrt((v * v).sum(axis=1)) * (1.0 + 1e-6)
+    return bits, stat, gf_mod.expected_maxima(stat, n)
+
+
+def _l2_source(n=300, ud=100, scale=1.5):
+    x = _source(n, ud, seed=n + ud)
+    x = (x / np.linalg.norm(x.astype(np.float64), axis=1, keepdims=True) * scale).astype(np.float32)
+    x[7] = 0.0                                                          # zero row: c1 = -0.0
+    x[8] = x[9]
+    x[10] *= np.float32(1e-20)                                          # bias ~1e-40: below float32's normal range
+    return x
+
+
+@pytest.mark.parametrize("ud", [1, 61, 62, 100, 2048])
+@pytest.mark.parametrize("img_f16", [1, 0])
+def test_l2_checks_pass_on_the_model(tmp_path, img_f16, ud):
+    x = _l2_source(300 if ud < 2048 else 40, ud)
+    if not img_f16:
+        x[11] *= np.float32(300.0)                                      # bias beyond fp16's range
+    rows, bits, stat, gmax = model_l2_gallery(x, img_f16)
+    path = str(tmp_path / "g.bin")
+    write_gallery_file(path, rows, bits, stat, gmax, ud + 3, NORM_NONE, img_f16, metric=1)
+    g = gf_mod.read_gallery_file(path)
+    assert (g.metric, g.ud, g.d, g.dp) == (1, ud, ud + 3, -(-(ud + 3) // 64) * 64)
+    gf_mod.check_all(g, ref=x.astype(np.float64), get_rows=rows[:, :ud])
+    assert np.signbit(g.rows_f32[7, ud]) and not g.rows_f32[7].any() and g.image_bits[7, ud] == 0x8000
+    # an inner-product file of the same rows: the new check does not run, the header word is 0
+    write_gallery_file(path, rows, bits, stat, gmax, ud + 3, NORM_NONE, img_f16)
+    g = gf_mod.read_gallery_file(path)
+    assert (g.metric, g.ud) == (0, ud + 3)
+    gf_mod.check_all(g, ref=rows[:, :ud + 3].astype(np.float64), get_rows=rows[:, :ud + 3], norm_bounds=gmax)
+
+
+def test_l2_bias_beyond_float32_is_pinned_as_non_finite(tmp_path):
+    """A row of norm 1e20: -1/2 ||g||^2 = -5e39 is beyond float32, the split gives (-inf, +inf, NaN), the stats are non-finite and
+    stay outside the maxima; the checks accept exactly that, and only where the bias is that large."""
+    x = _l2_source()
+    x[11] = (x[11].astype(np.float64) / 1.5 * 1e20).astype(np.float32)
+    rows, bits, stat, gmax = model_l2_gallery(x, 0)
+    assert rows[11, 100] == -np.inf and rows[11, 101] == np.inf and np.isnan(rows[11, 102])
+    assert not np.isfinite(stat[11]).any() and np.isfinite(gmax).all()
+    path = str(tmp_path / "g.bin")
+    write_gallery_file(path, rows, bits, stat, gmax, 103, NORM_NONE, 0, metric=1)
+    gf_mod.check_all(gf_mod.read_gallery_file(path), ref=x.astype(np.float64), get_rows=rows[:, :100])
+    rows[12, 100:103] = rows[11, 100:103]                               # the same columns on an ordinary row
+    bits, stat, gmax = _l2_image_and_stats(rows, 512, 0)
+    write_gallery_file(path, rows, bits, stat, gmax, 103, NORM_NONE, 0, metric=1)
+    with pytest.raises(AssertionError, match="^l2 columns: split: non-finite"):
+        gf_mod.check_l2_columns(gf_mod.read_gallery_file(path))
+
+
+def _l2_damage(kind, x, img_f16):
+    """-> (check, message pattern, checks the same damage implies, rows, bits, stat, gmax, metric)"""
+    n, ud = x.shape
+    rows, bits, stat, gmax = model_l2_gallery(x, img_f16)
+    npad = bits.shape[0]
+    rnd = lambda v: gf_mod.decode16(gf_mod.round16_bits(v, img_f16), img_f16).astype(np.float32)   # noqa: E731
+    if kind == "hidden columns one chunk off in the image":
+        bits[:n, ud + 8:ud + 11] = bits[:n, ud:ud + 3]
+        bits[:n, ud:ud + 3] = 0
+        return "l2 columns", "l2 columns: image", {"image", "padding column", "rounding norms"}, rows, bits, stat, gmax, 1
+    if kind == "c2 and c3 swapped":
+        rows[:, [ud + 1, ud + 2]] = rows[:, [ud + 2, ud + 1]]
+        return ("l2 columns", r"l2 columns: split: c2 != float32\(B - c1\)", set(), rows) + _l2_image_and_stats(rows, npad, img_f16) + (1,)
+    if kind == "c2 replaced by its 16-bit rounding":
+        rows[:, ud + 1] = rnd(rows[:, ud + 1])
+        return ("l2 columns", "l2 columns: (split|value)", set(), rows) + _l2_image_and_stats(rows, npad, img_f16) + (1,)
+    if kind == "c1 not representable in the image type":
+        b = -0.5 * (x.astype(np.float64) ** 2).sum(1)
+        rows[:, ud] = b.astype(np.float32)
+        rows[:, ud + 1] = (b - rows[:, ud].astype(np.float64)).astype(np.float32)
+        rows[:, ud + 2] = 0.0
+        return ("l2 columns", r"l2 columns: split: c1 != round16", set(), rows) + _l2_image_and_stats(rows, npad, img_f16) + (1,)
+    if kind == "non-zero in column ud + 3":
+        rows[5, ud + 3] = 0.25
+        return ("stored rows", "stored rows: padding columns", {"padding column"}, rows) + _l2_image_and_stats(rows, npad, img_f16) + (1,)
+    if kind == "non-zero image element in column ud + 3":
+        bits[5, ud + 3] = 0x3C00
+        return "padding column", "padding column:", {"image", "rounding norms"}, rows, bits, stat, gmax, 1
+    if kind == "rounding norms over the user's columns only":
+        return ("rounding norms", "rounding norms: stat / norm outside", set(), rows) + _l2_image_and_stats(rows, npad, img_f16, ud) + (1,)
+    if kind == "bias of the wrong sign":
+        return ("l2 columns", "l2 columns: value", set()) + model_l2_gallery(x, img_f16, sign=-1.0) + (1,)
+    if kind == "metric word 2":
+        return "header", "header: metric word 2", set(), rows, bits, stat, gmax, 2
+    raise ValueError(kind)
+
+
+L2_DAMAGES = ["hidden columns one chunk off in the image", "c2 and c3 swapped", "c2 replaced by its 16-bit rounding",
+              "c1 not representable in the image type", "non-zero in column ud + 3", "non-zero image element in column ud + 3",
+              "rounding norms over the user's columns only", "bias of the wrong sign", "metric word 2"]
+
+
+@pytest.mark.parametrize("img_f16", [1, 0])
+@pytest.mark.parametrize("kind", L2_DAMAGES)
+def test_each_l2_damage_fails_the_check_meant_for_it(tmp_path, kind, img_f16):
+    x = _l2_source()
+    ud = x.shape[1]
+    check, pattern, implied, rows, bits, stat, gmax, metric = _l2_damage(kind, x, img_f16)
+    path = str(tmp_path / "g.bin")
+    write_gallery_file(path, rows, bits, stat, gmax, ud + 3, NORM_NONE, img_f16, metric=metric)
+    if check == "header":
+        with pytest.raises(AssertionError, match="^" + pattern):
+            gf_mod.read_gallery_file(path)
+        return
+    g = gf_mod.read_gallery_file(path)
+    kw = dict(ref=x.astype(np.float64), get_rows=rows[:, :ud], norm_bounds=None, whitened=False)
+    with pytest.raises(AssertionError, match="^" + pattern):
+        gf_mod.CHECKS[check](g, **kw)
+    with pytest.raises(AssertionError, match=pattern):
+        gf_mod.check_all(g, **kw)
+    for name, fn in gf_mod.CHECKS.items():
+        if name != check and name not in implied:
+            fn(g, **kw)

@@ -15,6 +15,8 @@ that consecutive true distances among the first k + 1 are either exactly equal (
 than B apart, so every id comparison below is exact equality for every query.  Returned dist64 must be within 2 D 2^-53
 relative of the truth (summation order), and dist must be float32(dist64) bit for bit."""
 import ctypes as C
+import os
+import tempfile
 
 import numpy as np
 import pytest
@@ -280,8 +282,8 @@ def _split_bias(X32, f16):
 def test_equals_a_gallery_ingested_with_the_columns():
     """An L2 gallery against a MI_NORM_NONE gallery ingested from the array [g, c1, c2, c3] (the split restated in numpy), searched
     with [q, 1, 1, 1].  This is NOT the section-by-section equality the two galleries should have: the image and RowStat
-    sections of an L2 gallery cannot be read back (no save, hidden columns, no debug entry point), so a few misplaced elements
-    or a norm a few per cent off would pass here.  What the test does pin is what depends on the sections:
+    sections are pinned element by element in tests/test_gpu_l2_gallery_reference.py (the saved file, read back on the host); a
+    few misplaced elements or a norm a few per cent off would pass here.  What the test does pin is what depends on the sections:
     the float64 inner-product scores of the augmented gallery reproduce the L2 distances (f32 section),
     both return the same rows, and the filter keeps and passes on to the exact re-score the same number of rows within a few
     per cent (image and RowStat sections: a wrong swizzle or a misplaced hidden column changes every approximate score, a wrong
@@ -543,7 +545,6 @@ def test_surface():
             lib.mi_range_search(g._h, P(Q), 9, 0, 128, 1, 0.5, 10, P(lims), P(idx), P(sc), None),
             lib.mi_knn_dense_search(g._h, P(Q), 9, 0, 128, 1, 10, P(idx), P(sc), None),
             lib.mi_knn_dense64_search(g._h, P(Q), 9, 0, 128, 1, 10, P(idx), P(sc), None, None),
-            lib.mi_gallery_save(g._h, b"/tmp/never_written.gal"),
             lib.mi_gallery_set_image_dtype(g._h, 0),
             lib.mi_knn_phase1_device(g._h, P(Q), 9, 10, P(sc), None),
             lib.mi_online_create(g._h, None, 10, 3, 4.0, 1e-6, 8, 100, C.byref(C.c_void_p())),
@@ -551,6 +552,18 @@ def test_surface():
         ]
         assert refused == [_lib.MI_ERR_UNSUPPORTED] * len(refused), refused
         assert b"MI_METRIC_L2" in lib.mi_last_error()
+        # save / load keep the metric: the loaded gallery answers bit for bit like the original
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "l2.gal")
+            g.save(path)
+            loaded = _lib.Gallery.load(path)
+        try:
+            assert loaded.get_option("metric") == 1 and (loaded.n, loaded.d) == (g.n, g.d)
+            a, b = g.search_l2(Q, 10), loaded.search_l2(Q, 10)
+            assert np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
+            assert np.array_equal(a[2].view(np.uint64), b[2].view(np.uint64)) and (a[0] == tid).all()
+        finally:
+            loaded.close()
         # what keeps working on the caller's d
         assert g.d == 128 and g.get_rows(0, 3).shape == (3, 128)
         assert g.scatter().shape == (128, 128)

@@ -282,7 +282,7 @@ def test_l2_gallery_and_knn_remove_ids():
     try:
         kept = g.remove(ids)
         assert np.array_equal(kept, np.setdiff1d(np.arange(n), ids)) and g.n == n - len(ids) and g.d == d
-        assert np.array_equal(g.get_rows(0, g.n).view(np.uint32), X[kept].view(np.uint32))     # the hidden columns moved with the rows
+        assert np.array_equal(g.get_rows(0, g.n).view(np.uint32), X[kept].view(np.uint32))     # (the hidden columns: tests/test_gpu_l2_gallery_reference.py)
         fresh = _lib.Gallery.l2_from_host(X[kept])
         a, b, c = g.search_l2(Q, k), fresh.search_l2(Q, k), g.dense64_search_l2(Q, k)
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[2].view(np.uint64), b[2].view(np.uint64))

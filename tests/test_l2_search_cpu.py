@@ -2,9 +2,14 @@
 are exported and bound, answer bad arguments before touching a device, and the three-way split of the bias -1/2 ||g||^2
 (csrc/l2_metric.hip l2_bias_kernel, restated in numpy) sums back to it in float64 for both 16-bit image types."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _gallery_file import split_bias  # noqa: E402  (the numpy restatement of l2_bias_kernel, shared with test_gallery_reference_cpu.py)
 
 NEW = ["mi_gallery_create_l2", "mi_knn_search_l2", "mi_knn_search_l2_device", "mi_knn_dense64_search_l2"]
 
@@ -66,23 +71,6 @@ def _bf16(x32):
     u = np.asarray(x32, np.float32).view(np.uint32).astype(np.uint64)
     u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
     return u.astype(np.uint32).view(np.float32)
-
-
-def split_bias(rows, f16):
-    """numpy restatement of l2_bias_kernel: b = -1/2 sum g^2 in f64; c1 = f32(b) rounded to the image type, c2 = f32(b - c1),
-    c3 = f32(b - c1 - c2)."""
-    g = np.asarray(rows, np.float32).astype(np.float64)
-    b = -0.5 * (g * g).sum(1)
-    b32 = b.astype(np.float32)
-    if f16:
-        with np.errstate(over="ignore"):
-            c1 = b32.astype(np.float16).astype(np.float32)
-        c1 = np.where(np.isfinite(c1), c1, np.float32(-65504.0)).astype(np.float32)   # beyond fp16: its largest finite value
-    else:
-        c1 = _bf16(b32)
-    c2 = (b - c1.astype(np.float64)).astype(np.float32)
-    c3 = (b - c1.astype(np.float64) - c2.astype(np.float64)).astype(np.float32)
-    return b, c1, c2, c3
 
 
 @pytest.mark.parametrize("f16", [True, False])
