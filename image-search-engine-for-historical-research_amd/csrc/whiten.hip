@@ -11,9 +11,10 @@
 //    copied, both into LDS rows of 18 doubles (18 r mod 32 is a different even 8-byte slot for each of the 16 rows of a
 //    ds_read_b64 fragment read, + k: conflict-free); the global loads of chunk c + 1 are in flight under the 64 MFMAs of chunk c;
 //  * the K order inside a 16x16x4 step is the hardware's; across steps it is ascending, like a row-major dot product;
-//  * XCD-aware tile order when dims is a multiple of 1024: XCD x owns the column blocks x, x + 8, .. (its 2 MB slab of P
-//    stays in its L2) and all XCDs walk the row tiles in the same order (an X tile leaves HBM once and is served to the
-//    other seven from the Infinity Cache);
+//  * XCD-aware tile order when the number of 128-column tiles, ceil(dims / 128), is a multiple of 8 (dims = 1000 as well as
+//    1024; the last column tile may be ragged): XCD x owns the column blocks x, x + 8, .. (its 2 MB slab of P stays in its
+//    L2) and all XCDs walk the row tiles in the same order (an X tile leaves HBM once and is served to the other seven
+//    from the Infinity Cache);
 //  * the normalisation reads every row ONCE into registers (dims <= 4096), reduces and writes it back scaled -- or the
 //    rows go straight into the gallery ingest (mi_gallery_append_whitened_device), whose MI_NORM_L2_EPS mode is this very
 //    tail, so that the [N, dims] float64 matrix never exists beyond a chunk.
