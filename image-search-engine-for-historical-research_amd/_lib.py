@@ -86,6 +86,10 @@ SIGNATURES = {
                             C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_debug_l2_tail_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "mi_knn_search_minkowski": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double,
+                                          C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_knn_search_minkowski_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_graph_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "mi_graph_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "mi_graph_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -418,6 +422,26 @@ def _upload_allow(bits, tdev):
     return None if bits is None else torch.from_numpy(np.ascontiguousarray(bits).view(np.int64)).to(tdev)
 
 
+MINK_L1, MINK_LINF, MINK_LP = 1, 2, 3
+MINK_METRICS = {"l1": MINK_L1, "linf": MINK_LINF, "lp": MINK_LP}
+MINK_MAX_K = 2048
+
+
+def minkowski_args(metric, p, k):
+    """The checks of a Minkowski search that need no device -> (metric code, p as the library takes it).  Raises ValueError on
+    an unknown metric, on "lp" without a finite p > 0 (use "linf" for the infinite case) and on k outside [1, 2048]; p is
+    ignored for "l1" and "linf"."""
+    if metric not in MINK_METRICS:
+        raise ValueError("metric must be 'l1', 'linf' or 'lp', got %r" % (metric,))
+    if metric != "lp":
+        p = 0.0
+    elif p is None or not np.isfinite(float(p)) or not float(p) > 0:
+        raise ValueError("metric 'lp' takes a finite p > 0 (got %r); 'linf' is the infinite case" % (p,))
+    if not 1 <= int(k) <= MINK_MAX_K:
+        raise ValueError("k = %d, a Minkowski search takes 1 .. %d" % (int(k), MINK_MAX_K))
+    return MINK_METRICS[metric], float(p)
+
+
 def _range_capacity(nq, max_results):
     """First capacity of a range search: max_results, by default Q * 1024."""
     return int(max_results) if max_results is not None else nq * 1024
@@ -705,6 +729,29 @@ class Gallery(_Handle):
         check(load().mi_refine_device(self._h, C.c_void_p(q_ptr), int(nq), C.c_void_p(cand_ptr), int(kc),
                                       int(kc if cand_stride is None else cand_stride), int(k), C.c_void_p(idx_ptr),
                                       C.c_void_p(val_ptr), C.c_void_p(val64_ptr), C.c_void_p(stream)))
+
+    def search_minkowski(self, queries, k, metric="l1", p=None, allow=None):
+        """Exact Minkowski top-k on this gallery's stored rows (mi_knn_search_minkowski; faiss IndexFlat with METRIC_L1 /
+        METRIC_Linf / METRIC_Lp): metric "l1" (sum |q - g|), "linf" (max |q - g|) or "lp" with p > 0 (sum |q - g| ** p, NOT
+        raised to 1 / p), in float64 over the stored f32 row -> (ids int64 [Q,k], dist float32 [Q,k], dist64 float64 [Q,k],
+        seconds): values ascending, ties to the lower id, fewer than k admitted rows -> ids -1, values +inf.  The query is used
+        as given.  allow: anything allow_bitmap takes.  Raises ValueError, before the library is called, on an unknown metric,
+        a p that is not finite and > 0, or k outside [1, 2048]."""
+        code, p = minkowski_args(metric, p, k)
+        a, dt, rs, cs = self._queries(queries)
+        nq, k = a.shape[0], int(k)
+        bits, bits_p, memspace = _resolve_allow(allow, None, self.n, self.row_offset)
+        return self._topk(nq, k, (np.float32, np.float64), lambda idx, dist, dist64, secs: load().mi_knn_search_minkowski(
+            self._h, C.c_void_p(_base_pointer(a)), nq, dt, rs, cs, code, p, k, bits_p, memspace, idx, dist, dist64, secs))
+
+    def search_minkowski_device(self, q_ptr, nq, k, idx_ptr, metric="l1", p=None, allow_ptr=None, dist_ptr=None, dist64_ptr=None,
+                                stream=None):
+        """mi_knn_search_minkowski_device: q_ptr packed float32 [nq][d], allow_ptr None or a device bitmap of ceil(n / 64) uint64
+        words; enqueued on `stream`, no synchronisation."""
+        code, p = minkowski_args(metric, p, k)
+        check(load().mi_knn_search_minkowski_device(self._h, C.c_void_p(q_ptr), int(nq), code, p, int(k), C.c_void_p(allow_ptr),
+                                                    C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), C.c_void_p(dist64_ptr),
+                                                    C.c_void_p(stream)))
 
     def range_search(self, queries, min_score, max_results=None):
         """Every row whose exact score is >= min_score (inclusive), per query ->

@@ -33,8 +33,11 @@
 //                     into candidate slots (forest_search.hip), the answer by launch_refine
 //   api_ivfflat.hip   IVF-Flat index (mi_ivfflat): centroids, list offsets and row lists over a gallery's raw rows; probe and assignment
 //                     by launch_refine over the centroid table, list build, scan with selection and merge in ivfflat.hip
+//   api_minkowski.hip exact L1 / L-infinity / Lp top-K over a gallery's raw rows (mi_knn_search_minkowski*): float64 scan of every
+//                     row on the vector pipe, selection and merge in minkowski.hip
 // Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index
-// family), graph_walk.h (the best-first walk of both graph indexes)
+// family), graph_walk.h (the best-first walk of both graph indexes), slab_select.h (sort, stream selection and emit on (key, id)
+// entries in LDS: ivfflat.hip, minkowski.hip)
 // The handles' grow-only device buffers own themselves: device_buf.h (DeviceBuf<T> and the per-handle DeviceBufSet; host code only);
 // graph_table.h (GraphTable: the neighbour table and entry rows both graph handles hold)
 #pragma once
@@ -354,6 +357,19 @@ struct mi_gallery {
     DeviceBuf<float> oval;
     DeviceBuf<double> oval64;
   } refine{scratch};
+  // Minkowski search (api_minkowski.hip)
+  struct MinkScratch {
+    explicit MinkScratch(DeviceBufSet& s) : qraw(s), qpad(s), val(s), part_key(s), part_id(s), bits(s), oidx(s), odist(s), odist64(s) {}
+    DeviceBuf<char> qraw;                // queries of a host call as given
+    DeviceBuf<float> qpad;               // [nq][dp] queries with 16-byte aligned rows
+    DeviceBuf<double> val;               // [queries of a chunk][n] f64 value of every row
+    DeviceBuf<uint64_t> part_key;        // [queries of a chunk][parts][k]
+    DeviceBuf<int64_t> part_id;
+    DeviceBuf<uint64_t> bits;            // device copy of a host bitmap
+    DeviceBuf<int64_t> oidx;             // [nq][k] results of a host call
+    DeviceBuf<float> odist;
+    DeviceBuf<double> odist64;
+  } mink{scratch};
   // row removal (api_remove.hip): one arena of exactly the bytes the largest call needed -- staging area of "remove_block_rows"
   // rows in the gallery's own layout, keep-list, bitmap, scan buffers
   DeviceBuf<char> rm_arena{scratch};

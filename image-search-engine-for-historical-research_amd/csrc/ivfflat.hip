@@ -29,6 +29,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "l2_wave.h"
+#include "slab_select.h"
 
 namespace mi {
 
@@ -36,41 +37,9 @@ constexpr int IVFF_THREADS = 512, IVFF_WAVES = IVFF_THREADS / 64;
 constexpr int IVFF_SLAB = IVFFLAT_SLAB_ROWS;                     // positions per scan workgroup
 constexpr int IVFF_WAVE_ROWS = IVFF_SLAB / IVFF_WAVES;           // consecutive positions one wave walks
 constexpr int IVFF_TILE = 256;                                   // rows per step of a build workgroup
-constexpr uint64_t IVFF_NOKEY = ~0ull;
+constexpr uint64_t IVFF_NOKEY = SLAB_NOKEY;
 
 static_assert(IVFF_WAVE_ROWS % 64 == 0, "a wave resolves 64 positions at a time");
-
-// (key, id) ascending, id -1 behind every row: the order of refine_sort_kernel
-__device__ __forceinline__ bool ivff_after(uint64_t ka, int64_t ia, uint64_t kb, int64_t ib) {
-  return ka != kb ? ka > kb : (uint64_t)ia > (uint64_t)ib;
-}
-
-// bitonic sort of N entries (a power of two) in LDS by NT threads; ends behind a barrier
-template <int N, int NT>
-__device__ __forceinline__ void ivff_sort(uint64_t* s_key, int64_t* s_id, int tid) {
-  for (uint32_t size = 2; size <= (uint32_t)N; size <<= 1)
-    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-      for (uint32_t p = tid; p < (uint32_t)N / 2; p += NT) {
-        const uint32_t lo = 2 * p - (p & (stride - 1)), hi = lo + stride;
-        const bool up = (lo & size) == 0;
-        const uint64_t ka = s_key[lo], kb = s_key[hi];
-        const int64_t ia = s_id[lo], ib = s_id[hi];
-        if (ivff_after(ka, ia, kb, ib) == up) {
-          s_key[lo] = kb;
-          s_key[hi] = ka;
-          s_id[lo] = ib;
-          s_id[hi] = ia;
-        }
-      }
-      __syncthreads();
-    }
-}
-
-// the value behind an l2_dist_key (NaN for the key of a NaN)
-__device__ __forceinline__ double ivff_key_value(uint64_t key) {
-  const uint64_t u = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
-  return __longlong_as_double((long long)u);
-}
 
 // ---- build
 __global__ __launch_bounds__(256) void ivff_take_ids_kernel(const int64_t* __restrict__ best, int64_t m, int32_t* __restrict__ out) {
@@ -282,7 +251,7 @@ __global__ __launch_bounds__(IVFF_THREADS) void ivff_scan_select_kernel(const fl
     s_id[slot] = (int64_t)row;
   }
   __syncthreads();
-  ivff_sort<IVFF_SLAB, IVFF_THREADS>(s_key, s_id, tid);
+  slab_sort<IVFF_SLAB, IVFF_THREADS>(s_key, s_id, tid);
   const int64_t o = ((int64_t)q * nslab + slab) * k;
   for (int32_t i = tid; i < k; i += IVFF_THREADS) {                   // k <= IVFF_SLAB
     part_key[o + i] = s_key[i];
@@ -329,29 +298,11 @@ __global__ __launch_bounds__(IVFF_THREADS) void ivff_merge_kernel(const uint64_t
   const int64_t count = (int64_t)slabs * k;
   const uint64_t* skey = part_key + (int64_t)q * nslab * k;
   const int64_t* sid = part_id + (int64_t)q * nslab * k;
-  for (int i = tid; i < HALF; i += IVFF_THREADS) {
-    s_key[i] = IVFF_NOKEY;
-    s_id[i] = -1;
-  }
-  for (int64_t c0 = 0; c0 < count; c0 += HALF) {
-    for (int i = tid; i < HALF; i += IVFF_THREADS) {
-      const bool in = c0 + i < count;
-      s_key[HALF + i] = in ? skey[c0 + i] : IVFF_NOKEY;
-      s_id[HALF + i] = in ? sid[c0 + i] : -1;
-    }
-    __syncthreads();
-    ivff_sort<2 * HALF, IVFF_THREADS>(s_key, s_id, tid);
-  }
-  __syncthreads();
-  const double padv = L2 ? (double)INFINITY : -(double)INFINITY;
-  for (int32_t i = tid; i < k; i += IVFF_THREADS) {
-    const int64_t id = s_id[i];
-    const double dec = ivff_key_value(s_key[i]);
-    const double v = id < 0 ? padv : (L2 ? dec : 0.0 - dec);
-    if (out_idx) out_idx[q * k + i] = id < 0 ? -1 : row_offset + id;
-    if (out_val64) out_val64[q * k + i] = v;
-    if (out_val) out_val[q * k + i] = (float)v;
-  }
+  slab_stream_best<HALF, IVFF_THREADS>(s_key, s_id, count, tid, [&](int64_t i, uint64_t& key, int64_t& id) {
+    key = skey[i];
+    id = sid[i];
+  });
+  slab_emit<L2, IVFF_THREADS>(s_key, s_id, k, q, row_offset, out_idx, out_val, out_val64, tid);
 }
 
 // ---- launchers

@@ -500,6 +500,33 @@ void launch_ivff_search(const float* gal_f32, const float* qry, int32_t dp, int3
                         int32_t k, int32_t nslab, int32_t nq, uint64_t* part_key, int64_t* part_id, uint32_t* pcnt, int64_t row_offset,
                         int64_t* out_idx, float* out_val, double* out_val64, int64_t* out_scanned, hipStream_t stream);
 
+// minkowski.hip -- exact Minkowski top-K over the stored f32 rows of a gallery (api_minkowski.hip).  The term of a
+// column with t = |q - g| in float64: t, max, t^2 (the bits of l2_direct_wave), sqrt(t), pow(t, p)
+constexpr int MINK_OP_L1 = 0, MINK_OP_LINF = 1, MINK_OP_SQ = 2, MINK_OP_SQRT = 3, MINK_OP_POW = 4;
+constexpr int MINK_MAX_K = 2048;
+constexpr int64_t MINK_SLAB_ROWS = 2048, MINK_MAX_PARTS = 64;
+// queries of a scan tile: as many of 8, 4, 2, 1 as fit into 160 KiB of LDS as float64 rows of round_up(d, 4); 0 = not even one
+static inline int mink_query_tile(int32_t d) {
+  const int64_t row = ((int64_t)d + 3) / 4 * 4 * 8;
+  for (int qt = 8; qt >= 1; qt >>= 1)
+    if (qt * row <= 160 * 1024) return qt;
+  return 0;
+}
+// rows per select workgroup: whole slabs of 2048, at most MINK_MAX_PARTS partial lists a query
+static inline int64_t mink_part_rows(int64_t n) {
+  const int64_t r = ((n + MINK_MAX_PARTS - 1) / MINK_MAX_PARTS + MINK_SLAB_ROWS - 1) / MINK_SLAB_ROWS * MINK_SLAB_ROWS;
+  return r < MINK_SLAB_ROWS ? MINK_SLAB_ROWS : r;
+}
+static inline int32_t mink_parts(int64_t n) {
+  const int64_t p = (n + mink_part_rows(n) - 1) / mink_part_rows(n);
+  return (int32_t)(p < 1 ? 1 : p);
+}
+// qry [nq][dp] with 16-byte aligned rows, nq <= 65535, 1 <= k <= MINK_MAX_K, mink_query_tile(d) >= 1; allow NULL or the bitmap over
+// local rows.  Scratch: val [nq][ld] (ld >= n), part_key / part_id [nq][mink_parts(n)][k].  Any of the three outputs may be NULL
+void launch_minkowski(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int64_t row_offset, int op, double p,
+                      const uint64_t* allow, int32_t k, int32_t nq, double* val, int64_t ld, uint64_t* part_key, int64_t* part_id,
+                      int64_t* out_idx, float* out_val, double* out_val64, hipStream_t stream);
+
 // pq_remove.hip -- in-place row removal of the PQ and the IVF-PQ index (api_pq.hip, api_ivfpq.hip).  keep [ceil(n / 64)]: the bitmap
 // of the rows that stay (bits at or beyond n clear); prefix [ceil(n / 64) + 1]: the exclusive count of keep bits per word.
 // Flat index, one chunk of source blocks [blk0, blk1): its survivors -> the staging area, whose block 0 stands for block dst_blk0

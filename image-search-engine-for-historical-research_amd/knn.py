@@ -17,6 +17,13 @@ IndexFlatL2.search -- through a squared-L2 gallery (Gallery.l2_from_host); ties 
 bit j & 7 of byte j >> 3), ascending -- the return of IndexBinaryFlat.search -- through a binary index (_lib.BinaryGallery);
 ties go to the lower id.  Removal, radius search, save / load and sharding are not built for binary indexes.
 
+    KNN(database[N,D], 'l1' | 'linf').search(queries[Q,D], k)    KNN(database[N,D], 'lp', p=0.5).search(queries[Q,D], k)
+        -> (distances float32 [Q,k] ascending, ids int64 [Q,k])
+
+`l1`, `linf` and `lp` are faiss.IndexFlat(D, METRIC_L1 | METRIC_Linf | METRIC_Lp) (metric_arg = p): sum |q - x|, max |q - x| and
+sum |q - x| ** p -- faiss's value, not raised to 1 / p -- of the rows as given, in float64 over a NORM_NONE gallery
+(Gallery.search_minkowski); ties go to the lower id.  remove_ids works; range_search is not built for them.
+
     ANN(database[N,D], 'euclidean', M=64, nbits=8, nlist=256, nprobe=64).search(queries[Q,D], k)
         -> (squared ADC distances float32 [Q,k] ascending, ids int64 [Q,k])
 
@@ -25,17 +32,20 @@ by_residual = true) on a residual _lib.IVFPQIndex.
 """
 import numpy as np
 
-from ._lib import BinaryGallery, Gallery, IVFPQIndex, IVF_MAX_LISTS, NORM_NONE, PQ_MAX_BOOKS
+from ._lib import BinaryGallery, Gallery, IVFPQIndex, IVF_MAX_LISTS, MINK_METRICS, NORM_NONE, PQ_MAX_BOOKS, minkowski_args
 
 
 class KNN:
     method = "cosine"
 
-    def __init__(self, database, method="cosine", device=0):
-        if method not in ("cosine", "euclidean", "hamming"):
-            raise NotImplementedError("method must be 'cosine' (IndexFlatIP), 'euclidean' (IndexFlatL2) or 'hamming' "
-                                      "(IndexBinaryFlat), got %r" % (method,))
-        self.method = method
+    def __init__(self, database, method="cosine", device=0, p=None):
+        if method not in ("cosine", "euclidean", "hamming") and method not in MINK_METRICS:
+            raise NotImplementedError("method must be 'cosine' (IndexFlatIP), 'euclidean' (IndexFlatL2), 'hamming' "
+                                      "(IndexBinaryFlat) or 'l1', 'linf', 'lp' (IndexFlat with a Minkowski metric), got %r"
+                                      % (method,))
+        self.method, self.p = method, p
+        if method in MINK_METRICS:
+            minkowski_args(method, p, 1)          # a bad p raises here, before a device is touched
         database = np.asarray(database)
         if method == "hamming":
             if database.dtype != np.uint8 or database.ndim != 2:
@@ -65,6 +75,9 @@ class KNN:
         if self.method == "euclidean":
             ids, dist, _, _, _ = self.gallery.search_l2(queries, int(k), allow)
             return dist, ids
+        if self.method in MINK_METRICS:           # -> (distances float32 [Q,k] ascending, ids int64 [Q,k]); short: -1 / +inf
+            ids, dist, _, _ = self.gallery.search_minkowski(queries, int(k), self.method, self.p, allow)
+            return dist, ids
         if allow is not None:
             ids, sims, _, _ = self.gallery.search_filtered(queries, int(k), allow)
             return sims, ids
@@ -84,7 +97,7 @@ class KNN:
         return lims, sims, ids
 
     def remove_ids(self, ids):
-        """faiss's IndexFlat.remove_ids, both float metrics: the rows leave the index, the others keep their order and are renumbered
+        """faiss's IndexFlat.remove_ids, every float metric: the rows leave the index, the others keep their order and are renumbered
         0 .. N' - 1.  ids: an array of row ids (duplicates are fine), a bool mask [N] or packed AllowBits words.  -> the number
         of rows removed."""
         if self.method == "hamming":

@@ -867,16 +867,55 @@ MATCHING_METHODS = {"HIP": matching_HIP, "L2": matching_L2_hip, "Greedyhash": ma
                     "ANNOY": matching_ANNOY_hip, "IVF": matching_IVF_hip}
 
 
-def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test):
+def _reference_unit_rows(a):
+    """x / ||x|| per row as the reference's matchers normalise (src/utils/nnsearch.py:715-720: np.linalg.norm in the array's own
+    dtype), as the float32 rows a gallery stores."""
+    a = np.asarray(a)
+    return np.ascontiguousarray(a / np.expand_dims(np.linalg.norm(a, axis=1), axis=1), dtype=np.float32)
+
+
+def _fractional_search(K, embedded_features_train, embedded_features_test, p):
+    """int64 [Q, K]: the K rows of smallest sum |q - x| ** p per query over unit rows and unit queries, ascending, ties to the lower
+    id (Gallery.search_minkowski, metric "lp").  The reference's fractional_distance is that sum ** (1 / p): the same order."""
+    train, test = _reference_unit_rows(embedded_features_train), _reference_unit_rows(embedded_features_test)
+    K = int(K)
+    if K > train.shape[0]:
+        raise RuntimeError("mi355_retrieval error 1: k > number of gallery rows")
+    g = _lib.Gallery.from_host(train, norm_mode=NORM_NONE)
+    try:
+        idx, _, _, _ = g.search_minkowski(test, K, "lp", p)
+    finally:
+        g.close()
+    return idx
+
+
+def matching_fractional_dis_hip(K, embedded_features_train, embedded_features_test, p=2):
     """Same signature and return shape as matching_fractional_dis (src/utils/nnsearch.py:709-731).  The reference calls
     its fractional distance with p = 2 (:721), which orders the gallery exactly like matching_L2, and slices the QUERY
     axis of the argsort by K before the gallery axis (:723-724): it returns the rankings of the first min(Q, K) queries,
-    int64 [min(Q, K), K].  Reproduced as is; the timer divides by all queries like the reference's (:730)."""
+    int64 [min(Q, K), K].  Reproduced as is; the timer divides by all queries like the reference's (:730).
+    p != 2: what the reference's function would return had it passed that p on to fractional_distance (whose own default is
+    0.5): rows and queries normalised as there, the exact Lp top-K of the HIP scan, the same slice."""
     t1 = time.time()
     test = np.asarray(embedded_features_test)
     num_test = test.shape[0]
-    idx, _ = matching_HIP(K, embedded_features_train, test[:int(K)])
+    if p == 2:
+        idx, _ = matching_HIP(K, embedded_features_train, test[:int(K)])
+    else:
+        idx = _fractional_search(K, embedded_features_train, test[:int(K)], p)
     return idx, (time.time() - t1) / num_test
+
+
+def matching_Lp_hip(K, embedded_features_train, embedded_features_test, p=0.5):
+    """(K, train, test) matcher by the reference's fractional_distance (src/utils/nnsearch.py:46-56, p = 0.5 by default) over unit
+    rows and unit queries: -> (idx int64 [Q, K], time_per_query), every query answered (no slice of the query axis)."""
+    t1 = time.time()
+    test = np.asarray(embedded_features_test)
+    idx = _fractional_search(K, embedded_features_train, test, p)
+    return idx, (time.time() - t1) / max(test.shape[0], 1)
+
+
+MATCHING_METHODS["Lp"] = matching_Lp_hip
 
 
 def ip_rank_hip(vecs, qvecs, dataset=None, ifgenerate=False, device=0, return_scores=False):

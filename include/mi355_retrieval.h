@@ -223,6 +223,43 @@ int mi_refine(mi_gallery* rows, const void* q, int64_t nq, int dtype, int64_t ro
 int mi_debug_l2_tail_device(mi_gallery* g, const float* q_dev, int64_t nq, const int64_t* ids_dev, int32_t ke, int32_t k,
                             int64_t* out_idx_dev, double* out_dist64_dev, void* stream);
 
+/* ---- exact Minkowski top-K on the raw rows: faiss IndexFlat with METRIC_L1, METRIC_Linf and METRIC_Lp, and the reference's
+ * fractional_distance (src/utils/nnsearch.py:46-56, p = 0.5 by default) behind matching_fractional_dis (:709-731).  DESIGN.md 5.19.
+ * `rows` is ONE shard on one device that holds its f32 rows, as for mi_refine; a row wider than 20480 columns is
+ * MI_ERR_UNSUPPORTED.  The value of a (query, row) pair is taken on the STORED f32 row g -- the row as given on MI_NORM_NONE and
+ * squared-L2 galleries, over the caller's d columns only; the normalised row under MI_NORM_L2 -- and the query rounded to f32 like
+ * every query batch and used as given.  With t_j = |(double)q_j - (double)g_j|:
+ *   MI_MINK_L1                sum_j t_j, float64 adds;
+ *   MI_MINK_LINF              max_j t_j (exact);
+ *   MI_MINK_LP, p == 1        as MI_MINK_L1, the same bits;
+ *   MI_MINK_LP, p == 2        sum_j t_j^2, float64 FMA: the arithmetic and the bits of mi_knn_search_l2;
+ *   MI_MINK_LP, p == 0.5      sum_j sqrt(t_j), float64 sqrt and adds;
+ *   MI_MINK_LP, other p > 0   sum_j pow(t_j, p), float64 pow and adds.
+ * The Lp value is faiss's: it is NOT raised to 1 / p.  The reference's fractional_distance is value ** (1 / p), a monotone map of
+ * it, so the order is the same up to ties which that last rounding creates.  Every sum runs in one fixed order, that of
+ * mi_knn_search_l2's direct form (lane l of 64 adds columns 4 l + 256 i + {0, 1, 2, 3} in ascending order, then an xor butterfly
+ * 32, 16, ... 1 over the lanes): the bits of a pair depend on nothing but the pair.  p <= 0, NaN or infinite is MI_ERR_INVALID
+ * (MI_MINK_LINF is the infinite case); p is ignored unless metric == MI_MINK_LP.
+ * Order (value asc, id asc); out_idx [nq][k] int64 (row_offset + local row), out_dist64 [nq][k] (may be NULL), out_dist [nq][k]
+ * f32 (may be NULL) = (float)out_dist64.  Fewer than k admitted rows: trailing ids -1, values +INFINITY.  1 <= k <= 2048.
+ * allow_bits NULL: every row; otherwise the bitmap of mi_knn_search_filtered over local rows.  The order among non-finite values
+ * (non-finite inputs) is unspecified.  Nothing is cached: a gallery that rows were appended to or removed from is searched as it
+ * then stands.  Host form: queries of any strides, q_dtype MI_F32 or MI_F64, as in mi_knn_search_l2; takes the handle's lock; synchronous; nq == 0
+ * is MI_OK and writes nothing. */
+#define MI_MINK_L1 1
+#define MI_MINK_LINF 2
+#define MI_MINK_LP 3
+int mi_knn_search_minkowski(mi_gallery* rows, const void* q, int64_t nq, int q_dtype, int64_t row_stride, int64_t col_stride,
+                            int metric, double p, int32_t k, const uint64_t* allow_bits, int allow_memspace,
+                            int64_t* out_idx, float* out_dist, double* out_dist64, double* out_seconds);
+/* Device form: q_dev [nq][d] packed f32, allow_bits_dev NULL or the bitmap in device memory; enqueued on `stream`, no
+ * synchronisation.  It stages the queries, the float64 value of every (query, row) pair of a chunk of queries and partial lists in
+ * buffers of the handle (grown when a larger call comes): calls on one handle must be serialised by the caller and enqueued on ONE
+ * stream, as for mi_knn_search_l2_device. */
+int mi_knn_search_minkowski_device(mi_gallery* rows, const float* q_dev, int64_t nq, int metric, double p, int32_t k,
+                                   const uint64_t* allow_bits_dev, int64_t* out_idx_dev, float* out_dist_dev,
+                                   double* out_dist64_dev, void* stream);
+
 /* ---- graph index: best-first search of a neighbour graph over the rows of a gallery, the role of the reference's HNSW matchers
  * (matching_HNSW and its kin, src/utils/nnsearch.py:59-538).  DESIGN.md 5.16.  What is approximate is WHICH rows the graph
  * reaches; everything else is an exact, deterministic function of graph, entry rows, stored rows and query.
