@@ -151,18 +151,18 @@ class Problem:
         x, xh = self.X.astype(np.float64), self.Xh.astype(np.float64)
         return _norm32(x).max(), _norm32(xh).max(), _norm32(xh - x).max()
 
-    def eps(self, form=0):
-        """float32 [patterns]: eps_q = gamma |q^||g^| + |q^||g^ - g| + |q^ - q||g|"""
-        g_f32, g_img, g_diff = self.norm_bounds()
+    def eps(self, form=0, bounds=None):
+        """float32 [patterns]: eps_q = gamma |q^||g^| + |q^||g^ - g| + |q^ - q||g|; bounds: other maxima than the gallery's own"""
+        g_f32, g_img, g_diff = self.norm_bounds() if bounds is None else (np.float32(v) for v in bounds)
         q = self.base_queries(form)
         qh = round16(q, self.image)
         q_img, q_diff = _norm32(qh), _norm32(qh.astype(np.float64) - q.astype(np.float64))
         gamma = np.float32(2.0) * np.float32(self.dp) * np.float32(5.9604645e-08)
         return gamma * q_img * g_img + q_img * g_diff + q_diff * g_f32
 
-    def margin(self, form=0):
+    def margin(self, form=0, bounds=None):
         """float32 [patterns]: 2 eps 1.001 + 1e-30"""
-        return np.float32(2.0) * self.eps(form) * np.float32(1.001) + np.float32(1e-30)
+        return np.float32(2.0) * self.eps(form, bounds) * np.float32(1.001) + np.float32(1e-30)
 
     # ---- top-K
     def _allowed(self, allow):

@@ -6,8 +6,9 @@ the lowest victim lies 0.95 ... 0.99 of the shipped margin below the K-th 16-bit
 that a filter applying 0.85 of the margin loses victims on exactly this data.  Every score is exact in every format and order, so
 ids are compared with ==, scores as bits, and the gallery must hold the rows it was given bit for bit.  The statistics show that
 the 16-bit path gave the answer: no overflowed batch, no speculative retry, and exactly the 2 K candidates per query the model
-counts (the f32 scorer would keep K).  Not covered: search_l2, whose hidden columns make the 16-bit score depend on the summation
-order ("What pins the margin")."""
+counts (the f32 scorer would keep K).  The two consumers this file leaves out have files of their own: the sharded protocol's
+worst-shard margin (tests/test_gpu_certificate_margin_sharded.py) and search_l2, whose hidden columns make the 16-bit score depend
+on the summation order, so that its model is banded (tests/test_gpu_certificate_margin_l2.py); DESIGN 3, "What pins the margin"."""
 import numpy as np
 import pytest
 
