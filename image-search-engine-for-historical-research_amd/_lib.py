@@ -120,6 +120,8 @@ SIGNATURES = {
     "mi_ivfflat_get_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi_ivfflat_get_centroids": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mi_ivfflat_destroy": (C.c_int, [C.c_void_p]),
+    "mi_ivfflat_sync": (C.c_int, [C.c_void_p, c_i64p]),
+    "mi_ivfflat_remove_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64p]),
     "mi_ivfflat_probe_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "mi_ivfflat_search_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -2466,8 +2468,11 @@ class IVFFlatIndex(_Handle):
     belongs to the list of its best centroid, a query evaluates the stored rows of the nprobe lists it probes.  Which rows are
     reached is approximate; the answer given centroids, lists, stored rows and query is exact: values are Gallery.refine's, the
     order is (value best first, id ascending).  The rows are not copied: the index costs 4 bytes per row plus the centroids.  The
-    gallery must outlive the index; after gallery.append* / gallery.remove probe and search raise (build a new index).  Nothing
-    routes to this index by default and its speed has not been measured: for large batches the exhaustive search stays the choice."""
+    gallery must outlive the index.  The index follows its gallery in place: after gallery.append* call sync(), and remove rows
+    through remove() of the index, which removes them from the gallery too; either leaves the lists and answers of a fresh
+    build(gallery, the same centroids), bit for bit.  Until sync() an appended-to gallery makes probe and search raise, and a
+    gallery.remove() made beside the index makes probe, search and sync() raise for good (build a new index).  Nothing routes to
+    this index by default and its speed has not been measured: for large batches the exhaustive search stays the choice."""
     _DESTROY = "mi_ivfflat_destroy"
     hbm_bytes = _hbm_bytes("mi_ivfflat_info", 3)
 
@@ -2600,6 +2605,31 @@ class IVFFlatIndex(_Handle):
         check(load().mi_ivfflat_search_device(self._h, C.c_void_p(q_ptr), int(nq), self._k(k), self._nprobe(nprobe), C.c_void_p(probes_ptr),
                                               C.c_void_p(allow_ptr), C.c_void_p(idx_ptr), C.c_void_p(val_ptr), C.c_void_p(val64_ptr),
                                               C.c_void_p(scanned_ptr), C.c_void_p(stream)))
+
+    def sync(self):
+        """mi_ivfflat_sync: takes in the rows appended to the gallery since the index was made or last updated -> their number.
+        Afterwards the index is the one build() makes on the gallery as it stands.  Raises RuntimeError after a gallery.remove()
+        made beside the index."""
+        added = C.c_int64()
+        with self.gallery._lock, self._lock:
+            check(load().mi_ivfflat_sync(self._h, C.byref(added)))
+            self.n += added.value
+        return added.value
+
+    def remove(self, rows):
+        """mi_ivfflat_remove_rows: removes rows from the gallery AND from the index -> their number.  `rows` is anything
+        Gallery.remove takes (a bool mask [n], an array of GLOBAL ids, packed AllowBits words); the survivors are renumbered as
+        Gallery.remove renumbers them, and gallery.n follows.  Afterwards the index is the one build() makes on the gallery as it
+        stands.  Raises ValueError, before the library is called, on a bad `rows`; RuntimeError when every row is named, when the
+        index is not in step with its gallery, and whenever Gallery.remove would."""
+        g = self.gallery
+        bits = allow_bitmap(rows, g.n, g.row_offset)
+        removed = C.c_int64()
+        with g._lock, self._lock:
+            check(load().mi_ivfflat_remove_rows(self._h, C.c_void_p(bits.ctypes.data), MI_HOST, C.byref(removed)))
+            g.n -= removed.value
+            self.n -= removed.value
+        return removed.value
 
     def list_sizes(self):
         """-> int64 [nlist]: the rows of every list."""

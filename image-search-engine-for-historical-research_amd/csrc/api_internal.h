@@ -377,6 +377,7 @@ struct mi_gallery {
   int32_t* dif_ids = nullptr;
   float* dif_vals = nullptr;
   int32_t dif_T = 0;
+  uint64_t removals = 0;              // calls that removed at least one row (api_remove.hip); mi_ivfflat records it, nothing public shows it
   std::mutex mu;
   std::atomic<int> online_users{0};   // mi_online handles built on this gallery: it cannot be destroyed under them
 };
@@ -480,6 +481,10 @@ MI_INTERNAL int gallery_alloc(mi_gallery* g);
 MI_INTERNAL int gallery_create_any(const void* data, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride,
                                    int memspace, int norm_mode, int metric, int device, int64_t row_offset, int64_t capacity,
                                    mi_gallery** out);
+// ---- api_remove.hip
+// mi_gallery_remove_rows behind its argument checks, its online-handle check and its lock, which the caller holds; out_removed (may
+// be NULL) is written only when rows left
+MI_INTERNAL int gallery_remove_rows_locked(mi_gallery* g, const uint64_t* remove_bits, int memspace, int64_t* out_removed);
 // ---- api_filter.hip
 MI_INTERNAL void filter_release_sub(mi_gallery* g);     // frees the compacted sub-gallery (option "filter_cache" 0)
 MI_INTERNAL void filter_invalidate(mi_gallery* g);      // rows or image type of the parent changed: the sub-gallery is stale

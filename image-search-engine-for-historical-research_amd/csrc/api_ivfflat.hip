@@ -5,6 +5,9 @@
 // caller's stream); the binding stages host queries.  Probe and assignment are launch_refine
 // over the centroid table (candidates 0 .. nlist - 1, one row of them shared by every query: cand_stride 0), so their values, ties and
 // order are mi_refine's; the list build, the prefix, the scan with its selection and the merge are ivfflat.hip's.
+// The index follows its gallery in place: mi_ivfflat_sync assigns the appended rows and splices them behind the rows of their lists,
+// mi_ivfflat_remove_rows removes rows from the gallery (api_remove.hip's own code) and compacts the lists by the same bitmap.  Either
+// writes new tables, swaps them in on success and leaves the bytes mi_ivfflat_build writes on the gallery as it then stands.
 #include "api_internal.h"
 
 // probe values, probes, prefixes, partial lists and counts of one chunk of queries: a batch that needs more goes in chunks of queries
@@ -14,7 +17,8 @@ constexpr size_t IVFF_ASSIGN_BYTES = (size_t)64 << 20;
 
 struct mi_ivfflat {
   mi_gallery* rows = nullptr;
-  int64_t n = 0;                       // rows of the gallery when the index was made; probe and search refuse any other number
+  int64_t n = 0;                       // rows of the gallery the lists cover; probe and search refuse any other number
+  uint64_t removals = 0;               // the gallery's count of removals the lists cover: one made outside the index shows here
   int32_t d = 0, nlist = 0;
   std::vector<int64_t> off_host;       // list_off on the host
   std::vector<int64_t> topsum;         // [nlist + 1]: topsum[p] = rows of the p longest lists, what p probes can reach at the most
@@ -53,9 +57,50 @@ static int ivff_search_check(const void* f, int64_t nq, int32_t k, int32_t nprob
   return MI_OK;
 }
 
-static int ivff_fresh(const mi_ivfflat* f) {
-  REQUIRE(f->rows->n == f->n, "the gallery has been appended to or had rows removed since the index was made: build a new index");
+// a removal the index was not told of renumbers the rows under its lists, and an append after it can put n back where it was
+static int ivff_no_outside_removal(const mi_ivfflat* f) {
+  REQUIRE(f->rows->removals == f->removals,
+          "the gallery has been appended to or had rows removed since the index was made: a removal was made outside the index "
+          "(mi_ivfflat_remove_rows keeps the two in step): build a new index");
   return MI_OK;
+}
+
+static int ivff_fresh(const mi_ivfflat* f) {
+  int rc = ivff_no_outside_removal(f);
+  if (rc != MI_OK) return rc;
+  REQUIRE(f->rows->n == f->n,
+          "the gallery has been appended to or had rows removed since the index was made: mi_ivfflat_sync takes the appended rows in, "
+          "or build a new index");
+  return MI_OK;
+}
+
+// rows per launch_refine call of an assignment of `rows` stored rows
+static int64_t ivff_assign_chunk(int64_t rows, int32_t nlist) {
+  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(rows, 65535), (int64_t)(IVFF_ASSIGN_BYTES / 8) / nlist));
+}
+
+// list ids of the stored rows [r0, r1) of the gallery -> lid[0 .. r1 - r0): the probe-1 list of each, launch_refine with k = 1 over
+// the centroid table.  The stored rows are the queries: rows of stride dp, d columns used.  val [chunk][nlist], best [chunk]
+static void ivff_assign(const mi_ivfflat* f, int64_t r0, int64_t r1, int64_t chunk, double* val, int64_t* best, int32_t* lid,
+                        hipStream_t s) {
+  const mi_gallery* g = f->rows;
+  const int32_t dp = g->dp, nlist = f->nlist;
+  const int l2 = g->metric == MI_METRIC_L2 ? 1 : 0;
+  for (int64_t r = r0; r < r1; r += chunk) {
+    const int64_t b = std::min<int64_t>(chunk, r1 - r);
+    launch_refine(f->cent, g->gal_f32 + (size_t)r * dp, dp, f->d, nlist, 0, l2, f->iota, nlist, 0, 1, b, val, best, nullptr, nullptr, s);
+    launch_ivff_take_ids(best, b, lid + (r - r0), s);
+  }
+}
+
+// off_host -> topsum
+static void ivff_topsum(mi_ivfflat* f) {
+  const int32_t nlist = f->nlist;
+  std::vector<int64_t> sz((size_t)nlist);
+  for (int32_t l = 0; l < nlist; ++l) sz[l] = f->off_host[l + 1] - f->off_host[l];
+  std::sort(sz.begin(), sz.end(), [](int64_t a, int64_t b) { return a > b; });
+  f->topsum.assign((size_t)nlist + 1, 0);
+  for (int32_t l = 0; l < nlist; ++l) f->topsum[l + 1] = f->topsum[l] + sz[l];
 }
 
 static int ivff_nprobe(const mi_ivfflat* f, int32_t nprobe) {
@@ -78,9 +123,9 @@ static int ivff_make(mi_gallery* g, const float* centroids, int32_t nlist, const
   int rc;
   if ((rc = join_tails(g, s)) != MI_OK) return rc;
   mi_ivfflat* f = new mi_ivfflat();
-  f->rows = g, f->n = n, f->d = d, f->nlist = nlist;
+  f->rows = g, f->n = n, f->removals = g->removals, f->d = d, f->nlist = nlist;
   const int64_t brows = ivff_block_rows(n), nb = (n + brows - 1) / brows;
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n, 65535), (int64_t)(IVFF_ASSIGN_BYTES / 8) / nlist));
+  const int64_t chunk = ivff_assign_chunk(n, nlist);
   DeviceBuf<int32_t> lid;                        // (these free themselves on return; every path out of here has synchronised `s`)
   DeviceBuf<uint32_t> hist, sizes;
   DeviceBuf<double> val;
@@ -116,25 +161,14 @@ static int ivff_make(mi_gallery* g, const float* centroids, int32_t nlist, const
     if ((rc = check_flag(f->flag, s, &raised)) != MI_OK) return bail(rc);
     if (raised) return bail(fail(MI_ERR_INVALID, "list ids must lie in [0, nlist)"));
   }
-  if (!ids) {
-    const int l2 = g->metric == MI_METRIC_L2 ? 1 : 0;
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {            // the stored rows are the queries: rows of stride dp, d columns used
-      const int64_t b = std::min<int64_t>(chunk, n - r0);
-      launch_refine(f->cent, g->gal_f32 + (size_t)r0 * dp, dp, d, nlist, 0, l2, f->iota, nlist, 0, 1, b, val, best, nullptr, nullptr, s);
-      launch_ivff_take_ids(best, b, lid + r0, s);
-    }
-  }
+  if (!ids) ivff_assign(f, 0, n, chunk, val, best, lid, s);
   launch_ivff_lists(lids, n, nlist, hist, sizes, f->list_off, f->list_rows, s);
   f->off_host.resize((size_t)nlist + 1);
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(f->off_host.data(), f->list_off, ((size_t)nlist + 1) * 8, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return bail(fail(MI_ERR_HIP, std::string("IVF-Flat build: ") + hipGetErrorString(e)));
-  std::vector<int64_t> sz((size_t)nlist);
-  for (int32_t l = 0; l < nlist; ++l) sz[l] = f->off_host[l + 1] - f->off_host[l];
-  std::sort(sz.begin(), sz.end(), [](int64_t a, int64_t b) { return a > b; });
-  f->topsum.assign((size_t)nlist + 1, 0);
-  for (int32_t l = 0; l < nlist; ++l) f->topsum[l + 1] = f->topsum[l] + sz[l];
+  ivff_topsum(f);
   *out = f;
   return MI_OK;
 }
@@ -239,6 +273,115 @@ int mi_ivfflat_destroy(mi_ivfflat* f) {
   (void)hipSetDevice(f->rows->device);
   (void)hipDeviceSynchronize();
   delete f;
+  return MI_OK;
+}
+
+// The new tables take the place of the old ones (new_off has been read into off_host and `s` synchronised): the memory moves, the
+// old blocks are freed, the host mirrors follow
+static void ivff_swap_in(mi_ivfflat* f, int64_t n, std::vector<int64_t>& off_host, DeviceBuf<int64_t>& new_off, DeviceBuf<int32_t>& new_rows) {
+  f->list_off = std::move(new_off);
+  f->list_rows = std::move(new_rows);
+  f->off_host.swap(off_host);
+  f->n = n;
+  ivff_topsum(f);
+}
+
+int mi_ivfflat_sync(mi_ivfflat* f, int64_t* out_added) {
+  REQUIRE(f, "null handle");
+  if (out_added) *out_added = 0;
+  mi_gallery* g = f->rows;
+  std::lock_guard<std::mutex> glock(g->mu);
+  std::lock_guard<std::mutex> lock(f->mu);
+  int rc = ivff_no_outside_removal(f);
+  if (rc != MI_OK) return rc;
+  const int64_t n0 = f->n, n1 = g->n, m = n1 - n0;
+  REQUIRE(m >= 0, "the gallery holds fewer rows than the index: build a new index");
+  if (m == 0) return MI_OK;
+  REQUIRE(n1 <= 0x7fffffff, "an IVF-Flat index takes at most 2^31 - 1 rows");
+  HIPC(hipSetDevice(g->device));
+  hipStream_t s = g->stream;
+  if ((rc = join_tails(g, s)) != MI_OK) return rc;
+  const int32_t nlist = f->nlist;
+  const int64_t brows = ivff_block_rows(m), nb = (m + brows - 1) / brows;
+  const int64_t chunk = ivff_assign_chunk(m, nlist);
+  // the lists of the appended rows alone, numbered from 0, then both spliced into tables of their own: until the swap the handle
+  // holds what it held (these free themselves on return; every path out of here has synchronised `s`)
+  DeviceBuf<int32_t> lid, tail_rows, new_rows;
+  DeviceBuf<uint32_t> hist, sizes;
+  DeviceBuf<double> val;
+  DeviceBuf<int64_t> best, tail_off, new_off;
+  if ((rc = lid.grow_exact((size_t)m)) != MI_OK || (rc = tail_rows.grow_exact((size_t)m)) != MI_OK ||
+      (rc = new_rows.grow_exact((size_t)n1)) != MI_OK || (rc = hist.grow_exact((size_t)nlist * nb)) != MI_OK ||
+      (rc = sizes.grow_exact((size_t)nlist)) != MI_OK || (rc = val.grow_exact((size_t)chunk * nlist)) != MI_OK ||
+      (rc = best.grow_exact((size_t)chunk)) != MI_OK || (rc = tail_off.grow_exact((size_t)nlist + 1)) != MI_OK ||
+      (rc = new_off.grow_exact((size_t)nlist + 1)) != MI_OK)
+    return rc;
+  ivff_assign(f, n0, n1, chunk, val, best, lid, s);
+  launch_ivff_lists(lid, m, nlist, hist, sizes, tail_off, tail_rows, s);
+  launch_ivff_splice(f->list_off, f->list_rows, tail_off, tail_rows, nlist, n0, m, new_off, new_rows, s);
+  std::vector<int64_t> off_host((size_t)nlist + 1);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(off_host.data(), new_off, ((size_t)nlist + 1) * 8, hipMemcpyDeviceToHost, s);
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(MI_ERR_HIP, std::string("IVF-Flat sync: ") + hipGetErrorString(e));
+  ivff_swap_in(f, n1, off_host, new_off, new_rows);
+  if (out_added) *out_added = m;
+  return MI_OK;
+}
+
+int mi_ivfflat_remove_rows(mi_ivfflat* f, const uint64_t* remove_bits, int memspace, int64_t* out_removed) {
+  REQUIRE(f, "null handle");
+  REQUIRE(remove_bits, "null pointer: remove_bits");
+  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
+  if (out_removed) *out_removed = 0;
+  mi_gallery* g = f->rows;
+  REQUIRE(g->online_users.load() == 0, "the gallery is in use by an online handle: mi_online_destroy comes first");
+  std::lock_guard<std::mutex> glock(g->mu);
+  std::lock_guard<std::mutex> lock(f->mu);
+  int rc = ivff_fresh(f);
+  if (rc != MI_OK) return rc;
+  const int64_t n = f->n;
+  HIPC(hipSetDevice(g->device));
+  RemovePlan plan;                                          // the bitmap of the rows that stay and its rank table, on the host
+  if ((rc = remove_plan(remove_bits, memspace, n, &plan)) != MI_OK) return rc;
+  if (plan.removed == 0) return MI_OK;                      // nothing changes
+  REQUIRE(plan.removed < n, "the bitmap names every row: an index needs at least one row");
+  hipStream_t s = g->stream;
+  if ((rc = join_tails(g, s)) != MI_OK) return rc;
+  const int32_t nlist = f->nlist;
+  const int64_t m = n - plan.removed, nwords = (n + 63) / 64;
+  const int64_t brows = ivff_block_rows(n), nb = (n + brows - 1) / brows;
+  // First the lists of the survivors, into tables of their own; then the gallery's removal; then the swap.  A removal the gallery
+  // refuses or fails leaves the handle with what it held
+  DeviceBuf<uint64_t> keep;
+  DeviceBuf<uint32_t> rank, tpre, bcnt, total;
+  DeviceBuf<int64_t> new_off;
+  DeviceBuf<int32_t> new_rows;
+  if ((rc = keep.grow_exact((size_t)nwords)) != MI_OK || (rc = rank.grow_exact((size_t)nwords + 1)) != MI_OK ||
+      (rc = tpre.grow_exact((size_t)((n + 255) / 256))) != MI_OK || (rc = bcnt.grow_exact((size_t)nb)) != MI_OK ||
+      (rc = total.grow_exact(64)) != MI_OK || (rc = new_off.grow_exact((size_t)nlist + 1)) != MI_OK ||
+      (rc = new_rows.grow_exact((size_t)m)) != MI_OK)
+    return rc;
+  std::vector<int64_t> off_host((size_t)nlist + 1);
+  hipError_t e = hipMemcpyAsync(keep, plan.keep.data(), (size_t)nwords * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(rank, plan.prefix.data(), ((size_t)nwords + 1) * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    launch_ivff_compact(f->list_off, f->list_rows, n, nlist, keep, rank, tpre, bcnt, total, new_off, new_rows, s);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(off_host.data(), new_off, ((size_t)nlist + 1) * 8, hipMemcpyDeviceToHost, s);
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(MI_ERR_HIP, std::string("IVF-Flat remove: ") + hipGetErrorString(e));
+  if (off_host[(size_t)nlist] != m) return fail(MI_ERR_HIP, "IVF-Flat remove: the lists do not hold every row of the gallery");
+  // the caller's bitmap has been read once: the gallery removes by the same bits (those at or beyond n are ignored there)
+  for (uint64_t& w : plan.keep) w = ~w;
+  int64_t removed = 0;
+  if ((rc = gallery_remove_rows_locked(g, plan.keep.data(), MI_HOST, &removed)) != MI_OK) return rc;
+  ivff_swap_in(f, m, off_host, new_off, new_rows);
+  f->removals = g->removals;
+  if (out_removed) *out_removed = removed;
   return MI_OK;
 }
 

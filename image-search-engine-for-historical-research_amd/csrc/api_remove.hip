@@ -13,16 +13,9 @@ static void diffusion_state_free(mi_gallery* g) {
   g->dif_ids = nullptr, g->dif_vals = nullptr, g->dif_T = 0;
 }
 
-extern "C" {
-
-int mi_gallery_remove_rows(mi_gallery* g, const uint64_t* remove_bits, int memspace, int64_t* out_removed) {
-  REQUIRE(g, "null handle");
-  REQUIRE(remove_bits, "null pointer: remove_bits");
-  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
-  if (out_removed) *out_removed = 0;
-  // the worker thread of an online handle searches this gallery between two requests, and its answers are ids
-  REQUIRE(g->online_users.load() == 0, "the gallery is in use by an online handle: mi_online_destroy comes first");
-  std::lock_guard<std::mutex> lock(g->mu);
+// The removal itself, with the gallery's lock held by the caller (mi_gallery_remove_rows; mi_ivfflat_remove_rows, which compacts its
+// lists by the same bitmap under the same lock)
+int gallery_remove_rows_locked(mi_gallery* g, const uint64_t* remove_bits, int memspace, int64_t* out_removed) {
   const int64_t n = g->n;
   if (n == 0) return MI_OK;
   HIPC(hipSetDevice(g->device));
@@ -123,8 +116,22 @@ int mi_gallery_remove_rows(mi_gallery* g, const uint64_t* remove_bits, int memsp
   g->samp_for_n = -1;            // the threshold samples are keyed by n in the same way
   g->samp_f32_for_n = -1;
   diffusion_state_free(g);       // the offline matrix holds ids of the old numbering
+  ++g->removals;                 // an index over the raw rows that was not told of this removal sees it, whatever n becomes
   if (out_removed) *out_removed = removed;
   return MI_OK;
+}
+
+extern "C" {
+
+int mi_gallery_remove_rows(mi_gallery* g, const uint64_t* remove_bits, int memspace, int64_t* out_removed) {
+  REQUIRE(g, "null handle");
+  REQUIRE(remove_bits, "null pointer: remove_bits");
+  REQUIRE(memspace == MI_HOST || memspace == MI_DEVICE, "memspace must be MI_HOST or MI_DEVICE");
+  if (out_removed) *out_removed = 0;
+  // the worker thread of an online handle searches this gallery between two requests, and its answers are ids
+  REQUIRE(g->online_users.load() == 0, "the gallery is in use by an online handle: mi_online_destroy comes first");
+  std::lock_guard<std::mutex> lock(g->mu);
+  return gallery_remove_rows_locked(g, remove_bits, memspace, out_removed);
 }
 
 }  // extern "C"

@@ -11,8 +11,17 @@
 //   ivff_scan_lists_kernel  one workgroup: list_off int64 [nlist + 1] from the sizes
 //   ivff_scatter_kernel     workgroup = block, tiles of 256 rows in ascending order: slot = list_off[l] + hist[l][block] + rows of
 //                           list l earlier in the block (a running count per list plus the rank inside the tile)
+// Update in place (into fresh tables, which the host swaps in; the bytes are those of a build on the gallery as it then stands):
+//   ivff_splice_off_kernel  mi_ivfflat_sync: list_off of the old lists + list_off of the lists built from the appended rows alone
+//   ivff_splice_kernel      thread = position of the new list_rows (binary search in the new list_off): the old run of its list,
+//                           then the tail's run with the old n added
+//   ivff_live_kernel        mi_ivfflat_remove_rows: workgroup = block of positions of list_rows, tiles of 256 in ascending order:
+//                           survivors (ballots over the keep bitmap) before every tile of the block, and of the block
+//   ivff_compact_kernel     the same walk: slot = survivors before the position (block prefix + running count + ballot prefix),
+//                           written there the survivor's new number (rank table of the bitmap + popcount below its bit)
+//   ivff_live_off_kernel    wave = entry of list_off: the survivors at positions below it
 // Search:
-//   ivff_prefix_kernel      workgroup = query: normalises a probe row (entries outside [0, nlist) and repeats of an earlier entry
+//   ivff_prefix_kernel     workgroup = query: normalises a probe row (entries outside [0, nlist) and repeats of an earlier entry
 //                           become -1) and writes the prefix of list sizes over it: the query's virtual sequence of candidates
 //   ivff_scan_select_kernel the hot path.  Grid = (slab of IVFF_SLAB positions of that sequence, query), 512 threads: a wave resolves
 //                           64 positions at a time (lane = position: binary search in the prefix, the row from list_rows, the allow
@@ -150,6 +159,113 @@ __global__ __launch_bounds__(IVFF_TILE) void ivff_scatter_kernel(const int32_t* 
     __syncthreads();
     if (l >= 0 && before == 0) cnt[l] += all;                     // one thread per list of the tile
   }
+}
+
+// ---- update in place: splice (mi_ivfflat_sync)
+// new_off[l] = old_off[l] + tail_off[l], l in [0, nlist]
+__global__ __launch_bounds__(256) void ivff_splice_off_kernel(const int64_t* __restrict__ old_off, const int64_t* __restrict__ tail_off,
+                                                             int32_t nlist, int64_t* __restrict__ new_off) {
+  const int32_t l = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+  if (l <= nlist) new_off[l] = old_off[l] + tail_off[l];
+}
+
+// thread = position p of the new list_rows [n_new]: its list is the last l with new_off[l] <= p (empty lists have empty ranges), its
+// entry the old run of that list followed by the tail's run with n_old added.  A list may hold anything from no row to every row:
+// the work is dealt out by position, not by list
+__global__ __launch_bounds__(256) void ivff_splice_kernel(const int64_t* __restrict__ old_off, const int32_t* __restrict__ old_rows,
+                                                         const int64_t* __restrict__ tail_off, const int32_t* __restrict__ tail_rows,
+                                                         const int64_t* __restrict__ new_off, int32_t nlist, int64_t n_old, int64_t n_new,
+                                                         int32_t* __restrict__ out) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n_new) return;
+  int32_t lo = 0, hi = nlist - 1;
+  while (lo < hi) {
+    const int32_t mid = (lo + hi + 1) >> 1;
+    if (new_off[mid] <= p) lo = mid;
+    else hi = mid - 1;
+  }
+  const int64_t j = p - new_off[lo], a = old_off[lo], old_size = old_off[lo + 1] - a;
+  out[p] = j < old_size ? old_rows[a + j] : (int32_t)(n_old + tail_rows[tail_off[lo] + (j - old_size)]);
+}
+
+// ---- update in place: compaction (mi_ivfflat_remove_rows).  keep [ceil(n / 64)]: the rows that stay; rank [ceil(n / 64) + 1]: the
+// exclusive count of keep bits per word.  The lists lie one behind the other in list_rows and the renumbering is monotone, so the new
+// list_rows is the old one with the entries of removed rows taken out and the others renumbered, in place order: ONE ordered
+// compaction over the positions, and new list_off[l] = the survivors at positions below old list_off[l]
+__device__ __forceinline__ bool ivff_stays(const uint64_t* __restrict__ keep, uint32_t row) {
+  return (keep[row >> 6] >> (row & 63u)) & 1ull;
+}
+
+// workgroup = block of brows consecutive positions (brows a multiple of IVFF_TILE), tiles in ascending order: tpre[tile] = survivors
+// of the block before the tile, bcnt[block] = survivors of the block
+__global__ __launch_bounds__(IVFF_TILE) void ivff_live_kernel(const int32_t* __restrict__ list_rows, int64_t n, int64_t brows,
+                                                             const uint64_t* __restrict__ keep, uint32_t* __restrict__ tpre,
+                                                             uint32_t* __restrict__ bcnt) {
+  __shared__ uint32_t s_w[IVFF_TILE / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x, r0 = b * brows, r1 = min(n, r0 + brows);
+  uint32_t run = 0;
+  for (int64_t t0 = r0; t0 < r1; t0 += IVFF_TILE) {                 // (uniform over the workgroup)
+    const int64_t p = t0 + tid;
+    const bool live = p < r1 && ivff_stays(keep, (uint32_t)list_rows[p]);
+    const uint64_t mask = __ballot(live);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (tid == 0) tpre[t0 / IVFF_TILE] = run;
+    for (int w = 0; w < IVFF_TILE / 64; ++w) run += s_w[w];
+    __syncthreads();                                                // the counts are read before the next tile writes them
+  }
+  if (tid == 0) bcnt[b] = run;
+}
+
+// the same walk; a survivor's slot = boff[block] + survivors of the block in earlier tiles + in earlier waves of the tile + in lower
+// lanes of its wave (ballot), and what is written there is its new number rank[w] + popcount(keep[w] below its bit)
+__global__ __launch_bounds__(IVFF_TILE) void ivff_compact_kernel(const int32_t* __restrict__ list_rows, int64_t n, int64_t brows,
+                                                                const uint64_t* __restrict__ keep, const uint32_t* __restrict__ rank,
+                                                                const uint32_t* __restrict__ boff, int32_t* __restrict__ out) {
+  __shared__ uint32_t s_w[IVFF_TILE / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t b = blockIdx.x, r0 = b * brows, r1 = min(n, r0 + brows);
+  int64_t run = boff[b];
+  for (int64_t t0 = r0; t0 < r1; t0 += IVFF_TILE) {
+    const int64_t p = t0 + tid;
+    const uint32_t row = p < r1 ? (uint32_t)list_rows[p] : 0u;
+    const bool live = p < r1 && ivff_stays(keep, row);
+    const uint64_t mask = __ballot(live);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t before = (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)), all = 0;
+    for (int w = 0; w < IVFF_TILE / 64; ++w) {
+      before += w < wave ? s_w[w] : 0u;
+      all += s_w[w];
+    }
+    if (live) out[run + before] = (int32_t)(rank[row >> 6] + (uint32_t)__popcll(keep[row >> 6] & ((1ull << (row & 63u)) - 1ull)));
+    run += all;
+    __syncthreads();
+  }
+}
+
+// wave = entry l of list_off, l in [0, nlist]: new_off[l] = survivors at positions below p = old_off[l] = boff[block of p] +
+// tpre[tile of p] + the survivors among the at most IVFF_TILE - 1 positions of that tile below p; p == n: all of them.  No barrier
+__global__ __launch_bounds__(256) void ivff_live_off_kernel(const int64_t* __restrict__ old_off, const int32_t* __restrict__ list_rows,
+                                                           int64_t n, int64_t brows, int32_t nlist, const uint64_t* __restrict__ keep,
+                                                           const uint32_t* __restrict__ boff, const uint32_t* __restrict__ tpre,
+                                                           const uint32_t* __restrict__ total, int64_t* __restrict__ new_off) {
+  const int lane = threadIdx.x & 63;
+  const int32_t l = (int32_t)(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (l > nlist) return;                                            // (wave-uniform)
+  const int64_t p = old_off[l];
+  if (p >= n) {
+    if (lane == 0) new_off[l] = (int64_t)total[0];
+    return;
+  }
+  const int64_t t0 = p / IVFF_TILE * IVFF_TILE;
+  uint32_t c = 0;
+  for (int j = 0; j < IVFF_TILE / 64; ++j) {
+    const int64_t pos = t0 + j * 64 + lane;
+    c += (uint32_t)__popcll(__ballot(pos < p && ivff_stays(keep, (uint32_t)list_rows[pos < p ? pos : t0])));
+  }
+  if (lane == 0) new_off[l] = (int64_t)boff[t0 / brows] + tpre[t0 / IVFF_TILE] + c;
 }
 
 // ---- probes in [nq][nprobe] (the library's int64 answers or the caller's int32) -> norm [nq][nprobe] (-1 = no list), pref
@@ -328,6 +444,28 @@ void launch_ivff_lists(const int32_t* ids, int64_t n, int32_t nlist, uint32_t* h
   ivff_scan_lists_kernel<<<dim3(1), 1024, 0, stream>>>(sizes, nlist, list_off);
   ivff_scatter_kernel<<<dim3((unsigned)nb), IVFF_TILE, (size_t)nlist * 4 + IVFF_TILE * 4, stream>>>(ids, n, brows, nlist, nb, hist, list_off,
                                                                                                   list_rows);
+}
+
+void launch_ivff_splice(const int64_t* old_off, const int32_t* old_rows, const int64_t* tail_off, const int32_t* tail_rows, int32_t nlist,
+                        int64_t n_old, int64_t m, int64_t* new_off, int32_t* new_rows, hipStream_t stream) {
+  if (m <= 0) return;
+  const int64_t n_new = n_old + m;
+  ivff_splice_off_kernel<<<dim3((unsigned)(nlist / 256 + 1)), 256, 0, stream>>>(old_off, tail_off, nlist, new_off);
+  ivff_splice_kernel<<<dim3((unsigned)((n_new + 255) / 256)), 256, 0, stream>>>(old_off, old_rows, tail_off, tail_rows, new_off, nlist, n_old,
+                                                                               n_new, new_rows);
+}
+
+void launch_ivff_compact(const int64_t* old_off, const int32_t* old_rows, int64_t n, int32_t nlist, const uint64_t* keep,
+                         const uint32_t* rank, uint32_t* tpre, uint32_t* bcnt, uint32_t* total, int64_t* new_off, int32_t* new_rows,
+                         hipStream_t stream) {
+  if (n <= 0) return;
+  const int64_t brows = ivff_block_rows(n);
+  const int32_t nb = (int32_t)((n + brows - 1) / brows);
+  ivff_live_kernel<<<dim3((unsigned)nb), IVFF_TILE, 0, stream>>>(old_rows, n, brows, keep, tpre, bcnt);
+  ivff_scan_blocks_kernel<<<dim3(1), 256, 0, stream>>>(bcnt, nb, total);           // bcnt -> its exclusive prefix, total[0] = n'
+  ivff_compact_kernel<<<dim3((unsigned)nb), IVFF_TILE, 0, stream>>>(old_rows, n, brows, keep, rank, bcnt, new_rows);
+  ivff_live_off_kernel<<<dim3((unsigned)(nlist / 4 + 1)), 256, 0, stream>>>(old_off, old_rows, n, brows, nlist, keep, bcnt, tpre, total,
+                                                                           new_off);
 }
 
 void launch_ivff_prefix(const void* in, int in_is_i64, int64_t nq, int32_t nlist, int32_t nprobe, const int64_t* list_off, int32_t* norm,

@@ -489,6 +489,16 @@ void launch_ivff_check(const int32_t* ids, int32_t nlist, int64_t m, uint32_t* f
 // ids [n] int32, every one in [0, nlist) -> list_off, list_rows.  Scratch: hist [nlist][ceil(n / ivff_block_rows(n))], sizes [nlist]
 void launch_ivff_lists(const int32_t* ids, int64_t n, int32_t nlist, uint32_t* hist, uint32_t* sizes, int64_t* list_off, int32_t* list_rows,
                        hipStream_t stream);
+// mi_ivfflat_sync: the lists of n_old rows and the lists of the m rows behind them (tail_rows numbered from 0) -> the lists of
+// n_old + m rows, new_off [nlist + 1] and new_rows [n_old + m], neither of them an input
+void launch_ivff_splice(const int64_t* old_off, const int32_t* old_rows, const int64_t* tail_off, const int32_t* tail_rows, int32_t nlist,
+                        int64_t n_old, int64_t m, int64_t* new_off, int32_t* new_rows, hipStream_t stream);
+// mi_ivfflat_remove_rows: keep [ceil(n / 64)] the rows that stay (bits at or beyond n clear, at least one set), rank [ceil(n / 64) + 1]
+// the exclusive count of its bits per word -> the lists of the survivors in their new numbering, new_off [nlist + 1] and new_rows
+// [n'], neither of them an input.  Scratch: tpre [ceil(n / 256)], bcnt [ceil(n / ivff_block_rows(n))], total [1]
+void launch_ivff_compact(const int64_t* old_off, const int32_t* old_rows, int64_t n, int32_t nlist, const uint64_t* keep,
+                         const uint32_t* rank, uint32_t* tpre, uint32_t* bcnt, uint32_t* total, int64_t* new_off, int32_t* new_rows,
+                         hipStream_t stream);
 // probes [nq][nprobe], int64 (in_is_i64) or int32: entries outside [0, nlist) and repeats of an earlier entry -> -1 in norm, then
 // the prefix of list sizes pref [nq][nprobe + 1]
 void launch_ivff_prefix(const void* in, int in_is_i64, int64_t nq, int32_t nlist, int32_t nprobe, const int64_t* list_off, int32_t* norm,

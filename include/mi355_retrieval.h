@@ -403,9 +403,35 @@ int mi_forest_search_device(mi_forest* f, const float* q_dev, int64_t nq, int32_
  * Consequences: with nprobe == nlist and no bitmap an L2 gallery gives mi_knn_search_l2's ids and dist64 bit for bit; any probe set
  * gives the answer of mi_knn_search_l2 with the allow bitmap of those lists.  The answer does not depend on the batch or on how it
  * is split into launches (no atomics, no grid barrier).
- * The handle records the gallery's n: after mi_gallery_append* or mi_gallery_remove_rows probe and search return MI_ERR_INVALID
- * and read no stale table.  Not built: updating an index in place, sharding, residuals, a list-major scan that shares a list's
- * rows between the queries that probe it.  Nothing routes to this index by default, and its speed has not been measured. */
+ * The handle records the gallery's n and its internal count of removals: after mi_gallery_append* or mi_gallery_remove_rows probe
+ * and search return MI_ERR_INVALID and read no stale table -- also when a removal and an append have put n back where it was.
+ * Updating in place.  The assignment reads the stored row alone and a removal leaves the stored rows of the survivors bit for
+ * bit, so both calls below have one contract: afterwards mi_ivfflat_info's n, mi_ivfflat_list_sizes, mi_ivfflat_get_lists (both
+ * tables) and every probe and search are, bit for bit, those of mi_ivfflat_build(rows, the same centroids) on the gallery as it
+ * now stands.  The centroids do not move.  Both are synchronous on the gallery's stream and take the gallery's and the handle's
+ * locks; rows appended with mi_gallery_append_device on another stream must be complete before the call.
+ *   mi_ivfflat_sync         takes in the rows [index n, gallery n) that mi_gallery_append* added since the index was made or last
+ *                           updated: assigned as the build assigns (in chunks of stored rows, no row crosses the host link) and
+ *                           spliced behind the rows of their lists.  *out_added (may be NULL): their number.  Nothing appended:
+ *                           MI_OK, nothing written, no launch.  More than 2^31 - 1 rows afterwards: MI_ERR_INVALID, index unchanged.
+ *                           Work: m * nlist row-centroid values for m new rows, where a new build evaluates n * nlist.
+ *   mi_ivfflat_remove_rows  removes rows from the gallery under the index AND from the index: arguments and bitmap of
+ *                           mi_gallery_remove_rows (ceil(n / 64) words, bit (i & 63) of word (i >> 6) names local row i, bits at or
+ *                           beyond n ignored, host or device memory).  The index must be fresh.  The lists are compacted by the
+ *                           bitmap (survivor i becomes i - the named rows below i; lists stay ascending), the gallery's rows by
+ *                           mi_gallery_remove_rows's own code.  *out_removed (may be NULL): n - n'.  No row named: MI_OK, 0,
+ *                           nothing touched.  Every row named: MI_ERR_INVALID before anything is touched (an index needs a row).
+ *                           Whatever makes mi_gallery_remove_rows refuse (an online handle on the gallery) makes this refuse,
+ *                           index and gallery unchanged.
+ * A removal made through mi_gallery_remove_rows alone is NOT followed: probe, search and mi_ivfflat_sync then return
+ * MI_ERR_INVALID (a removal was made outside the index: build a new index).
+ * Storage: either call writes new list tables beside the old ones, swaps them in and frees the old ones and its scratch.  After a
+ * sync or a removal the handle costs what it costs after a build: 4 bytes per row (list_rows is exactly [n]) plus 8 * (nlist + 1)
+ * bytes of list_off and the centroids; hbm_bytes reports what is held.  During the call the device also holds the new list_rows
+ * (4 bytes per row of the result) and scratch: a sync 8 bytes per appended row plus the assignment's values (at most 64 MiB), a
+ * removal the bitmap, its rank table and n / 64 bytes of counts.
+ * Not built: sharding, residuals, a list-major scan that shares a list's rows between the queries that probe it, re-training or
+ * moving centroids.  Nothing routes to this index by default, and its speed has not been measured. */
 typedef struct mi_ivfflat mi_ivfflat; /* opaque */
 int mi_ivfflat_build(mi_gallery* rows, const float* centroids, int32_t nlist, mi_ivfflat** out);
 int mi_ivfflat_create(mi_gallery* rows, const float* centroids, int32_t nlist, const int32_t* list_ids, int memspace,
@@ -417,6 +443,8 @@ int mi_ivfflat_list_sizes(mi_ivfflat* f, int64_t* out_sizes);
 int mi_ivfflat_get_lists(mi_ivfflat* f, int64_t* out_list_off, int32_t* out_list_rows);
 int mi_ivfflat_get_centroids(mi_ivfflat* f, float* out_host);
 int mi_ivfflat_destroy(mi_ivfflat* f); /* NULL is MI_OK */
+int mi_ivfflat_sync(mi_ivfflat* f, int64_t* out_added);
+int mi_ivfflat_remove_rows(mi_ivfflat* f, const uint64_t* remove_bits, int memspace, int64_t* out_removed);
 /* Every query entry point is a device form: q_dev [nq][d] packed f32, probes_dev and allow_dev in device memory (either may be
  * NULL), outputs in device memory; enqueued on `stream`, no synchronisation.  It stages the queries, the probes, their prefixes
  * and the partial lists of the scan in buffers of the handle (grown when a larger call comes; a batch whose staging would exceed
