@@ -178,6 +178,13 @@ SIGNATURES = {
     "mi_pq_train": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.c_int32, C.c_int32,
                               C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_pq_train_timing": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mi_kmeans_train": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int32, C.c_int32,
+                                  C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
+    "mi_kmeans_assign": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int,
+                                   C.c_void_p, c_i64p]),
+    "mi_kmeans_assign_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, c_i64p]),
+    "mi_kmeans_assign_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mi_ivfpq_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                   C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "mi_ivfpq_create_residual": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1847,17 +1854,23 @@ def pq_train(x, M, Ks, iters=20, init=None, init_rows=None, seed=None, device=0,
     keeps its value -- scipy.cluster.vq.kmeans2(minit="matrix"), the routine nanopq.PQ.fit runs per book.  It does NOT reproduce
     nanopq's or faiss's random draw of initial points, nor their float32 arithmetic.  Bad arguments and non-finite rows raise
     ValueError before the device is touched."""
+    a, code, rs, cs, cb0 = _pq_train_operands(x, M, Ks, iters, init, init_rows, seed, _max_words)
+    return _pq_train_call(_base_pointer(a), a.shape[0], a.shape[1], code, rs, cs, MI_HOST, int(M), int(Ks), int(iters), cb0, device, _fn)
+
+
+def _pq_train_operands(x, M, Ks, iters, init, init_rows, seed, max_words):
+    """What pq_train checks and prepares before the library is loaded -> (rows, dtype code, row stride, col stride, C_0 or None)."""
     a, code, rs, cs = _strided(x)
     n, d = a.shape
     M, Ks, iters = int(M), int(Ks), int(iters)
-    L = _pq_train_shape(n, d, M, Ks, iters, _max_words)
+    L = _pq_train_shape(n, d, M, Ks, iters, max_words)
     if (init is not None) + (init_rows is not None) + (seed is not None) > 1:
         raise ValueError("give at most one of init, init_rows and seed")
     if not np.isfinite(a).all():
         raise ValueError("training rows must be finite")
     cb0 = None
     if init is not None:
-        cb0 = _pq_train_init(init, M, Ks, L, _max_words)
+        cb0 = _pq_train_init(init, M, Ks, L, max_words)
     elif seed is not None:
         rng = np.random.RandomState(seed)
         init_rows = np.stack([rng.choice(n, Ks, replace=False) for _ in range(M)])
@@ -1868,7 +1881,7 @@ def pq_train(x, M, Ks, iters=20, init=None, init_rows=None, seed=None, device=0,
         if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= n):
             raise ValueError("init_rows must lie in [0, n = %d)" % n)
         cb0 = np.ascontiguousarray(np.stack([a[rows[j], j * L:(j + 1) * L] for j in range(M)]), dtype=np.float32)
-    return _pq_train_call(_base_pointer(a), n, d, code, rs, cs, MI_HOST, M, Ks, iters, cb0, device, _fn)
+    return a, code, rs, cs, cb0
 
 
 def pq_train_device(x_ptr, n, d, M, Ks, iters, init=None, dtype=MI_F32, row_stride=None, col_stride=1, device=0,
@@ -1904,6 +1917,123 @@ def pq_train_timing():
     a, u = np.zeros(cap, np.float32), np.zeros(cap, np.float32)
     check(load().mi_pq_train_timing(cap, a.ctypes.data_as(C.c_void_p), u.ctypes.data_as(C.c_void_p), None, None))
     return a[:na.value], u[:nu.value]
+
+
+KMEANS_MAX_CLUSTERS = PQW_MAX_WORDS  # centroids of kmeans_train / kmeans_assign (mi_kmeans_*)
+
+
+def _kmeans_call(ptr, n, d, code, rs, cs, memspace, k, iters, cb0, device, return_flagged):
+    out = np.empty((k, d), dtype=np.float32)
+    moved, flagged = np.zeros(iters, dtype=np.int64), np.zeros(iters, dtype=np.int64)
+    check(load().mi_kmeans_train(C.c_void_p(ptr), int(n), int(d), code, int(rs), int(cs), memspace, k, iters,
+                                 None if cb0 is None else C.c_void_p(cb0.ctypes.data), device, out.ctypes.data_as(C.c_void_p),
+                                 moved.ctypes.data_as(C.c_void_p), flagged.ctypes.data_as(C.c_void_p), None))
+    return (out, moved, flagged) if return_flagged else (out, moved)
+
+
+def _kmeans_book(a, what):
+    """A centroid array [k, d] or row-index array [k] in pq_train's one-book shape, [1, k, d] or [1, k]."""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    return a[None] if a.ndim == what else a
+
+
+def kmeans_train(x, k, iters=20, init=None, init_rows=None, seed=None, device=0, return_flagged=False):
+    """k-means over whole rows on the device (mi_kmeans_train): Lloyd's iteration with k centroids of d floats, 2 <= k <= 8192 ->
+    (centroids float32 [k, d], moved int64 [iters]), bit for bit pqw_train(x, 1, k, ...)'s codebook and move counts -- the same
+    contract, init rules (init [k, d], init_rows [k], seed, or the rows floor(c * n / k)) and ValueErrors with M = 1.  The
+    assignment runs at f64 matrix rate: an MFMA kernel decides every row whose two best centroids lie further apart than a
+    rounding bound, the direct-form arithmetic the rest.  return_flagged=True appends flagged int64 [iters], the rows per
+    iteration the second kind decided.  pq_train_timing reports this call too."""
+    a, code, rs, cs, cb0 = _pq_train_operands(x, 1, k, iters, _kmeans_book(init, 2), _kmeans_book(init_rows, 1), seed, KMEANS_MAX_CLUSTERS)
+    return _kmeans_call(_base_pointer(a), a.shape[0], a.shape[1], code, rs, cs, MI_HOST, int(k), int(iters), cb0, device,
+                        return_flagged)
+
+
+def kmeans_train_device(x_ptr, n, d, k, iters, init=None, dtype=MI_F32, row_stride=None, col_stride=1, device=0,
+                        return_flagged=False):
+    """kmeans_train on device-resident rows (used where they lie; their producer must have completed), addressed as in
+    pq_train_device.  init: centroids [k, d] or None (the rows floor(c * n / k))."""
+    k, iters = int(k), int(iters)
+    _pq_train_shape(n, d, 1, k, iters, KMEANS_MAX_CLUSTERS)
+    cb0 = None if init is None else _pq_train_init(_kmeans_book(init, 2), 1, k, int(d), KMEANS_MAX_CLUSTERS)
+    return _kmeans_call(int(x_ptr), n, d, dtype, d if row_stride is None else row_stride, col_stride, MI_DEVICE, k, iters, cb0,
+                        device, return_flagged)
+
+
+def kmeans_centroids(centroids, d=None):
+    """float32 [k, d] C-contiguous centroids, checked against what kmeans_assign takes: 2 <= k <= 8192, d <= 4096, finite.  Raises
+    ValueError."""
+    g = np.asarray(centroids)
+    if g.ndim == 3 and g.shape[0] == 1:              # what pq_train(x, 1, k) returns
+        g = g[0]
+    g = pq_codebooks(g[None] if g.ndim == 2 else g, KMEANS_MAX_CLUSTERS)[0]
+    if d is not None and g.shape[1] != int(d):
+        raise ValueError("centroids of %d columns, the rows have d = %d" % (g.shape[1], d))
+    return g
+
+
+def kmeans_assign(x, centroids, device=0, return_flagged=False):
+    """-> int32 [n]: the id of every row's nearest centroid (mi_kmeans_assign), the float64 direct-form argmin with ties to the
+    lower id -- what WidePQIndex.encode returns on a one-book index holding `centroids` [k, d].  Host in, host out; the rows pass
+    through the device in bounded blocks.  return_flagged=True -> (ids, the number of rows the direct-form kernel decided)."""
+    a, code, rs, cs = _strided(x)
+    g = kmeans_centroids(centroids, a.shape[1])
+    if not np.isfinite(a).all():
+        raise ValueError("rows must be finite")
+    out = np.empty(a.shape[0], dtype=np.int32)
+    flagged = C.c_int64()
+    check(load().mi_kmeans_assign(C.c_void_p(_base_pointer(a)), a.shape[0], a.shape[1], code, rs, cs, C.c_void_p(g.ctypes.data),
+                                  g.shape[0], device, out.ctypes.data_as(C.c_void_p), C.byref(flagged)))
+    return (out, flagged.value) if return_flagged else out
+
+
+def kmeans_assign_workspace_bytes(k, n):
+    """Bytes of device workspace kmeans_assign_device uses for n rows and k centroids (at most 64 MiB and a little)."""
+    _pq_check_words(int(k), KMEANS_MAX_CLUSTERS)
+    b = C.c_int64()
+    check(load().mi_kmeans_assign_workspace_bytes(int(k), int(n), C.byref(b)))
+    return b.value
+
+
+def kmeans_assign_device(x_ptr, n, d, centroids_ptr, k, out_ptr, workspace_ptr, workspace_bytes, flagged_ptr=None, dtype=MI_F32,
+                         row_stride=None, col_stride=1, stream=None):
+    """Device rows [n][d] and float32 centroids [k][d] -> int32 ids [n] on the device, enqueued on `stream` with no
+    synchronisation and nothing read back (mi_kmeans_assign_device).  flagged_ptr: an optional device uint64 that receives the
+    number of rows the direct-form kernel decided.  The workspace (kmeans_assign_workspace_bytes) is the caller's and stays
+    untouched by others until the work on `stream` is done."""
+    check(load().mi_kmeans_assign_device(C.c_void_p(x_ptr), int(n), int(d), dtype, int(d if row_stride is None else row_stride),
+                                         int(col_stride), C.c_void_p(centroids_ptr), int(k), C.c_void_p(out_ptr),
+                                         C.c_void_p(flagged_ptr), C.c_void_p(workspace_ptr), int(workspace_bytes),
+                                         C.c_void_p(stream)))
+
+
+class KMeans:
+    """The members the reference uses of sklearn.cluster.KMeans (src/utils/nnsearch.py:967-989) on kmeans_train / kmeans_assign:
+    fit(x) draws the initial rows as RandomState(seed).choice(n, n_clusters, replace=False) and leaves cluster_centers_ float32
+    [n_clusters, d], labels_ int32 [n] (the assignment under the final centroids) and n_iter_; predict(x) -> int32 ids.
+    Deterministic; it is Lloyd's iteration in float64 as kmeans_train states it, not sklearn's k-means++ or its tolerance."""
+
+    def __init__(self, n_clusters, iters=20, seed=0, device=0):
+        self.n_clusters, self.iters, self.seed, self.device = int(n_clusters), int(iters), seed, device
+        _pq_check_words(self.n_clusters, KMEANS_MAX_CLUSTERS)
+        if self.iters < 1:
+            raise ValueError("iters = %d, training takes at least one iteration" % self.iters)
+        self.cluster_centers_ = self.labels_ = self.n_iter_ = None
+
+    def fit(self, x):
+        c, moved = kmeans_train(x, self.n_clusters, iters=self.iters, seed=self.seed, device=self.device)
+        stops = np.flatnonzero(moved[1:] == 0)
+        self.n_iter_ = int(stops[0]) + 2 if stops.size else self.iters      # iterations that assigned (the stopping one included)
+        self.cluster_centers_ = c
+        self.labels_ = kmeans_assign(x, c, device=self.device)
+        return self
+
+    def predict(self, x):
+        if self.cluster_centers_ is None:
+            raise ValueError("predict before fit: the KMeans has no centroids yet")
+        return kmeans_assign(x, self.cluster_centers_, device=self.device)
 
 
 def _remove_rows(index, name, rows):
@@ -2486,12 +2616,21 @@ class IVFFlatIndex(_Handle):
     @staticmethod
     def train(x, nlist, iters=20, seed=0, device=0):
         """-> centroids float32 [nlist, d]: deterministic k-means on x [n, d] with ONE book of nlist full-dimension codewords,
-        pq_train up to 256 lists and pqw_train above that (up to 8192)."""
+        pq_train up to 256 lists and pqw_train above that (up to 8192).  train_matrix returns the same centroids bit for bit with
+        the assignment at f64 matrix rate."""
         nlist = int(nlist)
         if not 2 <= nlist <= IVFFLAT_MAX_LISTS:
             raise ValueError("nlist = %d lists, an IVF-Flat index takes 2 .. %d" % (nlist, IVFFLAT_MAX_LISTS))
         fit = pq_train if nlist <= PQ_MAX_WORDS else pqw_train
         return np.ascontiguousarray(fit(x, 1, nlist, iters=iters, seed=seed, device=device)[0][0], dtype=np.float32)
+
+    @staticmethod
+    def train_matrix(x, nlist, iters=20, seed=0, device=0):
+        """train with the assignment at f64 matrix rate (kmeans_train): the same arguments, the same centroids bit for bit."""
+        nlist = int(nlist)
+        if not 2 <= nlist <= IVFFLAT_MAX_LISTS:
+            raise ValueError("nlist = %d lists, an IVF-Flat index takes 2 .. %d" % (nlist, IVFFLAT_MAX_LISTS))
+        return kmeans_train(x, nlist, iters=iters, seed=seed, device=device)[0]
 
     @classmethod
     def build(cls, gallery, centroids):

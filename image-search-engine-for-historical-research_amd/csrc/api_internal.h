@@ -531,6 +531,49 @@ static bool pq_all_finite(const T* x, int64_t rows, int32_t d, int64_t rs, int64
       if (!std::isfinite(x[r * rs + (int64_t)c * cs])) return false;
   return true;
 }
+// api_pq_train.hip, api_kmeans.hip: what a training call owns -- a stream, its events and its buffers, freed before it returns
+template <typename CodeT>
+struct TrainScratch {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};     // assignment begin / end, update begin / end
+  void* xdev = nullptr;                    // host rows, packed [n][d] in their own type
+  CodeT* codes[2] = {nullptr, nullptr};    // [n][m] of this iteration and of the one before
+  CodeT* cols = nullptr;                   // [m][n]
+  float* cb = nullptr;                     // [m][ks][L], updated in place
+  unsigned long long* moved = nullptr;
+  ~TrainScratch() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (void* p : {xdev, (void*)codes[0], (void*)codes[1], (void*)cols, (void*)cb, (void*)moved}) (void)hipFree(p);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+// host rows -> packed [n][d] on the device, once.  Rows that are not contiguous pass through a host block of 64 MiB
+template <typename CodeT>
+static int train_upload(TrainScratch<CodeT>& w, const void* x, int64_t n, int32_t d, size_t esz, int64_t rs, int64_t cs) {
+  if (cs == 1 && (rs == d || n == 1)) {
+    HIPC(hipMemcpyAsync(w.xdev, x, (size_t)n * d * esz, hipMemcpyHostToDevice, w.stream));
+    HIPC(hipStreamSynchronize(w.stream));
+    return MI_OK;
+  }
+  const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)d * (int64_t)esz));
+  std::vector<char> pack((size_t)std::min(step, n) * d * esz);
+  for (int64_t r0 = 0; r0 < n; r0 += step) {
+    const int64_t mm = std::min(step, n - r0);
+    const char* src = (const char*)x + (size_t)r0 * rs * esz;
+    for (int64_t r = 0; r < mm; ++r)
+      for (int32_t c = 0; c < d; ++c)
+        std::memcpy(pack.data() + ((size_t)r * d + c) * esz, src + ((size_t)r * rs + (size_t)c * cs) * esz, esz);
+    HIPC(hipMemcpyAsync((char*)w.xdev + (size_t)r0 * d * esz, pack.data(), (size_t)mm * d * esz, hipMemcpyHostToDevice, w.stream));
+    HIPC(hipStreamSynchronize(w.stream));              // the block is packed again
+  }
+  return MI_OK;
+}
+// device times of the calling thread's last mi_pq_train / mi_pqw_train / mi_kmeans_train, per iteration that ran
+// (mi_pq_train_timing; defined in api_pq_train.hip)
+struct TrainTimes { std::vector<float> assign_ms, update_ms; };
+MI_INTERNAL TrainTimes& train_times();
 // api_pq.hip, api_ivfpq.hip: the checks the host query entry points share
 static inline int check_host_queries(int32_t d, const void* q, int64_t nq, int dtype, int64_t rs, int64_t cs) {
   REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype must be MI_F32 or MI_F64");

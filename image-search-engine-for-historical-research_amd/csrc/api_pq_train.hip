@@ -6,49 +6,6 @@
 
 namespace {
 
-template <typename CodeT>
-struct TrainScratch {
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};     // assignment begin / end, update begin / end
-  void* xdev = nullptr;                    // host rows, packed [n][d] in their own type
-  CodeT* codes[2] = {nullptr, nullptr};    // [n][m] of this iteration and of the one before
-  CodeT* cols = nullptr;                   // [m][n]
-  float* cb = nullptr;                     // [m][ks][L], updated in place
-  unsigned long long* moved = nullptr;
-  ~TrainScratch() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (void* p : {xdev, (void*)codes[0], (void*)codes[1], (void*)cols, (void*)cb, (void*)moved}) (void)hipFree(p);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-// device times of the calling thread's last mi_pq_train / mi_pqw_train, per iteration that ran (mi_pq_train_timing)
-thread_local std::vector<float> t_assign_ms, t_update_ms;
-
-// host rows -> packed [n][d] on the device, once.  Rows that are not contiguous pass through a host block of 64 MiB
-template <typename CodeT>
-int train_upload(TrainScratch<CodeT>& w, const void* x, int64_t n, int32_t d, size_t esz, int64_t rs, int64_t cs) {
-  if (cs == 1 && (rs == d || n == 1)) {
-    HIPC(hipMemcpyAsync(w.xdev, x, (size_t)n * d * esz, hipMemcpyHostToDevice, w.stream));
-    HIPC(hipStreamSynchronize(w.stream));
-    return MI_OK;
-  }
-  const int64_t step = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)d * (int64_t)esz));
-  std::vector<char> pack((size_t)std::min(step, n) * d * esz);
-  for (int64_t r0 = 0; r0 < n; r0 += step) {
-    const int64_t mm = std::min(step, n - r0);
-    const char* src = (const char*)x + (size_t)r0 * rs * esz;
-    for (int64_t r = 0; r < mm; ++r)
-      for (int32_t c = 0; c < d; ++c)
-        std::memcpy(pack.data() + ((size_t)r * d + c) * esz, src + ((size_t)r * rs + (size_t)c * cs) * esz, esz);
-    HIPC(hipMemcpyAsync((char*)w.xdev + (size_t)r0 * d * esz, pack.data(), (size_t)mm * d * esz, hipMemcpyHostToDevice, w.stream));
-    HIPC(hipStreamSynchronize(w.stream));              // the block is packed again
-  }
-  return MI_OK;
-}
-
 // the training proper; ks_max and ks_msg are the entry point's limit on ks
 template <typename CodeT>
 int train_run(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t m,
@@ -75,8 +32,8 @@ int train_run(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride
   }
   const auto t0 = std::chrono::steady_clock::now();
   if (out_seconds) *out_seconds = 0.0;
-  t_assign_ms.clear();
-  t_update_ms.clear();
+  train_times().assign_ms.clear();
+  train_times().update_ms.clear();
   HIPC(hipSetDevice(device));
   const int32_t L = d / m;
   const size_t esz = dtype == MI_F32 ? 4 : 8;
@@ -110,7 +67,7 @@ int train_run(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride
     if (!update_pending) return MI_OK;
     float ms = 0.f;
     HIPC(hipEventElapsedTime(&ms, w.ev[2], w.ev[3]));
-    t_update_ms.push_back(ms);
+    train_times().update_ms.push_back(ms);
     update_pending = false;
     return MI_OK;
   };
@@ -132,7 +89,7 @@ int train_run(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride
     if ((rc = read_update()) != MI_OK) return rc;
     float ms = 0.f;
     HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    t_assign_ms.push_back(ms);
+    train_times().assign_ms.push_back(ms);
     if (out_moved) out_moved[t] = (int64_t)moved;
     if (t > 0 && moved == 0) break;                    // the same members give the same sums: C_iters = C_t
     HIPC(hipEventRecord(w.ev[2], s));
@@ -154,6 +111,11 @@ int train_run(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride
 
 }  // namespace
 
+TrainTimes& train_times() {
+  thread_local TrainTimes t;
+  return t;
+}
+
 extern "C" {
 
 int mi_pq_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t m,
@@ -174,10 +136,10 @@ int mi_pqw_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_str
 int mi_pq_train_timing(int32_t capacity, float* out_assign_ms, float* out_update_ms, int32_t* out_assignments, int32_t* out_updates) {
   REQUIRE(capacity >= 0, "negative capacity");
   REQUIRE(capacity == 0 || (out_assign_ms && out_update_ms), "null pointer");
-  for (int32_t i = 0; i < capacity && i < (int32_t)t_assign_ms.size(); ++i) out_assign_ms[i] = t_assign_ms[i];
-  for (int32_t i = 0; i < capacity && i < (int32_t)t_update_ms.size(); ++i) out_update_ms[i] = t_update_ms[i];
-  if (out_assignments) *out_assignments = (int32_t)t_assign_ms.size();
-  if (out_updates) *out_updates = (int32_t)t_update_ms.size();
+  for (int32_t i = 0; i < capacity && i < (int32_t)train_times().assign_ms.size(); ++i) out_assign_ms[i] = train_times().assign_ms[i];
+  for (int32_t i = 0; i < capacity && i < (int32_t)train_times().update_ms.size(); ++i) out_update_ms[i] = train_times().update_ms[i];
+  if (out_assignments) *out_assignments = (int32_t)train_times().assign_ms.size();
+  if (out_updates) *out_updates = (int32_t)train_times().update_ms.size();
   return MI_OK;
 }
 

@@ -429,6 +429,24 @@ void launch_pq_moved(const uint16_t* a, const uint16_t* b, int64_t bytes, unsign
 void launch_pq_update(const void* x, int dtype, int64_t rs, int64_t cs, int64_t n, const uint16_t* cols, int32_t M, int32_t Ks, int32_t L,
                       float* cb, hipStream_t stream);
 
+// kmeans.hip -- k-means assignment over whole rows at f64 matrix rate (api_kmeans.hip): out[i] = the id of row i's
+// nearest centroid of cb [k][d] f32 in the float64 direct form, ties to the lower id -- launch_pq_encode's answer with one book.
+// An MFMA kernel decides the rows a rounding certificate covers, a fixed-grid direct-form kernel the rest; *total (may be NULL)
+// += the number of rows the latter decided.  Everything is enqueued on `stream`, nothing is read back.  The rows pass in chunks of
+// w.rows, so the workspace is bounded whatever n is: km_workspace lays `bytes` at `base` out (rows < 128: too small)
+struct KmWorkspace {
+  int64_t rows = 0;                  // rows per chunk, a multiple of 128
+  double *cn = nullptr, *cmax2 = nullptr, *xn2 = nullptr, *wb = nullptr, *ws = nullptr;
+  int32_t* wi = nullptr;
+  uint32_t *list = nullptr, *count = nullptr;
+};
+int64_t km_workspace_bytes(int32_t k, int64_t rows);           // what chunks of `rows` rows need
+KmWorkspace km_workspace(void* base, int64_t bytes, int32_t k);
+void launch_km_assign(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, const float* cb, int32_t k, int32_t* out,
+                      unsigned long long* total, const KmWorkspace& w, hipStream_t stream);
+void launch_km_assign(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, const float* cb, int32_t k, uint16_t* out,
+                      unsigned long long* total, const KmWorkspace& w, hipStream_t stream);   // the training's codes
+
 // pq_wide.hip -- exact ADC top-K on wide PQ codes (api_pq_wide.hip): Ks <= 8192, a code is M uint16.  Gallery blocks
 // of 64 rows, two books to a dword, dwords transposed: codes[block][w < ceil(M / 2)][64].  Only the scan is this file's: tables,
 // matrix, selection and emit are pq.hip's (launch_pq_table, launch_dense_topk, launch_pq_emit), and so are check, ingest, encoder and

@@ -692,6 +692,39 @@ int mi_pqw_train(const void* x, int64_t n, int32_t d, int dtype, int64_t row_str
                  int32_t ks, int32_t iters, const float* init_codebooks_host, int device, float* out_codebooks_host,
                  int64_t* out_moved, double* out_seconds);
 
+/* ---- k-means over whole rows at f64 matrix rate: the coarse quantizer of the IVF indexes, faiss.Kmeans / Clustering, the
+ * reference's sklearn.cluster.KMeans(n_clusters).fit / .predict (src/utils/nnsearch.py:967-989).  DESIGN.md 5.14g.
+ * mi_kmeans_train is Lloyd's iteration with k centroids of d floats (2 <= k <= 8192, 1 <= d <= 4096, n >= k, iters >= 1) and its
+ * contract is mi_pqw_train's with m = 1, word for word: the default C_0 (rows floor(c * n / k)), the float64 direct-form argmin
+ * with ties to the lower centroid, moved[t] and the exact early stop, update sums in ascending row order with one divide, float32
+ * centroids after every iteration, an empty centroid keeps its value, a result passed back in resumes the run.
+ * out_centroids_host [k][d] and out_moved [iters] equal what mi_pqw_train(..., m = 1, ks = k, ...) writes, BIT FOR BIT.  What
+ * differs is how the assignment is found: an f64 MFMA kernel evaluates ||c||^2 - 2 x.c for every (row, centroid) and decides every
+ * row whose two best centroids lie further apart than a rounding bound (tau = 4 gamma (||x|| + max ||c||)^2, gamma = (d + 3) u /
+ * (1 - (d + 3) u), u = 2^-53, every factor rounded up); the other rows -- near-ties, ties, NaN, infinity -- are decided by the
+ * direct-form arithmetic itself.  out_flagged [iters] (may be NULL) receives, per iteration that ran, the number of rows of the
+ * second kind (0 for the iterations that did not run).  Argument checks, the refusal of non-finite host rows, memory (one packed
+ * copy of host rows, 3 * n * 2 bytes of ids, at most 64 MiB of workspace) and synchronisation are mi_pqw_train's; one 16-byte
+ * read-back per iteration.  mi_pq_train_timing reports this call too.  x_dtype is MI_F32 or MI_F64, in all three entry points. */
+int mi_kmeans_train(const void* x, int64_t n, int32_t d, int x_dtype, int64_t row_stride, int64_t col_stride, int memspace, int32_t k,
+                    int32_t iters, const float* init_centroids_host, int device, float* out_centroids_host, int64_t* out_moved,
+                    int64_t* out_flagged, double* out_seconds);
+/* The assignment alone: out_ids[r] = the centroid nearest to row r, what mi_pqw_encode returns on a one-book index holding
+ * centroids_host [k][d] (finite).  Host rows (any strides, finite) pass through the device in blocks of at most 64 MiB, as in
+ * mi_lsh_encode; synchronous.  out_flagged (may be NULL): the rows the direct-form kernel decided. */
+int mi_kmeans_assign(const void* x, int64_t n, int32_t d, int x_dtype, int64_t row_stride, int64_t col_stride,
+                     const float* centroids_host, int32_t k, int device, int32_t* out_ids, int64_t* out_flagged);
+/* The device form: rows, centroids [k][d] float32, ids [n] int32 and the optional flagged count (one uint64, set, not added to) on
+ * the current device; enqueued on `stream`, no synchronisation, no allocation and NOTHING read back -- the direct-form kernel runs
+ * with a fixed grid over a list whose length it reads from device memory.  The caller lends the workspace (8-byte aligned;
+ * mi_kmeans_assign_workspace_bytes(k, n) is what serves n rows in the largest chunks the call uses, at most 64 MiB; anything from
+ * mi_kmeans_assign_workspace_bytes(k, 128) up is accepted and only makes the chunks smaller) until the work on `stream` is done.
+ * Non-finite rows get the id the direct form gives them. */
+int mi_kmeans_assign_workspace_bytes(int32_t k, int64_t n, int64_t* out_bytes);
+int mi_kmeans_assign_device(const void* x_dev, int64_t n, int32_t d, int x_dtype, int64_t row_stride, int64_t col_stride,
+                            const float* centroids_dev, int32_t k, int32_t* out_ids_dev, uint64_t* out_flagged_dev,
+                            void* workspace_dev, int64_t workspace_bytes, void* stream);
+
 /* ---- graph index over PQ codes: best-first search of a neighbour graph whose rows are the codes of ONE mi_pq index, the role of
  * the reference's PQ + HNSW matchers (matching_HNSW_PQ, matching_HNSW_NanoPQ, matching_PQ_HNSW_faiss; src/utils/nnsearch.py:541-683,
  * 802-825).  DESIGN.md 5.16b.  No raw rows are resident: the index is the m code bytes and the 4 R table bytes of a row, and a
