@@ -90,6 +90,13 @@ SIGNATURES = {
                                           C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_knn_search_minkowski_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_int32, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_range_search_minkowski": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double,
+                                            C.c_double, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            c_f64p]),
+    "mi_range_search_minkowski_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mi_minkowski_self_range": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_graph_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "mi_graph_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "mi_graph_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -451,6 +458,16 @@ def minkowski_args(metric, p, k):
     return MINK_METRICS[metric], float(p)
 
 
+def minkowski_range_args(metric, p, radius):
+    """The checks of a Minkowski radius search that need no device -> (metric code, p, radius as the library takes them).
+    Raises ValueError on what minkowski_args refuses and on a radius that is NaN or negative (+inf is fine)."""
+    code, p = minkowski_args(metric, p, 1)
+    radius = float(radius)
+    if not radius >= 0:
+        raise ValueError("radius must be >= 0 and not NaN, got %r" % (radius,))
+    return code, p, radius
+
+
 def _range_capacity(nq, max_results):
     """First capacity of a range search: max_results, by default Q * 1024."""
     return int(max_results) if max_results is not None else nq * 1024
@@ -474,6 +491,27 @@ def _range_call(lock, call, nq, max_results, dtype):
         check(rc)
     total = int(lims[-1])
     return lims, idx[:total], val[:total], secs.value
+
+
+def _mink_range_call(lock, call, nq, max_results):
+    """_range_call for the Minkowski radius searches, which return two value arrays: `call(cap, lims, idx, dist, dist64, secs)`
+    -> (lims int64 [nq+1], idx int64, dist float32, dist64 float64, seconds)."""
+    cap = _range_capacity(nq, max_results)
+    lims = np.zeros(nq + 1, dtype=np.int64)
+    secs = C.c_double()
+    with lock:
+        for attempt in range(2):
+            idx = np.empty(cap, dtype=np.int64)
+            dist = np.empty(cap, dtype=np.float32)
+            dist64 = np.empty(cap, dtype=np.float64)
+            rc = call(cap, lims.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
+                      dist64.ctypes.data_as(C.c_void_p), C.byref(secs))
+            if rc != MI_ERR_CAPACITY or attempt == 1:
+                break
+            cap = int(lims[-1])
+        check(rc)
+    total = int(lims[-1])
+    return lims, idx[:total], dist[:total], dist64[:total], secs.value
 
 
 def _hbm_bytes(info, nouts):
@@ -761,6 +799,47 @@ class Gallery(_Handle):
         check(load().mi_knn_search_minkowski_device(self._h, C.c_void_p(q_ptr), int(nq), code, p, int(k), C.c_void_p(allow_ptr),
                                                     C.c_void_p(idx_ptr), C.c_void_p(dist_ptr), C.c_void_p(dist64_ptr),
                                                     C.c_void_p(stream)))
+
+    def range_search_minkowski(self, queries, radius, metric="l1", p=None, allow=None, max_results=None):
+        """Exact Minkowski radius search on this gallery's stored rows (mi_range_search_minkowski; faiss IndexFlat.range_search):
+        every admitted row whose value -- search_minkowski's for that pair, bit for bit -- is <= radius (inclusive, float64) ->
+        (lims int64 [Q+1], ids int64 [lims[-1]], dist float32, dist64 float64, seconds).  The hits of query i are
+        ids/dist/dist64[lims[i]:lims[i+1]], ordered by (value asc, id asc); a query has 0 .. n of them.  For "lp" the radius
+        applies to sum |q - g| ** p, NOT to its 1 / p-th power (a Euclidean radius r is metric="lp", p=2, radius=r * r).  allow:
+        anything allow_bitmap takes.  The first call's capacity is `max_results` (default Q * 1024); if the hits do not fit, the
+        call is made once more with exactly lims[-1].  Raises ValueError, before the library is called, on an unknown metric, a
+        p that is not finite and > 0, a NaN or negative radius or queries of another width."""
+        code, p, radius = minkowski_range_args(metric, p, radius)
+        a, dt, rs, cs = self._queries(queries)
+        nq = a.shape[0]
+        bits, bits_p, memspace = _resolve_allow(allow, None, self.n, self.row_offset)
+        lib = load()
+        return _mink_range_call(
+            self._lock, lambda cap, lims, idx, dist, dist64, secs: lib.mi_range_search_minkowski(
+                self._h, C.c_void_p(_base_pointer(a)), nq, dt, rs, cs, code, p, radius, bits_p, memspace, cap, lims, idx, dist, dist64,
+                secs),
+            nq, max_results)
+
+    def range_search_minkowski_device(self, q_ptr, nq, radius, max_results, lims_ptr, idx_ptr, metric="l1", p=None, allow_ptr=None,
+                                      dist_ptr=None, dist64_ptr=None, stream=None):
+        """Enqueued on `stream` without synchronising (mi_range_search_minkowski_device): q_ptr packed float32 [nq][d], lims
+        [nq + 1] int64, ids / dist / dist64 [max_results] on the device.  When lims[nq] > max_results nothing is written to ids /
+        dist / dist64: read lims[nq]."""
+        code, p, radius = minkowski_range_args(metric, p, radius)
+        check(load().mi_range_search_minkowski_device(self._h, C.c_void_p(q_ptr), int(nq), code, p, radius, C.c_void_p(allow_ptr),
+                                                      int(max_results), C.c_void_p(lims_ptr), C.c_void_p(idx_ptr),
+                                                      C.c_void_p(dist_ptr), C.c_void_p(dist64_ptr), C.c_void_p(stream)))
+
+    def self_range_minkowski(self, row0, nrows, radius, metric="l1", p=None, max_results=None):
+        """Stored rows [row0, row0 + nrows) as queries against the rows above each of them -> (lims int64 [nrows+1], ids, dist,
+        dist64, seconds): the hits of row row0 + i are the rows j > row0 + i with value <= radius, by (value asc, j asc)
+        (mi_minkowski_self_range).  The query rows never leave the device.  Capacity as in range_search_minkowski."""
+        code, p, radius = minkowski_range_args(metric, p, radius)
+        lib = load()
+        return _mink_range_call(
+            self._lock, lambda cap, lims, idx, dist, dist64, secs: lib.mi_minkowski_self_range(
+                self._h, int(row0), int(nrows), code, p, radius, cap, lims, idx, dist, dist64, secs),
+            int(nrows), max_results)
 
     def range_search(self, queries, min_score, max_results=None):
         """Every row whose exact score is >= min_score (inclusive), per query ->

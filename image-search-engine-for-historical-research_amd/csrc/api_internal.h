@@ -35,6 +35,9 @@
 //                     by launch_refine over the centroid table, list build, scan with selection and merge in ivfflat.hip
 //   api_minkowski.hip exact L1 / L-infinity / Lp top-K over a gallery's raw rows (mi_knn_search_minkowski*): float64 scan of every
 //                     row on the vector pipe, selection and merge in minkowski.hip
+//   api_minkowski_range.hip  radius search and self-join in the same metrics (mi_range_search_minkowski*, mi_minkowski_self_range):
+//                     the same scan, then count / offsets / emit / order / write-out in minkowski_range.hip, chunked by
+//                     "minkowski_range_bytes"; mink_range_plan.h has the chunk arithmetic
 // Device code shared between kernel files lives in headers of its own: l2_wave.h (squared-L2 wave arithmetic), pq_device.h (PQ index
 // family), graph_walk.h (the best-first walk of both graph indexes), slab_select.h (sort, stream selection and emit on (key, id)
 // entries in LDS: ivfflat.hip, minkowski.hip)
@@ -93,6 +96,7 @@ extern MI_INTERNAL std::atomic<int64_t> g_remove_block_rows;    // mi_gallery_re
 extern MI_INTERNAL std::atomic<int64_t> g_pq_remove_block_rows; // mi_pq_remove_rows: rows of the staging area (default 2 097 152)
 extern MI_INTERNAL std::atomic<int64_t> g_hamming_matrix_bytes; // mi_hamming_search*: bytes of the distance matrix (default 2 GiB)
 extern MI_INTERNAL std::atomic<int64_t> g_hamming_range_bytes;  // mi_hamming_range_search* / self_range: bytes of the (block, query) workspace (default 1 GiB)
+extern MI_INTERNAL std::atomic<int64_t> g_minkowski_range_bytes; // mi_range_search_minkowski* / mi_minkowski_self_range: bytes of the value matrix and counts of a chunk (default 256 MiB)
 extern MI_INTERNAL std::atomic<int> g_hamming_range_early_exit; // ... drop a (block, query) whose partial sums are all above the radius (default 1)
 extern MI_INTERNAL std::atomic<int64_t> g_pq_matrix_bytes;      // mi_pq_search*: bytes of the distance matrix (default 2 GiB); mi_ivfpq_search*: of the partial lists
 extern MI_INTERNAL std::atomic<int64_t> g_forest_build_bytes;   // mi_forest_build: bytes of the scratch of a group of trees (default 1 GiB)
@@ -359,7 +363,9 @@ struct mi_gallery {
   } refine{scratch};
   // Minkowski search (api_minkowski.hip)
   struct MinkScratch {
-    explicit MinkScratch(DeviceBufSet& s) : qraw(s), qpad(s), val(s), part_key(s), part_id(s), bits(s), oidx(s), odist(s), odist64(s) {}
+    explicit MinkScratch(DeviceBufSet& s) : qraw(s), qpad(s), val(s), part_key(s), part_id(s), bits(s), oidx(s), odist(s), odist64(s), rcnt(s),
+                                            roff(s), rkey{DeviceBuf<uint64_t>(s), DeviceBuf<uint64_t>(s)},
+                                            rrow{DeviceBuf<uint32_t>(s), DeviceBuf<uint32_t>(s)}, rlims(s) {}
     DeviceBuf<char> qraw;                // queries of a host call as given
     DeviceBuf<float> qpad;               // [nq][dp] queries with 16-byte aligned rows
     DeviceBuf<double> val;               // [queries of a chunk][n] f64 value of every row
@@ -369,6 +375,13 @@ struct mi_gallery {
     DeviceBuf<int64_t> oidx;             // [nq][k] results of a host call
     DeviceBuf<float> odist;
     DeviceBuf<double> odist64;
+    // radius search (api_minkowski_range.hip): counts and places per (query, part) of a chunk, the chunk's hits (ping-pong of the
+    // merge passes), the CSR offsets of a host call
+    DeviceBuf<uint32_t> rcnt;
+    DeviceBuf<int64_t> roff;
+    DeviceBuf<uint64_t> rkey[2];
+    DeviceBuf<uint32_t> rrow[2];
+    DeviceBuf<int64_t> rlims;
   } mink{scratch};
   // row removal (api_remove.hip): one arena of exactly the bytes the largest call needed -- staging area of "remove_block_rows"
   // rows in the gallery's own layout, keep-list, bitmap, scan buffers
@@ -493,6 +506,10 @@ MI_INTERNAL void filter_invalidate(mi_gallery* g);      // rows or image type of
 MI_INTERNAL int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                                      int32_t k, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
                                      mi_filter_info* out_info, double* out_seconds, bool l2_caller);
+// ---- api_minkowski.hip
+// the argument checks of every Minkowski entry point (*op: the term the kernels evaluate, MINK_OP_*); what the gallery must be
+MI_INTERNAL int mink_check(const mi_gallery* g, int64_t nq, int metric, double p, int32_t k, int* op);
+MI_INTERNAL int mink_rows_check(const mi_gallery* g);
 // ---- helpers of the handles (static: every translation unit has its own, nothing is exported)
 // the staging of a host search on a gallery (mi_gallery::io_*): `bytes` bytes, NULL when out of memory.  Sized in bytes, with its
 // own spare of a quarter + 256

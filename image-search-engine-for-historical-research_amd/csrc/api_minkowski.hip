@@ -7,8 +7,8 @@
 // values and partial lists of one chunk of queries: a batch that needs more goes in chunks of queries
 constexpr size_t MINK_STAGE_BYTES = (size_t)256 << 20;
 
-// the argument checks both forms share: they answer before the handle is read.  *op: the term the kernels evaluate
-static int mink_check(const mi_gallery* g, int64_t nq, int metric, double p, int32_t k, int* op) {
+// the argument checks both forms (and the radius search, api_minkowski_range.hip) share: they answer before the handle is read.  *op: the term the kernels evaluate
+int mink_check(const mi_gallery* g, int64_t nq, int metric, double p, int32_t k, int* op) {
   REQUIRE(g, "null handle");
   REQUIRE(metric == MI_MINK_L1 || metric == MI_MINK_LINF || metric == MI_MINK_LP, "metric must be MI_MINK_L1, MI_MINK_LINF or MI_MINK_LP");
   REQUIRE(metric != MI_MINK_LP || (std::isfinite(p) && p > 0.0), "p must be finite and > 0 (MI_MINK_LINF is the infinite case)");
@@ -21,7 +21,7 @@ static int mink_check(const mi_gallery* g, int64_t nq, int metric, double p, int
 }
 
 // what the gallery must be: one shard that holds its f32 rows, of a width whose query fits into LDS
-static int mink_rows_check(const mi_gallery* g) {
+int mink_rows_check(const mi_gallery* g) {
   if (!g->gal_f32) return fail(MI_ERR_UNSUPPORTED, "the gallery does not hold its f32 rows");
   if (mink_query_tile(g->ud) < 1)
     return fail(MI_ERR_UNSUPPORTED, "Minkowski search takes rows of at most 20480 columns (one float64 query in LDS)");

@@ -37,6 +37,10 @@ std::atomic<int64_t> g_hamming_matrix_bytes{HAMMING_MATRIX_DEFAULT};
 constexpr int64_t HAMMING_RANGE_DEFAULT = (int64_t)1 << 30;
 std::atomic<int64_t> g_hamming_range_bytes{HAMMING_RANGE_DEFAULT};
 std::atomic<int> g_hamming_range_early_exit{1};
+// mi_set_global_option("minkowski_range_bytes", ...): upper limit of the workspace of a Minkowski radius search (api_minkowski_range.hip):
+// the float64 values [queries of a chunk][rows] and the chunk's counts; a batch goes through it in chunks of whole query tiles
+constexpr int64_t MINK_RANGE_DEFAULT = (int64_t)256 << 20;
+std::atomic<int64_t> g_minkowski_range_bytes{MINK_RANGE_DEFAULT};
 // mi_set_global_option("pq_matrix_bytes", ...): the same limit for the float32 distance matrix of a PQ index (api_pq.hip); a batch
 // goes through it in chunks of whole query tiles, four queries at the least
 constexpr int64_t PQ_MATRIX_DEFAULT = (int64_t)2 << 30;
@@ -282,6 +286,10 @@ int mi_set_global_option(const char* name, double value) {
     REQUIRE(value >= 0 && value <= 1e13, "hamming_range_bytes: bytes of the workspace of a radius search on a binary index (0 = default, 1 GiB)");
     g_hamming_range_bytes = value == 0 ? HAMMING_RANGE_DEFAULT : (int64_t)value;
   }
+  else if (n == "minkowski_range_bytes") {
+    REQUIRE(value >= 0 && value <= 1e13, "minkowski_range_bytes: bytes of the workspace of a Minkowski radius search (0 = default, 256 MiB)");
+    g_minkowski_range_bytes = value == 0 ? MINK_RANGE_DEFAULT : (int64_t)value;
+  }
   else if (n == "hamming_range_early_exit") {
     REQUIRE(value == 0 || value == 1, "hamming_range_early_exit: 0 or 1");
     g_hamming_range_early_exit = (int)value;
@@ -316,6 +324,7 @@ int mi_get_global_option(const char* name, double* out_value) {
   else if (n == "pq_remove_block_rows") *out_value = (double)g_pq_remove_block_rows.load();
   else if (n == "hamming_matrix_bytes") *out_value = (double)g_hamming_matrix_bytes.load();
   else if (n == "hamming_range_bytes") *out_value = (double)g_hamming_range_bytes.load();
+  else if (n == "minkowski_range_bytes") *out_value = (double)g_minkowski_range_bytes.load();
   else if (n == "hamming_range_early_exit") *out_value = g_hamming_range_early_exit.load();
   else if (n == "pq_matrix_bytes") *out_value = (double)g_pq_matrix_bytes.load();
   else if (n == "forest_build_bytes") *out_value = (double)g_forest_build_bytes.load();

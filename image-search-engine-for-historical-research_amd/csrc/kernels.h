@@ -533,6 +533,7 @@ void launch_ivff_search(const float* gal_f32, const float* qry, int32_t dp, int3
 constexpr int MINK_OP_L1 = 0, MINK_OP_LINF = 1, MINK_OP_SQ = 2, MINK_OP_SQRT = 3, MINK_OP_POW = 4;
 constexpr int MINK_MAX_K = 2048;
 constexpr int64_t MINK_SLAB_ROWS = 2048, MINK_MAX_PARTS = 64;
+constexpr int64_t MINK_SCAN_BLOCK_ROWS = 256;                     // rows per workgroup of the scan
 // queries of a scan tile: as many of 8, 4, 2, 1 as fit into 160 KiB of LDS as float64 rows of round_up(d, 4); 0 = not even one
 static inline int mink_query_tile(int32_t d) {
   const int64_t row = ((int64_t)d + 3) / 4 * 4 * 8;
@@ -554,6 +555,38 @@ static inline int32_t mink_parts(int64_t n) {
 void launch_minkowski(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int64_t row_offset, int op, double p,
                       const uint64_t* allow, int32_t k, int32_t nq, double* val, int64_t ld, uint64_t* part_key, int64_t* part_id,
                       int64_t* out_idx, float* out_val, double* out_val64, hipStream_t stream);
+// the scan alone: val [query][row] of the rows the bitmap admits (the others keep what they held); n < 1 launches nothing
+void launch_minkowski_scan(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int op, double p, const uint64_t* allow,
+                           int32_t nq, double* val, int64_t ld, hipStream_t stream);
+
+// minkowski_range.hip -- what follows the scan in a Minkowski radius search or self-join (api_minkowski_range.hip): the
+// hits value <= radius of one chunk of queries counted per (query, part of the rows), placed by prefix sums, ordered by
+// (l2_dist_key(value) asc, row asc) and written out in CSR form.  A part is mink_part_rows(nrows) rows, a query has mink_parts(nrows)
+struct MinkRangeArgs {
+  const double* val = nullptr;       // [nq][ld]: column r is the value of local row row_base + r
+  int64_t ld = 0, nrows = 0;         // nrows: the rows that were scanned
+  int64_t row_base = 0;
+  int32_t nq = 0;                    // queries of the chunk (<= 65535)
+  const uint64_t* allow = nullptr;   // NULL or the bitmap over local rows
+  double radius = 0.0;
+  int64_t self_row0 = -1;            // >= 0: the self-join, query q is stored row self_row0 + q and only the rows above it count
+  uint32_t* cnt = nullptr;           // [nq][parts] hits
+  int64_t* off = nullptr;            // [nq][parts] their first place among the chunk's hits
+  int64_t* lims = nullptr;           // the CSR offsets from the chunk's first query on: [nq + 1]
+  const int64_t* total = nullptr;    // the call's lims[all queries]; nothing is written once *total > max_results
+  int64_t max_results = 0;
+  uint64_t* key[2] = {nullptr, nullptr};   // the chunk's hits from place 0 on: keys and local rows, ping-pong of the merge passes
+  uint32_t* row[2] = {nullptr, nullptr};
+};
+// counts, then off and (write_lims) lims[1 ..] on top of lims[0], which `first` sets to 0
+void launch_mink_range_count(const MinkRangeArgs& a, bool first, bool write_lims, hipStream_t stream);
+void launch_mink_range_emit(const MinkRangeArgs& a, hipStream_t stream);                 // -> key[0] / row[0], ascending rows per query
+// max_cnt: no query of the chunk has more hits.  -> the buffer (0 or 1) that holds the ordered lists
+int launch_mink_range_order(const MinkRangeArgs& a, int64_t max_cnt, int64_t max_total, hipStream_t stream);
+// the ordered lists of buffer `cur` -> out_*[lims[0] ..]; out_idx is written, either value output may be NULL
+void launch_mink_range_write(const MinkRangeArgs& a, int cur, int64_t max_total, int64_t row_offset, int64_t* out_idx, float* out_val,
+                             double* out_val64, hipStream_t stream);
+int64_t mink_range_run_length();                                                         // entries of one LDS-sorted run
 
 // pq_remove.hip -- in-place row removal of the PQ and the IVF-PQ index (api_pq.hip, api_ivfpq.hip).  keep [ceil(n / 64)]: the bitmap
 // of the rows that stay (bits at or beyond n clear); prefix [ceil(n / 64) + 1]: the exclusive count of keep bits per word.

@@ -36,6 +36,7 @@ constexpr int MINK_WAVE_ROWS = MINK_BLOCK_ROWS / MINK_WAVES;      // consecutive
 __host__ __device__ constexpr int mink_rows(int op) { return op == MINK_OP_SQRT || op == MINK_OP_POW ? 1 : 4; }
 __host__ __device__ constexpr int mink_queries(int op, int qt) { return op == MINK_OP_POW ? 1 : qt; }
 static_assert(MINK_WAVE_ROWS % 4 == 0, "a wave walks whole groups of rows");
+static_assert(MINK_BLOCK_ROWS == MINK_SCAN_BLOCK_ROWS, "the self-join starts its scans at whole blocks (api_minkowski_range.hip)");
 
 __device__ __forceinline__ double mink_wave_max(double x) {
   for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o));
@@ -220,20 +221,24 @@ static void mink_select_launch(const double* val, int64_t ld, int64_t n, const u
                                                                                       out_val, out_val64);
 }
 
+void launch_minkowski_scan(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int op, double p, const uint64_t* allow,
+                           int32_t nq, double* val, int64_t ld, hipStream_t stream) {
+  if (nq <= 0 || n < 1) return;
+  const int qt = mink_query_tile(d);
+  switch (op) {
+    case MINK_OP_L1: mink_scan_op<MINK_OP_L1>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
+    case MINK_OP_LINF: mink_scan_op<MINK_OP_LINF>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
+    case MINK_OP_SQ: mink_scan_op<MINK_OP_SQ>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
+    case MINK_OP_SQRT: mink_scan_op<MINK_OP_SQRT>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
+    default: mink_scan_op<MINK_OP_POW>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
+  }
+}
+
 void launch_minkowski(const float* gal_f32, const float* qry, int32_t dp, int32_t d, int64_t n, int64_t row_offset, int op, double p,
                       const uint64_t* allow, int32_t k, int32_t nq, double* val, int64_t ld, uint64_t* part_key, int64_t* part_id,
                       int64_t* out_idx, float* out_val, double* out_val64, hipStream_t stream) {
   if (nq <= 0) return;
-  const int qt = mink_query_tile(d);
-  if (n >= 1) {
-    switch (op) {
-      case MINK_OP_L1: mink_scan_op<MINK_OP_L1>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
-      case MINK_OP_LINF: mink_scan_op<MINK_OP_LINF>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
-      case MINK_OP_SQ: mink_scan_op<MINK_OP_SQ>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
-      case MINK_OP_SQRT: mink_scan_op<MINK_OP_SQRT>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
-      default: mink_scan_op<MINK_OP_POW>(qt, gal_f32, qry, dp, d, n, nq, allow, p, val, ld, stream); break;
-    }
-  }
+  launch_minkowski_scan(gal_f32, qry, dp, d, n, op, p, allow, nq, val, ld, stream);
   const int64_t part_rows = mink_part_rows(n);
   const int32_t nparts = mink_parts(n);
   if (k <= 1024)

@@ -4,7 +4,8 @@ The same print, photo or scan often enters an archive database more than once wh
 (the reference's `src/offline.py --datasets 'A, B, ...'`); this finds those copies as a self-join of exact range searches
 (Gallery.range_search) with the gallery's own stored rows as queries.  near_duplicate_pairs_hamming is the same
 join on the hash codes of a binary index (BinaryGallery.self_range): integer distances, 256 bytes per row at 2048
-bits instead of 8 KiB, and the queries never leave the device.
+bits instead of 8 KiB, and the queries never leave the device.  near_duplicate_pairs_minkowski is the join on the raw rows in
+L1, L-infinity, Lp or squared L2 (Gallery.self_range_minkowski): exact float64 values, the queries read on the device.
 """
 import numpy as np
 
@@ -54,3 +55,25 @@ def near_duplicate_pairs_hamming(binary, radius, batch=1024):
     if not out_i:
         return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32)
     return np.concatenate(out_i), np.concatenate(out_j), np.concatenate(out_d)
+
+
+def near_duplicate_pairs_minkowski(gallery, radius, metric="lp", p=2, batch=1024):
+    """-> (pairs int64 [P, 2] with i < j, dist64 float64 [P]): all pairs of stored rows whose Minkowski value is <= radius
+    (inclusive), in the order of i, then of (value asc, j asc).  metric "l1", "linf" or "lp" with p > 0 (the default, p = 2, is the
+    squared Euclidean distance; the radius applies to sum |x_i - x_j| ** p, not to its 1 / p-th power).  The join runs as
+    self_range_minkowski calls over `batch` rows at a time.  Assumes a single-shard gallery with row_offset 0 (ids are rows)."""
+    if gallery.row_offset != 0:
+        raise ValueError("near_duplicate_pairs_minkowski needs a gallery with row_offset 0 (a single shard)")
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    out_i, out_j, out_d = [], [], []
+    for r0 in range(0, gallery.n, batch):
+        m = min(batch, gallery.n - r0)
+        lims, idx, _, dist64, _ = gallery.self_range_minkowski(r0, m, radius, metric, p)
+        out_i.append(np.repeat(np.arange(r0, r0 + m, dtype=np.int64), np.diff(lims)))
+        out_j.append(np.asarray(idx, dtype=np.int64))
+        out_d.append(np.asarray(dist64, dtype=np.float64))
+    if not out_i:
+        return np.zeros((0, 2), np.int64), np.zeros(0, np.float64)
+    return np.stack([np.concatenate(out_i), np.concatenate(out_j)], axis=1), np.concatenate(out_d)

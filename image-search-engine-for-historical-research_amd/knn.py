@@ -22,7 +22,13 @@ ties go to the lower id.  Removal, radius search, save / load and sharding are n
 
 `l1`, `linf` and `lp` are faiss.IndexFlat(D, METRIC_L1 | METRIC_Linf | METRIC_Lp) (metric_arg = p): sum |q - x|, max |q - x| and
 sum |q - x| ** p -- faiss's value, not raised to 1 / p -- of the rows as given, in float64 over a NORM_NONE gallery
-(Gallery.search_minkowski); ties go to the lower id.  remove_ids works; range_search is not built for them.
+(Gallery.search_minkowski); ties go to the lower id.  remove_ids works; range_search is not defined for them, radius_search is:
+
+    KNN(database[N,D], 'euclidean' | 'l1' | 'linf' | 'lp').radius_search(queries[Q,D], radius)
+        -> (lims int64 [Q+1], D float32 [lims[-1]] ascending per query, I int64 [lims[-1]])
+
+every row whose value in the index's own metric is <= radius (inclusive; Gallery.range_search_minkowski): squared L2 for
+'euclidean', faiss's un-rooted sum for 'lp'.
 
     ANN(database[N,D], 'euclidean', M=64, nbits=8, nlist=256, nprobe=64).search(queries[Q,D], k)
         -> (squared ADC distances float32 [Q,k] ascending, ids int64 [Q,k])
@@ -32,7 +38,8 @@ by_residual = true) on a residual _lib.IVFPQIndex.
 """
 import numpy as np
 
-from ._lib import BinaryGallery, Gallery, IVFPQIndex, IVF_MAX_LISTS, MINK_METRICS, NORM_NONE, PQ_MAX_BOOKS, minkowski_args
+from ._lib import (BinaryGallery, Gallery, IVFPQIndex, IVF_MAX_LISTS, MINK_METRICS, NORM_NONE, PQ_MAX_BOOKS, minkowski_args,
+                   minkowski_range_args)
 
 
 class KNN:
@@ -95,6 +102,23 @@ class KNN:
             queries = queries.astype(np.float32)
         lims, ids, sims, _ = self.gallery.range_search(queries, float(thresh))
         return lims, sims, ids
+
+    def radius_search(self, queries, radius):
+        """-> (lims int64 [Q+1], D float32 [lims[-1]], I int64 [lims[-1]]), the return shape of range_search: every row whose
+        distance to the query in the index's own metric is <= radius (the bound is INCLUSIVE), ordered by (distance asc, id asc).
+        'euclidean': squared L2 distances, the values search returns (faiss IndexFlatL2.range_search), so a Euclidean radius r is
+        passed as r * r; 'l1', 'linf', 'lp': the values search returns ('lp': sum |q - x| ** p, not raised to 1 / p).  'cosine'
+        and 'hamming' have range_search."""
+        if self.method in ("cosine", "hamming"):
+            raise NotImplementedError("radius_search is defined for 'euclidean', 'l1', 'linf' and 'lp'; %r has range_search"
+                                      % (self.method,))
+        metric, p = ("lp", 2.0) if self.method == "euclidean" else (self.method, self.p)
+        minkowski_range_args(metric, p, radius)   # a bad radius raises here, before the queries are touched
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            queries = queries.astype(np.float32)
+        lims, ids, dist, _, _ = self.gallery.range_search_minkowski(queries, float(radius), metric, p)
+        return lims, dist, ids
 
     def remove_ids(self, ids):
         """faiss's IndexFlat.remove_ids, every float metric: the rows leave the index, the others keep their order and are renumbered

@@ -38,8 +38,9 @@ enum mi_status {
   MI_ERR_IO = 4,
   MI_ERR_OVERFLOW = 5,    /* candidate buffers overflowed and the exact fallback was disabled */
   MI_ERR_UNSUPPORTED = 6,
-  MI_ERR_CAPACITY = 7     /* mi_range_search, mi_hamming_range_search, mi_hamming_self_range: more results than max_results;
-                             out_lims[nq] says how many */
+  MI_ERR_CAPACITY = 7     /* mi_range_search, mi_hamming_range_search, mi_hamming_self_range, mi_range_search_minkowski,
+                             mi_range_search_minkowski_device (which reports it through out_lims_dev[nq] only),
+                             mi_minkowski_self_range: more results than max_results; out_lims[nq] says how many */
 };
 enum mi_dtype { MI_F32 = 0, MI_F64 = 1 };
 enum mi_memspace { MI_HOST = 0, MI_DEVICE = 1 };
@@ -259,6 +260,43 @@ int mi_knn_search_minkowski(mi_gallery* rows, const void* q, int64_t nq, int q_d
 int mi_knn_search_minkowski_device(mi_gallery* rows, const float* q_dev, int64_t nq, int metric, double p, int32_t k,
                                    const uint64_t* allow_bits_dev, int64_t* out_idx_dev, float* out_dist_dev,
                                    double* out_dist64_dev, void* stream);
+
+/* Exact radius search in the same metrics (faiss IndexFlat::range_search with METRIC_L1 / METRIC_Linf / METRIC_Lp / METRIC_L2):
+ * every row the bitmap admits whose value is <= radius.  DESIGN.md 5.19b.  The value of a (query, row) pair is
+ * mi_knn_search_minkowski's for that pair, bit for bit -- the same kernel computes it -- so it depends on nothing but the pair;
+ * metric, p, the gallery and the query are taken exactly as there (an L2 gallery: the caller's d columns; MI_MINK_LP with p == 2
+ * gives the bits of mi_knn_search_l2).  The comparison is made in float64 and is INCLUSIVE, like mi_hamming_range_search's; a NaN
+ * value is never a hit.  For MI_MINK_LP the radius applies to the value as defined above, sum_j t_j^p (faiss's), NOT to its 1 / p-th
+ * power: a Euclidean radius r is passed as r * r.  radius NaN or negative: MI_ERR_INVALID; +inf returns every admitted row whose
+ * value is not NaN.
+ * Results in CSR form: the hits of query i are out_idx / out_dist / out_dist64[out_lims[i] .. out_lims[i+1]), ordered by
+ * (value asc, id asc), ids row_offset + local row; a query has anywhere from 0 to n hits; out_dist is (float)out_dist64.
+ * out_lims [nq + 1] is always written in full.  If out_lims[nq] > max_results, nothing is written to out_idx / out_dist /
+ * out_dist64 and MI_ERR_CAPACITY is returned: call again with max_results >= out_lims[nq].  Either distance output may be NULL;
+ * out_idx may be NULL when max_results is 0.  nq == 0 is MI_OK.  Queries, bitmap and out_seconds as in mi_knn_search_minkowski.
+ * Fully determined: every output position is a prefix sum over (query, part of the rows, row) in ascending order, never the order
+ * in which the device ran, and the order inside a query is a total order.  The float64 values of a chunk of queries (8 bytes per
+ * (query, row) pair) and its counts stay within the global option "minkowski_range_bytes" (default 256 MiB; one scan tile of
+ * queries at the least), plus 24 bytes per hit of one chunk; a call of more than one chunk scans the gallery twice. */
+int mi_range_search_minkowski(mi_gallery* rows, const void* q, int64_t nq, int q_dtype, int64_t row_stride, int64_t col_stride,
+                              int metric, double p, double radius, const uint64_t* allow_bits, int allow_memspace,
+                              int64_t max_results, int64_t* out_lims, int64_t* out_idx, float* out_dist, double* out_dist64,
+                              double* out_seconds);
+/* Device form: q_dev [nq][d] packed f32, allow_bits_dev NULL or the bitmap in device memory, out_lims_dev [nq + 1] and
+ * out_idx_dev / out_dist_dev / out_dist64_dev [max_results] in device memory; enqueued on `stream`, no synchronisation.  The
+ * capacity decision is made on the device: the call returns MI_OK, and when out_lims_dev[nq] > max_results nothing was written to
+ * the three hit arrays -- the caller reads out_lims_dev[nq].  Buffers of the handle, serialisation and the ONE stream as for
+ * mi_knn_search_minkowski_device. */
+int mi_range_search_minkowski_device(mi_gallery* rows, const float* q_dev, int64_t nq, int metric, double p, double radius,
+                                     const uint64_t* allow_bits_dev, int64_t max_results, int64_t* out_lims_dev,
+                                     int64_t* out_idx_dev, float* out_dist_dev, double* out_dist64_dev, void* stream);
+/* Self-join: query i is the stored row row0 + i (read on the device, never copied to the host), and only the rows j > row0 + i
+ * are reported, so that a sweep over the whole gallery reports every pair once (ids are row_offset + j).  0 <= row0,
+ * 0 <= nrows, row0 + nrows <= n, otherwise MI_ERR_INVALID; nrows == 0 is MI_OK.  No bitmap.  The 256-row blocks wholly below
+ * row0 are not scanned.  Everything else as mi_range_search_minkowski. */
+int mi_minkowski_self_range(mi_gallery* rows, int64_t row0, int64_t nrows, int metric, double p, double radius,
+                            int64_t max_results, int64_t* out_lims, int64_t* out_idx, float* out_dist, double* out_dist64,
+                            double* out_seconds);
 
 /* ---- graph index: best-first search of a neighbour graph over the rows of a gallery, the role of the reference's HNSW matchers
  * (matching_HNSW and its kin, src/utils/nnsearch.py:59-538).  DESIGN.md 5.16.  What is approximate is WHICH rows the graph
@@ -1200,6 +1238,9 @@ int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
  * "hamming_matrix_bytes": upper limit of the distance matrix of a binary index (mi_hamming_search*; 0 = default, 2 GiB).
  * "hamming_range_bytes": upper limit of the (block, query) workspace of a radius search on a binary index
  * (mi_hamming_range_search*, mi_hamming_self_range; 0 = default, 1 GiB; 64 queries at the least).  The result does not depend on it.
+ * "minkowski_range_bytes": upper limit of the float64 values and counts of one chunk of queries of a Minkowski radius search
+ * (mi_range_search_minkowski*, mi_minkowski_self_range; 0 = default, 256 MiB; one scan tile of queries -- 8 at d <= 2560 -- at the
+ * least).  The result does not depend on it.
  * "hamming_range_early_exit": 1 (default) = the radius scan drops a (block, query) pair as soon as the partial distances of all
  * 64 rows exceed the radius; 0 = every pair is scanned to the last word.  The result does not depend on it.
  * "pq_matrix_bytes": upper limit of the distance matrix of a PQ index (mi_pq_search*; 0 = default, 2 GiB) and of the partial
@@ -1208,7 +1249,7 @@ int mi_set_global_option(const char* name, double value);
 /* "release_spares" (any value) gives the spare slots back now and leaves "keep_buffers" as it is.  An allocation of the library
  * that fails with out-of-memory releases them by itself and is tried once more; a gallery of other sizes than the spare releases
  * it when the device could not hold both.  mi_get_global_option reads "image_dtype", "host_ingest", "keep_buffers", "scatter_block_rows",
- * "remove_block_rows", "pq_remove_block_rows", "hamming_matrix_bytes", "hamming_range_bytes", "hamming_range_early_exit", "pq_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
+ * "remove_block_rows", "pq_remove_block_rows", "hamming_matrix_bytes", "hamming_range_bytes", "minkowski_range_bytes", "hamming_range_early_exit", "pq_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
  * extractor's PyTorch allocator) cannot see otherwise. */
 int mi_get_global_option(const char* name, double* out_value);
 

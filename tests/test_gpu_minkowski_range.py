@@ -1,0 +1,436 @@
+"""GPU: exact radius search and self-join in the Minkowski metrics (mi_range_search_minkowski, mi_range_search_minkowski_device,
+mi_minkowski_self_range, Gallery.range_search_minkowski / self_range_minkowski, KNN.radius_search,
+dedup.near_duplicate_pairs_minkowski) against the numpy truth of tests/_minkowski_range_truth.py.
+
+"l1", "linf", "lp" with p == 1 and p == 2 must give the truth's lims, ids and float64 BITS (the value of a pair is the top-K search's,
+whose sum order the contract fixes); the data spans 48 binades so that a wrong order would show.  p == 0.5 and p == 3 go against the
+high-accuracy reference at radii placed in the middle of a gap of at least 1e-9 between adjacent reference values, with the value
+tolerances of tests/test_gpu_minkowski.py."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _layouts as L
+import _minkowski_range_truth as R
+import _minkowski_truth as T
+
+pytestmark = pytest.mark.gpu
+
+QT = T.QT
+EXACT = (("l1", None), ("linf", None), ("lp", 1), ("lp", 2))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return L.load_lib()
+
+
+def _wide(seed, n, d):
+    rng = np.random.default_rng([seed, n, d])
+    return (rng.standard_normal((n, d)) * 2.0 ** rng.integers(-24, 24, (n, d))).astype(np.float32)
+
+
+def _gauss(seed, n, d):
+    return np.random.default_rng([seed, n, d]).standard_normal((n, d)).astype(np.float32)
+
+
+def _lattice(seed, n, d, lo=-1, hi=2):
+    return np.random.default_rng([seed, n, d]).integers(lo, hi, (n, d)).astype(np.float32)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _same(got, want, what=""):
+    lims, ids, dist, dist64 = got[:4]
+    assert lims.dtype == np.int64 and ids.dtype == np.int64 and dist.dtype == np.float32 and dist64.dtype == np.float64
+    assert np.array_equal(lims, want[0]), what
+    assert np.array_equal(ids, want[1]), what
+    assert np.array_equal(_bits(dist64), _bits(want[2])), what
+    assert np.array_equal(dist, want[2].astype(np.float32)), what
+
+
+def _kth(vals, i, k):
+    """the k-th smallest value (1-based, at most n) of query i"""
+    v = np.sort(vals[i])
+    return float(v[min(k, v.size) - 1])
+
+
+def _check(g, vals, q, radius, metric, p, allow=None, mask=None, off=0):
+    want = R.csr(vals, radius, allow=mask, row_offset=off)
+    got = g.range_search_minkowski(q, radius, metric, p, allow=allow)
+    _same(got, want, "%s p=%s radius=%r" % (metric, p, radius))
+    return got
+
+
+# (n, d, nq): the 256-row scan block, the 2048-row slab and the part boundary; the float4 tail and the 256-column stride; the
+# eight-query tile
+SHAPES = ([(n, 5, 9) for n in (1, 63, 255, 256, 257, 2047, 2048, 2049, 4100)] +
+          [(257, d, 7) for d in (1, 3, 4, 259)] + [(65, 2048, 9)] +
+          [(300, 37, nq) for nq in (1, 8, 17)])
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "n%d-d%d-nq%d" % s)
+def test_bit_exact_shapes_and_radius_edges(lib, shape):
+    """radius = an attained value (the 5th smallest of query 0: that row is a hit), the float64 below it (it is not), +inf (every
+    row) and a radius below every value of the call (nothing)"""
+    n, d, nq = shape
+    rows, q = _wide(1, n, d), _wide(2, nq, d)
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+        for metric, p in EXACT:
+            vals = T.values(rows, q, metric, p)
+            r5 = _kth(vals, 0, 5)
+            at = _check(g, vals, q, r5, metric, p)
+            assert at[0][1] >= min(5, n) and at[3][at[0][1] - 1] == r5                 # the last hit of query 0 sits AT the radius
+            below = _check(g, vals, q, float(np.nextafter(r5, -np.inf)), metric, p)
+            assert below[0][1] == at[0][1] - int((vals[0] == r5).sum())
+            every = _check(g, vals, q, math.inf, metric, p)
+            assert (np.diff(every[0]) == n).all()
+            none = _check(g, vals, q, float(np.nextafter(vals.min(), -np.inf)) if vals.min() > 0 else 0.0, metric, p)
+            assert vals.min() == 0 or none[0][-1] == 0
+
+
+def test_empty_and_full_query_in_one_call_and_zero_radius(lib):
+    """a query far away beside queries among the rows; radius 0 on a gallery with duplicated rows finds the row and its copies"""
+    n, d = 2500, 19
+    rows = _wide(3, n, d)
+    rows[[300, 2049, 2499]] = rows[7]
+    rows[256] = rows[255]
+    q = np.concatenate([rows[[7, 255, 1000]], np.full((1, d), 3e30, np.float32)])
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+        for metric, p in EXACT + (("lp", 0.5), ("lp", 3)):
+            lims, ids, dist, dist64, _ = g.range_search_minkowski(q, 0.0, metric, p)
+            assert lims.tolist() == [0, 4, 6, 7, 7] and ids.tolist() == [7, 300, 2049, 2499, 255, 256, 1000]
+            assert (dist64 == 0).all() and not np.signbit(dist64).any()
+        vals = T.values(rows, q, "l1")
+        big = float(vals[:3].max())
+        assert vals[3].min() > big
+        got = _check(g, vals, q, big, "l1", None)
+        assert np.diff(got[0]).tolist()[3] == 0 and n in np.diff(got[0]).tolist()
+        one = _check(g, vals[2:], q[2:], 0.0, "l1", None)                               # (a query with one hit)
+        assert one[0].tolist() == [0, 1, 1]
+
+
+def test_ties_order_and_the_merge_passes(lib):
+    """integer-lattice rows: a few values shared by thousands of rows, ids ascending inside a tie class; query 0 has more hits than
+    one LDS-sorted run of the ordering kernel (the length is read from the source), so its list goes through the merge passes,
+    beside a query with no hit and one with a single hit"""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "image-search-engine-for-historical-research_amd",
+                            "csrc", "minkowski_range.hip")).read()
+    run = int(re.search(r"constexpr int MINK_RANGE_RUN = (\d+);", src).group(1))
+    n, d = 4 * run + 37, 12
+    rows = _lattice(4, n, d)
+    q = _lattice(5, QT + 1, d)
+    q[1] = 50.0                                                                       # no hit
+    q[2] = 9.0
+    rows[n - 3] = 9.0                                                                 # one hit, at 0
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+        for metric, p in EXACT:
+            vals = T.values(rows, q, metric, p)
+            radius = float(np.sort(vals[0])[3 * run + 5])
+            got = _check(g, vals, q, radius, metric, p)
+            cnt = np.diff(got[0])
+            assert cnt[0] > 3 * run and cnt[1] == 0 and cnt[2] == 1 and got[1][got[0][2]] == n - 3
+            ids0, d0 = got[1][:cnt[0]], got[3][:cnt[0]]
+            assert np.unique(d0).size < 40
+            for v in np.unique(d0):
+                assert (np.diff(ids0[d0 == v]) > 0).all()
+            _check(g, vals, q, math.inf, metric, p)
+
+
+LP_K = 24
+
+
+@pytest.mark.parametrize("p", [0.5, 3])
+def test_lp_classes_against_the_reference(lib, p):
+    from test_gpu_minkowski import LP_CAP, LP_MEASURED
+    tol = 8 * LP_MEASURED[p]
+    assert tol <= LP_CAP
+    n, d = 2500, 100
+    rows, q = _gauss(100, n, d), _gauss(200, 5, d)
+    rid, rval = T.lp_reference_topk(rows, q, p, LP_K)
+    gap = T.min_relative_gap(rval)
+    assert gap >= 1e-9, "the reference's own values lie %.3g apart: pick another seed" % gap
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+        for i in range(q.shape[0]):
+            for k in (1, LP_K):                                                # the radius between the k-th and the (k + 1)-th value
+                radius = 0.5 * (rval[i, k - 1] + rval[i, k])
+                lims, ids, dist, dist64, _ = g.range_search_minkowski(q, radius, "lp", p)
+                mine, val = ids[lims[i]:lims[i + 1]], dist64[lims[i]:lims[i + 1]]
+                assert np.array_equal(mine, rid[i, :k])
+                dev = float((np.abs(val - rval[i, :k]) / rval[i, :k]).max())
+                print("lp p=%s query %d k=%d: max relative deviation %.3g (tolerance %.3g)" % (p, i, k, dev, tol))
+                assert dev <= tol
+                assert np.array_equal(dist, dist64.astype(np.float32))
+
+
+def test_l2_gallery_gives_the_bits_of_search_l2(lib):
+    n, d, nq = 500, 259, QT + 1
+    rows, q = _wide(6, n, d), _wide(7, nq, d)
+    vals = T.values(rows, q, "lp", 2)
+    with lib.Gallery.l2_from_host(rows) as g:
+        for radius in (_kth(vals, 0, 5), _kth(vals, 1, 200), math.inf):
+            got = _check(g, vals, q, radius, "lp", 2)                          # (only the caller's d columns count)
+            ids, _, dist64 = g.search_l2(q, n)[:3]
+            for i in range(nq):
+                seg = slice(got[0][i], got[0][i + 1])
+                m = seg.stop - seg.start
+                assert np.array_equal(got[1][seg], ids[i, :m]) and np.array_equal(_bits(got[3][seg]), _bits(dist64[i, :m]))
+        for metric, p in EXACT:
+            v = T.values(rows, q, metric, p)
+            _check(g, v, q, _kth(v, 0, 30), metric, p)
+
+
+def test_norm_l2_gallery_uses_the_stored_rows(lib):
+    n, d = 700, 45
+    unit, q = _gauss(8, n, d), _gauss(9, 3, d)
+    with lib.Gallery.from_host(unit, norm_mode=lib.NORM_L2) as g:
+        stored = g.get_rows(0, n)
+        assert not np.array_equal(stored, unit)
+        for metric, p in EXACT:
+            vals = T.values(stored, q, metric, p)
+            _check(g, vals, q, _kth(vals, 0, 50), metric, p)
+
+
+def _raw(lib, g, q, radius, cap, metric=1, p=0.0, null=False, nq=None):
+    """mi_range_search_minkowski with sentinel-filled outputs -> (rc, lims, idx, dist, dist64)"""
+    lims = np.full(q.shape[0] + 1, -9, np.int64)
+    idx, dist, dist64 = np.full(cap + 1, -7, np.int64), np.full(cap + 1, -7, np.float32), np.full(cap + 1, -7, np.float64)
+    P = lambda a: None if null else a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    rc = lib.load().mi_range_search_minkowski(g._h, q.ctypes.data_as(C.c_void_p), q.shape[0] if nq is None else nq, 0, q.shape[1], 1,
+                                              metric, p, radius, None, 0, cap, lims.ctypes.data_as(C.c_void_p), P(idx), P(dist),
+                                              P(dist64), None)
+    return rc, lims, idx, dist, dist64
+
+
+def test_capacity_protocol(lib):
+    n, d, nq = 2100, 11, QT + 1
+    rows, q = _wide(10, n, d), _wide(11, nq, d)
+    vals = T.values(rows, q, "l1")
+    radius = _kth(vals, 0, 40)
+    want = R.csr(vals, radius)
+    total = int(want[0][-1])
+    assert total > nq
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+        rc, lims, idx, dist, dist64 = _raw(lib, g, q, radius, total - 1)
+        assert rc == lib.MI_ERR_CAPACITY and np.array_equal(lims, want[0])
+        assert (idx == -7).all() and (dist == -7).all() and (dist64 == -7).all()
+        rc, lims, idx, dist, dist64 = _raw(lib, g, q, radius, total)
+        assert rc == 0 and np.array_equal(lims, want[0]) and np.array_equal(idx[:total], want[1])
+        assert np.array_equal(_bits(dist64[:total]), _bits(want[2])) and idx[total] == -7 and dist64[total] == -7
+        rc, lims = _raw(lib, g, q, radius, 0, null=True)[:2]
+        assert rc == lib.MI_ERR_CAPACITY and np.array_equal(lims, want[0])
+        rc, lims = _raw(lib, g, q, float(np.nextafter(vals.min(), -np.inf)), 0, null=True)[:2]
+        assert rc == 0 and (lims == 0).all()                                   # no hit: no array is needed
+        rc, lims, idx = _raw(lib, g, q, radius, 5, nq=0)[:3]
+        assert rc == 0 and lims[0] == 0 and (lims[1:] == -9).all() and (idx == -7).all()
+        for bad in (math.nan, -1.0):
+            assert _raw(lib, g, q, bad, 5)[0] == lib.MI_ERR_INVALID
+        # the binding retries once at the reported size
+        _same(g.range_search_minkowski(q, radius, "l1", max_results=3), want)
+        _same(g.range_search_minkowski(q, radius, "l1", max_results=total), want)
+
+
+def _device(g, q, radius, cap, metric, p, allow_words=None):
+    import torch
+    nq = q.shape[0]
+    side = torch.cuda.Stream()
+    tq = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).cuda()
+    lims = torch.full((nq + 1,), -9, dtype=torch.int64, device="cuda")
+    idx = torch.full((cap + 1,), -7, dtype=torch.int64, device="cuda")
+    d32 = torch.full((cap + 1,), -7, dtype=torch.float32, device="cuda")
+    d64 = torch.full((cap + 1,), -7, dtype=torch.float64, device="cuda")
+    ta = None if allow_words is None else torch.from_numpy(np.ascontiguousarray(allow_words).view(np.int64)).cuda()
+    torch.cuda.synchronize()
+    g.range_search_minkowski_device(tq.data_ptr(), nq, radius, cap, lims.data_ptr(), idx.data_ptr(), metric, p,
+                                    None if ta is None else ta.data_ptr(), d32.data_ptr(), d64.data_ptr(), side.cuda_stream)
+    side.synchronize()
+    torch.cuda.synchronize()
+    return lims.cpu().numpy(), idx.cpu().numpy(), d32.cpu().numpy(), d64.cpu().numpy()
+
+
+def test_device_form_on_a_side_stream(lib):
+    n, d, nq = 4100, 13, 2 * QT + 1
+    rows, q = _wide(12, n, d), _wide(13, nq, d)
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+        for metric, p in (("l1", None), ("lp", 2), ("lp", 0.5)):
+            vals = T.values(rows, q, metric, p)
+            for radius in (_kth(vals, 0, 30), _kth(vals, 3, 2500)):           # (the second: lists beyond one sorted run)
+                host = g.range_search_minkowski(q, radius, metric, p)
+                total = int(host[0][-1])
+                lims, idx, d32, d64 = _device(g, q, radius, total - 1, metric, p)
+                assert np.array_equal(lims, host[0]) and (idx == -7).all() and (d32 == -7).all() and (d64 == -7).all()
+                lims, idx, d32, d64 = _device(g, q, radius, total + 3, metric, p)
+                assert np.array_equal(lims, host[0]) and np.array_equal(idx[:total], host[1])
+                assert np.array_equal(d32[:total], host[2]) and np.array_equal(_bits(d64[:total]), _bits(host[3]))
+                assert (idx[total:] == -7).all() and (d64[total:] == -7).all()
+            lims = _device(g, q, _kth(vals, 0, 30), 0, metric, p)[0]
+            assert lims[-1] > 0                                                # capacity 0: the counts alone
+        import torch
+        one = torch.full((1,), -9, dtype=torch.int64, device="cuda")
+        g.range_search_minkowski_device(0, 0, 1.0, 0, one.data_ptr(), 0, "l1", stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert one.item() == 0                                                 # nq == 0: lims[0]
+
+
+def test_allow_bitmap_row_offset_and_chunking(lib):
+    n, d, nq, off = 4100, 21, 17, 1000
+    rows, q = _wide(14, n, d), _wide(15, nq, d)
+    mask = np.arange(n) % 3 == 0
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE, row_offset=off) as g:
+        answers = {}
+        for metric, p in EXACT:
+            vals = T.values(rows, q, metric, p)
+            radius = _kth(vals, 0, 90)
+            plain = _check(g, vals, q, radius, metric, p, off=off)
+            assert plain[1].min() >= off
+            host = _check(g, vals, q, radius, metric, p, allow=mask, mask=mask, off=off)
+            _check(g, vals, q, radius, metric, p, allow=np.flatnonzero(mask) + off, mask=mask, off=off)      # global ids
+            empty = _check(g, vals, q, math.inf, metric, p, allow=np.zeros(n, bool), mask=np.zeros(n, bool), off=off)
+            assert empty[0][-1] == 0
+            total = int(host[0][-1])
+            lims, idx, d32, d64 = _device(g, q, radius, total, metric, p, lib.allow_bitmap(mask, n))           # the device bitmap
+            assert np.array_equal(lims, host[0]) and np.array_equal(idx[:total], host[1])
+            assert np.array_equal(_bits(d64[:total]), _bits(host[3]))
+            answers[(metric, p)] = (radius, plain, host, g.range_search_minkowski(q, math.inf, metric, p))
+        # 17 queries in three chunks of one scan tile: the same answer, host and device form
+        try:
+            lib.set_global_option("minkowski_range_bytes", 1)
+            for (metric, p), (radius, plain, host, every) in answers.items():
+                L.same(g.range_search_minkowski(q, radius, metric, p)[:4], plain[:4], "chunked %s %s" % (metric, p))
+                L.same(g.range_search_minkowski(q, radius, metric, p, allow=mask)[:4], host[:4], "chunked, bitmap %s %s" % (metric, p))
+                L.same(g.range_search_minkowski(q, math.inf, metric, p)[:4], every[:4], "chunked, every row %s %s" % (metric, p))
+                total = int(plain[0][-1])
+                lims, idx, d32, d64 = _device(g, q, radius, total, metric, p)
+                assert np.array_equal(lims, plain[0]) and np.array_equal(idx[:total], plain[1])
+                assert np.array_equal(_bits(d64[:total]), _bits(plain[3]))
+                lims, idx = _device(g, q, radius, total - 1, metric, p)[:2]
+                assert np.array_equal(lims, plain[0]) and (idx == -7).all()
+        finally:
+            lib.set_global_option("minkowski_range_bytes", 0)
+        assert lib.get_global_option("minkowski_range_bytes") == 256 << 20
+
+
+def test_after_append_and_remove(lib):
+    n, d = 2300, 18
+    rows, more, q = _wide(16, n, d), _wide(17, 300, d), _wide(18, 3, d)
+    g = lib.Gallery.l2_from_host(rows, capacity=n + 300)
+    try:
+        now = rows
+        for step in range(3):
+            for metric, p in EXACT:
+                vals = T.values(now, q, metric, p)
+                _check(g, vals, q, _kth(vals, 0, 60), metric, p)
+            if step == 0:
+                now = rows[g.remove(np.random.default_rng(19).choice(n, 700, replace=False))]
+            elif step == 1:
+                g.append(more)
+                now = np.concatenate([now, more])
+    finally:
+        g.close()
+
+
+def test_self_join_equals_the_search_with_the_rows_as_queries(lib):
+    n, d = 700, 9
+    rows = _lattice(20, n, d, -2, 3)
+    rows[256] = rows[255]                                                      # copies across a scan-block boundary
+    rows[300] = rows[10]
+    rows[699] = rows[256]
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+        for chunk_bytes in (0, 1):
+            try:
+                lib.set_global_option("minkowski_range_bytes", chunk_bytes)
+                for row0, nrows in ((0, 700), (1, 13), (255, 3), (256, 300), (300, 399), (699, 1)):
+                    for metric, p, radius in (("l1", None, 6.0), ("linf", None, 1.0), ("lp", 2, 9.0), ("lp", 2, 0.0), ("lp", 0.5, 0.0)):
+                        lims, ids, dist, dist64, _ = g.self_range_minkowski(row0, nrows, radius, metric, p)
+                        full = g.range_search_minkowski(rows[row0:row0 + nrows], radius, metric, p)
+                        qi = np.repeat(np.arange(row0, row0 + nrows), np.diff(full[0]))
+                        keep = full[1] > qi
+                        want_lims = np.concatenate([[0], np.cumsum(np.bincount(qi[keep] - row0, minlength=nrows))])
+                        what = "row0=%d nrows=%d %s p=%s radius=%s" % (row0, nrows, metric, p, radius)
+                        assert np.array_equal(lims, want_lims), what
+                        assert np.array_equal(ids, full[1][keep]) and np.array_equal(_bits(dist64), _bits(full[3][keep])), what
+                        assert np.array_equal(dist, full[2][keep]), what
+                        if radius == 0.0 and row0 == 0:                        # every planted copy once
+                            found = set(zip(np.repeat(np.arange(n), np.diff(lims)).tolist(), ids.tolist()))
+                            assert {(255, 256), (255, 699), (256, 699), (10, 300)} <= found
+                            same = (rows[:, None, :] == rows[None, :, :]).all(axis=2)
+                            assert len(found) == int(np.triu(same, 1).sum()) == lims[-1]
+                vals = T.values(rows, rows[5:400], "l1")
+                want = R.csr(vals, 5.0, above=np.arange(5, 400))
+                _same(g.self_range_minkowski(5, 395, 5.0, "l1"), want)
+            finally:
+                lib.set_global_option("minkowski_range_bytes", 0)
+        L_ = lib.load()
+        lims, idx = np.full(4, -9, np.int64), np.full(8, -7, np.int64)
+        P = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+        assert L_.mi_minkowski_self_range(g._h, 698, 3, 1, 0.0, 1.0, 8, P(lims), P(idx), None, None, None) == lib.MI_ERR_INVALID
+        assert L_.mi_minkowski_self_range(g._h, 701, 0, 1, 0.0, 1.0, 8, P(lims), P(idx), None, None, None) == lib.MI_ERR_INVALID
+        assert (lims == -9).all()
+        assert L_.mi_minkowski_self_range(g._h, 700, 0, 1, 0.0, 1.0, 8, P(lims), P(idx), None, None, None) == 0
+        assert lims[0] == 0 and (lims[1:] == -9).all() and (idx == -7).all()       # nrows == 0: MI_OK
+
+
+def test_near_duplicate_pairs(lib):
+    from isehr_amd.dedup import near_duplicate_pairs_minkowski
+    n, d = 600, 40
+    rng = np.random.default_rng(21)
+    rows = _gauss(22, n, d)
+    src, dst = rng.choice(300, 20, replace=False), 300 + rng.choice(300, 20, replace=False)
+    rows[dst] = rows[src] + (rng.standard_normal((20, d)) * 1e-3).astype(np.float32)
+    for metric, p, radius in (("lp", 2, 1e-3), ("l1", None, 0.2), ("linf", None, 0.01)):
+        vals = T.values(rows, rows, metric, p)
+        want_pairs, want_dist = R.pairs(vals, radius)
+        assert {tuple(x) for x in want_pairs.tolist()} == set(zip(src.tolist(), dst.tolist()))
+        with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+            for batch in (64, 1024):
+                pairs, dist64 = near_duplicate_pairs_minkowski(g, radius, metric, p, batch=batch)
+                assert pairs.dtype == np.int64 and pairs.shape == (20, 2) and dist64.dtype == np.float64
+                assert np.array_equal(pairs, want_pairs) and np.array_equal(_bits(dist64), _bits(want_dist))
+                assert (pairs[:, 0] < pairs[:, 1]).all() and len({tuple(x) for x in pairs.tolist()}) == 20
+    with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:                # the defaults: squared L2
+        pairs, _ = near_duplicate_pairs_minkowski(g, 1e-3)
+        assert np.array_equal(pairs, R.pairs(T.values(rows, rows, "lp", 2), 1e-3)[0])
+
+
+def test_knn_radius_search(lib):
+    from isehr_amd.knn import KNN
+    n, d = 1200, 30
+    x, q = _wide(23, n, d), _wide(24, 5, d)
+    for method, metric, p in (("euclidean", "lp", 2), ("l1", "l1", None)):
+        vals = T.values(x, q, metric, p)
+        knn = KNN(x, method)
+        try:
+            for radius in (_kth(vals, 0, 25), 0.0, math.inf):
+                want = R.csr(vals, radius)
+                lims, dist, ids = knn.radius_search(q, radius)
+                assert np.array_equal(lims, want[0]) and np.array_equal(ids, want[1])
+                assert dist.dtype == np.float32 and np.array_equal(dist, want[2].astype(np.float32))
+                for i in range(5):
+                    assert (np.diff(dist[lims[i]:lims[i + 1]].astype(np.float64)) >= 0).all()
+            with pytest.raises(NotImplementedError):
+                knn.range_search(q, 1.0)
+        finally:
+            knn.close()
+
+
+def test_query_layouts_give_the_contiguous_answer(lib):
+    n = 700
+    for nq, d in ((7, 5), (QT + 1, 37)):
+        rows, q = _wide(26, n, d), _wide(27, nq, d)
+        with lib.Gallery.from_host(rows, norm_mode=lib.NORM_NONE) as g:
+            for metric, p in (("l1", None), ("lp", 2)):
+                radius = _kth(T.values(rows, q, metric, p), 0, 20)
+                call = lambda x: g.range_search_minkowski(x, radius, metric, p)[:4]   # noqa: E731
+                want = call(q)
+                assert want[0][-1] >= 20
+                for lay in L.layouts(q, np.nan, bcast=True):
+                    ref = want if lay.name != "bcast32" else call(L.expected(lay, q))
+                    L.same(call(lay.view), ref, "%s p=%s, %d x %d, %s" % (metric, p, nq, d, lay.name))
+                q64 = L.beyond_float32(q, [0, nq - 1], [0, d - 1])
+                L.same(call(q64), want, "%s p=%s, %d x %d, float64 beyond float32" % (metric, p, nq, d))
