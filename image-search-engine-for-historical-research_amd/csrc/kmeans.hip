@@ -3,10 +3,8 @@
 // found by a filter, a certificate and an exact fallback:
 //
 //   km_sqnorm_*_kernel      sum_j double(v_j)^2 of every row of X (xn2) and of every centroid (cn); km_max_kernel: max_c cn[c]
-//   km_assign_mfma_kernel   e[i][c] = cn[c] - 2 x_i . c, the expanded form without its row constant, as an f64 GEMM.  The main loop is
-//                           lsh_encode_kernel's (lsh.hip), copied so that lsh.hip and whiten.hip stay as they are: 128 x 128 outputs
-//                           per 256-thread workgroup = 4 waves x 4 x 4 blocks of v_mfma_f64_16x16x4_f64, K in chunks of 16 through
-//                           double-buffered LDS rows of 18 doubles, X promoted to double on load, XCD-aware tile order; B is the
+//   km_assign_mfma_kernel   e[i][c] = cn[c] - 2 x_i . c, the expanded form without its row constant, as an f64 GEMM.  On the 128 x 128 tile of
+//                           f64_tile.h (geometry, K chunks through LDS, XCD-aware tile order), X promoted to double on load; B is the
 //                           centroid table, float32 in memory, promoted to double on load.  The products never leave the registers:
 //                           the epilogue keeps per row (lowest e, its centroid, second lowest e) over the workgroup's 128 columns --
 //                           4 columns in the lane, 16 lanes by shuffles, the two column waves through LDS -- and writes ONE triple per
@@ -20,17 +18,12 @@
 // The list's order is the order the atomics landed in and shows in no result: every listed row is recomputed on its own.
 #include <algorithm>
 
+#include "f64_tile.h"
 #include "kernels.h"
 #include "pq_device.h"
 
 namespace mi {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KM_TILE = 128;         // rows and centroids per workgroup
-constexpr int KM_KC = 16;            // K-chunk staged in LDS
-constexpr int KM_LD = KM_KC + 2;     // LDS row stride in doubles: 18 r mod 32 is a different even slot for each of 16 rows
-constexpr int KM_PER = KM_TILE * KM_KC / 256;   // elements of one operand chunk per thread (8)
 constexpr int KM_EXACT_GRID = 2048;  // workgroups of km_exact_rows_kernel, whatever the list holds
 
 // ---- the certificate.  With u = 2^-53, gamma = (d + 3) u / (1 - (d + 3) u), xn >= ||x|| and cmax >= max_c ||c||: the direct form
@@ -123,62 +116,54 @@ __global__ __launch_bounds__(256, 2) void km_assign_mfma_kernel(const InT* __res
                                                                 int32_t* __restrict__ Wi, int64_t wstride, uint32_t ncb, uint32_t nrb) {
   extern __shared__ __attribute__((aligned(16))) double km_lds[];
   double* const Xs0 = km_lds;
-  double* const Ps0 = km_lds + 2 * KM_TILE * KM_LD;
-  const uint32_t b = blockIdx.x;
+  double* const Ps0 = km_lds + 2 * F64T_BUF;
   uint32_t cb, rt;
-  if ((ncb & 7u) == 0) {                                    // XCD x owns the column blocks x, x + 8, ..: its slab of C stays in its L2
-    const uint32_t x = b & 7u, j = b >> 3;
-    cb = x + 8u * (j / nrb);
-    rt = j % nrb;
-  } else {
-    cb = b % ncb;
-    rt = b / ncb;
-  }
+  f64t_tile_order(blockIdx.x, ncb, nrb, &cb, &rt);
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int wr = w >> 1, wc = w & 1, l15 = lane & 15, lq = lane >> 4;
-  const int64_t row0 = (int64_t)rt * KM_TILE;
-  const int32_t col0 = (int32_t)cb * KM_TILE;
+  const int64_t row0 = (int64_t)rt * F64T_TILE;
+  const int32_t col0 = (int32_t)cb * F64T_TILE;
   // element i of this thread in an operand chunk: X (r, kk) = (xr0 + 16 i, xk0) (ROWS) or (xr0 + 64 (i & 1), xk0 + 4 (i >> 1));
   // C (pj0 + 16 i, pk)
-  const int xr0 = ROWS ? t / KM_KC : t % 64, xk0 = ROWS ? t % KM_KC : t / 64;
-  auto x_r = [&](int i) { return ROWS ? xr0 + (256 / KM_KC) * i : xr0 + 64 * (i & 1); };
+  const int xr0 = ROWS ? t / F64T_KC : t % 64, xk0 = ROWS ? t % F64T_KC : t / 64;
+  auto x_r = [&](int i) { return ROWS ? xr0 + F64T_RSTEP * i : xr0 + 64 * (i & 1); };
   auto x_k = [&](int i) { return ROWS ? xk0 : xk0 + 4 * (i >> 1); };
-  const int pj0 = t / KM_KC, pk = t % KM_KC;
-  const bool interior = row0 + KM_TILE <= n && col0 + KM_TILE <= k;
+  const int pj0 = t / F64T_KC, pk = t % F64T_KC;
+  const bool interior = row0 + F64T_TILE <= n && col0 + F64T_TILE <= k;
   const InT* xp0 = X + (row0 + xr0) * rs + (int64_t)xk0 * cs;
   const float* pp0 = Cb + (int64_t)(col0 + pj0) * d + pk;
 
-  InT xr[KM_PER];
-  float pr[KM_PER];
+  InT xr[F64T_PER];
+  float pr[F64T_PER];
   bool fast = false;                                        // the chunk in the registers lies inside X and C: no masking
   auto load_chunk = [&](int32_t k0) {
-    fast = interior && k0 + KM_KC <= d;
+    fast = interior && k0 + F64T_KC <= d;
     if (fast) {
       const InT* xp = xp0 + (int64_t)k0 * cs;
       const float* pp = pp0 + k0;
 #pragma unroll
-      for (int i = 0; i < KM_PER; ++i) {
-        xr[i] = ROWS ? xp[(int64_t)(256 / KM_KC) * i * rs] : xp[(int64_t)(64 * (i & 1)) * rs + (int64_t)(4 * (i >> 1)) * cs];
-        pr[i] = pp[(int64_t)(256 / KM_KC) * i * d];
+      for (int i = 0; i < F64T_PER; ++i) {
+        xr[i] = ROWS ? xp[(int64_t)F64T_RSTEP * i * rs] : xp[(int64_t)(64 * (i & 1)) * rs + (int64_t)(4 * (i >> 1)) * cs];
+        pr[i] = pp[(int64_t)F64T_RSTEP * i * d];
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < KM_PER; ++i) {
+      for (int i = 0; i < F64T_PER; ++i) {
         const int64_t row = row0 + x_r(i);
         const int32_t kk = k0 + x_k(i);
         xr[i] = (row < n && kk < d) ? X[row * rs + (int64_t)kk * cs] : (InT)0;
-        const int32_t pj = col0 + pj0 + (256 / KM_KC) * i;
+        const int32_t pj = col0 + pj0 + F64T_RSTEP * i;
         pr[i] = (pj < k && k0 + pk < d) ? Cb[(int64_t)pj * d + k0 + pk] : 0.0f;
       }
     }
   };
   auto store_chunk = [&](int buf) {
-    double* const Xs = Xs0 + buf * KM_TILE * KM_LD;
-    double* const Ps = Ps0 + buf * KM_TILE * KM_LD;
+    double* const Xs = Xs0 + buf * F64T_BUF;
+    double* const Ps = Ps0 + buf * F64T_BUF;
 #pragma unroll
-    for (int i = 0; i < KM_PER; ++i) {
-      Xs[x_r(i) * KM_LD + x_k(i)] = (double)xr[i];          // padded rows / k were loaded as zero
-      Ps[(pj0 + (256 / KM_KC) * i) * KM_LD + pk] = (double)pr[i];
+    for (int i = 0; i < F64T_PER; ++i) {
+      Xs[x_r(i) * F64T_LD + x_k(i)] = (double)xr[i];          // padded rows / k were loaded as zero
+      Ps[(pj0 + F64T_RSTEP * i) * F64T_LD + pk] = (double)pr[i];
     }
   };
 
@@ -188,34 +173,21 @@ __global__ __launch_bounds__(256, 2) void km_assign_mfma_kernel(const InT* __res
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = (f64x4){0.0, 0.0, 0.0, 0.0};
 
-  const int xa_off = (wr * 64 + l15) * KM_LD + lq;          // A[i = lane & 15][k = lane >> 4]
-  const int pb_off = (wc * 64 + l15) * KM_LD + lq;          // B[k = lane >> 4][j = lane & 15] = C[j][k]
+  const int xa_off = (wr * 64 + l15) * F64T_LD + lq;          // A[i = lane & 15][k = lane >> 4]
+  const int pb_off = (wc * 64 + l15) * F64T_LD + lq;          // B[k = lane >> 4][j = lane & 15] = C[j][k]
   auto mfma_steps = [&](int buf, int ks0, int ks1) {
-    const double* xa = Xs0 + buf * KM_TILE * KM_LD + xa_off;
-    const double* pb = Ps0 + buf * KM_TILE * KM_LD + pb_off;
-#pragma unroll
-    for (int ks = ks0; ks < ks1; ++ks) {
-      double a[4], bb[4];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) a[mi] = xa[mi * 16 * KM_LD + ks * 4];
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) bb[ni] = pb[ni * 16 * KM_LD + ks * 4];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bb[ni], acc[mi][ni], 0, 0, 0);
-    }
+    f64t_mfma_steps(acc, Xs0 + buf * F64T_BUF + xa_off, Ps0 + buf * F64T_BUF + pb_off, ks0, ks1);
   };
   load_chunk(0);
   store_chunk(0);
   __syncthreads();
   int buf = 0;
-  for (int32_t k0 = 0; k0 < d; k0 += KM_KC, buf ^= 1) {
-    const bool more = k0 + KM_KC < d;
-    if (more) load_chunk(k0 + KM_KC);                       // in flight under the first three quarters of this chunk's MFMAs
+  for (int32_t k0 = 0; k0 < d; k0 += F64T_KC, buf ^= 1) {
+    const bool more = k0 + F64T_KC < d;
+    if (more) load_chunk(k0 + F64T_KC);                       // in flight under the first three quarters of this chunk's MFMAs
     mfma_steps(buf, 0, 3);
     if (more) store_chunk(buf ^ 1);                         // the other buffer: nobody reads it before the barrier below
-    mfma_steps(buf, 3, KM_KC / 4);
+    mfma_steps(buf, 3, F64T_KC / 4);
     __syncthreads();                                        // chunk c + 1 is complete, chunk c's fragments are done with
   }
 
@@ -395,13 +367,13 @@ static void sqnorm_launch(const void* x, int dtype, int64_t n, int32_t d, int64_
 
 KmWorkspace km_workspace(void* base, int64_t bytes, int32_t k) {
   KmWorkspace w;
-  const int64_t ncb = (k + KM_TILE - 1) / KM_TILE;
+  const int64_t ncb = (k + F64T_TILE - 1) / F64T_TILE;
   const int64_t head = ((int64_t)k * 8 + 8 + 8 + 255) / 256 * 256;          // cn, cmax2, count
   const int64_t per_row = 8 + 4 + ncb * (8 + 8 + 4);                        // xn2, list, the triples
-  int64_t rows = bytes > head ? (bytes - head) / per_row / KM_TILE * KM_TILE : 0;
+  int64_t rows = bytes > head ? (bytes - head) / per_row / F64T_TILE * F64T_TILE : 0;
   rows = std::min<int64_t>(rows, (int64_t)1 << 22);                         // the grids stay far below 2^31
   w.rows = rows;
-  if (rows < KM_TILE) return w;
+  if (rows < F64T_TILE) return w;
   char* p = (char*)base;
   w.cn = (double*)p;
   w.cmax2 = w.cn + k;
@@ -420,9 +392,9 @@ KmWorkspace km_workspace(void* base, int64_t bytes, int32_t k) {
 }
 
 int64_t km_workspace_bytes(int32_t k, int64_t rows) {
-  const int64_t ncb = (k + KM_TILE - 1) / KM_TILE;
+  const int64_t ncb = (k + F64T_TILE - 1) / F64T_TILE;
   const int64_t head = ((int64_t)k * 8 + 8 + 8 + 255) / 256 * 256;
-  const int64_t r = (rows + KM_TILE - 1) / KM_TILE * KM_TILE;
+  const int64_t r = (rows + F64T_TILE - 1) / F64T_TILE * F64T_TILE;
   return head + r * (8 + 4 + ncb * 20) + 256;
 }
 
@@ -430,27 +402,19 @@ template <typename OutT>
 static void assign_launch(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, int64_t cs, const float* cb, int32_t k, OutT* out,
                           unsigned long long* total, const KmWorkspace& w, hipStream_t stream) {
   if (n <= 0) return;
-  const uint32_t ncb = (uint32_t)((k + KM_TILE - 1) / KM_TILE);
-  const int lds = 4 * KM_TILE * KM_LD * (int)sizeof(double);          // X and C, two buffers each
+  const uint32_t ncb = (uint32_t)((k + F64T_TILE - 1) / F64T_TILE);
   const size_t esz = dtype == 0 ? 4 : 8;
   sqnorm_launch(cb, 0, k, d, d, 1, w.cn, stream);
   km_max_kernel<<<1, 256, 0, stream>>>(w.cn, k, w.cmax2);
   for (int64_t r0 = 0; r0 < n; r0 += w.rows) {
     const int64_t nn = std::min(w.rows, n - r0);
-    const uint32_t nrb = (uint32_t)((nn + KM_TILE - 1) / KM_TILE);
-    const dim3 grid(ncb * nrb), block(256);
+    const uint32_t nrb = (uint32_t)((nn + F64T_TILE - 1) / F64T_TILE);
+    const dim3 grid(ncb * nrb);
     const void* x = (const char*)X + (size_t)r0 * (size_t)rs * esz;
     (void)hipMemsetAsync(w.count, 0, 4, stream);
     sqnorm_launch(x, dtype, nn, d, rs, cs, w.xn2, stream);
-#define MI_KM_LAUNCH(T, ROWS)                                                                                           \
-  do {                                                                                                                  \
-    ensure_dynamic_lds((const void*)km_assign_mfma_kernel<T, ROWS>, lds);                                               \
-    hipLaunchKernelGGL((km_assign_mfma_kernel<T, ROWS>), grid, block, lds, stream, (const T*)x, nn, d, rs, cs, cb, w.cn, k, w.wb, \
-                       w.ws, w.wi, w.rows, ncb, nrb);                                                                   \
-  } while (0)
-    if (dtype == 0) { if (cs == 1) MI_KM_LAUNCH(float, true); else MI_KM_LAUNCH(float, false); }
-    else { if (cs == 1) MI_KM_LAUNCH(double, true); else MI_KM_LAUNCH(double, false); }
-#undef MI_KM_LAUNCH
+    f64t_launch(dtype, cs == 1, MI_F64T_KERNELS(km_assign_mfma_kernel), grid, stream, x, nn, d, rs, cs, cb, w.cn, k, w.wb, w.ws, w.wi,
+                w.rows, ncb, nrb);
     km_fold_kernel<OutT><<<dim3((unsigned)((nn + 255) / 256)), 256, 0, stream>>>(w.wb, w.ws, w.wi, w.rows, nn, (int32_t)ncb, w.xn2,
                                                                                  w.cmax2, d, out + r0, w.list, w.count);
     if (dtype == 0)

@@ -4,10 +4,9 @@
 //   pairs mode  C (+)= sum_i (x_{q_i} - x_{p_i})(x_{q_i} - x_{p_i})^T   over n_pairs index pairs (no centre)
 // It is the whitening GEMM (whiten.hip) turned on its side: the reduction runs over the ROWS of X, both operands come from the
 // same rows (column block ti and column block tj), the output is d x d and symmetric.
-//  * v_mfma_f64_16x16x4_f64, 128 x 128 outputs per 256-thread workgroup = 4 waves x (64 x 64) = 4 x 4 MFMA blocks per wave
-//    (128 accumulator registers), two workgroups per CU -- the geometry of whiten_mfma_kernel;
+//  * the 128 x 128 tile of f64_tile.h (geometry, fragment layout, MFMA steps), two workgroups per CU;
 //  * the rows stream in chunks of 16: both 16 x 128 operand chunks are promoted to f64 and centred ((double)x - c[col]; pairs:
-//    (double)x_q - (double)x_p) ON LOAD and stored [col][18] in LDS (row padding of whiten.hip: conflict-free ds_read_b64
+//    (double)x_q - (double)x_p) ON LOAD and stored [col][F64T_LD] in LDS (conflict-free ds_read_b64
 //    fragments); two buffers, one barrier per chunk, the global loads of chunk c + 1 in flight under the MFMAs of chunk c.
 //    Never sum x x^T - n c c^T: that cancels on non-negative descriptors;
 //  * symmetry: only the T = nt (nt + 1) / 2 tiles with ti <= tj are multiplied (nt = ceil(d / 128); 136 of 256 at d = 2048);
@@ -24,24 +23,19 @@
 // consecutive rows of 4 columns per instruction; otherwise 64 consecutive columns of one row (coalesced for cs == 1, correct
 // for any strides).  Pairs mode gathers rows and always takes the second path.
 #include "common.h"
+#include "f64_tile.h"
 #include "kernels.h"
 
 #include <algorithm>
 
 namespace mi {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int S_TILE = 128;          // rows and columns of C per workgroup
-constexpr int S_KC = 16;             // rows of X per chunk staged in LDS
-constexpr int S_LD = S_KC + 2;       // LDS stride in doubles (18 r mod 32: a different even slot for each of 16 rows)
-constexpr int S_PER = S_TILE * S_KC / 256;   // elements of one operand chunk per thread (8)
 constexpr int S_MAX_SPLITS = 16;
-constexpr int64_t S_SLAB = (int64_t)S_TILE * S_TILE;              // doubles per (split, tile)
+constexpr int64_t S_SLAB = (int64_t)F64T_TILE * F64T_TILE;              // doubles per (split, tile)
 constexpr int64_t S_WS_LIMIT = (int64_t)512 << 20;
 
 static inline int64_t scatter_tiles(int32_t d) {
-  const int64_t nt = (d + S_TILE - 1) / S_TILE;
+  const int64_t nt = (d + F64T_TILE - 1) / F64T_TILE;
   return nt * (nt + 1) / 2;
 }
 
@@ -60,9 +54,9 @@ __global__ __launch_bounds__(256, 2) void scatter_mfma_kernel(const InT* __restr
                                                               uint32_t nt, int64_t chunks_per_split,
                                                               double* __restrict__ slabs) {
   extern __shared__ __attribute__((aligned(16))) double s_lds[];
-  double* const As0 = s_lds;                                  // [2][128][18]
-  double* const Bs0 = s_lds + 2 * S_TILE * S_LD;              // [2][128][18]
-  double* const cen = s_lds + 4 * S_TILE * S_LD;              // [2][128]: centre of the columns of tile ti, tile tj
+  double* const As0 = s_lds;                                  // [2][128][F64T_LD]
+  double* const Bs0 = s_lds + 2 * F64T_BUF;              // [2][128][F64T_LD]
+  double* const cen = s_lds + 4 * F64T_BUF;              // [2][128]: centre of the columns of tile ti, tile tj
   const uint32_t tile = blockIdx.x % ntile, split = blockIdx.x / ntile;
   uint32_t ti = 0, rem = tile;
   while (rem >= nt - ti) {
@@ -70,29 +64,29 @@ __global__ __launch_bounds__(256, 2) void scatter_mfma_kernel(const InT* __restr
     ++ti;
   }
   const uint32_t tj = ti + rem;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const int wr = w >> 1, wc = w & 1, l15 = lane & 15, lq = lane >> 4;
-  const int32_t ca0 = (int32_t)ti * S_TILE, cb0 = (int32_t)tj * S_TILE;
-  const int64_t k_begin = (int64_t)split * chunks_per_split * S_KC;
-  const int64_t k_end = min(nk, k_begin + chunks_per_split * S_KC);
+  const F64Lane ln;
+  const int t = ln.t;
+  const int32_t ca0 = (int32_t)ti * F64T_TILE, cb0 = (int32_t)tj * F64T_TILE;
+  const int64_t k_begin = (int64_t)split * chunks_per_split * F64T_KC;
+  const int64_t k_end = min(nk, k_begin + chunks_per_split * F64T_KC);
 
   {
-    const int32_t c = (t < S_TILE ? ca0 : cb0) + (t & (S_TILE - 1));
+    const int32_t c = (t < F64T_TILE ? ca0 : cb0) + (t & (F64T_TILE - 1));
     cen[t] = (!PAIRS && centre && c < d) ? centre[c] : 0.0;
   }
   // element i of this thread in an operand chunk: (k, col) = KSEQ ? (t % 16, t / 16 + 16 i) : (t / 128 + 2 i, t % 128)
-  const int xk0 = KSEQ ? t % S_KC : t / S_TILE, xc0 = KSEQ ? t / S_KC : t % S_TILE;
+  const int xk0 = KSEQ ? t % F64T_KC : t / F64T_TILE, xc0 = KSEQ ? t / F64T_KC : t % F64T_TILE;
   auto x_k = [&](int i) { return KSEQ ? xk0 : xk0 + 2 * i; };
   auto x_c = [&](int i) { return KSEQ ? xc0 + 16 * i : xc0; };
-  const bool cols_inside = cb0 + S_TILE <= d;                  // ca0 <= cb0
+  const bool cols_inside = cb0 + F64T_TILE <= d;                  // ca0 <= cb0
 
-  InT xa[S_PER], xb[S_PER];
-  InT ya[PAIRS ? S_PER : 1], yb[PAIRS ? S_PER : 1];            // pairs: the p row
+  InT xa[F64T_PER], xb[F64T_PER];
+  InT ya[PAIRS ? F64T_PER : 1], yb[PAIRS ? F64T_PER : 1];            // pairs: the p row
   bool fast = false;
   auto load_chunk = [&](int64_t k0) {
-    fast = cols_inside && k0 + S_KC <= k_end;
+    fast = cols_inside && k0 + F64T_KC <= k_end;
 #pragma unroll
-    for (int i = 0; i < S_PER; ++i) {
+    for (int i = 0; i < F64T_PER; ++i) {
       const int64_t k = k0 + x_k(i);
       const int32_t a = ca0 + x_c(i), b = cb0 + x_c(i);
       const bool kin = fast || k < k_end;
@@ -113,10 +107,10 @@ __global__ __launch_bounds__(256, 2) void scatter_mfma_kernel(const InT* __restr
     }
   };
   auto store_chunk = [&](int64_t k0, int buf) {
-    double* const As = As0 + buf * S_TILE * S_LD;
-    double* const Bs = Bs0 + buf * S_TILE * S_LD;
+    double* const As = As0 + buf * F64T_BUF;
+    double* const Bs = Bs0 + buf * F64T_BUF;
 #pragma unroll
-    for (int i = 0; i < S_PER; ++i) {
+    for (int i = 0; i < F64T_PER; ++i) {
       const int kk = x_k(i), c = x_c(i);
       // promoted and centred in float64 exactly like `X - m` / `X[:, q] - X[:, p]` in the reference; padding: zero
       double va, vb;
@@ -125,15 +119,15 @@ __global__ __launch_bounds__(256, 2) void scatter_mfma_kernel(const InT* __restr
         vb = (double)xb[i] - (double)yb[i];
       } else {
         va = (double)xa[i] - cen[c];
-        vb = (double)xb[i] - cen[S_TILE + c];
+        vb = (double)xb[i] - cen[F64T_TILE + c];
       }
       if (!fast) {
         const bool kin = k0 + kk < k_end;
         va = (kin && ca0 + c < d) ? va : 0.0;
         vb = (kin && cb0 + c < d) ? vb : 0.0;
       }
-      As[c * S_LD + kk] = va;
-      Bs[c * S_LD + kk] = vb;
+      As[c * F64T_LD + kk] = va;
+      Bs[c * F64T_LD + kk] = vb;
     }
   };
 
@@ -143,23 +137,10 @@ __global__ __launch_bounds__(256, 2) void scatter_mfma_kernel(const InT* __restr
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = (f64x4){0.0, 0.0, 0.0, 0.0};
 
-  const int a_off = (wr * 64 + l15) * S_LD + lq;           // A[i = lane & 15][k = lane >> 4] = x[k][ca0 + i]
-  const int b_off = (wc * 64 + l15) * S_LD + lq;           // B[k = lane >> 4][j = lane & 15] = x[k][cb0 + j]
+  const int a_off = ln.a_off();                              // A[i = lane & 15][k = lane >> 4] = x[k][ca0 + i]
+  const int b_off = ln.b_off();                              // B[k = lane >> 4][j = lane & 15] = x[k][cb0 + j]
   auto mfma_steps = [&](int buf, int ks0, int ks1) {
-    const double* pa = As0 + buf * S_TILE * S_LD + a_off;
-    const double* pb = Bs0 + buf * S_TILE * S_LD + b_off;
-#pragma unroll
-    for (int ks = ks0; ks < ks1; ++ks) {
-      double a[4], bb[4];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) a[mi] = pa[mi * 16 * S_LD + ks * 4];
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) bb[ni] = pb[ni * 16 * S_LD + ks * 4];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bb[ni], acc[mi][ni], 0, 0, 0);
-    }
+    f64t_mfma_steps(acc, As0 + buf * F64T_BUF + a_off, Bs0 + buf * F64T_BUF + b_off, ks0, ks1);
   };
   if (k_begin < k_end) {
     __syncthreads();                                         // cen[]
@@ -167,25 +148,24 @@ __global__ __launch_bounds__(256, 2) void scatter_mfma_kernel(const InT* __restr
     store_chunk(k_begin, 0);
     __syncthreads();
     int buf = 0;
-    for (int64_t k0 = k_begin; k0 < k_end; k0 += S_KC, buf ^= 1) {
-      const bool more = k0 + S_KC < k_end;
-      if (more) load_chunk(k0 + S_KC);                       // in flight under the first three quarters of this chunk's MFMAs
+    for (int64_t k0 = k_begin; k0 < k_end; k0 += F64T_KC, buf ^= 1) {
+      const bool more = k0 + F64T_KC < k_end;
+      if (more) load_chunk(k0 + F64T_KC);                       // in flight under the first three quarters of this chunk's MFMAs
       mfma_steps(buf, 0, 3);
-      if (more) store_chunk(k0 + S_KC, buf ^ 1);             // the other buffer: nobody reads it before the barrier below
-      mfma_steps(buf, 3, S_KC / 4);
+      if (more) store_chunk(k0 + F64T_KC, buf ^ 1);             // the other buffer: nobody reads it before the barrier below
+      mfma_steps(buf, 3, F64T_KC / 4);
       __syncthreads();
     }
   }
-  // C layout of v_mfma_f64_16x16x4_f64: column = lane & 15, row = (lane >> 4) + 4 * register.  The whole slab is written
-  // (zeros where the tile overhangs d or the split has no rows): the finishing kernel reads every slab of its tile.
+  // The whole slab is written (zeros where the tile overhangs d or the split has no rows): the finishing kernel reads every slab of its tile.
   double* const out = slabs + ((int64_t)split * ntile + tile) * S_SLAB;
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int row = wr * 64 + mi * 16 + lq + 4 * r;
+      const int row = ln.row(mi, r);
 #pragma unroll
-      for (int ni = 0; ni < 4; ++ni) out[row * S_TILE + wc * 64 + ni * 16 + l15] = acc[mi][ni][r];
+      for (int ni = 0; ni < 4; ++ni) out[row * F64T_TILE + ln.col(ni)] = acc[mi][ni][r];
     }
 }
 
@@ -201,10 +181,10 @@ __global__ __launch_bounds__(256) void scatter_finish_kernel(const double* __res
   }
   const uint32_t tj = ti + rem;
   const int i = blockIdx.y * 2 + (threadIdx.x >> 7), j = threadIdx.x & 127;
-  const int64_t gi = (int64_t)ti * S_TILE + i, gj = (int64_t)tj * S_TILE + j;
+  const int64_t gi = (int64_t)ti * F64T_TILE + i, gj = (int64_t)tj * F64T_TILE + j;
   if (gi >= d || gj >= d || gi > gj) return;
   double v = accumulate ? C[gi * d + gj] : 0.0;
-  const double* p = slabs + (int64_t)tile * S_SLAB + i * S_TILE + j;
+  const double* p = slabs + (int64_t)tile * S_SLAB + i * F64T_TILE + j;
   for (int32_t s = 0; s < nsplit; ++s) v += p[(int64_t)s * ntile * S_SLAB];
   C[gi * d + gj] = v;
   C[gj * d + gi] = v;
@@ -214,7 +194,7 @@ __global__ __launch_bounds__(256) void scatter_finish_kernel(const double* __res
 // chunks (256 rows) per workgroup, at most what the workspace holds
 static int scatter_pick_splits(int32_t d, int64_t nk) {
   const int64_t T = scatter_tiles(d), slots = 2 * (int64_t)current_device_cus();
-  const int64_t chunks = (nk + S_KC - 1) / S_KC;
+  const int64_t chunks = (nk + F64T_KC - 1) / F64T_KC;
   const int smax = (int)std::max<int64_t>(1, std::min<int64_t>(scatter_max_splits(d), chunks / 16));
   int best = 1;
   double best_eff = 0.0;
@@ -234,12 +214,12 @@ void launch_scatter(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, 
                     double* workspace, hipStream_t stream) {
   const bool pairs = pair_q != nullptr;
   const int64_t nk = pairs ? n_pairs : n;
-  const uint32_t nt = (uint32_t)((d + S_TILE - 1) / S_TILE), ntile = (uint32_t)scatter_tiles(d);
+  const uint32_t nt = (uint32_t)((d + F64T_TILE - 1) / F64T_TILE), ntile = (uint32_t)scatter_tiles(d);
   const int nsplit = scatter_pick_splits(d, nk);
-  const int64_t chunks = (nk + S_KC - 1) / S_KC;
+  const int64_t chunks = (nk + F64T_KC - 1) / F64T_KC;
   const int64_t cps = (chunks + nsplit - 1) / nsplit;
   const dim3 grid(ntile * (uint32_t)nsplit), block(256);
-  const int lds = (4 * S_TILE * S_LD + 2 * S_TILE) * (int)sizeof(double);
+  const int lds = F64T_LDS_BYTES + 2 * F64T_TILE * (int)sizeof(double);          // and cen[]
 #define MI_S_LAUNCH(T, KSEQ, PAIRS)                                                                                      \
   do {                                                                                                                   \
     ensure_dynamic_lds((const void*)scatter_mfma_kernel<T, KSEQ, PAIRS>, lds);                                           \
@@ -256,7 +236,7 @@ void launch_scatter(const void* X, int dtype, int64_t n, int32_t d, int64_t rs, 
     else MI_S_LAUNCH(double, false, false);
   }
 #undef MI_S_LAUNCH
-  hipLaunchKernelGGL(scatter_finish_kernel, dim3(ntile, S_TILE / 2), block, 0, stream, workspace, ntile, nt, nsplit, d,
+  hipLaunchKernelGGL(scatter_finish_kernel, dim3(ntile, F64T_TILE / 2), block, 0, stream, workspace, ntile, nt, nsplit, d,
                      accumulate, C);
 }
 

@@ -165,6 +165,40 @@ def test_layouts_and_types_give_the_packed_answer(lib):
         assert np.array_equal(lib.kmeans_assign(v, C), ids), name
 
 
+@pytest.mark.parametrize("k", [1000, 1024])
+def test_eight_column_blocks_take_the_xcd_tile_order(lib, k):
+    """k = 1000 and 1024: 8 column blocks (the last ragged at 1000), so km_assign_mfma_kernel decodes its tile by the XCD-aware
+    branch of f64t_tile_order (csrc/f64_tile_order.h); n = 130, d = 33: two row tiles, ragged rows and K.  Lattice rows and
+    centroids (coordinates in {-2 .. 2}): every sum of either form is an integer below 2^53, exact in any order, so the ids are
+    the float64 direct-form argmin whatever the tile a centroid was scored in.  Contiguous float32, [D, N] and float64 rows,
+    typed and device forms."""
+    import torch
+    n, d = 130, 33
+    x, C = lattice(np.random.RandomState(11 + k), n, k, d=d)
+    for a in (x, C):                                           # the precondition: small integers, so every partial sum is exact
+        assert np.array_equal(a, np.rint(a)) and np.abs(a).max() <= 2
+    assert d * (2 + 2) ** 2 < 2 ** 53
+    want = assign_truth(x, C)
+    assert len(np.unique(want // 128)) == 8                    # every column block wins somewhere: a misplaced tile shows
+    x64 = x.astype(np.float64)
+    views = {"float32": x, "[D, N]": np.ascontiguousarray(x.T).T, "float64": x64}
+    assert views["[D, N]"].strides == (4, 4 * n)
+    cd = torch.from_numpy(np.array(C)).cuda()
+    bytes_ = lib.kmeans_assign_workspace_bytes(k, n)
+    for name, v in views.items():
+        assert np.array_equal(lib.kmeans_assign(v, C), want), name
+        t = torch.from_numpy(np.ascontiguousarray(v.T)).cuda().t() if name == "[D, N]" else torch.from_numpy(np.array(v)).cuda()
+        assert tuple(t.stride()) == tuple(s // v.itemsize for s in v.strides)
+        out = torch.full((n,), -7, dtype=torch.int32, device="cuda")
+        ws = torch.empty(bytes_, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        lib.kmeans_assign_device(t.data_ptr(), n, d, cd.data_ptr(), k, out.data_ptr(), ws.data_ptr(), bytes_,
+                                 dtype=lib.MI_F32 if t.dtype == torch.float32 else lib.MI_F64, row_stride=t.stride(0),
+                                 col_stride=t.stride(1), stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy(), want), name
+
+
 def test_the_layout_sweep_of_the_typed_entry_points(lib):
     """every view of tests/_layouts.py (contiguous, [D, N], padded rows, every other column, a sub-block; float32 and float64),
     embedded in buffers whose other elements are NaN, through the three typed entry points: the answer is the contiguous float32

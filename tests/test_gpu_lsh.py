@@ -15,7 +15,9 @@ pytestmark = pytest.mark.gpu
 
 # (n, d, nbits): n and nbits at 1, 127-130 and 257, d at 1, 16, 17 and 2048 -- the edges of the 128 x 128 tile and the 16-wide K chunk
 SHAPES = [(300, 2048, 264), (129, 17, 136), (1, 1, 8), (127, 100, 4096), (257, 2048, 2048), (130, 16, 128)]
-LAYOUT_SHAPES = SHAPES[:2]
+# the last two: 8 column blocks, the XCD-aware tile order of csrc/f64_tile.h, with every loader -- ragged last block, rows and K;
+# then 8 full blocks
+LAYOUT_SHAPES = SHAPES[:2] + [(130, 33, 1000), (129, 32, 1024)]
 
 
 @pytest.fixture(scope="module")
