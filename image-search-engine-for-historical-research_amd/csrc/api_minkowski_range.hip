@@ -4,7 +4,8 @@
 // The queries go in chunks of whole scan tiles whose values and counts fit into "minkowski_range_bytes" (mink_range_plan.h).  Pass 1
 // scans and counts every chunk and leaves the CSR offsets; pass 2 places, orders and writes the hits of one chunk after the other
 // (a call of more than one chunk scans again: the values of a chunk are gone by then).  Kernels: minkowski.hip (the scan, unchanged),
-// minkowski_range.hip (everything behind it).  Nothing is cached: the gallery is searched as it stands.
+// minkowski_range.hip (counts, offsets, placing), csr_order.hip (order and write-out).  Nothing is cached: the gallery is searched as
+// it stands.
 #include "api_internal.h"
 #include "mink_range_plan.h"
 
@@ -96,8 +97,8 @@ int mr_pass2(mi_gallery* g, const MrCall& c, const MrPlan& p, int64_t* lims_dev,
     a.max_results = max_results;
     for (int i = 0; i < 2; ++i) a.key[i] = m.rkey[i], a.row[i] = m.rrow[i];
     launch_mink_range_emit(a, s);
-    const int cur = launch_mink_range_order(a, max_cnt, max_total, s);
-    launch_mink_range_write(a, cur, max_total, g->row_offset, out_idx, out_dist, out_dist64, s);
+    const int cur = launch_csr_order(a, max_cnt, max_total, s);
+    launch_csr_write(a, cur, false, max_total, g->row_offset, out_idx, out_dist, out_dist64, s);
   }
   HIPC(hipGetLastError());
   return MI_OK;

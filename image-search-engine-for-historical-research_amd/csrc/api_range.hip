@@ -140,16 +140,18 @@ static int range_batch(mi_gallery* g, const void* src, int dtype, int64_t rs, in
   int rc;
   if ((rc = grow_all((size_t)total, r.bkey[0], r.brow[0], r.bkey[1], r.brow[1])) != MI_OK) return rc;
   launch_range_gather(r.akey, r.arow, r.coff, r.ccnt, (int32_t)nchunks, QB, nb, r.lims, r.bkey[0], r.brow[0], s);
-  launch_range_sort_runs(r.bkey[0], r.brow[0], r.lims, nb, max_cnt, s);
-  int cur = 0;
-  for (int64_t w = range_run_length(); w < max_cnt; w *= 2) {
-    launch_range_merge(r.bkey[cur], r.brow[cur], r.bkey[cur ^ 1], r.brow[cur ^ 1], r.lims, nb, total, w, s);
-    cur ^= 1;
-  }
-  // the emit staging: the other ping-pong buffer holds total * 12 bytes, enough for the int64 ids (8) + f32 scores (4)
+  // lims[0] is 0 and the total fits `room` (checked above), so the stage's capacity guard never fires here
+  CsrList c;
+  c.nq = nb;
+  c.lims = r.lims;
+  c.total = r.lims + nb;
+  c.max_results = room;
+  for (int i = 0; i < 2; ++i) c.key[i] = r.bkey[i], c.row[i] = r.brow[i];
+  const int cur = launch_csr_order(c, max_cnt, total, s);
+  // the write-out's staging: the other ping-pong buffer holds total * 12 bytes, enough for the int64 ids (8) + f32 scores (4)
   int64_t* idx_d = reinterpret_cast<int64_t*>(r.bkey[cur ^ 1].get());
   float* sc_d = reinterpret_cast<float*>(r.brow[cur ^ 1].get());
-  launch_range_emit(r.bkey[cur], r.brow[cur], total, g->row_offset, idx_d, sc_d, s);
+  launch_csr_write(c, cur, true, total, g->row_offset, idx_d, sc_d, nullptr, s);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(s));      // the handle's stream does not block: the caller's hipMemcpy would not wait for it
   *idx_out = idx_d;

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "f64_key.h"
 #include "kernels.h"
 
 namespace mi {
@@ -182,14 +183,6 @@ __global__ __launch_bounds__(256) void dense_score64_kernel(const float* __restr
   }
 }
 
-// order-preserving 64-bit key of an f64 score: NaN lowest, -0 == +0
-__device__ __forceinline__ uint64_t d2key(double d) {
-  if (d != d) return 0ull;
-  d += 0.0;
-  const uint64_t u = (uint64_t)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
 // dense_topk_kernel on f64 rows: the 64-bit key of the k-th largest score is found in two 32-bit radix selects (high
 // word, then low word among the rows that share it), the rest is the same (index select among exact ties, collect,
 // bitonic sort by (score desc, idx asc)).
@@ -208,9 +201,9 @@ __global__ __launch_bounds__(512) void dense_topk64_kernel(const double* __restr
   if (threadIdx.x < 8) sh[threadIdx.x] = 0;
   __syncthreads();
   const uint32_t hiK = block_radix_kth_largest(
-      [&](uint32_t i, uint32_t& key) { key = (uint32_t)(d2key(row[i]) >> 32); return true; }, n, (uint32_t)k, hist, sh);
+      [&](uint32_t i, uint32_t& key) { key = (uint32_t)(f64_key_nan_lowest(row[i]) >> 32); return true; }, n, (uint32_t)k, hist, sh);
   uint32_t cnt = 0;
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) cnt += ((uint32_t)(d2key(row[i]) >> 32) > hiK);
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) cnt += ((uint32_t)(f64_key_nan_lowest(row[i]) >> 32) > hiK);
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
   if ((threadIdx.x & 63) == 0) atomicAdd(&sh[2], cnt);
   __syncthreads();
@@ -218,28 +211,28 @@ __global__ __launch_bounds__(512) void dense_topk64_kernel(const double* __restr
   __syncthreads();
   const uint32_t loK = block_radix_kth_largest(
       [&](uint32_t i, uint32_t& key) {
-        const uint64_t kk = d2key(row[i]);
+        const uint64_t kk = f64_key_nan_lowest(row[i]);
         key = (uint32_t)kk;
         return (uint32_t)(kk >> 32) == hiK;
       },
       n, need_lo, hist, sh);
   const uint64_t keyK = ((uint64_t)hiK << 32) | loK;
   cnt = 0;
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) cnt += (d2key(row[i]) > keyK);
+  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) cnt += (f64_key_nan_lowest(row[i]) > keyK);
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
   if ((threadIdx.x & 63) == 0) atomicAdd(&sh[4], cnt);
   __syncthreads();
   const uint32_t need_ties = (uint32_t)k - sh[4];            // >= 1
   __syncthreads();
   const uint32_t invT = block_radix_kth_largest(
-      [&](uint32_t i, uint32_t& key) { key = ~i; return d2key(row[i]) == keyK; }, n, need_ties, hist, sh);
+      [&](uint32_t i, uint32_t& key) { key = ~i; return f64_key_nan_lowest(row[i]) == keyK; }, n, need_ties, hist, sh);
   const uint32_t idxT = ~invT;
   // padding: (NaN, 0xFFFFFFFF), as in dense_topk_kernel
   for (uint32_t i = threadIdx.x; i < k2; i += blockDim.x) { s[i] = __builtin_nan(""); id[i] = 0xFFFFFFFFu; }
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
     const double v = row[i];
-    const uint64_t key = d2key(v);
+    const uint64_t key = f64_key_nan_lowest(v);
     if (key > keyK || (key == keyK && i <= idxT)) {
       const uint32_t pos = atomicAdd(&sh[3], 1u);
       if (pos < k2) { s[pos] = v; id[pos] = i; }

@@ -1,5 +1,5 @@
 // Best-first search of a neighbour graph over the stored f32 rows (the role of HNSW's bottom layer): the scorer
-// of graph_walk.h for raw rows.  A place of W is a 64-bit key (l2_dist_key of the value, so ascending = best first) and a 32-bit
+// of graph_walk.h for raw rows.  A place of W is a 64-bit key (f64_key_nan_highest of the value, so ascending = best first) and a 32-bit
 // word holding the local row with the `expanded` mark in bit 31; the order is (key ascending, id ascending).  A new row is
 // evaluated by a whole wave, the four waves taking the rows in turn: l2_direct_wave / refine_dot_wave, the bits of mi_refine.  The
 // query row is read from global memory (every wave re-reads it per row: it stays in L1 / L2).
@@ -11,12 +11,6 @@
 namespace mi {
 
 constexpr uint32_t GS_EXPANDED = 0x80000000u;
-
-// the value behind an l2_dist_key (NaN for the key of a NaN)
-__device__ __forceinline__ double gs_key_value(uint64_t key) {
-  const uint64_t u = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
-  return __longlong_as_double((long long)u);
-}
 
 template <bool L2>
 struct GsRows {
@@ -62,7 +56,7 @@ struct GsRows {
     for (int i = t >> 6; i < m; i += 4) {
       const float* grow = gal_f32 + (int64_t)n_id[i] * dp;
       const double v = L2 ? l2_direct_wave(qrow, grow, d, lane) : refine_dot_wave(qrow, grow, d, lane);
-      if (lane == 0) nw.k[i] = l2_dist_key(L2 ? v : 0.0 - v);
+      if (lane == 0) nw.k[i] = f64_key_nan_highest(L2 ? v : 0.0 - v);
     }
   }
   __device__ __forceinline__ void emit(int64_t o, int i, bool have) const {
@@ -71,7 +65,7 @@ struct GsRows {
     if (have) {
       const Place p = bare(w.load(i));
       id = row_offset + (int64_t)p.id;
-      const double dec = gs_key_value(p.key);
+      const double dec = f64_key_value(p.key);
       v = L2 ? dec : 0.0 - dec;
     }
     out_idx[o] = id;

@@ -25,7 +25,7 @@
 //                           become -1) and writes the prefix of list sizes over it: the query's virtual sequence of candidates
 //   ivff_scan_select_kernel the hot path.  Grid = (slab of IVFF_SLAB positions of that sequence, query), 512 threads: a wave resolves
 //                           64 positions at a time (lane = position: binary search in the prefix, the row from list_rows, the allow
-//                           bit), then evaluates them one row per step with all 64 lanes; entry = (l2_dist_key(value or 0.0 -
+//                           bit), then evaluates them one row per step with all 64 lanes; entry = (f64_key_nan_highest(value or 0.0 -
 //                           value), local row), the sentinel (~0, -1) for rows the bitmap clears and positions beyond the sequence;
 //                           the 2048 entries are bitonic-sorted in LDS (32 KiB: five workgroups to a CU) and the first k written to
 //                           part[query][slab][k], the rows evaluated to pcnt[query][slab]
@@ -361,7 +361,7 @@ __global__ __launch_bounds__(IVFF_THREADS) void ivff_scan_select_kernel(const fl
       const int32_t r = __shfl(row, j);
       const float* grow = gal_f32 + (int64_t)r * dp;
       const double val = L2 ? l2_direct_wave(qrow, grow, d, lane) : refine_dot_wave(qrow, grow, d, lane);
-      if (lane == j) key = l2_dist_key(L2 ? val : 0.0 - val);
+      if (lane == j) key = f64_key_nan_highest(L2 ? val : 0.0 - val);
     }
     s_key[slot] = key;
     s_id[slot] = (int64_t)row;

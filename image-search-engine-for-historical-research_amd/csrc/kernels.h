@@ -149,7 +149,8 @@ void launch_merge(const double* score64, const int64_t* idx, int32_t nshards, in
                   int64_t* out_idx, float* out_score, hipStream_t stream);
 
 // range_select.hip -- exact range search (api_range.hip): fixed threshold, survivor rows for rescore_kernel, rows kept at
-// f64 score >= min_score (CSR per chunk), per-query counts / offsets, order by (score desc, row asc), emit
+// f64 score >= min_score (CSR per chunk, keyed by ~f64_key_nan_lowest(score)), per-query counts / offsets, the gather into the
+// batch's CSR list; csr_order.hip orders it and writes it out
 void launch_range_threshold(QueryState st, int32_t nq, int32_t qpad, double min_score, hipStream_t stream);
 void launch_range_chunk_begin(QueryState st, int32_t qpad, unsigned long long* total, hipStream_t stream);
 void launch_range_rows(QueryState st, int32_t nq, uint32_t* rows, uint32_t* rcnt, int dense, uint32_t row0, uint32_t nrows,
@@ -160,12 +161,25 @@ void launch_range_keep(const uint32_t* rows, const uint32_t* rcnt, const double*
 void launch_range_lims(const uint32_t* cnt, int32_t nchunks, int32_t ld, int32_t nq, int64_t* lims, hipStream_t stream);
 void launch_range_gather(const uint64_t* akey, const uint32_t* arow, const uint64_t* off, const uint32_t* cnt, int32_t nchunks,
                          int32_t ld, int32_t nq, const int64_t* lims, uint64_t* key, uint32_t* row, hipStream_t stream);
-void launch_range_sort_runs(uint64_t* key, uint32_t* row, const int64_t* lims, int32_t nq, int64_t max_cnt, hipStream_t stream);
-int64_t range_run_length();
-void launch_range_merge(const uint64_t* skey, const uint32_t* srow, uint64_t* dkey, uint32_t* drow, const int64_t* lims,
-                        int32_t nq, int64_t total, int64_t w, hipStream_t stream);
-void launch_range_emit(const uint64_t* key, const uint32_t* row, int64_t total, int64_t row_offset, int64_t* out_idx,
-                       float* out_score, hipStream_t stream);
+
+// csr_order.hip -- the ordering stage of the range searches (api_range.hip, api_minkowski_range.hip): the CSR list of
+// a chunk of queries, (uint64 key, uint32 local row) entries, ordered per query by (key asc, row asc) and written out
+struct CsrList {
+  int32_t nq = 0;                    // queries of the chunk (<= 65535)
+  int64_t* lims = nullptr;           // the CSR offsets from the chunk's first query on: [nq + 1]
+  const int64_t* total = nullptr;    // the call's hit count on the device; nothing is written once *total > max_results
+  int64_t max_results = 0;
+  uint64_t* key[2] = {nullptr, nullptr};   // the chunk's hits from place 0 on: keys and local rows, ping-pong of the merge passes
+  uint32_t* row[2] = {nullptr, nullptr};
+};
+// buffer 0 holds the lists; max_cnt: no query of the chunk has more hits, max_total: the chunk has no more.  -> the buffer (0 or 1)
+// that holds the ordered lists
+int launch_csr_order(const CsrList& a, int64_t max_cnt, int64_t max_total, hipStream_t stream);
+// the ordered lists of buffer `cur` -> out_*[lims[0] ..]: id = row_offset + row, value = the float64 behind the key (complement: behind
+// ~key, for lists keyed by ~f64_key_nan_lowest(value)) and its float32.  out_idx is written, either value output may be NULL
+void launch_csr_write(const CsrList& a, int cur, bool complement, int64_t max_total, int64_t row_offset, int64_t* out_idx, float* out_val,
+                      double* out_val64, hipStream_t stream);
+int64_t csr_run_length();            // entries of one LDS-sorted run
 
 // dense.hip -- exact top-k of dense score rows (global-memory radix select + LDS bitonic sort), k <= 4096
 void launch_dense_topk(const float* scores, int64_t ld, int64_t n, int32_t nq, int32_t k, int64_t row_offset,
@@ -560,33 +574,22 @@ void launch_minkowski_scan(const float* gal_f32, const float* qry, int32_t dp, i
                            int32_t nq, double* val, int64_t ld, hipStream_t stream);
 
 // minkowski_range.hip -- what follows the scan in a Minkowski radius search or self-join (api_minkowski_range.hip): the
-// hits value <= radius of one chunk of queries counted per (query, part of the rows), placed by prefix sums, ordered by
-// (l2_dist_key(value) asc, row asc) and written out in CSR form.  A part is mink_part_rows(nrows) rows, a query has mink_parts(nrows)
-struct MinkRangeArgs {
+// hits value <= radius of one chunk of queries counted per (query, part of the rows) and placed by prefix sums as
+// (f64_key_nan_highest(value), row) entries of a CsrList, which csr_order.hip orders and writes out.  A part is mink_part_rows(nrows)
+// rows, a query has mink_parts(nrows).  total: the call's lims[all queries]
+struct MinkRangeArgs : CsrList {
   const double* val = nullptr;       // [nq][ld]: column r is the value of local row row_base + r
   int64_t ld = 0, nrows = 0;         // nrows: the rows that were scanned
   int64_t row_base = 0;
-  int32_t nq = 0;                    // queries of the chunk (<= 65535)
   const uint64_t* allow = nullptr;   // NULL or the bitmap over local rows
   double radius = 0.0;
   int64_t self_row0 = -1;            // >= 0: the self-join, query q is stored row self_row0 + q and only the rows above it count
   uint32_t* cnt = nullptr;           // [nq][parts] hits
   int64_t* off = nullptr;            // [nq][parts] their first place among the chunk's hits
-  int64_t* lims = nullptr;           // the CSR offsets from the chunk's first query on: [nq + 1]
-  const int64_t* total = nullptr;    // the call's lims[all queries]; nothing is written once *total > max_results
-  int64_t max_results = 0;
-  uint64_t* key[2] = {nullptr, nullptr};   // the chunk's hits from place 0 on: keys and local rows, ping-pong of the merge passes
-  uint32_t* row[2] = {nullptr, nullptr};
 };
 // counts, then off and (write_lims) lims[1 ..] on top of lims[0], which `first` sets to 0
 void launch_mink_range_count(const MinkRangeArgs& a, bool first, bool write_lims, hipStream_t stream);
 void launch_mink_range_emit(const MinkRangeArgs& a, hipStream_t stream);                 // -> key[0] / row[0], ascending rows per query
-// max_cnt: no query of the chunk has more hits.  -> the buffer (0 or 1) that holds the ordered lists
-int launch_mink_range_order(const MinkRangeArgs& a, int64_t max_cnt, int64_t max_total, hipStream_t stream);
-// the ordered lists of buffer `cur` -> out_*[lims[0] ..]; out_idx is written, either value output may be NULL
-void launch_mink_range_write(const MinkRangeArgs& a, int cur, int64_t max_total, int64_t row_offset, int64_t* out_idx, float* out_val,
-                             double* out_val64, hipStream_t stream);
-int64_t mink_range_run_length();                                                         // entries of one LDS-sorted run
 
 // pq_remove.hip -- in-place row removal of the PQ and the IVF-PQ index (api_pq.hip, api_ivfpq.hip).  keep [ceil(n / 64)]: the bitmap
 // of the rows that stay (bits at or beyond n clear); prefix [ceil(n / 64) + 1]: the exclusive count of keep bits per word.

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void l2_tail_kernel(const float* __restrict__ 
   }
   __syncthreads();
   auto after = [&](uint32_t a, uint32_t b) {                   // entry a belongs behind entry b
-    const uint64_t ka = l2_dist_key(s_dist[a]), kb = l2_dist_key(s_dist[b]);
+    const uint64_t ka = f64_key_nan_highest(s_dist[a]), kb = f64_key_nan_highest(s_dist[b]);
     if (ka != kb) return ka > kb;
     return (uint64_t)s_id[a] > (uint64_t)s_id[b];               // -1 -> the largest: padding last
   };

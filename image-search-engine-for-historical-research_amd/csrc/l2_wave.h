@@ -2,6 +2,7 @@
 // of shortlists (refine.hip) and the graph search (graph_search.hip): all give a (query, row) pair the same bits.  DESIGN.md 5.11, 5.15.
 #pragma once
 #include "common.h"
+#include "f64_key.h"
 
 namespace mi {
 
@@ -39,14 +40,6 @@ __device__ __forceinline__ double refine_dot_wave(const float* __restrict__ q, c
     if (c + 3 < d) acc = __builtin_fma((double)a.w, (double)b.w, acc);
   }
   return l2_wave_sum(acc);
-}
-
-// order-preserving key of a distance (>= 0, +inf for padding; NaN last)
-__device__ __forceinline__ uint64_t l2_dist_key(double x) {
-  if (x != x) return ~0ull;
-  x += 0.0;
-  const uint64_t u = (uint64_t)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
 
 }  // namespace mi

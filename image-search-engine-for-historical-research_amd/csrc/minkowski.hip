@@ -12,7 +12,7 @@
 //                       with float4 loads, converts them to float64 once and evaluates them against QI queries out of LDS at a time
 //                       (R x QI accumulators in registers), so a row's HBM bytes and conversions are paid once per tile and a query's
 //                       LDS bytes once per R rows.  Rows the allow bitmap clears are not evaluated.  The values go to val [query][row]
-//   mink_select_kernel  grid = (part of part_rows consecutive rows, query): the part's values as a stream of (l2_dist_key(value), local
+//   mink_select_kernel  grid = (part of part_rows consecutive rows, query): the part's values as a stream of (f64_key_nan_highest(value), local
 //                       row) -- the sentinel for rows the bitmap clears -- through slab_stream_best; the best k to part [query][part][k]
 //   mink_merge_kernel   workgroup = query: the partial lists of its parts -> the k best in order, then ids and values
 // The scan cannot select by itself: beside 128 KiB of queries (QT = 8, d = 2048) LDS has no room for the 2048 entries of eight
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(MINK_THREADS) void mink_select_kernel(const double*
   slab_stream_best<HALF, MINK_THREADS>(s_key, s_id, count, tid, [&](int64_t i, uint64_t& key, int64_t& id) {
     const int64_t row = r0 + i;
     if (mink_allowed(allow, row)) {
-      key = l2_dist_key(v[row]);
+      key = f64_key_nan_highest(v[row]);
       id = row;
     }
   });

@@ -8,27 +8,19 @@
 //   mink_range_offsets_kernel  one workgroup: the exclusive prefix of cnt over (query, part) in that order -> off [query][part], the
 //                              place of the pair's first hit among the chunk's; lims[1 + query] on top of lims[0], the chunk's base
 //   mink_range_emit_kernel     the count's traversal again: a hit goes to off + hits before it in the part (the waves' counts of the
-//                              step prefixed in LDS + the ballot below the lane), as (l2_dist_key(value), local row): a query's list is
-//                              in ascending row order
-//   mink_range_sort_kernel     grid = (run of MINK_RANGE_RUN entries, query): the run ordered by (key asc, row asc) in LDS, in place
-//   mink_range_merge_kernel    one pass: ordered runs of w entries of every query -> runs of 2 w, one thread per entry (its place =
-//                              its index in its run + the entries of the other run before it), into the other buffer
-//   mink_range_write_kernel    ordered entries -> int64 id, the float64 behind the key, its float32
-// Every place is a prefix sum over (query, part, row) in ascending order and (key, row) is a total order, so nothing follows the order
-// in which workgroups ran: no atomics, no grid barrier.  From the emit on every kernel first reads *total, the call's hit count, from
-// device memory: beyond max_results it writes nothing (uniform per launch).
-#include <algorithm>
-
+//                              step prefixed in LDS + the ballot below the lane), as (f64_key_nan_highest(value), local row): a
+//                              query's list is in ascending row order
+// csr_order.hip then orders every query's list by (key asc, row asc) and writes it out.  Every place is a prefix sum over (query,
+// part, row) in ascending order and (key, row) is a total order, so nothing follows the order in which workgroups ran: no atomics, no
+// grid barrier.  From the emit on every kernel first reads *total, the call's hit count, from device memory: beyond max_results it
+// writes nothing (uniform per launch).
 #include "common.h"
+#include "f64_key.h"
 #include "kernels.h"
-#include "l2_wave.h"
-#include "slab_select.h"
 
 namespace mi {
 
 constexpr int MR_THREADS = 512, MR_WAVES = MR_THREADS / 64;
-constexpr int MINK_RANGE_RUN = 2048;
-constexpr int MR_SORT_THREADS = 1024;
 constexpr int MR_SCAN_THREADS = 1024;
 
 // row r of the chunk's values (local row a.row_base + r) is a hit of query q
@@ -126,99 +118,10 @@ __global__ __launch_bounds__(MR_THREADS) void mink_range_emit_kernel(const doubl
     }
     if (hit) {
       const int64_t pos = run + before + __popcll(m & ((1ull << lane) - 1ull));
-      key[pos] = l2_dist_key(v[r]);
+      key[pos] = f64_key_nan_highest(v[r]);
       row[pos] = (uint32_t)(row_base + r);
     }
     run += tot;
-  }
-}
-
-// (key, row) ascending; the padding (~0, ~0) behind every hit
-__device__ __forceinline__ bool mr_after(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) { return ka != kb ? ka > kb : ia > ib; }
-
-__global__ __launch_bounds__(MR_SORT_THREADS) void mink_range_sort_kernel(uint64_t* __restrict__ key, uint32_t* __restrict__ row,
-                                                                         const int64_t* __restrict__ lims,
-                                                                         const int64_t* __restrict__ total, int64_t max_results) {
-  __shared__ uint64_t k[MINK_RANGE_RUN];
-  __shared__ uint32_t id[MINK_RANGE_RUN];
-  if (*total > max_results) return;
-  const uint32_t q = blockIdx.y;
-  const int64_t lo = lims[q] - lims[0], n = lims[q + 1] - lims[q];
-  const int64_t r0 = (int64_t)blockIdx.x * MINK_RANGE_RUN;
-  if (r0 >= n) return;
-  const uint32_t m = (uint32_t)min((int64_t)MINK_RANGE_RUN, n - r0);
-  if (m < 2) return;
-  uint32_t len = 2;
-  while (len < m) len <<= 1;                                                // block-uniform network width
-  for (uint32_t i = threadIdx.x; i < len; i += MR_SORT_THREADS) {
-    const bool v = i < m;
-    k[i] = v ? key[lo + r0 + i] : ~0ull;
-    id[i] = v ? row[lo + r0 + i] : 0xFFFFFFFFu;
-  }
-  __syncthreads();
-  for (uint32_t w = 2; w <= len; w <<= 1) {
-    for (uint32_t j = w >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = threadIdx.x; t < (len >> 1); t += MR_SORT_THREADS) {
-        const uint32_t a = 2 * t - (t & (j - 1)), b = a + j;
-        const bool up = (a & w) == 0;                                       // this half of the network puts a before b
-        const uint64_t ka = k[a], kb = k[b];
-        const uint32_t ia = id[a], ib = id[b];
-        if (mr_after(ka, ia, kb, ib) == up) {
-          k[a] = kb; k[b] = ka;
-          id[a] = ib; id[b] = ia;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (uint32_t i = threadIdx.x; i < m; i += MR_SORT_THREADS) {
-    key[lo + r0 + i] = k[i];
-    row[lo + r0 + i] = id[i];
-  }
-}
-
-// lims: the chunk's, nq + 1 of them.  Entries are distinct (a query holds a row once), so "not after" is "before"
-__global__ __launch_bounds__(256) void mink_range_merge_kernel(const uint64_t* __restrict__ skey, const uint32_t* __restrict__ srow,
-                                                               uint64_t* __restrict__ dkey, uint32_t* __restrict__ drow,
-                                                               const int64_t* __restrict__ lims, int32_t nq, int64_t w,
-                                                               const int64_t* __restrict__ total, int64_t max_results) {
-  if (*total > max_results) return;
-  const int64_t first = lims[0], cnt = lims[nq] - first;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-    int lo = 0, hi = nq;                                                    // query of entry i: lims[q] <= first + i < lims[q + 1]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (lims[mid] - first <= i) lo = mid; else hi = mid;
-    }
-    const int64_t base = lims[lo] - first, n = lims[lo + 1] - lims[lo], local = i - base;
-    const int64_t start = local / (2 * w) * (2 * w);
-    const int64_t a0 = start, a1 = min(start + w, n), b0 = a1, b1 = min(start + 2 * w, n);
-    const uint64_t kx = skey[i];
-    const uint32_t ix = srow[i];
-    const bool in_a = local < a1;
-    int64_t l = in_a ? b0 : a0, h = in_a ? b1 : a1;                         // the other run's entries before x
-    while (l < h) {
-      const int64_t mid = (l + h) >> 1;
-      if (mr_after(kx, ix, skey[base + mid], srow[base + mid])) l = mid + 1; else h = mid;
-    }
-    const int64_t place = start + (local - (in_a ? a0 : b0)) + (l - (in_a ? b0 : a0));
-    dkey[base + place] = kx;
-    drow[base + place] = ix;
-  }
-}
-
-__global__ __launch_bounds__(256) void mink_range_write_kernel(const uint64_t* __restrict__ key, const uint32_t* __restrict__ row,
-                                                               const int64_t* __restrict__ lims, int32_t nq, int64_t row_offset,
-                                                               const int64_t* __restrict__ total, int64_t max_results,
-                                                               int64_t* __restrict__ out_idx, float* __restrict__ out_val,
-                                                               double* __restrict__ out_val64) {
-  if (*total > max_results) return;
-  const int64_t first = lims[0], cnt = lims[nq] - first;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-    const double v = slab_key_value(key[i]);
-    out_idx[first + i] = row_offset + (int64_t)row[i];
-    if (out_val64) out_val64[first + i] = v;
-    if (out_val) out_val[first + i] = (float)v;
   }
 }
 
@@ -239,29 +142,5 @@ void launch_mink_range_emit(const MinkRangeArgs& a, hipStream_t stream) {
       a.val, a.ld, a.nrows, a.row_base, mink_part_rows(a.nrows), nparts, a.allow, a.radius, a.self_row0, a.off, a.total, a.max_results,
       a.key[0], a.row[0]);
 }
-
-static unsigned mr_flat_grid(int64_t max_total) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((max_total + 255) / 256, 8192)); }
-
-int launch_mink_range_order(const MinkRangeArgs& a, int64_t max_cnt, int64_t max_total, hipStream_t stream) {
-  if (a.nq <= 0 || max_cnt < 2) return 0;
-  const unsigned runs = (unsigned)((max_cnt + MINK_RANGE_RUN - 1) / MINK_RANGE_RUN);
-  mink_range_sort_kernel<<<dim3(runs, (unsigned)a.nq), MR_SORT_THREADS, 0, stream>>>(a.key[0], a.row[0], a.lims, a.total, a.max_results);
-  int cur = 0;
-  for (int64_t w = MINK_RANGE_RUN; w < max_cnt; w *= 2) {
-    mink_range_merge_kernel<<<dim3(mr_flat_grid(max_total)), 256, 0, stream>>>(a.key[cur], a.row[cur], a.key[cur ^ 1], a.row[cur ^ 1], a.lims,
-                                                                              a.nq, w, a.total, a.max_results);
-    cur ^= 1;
-  }
-  return cur;
-}
-
-void launch_mink_range_write(const MinkRangeArgs& a, int cur, int64_t max_total, int64_t row_offset, int64_t* out_idx, float* out_val,
-                             double* out_val64, hipStream_t stream) {
-  if (a.nq <= 0) return;
-  mink_range_write_kernel<<<dim3(mr_flat_grid(max_total)), 256, 0, stream>>>(a.key[cur], a.row[cur], a.lims, a.nq, row_offset, a.total,
-                                                                            a.max_results, out_idx, out_val, out_val64);
-}
-
-int64_t mink_range_run_length() { return MINK_RANGE_RUN; }
 
 }  // namespace mi

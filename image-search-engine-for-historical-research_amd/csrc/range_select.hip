@@ -1,10 +1,9 @@
 // Kernels of the exact range search (api_range.hip): the fixed threshold of the scoring launches, the survivor rows handed to
 // the exact re-score (rescore_kernel, select.hip, unchanged), the rows kept at exact score >= min_score, their per-query
-// counts and offsets (CSR), and the order of every query's hits by (f64 score desc, row asc): runs of up to RANGE_RUN entries
-// sorted in LDS, longer lists merged in global memory.  DESIGN.md section 5.9.
-#include <algorithm>
-
+// counts and offsets (CSR) and every query's hits gathered into its CSR slot as (~key of the f64 score, row): csr_order.hip puts
+// them in (key asc, row asc) order, which is (score desc, row asc), and writes them out.  DESIGN.md section 5.9.
 #include "common.h"
+#include "f64_key.h"
 #include "kernels.h"
 
 namespace mi {
@@ -56,26 +55,10 @@ void launch_range_rows(QueryState st, int32_t nq, uint32_t* rows, uint32_t* rcnt
   hipLaunchKernelGGL(range_rows_kernel, dim3(16, nq), dim3(256), 0, stream, st, rows, rcnt, dense, row0, nrows);
 }
 
-// order-preserving 64-bit key of an f64 score (the key of emit_kernel): NaN lowest, -0 == +0
-__device__ __forceinline__ uint64_t range_key(double s) {
-  if (s != s) return 0ull;
-  if (s == 0.0) return 0x8000000000000000ull;
-  const uint64_t b = (uint64_t)__double_as_longlong(s);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double range_unkey(uint64_t k) {
-  const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-// "a comes before b": score desc, row asc
-__device__ __forceinline__ bool range_before(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
-  return ka > kb || (ka == kb && ia < ib);
-}
-
 // keep the re-scored rows with f64 score >= min_score: query q's hits of this chunk go to key/row[off[q] .. off[q] + cnt[q]),
 // off[q] = base + its share of the chunk's counter *total (the order of the queries inside a chunk is whatever the atomics
-// give; api_range.hip orders every query's hits afterwards).  Writes past `cap` (never: the host sizes the buffer for every
-// re-scored row) raise FLAG_SURV_OVERFLOW instead.
+// give; api_range.hip orders every query's hits afterwards), keyed by the complement of f64_key_nan_lowest(score).  Writes
+// past `cap` (never: the host sizes the buffer for every re-scored row) raise FLAG_SURV_OVERFLOW instead.
 __global__ __launch_bounds__(256) void range_keep_kernel(const uint32_t* __restrict__ rows, const uint32_t* __restrict__ rcnt,
                                                          const double* __restrict__ sc, uint32_t lcap, double min_score,
                                                          unsigned long long* total, uint64_t* __restrict__ off,
@@ -106,7 +89,7 @@ __global__ __launch_bounds__(256) void range_keep_kernel(const uint32_t* __restr
     if (v >= min_score) {
       const uint64_t p = o + atomicAdd(&c, 1u);
       if (p < cap) {
-        key[p] = range_key(v);
+        key[p] = ~f64_key_nan_lowest(v);                      // complemented: key ascending = score descending
         row[p] = r[i];
       } else {
         atomicOr(flags, FLAG_SURV_OVERFLOW);
@@ -168,111 +151,6 @@ __global__ __launch_bounds__(256) void range_gather_kernel(const uint64_t* __res
 void launch_range_gather(const uint64_t* akey, const uint32_t* arow, const uint64_t* off, const uint32_t* cnt, int32_t nchunks,
                          int32_t ld, int32_t nq, const int64_t* lims, uint64_t* key, uint32_t* row, hipStream_t stream) {
   hipLaunchKernelGGL(range_gather_kernel, dim3(nq), dim3(256), 0, stream, akey, arow, off, cnt, nchunks, ld, lims, key, row);
-}
-
-// runs [lims[q] + r * RANGE_RUN, ...) of every query sorted in LDS (bitonic network, 1024 threads, 24 KiB), in place
-constexpr int RANGE_RUN = 2048;
-__global__ __launch_bounds__(1024) void range_sort_runs_kernel(uint64_t* __restrict__ key, uint32_t* __restrict__ row,
-                                                               const int64_t* __restrict__ lims) {
-  __shared__ uint64_t k[RANGE_RUN];
-  __shared__ uint32_t id[RANGE_RUN];
-  const uint32_t q = blockIdx.y;
-  const int64_t lo = lims[q], n = lims[q + 1] - lo;
-  const int64_t r0 = (int64_t)blockIdx.x * RANGE_RUN;
-  if (r0 >= n) return;
-  const uint32_t m = (uint32_t)min((int64_t)RANGE_RUN, n - r0);
-  uint32_t len = 2;
-  while (len < m) len <<= 1;                               // block-uniform network width
-  for (uint32_t i = threadIdx.x; i < len; i += blockDim.x) {
-    const bool v = i < m;
-    k[i] = v ? key[lo + r0 + i] : 0ull;                    // padding: key 0 with the largest id comes after everything
-    id[i] = v ? row[lo + r0 + i] : 0xFFFFFFFFu;
-  }
-  __syncthreads();
-  for (uint32_t w = 2; w <= len; w <<= 1) {
-    for (uint32_t j = w >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = threadIdx.x; t < (len >> 1); t += blockDim.x) {
-        const uint32_t a = 2 * j * (t / j) + (t % j), b = a + j;
-        const bool up = (a & w) == 0;                      // this half of the network puts a before b
-        const uint64_t ka = k[a], kb = k[b];
-        const uint32_t ia = id[a], ib = id[b];
-        const bool swap = up ? range_before(kb, ib, ka, ia) : range_before(ka, ia, kb, ib);
-        if (swap) {
-          k[a] = kb; k[b] = ka;
-          id[a] = ib; id[b] = ia;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
-    key[lo + r0 + i] = k[i];
-    row[lo + r0 + i] = id[i];
-  }
-}
-
-void launch_range_sort_runs(uint64_t* key, uint32_t* row, const int64_t* lims, int32_t nq, int64_t max_cnt, hipStream_t stream) {
-  const unsigned runs = (unsigned)((max_cnt + RANGE_RUN - 1) / RANGE_RUN);
-  if (runs == 0) return;
-  hipLaunchKernelGGL(range_sort_runs_kernel, dim3(runs, nq), dim3(1024), 0, stream, key, row, lims);
-}
-int64_t range_run_length() { return RANGE_RUN; }
-
-// one merge pass: sorted runs of width w of every query become runs of 2 w.  One thread per entry: its place in the merged
-// run is its index in its own run plus the number of entries of the other run that come before it (binary search; an equal
-// entry -- never, ids of a query are distinct -- counts as before for the second run only, so the places stay distinct).
-__global__ __launch_bounds__(256) void range_merge_kernel(const uint64_t* __restrict__ skey, const uint32_t* __restrict__ srow,
-                                                          uint64_t* __restrict__ dkey, uint32_t* __restrict__ drow,
-                                                          const int64_t* __restrict__ lims, int32_t nq, int64_t w) {
-  const int64_t total = lims[nq];
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    int lo = 0, hi = nq;                                    // query of entry i: lims[q] <= i < lims[q + 1]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (lims[mid] <= i) lo = mid; else hi = mid;
-    }
-    const int64_t base = lims[lo], n = lims[lo + 1] - base, local = i - base;
-    const int64_t start = local / (2 * w) * (2 * w);
-    const int64_t a0 = start, a1 = min(start + w, n), b0 = a1, b1 = min(start + 2 * w, n);
-    const uint64_t kx = skey[i];
-    const uint32_t ix = srow[i];
-    const bool in_a = local < a1;
-    int64_t l = in_a ? b0 : a0, h = in_a ? b1 : a1;         // count the other run's entries before (a) / not after (b) x
-    while (l < h) {
-      const int64_t mid = (l + h) >> 1;
-      const uint64_t km = skey[base + mid];
-      const uint32_t im = srow[base + mid];
-      const bool before = in_a ? range_before(km, im, kx, ix) : !range_before(kx, ix, km, im);
-      if (before) l = mid + 1; else h = mid;
-    }
-    const int64_t place = start + (local - (in_a ? a0 : b0)) + (l - (in_a ? b0 : a0));
-    dkey[base + place] = kx;
-    drow[base + place] = ix;
-  }
-}
-
-void launch_range_merge(const uint64_t* skey, const uint32_t* srow, uint64_t* dkey, uint32_t* drow, const int64_t* lims,
-                        int32_t nq, int64_t total, int64_t w, hipStream_t stream) {
-  if (total <= 0) return;
-  const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(range_merge_kernel, dim3(grid), dim3(256), 0, stream, skey, srow, dkey, drow, lims, nq, w);
-}
-
-// sorted hits -> (row_offset + row, f32 of the f64 score)
-__global__ __launch_bounds__(256) void range_emit_kernel(const uint64_t* __restrict__ key, const uint32_t* __restrict__ row,
-                                                         int64_t total, int64_t row_offset, int64_t* __restrict__ out_idx,
-                                                         float* __restrict__ out_score) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    out_idx[i] = row_offset + (int64_t)row[i];
-    out_score[i] = (float)range_unkey(key[i]);
-  }
-}
-
-void launch_range_emit(const uint64_t* key, const uint32_t* row, int64_t total, int64_t row_offset, int64_t* out_idx,
-                       float* out_score, hipStream_t stream) {
-  if (total <= 0) return;
-  const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(range_emit_kernel, dim3(grid), dim3(256), 0, stream, key, row, total, row_offset, out_idx, out_score);
 }
 
 }  // namespace mi

@@ -39,15 +39,9 @@ __global__ __launch_bounds__(256) void refine_gather_kernel(const float* __restr
   }
 }
 
-// the value behind an l2_dist_key (NaN for the key of a NaN)
-__device__ __forceinline__ double refine_key_value(uint64_t key) {
-  const uint64_t u = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
-  return __longlong_as_double((long long)u);
-}
-
 // One workgroup per query.  NMAX entries of 16 bytes in LDS: 32 KiB for kc <= 2048 (256 threads, five workgroups fit a CU's
-// 160 KiB), 128 KiB for kc <= 8192 (1024 threads, one workgroup per CU).  The key of a value v is l2_dist_key(v) ascending for L2
-// and l2_dist_key(0.0 - v) for the inner product, so one ascending sort serves both; padding is (~0, -1), behind everything.
+// 160 KiB), 128 KiB for kc <= 8192 (1024 threads, one workgroup per CU).  The key of a value v is f64_key_nan_highest(v) ascending for L2
+// and f64_key_nan_highest(0.0 - v) for the inner product, so one ascending sort serves both; padding is (~0, -1), behind everything.
 template <bool L2, int NMAX, int THREADS>
 __global__ __launch_bounds__(THREADS) void refine_sort_kernel(const double* __restrict__ val, const int64_t* __restrict__ cand,
                                                               int32_t kc, int64_t cand_stride, int64_t n, int64_t row_offset,
@@ -69,7 +63,7 @@ __global__ __launch_bounds__(THREADS) void refine_sort_kernel(const double* __re
       const int64_t local = id >= 0 ? id - row_offset : -1;       // (no difference is taken of a negative id: it may not fit)
       if (local >= 0 && local < n) {
         const double v = val[q * kc + i];
-        key = l2_dist_key(L2 ? v : 0.0 - v);
+        key = f64_key_nan_highest(L2 ? v : 0.0 - v);
       } else {
         id = -1;
       }
@@ -112,7 +106,7 @@ __global__ __launch_bounds__(THREADS) void refine_sort_kernel(const double* __re
   uint32_t pos = s_cnt[t] - mine;
   for (uint32_t i = e0; i < e1 && pos < (uint32_t)k; ++i) {
     if (!(s_id[i] >= 0 && (i == 0 || s_id[i] != s_id[i - 1]))) continue;
-    const double dec = refine_key_value(s_key[i]);
+    const double dec = f64_key_value(s_key[i]);
     const double v = L2 ? dec : 0.0 - dec;
     out_idx[q * k + pos] = s_id[i];
     if (out_val64) out_val64[q * k + pos] = v;

@@ -9,6 +9,7 @@
 #include <utility>
 
 #include "common.h"
+#include "f64_key.h"
 #include "kernels.h"
 
 namespace mi {
@@ -850,12 +851,6 @@ void launch_rescore(const float* gal_f32, const float* qry_f32, int32_t dp, int3
 // replaces (which staged rcap * 12 bytes -- 24 KiB -- per workgroup); 17 -> 8 us per 1024-query batch in isolation
 // (scripts/tailbench.hip).
 constexpr uint32_t EMIT_TILE = 512;
-__device__ __forceinline__ uint64_t emit_key(double s) {
-  if (s != s) return 0ull;                                    // NaN: after everything
-  if (s == 0.0) return 0x8000000000000000ull;                 // +0.0 and -0.0 compare equal
-  const uint64_t b = (uint64_t)__double_as_longlong(s);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 __global__ __launch_bounds__(256) void emit_kernel(const uint32_t* __restrict__ cand_rows,
                                                    const uint32_t* __restrict__ cand_cnt,
                                                    const double* __restrict__ cand_score, uint32_t rcap, int32_t k,
@@ -900,14 +895,14 @@ __global__ __launch_bounds__(256) void emit_kernel(const uint32_t* __restrict__ 
       for (uint32_t e = threadIdx.x; e < tn4; e += blockDim.x) {
         // padding to a multiple of four never counts: key 0 with the largest id comes before nothing
         const bool reg = (t0 == 0 && e == threadIdx.x);       // the first 256 entries of the list are in registers
-        tk[e] = e < tn ? emit_key(reg ? s_pre : qs[t0 + e]) : 0ull;
+        tk[e] = e < tn ? f64_key_nan_lowest(reg ? s_pre : qs[t0 + e]) : 0ull;
         ti[e] = e < tn ? (reg ? i_pre : qi[t0 + e]) : 0xFFFFFFFFu;
       }
       partial[threadIdx.x] = 0;
       __syncthreads();
       if (mine && !have_a) {                                  // my candidate: from the staged tile when it lies in it
         if (i >= t0 && i < t0 + tn) { ka = tk[i - t0]; ia = ti[i - t0]; }
-        else { ka = emit_key(qs[i]); ia = qi[i]; }
+        else { ka = f64_key_nan_lowest(qs[i]); ia = qi[i]; }
         have_a = true;
       }
       if (mine) {

@@ -3,6 +3,7 @@
 // give an answer the same order: (key asc, id asc), the sentinel (~0, -1) behind every row.  DESIGN.md 5.18, 5.19.
 #pragma once
 #include "common.h"
+#include "f64_key.h"
 
 namespace mi {
 
@@ -32,12 +33,6 @@ __device__ __forceinline__ void slab_sort(uint64_t* s_key, int64_t* s_id, int ti
       }
       __syncthreads();
     }
-}
-
-// the value behind an l2_dist_key (NaN for the key of a NaN)
-__device__ __forceinline__ double slab_key_value(uint64_t key) {
-  const uint64_t u = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
-  return __longlong_as_double((long long)u);
 }
 
 // The best HALF entries, in order, of a stream of `count` entries: s_key / s_id hold 2 HALF entries, [0, HALF) the best so far
@@ -72,7 +67,7 @@ __device__ __forceinline__ void slab_emit(const uint64_t* s_key, const int64_t* 
   const double padv = ASC ? (double)INFINITY : -(double)INFINITY;
   for (int32_t i = tid; i < k; i += NT) {
     const int64_t id = s_id[i];
-    const double dec = slab_key_value(s_key[i]);
+    const double dec = f64_key_value(s_key[i]);
     const double v = id < 0 ? padv : (ASC ? dec : 0.0 - dec);
     if (out_idx) out_idx[q * k + i] = id < 0 ? -1 : row_offset + id;
     if (out_val64) out_val64[q * k + i] = v;

@@ -6,10 +6,13 @@ resource metadata of both sides.  For kernels that differ it also lists the coun
 are built from.  CPU only (hipcc cross-compiles).
 
     python scripts/isa_compare.py OLD_TREE NEW_TREE [file.hip ...]       e.g. OLD_TREE = a `git worktree` of the parent commit
+    python scripts/isa_compare.py --moved a.hip:old_kernel[:i]=b.hip:new_kernel[:j] [--moved ...] OLD_TREE NEW_TREE [file.hip ...]
 
 Kernels are paired by (file, unqualified name without template arguments, position among the kernels of that name in the order
 the compiler emits them), so an instantiation whose template parameter list was shortened still meets its predecessor; both
-demangled names are printed for every pair that is not identical.  Exit status 1 when a kernel differs or has no partner.
+demangled names are printed for every pair that is not identical.  --moved pairs the first (or i-th, from 0) kernel of that name in one file of the
+old tree with the first (or j-th) of the other name in a file of the new tree (a kernel that changed its file, its name or both) and
+reports the pair under MOVED.  Exit status 1 when a kernel differs or has no partner.
 """
 import collections
 import os
@@ -82,13 +85,29 @@ def base_name(mangled):
     return name
 
 
+def compare(a, b, report):
+    """1 when old kernel a and new kernel b are identical, else 0 with the differences appended to report."""
+    if a[2] == b[2] and a[3] == b[3]:
+        return 1
+    report.append("  DIFFERS: %s\n       ->  %s\n    instructions %d -> %d" % (a[1], b[1], len(a[2]), len(b[2])))
+    report.append("    " + "  ".join("%s %d -> %d" % (m, a[3][m], b[3][m]) for m in META))
+    cnt = [collections.Counter(c for l in k[2] for c in CLASSES if c in l) for k in (a, b)]
+    report.append("    " + "  ".join("%s %d -> %d" % (c, cnt[0][c], cnt[1][c]) for c in CLASSES))
+    return 0
+
+
 def main():
-    old, new = os.path.abspath(sys.argv[1]), os.path.abspath(sys.argv[2])
-    files = sys.argv[3:] or sorted(set(f for t in (old, new) for f in os.listdir(os.path.join(t, PKG, "csrc")) if f.endswith(".hip")))
+    args, moved = sys.argv[1:], []
+    while args and args[0] == "--moved":
+        moved.append([tuple(x.split(":")) for x in args[1].split("=")])
+        args = args[2:]
+    old, new = os.path.abspath(args[0]), os.path.abspath(args[1])
+    files = args[2:] or sorted(set(f for t in (old, new) for f in os.listdir(os.path.join(t, PKG, "csrc")) if f.endswith(".hip")))
     differ = 0
     with tempfile.TemporaryDirectory() as td, ThreadPoolExecutor(max_workers=8) as ex:
         jobs = {(t, f): ex.submit(compile_asm, t, f, td) for f in files for t in (old, new)
                 if os.path.exists(os.path.join(t, PKG, "csrc", f))}
+        sides = {}
         for f in files:
             side = []
             for t in (old, new):
@@ -98,6 +117,11 @@ def main():
                     keyed[(b, seen[b])] = k
                     seen[b] += 1
                 side.append(keyed)
+            sides[f] = side
+        at = lambda x: (x[1], int(x[2]) if len(x) > 2 else 0)   # noqa: E731
+        moved = [(src, dst, sides[src[0]][0].pop(at(src)), sides[dst[0]][1].pop(at(dst))) for src, dst in moved]
+        for f in files:
+            side = sides[f]
             same = 0
             report = []
             for key in list(side[0]) + [k for k in side[1] if k not in side[0]]:
@@ -105,15 +129,17 @@ def main():
                 if a is None or b is None:
                     differ += 1
                     report.append("  ONLY IN %s: %s" % ("OLD" if b is None else "NEW", (a or b)[1]))
-                elif a[2] == b[2] and a[3] == b[3]:
-                    same += 1
                 else:
-                    differ += 1
-                    report.append("  DIFFERS: %s\n       ->  %s\n    instructions %d -> %d" % (a[1], b[1], len(a[2]), len(b[2])))
-                    report.append("    " + "  ".join("%s %d -> %d" % (m, a[3][m], b[3][m]) for m in META))
-                    cnt = [collections.Counter(c for l in k[2] for c in CLASSES if c in l) for k in (a, b)]
-                    report.append("    " + "  ".join("%s %d -> %d" % (c, cnt[0][c], cnt[1][c]) for c in CLASSES))
+                    same += compare(a, b, report)
+                    differ += 1 - compare(a, b, [])
             print("%-22s %3d kernels identical (instruction text and metadata)%s" % (f, same, ", the others:" if report else ""))
+            for r in report:
+                print(r)
+        for src, dst, a, b in moved:
+            report = []
+            ok = compare(a, b, report)
+            differ += 1 - ok
+            print("MOVED %s -> %s (%s): %s" % (":".join(src), ":".join(dst), b[1].split("(")[0], "identical (instruction text and metadata)" if ok else "NOT identical"))
             for r in report:
                 print(r)
     print("RESULT: %s" % ("every kernel identical" if not differ else "%d kernels differ or have no partner" % differ))

@@ -16,7 +16,7 @@ LO, HI = -3, 3                 # the integer lattice's entries
 D_MAX = 128                    # 9 * 128 = 1152 < 2048
 UNIT_D = 64
 UNIT = 0.125
-RANGE_RUN = 2048               # csrc/range_select.hip: the hits of a query are sorted in runs of this length, then merged
+RANGE_RUN = 2048               # csrc/csr_order.hip (CSR_RUN): the hits of a query are sorted in runs of this length, then merged
 # (rows scoring >= tau, rows scoring == tau) per planted query of a gallery of BOUNDARY_N rows: hit counts on and either side of
 # one run and of two runs, with tie classes that reach across positions 2048 and 4096
 BOUNDARY_N = 4200

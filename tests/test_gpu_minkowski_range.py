@@ -121,8 +121,8 @@ def test_ties_order_and_the_merge_passes(lib):
     one LDS-sorted run of the ordering kernel (the length is read from the source), so its list goes through the merge passes,
     beside a query with no hit and one with a single hit"""
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "image-search-engine-for-historical-research_amd",
-                            "csrc", "minkowski_range.hip")).read()
-    run = int(re.search(r"constexpr int MINK_RANGE_RUN = (\d+);", src).group(1))
+                            "csrc", "csr_order.hip")).read()
+    run = int(re.search(r"constexpr int CSR_RUN = (\d+);", src).group(1))
     n, d = 4 * run + 37, 12
     rows = _lattice(4, n, d)
     q = _lattice(5, QT + 1, d)

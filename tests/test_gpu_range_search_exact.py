@@ -1,4 +1,5 @@
-"""GPU: range search (mi_range_search, csrc/api_range.hip, csrc/range_select.hip) pinned to the exact answer on lattice data.
+"""GPU: range search (mi_range_search, csrc/api_range.hip, csrc/range_select.hip, csrc/csr_order.hip) pinned to the exact answer
+on lattice data.
 
 The data of tests/_lattice_truth.py scores exactly in every number format and summation order (test_lattice_truth_cpu.py), so
 the host truth is the device's answer to the bit and the contract at the top of api_range.hip is asserted with ==: every row
@@ -166,6 +167,36 @@ def test_run_boundaries(runs):
     _same(_ask(g, Q, -INF), _truth(S, -INF), "every row of every query")
 
 
+def test_signed_scores_through_two_merge_passes():
+    """The hits are keyed by the complement of the score's key and ordered ascending (csrc/csr_order.hip): one query whose hits
+    span negative, zero and positive scores in five tie classes of hundreds of rows each, more than three runs of them (four
+    sorted runs, two merge passes), beside a query with no hit and one with exactly one."""
+    run = lt.RANGE_RUN
+    rng = np.random.default_rng(8229)
+    n, d, tau = 4 * run + 37, 32, -1
+    X, Q = lt.planted_gallery(rng, n, d, tau, [(3 * run + 356, 900), (0, 0), (1, 1)])
+    S = lt.int_scores(X, Q)
+    want = _truth(S, tau)
+    hits = np.diff(want[0])
+    sc0 = want[2][:hits[0]]
+    classes, sizes = np.unique(sc0, return_counts=True)
+    # the truth first: more than three runs of hits, classes below, at and above zero, each of hundreds of rows
+    assert hits.tolist() == [3 * run + 356, 0, 1] and hits[0] > 3 * run
+    assert classes.tolist() == [-1.0, 0.0, 1.0, 2.0, 3.0] and (sizes >= 900).all()
+    g = _gallery(X)
+    try:
+        got = _ask(g, Q, float(tau))
+        _same(got, want, "signed scores, two merge passes")
+        ids0, got0 = got[1][:hits[0]], got[2][:hits[0]]
+        assert (np.diff(got0) <= 0).all()                    # descending across zero
+        for v in classes:
+            assert (np.diff(ids0[got0 == v]) > 0).all()      # ids ascend inside every tie class
+        for q in range(3):
+            _same(_ask(g, Q[q:q + 1], float(tau)), _truth(S[q:q + 1], tau), "signed scores, query %d alone" % q)
+    finally:
+        g.close()
+
+
 def test_chunk_ladder(runs):
     """survivor_cap 1024: a query with more than 1024 survivors in a chunk makes the chunk overflow and be done again in halves"""
     g, X, Q, S, tau = runs
@@ -305,3 +336,29 @@ def test_ids_offset_append_remove():
         for h in (g, go, ga, fresh):
             if h is not None:
                 h.close()
+
+
+def test_two_batch_capacity_protocol(small):
+    """nq = QB + 1 (QB = 1024 queries a batch, api_internal.h): the ordering stage's device-side guard is given the batch's room;
+    one entry short, whichever batch runs out, the call returns MI_ERR_CAPACITY with out_lims complete and out_idx untouched,
+    and at max_results = total it succeeds"""
+    from isehr_amd import _lib
+    g, X, Q, S, tau = small
+    nq = 1025
+    q = np.ascontiguousarray(Q[:nq])
+    want = _truth(S[:nq], tau)
+    total, first = int(want[0][-1]), int(want[0][1024])
+    assert 0 < first < total                                 # both batches have hits
+    P = lambda a: a.ctypes.data_as(C.c_void_p)   # noqa: E731
+    lib = _lib.load()
+    for cap in (total - 1, first, first - 1, 1, 0):          # the second batch does not fit; the first does not fit
+        lims = np.full(nq + 1, -7, np.int64)
+        idx = np.full(total, -3, np.int64)
+        sc = np.full(total, 5.0, np.float32)
+        rc = lib.mi_range_search(g._h, P(q), nq, _lib.MI_F32, q.shape[1], 1, float(tau), cap, P(lims), P(idx), P(sc), None)
+        assert rc == _lib.MI_ERR_CAPACITY, cap
+        assert np.array_equal(lims, want[0])                 # lims complete
+        assert (idx == -3).all() and (sc == 5.0).all()       # the output arrays untouched
+    rc = lib.mi_range_search(g._h, P(q), nq, _lib.MI_F32, q.shape[1], 1, float(tau), total, P(lims), P(idx), P(sc), None)
+    assert rc == 0
+    _same((lims, idx, sc), want, "two batches at max_results = total")
