@@ -46,6 +46,15 @@ class FilterInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class GroupInfo(C.Structure):
+    """mi_group_info: what one mi_knn_search_grouped call did."""
+    _fields_ = [("groups", C.c_int64), ("path", C.c_int32), ("kprime", C.c_int32), ("rerun_queries", C.c_int64),
+                ("excluded_found", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/mi355_retrieval.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "mi_last_error": (C.c_char_p, []),
@@ -72,6 +81,11 @@ SIGNATURES = {
                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, c_f64p]),
     "mi_knn_search_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(FilterInfo), c_f64p]),
+    "mi_gallery_set_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "mi_gallery_get_groups": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mi_gallery_group_count": (C.c_int, [C.c_void_p, c_i64p]),
+    "mi_knn_search_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GroupInfo), c_f64p]),
     "mi_gallery_create_l2": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int,
                                        C.c_int64, C.c_int64, C.POINTER(C.c_void_p)]),
     "mi_knn_search_l2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
@@ -438,6 +452,17 @@ def _upload_allow(bits, tdev):
     return None if bits is None else torch.from_numpy(np.ascontiguousarray(bits).view(np.int64)).to(tdev)
 
 
+def group_labels(labels):
+    """Group labels as the library takes them: a contiguous int32 array [n].  Raises ValueError on labels that are no integers
+    or lie outside int32 (what a label below -1 means is the library's to refuse)."""
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or not (np.issubdtype(lab.dtype, np.integer) or lab.dtype == np.bool_):
+        raise ValueError("group labels must be a 1-D integer array")
+    if lab.size and (lab.min() < -2 ** 31 or lab.max() > 2 ** 31 - 1):
+        raise ValueError("group labels must fit int32")
+    return np.ascontiguousarray(lab, dtype=np.int32)
+
+
 MINK_L1, MINK_LINF, MINK_LP = 1, 2, 3
 MINK_METRICS = {"l1": MINK_L1, "linf": MINK_LINF, "lp": MINK_LP}
 MINK_MAX_K = 2048
@@ -729,6 +754,55 @@ class Gallery(_Handle):
         idx, sc, secs = self._topk(nq, k, (np.float32,), lambda idx, sc, secs: load().mi_knn_search_filtered(
             self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, int(k), bits_p, memspace, idx, sc, C.byref(info), secs))
         return idx, sc, secs, info.as_dict()
+
+    def set_groups(self, labels):
+        """One int32 label per row of the shard (mi_gallery_set_groups): labels >= 0 name a group and need not be dense, -1 makes
+        the row a group of its own; None clears the groups.  append(), append_device() and remove() drop the labels: set them
+        again before the next search_grouped.  Raises ValueError, before the library is called, on labels that are no integers
+        or do not fit int32."""
+        if labels is None:
+            with self._lock:
+                check(load().mi_gallery_set_groups(self._h, None, 0, MI_HOST))
+            return
+        lab = group_labels(labels)
+        with self._lock:
+            check(load().mi_gallery_set_groups(self._h, C.c_void_p(lab.ctypes.data), lab.size, MI_HOST))
+
+    def groups(self):
+        """-> the labels as given, int32 [n]."""
+        out = np.empty(self.n, dtype=np.int32)
+        with self._lock:
+            check(load().mi_gallery_get_groups(self._h, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def group_count(self):
+        """-> the number of groups, every row labelled -1 counting once."""
+        out = C.c_int64()
+        with self._lock:
+            check(load().mi_gallery_group_count(self._h, C.byref(out)))
+        return out.value
+
+    def search_grouped(self, queries, k, exclude=None, return_labels=False, return_info=False):
+        """Exact grouped top-k (mi_knn_search_grouped): search()'s ranking of every row walked from the top, one row per group
+        -- the group's best, the lowest id among equal scores --, k groups per query, ordered by (that row's score desc, its id
+        asc).  exclude: None, one label, or one label per query: rows of that label are skipped (-1 or a label no row carries
+        skips nothing).  -> (idx int64 [Q,k], scores float32 [Q,k], seconds), then labels int32 [Q,k] (the caller's labels, -1
+        for a singleton row) with return_labels and the info dict (groups, path, kprime, rerun_queries, excluded_found) with
+        return_info.  Fewer than k eligible groups: trailing ids -1, scores -inf, labels -1.  Every score is the one `search`
+        gives that row."""
+        a, code, rs, cs = self._queries(queries)
+        nq = a.shape[0]
+        ex = None
+        if exclude is not None:
+            ex = group_labels(np.broadcast_to(np.asarray(exclude), (nq,)) if np.ndim(exclude) == 0 else exclude)
+            if ex.size != nq:
+                raise ValueError("exclude holds %d labels for %d queries" % (ex.size, nq))
+        lab = np.empty((nq, int(k)), dtype=np.int32)
+        info = GroupInfo()
+        idx, sc, secs = self._topk(nq, k, (np.float32,), lambda idx, sc, secs: load().mi_knn_search_grouped(
+            self._h, C.c_void_p(_base_pointer(a)), nq, code, rs, cs, int(k), None if ex is None else C.c_void_p(ex.ctypes.data),
+            idx, sc, C.c_void_p(lab.ctypes.data), C.byref(info), secs))
+        return (idx, sc, secs) + ((lab,) if return_labels else ()) + ((info.as_dict(),) if return_info else ())
 
     def search_l2(self, queries, k, allow=None):
         """Exact squared-L2 top-k of a gallery built by l2_from_host -> (ids int64 [Q,k], dist float32 [Q,k], dist64 float64

@@ -330,6 +330,7 @@ int mi_gallery_append_device(mi_gallery* g, const float* rows_dev, int64_t m, vo
   g->n += m;
   g->npad = round_up(g->n, TILE);
   filter_invalidate(g);        // the compacted sub-gallery of the filtered search was cut from the old rows
+  groups_drop(g);              // the group labels named the old rows
   return MI_OK;
 }
 
@@ -376,6 +377,7 @@ int mi_gallery_append(mi_gallery* g, const void* data, int64_t m, int dtype, int
   g->n += m;
   g->npad = round_up(g->n, TILE);
   filter_invalidate(g);        // the compacted sub-gallery of the filtered search was cut from the old rows
+  groups_drop(g);              // the group labels named the old rows
   return MI_OK;
 }
 
@@ -432,6 +434,7 @@ int mi_gallery_append_whitened_device(mi_gallery* g, const void* X_dev, int64_t 
   g->n += m;
   g->npad = round_up(g->n, TILE);
   filter_invalidate(g);        // the compacted sub-gallery of the filtered search was cut from the old rows
+  groups_drop(g);              // the group labels named the old rows
   return MI_OK;
 }
 

@@ -10,6 +10,8 @@
 //   api_options.hip   per-handle options, statistics, profiling, flags, diagnostics
 //   api_range.hip     exact range search: fixed-threshold chunk schedule, overflow split, dense chunks, CSR tail
 //   api_filter.hip    filtered top-K: compacted sub-gallery (cached per bitmap) or over-fetch with a certificate
+//   api_group.hip     grouped top-K (one row per group, one excluded group per query): labels on the handle, over-fetch with a
+//                     certificate or the dense float64 fallback over the group CSR
 //   api_l2.hip        squared-L2 metric: L2 galleries (hidden bias columns), top-K by distance (host / device), dense checker
 //   api_refine.hip    exact re-ranking of index shortlists on the stored rows (mi_refine*): gather launch + per-query sort
 //   api_remove.hip    row removal in place: keep-list, block-ordered move through a bounded staging area, invalidations
@@ -99,6 +101,8 @@ extern MI_INTERNAL std::atomic<int64_t> g_hamming_range_bytes;  // mi_hamming_ra
 extern MI_INTERNAL std::atomic<int64_t> g_minkowski_range_bytes; // mi_range_search_minkowski* / mi_minkowski_self_range: bytes of the value matrix and counts of a chunk (default 256 MiB)
 extern MI_INTERNAL std::atomic<int> g_hamming_range_early_exit; // ... drop a (block, query) whose partial sums are all above the radius (default 1)
 extern MI_INTERNAL std::atomic<int64_t> g_pq_matrix_bytes;      // mi_pq_search*: bytes of the distance matrix (default 2 GiB); mi_ivfpq_search*: of the partial lists
+extern MI_INTERNAL std::atomic<int64_t> g_group_dense_bytes;    // mi_knn_search_grouped: bytes of the float64 scores and group tables of a fallback sub-batch (default 1 GiB)
+extern MI_INTERNAL std::atomic<int> g_group_overfetch;          // mi_knn_search_grouped: f of the over-fetch depth K' = f k + 32 (default 4)
 extern MI_INTERNAL std::atomic<int64_t> g_forest_build_bytes;   // mi_forest_build: bytes of the scratch of a group of trees (default 1 GiB)
 constexpr size_t SPARE_MAX_BYTES = (size_t)16 << 30;
 MI_INTERNAL void spare_release_locked();
@@ -119,6 +123,7 @@ MI_INTERNAL const char* last_error_message();
   } while (0)
 #include "device_buf.h"   // DeviceBuf<T>, DeviceBufSet, grow_all
 #include "graph_table.h"  // GraphTable
+#include "group_plan.h"   // GroupPlan
 
 
 // The host half of a row removal on a PQ or an IVF-PQ index (mi_pq_remove_rows, mi_ivfpq_remove_rows; defined in api_pq.hip): the
@@ -340,6 +345,33 @@ struct mi_gallery {
     std::vector<uint64_t> last_key;      // the bitmap of the previous call (auto compacts a bitmap it sees twice in a row)
     int64_t last_key_n = -1;
   } filt{scratch};
+  // grouped top-K search (api_group.hip): the labels of mi_gallery_set_groups in the dense form the kernels read, and the
+  // grow-only buffers of a call.  Dropped by whatever changes n or the rows (mi_gallery_append*, mi_gallery_remove_rows:
+  // groups_drop); never written to the gallery file
+  int group_path = 0;                  // option "group_path": 0 = auto, 1 = always the dense fallback, 2 = always over-fetch
+  struct GroupState {
+    explicit GroupState(DeviceBufSet& s) : grp(s), group_off(s), group_rows(s), chunk_g0(s), label_of_group(s), excl(s), ok(s), idx(s),
+                                           sc(s), lab(s), qbuf(s), dense(s), key{DeviceBuf<uint64_t>(s), DeviceBuf<uint64_t>(s)},
+                                           row{DeviceBuf<uint32_t>(s), DeviceBuf<uint32_t>(s)}, lims(s), cand_rows(s), cand_cnt(s),
+                                           cand_score(s) {}
+    bool valid = false;                  // the plan below is the one of the gallery's current n rows
+    GroupPlan plan;                      // host copy (group_plan.h): label -> dense id, G, the chunk count
+    std::vector<int32_t> labels;         // the labels as given (mi_gallery_get_groups)
+    DeviceBuf<uint32_t> grp, group_off, group_rows, chunk_g0;
+    DeviceBuf<int32_t> label_of_group;
+    DeviceBuf<uint32_t> excl;            // [nq] dense id of the group a query excludes (GROUP_NONE = none)
+    DeviceBuf<uint32_t> ok;              // [nq] over-fetch certificate per query
+    DeviceBuf<int64_t> idx;              // [nq][k] answer of a path
+    DeviceBuf<float> sc;
+    DeviceBuf<int32_t> lab;
+    DeviceBuf<char> qbuf;                // queries the over-fetch could not certify, packed
+    DeviceBuf<double> dense;             // [queries of a sub-batch][n] float64 scores ("group_dense_bytes")
+    DeviceBuf<uint64_t> key[2];          // [queries of a sub-batch][G] group table (ping-pong of csr_order.hip's merge passes)
+    DeviceBuf<uint32_t> row[2];
+    DeviceBuf<int64_t> lims;             // [queries of a sub-batch + 1] and, behind them, the list total csr_order.hip reads
+    DeviceBuf<uint32_t> cand_rows, cand_cnt;   // [queries of a sub-batch][k] rows taken, re-scored by rescore_kernel
+    DeviceBuf<double> cand_score;
+  } groups{scratch};
   // squared-L2 search (api_l2.hip)
   struct L2Scratch {
     explicit L2Scratch(DeviceBufSet& s) : qraw(s), qaug(s), ids(s), oidx(s), odist(s), odist64(s) {}
@@ -506,6 +538,8 @@ MI_INTERNAL void filter_invalidate(mi_gallery* g);      // rows or image type of
 MI_INTERNAL int filtered_search_host(mi_gallery* g, const void* q, int64_t nq, int dtype, int64_t row_stride, int64_t col_stride,
                                      int32_t k, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
                                      mi_filter_info* out_info, double* out_seconds, bool l2_caller);
+// ---- api_group.hip
+MI_INTERNAL void groups_drop(mi_gallery* g);            // n or the rows changed: the labels no longer name them
 // ---- api_minkowski.hip
 // the argument checks of every Minkowski entry point (*op: the term the kernels evaluate, MINK_OP_*); what the gallery must be
 MI_INTERNAL int mink_check(const mi_gallery* g, int64_t nq, int metric, double p, int32_t k, int* op);

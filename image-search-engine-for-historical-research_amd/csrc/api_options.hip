@@ -113,6 +113,7 @@ int mi_get_option(const mi_gallery* g, const char* name, double* out_value) {
   else if (n == "filter_path") *out_value = g->filter_path;
   else if (n == "filter_compact_max") *out_value = g->filter_compact_max;
   else if (n == "filter_cache") *out_value = g->filter_cache;
+  else if (n == "group_path") *out_value = g->group_path;
   else return fail(MI_ERR_INVALID, "unknown option: " + n);
   return MI_OK;
 }
@@ -182,6 +183,10 @@ int mi_set_option(mi_gallery* g, const char* name, double value) {
       filter_release_sub(g);
       filter_invalidate(g);
     }
+  }
+  else if (n == "group_path") {
+    REQUIRE(value == 0 || value == 1 || value == 2, "group_path: 0 (auto), 1 (dense fallback) or 2 (over-fetch)");
+    g->group_path = (int)value;
   }
   else return fail(MI_ERR_INVALID, "unknown option: " + n);
   return MI_OK;

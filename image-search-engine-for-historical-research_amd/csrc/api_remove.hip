@@ -113,6 +113,7 @@ int gallery_remove_rows_locked(mi_gallery* g, const uint64_t* remove_bits, int m
   g->n = m;
   g->npad = new_pad;
   filter_invalidate(g);          // a remove followed by an append of as many rows restores n: the sub-gallery's key would match
+  groups_drop(g);              // the group labels named the old rows
   g->samp_for_n = -1;            // the threshold samples are keyed by n in the same way
   g->samp_f32_for_n = -1;
   diffusion_state_free(g);       // the offline matrix holds ids of the old numbering

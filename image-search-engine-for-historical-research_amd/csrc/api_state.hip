@@ -54,6 +54,13 @@ std::atomic<int64_t> g_pq_remove_block_rows{PQ_REMOVE_BLOCK_ROWS_DEFAULT};
 // through the build in groups that fit it, one tree at the least
 constexpr int64_t FOREST_BUILD_DEFAULT = (int64_t)1 << 30;
 std::atomic<int64_t> g_forest_build_bytes{FOREST_BUILD_DEFAULT};
+// mi_set_global_option("group_dense_bytes", ...): upper limit of what one sub-batch of the dense fallback of mi_knn_search_grouped holds
+// (api_group.hip): float64 scores [queries][rows] and the group tables; one query at the least.  "group_overfetch": the factor f of
+// the over-fetch depth K' = min(2048, n, f k + 32); 4 is a placeholder until scripts/grouped_search_timing.py has run
+constexpr int64_t GROUP_DENSE_DEFAULT = (int64_t)1 << 30;
+constexpr int GROUP_OVERFETCH_DEFAULT = 4;
+std::atomic<int64_t> g_group_dense_bytes{GROUP_DENSE_DEFAULT};
+std::atomic<int> g_group_overfetch{GROUP_OVERFETCH_DEFAULT};
 void spare_release_locked() {
   if (g_spare.device < 0) return;
   int cur = 0;
@@ -302,6 +309,14 @@ int mi_set_global_option(const char* name, double value) {
     REQUIRE(value >= 0 && value <= 1e13, "forest_build_bytes: bytes of the scratch of mi_forest_build (0 = default, 1 GiB)");
     g_forest_build_bytes = value == 0 ? FOREST_BUILD_DEFAULT : (int64_t)value;
   }
+  else if (n == "group_dense_bytes") {
+    REQUIRE(value >= 0 && value <= 1e13, "group_dense_bytes: bytes of a sub-batch of the dense fallback of the grouped search (0 = default, 1 GiB)");
+    g_group_dense_bytes = value == 0 ? GROUP_DENSE_DEFAULT : (int64_t)value;
+  }
+  else if (n == "group_overfetch") {
+    REQUIRE(value == 0 || (value >= 1 && value <= 2048), "group_overfetch: the factor f of the over-fetch depth f k + 32, 1 .. 2048 (0 = default, 4)");
+    g_group_overfetch = value == 0 ? GROUP_OVERFETCH_DEFAULT : (int)value;
+  }
   else if (n == "release_spares") {
     // gives the spare slots back NOW and leaves the mode alone (a caller that is done with its galleries for a while --
     // nnsearch.drop_cached_galleries -- or a co-tenant that needs the memory)
@@ -328,6 +343,8 @@ int mi_get_global_option(const char* name, double* out_value) {
   else if (n == "hamming_range_early_exit") *out_value = g_hamming_range_early_exit.load();
   else if (n == "pq_matrix_bytes") *out_value = (double)g_pq_matrix_bytes.load();
   else if (n == "forest_build_bytes") *out_value = (double)g_forest_build_bytes.load();
+  else if (n == "group_dense_bytes") *out_value = (double)g_group_dense_bytes.load();
+  else if (n == "group_overfetch") *out_value = g_group_overfetch.load();
   else if (n == "spare_bytes") {
     // device memory this process holds in the spare slots right now (gallery buffers + search workspace of destroyed handles)
     std::lock_guard<std::mutex> lock(g_spare_mu);

@@ -268,6 +268,28 @@ void launch_filter_overfetch(const int64_t* in_idx, const float* in_sc, int64_t 
 void launch_filter_remap(const int64_t* sidx, const float* ssc, int64_t nq, int32_t ke, int32_t k, const uint32_t* rows,
                          int64_t m, int64_t row_offset, int64_t* out_idx, float* out_sc, hipStream_t stream);
 
+// group_select.hip -- grouped top-K search (api_group.hip).  grp [n]: dense group id of every local row;
+// label_of_group [G]: the caller's label (-1 for a singleton row); the group CSR group_off [G + 1] / group_rows [n] (rows of a group
+// contiguous, ascending); chunk_g0 [chunks + 1]: the CSR cut into chunks of whole groups of at most GROUP_CHUNK_ROWS rows, a larger
+// group being a chunk of its own; excl [nq]: the dense id of the group a query excludes, 0xFFFFFFFF = none
+constexpr int GROUP_CHUNK_ROWS = 2048, GROUP_BEST_THREADS = 256;
+// in_idx / in_sc [nq][kp <= 2048] -> the first k group-distinct entries [nq][k] (padding -1 / -inf / -1), ok [nq] the certificate
+void launch_group_collapse(const int64_t* in_idx, const float* in_sc, int64_t nq, int32_t kp, int32_t k, const uint32_t* grp,
+                           const int32_t* label_of_group, int64_t n, int64_t row_offset, const uint32_t* excl, int32_t covers,
+                           int64_t* out_idx, float* out_sc, int32_t* out_lab, uint32_t* ok, hipStream_t stream);
+// dense [nq][ld] float64 scores -> out_key / out_row [nq][G]: ~f64_key_nan_lowest(best value) and the lowest row that has it, per
+// group; the excluded group's entry is (~0, ~0u).  nq <= 65535
+void launch_group_best(const double* dense, int64_t ld, int32_t nq, const uint32_t* grp, const uint32_t* group_rows,
+                       const uint32_t* group_off, const uint32_t* chunk_g0, int64_t chunks, int64_t G, const uint32_t* excl,
+                       uint64_t* out_key, uint32_t* out_row, hipStream_t stream);
+void launch_group_lims(int64_t* lims, int64_t* total, int32_t nq, int64_t G, hipStream_t stream);   // lims[i] = i G, *total = 0
+// row [nq][G] ordered by csr_order.hip -> cand_rows [nq][k], cand_cnt [nq] (what launch_rescore takes, rcap = k)
+void launch_group_take(const uint32_t* row, int64_t G, int32_t nq, int32_t k, uint32_t* cand_rows, uint32_t* cand_cnt,
+                       hipStream_t stream);
+void launch_group_emit(const uint32_t* cand_rows, const uint32_t* cand_cnt, const double* cand_score, const uint32_t* grp,
+                       const int32_t* label_of_group, int32_t nq, int32_t k, int64_t row_offset, int64_t* out_idx, float* out_sc,
+                       int32_t* out_lab, hipStream_t stream);
+
 // row_remove.hip -- in-place row removal (api_remove.hip): surviving rows rows[j0 .. j1) (padding rows up to j1_pad, j >= m,
 // written as zeros) gathered into a staging area of the gallery's own layout, and the staging area written back as three
 // contiguous runs (rows_f32 f32 rows, rows_pad image rows and RowStats)

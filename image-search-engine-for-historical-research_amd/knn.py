@@ -91,6 +91,25 @@ class KNN:
         ids, sims, _ = self.gallery.search(queries, int(k))
         return sims, ids
 
+    def set_groups(self, labels):
+        """One integer label per database row ('cosine' only): rows of one label are one item for search_grouped; -1 makes a row
+        an item of its own, None clears the labels.  remove_ids drops them."""
+        if self.method != "cosine":
+            raise NotImplementedError("groups are defined for 'cosine' only")
+        self.gallery.set_groups(labels)
+
+    def search_grouped(self, queries, k, exclude=None):
+        """-> (sims float32 [Q,k], ids int64 [Q,k]) like search, but at most one row per group -- the group's best --, k groups
+        per query (the collapse / group-by search of other engines).  exclude: None, one label or one per query, whose rows are
+        skipped.  Fewer than k groups: trailing ids -1, sims -inf.  'cosine' only."""
+        if self.method != "cosine":
+            raise NotImplementedError("search_grouped is defined for 'cosine' only")
+        queries = np.asarray(queries)
+        if queries.dtype != np.float32:
+            queries = queries.astype(np.float32)
+        ids, sims, _ = self.gallery.search_grouped(queries, int(k), exclude)
+        return sims, ids
+
     def range_search(self, queries, thresh):
         """-> (lims int64 [Q+1], D float32 [lims[-1]], I int64 [lims[-1]]), the return shape of faiss's `range_search`: the
         results of query i are D/I[lims[i]:lims[i+1]].  Every row whose exact inner product with the query is >= thresh

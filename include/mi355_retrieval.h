@@ -162,6 +162,51 @@ int mi_knn_search_filtered(mi_gallery* g, const void* q, int64_t nq, int dtype, 
                            int32_t k, const uint64_t* allow_bits, int allow_memspace, int64_t* out_idx, float* out_score,
                            mi_filter_info* out_info, double* out_seconds);
 
+/* ---- exact grouped top-K (collapse / group-by search): the best row of every group, k groups per query, one excluded group per
+ * query.  The selection loop of the reference's hard-negative mining (create_epoch_tuples, src/datasets/traindataset.py:219-243,
+ * 466-490: full sort of every column, skip the query's own cluster, at most one image per cluster).  DESIGN.md 5.10b.
+ * mi_gallery_set_groups: one int32 label per LOCAL row, n == the gallery's n (else MI_ERR_INVALID); memspace MI_HOST or MI_DEVICE
+ * (device labels are copied to the host first and must be complete).  Labels >= 0 are arbitrary, need not be dense; -1 makes the
+ * row a group of its own; any other negative label is MI_ERR_INVALID.  labels == NULL clears the groups.  The handle keeps the
+ * labels and a dense relabelling (built on the host, uploaded).  Whatever changes n or the rows -- mi_gallery_append*,
+ * mi_gallery_remove_rows -- DROPS the labels: the grouped search then refuses (MI_ERR_INVALID, "not in step") until labels are
+ * set again, like an index on a changed gallery.  mi_gallery_save does not write them.
+ * mi_gallery_get_groups: the labels as given, [n] int32 to the host.  mi_gallery_group_count: the number of groups G, every -1 row
+ * counting once.  Both are MI_ERR_INVALID without labels. */
+int mi_gallery_set_groups(mi_gallery* g, const int32_t* labels, int64_t n, int memspace);
+int mi_gallery_get_groups(mi_gallery* g, int32_t* out_host);
+int mi_gallery_group_count(mi_gallery* g, int64_t* out);
+/* mi_knn_search_grouped: take mi_knn_search's complete ranking of every stored row for a query, (score desc, id asc), walk it from
+ * the top, keep a row if its group has not been kept yet and its label is not exclude_labels[query] (host array [nq] or NULL; -1
+ * or a label no row carries excludes nothing), stop at k kept rows.  So the row kept for a group is the group's best row (the
+ * lowest id among equal scores) and the groups come in the order of (their best row's score desc, that row's id asc).
+ * out_idx [nq][k] = row_offset + local row; out_score [nq][k] (may be NULL) the f32 mi_knn_search returns for that row, bit for
+ * bit; out_label [nq][k] (may be NULL) the caller's label, -1 for a singleton row.  Fewer than k eligible groups: trailing ids -1,
+ * scores -INFINITY, labels -1.  1 <= k <= 2048.  With every row labelled -1 and no exclusion the output is mi_knn_search's.
+ * Host input and host output, queries as in mi_knn_search (q_dtype is its dtype, MI_F32 or MI_F64: float64 is rounded to float32 as
+ * every query batch is; every layout is swept by tests/test_gpu_input_layouts_grouped.py); out_info and out_seconds may be NULL.  Like mi_knn_search_filtered the
+ * call completes a pending deferred tail first and leaves the sticky flags as it found them.  MI_ERR_UNSUPPORTED on an L2
+ * gallery; MI_ERR_INVALID on a gallery without labels in step with its rows.
+ * Two exact paths (option "group_path" 0 = auto, 1 = always the fallback, 2 = always the over-fetch; both give the same ids,
+ * score bits and labels): 2 = the unfiltered search at depth K' = min(2048, n, f k + 32) (global option "group_overfetch", f = 4)
+ * collapsed on the device; a query is certified when it kept k rows or K' covered the shard.  1 = what the over-fetch cannot
+ * certify (a query whose own item has more than K' rows at the top): dense float64 scores of sub-batches of queries (global
+ * option "group_dense_bytes", default 1 GiB, one query at the least), every group reduced to its best row over the group CSR,
+ * the G entries of a query ordered, the first k written.
+ * Out of scope: more than one row per group; an allow bitmap combined with groups; L2 and Minkowski galleries; the binary and PQ
+ * index families; merging grouped answers across shards (a per-shard call honours row_offset, but a merge across shards must
+ * collapse again); saving the labels with the gallery. */
+typedef struct mi_group_info {
+  int64_t groups;          /* G of the gallery */
+  int32_t path;            /* 1 = dense fallback for every query, 2 = over-fetch */
+  int32_t kprime;          /* over-fetch depth used (0 on path 1) */
+  int64_t rerun_queries;   /* queries the over-fetch could not certify; they were answered by the fallback */
+  int64_t excluded_found;  /* queries whose exclude label names a group of the gallery */
+} mi_group_info;
+int mi_knn_search_grouped(mi_gallery* g, const void* q, int64_t nq, int q_dtype, int64_t row_stride, int64_t col_stride,
+                          int32_t k, const int32_t* exclude_labels, int64_t* out_idx, float* out_score, int32_t* out_label,
+                          mi_group_info* out_info, double* out_seconds);
+
 /* ---- exact squared-L2 (Euclidean) top-K on raw descriptors: faiss IndexFlatL2 behind KNN(database, 'euclidean')
  * (src/utils/knn.py:33-40), the metric string every reference entry point passes (src/offline.py:112, src/online.py:137,
  * src/test_rOP1m.py:156).  On rows that are not unit length its order differs from the inner product's.  DESIGN.md 5.11.
@@ -1205,7 +1250,9 @@ int mi_profile_launch_ms(mi_gallery* g, float* out_host, int64_t cap, int64_t* o
  * was built from, and -- not all rows allowed -- whenever it equals the previous call's; default 0.15, the crossover of first
  * calls at 1 and 70 queries measured in DESIGN.md 5.10), "filter_cache" (1 = keep the compacted
  * sub-gallery for the next call with an equal bitmap (default); 0 = free it now and at the end of every call, and do not
- * compact a bitmap only because it came twice; a kept sub-gallery holds up to 12 KB of HBM per allowed row at D = 2048).
+ * compact a bitmap only because it came twice; a kept sub-gallery holds up to 12 KB of HBM per allowed row at D = 2048),
+ * "group_path" (mi_knn_search_grouped: 0 = auto (default: the over-fetch, and the dense fallback for what it cannot certify),
+ * 1 = the dense fallback for every query, 2 = always the over-fetch, which still re-runs what it cannot certify).
  * mi_get_option also answers "image_dtype" (1 = fp16, 0 = bf16; read-only, see mi_gallery_set_image_dtype),
  * "sample_rows" (rows of the threshold sample in effect) and "metric" (an mi_metric value; read-only). */
 int mi_set_option(mi_gallery* g, const char* name, double value);
@@ -1244,12 +1291,15 @@ int mi_search_flags(mi_gallery* g, uint32_t* out_flags);
  * "hamming_range_early_exit": 1 (default) = the radius scan drops a (block, query) pair as soon as the partial distances of all
  * 64 rows exceed the radius; 0 = every pair is scanned to the last word.  The result does not depend on it.
  * "pq_matrix_bytes": upper limit of the distance matrix of a PQ index (mi_pq_search*; 0 = default, 2 GiB) and of the partial
- * lists of an IVF-PQ index (mi_ivfpq_search*). */
+ * lists of an IVF-PQ index (mi_ivfpq_search*).
+ * "group_overfetch": the factor f of the over-fetch depth K' = min(2048, n, f k + 32) of mi_knn_search_grouped (1 .. 2048; 0 =
+ * default, 4 -- a placeholder, not taken from a measurement yet).  "group_dense_bytes": upper limit of the float64 scores and group
+ * tables of one sub-batch of its dense fallback (0 = default, 1 GiB; one query at the least).  The result depends on neither. */
 int mi_set_global_option(const char* name, double value);
 /* "release_spares" (any value) gives the spare slots back now and leaves "keep_buffers" as it is.  An allocation of the library
  * that fails with out-of-memory releases them by itself and is tried once more; a gallery of other sizes than the spare releases
  * it when the device could not hold both.  mi_get_global_option reads "image_dtype", "host_ingest", "keep_buffers", "scatter_block_rows",
- * "remove_block_rows", "pq_remove_block_rows", "hamming_matrix_bytes", "hamming_range_bytes", "minkowski_range_bytes", "hamming_range_early_exit", "pq_matrix_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
+ * "remove_block_rows", "pq_remove_block_rows", "hamming_matrix_bytes", "hamming_range_bytes", "minkowski_range_bytes", "hamming_range_early_exit", "pq_matrix_bytes", "group_overfetch", "group_dense_bytes" and "spare_bytes": the device memory the process holds in the spare slots right now -- what a co-tenant of the GPU (the
  * extractor's PyTorch allocator) cannot see otherwise. */
 int mi_get_global_option(const char* name, double* out_value);
 
