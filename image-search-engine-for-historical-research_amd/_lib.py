@@ -164,6 +164,14 @@ SIGNATURES = {
     "mi_hamming_self_range": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                         c_f64p]),
     "mi_hamming_destroy": (C.c_int, [C.c_void_p]),
+    "mi_components_create": (C.c_int, [C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
+    "mi_components_reset": (C.c_int, [C.c_void_p]),
+    "mi_components_add_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "mi_components_add_csr": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "mi_components_add_hamming_self": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
+    "mi_components_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64p]),
+    "mi_components_info": (C.c_int, [C.c_void_p, c_i64p, C.POINTER(C.c_int32)]),
+    "mi_components_destroy": (C.c_int, [C.c_void_p]),
     "mi_lsh_encode_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                        C.c_void_p, C.c_int64, C.c_void_p]),
     "mi_lsh_encode": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int,
@@ -1662,6 +1670,86 @@ class BinaryGallery(_Handle):
         with self._lock:
             check(load().mi_hamming_get_codes(self._h, int(row0), nrows, out.ctypes.data_as(C.c_void_p)))
         return out
+
+
+def component_ids(a, what="ids"):
+    """Row ids as mi_components takes them: a contiguous int64 array [m], from integers of any dtype and stride (lists too).
+    Raises ValueError on anything that is not a 1-D array of integers; the range [0, n) is the library's to check."""
+    a = np.asarray(a)
+    if a.ndim != 1 or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+        raise ValueError("%s must be a 1-D integer array" % what)
+    if a.dtype == np.uint64 and a.size and a.max() > 2 ** 63 - 1:
+        raise ValueError("%s must fit int64" % what)
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+class Components(_Handle):
+    """Connected components of n rows on one MI355X (a `mi_components` handle): a union-find forest of 4 bytes per row, fed with
+    the hits of the near-duplicate self-joins.  labels()[v] is the smallest row of v's component, whatever order the edges came
+    in -- what Gallery.set_groups takes."""
+    _DESTROY = "mi_components_destroy"
+
+    def __init__(self, n, device=0):
+        h = C.c_void_p()
+        check(load().mi_components_create(int(n), int(device), C.byref(h)))
+        super().__init__(h.value)
+        self.n, self.device = int(n), int(device)
+
+    def reset(self):
+        """Every row a component of its own again."""
+        with self._lock:
+            check(load().mi_components_reset(self._h))
+
+    def add_pairs(self, i, j):
+        """Edges (i[e], j[e]): integer arrays of any integer dtype and stride, or lists.  An id outside [0, n) raises
+        RuntimeError and nothing is united."""
+        i, j = component_ids(i, "i"), component_ids(j, "j")
+        if i.size != j.size:
+            raise ValueError("i and j must have the same length")
+        with self._lock:
+            check(load().mi_components_add_pairs(self._h, C.c_void_p(i.ctypes.data), C.c_void_p(j.ctypes.data), i.size, MI_HOST))
+
+    def add_pairs_device(self, i_ptr, j_ptr, m):
+        """m edges in device arrays of int64 (complete when the call is made); ids checked on the device."""
+        with self._lock:
+            check(load().mi_components_add_pairs(self._h, C.c_void_p(i_ptr), C.c_void_p(j_ptr), int(m), MI_DEVICE))
+
+    def add_csr(self, row0, lims, idx):
+        """The CSR output of a self-join: query q is row row0 + q and its hits are idx[lims[q]:lims[q+1]] -- the (lims, ids) of
+        Gallery.range_search on stored rows, Gallery.self_range_minkowski or BinaryGallery.self_range (row_offset 0)."""
+        lims, idx = component_ids(lims, "lims"), component_ids(idx, "idx")
+        if lims.size < 1:
+            raise ValueError("lims must hold nq + 1 offsets")
+        with self._lock:
+            check(load().mi_components_add_csr(self._h, int(row0), C.c_void_p(lims.ctypes.data), C.c_void_p(idx.ctypes.data),
+                                               lims.size - 1, MI_HOST))
+
+    def add_csr_device(self, row0, lims_ptr, idx_ptr, nq):
+        """lims int64 [nq + 1] and the hits int64 [lims[nq]] in device arrays (complete when the call is made)."""
+        with self._lock:
+            check(load().mi_components_add_csr(self._h, int(row0), C.c_void_p(lims_ptr), C.c_void_p(idx_ptr), int(nq), MI_DEVICE))
+
+    def add_hamming_self(self, binary, row0, nrows, radius):
+        """Unites what binary.self_range(row0, nrows, radius) would report, without any pair being made: `binary` is a
+        BinaryGallery or an LSHIndex (its gallery is used) of exactly n codes with row_offset 0 on this device."""
+        g = getattr(binary, "gallery", binary)
+        with self._lock, g._lock:
+            check(load().mi_components_add_hamming_self(self._h, g._h, int(row0), int(nrows), int(radius)))
+
+    def labels(self):
+        """-> (labels int32 [n], n_groups): the smallest row of every row's component, and the number of components."""
+        out = np.empty(self.n, dtype=np.int32)
+        groups = C.c_int64()
+        with self._lock:
+            check(load().mi_components_labels(self._h, C.c_void_p(out.ctypes.data), MI_HOST, C.byref(groups)))
+        return out, groups.value
+
+    def labels_device(self, out_ptr):
+        """The labels into a device array of int32 [n] -> n_groups."""
+        groups = C.c_int64()
+        with self._lock:
+            check(load().mi_components_labels(self._h, C.c_void_p(out_ptr), MI_DEVICE, C.byref(groups)))
+        return groups.value
 
 
 LSH_MAX_BITS, LSH_MAX_DIM = 4096, 4096

@@ -12,10 +12,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmi355_retrieval.so")
 SOURCES = ["api_state.hip", "api_schedule.hip", "api_gallery.hip", "api_file.hip", "api_entry.hip", "api_aux.hip", "api_options.hip",
-           "api_online.hip", "api_range.hip", "api_filter.hip", "api_group.hip", "api_l2.hip", "api_refine.hip", "api_remove.hip", "api_hamming.hip", "api_lsh.hip", "api_pq.hip", "api_pq_train.hip", "api_kmeans.hip", "kmeans.hip", "api_pq_wide.hip",
+           "api_online.hip", "api_range.hip", "api_filter.hip", "api_group.hip", "api_l2.hip", "api_refine.hip", "api_remove.hip", "api_hamming.hip", "api_components.hip", "api_lsh.hip", "api_pq.hip", "api_pq_train.hip", "api_kmeans.hip", "kmeans.hip", "api_pq_wide.hip",
            "api_ivfpq.hip", "api_ivfflat.hip", "api_minkowski.hip", "minkowski.hip", "api_minkowski_range.hip", "minkowski_range.hip", "api_graph.hip", "api_pq_graph.hip", "api_forest.hip", "forest_project.hip", "forest_build.hip", "forest_search.hip", "graph_search.hip", "graph_build.hip", "pq_graph_search.hip", "ivfpq.hip", "ivfpq_residual.hip", "ivfflat.hip",
            "ingest.hip", "gemm_select.hip", "stream_select.hip", "select.hip", "range_select.hip", "csr_order.hip", "filter_select.hip", "group_select.hip", "row_remove.hip", "exact_score.hip", "aqe.hip",
-           "synth.hip", "l2_metric.hip", "refine.hip", "hamming.hip", "hamming_range.hip", "lsh.hip", "pq.hip", "pq_train.hip", "pq_wide.hip", "pq_remove.hip", "dense.hip", "diffusion.hip", "whiten.hip", "scatter.hip", "desc_tail.hip", "kr_rerank.hip"]
+           "synth.hip", "l2_metric.hip", "refine.hip", "hamming.hip", "hamming_range.hip", "components.hip", "lsh.hip", "pq.hip", "pq_train.hip", "pq_wide.hip", "pq_remove.hip", "dense.hip", "diffusion.hip", "whiten.hip", "scatter.hip", "desc_tail.hip", "kr_rerank.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-unused-result"]
 
 

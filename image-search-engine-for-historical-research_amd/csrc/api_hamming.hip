@@ -143,6 +143,47 @@ static int hr_fill(mi_hamming* h, const HrCall& c, const HrPlan& p, const int64_
   return MI_OK;
 }
 
+// ---- the self-join's ballots without its pairs (api_components.hip): the same plan, the same scan launch, nothing behind it
+static HrCall hr_self_call(int64_t row0, int64_t nrows, int32_t radius) {
+  HrCall c;
+  c.row0 = row0;
+  c.nq = nrows;
+  c.radius = (uint32_t)radius;
+  return c;
+}
+
+int hamming_self_check(const mi_hamming* h, int64_t row0, int64_t nrows, int32_t radius) {
+  REQUIRE(radius >= 0, "radius must be >= 0");
+  REQUIRE(row0 >= 0 && nrows >= 0, "row range outside the index");
+  REQUIRE(row0 <= h->n && nrows <= h->n - row0, "row range outside the index");
+  return MI_OK;
+}
+
+int hamming_self_plan(mi_hamming* h, int64_t row0, int64_t nrows, int64_t* qc) {
+  HrPlan p;
+  const int rc = hr_prepare(h, nrows, (row0 + 1) >> 6, &p);
+  *qc = p.qc;
+  return rc;
+}
+
+int hamming_self_scan(mi_hamming* h, int64_t row0, int64_t nrows, int32_t radius, int64_t qc, int64_t q0, HammingBallots* out,
+                      hipStream_t s) {
+  HrPlan p;
+  p.qc = qc;
+  p.nchunks = (nrows + qc - 1) / qc;
+  const HammingRangeArgs a = hr_args(h, hr_self_call(row0, nrows, radius), p, q0);
+  out->masks = a.masks;
+  out->b0 = a.b0;
+  out->nbl = std::max<int64_t>(0, (h->n + 63) / 64 - a.b0);     // 0: a chunk at the last rows, nothing above it to scan
+  out->qstride = a.qstride;
+  out->qrow0 = a.qrow0;
+  out->nq = a.nq;
+  if (out->nbl == 0) return MI_OK;
+  launch_hamming_range_scan(a, s);
+  HIPC(hipGetLastError());
+  return MI_OK;
+}
+
 // host output of a radius search or a self-join whose queries (and bitmap) are on the device already
 static int hr_host(mi_hamming* h, const HrCall& c, int64_t max_results, int64_t* out_lims, int64_t* out_idx, int32_t* out_dist) {
   hipStream_t s = h->stream;
@@ -420,11 +461,7 @@ int mi_hamming_self_range(mi_hamming* h, int64_t row0, int64_t nrows, int32_t ra
   if (nrows == 0) return MI_OK;
   const auto t0 = std::chrono::steady_clock::now();
   HIPC(hipSetDevice(h->device));
-  HrCall c;
-  c.row0 = row0;
-  c.nq = nrows;
-  c.radius = (uint32_t)radius;
-  const int rc = hr_host(h, c, max_results, out_lims, out_idx, out_dist);
+  const int rc = hr_host(h, hr_self_call(row0, nrows, radius), max_results, out_lims, out_idx, out_dist);
   if (out_seconds) *out_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return rc;
 }

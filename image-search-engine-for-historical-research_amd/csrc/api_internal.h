@@ -17,6 +17,8 @@
 //   api_remove.hip    row removal in place: keep-list, block-ordered move through a bounded staging area, invalidations
 //   api_hamming.hip   binary index (mi_hamming): packed codes, exact Hamming top-K through a bounded uint16 distance matrix;
 //                     radius search and self-join through one ballot per (block, query)
+//   api_components.hip  connected components (mi_components): union-find over pair lists, self-join CSR output or the Hamming
+//                     self-join's ballots (hamming_self_scan below), labels for mi_gallery_set_groups
 //   api_pq.hip        PQ index (mi_pq): codebooks and byte codes, exact ADC top-K through a bounded float32 distance matrix
 //   pq_flat.h         the host functions of both flat PQ indexes, templates over the handle (PqFlat<CodeT> below); api_pq.hip and
 //                     api_pq_wide.hip forward their entry points to them
@@ -448,6 +450,31 @@ struct mi_hamming {
   DeviceBuf<uint32_t> rseg{bufs};
   DeviceBuf<unsigned long long> rstage{bufs};
   DeviceBuf<int64_t> rlims{bufs};
+  std::mutex mu;
+};
+// ---- api_hamming.hip, for api_components.hip: the ballots of a self-join over rows [row0, row0 + nrows) chunk by chunk, with no
+// offsets, fill or order stage behind them.  The caller holds h->mu and has set the device.
+struct HammingBallots {
+  const unsigned long long* masks = nullptr;   // [nbl][qstride] in the index's own workspace, valid until its next scan
+  int64_t b0 = 0, nbl = 0;                     // first block scanned, blocks scanned (0: no row above the chunk, nothing launched)
+  int64_t qstride = 0, qrow0 = 0;              // words of a row of masks; the stored row that is query 0 of the chunk
+  int32_t nq = 0;                              // queries of the chunk
+};
+MI_INTERNAL int hamming_self_check(const mi_hamming* h, int64_t row0, int64_t nrows, int32_t radius);   // mi_hamming_self_range's checks
+// hr_prepare for the call: the workspace within "hamming_range_bytes", *qc queries per chunk
+MI_INTERNAL int hamming_self_plan(mi_hamming* h, int64_t row0, int64_t nrows, int64_t* qc);
+// the scan launch of the chunk that starts at query q0 (a multiple of qc), enqueued on s
+MI_INTERNAL int hamming_self_scan(mi_hamming* h, int64_t row0, int64_t nrows, int32_t radius, int64_t qc, int64_t q0,
+                                  HammingBallots* out, hipStream_t s);
+
+// connected components of the rows [0, n) (api_components.hip; kernels in components.hip)
+struct mi_components {
+  int device = 0;
+  int64_t n = 0;
+  DeviceBufSet bufs;
+  DeviceBuf<int32_t> parent{bufs};                 // [n] exactly: the forest, flat between calls (every entry a root)
+  DeviceBuf<unsigned long long> word{bufs};        // the flag of an id check / the count of roots (256 bytes)
+  hipStream_t stream = nullptr;
   std::mutex mu;
 };
 

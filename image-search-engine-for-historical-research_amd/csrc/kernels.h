@@ -388,6 +388,22 @@ void launch_hamming_range_fill(const HammingRangeArgs& a, hipStream_t stream);
 void launch_hamming_range_order(const HammingRangeArgs& a, int64_t row_offset, int64_t* out_idx, int32_t* out_dist,
                                 hipStream_t stream);
 
+// components.hip -- connected components of the rows [0, n) (api_components.hip): a union-find forest parent [n] int32 with
+// parent[v] <= v, a root hooked only under a smaller root by compare-and-swap, so the label of a component is its smallest row
+// whatever the order of the edges.  Ids are checked before a union launch; flatten runs behind the union launches of a call
+void launch_components_init(int32_t* parent, int64_t n, hipStream_t stream);                     // parent[v] = v
+// a, b (b may be NULL) [m]: an id outside [0, n) raises *flag
+void launch_components_check(const int64_t* a, const int64_t* b, int64_t m, int64_t n, uint32_t* flag, hipStream_t stream);
+void launch_components_pairs(int32_t* parent, const int64_t* i, const int64_t* j, int64_t m, hipStream_t stream);
+// hit idx[t], lims[q] <= t < lims[q + 1], unites row0 + q with idx[t]; total = lims[nq]
+void launch_components_csr(int32_t* parent, int64_t row0, const int64_t* lims, const int64_t* idx, int64_t nq, int64_t total,
+                           hipStream_t stream);
+// masks [nbl][qstride] of a self-join chunk (HammingRangeArgs::masks): bit l of masks[bl][q] unites qrow0 + q with (b0 + bl) 64 + l
+void launch_components_ballots(int32_t* parent, const unsigned long long* masks, int64_t b0, int64_t nbl, int64_t qstride,
+                               int64_t qrow0, int32_t nq, hipStream_t stream);
+void launch_components_flatten(int32_t* parent, int64_t n, hipStream_t stream);                  // parent[v] = root(v)
+void launch_components_count(const int32_t* parent, int64_t n, unsigned long long* count, hipStream_t stream);   // *count += roots
+
 // lsh.hip -- LSH codes (api_lsh.hip): bit j of row i = (sum_k double(x[i][k]) R[j][k] >= thr[j]) (thr NULL: 0), f64 MFMA with the
 // comparison and the packing in the epilogue.  out != NULL: rows of nbits / 8 bytes at out_rs; else the words of rows dst_row0 ..
 // dst_row0 + n of a binary gallery of nbits-bit codes (hamming.hip's layout)

@@ -614,6 +614,49 @@ int mi_hamming_self_range(mi_hamming* h, int64_t row0, int64_t nrows, int32_t ra
                           int64_t* out_idx, int32_t* out_dist, double* out_seconds);
 int mi_hamming_destroy(mi_hamming* h); /* NULL is MI_OK */
 
+/* ---- Connected components: near-duplicate GROUPS from self-join hits.  DESIGN.md 5.13d.  The self-joins (mi_range_search on
+ * stored rows, mi_minkowski_self_range, mi_hamming_self_range) return pairs; mi_gallery_set_groups wants one label per row.  This
+ * handle closes "a ~ b and b ~ c, so a, b and c are one item" on the device: a union-find forest of n int32 entries, 4 bytes of
+ * device memory per row, in which a root is only ever hooked under a smaller root.  Hence
+ *   labels    out_labels[v] is the SMALLEST row of v's component (a row of its own is its own label); they are a function of the
+ *             SET of edges added since creation or the last reset -- the order of the edges, their split into calls, the memspace
+ *             and the source (pairs, CSR or ballots) make no difference, and neither does the order in which the device ran.
+ * Ids.  Every id is a local row in [0, n); anything else is MI_ERR_INVALID.  Host arrays are checked on the host before a device
+ * is touched, device arrays by a flag kernel before anything is united: a failed call leaves the components as they were.
+ * i == j is allowed and does nothing; so does an edge given twice.  m == 0 or nq == 0 is MI_OK.
+ * All calls are synchronous: they return when the work is done.  A handle is ONE device's; calls on one handle are serialised.
+ * Integer and exact: no tolerance, no flag, no fallback.
+ * Out of scope: pair-free paths for the inner-product and the Minkowski joins (they feed mi_components_add_csr from the host CSR
+ * they return already); removing edges (reset and add again); sharded galleries, indexes with row_offset != 0, n > INT32_MAX;
+ * saving a handle.
+ * mi_components_create: 0 <= n <= INT32_MAX, else MI_ERR_INVALID before a device is touched; every row a component of its own.
+ * mi_components_reset: every row a component of its own again. */
+typedef struct mi_components mi_components; /* opaque; 4 bytes of device memory per row */
+int mi_components_create(int64_t n, int device, mi_components** out);
+int mi_components_reset(mi_components* h);
+/* m edges (i[e], j[e]); both arrays MI_HOST or both MI_DEVICE (device arrays complete when the call is made). */
+int mi_components_add_pairs(mi_components* h, const int64_t* i, const int64_t* j, int64_t m, int memspace);
+/* The CSR output of a self-join whose queries are stored rows: query q is row row0 + q, 0 <= q < nq, and its hits are
+ * idx[lims[q] .. lims[q+1]) -- what mi_range_search, mi_minkowski_self_range, mi_hamming_self_range and their Python forms return
+ * for such queries (of an index with row_offset 0).  A row listed among its own hits is harmless.  lims [nq + 1] must be
+ * non-decreasing with lims[0] == 0, and row0 .. row0 + nq must lie in [0, n]: otherwise MI_ERR_INVALID.  lims and idx are both
+ * MI_HOST or both MI_DEVICE; device offsets are read back (8 (nq + 1) bytes), the hits stay where they are. */
+int mi_components_add_csr(mi_components* h, int64_t row0, const int64_t* lims, const int64_t* idx, int64_t nq, int memspace);
+/* Unites every pair (row0 + q, j), 0 <= q < nrows, j > row0 + q, of Hamming distance <= radius: exactly the pairs
+ * mi_hamming_self_range(b, row0, nrows, radius, ...) reports -- but no pair is staged, counted, ordered or returned.  Per chunk of
+ * queries the self-join's scan launch leaves its 64-bit ballots in the index's own workspace (chunked as there, global option
+ * "hamming_range_bytes" included) and a union launch reads them; the offsets, fill and order stages do not run.  b must hold
+ * exactly n rows on the handle's device with row_offset 0, else MI_ERR_INVALID; argument checks otherwise those of
+ * mi_hamming_self_range; nrows == 0 is MI_OK.  Runs on the index's stream under the index's one-stream contract, and returns when
+ * it is done. */
+int mi_components_add_hamming_self(mi_components* h, mi_hamming* b, int64_t row0, int64_t nrows, int32_t radius);
+/* out_labels [n] int32 in `memspace` (MI_HOST or MI_DEVICE), ready for mi_gallery_set_groups; out_groups (may be NULL) receives
+ * the number of components.  The forest is kept flat between calls, so this is a copy (and a count).  The call does not end the
+ * handle: more edges may be added afterwards. */
+int mi_components_labels(mi_components* h, int32_t* out_labels, int memspace, int64_t* out_groups);
+int mi_components_info(const mi_components* h, int64_t* n, int32_t* device);
+int mi_components_destroy(mi_components* h); /* NULL is MI_OK */
+
 /* ---- LSH codes: float descriptors -> packed sign codes of their projections, the first half of faiss IndexLSH(d, nbits)
  * (matching_LSH_faiss, src/utils/nnsearch.py:734-745); the second half is the Hamming search above.  DESIGN.md 5.13b.
  *   bit j of row i  =  ( sum_k double(x[i][k]) * R[j][k]  >=  t[j] ),       t == NULL: every threshold 0
